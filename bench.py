@@ -148,7 +148,10 @@ def main():
     ap.add_argument("--nv", type=int, default=0, help="override (debugging only; invalidates the metric)")
     ap.add_argument("--config4-resolution", type=int, default=0, help="override of the N = 8 companion job (tests only; invalidates it)")
     ap.add_argument("--config4-nv", type=int, default=0, help="override of the N = 8 companion job (tests only; invalidates it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the voxels of the last timed step to DIR/*.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
     import torch  # first: the HIP runtime (and RCCL) torch bundles must be the copies that get loaded
@@ -201,7 +204,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def time_workload(name, res, nv, steps, warmup, loaded=None):
+    def time_workload(name, res, nv, steps, warmup, loaded=None, dump=None):
         kw, text = {}, None
         if loaded is not None:     # a real asset (N = 1): (verts, materials, textures, resolution, keywords, description)
             verts, mat, textures, res, kw, text = loaded
@@ -211,11 +214,10 @@ def main():
             verts = meshes.uv_sphere(nv)
             dv.set_triangles(verts)
         if n == 1:
-            step = lambda **t: (dv.voxelize(res, read=False, **kw, **t), None)   # noqa: E731
+            step = lambda **t: (dv.voxelize(res, read=False, **kw, **t), None, None)   # noqa: E731
         else:
             def step(**t):
-                count, counts, cuts = dv.voxelize_sharded(comm, res, read=False, **t)
-                return count, counts
+                return dv.voxelize_sharded(comm, res, read=False, **t)
         for _ in range(warmup):
             step()
         names = ("bounds_ms", "expand_ms", "voxelize_ms", "scan_ms", "resolve_ms", "total_ms", "plan_ms", "collective_ms")
@@ -223,9 +225,11 @@ def main():
         t0 = time.perf_counter()
         count = 0
         for _ in range(steps):   # the timed region: the steps and nothing else
-            count, counts = step()
+            count, counts, cuts = step()
         barrier()
         elapsed = time.perf_counter() - t0
+        if dump:   # before the steps below overwrite the last timed step's records
+            dump_outputs(dump, dv.read_voxels(), rank, n, counts, cuts)
         total_voxels, max_elapsed = slabs.reduce_job(dist, count, elapsed,
                                                       device="cuda" if (dist is not None and args.backend == "nccl") else None)
         # the clip kernel's duration in the timed steps (two hipEvents on the kernel's own dispatch, recorded in every step: read
@@ -268,7 +272,7 @@ def main():
     if n == 1 and not (args.resolution or args.nv) and workloads.asset_path("dragon"):
         loaded = workloads.load("asset:dragon")      # BASELINE configs[2] names this asset: it is the headline when present
         name = "asset:dragon"
-    main_run = time_workload(name, res, nv, args.steps, args.warmup, loaded)
+    main_run = time_workload(name, res, nv, args.steps, args.warmup, loaded, dump=args.dump_outputs)
     routes = None
     if n == 1 and not args.no_routes and not (args.resolution or args.nv):
         names = list(workloads.BENCH_ROUTES)
@@ -306,14 +310,7 @@ def main():
         if strong is not None:
             out["strong_scaling_same_job"] = strong_entry(strong, main_run, n)
         if companion:
-            sec = companion["seconds_per_step"]
-            out["config4"] = {
-                "workload": WORKLOAD_TEXT["config4"].format(nv=companion["nv"], T=companion["T"], res=companion["res"], n=n),
-                "metric": f"Mvoxels/sec at {companion['res']}^3 grid", "value": round(companion["voxels"] / sec / 1e6, 2),
-                "mtris_per_s": round(companion["T"] / sec / 1e6, 2), "ms_per_step": round(sec * 1e3, 4),
-                "voxels": companion["voxels"], "stages_ms_rank0": {k: round(v, 4) for k, v in companion["stages_ms"].items()},
-                "strong_scaling_same_job": strong_entry(companion["strong"], companion, n),
-                "answers": "BASELINE.json north_star '>= 6x at 8 GPUs': strong_scaling_same_job.speedup of this job (DESIGN.md section 5)"}
+            out["config4"] = config4_entry(companion, n)
         emit(out)
     dv.close()
     if comm is not None:
@@ -441,6 +438,42 @@ def strong_entry(strong, run, n):
     return {"one_gpu_ms": round(strong["seconds"] * 1e3, 4), "n_gpu_ms": round(t_n * 1e3, 4), "speedup": round(strong["seconds"] / t_n, 3),
             "efficiency": round(strong["seconds"] / t_n / n, 3), "voxels_match": strong["voxels"] == run["voxels"],
             "what": f"the job's {n} planned z-slabs one after the other on rank 0's GPU (plan + slabs, median of 3) / the {n}-GPU step"}
+
+
+def config4_entry(companion, n):
+    """The N = 8 line's BASELINE configs[4] companion job (a time_workload() run with `strong` = same_job_on_one_gpu())."""
+    sec = companion["seconds_per_step"]
+    return {"workload": WORKLOAD_TEXT["config4"].format(nv=companion["nv"], T=companion["T"], res=companion["res"], n=n),
+            "metric": f"Mvoxels/sec at {companion['res']}^3 grid", "value": round(companion["voxels"] / sec / 1e6, 2),
+            "mtris_per_s": round(companion["T"] / sec / 1e6, 2), "ms_per_step": round(sec * 1e3, 4),
+            "voxels": companion["voxels"], "stages_ms_rank0": {k: round(v, 4) for k, v in companion["stages_ms"].items()},
+            "strong_scaling_same_job": strong_entry(companion["strong"], companion, n),
+            "answers": "BASELINE.json north_star '>= 6x at 8 GPUs': strong_scaling_same_job.speedup of this job (DESIGN.md section 5)"}
+
+
+DUMP_ROWS = 1 << 20        # voxels written by --dump-outputs over all ranks: 32 MiB of float64, under the 64 MB the dump may take
+DUMP_SEED = 0
+
+
+def dump_outputs(directory, voxels, rank, n, counts=None, cuts=None):
+    """--dump-outputs: what a caller of the timed path receives from its last step, so that two builds can be compared output for
+    output on the same arguments.  voxels: this rank's uint32 [V, 4] records (x, y, z, argb) in the order the device left them
+    (unspecified), put in canonical order (z, y, x) and written as float64 (exact for every uint32) to voxels.npy
+    (voxels_rank<r>.npy for N > 1).  Above DUMP_ROWS / N records, a fixed seeded sample of them (in canonical order) is written;
+    voxel_count.npy holds V.  N > 1: rank 0 also writes voxel_counts.npy (every rank's V) and z_cuts.npy (the slab cuts)."""
+    import numpy as np
+    from obj2voxel_amd import meshes
+    os.makedirs(directory, exist_ok=True)
+    suffix = "" if n == 1 else f"_rank{rank}"
+    vox = meshes.sorted_voxels(voxels)
+    keep = DUMP_ROWS // n
+    if len(vox) > keep:
+        vox = vox[np.sort(np.random.default_rng(DUMP_SEED).choice(len(vox), keep, replace=False))]
+    np.save(os.path.join(directory, f"voxels{suffix}.npy"), vox.astype(np.float64))
+    np.save(os.path.join(directory, f"voxel_count{suffix}.npy"), np.array([len(voxels)], dtype=np.float64))
+    if n > 1 and rank == 0:
+        np.save(os.path.join(directory, "voxel_counts.npy"), np.asarray(counts, dtype=np.float64))
+        np.save(os.path.join(directory, "z_cuts.npy"), np.asarray(cuts, dtype=np.float64))
 
 
 def upload_comparison(verts, dv, dist, backend, rank, barrier):

@@ -31,7 +31,10 @@ def test_workload_series():
 
 
 class _Comm:
-    kind, world = "rccl", 2
+    kind = "rccl"
+
+    def __init__(self, world=2):
+        self.world = world
 
 
 def _line(n, stats, name="config2", res=1024, nv=467, comm=None):
@@ -112,7 +115,7 @@ def _full_line(n=1):
     """A line as heavy as the real one: routes, stages, capi_wall, published_workload, a cpu_baseline with every diagnostic."""
     cur = json.load(open(bench.PROFILE_SUMMARY))
     stats = dict(STATS, **{k: v for k, v in cur["workload_stats"].items() if not k.startswith("_")})
-    out = _line(n, stats, comm=_Comm() if n > 1 else None, **({"name": "weak", "res": 2896, "nv": 1321} if n > 1 else {}))
+    out = _line(n, stats, comm=_Comm(n) if n > 1 else None, **({"name": "weak", "res": 2896, "nv": 1321} if n > 1 else {}))
     out["routes"] = [{"workload": f"route{i}", "what": "x" * 200, "kernels_ms": {f"k{j}": 0.1 for j in range(30)}} for i in range(8)]
     out["capi_wall"] = {"ms": 4.1, "ms_all": [4.1] * 8, "what": "y" * 300}
     out["published_workload"] = {"workload": "z" * 300, "later_calls_s": [0.03] * 4}
@@ -127,9 +130,9 @@ def _full_line(n=1):
         se = bench.strong_entry({"seconds": 4.0e-3, "voxels": stats["voxels"] * n, "cuts": list(range(n + 1))},
                                 {"seconds_per_step": 0.6e-3, "voxels": stats["voxels"] * n}, n)
         out["strong_scaling_same_job"] = se
-        out["config4"] = {"workload": bench.WORKLOAD_TEXT["config4"].format(nv=3536, T=49999040, res=4096, n=n), "metric": "Mvoxels/sec at 4096^3 grid",
-                          "value": 60000.0, "mtris_per_s": 30000.0, "ms_per_step": 1.3, "voxels": 79000000, "stages_ms_rank0": dict(STAGES),
-                          "strong_scaling_same_job": se, "answers": "w" * 200}
+        companion = {"nv": 3536, "T": 49999040, "res": 4096, "voxels": 79000000, "seconds_per_step": 1.3e-3, "stages_ms": dict(STAGES),
+                     "strong": {"seconds": 9.0e-3, "voxels": 79000000, "cuts": list(range(n + 1))}}
+        out["config4"] = bench.config4_entry(companion, n)
         out["config"]["upload"] = {"bytes": 1, "what": "v" * 200}
     return out
 
@@ -160,9 +163,13 @@ def test_stdout_line_of_an_eight_gpu_run_is_compact_and_carries_both_curves():
     s = bench.compact_line(out)
     line = json.loads(s)
     assert len(s) < 4096 and line["n_gpus"] == 8 and line["scaling"] == "weak"
-    assert line["config"]["collectives"]["rccl_world_size"] == 2 or line["config"]["collectives"]["rccl_world_size"] == 8
+    assert line["config"]["parallelism"] == "zslab8" and line["config"]["collectives"]["world"] == 8
+    assert line["config"]["collectives"]["rccl_world_size"] == 8
     assert line["strong_scaling_same_job"]["speedup"] > 0 and line["config4"]["strong_scaling_same_job"]["speedup"] > 0
+    c4 = line["config4"]
+    assert c4["value"] > 0 and c4["voxels"] > 0 and c4["strong_scaling_same_job"]["voxels_match"] is True and "4096^3" in c4["workload"]
     assert "upload" not in line["config"] and "answers" not in line["config4"]
+    assert out["config4"]["answers"] and out["config"]["upload"]    # (in the details)
 
 
 def test_stdout_line_budget_sheds_text_then_optional_keys(monkeypatch):
@@ -197,6 +204,32 @@ def test_same_job_strong_scaling_entry():
     e = bench.strong_entry({"seconds": 20.0e-3, "voxels": 79_000_000, "cuts": list(range(9))}, run, 8)
     assert e["speedup"] == 8.0 and e["efficiency"] == 1.0 and e["voxels_match"] is True and e["one_gpu_ms"] == 20.0 and e["n_gpu_ms"] == 2.5
     assert bench.strong_entry(None, run, 8) is None
+
+
+def test_dump_outputs_canonical_exact_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: the records in canonical order as float64 (exact for every uint32, argb included), the count beside them;
+    above DUMP_ROWS / N records the same seeded sample every time; N > 1 adds every rank's count and the cuts."""
+    import numpy as np
+    from obj2voxel_amd import meshes
+    rng = np.random.default_rng(5)
+    cells = rng.choice(64 ** 3, 5000, replace=False)
+    vox = np.stack([cells % 64, cells // 64 % 64, cells // 4096, rng.integers(0, 2 ** 32, 5000)], axis=1).astype(np.uint32)
+    bench.dump_outputs(str(tmp_path / "a"), vox, 0, 1)
+    whole = np.load(tmp_path / "a" / "voxels.npy")
+    assert whole.dtype == np.float64 and np.array_equal(whole.astype(np.uint32), meshes.sorted_voxels(vox))
+    assert np.array_equal(whole, meshes.sorted_voxels(vox).astype(np.float64)) and whole[:, 3].max() > 2 ** 24
+    assert np.load(tmp_path / "a" / "voxel_count.npy").tolist() == [5000]
+    monkeypatch.setattr(bench, "DUMP_ROWS", 2000)
+    for d in ("b", "c"):   # the input order the device happened to leave does not matter
+        bench.dump_outputs(str(tmp_path / d), vox[rng.permutation(len(vox))], 1, 2, counts=[4000, 5000], cuts=[0, 30, 64])
+    b, c = np.load(tmp_path / "b" / "voxels_rank1.npy"), np.load(tmp_path / "c" / "voxels_rank1.npy")
+    assert b.shape == (1000, 4) and np.array_equal(b, c)
+    assert np.array_equal(meshes.sorted_voxels(b.astype(np.uint32)), b.astype(np.uint32))
+    assert set(map(tuple, b.astype(np.uint32))) <= set(map(tuple, vox))
+    assert np.load(tmp_path / "b" / "voxel_count_rank1.npy").tolist() == [5000]
+    assert not (tmp_path / "b" / "voxel_counts.npy").exists()          # (rank 0 writes those)
+    bench.dump_outputs(str(tmp_path / "b"), vox[:4000], 0, 2, counts=[4000, 5000], cuts=[0, 30, 64])
+    assert np.load(tmp_path / "b" / "voxel_counts.npy").tolist() == [4000, 5000] and np.load(tmp_path / "b" / "z_cuts.npy").tolist() == [0, 30, 64]
 
 
 def test_route_entry_contract():

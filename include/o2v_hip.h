@@ -180,7 +180,10 @@ int o2v_hip_plan_slabs(o2v_hip_ctx *ctx, const o2v_hip_params *params, uint32_t 
 /* The thickest z-slab (in output layers, a multiple of 4 unless it is the whole grid) whose dense grids fit the device memory
  * that is free right now (plus what the context already holds), leaving room for the work buffers: a voxelization of
  * `params` can be run as ceil(resolution / layers) calls with consecutive slabs.  obj2voxel_voxelize() does that by itself
- * (the reference's sparse VoxelMap has no such limit: src/util.hpp:179-208); 0 layers = not even one brick layer fits. */
+ * (the reference's sparse VoxelMap has no such limit: src/util.hpp:179-208); 0 layers = not even one brick layer fits.
+ * A slab is also never taller than one pass' box may be (65 535 samples): when the mesh's voxel bounding box is taller than
+ * that in z, the result is at most (65535 / supersampling) & ~3 layers (65 532, or 32 764 at 2x supersampling), however
+ * much memory is free. */
 int o2v_hip_max_slab_layers(o2v_hip_ctx *ctx, const o2v_hip_params *params, uint32_t *out_layers);
 
 /* Copies voxels [first, first+count) of the last result to host memory as (x, y, z, argb) uint32 quadruples,
@@ -274,7 +277,8 @@ const char *o2v_hip_comm_last_error(const o2v_hip_comm *comm);
  * (z_begin / z_end are ignored).  Plans work-balanced slabs from the sharded passes, voxelizes this rank's slab and
  * gathers the slab counts.  out_count: this rank's voxels (read them with o2v_hip_read_voxels); out_counts_all (optional):
  * world entries; out_cuts (optional): world + 1 ascending z cuts, rank r owns [out_cuts[r], out_cuts[r + 1]).
- * With a world of 1 this is o2v_hip_voxelize.  * Time limits: ncclCommInitRank and the run's first collective are given O2V_COMM_TIMEOUT_S seconds (120) for the other ranks to
+ * With a world of 1 this is o2v_hip_voxelize.
+ * Time limits: ncclCommInitRank and the run's first collective are given O2V_COMM_TIMEOUT_S seconds (120) for the other ranks to
  * arrive; after that the call fails with a message naming the rank.  A collective that timed out stays queued on the device:
  * the context and the communicator are then unusable (every later call on them fails or would wait for ever), o2v_hip_destroy
  * and o2v_hip_comm_destroy return without waiting for the device (the communicator is aborted, the context's device memory is

@@ -643,7 +643,13 @@ obj2voxel_error_t voxelize_on_device(obj2voxel_instance &inst, Session *session,
         }
     };
 
-    if (session->group) {
+    // A pass handles a box of at most 65 535 samples per axis (voxel coordinates travel in 16-bit fields relative to it,
+    // include/o2v_hip.h), where the reference carries u32 coordinates (src/util.hpp:185-196).  The sharded voxelization of a
+    // group has no x / y tiles (its slab plan takes no grid above 65 535 samples): such a grid is voxelized on the group's
+    // first device - which holds every triangle, o2v_hip_group_set_triangles - the way one device does it below.
+    const uint32_t ss = params.supersampling ? params.supersampling : 1u;
+    const bool group_fits = (uint64_t) params.resolution * ss <= 65535u;
+    if (session->group && group_fits) {
         if (o2v_hip_group_voxelize(session->group, &params, counts.data(), nullptr) != O2V_HIP_OK)
             return device_error("device voxelization failed");
         ms_device = clock.lap_ms();
@@ -653,16 +659,23 @@ obj2voxel_error_t voxelize_on_device(obj2voxel_instance &inst, Session *session,
         ms_sink = clock.lap_ms();
     }
     else {
-        // One GPU.  The dense grids of the whole resolution may not fit the device (4 + 8 bytes per cell: 8192^3, the reference
-        // README's showcase resolution, would take 6.6 TB), where the reference's sparse VoxelMap just grows (util.hpp:179-208):
+        // One GPU (or, for a grid finer than one pass' box, the first device of a group).  The dense grids of the whole resolution
+        // may not fit the device (4 + 8 bytes per cell: 8192^3, the reference README's showcase resolution, would take 6.6 TB),
+        // where the reference's sparse VoxelMap just grows (util.hpp:179-208):
         // the grid is then voxelized as consecutive z-slabs as thick as the free memory allows - the reference's chunk
         // mechanism again (obj2voxel.cpp:226-243, voxelization.cpp:440-444) - each slab's records going to the sink before the
         // next slab starts.  The mesh bounds and the z extents of the triangle blocks (which let a slab skip the blocks it
         // cannot meet) are computed once, by the slab plan.
-        // A pass handles a box of at most 65 535 samples per axis (voxel coordinates travel in 16-bit fields relative to it,
-        // include/o2v_hip.h), where the reference carries u32 coordinates (src/util.hpp:185-196): a finer grid is cut into x / y
-        // tiles the same way - every output voxel belongs to exactly one tile.
-        const uint32_t ss = params.supersampling ? params.supersampling : 1u;
+        // A grid finer than one pass' box is cut into x / y tiles the same way - every output voxel belongs to exactly one tile -
+        // and o2v_hip_max_slab_layers keeps a slab within the box in z.
+        o2v_hip_ctx *ctx = session->rank_ctx(0);
+        auto pass_error = [&](const char *what) {  // (the message of this context: a group's own is that of its last group call)
+            log_message(OBJ2VOXEL_LOG_LEVEL_ERROR, std::string(what) + ": " + o2v_hip_last_error(ctx));
+            return OBJ2VOXEL_ERR_DEVICE;
+        };
+        if (session->group)
+            log_message(OBJ2VOXEL_LOG_LEVEL_DEBUG, "resolution " + std::to_string(params.resolution) + " x " + std::to_string(ss) +
+                                                       " samples: the grid is voxelized on one device (device " + std::to_string(devices[0]) + ")");
         const uint32_t tile = (65535u / ss) & ~3u;
         const bool tiled = params.resolution > tile;
         if (tiled)
@@ -676,7 +689,7 @@ obj2voxel_error_t voxelize_on_device(obj2voxel_instance &inst, Session *session,
                     params.y_end = std::min<uint64_t>(params.resolution, (uint64_t) y0 + tile);
                 }
                 uint32_t layers = 0;
-                if (o2v_hip_max_slab_layers(session->ctx, &params, &layers) != O2V_HIP_OK) return device_error("querying device memory failed");
+                if (o2v_hip_max_slab_layers(ctx, &params, &layers) != O2V_HIP_OK) return pass_error("querying device memory failed");
                 if (const char *force = std::getenv("O2V_TEST_SLAB_LAYERS")) layers = std::min<uint32_t>(layers, (uint32_t) std::atoi(force));  // test hook
                 if (layers == 0) {
                     log_message(OBJ2VOXEL_LOG_LEVEL_ERROR, "resolution " + std::to_string(params.resolution) + ": not even one 4-layer slab of the dense grid fits the device memory");
@@ -688,14 +701,14 @@ obj2voxel_error_t voxelize_on_device(obj2voxel_instance &inst, Session *session,
                                                                std::to_string(layers) + " layers");
                     uint32_t cuts[2];
                     float bounds[6];
-                    if (o2v_hip_plan_slabs(session->ctx, &params, 1, cuts, bounds) != O2V_HIP_OK) return device_error("device slab plan failed");
+                    if (o2v_hip_plan_slabs(ctx, &params, 1, cuts, bounds) != O2V_HIP_OK) return pass_error("device slab plan failed");
                     params.bounds_known = 1;
                     for (int i = 0; i < 6; ++i) params.bounds[i] = bounds[i];
                 }
                 for (uint32_t z0 = 0; z0 < params.resolution; z0 += layers) {
                     params.z_begin = layers < params.resolution ? z0 : 0;
                     params.z_end = layers < params.resolution ? std::min<uint32_t>(params.resolution, z0 + layers) : 0;
-                    if (o2v_hip_voxelize(session->ctx, &params, &counts[0]) != O2V_HIP_OK) return device_error("device voxelization failed");
+                    if (o2v_hip_voxelize(ctx, &params, &counts[0]) != O2V_HIP_OK) return pass_error("device voxelization failed");
                     ms_device += clock.lap_ms();
                     log_pipeline();
                     const obj2voxel_error_t rc_sink = drain_to_sink();

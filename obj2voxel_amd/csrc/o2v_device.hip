@@ -2011,7 +2011,13 @@ int o2v_hip_max_slab_layers(o2v_hip_ctx *ctx, const o2v_hip_params *params, uint
     const uint64_t layers = brick_layers * kBrickZ;
     // (the grids only span the mesh's box in z as well: if that many layers fit, the whole resolution is one slab)
     const uint64_t box_layers = box.empty ? 0ull : (uint64_t) (box.hi[2] - box.lo[2]) + kBrickZ;
-    *out_layers = (layers >= G || layers >= box_layers) ? (uint32_t) G : (uint32_t) layers;
+    uint64_t out = (layers >= G || layers >= box_layers) ? G : layers;
+    // ... and a pass' box is at most 65 535 samples tall, as it is wide (o2v_hip_voxelize): a mesh box taller than that is cut
+    // into slabs of at most this many layers, whatever the memory would hold (a multiple of 4, as the x / y tiles of
+    // obj2voxel_voxelize() are)
+    const uint64_t pass_layers = (65535u / ss_l) & ~3u;
+    if (!box.empty && (uint64_t) (box.hi[2] - box.lo[2]) * ss_l > 65535u) out = std::min(out, pass_layers);
+    *out_layers = (uint32_t) out;
     return O2V_HIP_OK;
 }
 

@@ -152,6 +152,47 @@ def diagonal_strip(n=400, width=6e-5, thickness=4e-5):
     return np.ascontiguousarray(v)
 
 
+def z_pole(n=300, width=3e-5, base=(0.0, 0.0), tilt=(2e-5, 1e-5)):
+    """A thin ribbon along z from z = 0 to z = 1, slightly wavy in x / y: the mesh of a pole or a cable, whose box is as tall as
+    the grid and a few voxels wide at a resolution near 100 000.  The centre line runs from (base, 0) to (base + tilt, 1); the
+    ribbon's width lies along the x = -y diagonal, so no triangle is axis-aligned.  Its segments alternate between one long
+    one (1 / n of the height: hundreds of voxels at such resolutions, the root / subdivision path) and eight short ones (1 / 40 of
+    a long one: below 16 voxels, the small-triangle path); 2 triangles per segment."""
+    long_dz = 1.0 / (n + n * 8 / 40.0)
+    steps = np.tile(np.array([long_dz] + [long_dz / 40.0] * 8), n)
+    z = np.concatenate([[0.0], np.cumsum(steps)])
+    z /= z[-1]  # (exactly 0 .. 1)
+    m = len(z)
+    i = np.arange(m)
+    half = 0.5 * width
+    # centre line with a wave of a quarter of the width, the ribbon's edges + / - half the width along (1, -1) / sqrt 2
+    cx = base[0] + tilt[0] * z + 0.25 * width * np.sin(i * 0.37)
+    cy = base[1] + tilt[1] * z + 0.25 * width * np.cos(i * 0.23)
+    e = half / np.sqrt(2.0)
+    dz = 0.1 * long_dz / 40.0 * np.sin(i * 1.3)  # (the edges' ends are not level either)
+    a = np.stack([cx - e, cy + e, np.clip(z + dz, 0.0, 1.0)], axis=1)
+    b = np.stack([cx + e, cy - e, np.clip(z - dz, 0.0, 1.0)], axis=1)
+    tris = []
+    for k in range(m - 1):
+        tris.append(np.concatenate([a[k], b[k], a[k + 1]]))
+        tris.append(np.concatenate([b[k], b[k + 1], a[k + 1]]))
+    return np.ascontiguousarray(np.asarray(tris, dtype=np.float32))
+
+
+def sliver(axis, length=1.0, width=3e-5):
+    """Two long thin triangles whose boxes span the whole mesh box (0 .. length) along `axis` (0, 1, 2 = x, y, z) and a few
+    voxels across at a resolution near 65 536: at such a resolution each is one leaf or root whose clamped extent along
+    `axis` fills the pass' box.  Neither is axis-aligned: they twist about the axis."""
+    p = np.array([[0.0, 0.0, 0.0],
+                  [length, 2.0 * width, 0.7 * width],
+                  [0.5 * length, 0.4 * width, 1.6 * width],
+                  [length, 0.3 * width, 2.2 * width]], dtype=np.float64)
+    perm = [(0, 1, 2), (1, 0, 2), (2, 1, 0)][axis]  # (the long coordinate goes to `axis`)
+    p = p[:, np.argsort(perm)]
+    v = np.stack([np.concatenate([p[0], p[1], p[2]]), np.concatenate([p[0], p[3], p[2]])])
+    return np.ascontiguousarray(v.astype(np.float32))
+
+
 def random_soup(T, seed=0, scale=0.2):
     """Random small triangles in the unit cube plus a few large diagonal ones (subdivision-heavy)."""
     rng = np.random.default_rng(seed)

@@ -58,6 +58,8 @@ typedef struct {
      * to the box (the reference carries u32, src/util.hpp:185-196).  A wider grid is voxelized tile by tile; every output voxel
      * belongs to exactly one tile, so the tiles' records concatenated are the whole grid's (obj2voxel_voxelize() does that). */
     uint32_t x_begin, x_end, y_begin, y_end;
+    /* O2V_HIP_FLAG_FILL_INTERIOR: the colour (0xAARRGGBB) of the interior voxels' records.  Unused without the flag. */
+    uint32_t fill_argb;
 } o2v_hip_params;
 
 /* o2v_hip_params::flags.
@@ -72,8 +74,29 @@ typedef struct {
  * Implies STAGE_TIMES.
  * STAGE_TIMES: records a HIP event before, between and behind the stages of a pass, for o2v_hip_timings' stage times and
  * total_ms.  Not the default because an event between two kernels is a command of its own in the queue and costs about 4 us
- * of device time (six of them: 3 % of the bench headline's step, profiles/r05/NOTES.md). */
-enum { O2V_HIP_FLAG_EXACT_CLIP = 1u, O2V_HIP_FLAG_KERNEL_TIMES = 2u, O2V_HIP_FLAG_STAGE_TIMES = 4u };
+ * of device time (six of them: 3 % of the bench headline's step, profiles/r05/NOTES.md).
+ * FILL_INTERIOR: solid voxelization.  The call returns the surface records it returns without the flag (the same multiset,
+ * first in the output), followed by one record (i, j, k, fill_argb) for every voxel of the pass box that is not a surface voxel
+ * and whose centre is inside by z-parity:
+ *   S = resolution x supersampling; each triangle's vertices are transformed to sample space as the pipeline does (affine_apply,
+ *   float32); a triangle with a non-finite coordinate contributes nothing.  The column of output voxel (i, j) is the vertical line
+ *   through P = (i ss + ss/2, j ss + ss/2).  A triangle covers the column if the exact signs of its edge functions
+ *   e(U, V, P) = (V.x - U.x)(P.y - U.y) - (V.y - U.y)(P.x - U.x) over V0->V1, V1->V2, V2->V0 (float32 vertex values, the sign
+ *   of the exact value) are all +1 or all -1; an exact zero takes the sign of the symbolic perturbation P + (eps, eps^2),
+ *   -sgn(V.y - U.y), or sgn(V.x - U.x) when V.y = U.y; an edge whose projected ends coincide has sign 0.  With one predicate
+ *   and one perturbation for all edges, a mesh whose every edge (pair of bit-identical sample-space vertices) is shared by an
+ *   even number of triangles covers every column an even number of times; vertical faces cover nothing.  A covering triangle
+ *   crosses the column at z = (w0 V0.z + w1 V1.z + w2 V2.z) / (w0 + w1 + w2) in double, op by op, left to right, without FMA,
+ *   with w0 = e(V1, V2, P), w1 = e(V2, V0, P), w2 = e(V0, V1, P) in double as written (the smallest vertex z if the denominator
+ *   is 0 or z is not finite), and toggles every voxel k >= k0 of the column, k0 the smallest k >= 0 with k ss + ss/2 > z.  A voxel
+ *   toggled an odd number of times is in the parity set.
+ * Interior voxels exist only within the pass box (the mesh's voxel bounding box within slab and tile); a crossing below a
+ * slab's first layer toggles from that layer up, a triangle whose lowest vertex lies at or above the slab's top is not looked
+ * at.  For a closed mesh that is its solid interior; for an open one, whatever the definition gives (voxels above an open sheet,
+ * up to the top of the box) - nothing is repaired.  Slabs and tiles split the set exactly as they split the surface.  The
+ * stage needs a bitmap of one bit per cell of the pass box and 16 bytes per interior record, and one pass may hold at most
+ * 2^32 - 16 records in all (o2v_hip_max_slab_layers counts both). */
+enum { O2V_HIP_FLAG_EXACT_CLIP = 1u, O2V_HIP_FLAG_KERNEL_TIMES = 2u, O2V_HIP_FLAG_STAGE_TIMES = 4u, O2V_HIP_FLAG_FILL_INTERIOR = 8u };
 
 /* Device times of the last o2v_hip_voxelize call.  voxelize_ms is measured in every call (two hipEvents that ride on the clip
  * kernel's own dispatch), passes and plan_ms likewise; the other stage times, total_ms and the collectives' times only in a call
@@ -98,6 +121,8 @@ typedef struct {
                             [1] unused (0), [2] every rank's z histogram of predicted work (2048 x u64) and the z extents of
                             its blocks (8 bytes per 256 triangles) in one all-gather - each rank adds the histograms up itself -
                             [3] unused (0), [4] slab voxel counts (all-gather, 8 bytes per rank) */
+    float fill_ms;       /* K6  solid fill (O2V_HIP_FLAG_FILL_INTERIOR): crossings, prefix XOR, surface removal, count, emission;
+                            measured like the other stage times (not part of total_ms) */
 } o2v_hip_timings;
 
 /* Work counters of the last o2v_hip_voxelize call. */
@@ -107,7 +132,7 @@ typedef struct {
     uint64_t tiles;       /* work tiles of <= 256 candidate voxels */
     uint64_t candidates;  /* (leaf, voxel) pairs examined */
     uint64_t hits;        /* (leaf, voxel) pairs with non-zero weight */
-    uint64_t voxels;      /* occupied output voxels */
+    uint64_t voxels;      /* occupied output voxels: every record of the call, interior voxels included */
     uint64_t grid_cells;  /* dense grid cells owned by this context (bricks of 4x4x4, padded) */
     uint64_t grid_bytes;  /* bytes of the dense grid allocation incl. the per-brick dirty flags */
     uint64_t bricks;      /* bricks of the slab */
@@ -123,6 +148,7 @@ typedef struct {
                              the voxels do not) */
     uint64_t bypassed_leaves; /* occupancy-only mode: those of `leaves` (and `tiles`) that have no Leaf / Tile record - root triangles
                                  of one tile, which the clip kernel stages from the vertex array itself */
+    uint64_t interior_voxels; /* O2V_HIP_FLAG_FILL_INTERIOR: the records behind the surface records (part of voxels); else 0 */
 } o2v_hip_stats;
 
 int o2v_hip_device_count(void);
@@ -201,6 +227,11 @@ void *o2v_hip_alloc_pinned_on(int device, size_t bytes);
 void o2v_hip_free_pinned(void *p);
 /* Releases the device session that obj2voxel_voxelize() keeps between calls (contexts, dense grids, staging memory). */
 void o2v_release_cached_device_memory(void);
+/* Solid voxelization through the public C API: with enabled != 0, obj2voxel_voxelize() fills the interior of the mesh with voxels
+ * of colour argb (0xAARRGGBB), O2V_HIP_FLAG_FILL_INTERIOR in every pass; every output receives them like any other voxel.
+ * Off by default. */
+struct obj2voxel_instance; /* include/obj2voxel.h */
+void o2v_set_fill(struct obj2voxel_instance *instance, int enabled, uint32_t argb);
 /* Device pointer to the same records (valid until the next voxelize/destroy). */
 int o2v_hip_voxels_device_ptr(o2v_hip_ctx *ctx, const uint32_t **out_ptr, uint64_t *out_count);
 

@@ -56,6 +56,11 @@ SIGNATURES = {
     "obj2voxel_voxelize": (C.c_ubyte, [C.c_void_p]),
 }
 
+# extension entry points of include/o2v_hip.h that take an obj2voxel_instance (not part of the reference's API)
+EXTENSIONS = {
+    "o2v_set_fill": (None, [C.c_void_p, C.c_int, C.c_uint32]),  # solid voxelization: enabled, ARGB of the interior voxels
+}
+
 _bound = None
 
 
@@ -63,7 +68,7 @@ def api():
     global _bound
     if _bound is None:
         L = lib()
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(EXTENSIONS.items()):
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args

@@ -117,6 +117,8 @@ struct obj2voxel_instance {
     uint32_t supersampling = 1;
     bool parallel = false;
     int unit_transform[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    bool fill = false;                 // o2v_set_fill (extension): solid voxelization, O2V_HIP_FLAG_FILL_INTERIOR in every pass
+    uint32_t fill_argb = 0xFFFFFFFFu;
 
     std::unique_ptr<VoxelSink> sink;
 
@@ -591,6 +593,10 @@ obj2voxel_error_t voxelize_on_device(obj2voxel_instance &inst, Session *session,
     for (int i = 0; i < 6; ++i) params.bounds[i] = inst.mesh_bounds[i];
     params.z_begin = params.z_end = 0;
     if (g_log_level >= OBJ2VOXEL_LOG_LEVEL_DEBUG) params.flags |= O2V_HIP_FLAG_STAGE_TIMES;  // (log_pipeline prints the device time)
+    if (inst.fill) {
+        params.flags |= O2V_HIP_FLAG_FILL_INTERIOR;
+        params.fill_argb = inst.fill_argb;
+    }
 
     const uint32_t n_ranks = session->ranks();
     std::vector<uint64_t> counts(n_ranks, 0);
@@ -648,7 +654,10 @@ obj2voxel_error_t voxelize_on_device(obj2voxel_instance &inst, Session *session,
     // group has no x / y tiles (its slab plan takes no grid above 65 535 samples): such a grid is voxelized on the group's
     // first device - which holds every triangle, o2v_hip_group_set_triangles - the way one device does it below.
     const uint32_t ss = params.supersampling ? params.supersampling : 1u;
-    const bool group_fits = (uint64_t) params.resolution * ss <= 65535u;
+    // (solid fill: the group's slabs are planned on surface work and are not cut further for memory, so a grid is filled there only
+    // if all of its cells' records fit one pass; a finer one takes the slab loop of one device below)
+    const uint64_t G = params.resolution;
+    const bool group_fits = G * ss <= 65535u && (!inst.fill || G * G * G < (1ull << 32) - 16u);
     if (session->group && group_fits) {
         if (o2v_hip_group_voxelize(session->group, &params, counts.data(), nullptr) != O2V_HIP_OK)
             return device_error("device voxelization failed");
@@ -676,7 +685,9 @@ obj2voxel_error_t voxelize_on_device(obj2voxel_instance &inst, Session *session,
         if (session->group)
             log_message(OBJ2VOXEL_LOG_LEVEL_DEBUG, "resolution " + std::to_string(params.resolution) + " x " + std::to_string(ss) +
                                                        " samples: the grid is voxelized on one device (device " + std::to_string(devices[0]) + ")");
-        const uint32_t tile = (65535u / ss) & ~3u;
+        // (solid fill: a pass' records - 16 bytes per interior voxel - must stay below 2^32, and one slab of four layers of a tile
+        // with them within the device's memory: 4 x 16384^2 cells, 17 GB of records at most; o2v_hip_max_slab_layers counts them)
+        const uint32_t tile = inst.fill ? std::min<uint32_t>((65535u / ss) & ~3u, 16384u) : (65535u / ss) & ~3u;
         const bool tiled = params.resolution > tile;
         if (tiled)
             log_message(OBJ2VOXEL_LOG_LEVEL_DEBUG, "resolution " + std::to_string(params.resolution) + ": x / y tiles of " + std::to_string(tile) + " voxels");
@@ -1178,6 +1189,14 @@ extern "C" void o2v_release_cached_device_memory(void)
         }
     }
     delete s;
+}
+
+// Extension (declared in include/o2v_hip.h): solid voxelization for the next obj2voxel_voxelize() of this instance.
+extern "C" void o2v_set_fill(obj2voxel_instance *instance, int enabled, uint32_t argb)
+{
+    O2V_ASSERT(instance != nullptr, "null instance");
+    instance->fill = enabled != 0;
+    instance->fill_argb = argb;
 }
 
 // texture accessors for o2v_io.cpp (OBJ loader creates textures it owns)

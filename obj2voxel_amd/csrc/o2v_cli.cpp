@@ -1,11 +1,13 @@
-// o2v_cli.cpp -- command line front end over the public C API (include/obj2voxel.h only), flag-compatible with the
-// subset of the reference CLI that does not depend on its absent argument parser:
+// o2v_cli.cpp -- command line front end over the public C API (include/obj2voxel.h, and the one extension of
+// include/o2v_hip.h it needs: o2v_set_fill), flag-compatible with the subset of the reference CLI that does not depend on its
+// absent argument parser:
 //   obj2voxel-amd INPUT_FILE OUTPUT_FILE -r RES [-s max|blend] [-p PERM] [-u] [-j THREADS] [-i FMT] [-o FMT]
-//                 [-t TEXTURE] [-v] [-h]
+//                 [-t TEXTURE] [--fill | --fill-color AARRGGBB] [-v] [-h]
 // Reference: src/main.cpp:115-202 (mainImpl: the API call sequence), :224-262 (axis permutation), :291-312 (flags).
 // -j is accepted for compatibility: worker threads are started and joined exactly like the reference does, but the
 // MI355X path does not dispatch work to them.
 #include "../../include/obj2voxel.h"
+#include "../../include/o2v_hip.h"
 
 #include <cctype>
 #include <algorithm>
@@ -29,6 +31,8 @@ void usage()
               "  -j, --threads N     worker threads to start (kept for compatibility; the GPU path ignores them)\n"
               "  -i FMT / -o FMT     explicit input (obj|stl) / output (ply|vl32|xyzrgb) format\n"
               "  -t TEXTURE          fallback texture (png) for faces with uv coordinates but no material\n"
+              "  --fill              solid model: fill the interior of the (closed) mesh with white voxels\n"
+              "  --fill-color C      the same with colour C, hexadecimal AARRGGBB (e.g. FF8000FF)\n"
               "  -v, --verbose       debug logging\n"
               "  -V, --version       version and build information\n"
               "  --80                accepted for compatibility (the reference prints its help 80 columns wide)\n"
@@ -61,7 +65,8 @@ int main(int argc, char **argv)
     std::vector<std::string> positional;
     std::string in_format, out_format, texture_file, perm = "xyz", strat = "max";
     unsigned resolution = 0, threads = 0;
-    bool supersample = false, verbose = false, have_res = false;
+    bool supersample = false, verbose = false, have_res = false, fill = false;
+    uint32_t fill_argb = 0xFFFFFFFFu;  // --fill: white
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto value = [&](const char *name) -> const char * {
@@ -82,6 +87,18 @@ int main(int argc, char **argv)
         else if (a == "-s" || a == "--strat") strat = value("-s");
         else if (a == "-p" || a == "--perm") perm = value("-p");
         else if (a == "-u" || a == "--super") supersample = true;
+        else if (a == "--fill") fill = true;
+        else if (a == "--fill-color") {
+            const char *v = value("--fill-color");
+            char *end = nullptr;
+            const unsigned long c = std::strtoul(v, &end, 16);
+            if (!*v || *end || std::strlen(v) > 8 || c > 0xfffffffful) {
+                std::fprintf(stderr, "--fill-color takes a hexadecimal AARRGGBB colour, not \"%s\"\n", v);
+                return 1;
+            }
+            fill = true;
+            fill_argb = (uint32_t) c;
+        }
         else if (a == "-j" || a == "--threads") threads = (unsigned) std::strtoul(value("-j"), nullptr, 10);
         else if (a == "-i") in_format = value("-i");
         else if (a == "-o") out_format = value("-o");
@@ -138,6 +155,7 @@ int main(int argc, char **argv)
     obj2voxel_set_resolution(instance, resolution);
     obj2voxel_set_supersampling(instance, supersample ? 2 : 1);
     obj2voxel_set_color_strategy(instance, strategy);
+    if (fill) o2v_set_fill(instance, 1, fill_argb);
     const obj2voxel_error_t result = obj2voxel_voxelize(instance);
     obj2voxel_stop_workers(instance);
     for (std::thread &w : workers) w.join();

@@ -22,6 +22,8 @@
 //                              (voxelization.cpp:56-63,466-468) and moveUvBufferIntoVoxels (:513-526) with
 //                              MAX / BLEND, then packs (x, y, z, argb) (obj2voxel.cpp:279-297);
 //       k_pick / k_emit_max    direct MAX path: winner colours of textured meshes; the 64-bit max grid -> records
+//   K6  k_fill_*               O2V_HIP_FLAG_FILL_INTERIOR: parity crossings per column of the pass box, prefix XOR along z,
+//                              the surface cells removed, interior records appended behind the surface records
 //   plan k_zhist               o2v_hip_plan_slabs: predicted hits per z layer -> work-balanced slabs for N GPUs
 // With the direct MAX path K1's counters reach the host while K2 runs, and only the stages that have work are enqueued
 // behind it.  N > 1 GPUs: o2v_hip_voxelize_sharded (bounds / work-histogram passes sharded over the ranks, RCCL).
@@ -62,6 +64,7 @@ namespace {
 #include "o2v_dev_k2_voxelize.hpp"
 #include "o2v_dev_k5_scan_scatter.hpp"
 #include "o2v_dev_k3_resolve.hpp"
+#include "o2v_dev_k6_fill.hpp"
 
 }  // namespace
 
@@ -223,6 +226,14 @@ struct o2v_hip_ctx {
     DevArray<uint8_t> d_dirty_max;      // ... its dirty-brick flags and list
     DevArray<uint32_t> d_dirty_list_max;
     hipEvent_t ev_k1 = nullptr;         // after K1: its counters decide which stages follow k_voxelize
+    // solid fill (O2V_HIP_FLAG_FILL_INTERIOR, K6): allocated by the first call that asks for it
+    DevArray<uint32_t> d_fill_bits;              // toggle bitmap of the pass box, [z-word][y][x]
+    DevArray<unsigned long long> d_fill_ends;    // per triangle: inclusive end of its (triangle, column) items
+    DevArray<unsigned long long> d_fill_blocks;  // per block of kBlock triangles: its items' offset
+    DevArray<unsigned long long> d_fill_chunks;  // per chunk of kFillChunk bitmap words: its records' offset
+    DevArray<unsigned long long> d_fill_ctr;     // [0] items, [1] interior voxels
+    PinnedArray<unsigned long long> h_fill_ctr;
+    hipEvent_t ev_fill[2] = {nullptr, nullptr};  // around the stage (O2V_HIP_FLAG_STAGE_TIMES)
     bool maxgrid_dirty = false;
     bool grid_dirty = false;
 
@@ -665,15 +676,9 @@ int launch_resolve(o2v_hip_ctx *ctx, const Params &p, bool use_uv, uint32_t reso
     return O2V_HIP_OK;
 }
 
-// The end of a pass: the counters to the host, the per-kernel times, and the next pass's counters zeroed behind this one.
-int finish_pass(o2v_hip_ctx *ctx)
+// The per-kernel times of the launches bracketed since the pass began (O2V_HIP_FLAG_KERNEL_TIMES), once the stream has drained.
+int collect_kernel_times(o2v_hip_ctx *ctx)
 {
-    hipStream_t s = ctx->stream;
-    // (a kernel that writes the counters into the page-locked copy instead of this copy command was measured: the same step time)
-    O2V_CHECK(hipMemcpyAsync(ctx->h_ctr.ptr, ctx->d_ctr.ptr, kPassCounterWords * 4u, hipMemcpyDeviceToHost, s));
-    // (polling the stream with hipStreamQuery instead was measured: the same step time - the runtime's wait spins already)
-    O2V_CHECK(hipStreamSynchronize(s));
-    O2V_CHECK(hipGetLastError());
     ctx->kernel_times.clear();
     for (size_t i = 0; i < ctx->ktimes_used; ++i) {
         const o2v_hip_ctx::KernelBracket &b = ctx->ktimes[i];
@@ -690,6 +695,19 @@ int finish_pass(o2v_hip_ctx *ctx)
         it->ms += ms;
         it->launches += 1;
     }
+    return O2V_HIP_OK;
+}
+
+// The end of a pass: the counters to the host, the per-kernel times, and the next pass's counters zeroed behind this one.
+int finish_pass(o2v_hip_ctx *ctx)
+{
+    hipStream_t s = ctx->stream;
+    // (a kernel that writes the counters into the page-locked copy instead of this copy command was measured: the same step time)
+    O2V_CHECK(hipMemcpyAsync(ctx->h_ctr.ptr, ctx->d_ctr.ptr, kPassCounterWords * 4u, hipMemcpyDeviceToHost, s));
+    // (polling the stream with hipStreamQuery instead was measured: the same step time - the runtime's wait spins already)
+    O2V_CHECK(hipStreamSynchronize(s));
+    O2V_CHECK(hipGetLastError());
+    if (const int rc = collect_kernel_times(ctx)) return rc;
     // the next pass's counters: zeroed now, behind this pass (its results are on the host)
     hipLaunchKernelGGL(k_init, dim3(1), dim3(64), 0, s, ctx->d_ctr.ptr, kPassCounterWords);
     O2V_CHECK(hipGetLastError());
@@ -802,6 +820,7 @@ int run_pass(o2v_hip_ctx *ctx, const Params &p, const Switches &sw, bool use_uv,
 // One o2v_hip_voxelize call: its pass geometry and routes (Params), and what its passes ask of the buffers.
 struct Run {
     Params p{};
+    GridBox box{};             // the pass box (output space)
     bool use_uv = false;
     uint64_t n_bricks = 0;
     uint32_t n_rounds = 0;     // subdivision rounds launched
@@ -850,6 +869,7 @@ int pass_geometry(o2v_hip_ctx *ctx, const o2v_hip_params *params, const Switches
     p.G = params->resolution;
     // the dense grids cover the mesh's voxel bounding box within the slab (grid_box)
     const GridBox box = grid_box(ctx, params, sw, ss, z0, z1);   // (within the x / y tile, if the call names one)
+    r.box = box;
     empty = box.empty;
     if (empty) return O2V_HIP_OK;
     // Voxel coordinates travel in 16-bit fields relative to the grid's origin (Params::so): what is limited is the box of one
@@ -1236,18 +1256,103 @@ int check_pass(o2v_hip_ctx *ctx, Run &r, bool &again)
     return O2V_HIP_OK;
 }
 
-// The results of the pass that stood: counts, stats, stage times and the transform.
-int publish(o2v_hip_ctx *ctx, const Run &r, uint64_t *out_voxel_count)
+// Whether the pass that stood emitted its records from the 64-bit max grid (direct_active() on the device): h.n_out records, else h.n_vox.
+bool pass_direct(const Params &p, const Counters &h) { return p.direct_max && (p.occupancy_only || h.n_nodes[0] <= h.n_root_leaves); }
+
+// K6, the solid fill (O2V_HIP_FLAG_FILL_INTERIOR), behind the n_surf surface records of the pass that stood: appends the
+// interior records of the pass box to d_out (o2v_dev_k6_fill.hpp) and returns their number in n_interior.
+int fill_stage(o2v_hip_ctx *ctx, const o2v_hip_params *params, const Run &r, uint64_t n_surf, uint64_t &n_interior)
+{
+    hipStream_t s = ctx->stream;
+    n_interior = 0;
+    FillBox b{};
+    b.x0 = r.box.lo[0];
+    b.y0 = r.box.lo[1];
+    b.z0 = r.box.lo[2];
+    b.nx = r.box.hi[0] - r.box.lo[0];
+    b.ny = r.box.hi[1] - r.box.lo[1];
+    b.nz = r.box.hi[2] - r.box.lo[2];
+    b.nzw = (b.nz + 31u) / 32u;
+    b.ss = params->supersampling ? params->supersampling : 1u;
+    b.argb = params->fill_argb;
+    b.n_cols = (uint64_t) b.nx * b.ny;
+    b.n_words = (uint64_t) b.nzw * b.n_cols;
+    const uint64_t T = ctx->n_tris, n_blocks = (T + kBlock - 1) / kBlock;
+    const uint64_t n_chunks = (b.n_words + kFillChunk - 1) / kFillChunk;
+    // (kMaxRecords: the grids' arrays of 32-bit capacity; the bitmap is indexed in 64 bits, its limit is the memory)
+    int rc;
+    if ((rc = grow(ctx, ctx->d_fill_bits, b.n_words, kNoLimit)) || (rc = grow(ctx, ctx->d_fill_ends, T, kNoLimit)) ||
+        (rc = grow(ctx, ctx->d_fill_blocks, n_blocks, kNoLimit)) || (rc = grow(ctx, ctx->d_fill_chunks, n_chunks, kNoLimit)) ||
+        (rc = grow(ctx, ctx->d_fill_ctr, 2)) || (rc = grow(ctx, ctx->h_fill_ctr, 2)))
+        return rc;
+    const bool timed = ctx->stage_events;
+    if (timed)
+        for (hipEvent_t &e : ctx->ev_fill)
+            if (!e) O2V_CHECK(create_timing_event(&e));
+    if (timed) O2V_CHECK(hipEventRecord(ctx->ev_fill[0], s));
+    Affine xf;
+    const float *x = ctx->h_ctr.ptr->xform;  // (k_setup's transform of this pass)
+    for (int i = 0; i < 3; ++i) xf.m[i] = {x[i * 3], x[i * 3 + 1], x[i * 3 + 2]};
+    xf.t = {x[9], x[10], x[11]};
+    O2V_CHECK(hipMemsetAsync(ctx->d_fill_bits.ptr, 0, b.n_words * sizeof(uint32_t), s));
+    O2V_CHECK(hipMemsetAsync(ctx->d_fill_ctr.ptr, 0, 2 * sizeof(unsigned long long), s));
+    const uint32_t persistent = (uint32_t) ctx->num_cus * 8u;
+    if (T) {
+        O2V_LAUNCH("k_fill_count", s, k_fill_count, dim3((uint32_t) n_blocks), dim3(kBlock), 0, s, ctx->d_verts.ptr, T, xf, b,
+                   ctx->d_fill_ends.ptr, ctx->d_fill_blocks.ptr);
+        O2V_LAUNCH("k_fill_scan_blocks", s, k_fill_scan_blocks, dim3(1), dim3(kBlock), 0, s, ctx->d_fill_blocks.ptr, n_blocks, ctx->d_fill_ctr.ptr);
+        O2V_LAUNCH("k_fill_offsets", s, k_fill_offsets, dim3((uint32_t) n_blocks), dim3(kBlock), 0, s, ctx->d_fill_ends.ptr, T, ctx->d_fill_blocks.ptr);
+        O2V_LAUNCH("k_fill_cross", s, k_fill_cross, dim3(persistent), dim3(kBlock), 0, s, ctx->d_verts.ptr, T, xf, b, ctx->d_fill_ends.ptr,
+                   ctx->d_fill_ctr.ptr, ctx->d_fill_bits.ptr);
+    }
+    O2V_LAUNCH("k_fill_prefix", s, k_fill_prefix, dim3((uint32_t) ((b.n_cols + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, ctx->d_fill_bits.ptr, b);
+    if (n_surf)
+        O2V_LAUNCH("k_fill_unmark", s, k_fill_unmark, dim3((uint32_t) std::min<uint64_t>(persistent, (n_surf + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
+                   ctx->d_out.ptr, n_surf, b, ctx->d_fill_bits.ptr);
+    const uint32_t chunk_wgs = (uint32_t) std::min<uint64_t>(persistent, (n_chunks + kBlock / 64u - 1) / (kBlock / 64u));
+    O2V_LAUNCH("k_fill_count_words", s, k_fill_count_words, dim3(chunk_wgs), dim3(kBlock), 0, s, ctx->d_fill_bits.ptr, b, ctx->d_fill_chunks.ptr,
+               ctx->d_fill_ctr.ptr + 1);
+    O2V_CHECK(hipMemcpyAsync(ctx->h_fill_ctr.ptr, ctx->d_fill_ctr.ptr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    O2V_CHECK(hipStreamSynchronize(s));
+    n_interior = ctx->h_fill_ctr.ptr[1];
+    const uint64_t need = n_surf + n_interior;
+    if (need > kMaxRecords) {
+        ctx->err = "the pass has 2^32 or more records with its interior voxels; use more z-slabs or x / y tiles";
+        return O2V_HIP_ERR_LIMIT;
+    }
+    if (n_interior) {
+        if (need > ctx->d_out.cap) {
+            // (exactly what is needed, the surface records moved over: the interior can be most of the device's memory)
+            DevArray<uint4> bigger;
+            O2V_CHECK(bigger.alloc(need));
+            if (n_surf) O2V_CHECK(hipMemcpyAsync(bigger.ptr, ctx->d_out.ptr, n_surf * sizeof(uint4), hipMemcpyDeviceToDevice, s));
+            O2V_CHECK(hipStreamSynchronize(s));
+            ctx->d_out = std::move(bigger);  // (the old array goes with `bigger`)
+        }
+        O2V_LAUNCH("k_fill_emit", s, k_fill_emit, dim3(chunk_wgs), dim3(kBlock), 0, s, ctx->d_fill_bits.ptr, b, ctx->d_fill_chunks.ptr, n_surf,
+                   ctx->d_out.ptr);
+    }
+    if (timed) O2V_CHECK(hipEventRecord(ctx->ev_fill[1], s));
+    O2V_CHECK(hipStreamSynchronize(s));
+    O2V_CHECK(hipGetLastError());
+    if (timed) O2V_CHECK(hipEventElapsedTime(&ctx->timings.fill_ms, ctx->ev_fill[0], ctx->ev_fill[1]));
+    return collect_kernel_times(ctx);
+}
+
+// The results of the pass that stood: counts, stats, stage times and the transform.  n_interior: records of the solid fill behind
+// the surface records (0 without O2V_HIP_FLAG_FILL_INTERIOR).
+int publish(o2v_hip_ctx *ctx, const Run &r, uint64_t n_interior, uint64_t *out_voxel_count)
 {
     const Params &p = r.p;
     const Counters &h = *ctx->h_ctr.ptr;
     if (!p.occupancy_only) ctx->grid_dirty = false;
     ctx->maxgrid_dirty = false;
-    const bool direct = p.direct_max && (p.occupancy_only || h.n_nodes[0] <= h.n_root_leaves);  // direct_active() on the device
-    const uint64_t n_final = direct ? h.n_out : h.n_vox;
+    const bool direct = pass_direct(p, h);
+    const uint64_t n_final = (direct ? h.n_out : h.n_vox) + n_interior;
     ctx->last_direct = direct;
     ctx->n_vox = n_final;
     o2v_hip_stats &st = ctx->stats;
+    st.interior_voxels = n_interior;
     st.leaves = h.n_leaves + h.n_bypass;  // (root_bypass: leaves of one tile that k_voxelize_occ made itself)
     st.tiles = h.n_tiles + h.n_bypass;
     st.candidates = h.n_candidates;
@@ -1305,7 +1410,13 @@ int voxelize(o2v_hip_ctx *ctx, const o2v_hip_params *params, const Switches &sw,
         ctx->timings.passes = pass;
         bool again = false;
         if ((rc = check_pass(ctx, r, again))) return rc;
-        if (!again) return publish(ctx, r, out_voxel_count);
+        if (again) continue;
+        uint64_t n_interior = 0;
+        if (params->flags & O2V_HIP_FLAG_FILL_INTERIOR) {
+            const Counters &h = *ctx->h_ctr.ptr;
+            if ((rc = fill_stage(ctx, params, r, pass_direct(r.p, h) ? h.n_out : h.n_vox, n_interior))) return rc;
+        }
+        return publish(ctx, r, n_interior, out_voxel_count);
     }
     ctx->err = "device buffers did not converge after 12 passes";
     return O2V_HIP_ERR_LIMIT;
@@ -1478,7 +1589,7 @@ void o2v_hip_destroy(o2v_hip_ctx *ctx)
     if (ctx->stream) (void) hipStreamSynchronize(ctx->stream);
     std::vector<hipEvent_t> events{std::begin(ctx->ev), std::end(ctx->ev)};
     events.insert(events.end(), {ctx->ev_coll[0], ctx->ev_coll[1], ctx->ev_stage[0], ctx->ev_stage[1], ctx->ev_fork, ctx->ev_sorted,
-                                 ctx->ev_k1, ctx->ev_join[0], ctx->ev_join[1], ctx->ev_join[2]});
+                                 ctx->ev_k1, ctx->ev_join[0], ctx->ev_join[1], ctx->ev_join[2], ctx->ev_fill[0], ctx->ev_fill[1]});
     for (const auto &b : ctx->ktimes) events.insert(events.end(), {b.e0, b.e1});
     for (hipEvent_t e : events)
         if (e) (void) hipEventDestroy(e);
@@ -2023,8 +2134,14 @@ int o2v_hip_max_slab_layers(o2v_hip_ctx *ctx, const o2v_hip_params *params, uint
     const uint64_t reserve = std::max<uint64_t>(8ull << 30, total_b / 4);
     const uint64_t held_slabs = ctx->d_slabs.cap * sizeof(uint32_t);
     const uint64_t avail = (uint64_t) free_b + held + held_slabs > reserve ? (uint64_t) free_b + held + held_slabs - reserve : 0;
-    uint64_t brick_layers = avail / (per_layer_bricks * per_brick);
+    // solid fill (O2V_HIP_FLAG_FILL_INTERIOR): per layer of the box also its bits of the toggle bitmap and, at worst, one 16-byte
+    // interior record per cell; and a pass holds fewer than 2^32 records
+    const bool fill = (params->flags & O2V_HIP_FLAG_FILL_INTERIOR) != 0;
+    const uint64_t per_layer_cells = per_layer_bricks * kBrickX * kBrickY;
+    const uint64_t fill_bytes = fill ? per_layer_cells * kBrickZ * sizeof(uint4) + (per_layer_cells * kBrickZ + 7u) / 8u : 0ull;
+    uint64_t brick_layers = avail / (per_layer_bricks * per_brick + fill_bytes);
     brick_layers = std::min<uint64_t>(brick_layers, ((1ull << 31) - 1) / per_layer_bricks);  // 32-bit brick ids
+    if (fill) brick_layers = std::min<uint64_t>(brick_layers, kMaxRecords / (per_layer_cells * kBrickZ));
     const uint64_t layers = brick_layers * kBrickZ;
     // (the grids only span the mesh's box in z as well: if that many layers fit, the whole resolution is one slab)
     const uint64_t box_layers = box.empty ? 0ull : (uint64_t) (box.hi[2] - box.lo[2]) + kBrickZ;

@@ -13,12 +13,14 @@ class _Params(C.Structure):
     _fields_ = [("resolution", C.c_uint32), ("supersampling", C.c_uint32), ("strategy", C.c_uint32),
                 ("unit_transform", C.c_int32 * 9), ("bounds_known", C.c_uint32), ("bounds", C.c_float * 6),
                 ("z_begin", C.c_uint32), ("z_end", C.c_uint32), ("flags", C.c_uint32),
-                ("x_begin", C.c_uint32), ("x_end", C.c_uint32), ("y_begin", C.c_uint32), ("y_end", C.c_uint32)]
+                ("x_begin", C.c_uint32), ("x_end", C.c_uint32), ("y_begin", C.c_uint32), ("y_end", C.c_uint32),
+                ("fill_argb", C.c_uint32)]
 
 
 FLAG_KERNEL_TIMES = 2  # ... every launch bracketed by events: DeviceVoxelizer.kernel_times()
 FLAG_STAGE_TIMES = 4   # ... an event between the stages of a pass: the stage times and total_ms of DeviceVoxelizer.timings()
 FLAG_EXACT_CLIP = 1  # o2v_hip_params::flags: the clip kernel without its work-removal shortcuts (include/o2v_hip.h)
+FLAG_FILL_INTERIOR = 8  # ... solid voxelization: the interior voxels (colour fill_argb) behind the surface records
 
 
 class _Texture(C.Structure):
@@ -29,7 +31,7 @@ class _Texture(C.Structure):
 class Timings(C.Structure):
     _fields_ = [("bounds_ms", C.c_float), ("expand_ms", C.c_float), ("voxelize_ms", C.c_float),
                 ("scan_ms", C.c_float), ("resolve_ms", C.c_float), ("total_ms", C.c_float), ("passes", C.c_uint32),
-                ("plan_ms", C.c_float), ("collective_ms", C.c_float), ("collective_parts_ms", C.c_float * 5)]
+                ("plan_ms", C.c_float), ("collective_ms", C.c_float), ("collective_parts_ms", C.c_float * 5), ("fill_ms", C.c_float)]
 
     def as_dict(self):
         d = {n: getattr(self, n) for n, _ in self._fields_}
@@ -40,7 +42,7 @@ class Timings(C.Structure):
 class Stats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("triangles", "leaves", "tiles", "candidates", "hits", "voxels",
                                           "grid_cells", "grid_bytes", "bricks", "dirty_bricks", "pool_slots", "direct_hits", "jobs",
-                                          "certain_hits", "skipped_jobs", "bypassed_leaves")]
+                                          "certain_hits", "skipped_jobs", "bypassed_leaves", "interior_voxels")]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -207,8 +209,10 @@ class DeviceVoxelizer:
                     "o2v_hip_set_textures")
 
     @staticmethod
-    def _params(resolution, supersampling, strategy, unit_transform, bounds, zslab, flags=0, xtile=(0, 0), ytile=(0, 0)):
+    def _params(resolution, supersampling, strategy, unit_transform, bounds, zslab, flags=0, xtile=(0, 0), ytile=(0, 0),
+                fill_argb=0):
         p = _Params()
+        p.fill_argb = fill_argb
         p.x_begin, p.x_end = xtile
         p.y_begin, p.y_end = ytile
         p.flags = flags
@@ -231,10 +235,15 @@ class DeviceVoxelizer:
         return [int(z) for z in cuts], bnd
 
     def voxelize(self, resolution, *, supersampling=1, strategy=STRATEGY_MAX, unit_transform=None, bounds=None,
-                 zslab=(0, 0), read=True, exact_clip=False, kernel_times=False, stage_times=False, xtile=(0, 0), ytile=(0, 0)):
-        """xtile / ytile: an x / y range of the output grid (o2v_hip_params::x_begin ..; begin a multiple of 4), like zslab."""
+                 zslab=(0, 0), read=True, exact_clip=False, kernel_times=False, stage_times=False, xtile=(0, 0), ytile=(0, 0),
+                 fill=False, fill_argb=0xFFFFFFFF):
+        """xtile / ytile: an x / y range of the output grid (o2v_hip_params::x_begin ..; begin a multiple of 4), like zslab.
+        fill: solid voxelization (O2V_HIP_FLAG_FILL_INTERIOR): the surface records, then the interior voxels in colour fill_argb."""
         flags = (FLAG_EXACT_CLIP if exact_clip else 0) | (FLAG_KERNEL_TIMES if kernel_times else 0) | (FLAG_STAGE_TIMES if stage_times else 0)
-        if tuple(xtile) != (0, 0) or tuple(ytile) != (0, 0):
+        if fill:
+            p = self._params(resolution, supersampling, strategy, unit_transform, bounds, zslab, flags | FLAG_FILL_INTERIOR,
+                             tuple(xtile), tuple(ytile), fill_argb)
+        elif tuple(xtile) != (0, 0) or tuple(ytile) != (0, 0):
             p = self._params(resolution, supersampling, strategy, unit_transform, bounds, zslab, flags, tuple(xtile), tuple(ytile))
         elif unit_transform is None and bounds is None:
             # (a loop of identical calls - bench.py's timed steps - does not build the parameter block again every time)
@@ -252,15 +261,17 @@ class DeviceVoxelizer:
         return self.read_voxels()
 
     def voxelize_sharded(self, comm, resolution, *, supersampling=1, strategy=STRATEGY_MAX, unit_transform=None, bounds=None,
-                         read=True, stage_times=False):
-        """o2v_hip_voxelize_sharded: collective over `comm` (a Comm); this rank voxelizes its planned z-slab.
+                         read=True, stage_times=False, fill=False, fill_argb=0xFFFFFFFF):
+        """o2v_hip_voxelize_sharded: collective over `comm` (a Comm); this rank voxelizes its planned z-slab (fill: and fills it).
         Returns (voxels or count of this rank, counts of all ranks, z cuts)."""
-        flags = FLAG_STAGE_TIMES if stage_times else 0
+        flags = (FLAG_STAGE_TIMES if stage_times else 0) | (FLAG_FILL_INTERIOR if fill else 0)
+        fill_argb = fill_argb if fill else 0
         # (a loop of identical calls - bench.py's timed steps - reuses the parameter block and the two small result arrays)
-        key = (resolution, supersampling, strategy, flags, comm.world) if unit_transform is None and bounds is None else None
+        key = (resolution, supersampling, strategy, flags, fill_argb, comm.world) if unit_transform is None and bounds is None else None
         if key is None or getattr(self, "_sharded_key", None) != key:
             self._sharded_key = key
-            self._sharded_params = self._params(resolution, supersampling, strategy, unit_transform, bounds, (0, 0), flags)
+            self._sharded_params = self._params(resolution, supersampling, strategy, unit_transform, bounds, (0, 0), flags,
+                                                fill_argb=fill_argb)
             self._sharded_counts = np.zeros(comm.world, dtype=np.uint64)
             self._sharded_cuts = np.zeros(comm.world + 1, dtype=np.uint32)
             self._sharded_ptrs = (_ptr(self._sharded_counts), _ptr(self._sharded_cuts))
@@ -477,9 +488,12 @@ class DeviceGroup:
         self._check(self._L.o2v_hip_group_set_textures(self._g, C.cast(arr, C.c_void_p), len(textures)), "o2v_hip_group_set_textures")
 
     def voxelize(self, resolution, *, supersampling=1, strategy=STRATEGY_MAX, unit_transform=None, bounds=None, read=True,
-                 stage_times=False):
-        """Returns (list of per-rank voxel arrays, or the per-rank counts if read=False; z cuts)."""
-        p = DeviceVoxelizer._params(resolution, supersampling, strategy, unit_transform, bounds, (0, 0), FLAG_STAGE_TIMES if stage_times else 0)
+                 stage_times=False, fill=False, fill_argb=0xFFFFFFFF):
+        """Returns (list of per-rank voxel arrays, or the per-rank counts if read=False; z cuts).  fill: solid voxelization, every
+        rank filling its own slab (DeviceVoxelizer.voxelize)."""
+        flags = (FLAG_STAGE_TIMES if stage_times else 0) | (FLAG_FILL_INTERIOR if fill else 0)
+        p = DeviceVoxelizer._params(resolution, supersampling, strategy, unit_transform, bounds, (0, 0), flags,
+                                    fill_argb=fill_argb if fill else 0)
         counts = np.zeros(self.size, dtype=np.uint64)
         cuts = np.zeros(self.size + 1, dtype=np.uint32)
         self._check(self._L.o2v_hip_group_voxelize(self._g, C.byref(p), _ptr(counts), _ptr(cuts)), "o2v_hip_group_voxelize")

@@ -113,10 +113,13 @@ def load(name):
     return verts, mat, textures, res, kw, text
 
 
-def run(name, steps=5, warmup=2, dv=None, kernel_steps=0, loaded=None):
+def run(name, steps=5, warmup=2, dv=None, kernel_steps=0, loaded=None, fill=False):
     """Times `steps` passes of the workload (wall clock around the calls, each of which waits for the device) and, in
-    `kernel_steps` further passes, the individual kernels (O2V_HIP_FLAG_KERNEL_TIMES: event pairs around every launch)."""
+    `kernel_steps` further passes, the individual kernels (O2V_HIP_FLAG_KERNEL_TIMES: event pairs around every launch).
+    fill: solid voxelization (O2V_HIP_FLAG_FILL_INTERIOR); its stage is stages_ms["fill_ms"], its kernels k_fill_*."""
     verts, mat, textures, res, kw, text = loaded if loaded is not None else load(name)
+    if fill:
+        kw = dict(kw, fill=True)
     own = dv is None
     if own:
         dv = hip.DeviceVoxelizer(0)
@@ -154,6 +157,8 @@ def run(name, steps=5, warmup=2, dv=None, kernel_steps=0, loaded=None):
                "stages_ms": {k: round(v / stage_steps, 4) for k, v in acc.items() if k.endswith("_ms")}, "k2_ms_timed": round(k2_ms, 4),
                "passes": passes, "stats": st,
                "build_id": hip.build_id()}
+        if fill:
+            out["fill"] = True
         if kernel_steps:
             out["kernels_ms"] = {k: {"ms": round(ms / kernel_steps, 4), "launches": launches // kernel_steps} for k, (ms, launches) in kernels.items()}
         return out

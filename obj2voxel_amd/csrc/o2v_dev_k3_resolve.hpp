@@ -419,7 +419,7 @@ __global__ __launch_bounds__(kBlock) void k_resolve_list16(const uint32_t *__res
 // record; the (key, position) pairs are bitonic-sorted across the W lanes with cross-lane moves only (no LDS, no
 // barrier); the payload is gathered to its sorted lane; the groups are folded and coloured in parallel by the lanes at their
 // first records, and the cell's chain over the groups runs on every lane of the cell on broadcast values.
-// (the body: wavefront `wave` of `n_waves` that share the list)
+// (wavefront `wave` of `n_waves` that share the list; run inside k_resolve_tiers)
 template <uint32_t W>
 __device__ __forceinline__ void resolve_wave_body(uint32_t wave, uint32_t n_waves, const uint32_t *__restrict__ list, const uint32_t *n_list,
                                                   const Counters *c, const Occ *__restrict__ occ, SortedView sorted, const Materials &m,
@@ -506,14 +506,6 @@ __device__ __forceinline__ void resolve_wave_body(uint32_t wave, uint32_t n_wave
         const uint32_t argb = f.finish(p.blend);
         if (n != 0 && sl == 0) emit_cell(o, argb, f.cell_acc.w, f.cell_key, out, i, c, p);
     }
-}
-template <uint32_t W>
-__global__ __launch_bounds__(kBlock) void k_resolve_wave(const uint32_t *__restrict__ list, const uint32_t *n_list,
-                                                         const Counters *c, const Occ *__restrict__ occ,
-                                                         SortedView sorted, Materials m, uint4 *out, uint32_t list_cap,
-                                                         Params p)
-{
-    resolve_wave_body<W>((blockIdx.x * kBlock + threadIdx.x) >> 6, gridDim.x * (kBlock / 64u), list, n_list, c, occ, sorted, m, out, list_cap, p);
 }
 
 // Between phases in which the lanes of ONE wavefront exchange values through LDS: the hardware runs a wavefront's LDS
@@ -657,6 +649,88 @@ __device__ __forceinline__ void bitonic_sort(KeyPtr key, IdxPtr idx, uint32_t n_
     }
 }
 
+// ---- the crowded tiers' shared steps (more than 64 hits a cell, one workgroup per cell) ---------------------------
+// The workgroup takes cells from its list, one at a time, through `cursor` and runs body(item) on each until the list's end.
+template <class Body>
+__device__ __forceinline__ void for_each_claimed_cell(uint32_t *cursor, uint32_t total, const Body &body)
+{
+    __shared__ uint32_t s_item;
+    for (;;) {
+        __syncthreads();
+        if (threadIdx.x == 0) s_item = atomicAdd(cursor, 1u);
+        __syncthreads();
+        const uint32_t item = s_item;
+        if (item >= total) break;
+        body(item);
+    }
+}
+
+// The cell's n keys with their positions, padded with the greatest key to n_pow2 and bitonic-sorted in key[] / idx[]
+// (LDS or global memory).  Ends with a barrier.
+template <uint32_t THREADS>
+__device__ __forceinline__ void sort_cell_keys(const CellRecords &recs, uint32_t n, uint32_t n_pow2, uint64_t *key, uint32_t *idx)
+{
+    for (uint32_t t = threadIdx.x; t < n_pow2; t += THREADS) {
+        if (t < n) {
+            const SortedRec r = recs.load(t);
+            key[t] = ((uint64_t) r.keyhi << 32) | r.keylo;
+            idx[t] = t;
+        }
+        else {
+            key[t] = ~0ull;
+            idx[t] = 0;
+        }
+    }
+    __syncthreads();
+    bitonic_sort(key, idx, n_pow2, threadIdx.x, THREADS);
+}
+
+// MAX over a sorted crowded cell: `new.w > existing.w ? new : existing` over ascending (sub-voxel, triangle) groups keeps
+// the first group with the greatest weight, which is a true reduction.  Every group is folded by the lane at its first
+// record (leaves of one triangle, in order), the groups are max-reduced with ties to the lower position, and thread 0
+// refolds the winning group (its uv, for a textured winner) and emits the cell.  hi_at(t) / hit_at(t): the group key and
+// {w, u, v} of the t-th sorted record.  s_best holds THREADS / 64 per-wavefront results; one wavefront does not use it.
+template <uint32_t THREADS, class HiAt, class HitAt>
+__device__ __forceinline__ void resolve_max_winner(const HiAt &hi_at, const HitAt &hit_at, uint32_t n, uint64_t *s_best, const Occ &o,
+                                                   uint32_t i, const Materials &m, uint4 *out, const Counters *c, const Params &p)
+{
+    auto fold_group = [&](uint32_t t) {
+        const uint32_t hi = hi_at(t);
+        WUv acc = hit_at(t);
+        for (uint32_t j = t + 1; j < n && hi_at(j) == hi; ++j) acc = wmix(hit_at(j), acc);
+        return acc;
+    };
+    unsigned long long best = 0;
+    for (uint32_t t = threadIdx.x; t < n; t += THREADS) {
+        if (t == 0 || hi_at(t - 1) != hi_at(t)) {
+            const WUv acc = fold_group(t);
+            // weights are non-negative, so their bit patterns order like the values
+            const unsigned long long cand = ((unsigned long long) __float_as_uint(acc.w) << 32) | (0xffffffffu - t);
+            best = cand > best ? cand : best;
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const unsigned long long other = __shfl_xor(best, d, 64);
+        best = other > best ? other : best;
+    }
+    if constexpr (THREADS > 64) {
+        __syncthreads();
+        if ((threadIdx.x & 63u) == 0) s_best[threadIdx.x >> 6] = best;
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (uint32_t wv = 1; wv < THREADS / 64; ++wv) best = s_best[wv] > best ? s_best[wv] : best;
+    }
+    if (threadIdx.x == 0) {
+        const uint32_t t = 0xffffffffu - (uint32_t) best;
+        const uint32_t hi = hi_at(t);
+        const WUv acc = fold_group(t);
+        float cr, cg, cb;
+        color_at(m, hi & 0x1fffffffu, acc.u, acc.v, cr, cg, cb);
+        emit_cell(o, pack_argb(cr, cg, cb), acc.w, hi, out, i, c, p);
+    }
+}
+
 // Tiers 2 and 3: THREADS lanes cooperate on one cell (a wavefront for up to 256 hits, a workgroup for up to 2048).
 // The cell's records are contiguous: keys are loaded coalesced, (key, idx) pairs are bitonic-sorted in LDS, the
 // payload is gathered in sorted order, and lane 0 replays the fold (which is inherently sequential: the float
@@ -672,34 +746,16 @@ __device__ __forceinline__ void resolve_sorted_body(const uint32_t *__restrict__
     __shared__ uint32_t s_idx[CAP];
     __shared__ uint32_t s_hi[CAP];
     __shared__ float s_w[CAP], s_u[CAP], s_v[CAP];
-    __shared__ uint32_t s_item;
     __shared__ uint32_t s_seg[16];
     __shared__ float s_res[32];
     const uint32_t total = *n_list < list_cap ? *n_list : list_cap;
-    for (;;) {
-        __syncthreads();
-        if (threadIdx.x == 0) s_item = atomicAdd(cursor, 1u);
-        __syncthreads();
-        const uint32_t item = s_item;
-        if (item >= total) break;
+    for_each_claimed_cell(cursor, total, [&](uint32_t item) {
         const uint32_t i = list[item];
         const Occ o = occ[i];
         const uint32_t n = o.count < CAP ? o.count : CAP;
         uint32_t n_pow2 = 1;
         while (n_pow2 < n) n_pow2 <<= 1;
-        for (uint32_t t = threadIdx.x; t < n_pow2; t += THREADS) {
-            if (t < n) {
-                const SortedRec r = cell_records(sorted, o, p).load(t);
-                s_key[t] = ((uint64_t) r.keyhi << 32) | r.keylo;
-                s_idx[t] = t;
-            }
-            else {
-                s_key[t] = ~0ull;
-                s_idx[t] = 0;
-            }
-        }
-        __syncthreads();
-        bitonic_sort(s_key, s_idx, n_pow2, threadIdx.x, THREADS);
+        sort_cell_keys<THREADS>(cell_records(sorted, o, p), n, n_pow2, s_key, s_idx);
         for (uint32_t t = threadIdx.x; t < n; t += THREADS) {
             const SortedRec r = cell_records(sorted, o, p).load(s_idx[t]);
             s_hi[t] = r.keyhi;
@@ -733,44 +789,10 @@ __device__ __forceinline__ void resolve_sorted_body(const uint32_t *__restrict__
             }
         }
         else {
-            // MAX: `new.w > existing.w ? new : existing` over ascending (sub-voxel, triangle) groups keeps the first
-            // group with the greatest weight, which is a true reduction: every group is folded by the lane at its
-            // first record (leaves of one triangle, in order), then the groups are max-reduced with ties to the
-            // lower position.
-            unsigned long long best = 0;
-            for (uint32_t t = threadIdx.x; t < n; t += THREADS) {
-                if (t == 0 || s_hi[t] != s_hi[t - 1]) {
-                    WUv acc{s_w[t], s_u[t], s_v[t]};
-                    uint32_t j = t + 1;
-                    for (; j < n && s_hi[j] == s_hi[t]; ++j) acc = wmix(WUv{s_w[j], s_u[j], s_v[j]}, acc);
-                    // weights are non-negative, so their bit patterns order like the values
-                    const unsigned long long cand = ((unsigned long long) __float_as_uint(acc.w) << 32) | (0xffffffffu - t);
-                    best = cand > best ? cand : best;
-                }
-            }
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {
-                const unsigned long long other = __shfl_xor(best, d, 64);
-                best = other > best ? other : best;
-            }
-            if (THREADS > 64) {
-                __syncthreads();
-                if ((threadIdx.x & 63u) == 0) s_key[threadIdx.x >> 6] = best;  // s_key is free after the sort
-                __syncthreads();
-                best = s_key[0];
-                for (uint32_t wv = 1; wv < THREADS / 64; ++wv) best = s_key[wv] > best ? s_key[wv] : best;
-            }
-            if (threadIdx.x == 0) {
-                const uint32_t t = 0xffffffffu - (uint32_t) best;
-                // rebuild the winning group's uv (needed for a textured winner) and emit
-                WUv acc{s_w[t], s_u[t], s_v[t]};
-                for (uint32_t j = t + 1; j < n && s_hi[j] == s_hi[t]; ++j) acc = wmix(WUv{s_w[j], s_u[j], s_v[j]}, acc);
-                float cr, cg, cb;
-                color_at(m, s_hi[t] & 0x1fffffffu, acc.u, acc.v, cr, cg, cb);
-                emit_cell(o, pack_argb(cr, cg, cb), acc.w, s_hi[t], out, i, c, p);
-            }
+            resolve_max_winner<THREADS>([&](uint32_t t) { return s_hi[t]; }, [&](uint32_t t) { return WUv{s_w[t], s_u[t], s_v[t]}; }, n,
+                                        s_key /* free after the sort */, o, i, m, out, c, p);
         }
-    }
+    });
 }
 template <uint32_t THREADS, uint32_t CAP>
 __global__ __launch_bounds__(THREADS) void k_resolve_sorted(const uint32_t *__restrict__ list, const uint32_t *n_list,
@@ -782,8 +804,8 @@ __global__ __launch_bounds__(THREADS) void k_resolve_sorted(const uint32_t *__re
 }
 
 // The cooperative tiers for 17 .. 256 hits in ONE launch of one-wavefront workgroups: the first `g_mid` take cells of 65 .. 256
-// hits from their cursor (k_resolve_sorted<64, 256>'s body - the longest cells, so they start first), the next `g_w64` are
-// k_resolve_wave<64>'s wavefronts (33 .. 64 hits), the rest k_resolve_wave<32>'s (17 .. 32).  Each of the three is a handful of
+// hits from their cursor (k_resolve_sorted<64, 256>'s body - the longest cells, so they start first), the next `g_w64` run
+// resolve_wave_body<64> (33 .. 64 hits), the rest resolve_wave_body<32> (17 .. 32).  Each of the three is a handful of
 // latency chains over few cells; as launches of their own on one stream they ran one after the other (configs[1]: 5 + 22 + 50 us
 // for 0.2 MB, the bench mesh with BLEND 47 + 33 + 92 us), together they take as long as the slowest.
 struct TierLists {
@@ -800,55 +822,67 @@ __global__ __launch_bounds__(64) void k_resolve_tiers(TierLists lists, uint32_t 
     else resolve_wave_body<32>(b - g_mid - g_w64, gridDim.x - g_mid - g_w64, lists.w32, lists.n_w32, c, occ, sorted, m, out, list_cap, p);
 }
 
-// Tier 3b: cells with 2049..8192 hits (the poles of a finely tessellated sphere at high resolution).  One workgroup
-// per cell; (key, idx) pairs are bitonic-sorted in dynamic LDS (96 KiB), the payload stays in global memory: MAX
-// folds the groups in parallel straight from it, BLEND stages it in sorted order, 1024 records at a time, for the
-// sequential replay.
+// Tiers 3b and 4: cells with more than 2048 hits, one workgroup per cell.  The (key, idx) pairs are bitonic-sorted where
+// Keys puts them, the payload stays in global memory: MAX folds the groups in parallel straight from it, BLEND stages it in
+// sorted order, kBigStage records at a time, for thread 0's sequential replay.
 constexpr uint32_t kBigStage = 1024, kBigThreads = 1024;
-__global__ __launch_bounds__(kBigThreads) void k_resolve_big(const uint32_t *__restrict__ list, Counters *c,
-                                                        const Occ *__restrict__ occ, SortedView sorted, Materials m,
-                                                        uint4 *out, uint32_t list_cap, Params p)
-{
-    extern __shared__ __align__(16) unsigned char s_dyn[];
-    uint64_t *s_key = reinterpret_cast<uint64_t *>(s_dyn);                                  // [kBigList]
-    uint32_t *s_idx = reinterpret_cast<uint32_t *>(s_dyn + (size_t) kBigList * 8);           // [kBigList]
-    __shared__ uint32_t s_hi[kBigStage];
-    __shared__ float s_w[kBigStage], s_u[kBigStage], s_v[kBigStage];
-    __shared__ unsigned long long s_best[kBigThreads / 64];
-    __shared__ uint32_t s_item;
-    if (pass_overflowed(c, p)) return;
-    const uint32_t total = c->n_bigl < list_cap ? c->n_bigl : list_cap;
-    for (;;) {
-        __syncthreads();
-        if (threadIdx.x == 0) s_item = atomicAdd(&c->cursor_big, 1u);
-        __syncthreads();
-        const uint32_t item = s_item;
-        if (item >= total) break;
-        const uint32_t i = list[item];
-        const Occ o = occ[i];
-        const uint32_t n = o.count < kBigList ? o.count : kBigList;
-        uint32_t n_pow2 = 1;
-        while (n_pow2 < n) n_pow2 <<= 1;
-        for (uint32_t t = threadIdx.x; t < n_pow2; t += kBigThreads) {
-            if (t < n) {
-                const SortedRec r = cell_records(sorted, o, p).load(t);
-                s_key[t] = ((uint64_t) r.keyhi << 32) | r.keylo;
-                s_idx[t] = t;
-            }
-            else {
-                s_key[t] = ~0ull;
-                s_idx[t] = 0;
-            }
+
+// Tier 3b (2049..8192 hits, the poles of a finely tessellated sphere at high resolution): the pairs in dynamic LDS (96 KiB).
+struct LdsKeys {
+    static constexpr uint32_t kCap = kBigList;
+    uint64_t *key;  // [kBigList]
+    uint32_t *idx;  // [kBigList]
+    __device__ __forceinline__ bool take(uint32_t) { return true; }
+};
+// Tier 4 (more than 8192 hits, a whole mesh inside a few voxels): each cell bump-allocates a power-of-two range of a global
+// scratch area (which holds 2 * cap_hits pairs).  Scratch too small: the cell is skipped, the host sees scratch_used above
+// the capacity, grows it and re-runs.
+struct ScratchKeys {
+    static constexpr uint32_t kCap = 0xffffffffu;
+    uint64_t *key;
+    uint32_t *idx;
+    uint64_t *scratch_key;
+    uint32_t *scratch_idx, scratch_cap;
+    Counters *c;
+    __device__ __forceinline__ bool take(uint32_t n_pow2)
+    {
+        __shared__ uint32_t s_base, s_ok;
+        if (threadIdx.x == 0) {
+            s_base = atomicAdd(&c->scratch_used, n_pow2);
+            s_ok = (uint64_t) s_base + n_pow2 <= scratch_cap ? 1u : 0u;
         }
         __syncthreads();
-        bitonic_sort(s_key, s_idx, n_pow2, threadIdx.x, kBigThreads);
+        key = scratch_key + s_base;
+        idx = scratch_idx + s_base;
+        return s_ok != 0u;
+    }
+};
+
+template <uint32_t THREADS, class Keys>
+__device__ __forceinline__ void resolve_crowded_body(const uint32_t *__restrict__ list, uint32_t total, uint32_t *cursor, Keys &keys,
+                                                     const Counters *c, const Occ *__restrict__ occ, SortedView sorted,
+                                                     const Materials &m, uint4 *out, const Params &p)
+{
+    __shared__ uint32_t s_hi[kBigStage];
+    __shared__ float s_w[kBigStage], s_u[kBigStage], s_v[kBigStage];
+    __shared__ uint64_t s_best[THREADS / 64];
+    if (pass_overflowed(c, p)) return;
+    for_each_claimed_cell(cursor, total, [&](uint32_t item) {
+        const uint32_t i = list[item];
+        const Occ o = occ[i];
+        const uint32_t n = o.count < Keys::kCap ? o.count : Keys::kCap;
+        uint32_t n_pow2 = 1;
+        while (n_pow2 < n) n_pow2 <<= 1;
+        if (!keys.take(n_pow2)) return;
+        const CellRecords recs = cell_records(sorted, o, p);
+        sort_cell_keys<THREADS>(recs, n, n_pow2, keys.key, keys.idx);
         if (p.blend) {
             CellFold f;  // only thread 0's copy is used
             for (uint32_t base = 0; base < n; base += kBigStage) {
                 const uint32_t m_here = n - base < kBigStage ? n - base : kBigStage;
                 __syncthreads();
-                for (uint32_t t = threadIdx.x; t < m_here; t += kBigThreads) {
-                    const SortedRec r = cell_records(sorted, o, p).load(s_idx[base + t]);
+                for (uint32_t t = threadIdx.x; t < m_here; t += THREADS) {
+                    const SortedRec r = recs.load(keys.idx[base + t]);
                     s_hi[t] = r.keyhi;
                     s_w[t] = r.w;
                     s_u[t] = r.u;
@@ -861,142 +895,33 @@ __global__ __launch_bounds__(kBigThreads) void k_resolve_big(const uint32_t *__r
             if (threadIdx.x == 0) out[i] = cell_record(o, f.finish(m, p.blend), p);
         }
         else {
-            unsigned long long best = 0;
-            for (uint32_t t = threadIdx.x; t < n; t += kBigThreads) {
-                const uint32_t hi = (uint32_t) (s_key[t] >> 32);
-                if (t == 0 || (uint32_t) (s_key[t - 1] >> 32) != hi) {
-                    SortedRec r = cell_records(sorted, o, p).load(s_idx[t]);
-                    WUv acc{r.w, r.u, r.v};
-                    for (uint32_t j = t + 1; j < n && (uint32_t) (s_key[j] >> 32) == hi; ++j) {
-                        r = cell_records(sorted, o, p).load(s_idx[j]);
-                        acc = wmix(WUv{r.w, r.u, r.v}, acc);
-                    }
-                    const unsigned long long cand = ((unsigned long long) __float_as_uint(acc.w) << 32) | (0xffffffffu - t);
-                    best = cand > best ? cand : best;
-                }
-            }
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {
-                const unsigned long long other = __shfl_xor(best, d, 64);
-                best = other > best ? other : best;
-            }
-            __syncthreads();
-            if ((threadIdx.x & 63u) == 0) s_best[threadIdx.x >> 6] = best;
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                for (uint32_t wv = 1; wv < kBigThreads / 64; ++wv) best = s_best[wv] > best ? s_best[wv] : best;
-                const uint32_t t = 0xffffffffu - (uint32_t) best;
-                const uint32_t hi = (uint32_t) (s_key[t] >> 32);
-                SortedRec r = cell_records(sorted, o, p).load(s_idx[t]);
-                WUv acc{r.w, r.u, r.v};
-                for (uint32_t j = t + 1; j < n && (uint32_t) (s_key[j] >> 32) == hi; ++j) {
-                    r = cell_records(sorted, o, p).load(s_idx[j]);
-                    acc = wmix(WUv{r.w, r.u, r.v}, acc);
-                }
-                float cr, cg, cb;
-                color_at(m, hi & 0x1fffffffu, acc.u, acc.v, cr, cg, cb);
-                emit_cell(o, pack_argb(cr, cg, cb), acc.w, hi, out, i, c, p);
-            }
+            resolve_max_winner<THREADS>([&](uint32_t t) { return (uint32_t) (keys.key[t] >> 32); },
+                                        [&](uint32_t t) {
+                                            const SortedRec r = recs.load(keys.idx[t]);
+                                            return WUv{r.w, r.u, r.v};
+                                        },
+                                        n, s_best, o, i, m, out, c, p);
         }
-    }
+    });
 }
 
-// Tier 4: cells with more than 8192 hits (a whole mesh inside a few voxels).  Same algorithm with the (key, idx)
-// pairs in a global scratch area; each cell bump-allocates a power-of-two range (scratch holds 2 * cap_hits pairs).
+__global__ __launch_bounds__(kBigThreads) void k_resolve_big(const uint32_t *__restrict__ list, Counters *c,
+                                                        const Occ *__restrict__ occ, SortedView sorted, Materials m,
+                                                        uint4 *out, uint32_t list_cap, Params p)
+{
+    extern __shared__ __align__(16) unsigned char s_dyn[];
+    LdsKeys keys{reinterpret_cast<uint64_t *>(s_dyn), reinterpret_cast<uint32_t *>(s_dyn + (size_t) kBigList * 8)};
+    resolve_crowded_body<kBigThreads>(list, c->n_bigl < list_cap ? c->n_bigl : list_cap, &c->cursor_big, keys, c, occ, sorted, m, out, p);
+}
+
 __global__ __launch_bounds__(kBlock) void k_resolve_huge(const uint32_t *__restrict__ list, Counters *c,
                                                          const Occ *__restrict__ occ, SortedView sorted,
                                                          Materials m, uint4 *out, uint64_t *scratch_key,
                                                          uint32_t *scratch_idx, uint32_t scratch_cap, uint32_t list_cap,
                                                          Params p)
 {
-    __shared__ uint32_t s_item, s_base, s_ok;
-    __shared__ unsigned long long s_best[kBlock / 64];
-    if (pass_overflowed(c, p)) return;
-    const uint32_t total = c->n_huge < list_cap ? c->n_huge : list_cap;
-    for (;;) {
-        __syncthreads();
-        if (threadIdx.x == 0) s_item = atomicAdd(&c->cursor_huge, 1u);
-        __syncthreads();
-        const uint32_t item = s_item;
-        if (item >= total) break;
-        const uint32_t i = list[item];
-        const Occ o = occ[i];
-        const uint32_t n = o.count;
-        uint32_t n_pow2 = 1;
-        while (n_pow2 < n) n_pow2 <<= 1;
-        if (threadIdx.x == 0) {
-            s_base = atomicAdd(&c->scratch_used, n_pow2);
-            // scratch too small: the host sees scratch_used > capacity, grows it and re-runs
-            s_ok = (uint64_t) s_base + n_pow2 <= scratch_cap ? 1u : 0u;
-        }
-        __syncthreads();
-        if (!s_ok) continue;
-        uint64_t *key = scratch_key + s_base;
-        uint32_t *idx = scratch_idx + s_base;
-        for (uint32_t t = threadIdx.x; t < n_pow2; t += kBlock) {
-            if (t < n) {
-                const SortedRec r = cell_records(sorted, o, p).load(t);
-                key[t] = ((uint64_t) r.keyhi << 32) | r.keylo;
-                idx[t] = t;
-            }
-            else {
-                key[t] = ~0ull;
-                idx[t] = 0;
-            }
-        }
-        __syncthreads();
-        bitonic_sort(key, idx, n_pow2, threadIdx.x, kBlock);
-        if (p.blend) {
-            // BLEND: sequential by nature (see k_resolve_sorted)
-            if (threadIdx.x == 0) {
-                CellFold f;
-                for (uint32_t t = 0; t < n; ++t) {
-                    const SortedRec r = cell_records(sorted, o, p).load(idx[t]);
-                    f.add(m, p.blend, r.keyhi, r.w, r.u, r.v);
-                }
-                out[i] = cell_record(o, f.finish(m, p.blend), p);
-            }
-        }
-        else {
-            // MAX: fold every (sub-voxel, triangle) group at its first record, max-reduce with ties to the earlier group
-            unsigned long long best = 0;
-            for (uint32_t t = threadIdx.x; t < n; t += kBlock) {
-                const uint32_t hi = (uint32_t) (key[t] >> 32);
-                if (t == 0 || (uint32_t) (key[t - 1] >> 32) != hi) {
-                    SortedRec r = cell_records(sorted, o, p).load(idx[t]);
-                    WUv acc{r.w, r.u, r.v};
-                    for (uint32_t j = t + 1; j < n && (uint32_t) (key[j] >> 32) == hi; ++j) {
-                        r = cell_records(sorted, o, p).load(idx[j]);
-                        acc = wmix(WUv{r.w, r.u, r.v}, acc);
-                    }
-                    const unsigned long long cand = ((unsigned long long) __float_as_uint(acc.w) << 32) | (0xffffffffu - t);
-                    best = cand > best ? cand : best;
-                }
-            }
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {
-                const unsigned long long other = __shfl_xor(best, d, 64);
-                best = other > best ? other : best;
-            }
-            __syncthreads();
-            if ((threadIdx.x & 63u) == 0) s_best[threadIdx.x >> 6] = best;
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                for (uint32_t wv = 1; wv < kBlock / 64; ++wv) best = s_best[wv] > best ? s_best[wv] : best;
-                const uint32_t t = 0xffffffffu - (uint32_t) best;
-                const uint32_t hi = (uint32_t) (key[t] >> 32);
-                SortedRec r = cell_records(sorted, o, p).load(idx[t]);
-                WUv acc{r.w, r.u, r.v};
-                for (uint32_t j = t + 1; j < n && (uint32_t) (key[j] >> 32) == hi; ++j) {
-                    r = cell_records(sorted, o, p).load(idx[j]);
-                    acc = wmix(WUv{r.w, r.u, r.v}, acc);
-                }
-                float cr, cg, cb;
-                color_at(m, hi & 0x1fffffffu, acc.u, acc.v, cr, cg, cb);
-                emit_cell(o, pack_argb(cr, cg, cb), acc.w, hi, out, i, c, p);
-            }
-        }
-    }
+    ScratchKeys keys{nullptr, nullptr, scratch_key, scratch_idx, scratch_cap, c};
+    resolve_crowded_body<kBlock>(list, c->n_huge < list_cap ? c->n_huge : list_cap, &c->cursor_huge, keys, c, occ, sorted, m, out, p);
 }
 
 // ---- direct MAX path: emission -----------------------------------------------------------------------------------

@@ -395,20 +395,50 @@ def test_long_hit_lists_with_supersampling(dv, oracle, strategy):
         _compare(got, want)
 
 
-@pytest.mark.parametrize("strategy", [0, 1])
-def test_big_and_huge_hit_lists(dv, oracle, strategy):
+def _hits_per_cell_histogram(dv):
+    """Occupied cells of the last run by hit count: bucket b holds the cells with 2^(b-1) < hits <= 2^b."""
+    import ctypes as C
+    h = np.zeros(32, np.uint64)
+    dv._L.o2v_hip_debug_hits_histogram.argtypes = [C.c_void_p, C.c_void_p]
+    assert dv._L.o2v_hip_debug_hits_histogram(dv._ctx, h.ctypes.data) == 0
+    return h
+
+
+@pytest.mark.parametrize("strategy,textured,supersampling", [
+    pytest.param(0, False, 1, id="0"), pytest.param(1, False, 1, id="1"),
+    # textured and coloured mixed: 6-word (uv) records, textured groups; then spread over the eight sub-voxels
+    pytest.param(0, True, 1, id="textured-0"), pytest.param(1, True, 1, id="textured-1"),
+    pytest.param(0, True, 2, id="textured-ss2-0"), pytest.param(1, True, 2, id="textured-ss2-1"),
+])
+def test_big_and_huge_hit_lists(dv, oracle, monkeypatch, strategy, textured, supersampling):
     """39 600 triangles into 8 cells (~5-10 k hits each: the dynamic-LDS tier, 2049..8192 hits) and into a single
-    cell (> 8192 hits: the global-memory sort)."""
+    cell (> 8192 hits: the global-memory sort).  No triangle is subdivided at these resolutions, so MAX would take the
+    direct path and leave the crowded tiers nothing: the textured cases run MAX through the general route."""
     from obj2voxel_amd import hip
-    v = meshes.uv_sphere(100)
-    T = len(v)
-    kw = dict(types=np.full(T, hip.TRI_UNTEXTURED, np.uint32), colors=meshes.triangle_colors(T), strategy=strategy)
+    if textured:
+        v, uv = meshes.uv_sphere(100, with_uv=True)
+        T = len(v)
+        types = np.where(np.arange(T) % 3 == 0, hip.TRI_TEXTURED, hip.TRI_UNTEXTURED).astype(np.uint32)
+        kw = dict(uvs=uv, types=types, colors=meshes.triangle_colors(T), texids=np.zeros(T, np.int32),
+                  textures=[(meshes.checker_texture(64, 8), 1)])
+        monkeypatch.setenv("O2V_NO_DIRECT_MAX", "1")
+    else:
+        v = meshes.uv_sphere(100)
+        T = len(v)
+        kw = dict(types=np.full(T, hip.TRI_UNTEXTURED, np.uint32), colors=meshes.triangle_colors(T))
+    hist = np.zeros(32, np.uint64)
+    counted = textured or strategy == 1     # (the direct MAX path keeps no hit lists)
     for res in (3, 2, 1):
-        got, want = _run_both(dv, oracle, v, res, **kw)
+        got, want = _run_both(dv, oracle, v, res, strategy=strategy, supersampling=supersampling, **kw)
         _compare(got, want)
         st = dv.stats()
         assert st["hits"] >= T
+        if counted:
+            hist += _hits_per_cell_histogram(dv)
     assert st["voxels"] == 1 and st["hits"] > 8192
+    if counted:
+        assert hist[12:14].sum() > 0, "no cell with 2049 .. 8192 hits (k_resolve_big)"
+        assert hist[14:].sum() > 0, "no cell with more than 8192 hits (k_resolve_huge)"
 
 
 def test_baseline_config2_spot_512_blend_textured(dv, oracle):

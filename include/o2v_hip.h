@@ -89,11 +89,12 @@ typedef struct {
  *   crosses the column at z = (w0 V0.z + w1 V1.z + w2 V2.z) / (w0 + w1 + w2) in double, op by op, left to right, without FMA,
  *   with w0 = e(V1, V2, P), w1 = e(V2, V0, P), w2 = e(V0, V1, P) in double as written (the smallest vertex z if the denominator
  *   is 0 or z is not finite), and toggles every voxel k >= k0 of the column, k0 the smallest k >= 0 with k ss + ss/2 > z.  A voxel
- *   toggled an odd number of times is in the parity set.
+ *   toggled an odd number of times and at or below the mesh's top layer floor(zmax / ss) is in the parity set, zmax the largest
+ *   sample-space z of a triangle with finite coordinates.
  * Interior voxels exist only within the pass box (the mesh's voxel bounding box within slab and tile); a crossing below a
  * slab's first layer toggles from that layer up, a triangle whose lowest vertex lies at or above the slab's top is not looked
  * at.  For a closed mesh that is its solid interior; for an open one, whatever the definition gives (voxels above an open sheet,
- * up to the top of the box) - nothing is repaired.  Slabs and tiles split the set exactly as they split the surface.  The
+ * up to the mesh's top layer) - nothing is repaired.  Slabs and tiles split the set exactly as they split the surface.  The
  * stage needs a bitmap of one bit per cell of the pass box and 16 bytes per interior record, and one pass may hold at most
  * 2^32 - 16 records in all (o2v_hip_max_slab_layers counts both). */
 enum { O2V_HIP_FLAG_EXACT_CLIP = 1u, O2V_HIP_FLAG_KERNEL_TIMES = 2u, O2V_HIP_FLAG_STAGE_TIMES = 4u, O2V_HIP_FLAG_FILL_INTERIOR = 8u };

@@ -9,9 +9,11 @@
 //
 // The stage, on a toggle bitmap of the pass box (one bit per cell, 32-bit words along z, laid out [z-word][y][x]):
 //   k_fill_count / k_fill_scan_blocks / k_fill_offsets   columns of each triangle's projected box within the pass box, and
-//                                                         their inclusive prefix sum: a flat (triangle, column) enumeration
+//                                                         their inclusive prefix sum: a flat (triangle, column) enumeration;
+//                                                         k_fill_count also reduces the mesh's top (largest finite z)
 //   k_fill_cross      one lane per (triangle, column): exact column test, crossing height, atomicXor of one bit at k0
-//   k_fill_prefix     one lane per column: prefix XOR along z (in-word by shifts, a carry across words)
+//   k_fill_prefix     one lane per column: prefix XOR along z (in-word by shifts, a carry across words), cut at the mesh's
+//                     top layer
 //   k_fill_unmark     the pass' surface records cleared from the bitmap (atomicAnd)
 //   k_fill_count_words / k_fill_emit   popcounts, wave prefix sums and one atomic per wave for the base; then 16-byte records,
 //                     written by all 64 lanes of a wave side by side
@@ -190,17 +192,38 @@ __device__ __forceinline__ uint64_t fill_block_exscan64(uint64_t v, uint64_t *s_
 
 // ---- kernels ------------------------------------------------------------------------------------------------------
 
-// columns per triangle -> cols[tri]; per block of kBlock triangles their sum -> block_sums[block]
+// columns per triangle -> cols[tri]; per block of kBlock triangles their sum -> block_sums[block].  Also the largest sample-space
+// z of every triangle with finite coordinates, before any cull by the box -> *zmax_enc (f2ord, zero-initialised: the mesh's top,
+// which bounds the parity set from above, k_fill_prefix)
 __global__ __launch_bounds__(kBlock) void k_fill_count(const float *__restrict__ verts, uint64_t n_tris, Affine xf, FillBox b,
-                                                       unsigned long long *__restrict__ cols, unsigned long long *__restrict__ block_sums)
+                                                       unsigned long long *__restrict__ cols, unsigned long long *__restrict__ block_sums,
+                                                       unsigned long long *__restrict__ zmax_enc)
 {
     __shared__ uint64_t s_wave[kBlock / 64];
+    __shared__ float s_zmax[kBlock / 64];
     const uint64_t tri = (uint64_t) blockIdx.x * kBlock + threadIdx.x;
-    const uint64_t n = tri < n_tris ? fill_tri(verts, tri, xf, b).count : 0u;
-    if (tri < n_tris) cols[tri] = n;
+    uint64_t n = 0;
+    float ztop = -__builtin_inff();
+    if (tri < n_tris) {
+        const FillTri t = fill_tri(verts, tri, xf, b);
+        n = t.count;
+        const float c[9] = {t.v0.x, t.v0.y, t.v0.z, t.v1.x, t.v1.y, t.v1.z, t.v2.x, t.v2.y, t.v2.z};
+        bool finite = true;
+        for (int k = 0; k < 9; ++k) finite = finite && isfinite(c[k]);
+        if (finite) ztop = fmaxf(t.v0.z, fmaxf(t.v1.z, t.v2.z));
+        cols[tri] = n;
+    }
     uint64_t total;
     (void) fill_block_exscan64(n, s_wave, total);
     if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
+    for (int d = 32; d >= 1; d >>= 1) ztop = fmaxf(ztop, __shfl_xor(ztop, d, 64));
+    if ((threadIdx.x & 63u) == 0) s_zmax[threadIdx.x >> 6] = ztop;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (uint32_t w = 1; w < kBlock / 64; ++w) ztop = fmaxf(ztop, s_zmax[w]);
+        const unsigned long long e = f2ord(ztop);
+        if (ztop > -__builtin_inff() && e > *zmax_enc) atomicMax(zmax_enc, e);  // (a plain read first: few atomics contend)
+    }
 }
 
 // exclusive scan of the block sums in place (one workgroup); the grand total -> *total
@@ -272,11 +295,16 @@ __global__ __launch_bounds__(kBlock) void k_fill_cross(const float *__restrict__
     }
 }
 
-// One lane per column: every toggle bit becomes the parity of the toggles at and below it; the bits above the box cleared.
-__global__ __launch_bounds__(kBlock) void k_fill_prefix(uint32_t *__restrict__ bits, FillBox b)
+// One lane per column: every toggle bit becomes the parity of the toggles at and below it; the bits above the box and above
+// the mesh's top layer floor(zmax / ss) cleared (the set does not depend on how far the box reaches above the mesh).
+__global__ __launch_bounds__(kBlock) void k_fill_prefix(uint32_t *__restrict__ bits, FillBox b, const unsigned long long *__restrict__ zmax_enc)
 {
     const uint64_t col = (uint64_t) blockIdx.x * kBlock + threadIdx.x;
     if (col >= b.n_cols) return;
+    // layers of the box at or below the top layer (0 if no triangle is finite or the mesh lies below the box)
+    const float zmax = ord2f((uint32_t) *zmax_enc);   // (*zmax_enc == 0, no finite triangle: NaN)
+    const double top = floor((double) zmax / b.ss);
+    const uint32_t n_valid = !(zmax >= 0.f) || top < (double) b.z0 ? 0u : (uint32_t) fmin(top - (double) b.z0 + 1.0, (double) b.nz);
     uint32_t carry = 0;
     for (uint32_t zw = 0; zw < b.nzw; ++zw) {
         uint32_t *q = bits + (uint64_t) zw * b.n_cols + col;
@@ -288,7 +316,7 @@ __global__ __launch_bounds__(kBlock) void k_fill_prefix(uint32_t *__restrict__ b
         w ^= w << 16;
         w ^= carry;
         carry = (uint32_t) ((int32_t) w >> 31);
-        const uint32_t valid = b.nz - zw * 32u;
+        const uint32_t valid = n_valid > zw * 32u ? n_valid - zw * 32u : 0u;
         if (valid < 32u) w &= (1u << valid) - 1u;
         *q = w;
     }

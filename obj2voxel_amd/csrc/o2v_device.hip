@@ -231,7 +231,7 @@ struct o2v_hip_ctx {
     DevArray<unsigned long long> d_fill_ends;    // per triangle: inclusive end of its (triangle, column) items
     DevArray<unsigned long long> d_fill_blocks;  // per block of kBlock triangles: its items' offset
     DevArray<unsigned long long> d_fill_chunks;  // per chunk of kFillChunk bitmap words: its records' offset
-    DevArray<unsigned long long> d_fill_ctr;     // [0] items, [1] interior voxels
+    DevArray<unsigned long long> d_fill_ctr;     // [0] items, [1] interior voxels, [2] the mesh's top (f2ord of its largest z)
     PinnedArray<unsigned long long> h_fill_ctr;
     hipEvent_t ev_fill[2] = {nullptr, nullptr};  // around the stage (O2V_HIP_FLAG_STAGE_TIMES)
     bool maxgrid_dirty = false;
@@ -1283,7 +1283,7 @@ int fill_stage(o2v_hip_ctx *ctx, const o2v_hip_params *params, const Run &r, uin
     int rc;
     if ((rc = grow(ctx, ctx->d_fill_bits, b.n_words, kNoLimit)) || (rc = grow(ctx, ctx->d_fill_ends, T, kNoLimit)) ||
         (rc = grow(ctx, ctx->d_fill_blocks, n_blocks, kNoLimit)) || (rc = grow(ctx, ctx->d_fill_chunks, n_chunks, kNoLimit)) ||
-        (rc = grow(ctx, ctx->d_fill_ctr, 2)) || (rc = grow(ctx, ctx->h_fill_ctr, 2)))
+        (rc = grow(ctx, ctx->d_fill_ctr, 3)) || (rc = grow(ctx, ctx->h_fill_ctr, 2)))
         return rc;
     const bool timed = ctx->stage_events;
     if (timed)
@@ -1295,17 +1295,18 @@ int fill_stage(o2v_hip_ctx *ctx, const o2v_hip_params *params, const Run &r, uin
     for (int i = 0; i < 3; ++i) xf.m[i] = {x[i * 3], x[i * 3 + 1], x[i * 3 + 2]};
     xf.t = {x[9], x[10], x[11]};
     O2V_CHECK(hipMemsetAsync(ctx->d_fill_bits.ptr, 0, b.n_words * sizeof(uint32_t), s));
-    O2V_CHECK(hipMemsetAsync(ctx->d_fill_ctr.ptr, 0, 2 * sizeof(unsigned long long), s));
+    O2V_CHECK(hipMemsetAsync(ctx->d_fill_ctr.ptr, 0, 3 * sizeof(unsigned long long), s));
     const uint32_t persistent = (uint32_t) ctx->num_cus * 8u;
     if (T) {
         O2V_LAUNCH("k_fill_count", s, k_fill_count, dim3((uint32_t) n_blocks), dim3(kBlock), 0, s, ctx->d_verts.ptr, T, xf, b,
-                   ctx->d_fill_ends.ptr, ctx->d_fill_blocks.ptr);
+                   ctx->d_fill_ends.ptr, ctx->d_fill_blocks.ptr, ctx->d_fill_ctr.ptr + 2);
         O2V_LAUNCH("k_fill_scan_blocks", s, k_fill_scan_blocks, dim3(1), dim3(kBlock), 0, s, ctx->d_fill_blocks.ptr, n_blocks, ctx->d_fill_ctr.ptr);
         O2V_LAUNCH("k_fill_offsets", s, k_fill_offsets, dim3((uint32_t) n_blocks), dim3(kBlock), 0, s, ctx->d_fill_ends.ptr, T, ctx->d_fill_blocks.ptr);
         O2V_LAUNCH("k_fill_cross", s, k_fill_cross, dim3(persistent), dim3(kBlock), 0, s, ctx->d_verts.ptr, T, xf, b, ctx->d_fill_ends.ptr,
                    ctx->d_fill_ctr.ptr, ctx->d_fill_bits.ptr);
     }
-    O2V_LAUNCH("k_fill_prefix", s, k_fill_prefix, dim3((uint32_t) ((b.n_cols + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, ctx->d_fill_bits.ptr, b);
+    O2V_LAUNCH("k_fill_prefix", s, k_fill_prefix, dim3((uint32_t) ((b.n_cols + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, ctx->d_fill_bits.ptr, b,
+               ctx->d_fill_ctr.ptr + 2);
     if (n_surf)
         O2V_LAUNCH("k_fill_unmark", s, k_fill_unmark, dim3((uint32_t) std::min<uint64_t>(persistent, (n_surf + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
                    ctx->d_out.ptr, n_surf, b, ctx->d_fill_bits.ptr);

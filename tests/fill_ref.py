@@ -1,13 +1,18 @@
 """Restatement of the solid fill's parity set (O2V_HIP_FLAG_FILL_INTERIOR, include/o2v_hip.h) in numpy, for small meshes.
 
 Signs of the 2-D edge function are exact: a float64 evaluation with Shewchuk's orient2d error bound decides where it can, the
-rest is evaluated with Python fractions on the float32 values.  The crossing height is float64, op by op, as specified; numpy
-does not contract multiply-adds.  Voxels are returned as int64 keys (x * G + y) * G + z."""
+rest is evaluated with Python fractions on the float32 values (EXACT counts those column tests).  The crossing height is float64,
+op by op, as specified; numpy does not contract multiply-adds.  The set ends at the mesh's top layer floor(zmax / ss), zmax the
+largest sample-space z of a triangle with finite coordinates: above it an open mesh's parity does not reach.  Voxels are
+returned as int64 keys (x * G + y) * G + z."""
 from fractions import Fraction
 
 import numpy as np
 
 _BOUND = (3.0 + 16.0 * 2.0 ** -53) * 2.0 ** -53   # ccwerrboundA
+
+# edge signs the float64 filter left to the exact evaluation since the last reset: all of them, and those that were not zero
+EXACT = {"calls": 0, "nonzero": 0}
 
 
 def sample_vertices(verts, xform):
@@ -53,18 +58,23 @@ def _exact_sign(ux, uy, vx, vy, px, py):
     return (d > 0) - (d < 0)
 
 
-def _signs(u, v, px, py):
-    """Column-test signs of edges u -> v ([n, 2] float32 each) at the columns (px, py), perturbation included."""
+def _signs(u, v, px, py, exact=True):
+    """Column-test signs of edges u -> v ([n, 2] float32 each) at the columns (px, py), perturbation included.  exact=False:
+    the plain float64 sign instead (not the definition; for tests that show the exact path matters)."""
     ux, uy = u[:, 0].astype(np.float64), u[:, 1].astype(np.float64)
     vx, vy = v[:, 0].astype(np.float64), v[:, 1].astype(np.float64)
     with np.errstate(all="ignore"):
         left = (vx - ux) * (py - uy)
         right = (vy - uy) * (px - ux)
         det = left - right
-        bound = _BOUND * (np.abs(left) + np.abs(right))
+        bound = _BOUND * (np.abs(left) + np.abs(right)) if exact else 0.0
     s = np.where(det > bound, 1, np.where(-det > bound, -1, 2)).astype(np.int64)
+    if not exact:
+        s[s == 2] = 0
     for n in np.nonzero(s == 2)[0]:
         s[n] = _exact_sign(float(ux[n]), float(uy[n]), float(vx[n]), float(vy[n]), float(px[n]), float(py[n]))
+        EXACT["calls"] += 1
+        EXACT["nonzero"] += int(s[n] != 0)
     tie = np.where(vy != uy, np.where(vy > uy, -1, 1), np.where(vx > ux, 1, -1))
     s = np.where(s == 0, tie, s)
     return np.where((ux == vx) & (uy == vy), 0, s)
@@ -85,7 +95,16 @@ def _first_centre(x, ss, n, strict):
     return i
 
 
-def crossings(sv, G, ss):
+def top_layer(sv, ss):
+    """The mesh's top layer floor(zmax / ss) (zmax over the triangles with finite coordinates); -1 if there is none."""
+    sv = np.asarray(sv, np.float32).reshape(-1, 3, 3)
+    sv = sv[np.all(np.isfinite(sv), axis=(1, 2))]
+    if not len(sv):
+        return -1
+    return max(int(np.floor(float(sv[:, :, 2].max()) / ss)), -1)
+
+
+def crossings(sv, G, ss, exact=True):
     """(column x, column y, k0) of every crossing of the parity definition, k0 clamped to G (= above the grid)."""
     sv = np.asarray(sv, np.float32).reshape(-1, 3, 3)
     sv = sv[np.all(np.isfinite(sv), axis=(1, 2))]
@@ -101,7 +120,7 @@ def crossings(sv, G, ss):
     cj = j0[tri] + local // np.maximum(wi[tri], 1)
     px, py = ci * float(ss) + h, cj * float(ss) + h
     V0, V1, V2 = sv[tri, 0], sv[tri, 1], sv[tri, 2]
-    s0, s1, s2 = _signs(V0, V1, px, py), _signs(V1, V2, px, py), _signs(V2, V0, px, py)
+    s0, s1, s2 = _signs(V0, V1, px, py, exact), _signs(V1, V2, px, py, exact), _signs(V2, V0, px, py, exact)
     cov = (s0 != 0) & (s0 == s1) & (s1 == s2)
     V0, V1, V2, px, py, ci, cj = V0[cov], V1[cov], V2[cov], px[cov], py[cov], ci[cov], cj[cov]
     with np.errstate(all="ignore"):
@@ -117,16 +136,17 @@ def crossings(sv, G, ss):
     return ci, cj, k
 
 
-def parity_keys(sv, G, ss):
-    """Sorted int64 keys of the parity set of the whole G^3 grid for sample-space triangles sv."""
-    ci, cj, k = crossings(sv, G, ss)
-    keep = k < G
+def parity_keys(sv, G, ss, exact=True):
+    """Sorted int64 keys of the parity set of the whole G^3 grid for sample-space triangles sv (layers up to the mesh's top)."""
+    ci, cj, k = crossings(sv, G, ss, exact)
+    top = min(top_layer(sv, ss) + 1, G)   # (layers [0, top) can hold a voxel of the set)
+    keep = k < top
     toggles = (ci[keep] * G + cj[keep]) * G + k[keep]   # (column, layer) as one key
     # equal toggles cancel in pairs; per column the remaining ones, in order, bound the runs [k_a, k_b) of odd parity
     vals, n = np.unique(toggles, return_counts=True)
     vals = vals[n % 2 == 1]
     cols, counts = np.unique(vals // G, return_counts=True)
-    vals = np.sort(np.concatenate([vals, cols[counts % 2 == 1] * G + G]))   # (an odd column runs up to the grid's top)
+    vals = np.sort(np.concatenate([vals, cols[counts % 2 == 1] * G + top]))   # (an odd column runs up to the mesh's top)
     starts, ends = vals[0::2], vals[1::2]
     n = ends - starts
     if not n.sum():

@@ -11,10 +11,9 @@ import pytest
 
 from obj2voxel_amd import meshes
 from tests import fill_ref
+from tests.fill_cases import ARGB, check_fill as _check_fill, materials as _materials, power_of_two_bounds as _power_of_two_bounds
 
 pytestmark = pytest.mark.gpu
-
-ARGB = 0xFF12AB34
 
 
 def _torus(n_major=48, n_minor=20, R=0.7, r=0.25):
@@ -36,36 +35,6 @@ def _torus(n_major=48, n_minor=20, R=0.7, r=0.25):
 
 def _nested():
     return np.concatenate([fill_ref.weld(meshes.uv_sphere(24)), fill_ref.weld(meshes.uv_sphere(16, radius=0.45, center=(0.1, 0.05, 0.0)))])
-
-
-def _materials(kind, v):
-    from obj2voxel_amd import hip
-    T = len(v)
-    if kind == "none":
-        return {}, []
-    if kind == "coloured":
-        return dict(types=np.full(T, hip.TRI_UNTEXTURED, np.uint32), colors=meshes.triangle_colors(T)), []
-    uv = np.tile(np.array([[0, 0, 1, 0, 0.5, 1]], np.float32), (T, 1))
-    return dict(uvs=uv, types=np.full(T, hip.TRI_TEXTURED, np.uint32), texids=np.zeros(T, np.int32)), [(meshes.checker_texture(64, 8), 1)]
-
-
-def _check_fill(dv, v, res, ss=1, bounds=None, **kw):
-    """flag off, then on: surface part, interior against the restatement, stats.  Returns (surface, filled)."""
-    surf = dv.voxelize(res, supersampling=ss, bounds=bounds, **kw)
-    filled = dv.voxelize(res, supersampling=ss, bounds=bounds, fill=True, fill_argb=ARGB, **kw)
-    st = dv.stats()
-    n = len(surf)
-    assert len(filled) >= n
-    assert np.array_equal(meshes.sorted_voxels(filled[:n]), meshes.sorted_voxels(surf)), "the surface part differs"
-    tail = filled[n:]
-    assert np.all(tail[:, 3] == ARGB)
-    assert st["interior_voxels"] == len(tail) and st["voxels"] == len(filled)
-    sv = fill_ref.sample_vertices(v, dv.transform())
-    want = np.setdiff1d(fill_ref.parity_keys(sv, res, ss), fill_ref.keys(surf, res))
-    got = fill_ref.keys(tail, res)
-    assert len(np.unique(got)) == len(got)
-    assert np.array_equal(got, want), (len(got), len(want))
-    return surf, filled
 
 
 CASES = [  # mesh, resolution, supersampling, strategy, materials
@@ -109,20 +78,6 @@ def test_surface_part_equals_oracle(oracle):
         assert np.array_equal(meshes.sorted_voxels(filled[:len(surf)]), meshes.sorted_voxels(want))
     finally:
         dv.close()
-
-
-def _power_of_two_bounds(dv, G, ss):
-    """User bounds [0, B]^3 under which the mesh transform is x -> 2^k x + 0.25 exactly (found by trying B = (S - 1/2) / 2^k),
-    so that model coordinates land exactly on any half-integer sample coordinate."""
-    S = G * ss
-    for k in range(12):
-        bounds = [0, 0, 0] + [float(np.float32((S - 0.5) / 2.0 ** k))] * 3
-        dv.voxelize(G, supersampling=ss, bounds=bounds)
-        xf = dv.transform()
-        m = float(xf[0])
-        if m > 0 and np.log2(m) == int(np.log2(m)) and xf[9] == 0.25 and xf[0] == xf[4] == xf[8] and xf[9] == xf[10] == xf[11]:
-            return bounds, m
-    pytest.fail("no user bounds with a power-of-two mesh transform")
 
 
 @pytest.mark.parametrize("ss", [1, 2])

@@ -98,3 +98,90 @@ def test_cli_help_lists_fill_flags():
     assert "--fill " in r.stdout and "--fill-color" in r.stdout
     bad = subprocess.run([cli, "a.stl", "b.vl32", "-r", "8", "--fill-color", "xyz"], capture_output=True, text=True, timeout=60)
     assert bad.returncode != 0 and "--fill-color" in bad.stderr
+
+
+def test_open_sheets_end_at_the_mesh_top_layer():
+    """An open mesh's set is the parity up to the mesh's top layer floor(zmax / ss), whatever the grid's height: a horizontal
+    sheet at z = 10.3 ss gives layer {10} (the first centre above it is 10 ss + ss/2, the top layer 10); a second sheet at
+    30.7 ss elsewhere adds nothing of its own (its first centre above, 31 ss + ss/2, is above the top layer 30) but lifts the
+    first sheet's runs to layer 30."""
+    G = 40
+    lo, hi = (3.3, 5.6), (17.2, 11.9)
+    for ss in (1, 2):
+        z = 10.3 * ss
+        sheet = _box((lo[0] * ss, lo[1] * ss, z), (hi[0] * ss, hi[1] * ss, z + 1.0))[:12]
+        sheet = sheet[np.all(sheet[:, :, 2] == np.float32(z), axis=1)]   # (the box's bottom face alone)
+        assert len(sheet) == 2 and fill_ref.odd_edges(sheet) != []
+        rule = lambda c, a, b: (c > a) & (c < b)  # noqa: E731
+        at = lambda ks: lambda c, a, b: np.isin(np.arange(G), ks)  # noqa: E731
+        sl, sh = np.float32(np.array(lo) * ss), np.float32(np.array(hi) * ss)
+        want = _lattice(G, ss, (sl[0], sl[1], 0), (sh[0], sh[1], 0), rule, at([10]))
+        assert fill_ref.top_layer(sheet, ss) == 10
+        assert np.array_equal(fill_ref.parity_keys(sheet, G, ss), want)
+        # a higher sheet beside it (z = 30.7 ss): the first sheet's columns now run from their first layer above it to 30
+        high = sheet.copy()
+        high[:, :, 0] += np.float32(20 * ss)
+        high[:, :, 2] = np.float32(30.7 * ss)
+        both = np.concatenate([sheet, high])
+        assert fill_ref.top_layer(both, ss) == 30
+        ks = np.arange(G)
+        first = _lattice(G, ss, (sl[0], sl[1], 0), (sh[0], sh[1], 0), rule, at(ks[(ks * ss + 0.5 * ss > z) & (ks <= 30)]))
+        second = _lattice(G, ss, (sl[0] + 20 * ss, sl[1], 0), (sh[0] + 20 * ss, sh[1], 0), rule, at([]))
+        assert np.array_equal(fill_ref.parity_keys(both, G, ss), np.union1d(first, second))
+        # non-finite triangles neither toggle nor lift the top
+        bad = np.array([[[np.nan, 1, 39], [2, 2, 39], [3, 1, 39]], [[1, 1, 1], [30, np.inf, 38], [4, 30, 38]]], np.float32)
+        assert np.array_equal(fill_ref.parity_keys(np.concatenate([both, bad]), G, ss), np.union1d(first, second))
+
+
+def test_exact_sign_set_needs_the_exact_path():
+    """The adversarial set of tests/test_gpu_fill_fuzz.py: every constructed column test is one the float64 filter leaves open,
+    whose Fraction sign is non-zero and differs from the plain float64 sign, so the naive restatement gives another set."""
+    from tests import fill_cases
+    for G, ss, seed in ((96, 1, 24), (64, 2, 25)):
+        sv, cols = fill_cases.exact_sign_set(seed, G, ss)
+        assert len(cols) == 6
+        for tri, (i, j) in zip(sv, cols):
+            px, py = i * ss + 0.5 * ss, j * ss + 0.5 * ss
+            args = (float(tri[0, 0]), float(tri[0, 1]), float(tri[1, 0]), float(tri[1, 1]), px, py)
+            exact = fill_ref._exact_sign(*args)
+            assert exact != 0 and fill_cases._naive_sign(*args) != exact
+            l, r = (args[2] - args[0]) * (py - args[1]), (args[3] - args[1]) * (px - args[0])
+            assert abs(l - r) <= fill_ref._BOUND * (abs(l) + abs(r))
+            assert fill_ref._signs(tri[0:1, :2], tri[1:2, :2], np.array([px]), np.array([py]))[0] == exact
+        fill_ref.EXACT.update(calls=0, nonzero=0)
+        want = fill_ref.parity_keys(sv, G, ss)
+        assert fill_ref.EXACT["nonzero"] >= len(cols)
+        naive = fill_ref.parity_keys(sv, G, ss, exact=False)
+        assert not np.array_equal(naive, want)
+        # the difference lies in the constructed columns, from layer 2 up to the top
+        diff = np.setxor1d(naive, want)
+        assert set(zip((diff // (G * G)).tolist(), (diff // G % G).tolist())) == set(cols)
+
+
+def test_mirrored_cropped_closed_mesh_maps_back():
+    """A closed mesh that sticks out of the grid on every side (crossings below layer 0, columns outside), mirrored in x or in
+    x and y (determinant -1 and +1): its set is the un-mirrored one mapped back.  Coordinates on a 2^-10 grid and off the column
+    centres, so that mirroring is exact and no tie decides a column."""
+    G, ss = 48, 1
+    S = G * ss
+    rng = np.random.default_rng(7)
+    s = fill_ref.weld(meshes.uv_sphere(14)).reshape(-1, 3).astype(np.float64)
+    pts = s * np.array([0.7, 0.55, 0.8]) * S + np.array([0.45, 0.5, 0.3]) * S + rng.normal(0, 1e-3, 3)
+    pts = np.round(pts * 1024) / 1024
+    frac = pts - np.floor(pts)
+    assert not np.any(frac == 0.5)
+    sv = pts.astype(np.float32).reshape(-1, 3, 3)
+    assert fill_ref.odd_edges(sv) == [] and sv[..., 2].min() < 0 and sv[..., 0].max() > S and sv[..., 0].min() < 0
+    want = fill_ref.parity_keys(sv, G, ss)
+    assert len(want) > 1000
+    for flip in ((True, False), (True, True)):
+        m = sv.copy()
+        for a in (0, 1):
+            if flip[a]:
+                m[..., a] = np.float32(S) - sv[..., a]
+        assert np.array_equal(np.float32(S) - m[..., 0], sv[..., 0])
+        got = fill_ref.parity_keys(m, G, ss)
+        x, y, z = got // (G * G), got // G % G, got % G
+        x = G - 1 - x if flip[0] else x
+        y = G - 1 - y if flip[1] else y
+        assert np.array_equal(np.sort((x * G + y) * G + z), want), flip

@@ -236,6 +236,43 @@ void o2v_set_fill(struct obj2voxel_instance *instance, int enabled, uint32_t arg
 /* Device pointer to the same records (valid until the next voxelize/destroy). */
 int o2v_hip_voxels_device_ptr(o2v_hip_ctx *ctx, const uint32_t **out_ptr, uint64_t *out_count);
 
+/* ---- device-resident input and dense output -------------------------------------------------
+ *
+ * The arrays of o2v_hip_set_triangles, in device memory of the context's device.  faces == NULL: positions is [count][9]
+ * (the host call's verts) and n_positions is ignored.  Otherwise positions is [n_positions][3], faces is [count][3] of
+ * index_bytes (4: int32, 8: int64) each, and triangle t is positions[faces[t][0..2]].  uvs [count][6], types [count],
+ * colors [count][3] and texids [count] are per triangle and optional, as in the host call.
+ * The context then holds exactly the arrays o2v_hip_set_triangles would hold for the host-gathered mesh, bit for bit; the
+ * rules on count (below 2^29), absent arrays and non-finite values are the host call's.
+ * Every pointer must be device (or managed) memory of the context's device, with the array's whole extent inside its
+ * allocation; anything else - host memory, another device's memory, an unknown pointer, a short allocation - is refused with
+ * O2V_HIP_ERR_BAD_ARGUMENT before anything is launched.  A face index that is negative, not below n_positions or (int64) not
+ * below 2^32 is never read (every index is clamped before its load) but fails the call with O2V_HIP_ERR_BAD_ARGUMENT
+ * ("face index out of range ..."); the context is then left with no triangles and stays usable.
+ * The arrays are read on the context's own stream: the caller must have finished writing them (synchronised its stream)
+ * before the call.  The call returns after the reads have landed; the caller may reuse the memory at once. */
+int o2v_hip_set_triangles_device(o2v_hip_ctx *ctx, const float *positions, uint64_t n_positions, const void *faces,
+                                 uint32_t index_bytes, const float *uvs, const uint32_t *types, const float *colors,
+                                 const int32_t *texids, uint64_t count);
+
+enum { O2V_HIP_DENSE_U8 = 0, O2V_HIP_DENSE_ARGB32 = 1, O2V_HIP_DENSE_BITS = 2 };
+/* Scatters the records of the last o2v_hip_voxelize call into a caller-owned dense grid in device memory of the context's
+ * device.  Voxel (x, y, z) with origin <= (x, y, z) < origin + dims goes to
+ *   U8, ARGB32: dst[(x - ox) * strides[0] + (y - oy) * strides[1] + (z - oz) * strides[2]]  (strides in elements)
+ *   BITS:       bit (x - ox) % 32 of 32-bit word ((x - ox) / 32) + (y - oy) * strides[1] + (z - oz) * strides[2]
+ *               (strides[0] must be 1; strides in words)
+ * U8 writes 1 for a surface record and 2 for an interior record (O2V_HIP_FLAG_FILL_INTERIOR), ARGB32 the record's argb,
+ * BITS sets the bit (a device-scope atomicOr).  ARGB32 does not encode occupancy: a texel with alpha 0 gives argb 0x00000000,
+ * which reads like an empty cell; take occupancy from U8 or BITS.  Nothing else in dst is written: the caller clears it.
+ * Records outside the box are not written and are counted in *out_outside (may be NULL).  dst is checked like the arrays of
+ * o2v_hip_set_triangles_device: the highest address the box and strides reach must lie inside its allocation; zero dims and
+ * BITS with strides[0] != 1 are refused.  The grid is written on the context's stream; the call returns when the writes have
+ * landed (the caller must have finished clearing dst before). */
+int o2v_hip_write_dense(o2v_hip_ctx *ctx, void *dst, uint32_t format, const uint32_t origin[3], const uint32_t dims[3],
+                        const uint64_t strides[3], uint64_t *out_outside);
+/* The tight box [lo, hi) of the last call's records, reduced on the device; lo = hi = 0 when there are none. */
+int o2v_hip_voxels_box(o2v_hip_ctx *ctx, uint32_t lo[3], uint32_t hi[3]);
+
 int o2v_hip_get_timings(const o2v_hip_ctx *ctx, o2v_hip_timings *out);
 /* Per-kernel device times of the last o2v_hip_voxelize call made with O2V_HIP_FLAG_KERNEL_TIMES (else none): up to
  * max_entries entries are written, *out_count receives how many there are. */

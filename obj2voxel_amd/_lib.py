@@ -3,6 +3,7 @@ missing, importing the bindings fails loudly."""
 import ctypes as C
 import os
 import subprocess
+import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libobj2voxel_amd.so")
@@ -21,15 +22,20 @@ def build(force=False):
 
 
 _lib = None
+# Whether torch was imported when the library was loaded.  The library links the HIP runtime by its versioned name, torch by
+# its unversioned one: loaded before torch, the two resolve to separate runtime copies that cannot share device memory
+# (obj2voxel_amd.dense refuses to work then).
+torch_was_loaded_first = None
 
 
 def lib():
-    global _lib
+    global _lib, torch_was_loaded_first
     if _lib is None:
         path = os.environ.get("O2V_LIB") or LIB_PATH  # O2V_LIB: a developer build (e.g. the instrumented library)
         if not os.path.exists(path):
             raise ImportError(
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(obj2voxel_amd has no CPU fallback)")
+        torch_was_loaded_first = "torch" in sys.modules
         _lib = C.CDLL(path)
     return _lib

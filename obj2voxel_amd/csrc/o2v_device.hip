@@ -24,6 +24,7 @@
 //       k_pick / k_emit_max    direct MAX path: winner colours of textured meshes; the 64-bit max grid -> records
 //   K6  k_fill_*               O2V_HIP_FLAG_FILL_INTERIOR: parity crossings per column of the pass box, prefix XOR along z,
 //                              the surface cells removed, interior records appended behind the surface records
+//   K7  k_gather_tris, k_dense_* device-resident input (positions + faces) and dense output grids; outside the pipeline
 //   plan k_zhist               o2v_hip_plan_slabs: predicted hits per z layer -> work-balanced slabs for N GPUs
 // With the direct MAX path K1's counters reach the host while K2 runs, and only the stages that have work are enqueued
 // behind it.  N > 1 GPUs: o2v_hip_voxelize_sharded (bounds / work-histogram passes sharded over the ranks, RCCL).
@@ -65,6 +66,7 @@ namespace {
 #include "o2v_dev_k5_scan_scatter.hpp"
 #include "o2v_dev_k3_resolve.hpp"
 #include "o2v_dev_k6_fill.hpp"
+#include "o2v_dev_k7_dense.hpp"
 
 }  // namespace
 
@@ -236,6 +238,9 @@ struct o2v_hip_ctx {
     hipEvent_t ev_fill[2] = {nullptr, nullptr};  // around the stage (O2V_HIP_FLAG_STAGE_TIMES)
     bool maxgrid_dirty = false;
     bool grid_dirty = false;
+    // K7 (o2v_hip_set_triangles_device, o2v_hip_write_dense, o2v_hip_voxels_box): flags and sums, allocated on first use
+    DevArray<DenseCtr> d_dense;
+    PinnedArray<DenseCtr> h_dense;
 
     // results of the last run
     uint64_t n_vox = 0;
@@ -2205,6 +2210,202 @@ int o2v_hip_voxels_device_ptr(o2v_hip_ctx *ctx, const uint32_t **out_ptr, uint64
     if (!ctx || !out_ptr || !out_count) return O2V_HIP_ERR_BAD_ARGUMENT;
     *out_ptr = reinterpret_cast<const uint32_t *>(ctx->d_out.ptr);
     *out_count = ctx->n_vox;
+    return O2V_HIP_OK;
+}
+
+}  // extern "C"
+
+// ---- K7: device-resident input, dense output -------------------------------------------------------------------------
+
+namespace {
+
+// [p, p + bytes) must be device (or managed) memory of the context's device and lie inside one allocation.  A pointer the
+// runtime does not know leaves an error in its per-thread state, which is cleared here so that the next call does not see it.
+int check_device_range(o2v_hip_ctx *ctx, const void *p, uint64_t bytes, const char *what)
+{
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void) hipGetLastError();
+        ctx->err = std::string(what) + " is not memory the HIP runtime knows";
+        return O2V_HIP_ERR_BAD_ARGUMENT;
+    }
+    if ((a.type != hipMemoryTypeDevice && a.type != hipMemoryTypeManaged && !a.isManaged) || a.device != ctx->device) {
+        ctx->err = std::string(what) + " is not device memory of the context's device " + std::to_string(ctx->device);
+        return O2V_HIP_ERR_BAD_ARGUMENT;
+    }
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(p)) != hipSuccess) {
+        (void) hipGetLastError();
+        ctx->err = std::string(what) + ": the runtime does not know its allocation";
+        return O2V_HIP_ERR_BAD_ARGUMENT;
+    }
+    const uint64_t offset = (uint64_t) ((const char *) p - (const char *) base);
+    if (offset > size || bytes > size - offset) {
+        ctx->err = std::string(what) + ": " + std::to_string(bytes) + " bytes from its address extend past its allocation";
+        return O2V_HIP_ERR_BAD_ARGUMENT;
+    }
+    return O2V_HIP_OK;
+}
+
+int dense_ctr(o2v_hip_ctx *ctx)
+{
+    if (!ctx->d_dense.ptr) O2V_CHECK(ctx->d_dense.alloc(1));
+    if (!ctx->h_dense.ptr) O2V_CHECK(ctx->h_dense.alloc(1));
+    return O2V_HIP_OK;
+}
+
+uint32_t stream_grid(const o2v_hip_ctx *ctx, uint64_t items, uint32_t per_cu)
+{
+    return (uint32_t) std::max<uint64_t>(1, std::min<uint64_t>((uint64_t) ctx->num_cus * per_cu, (items + kBlock - 1) / kBlock));
+}
+
+}  // namespace
+
+extern "C" {
+
+int o2v_hip_set_triangles_device(o2v_hip_ctx *ctx, const float *positions, uint64_t n_positions, const void *faces,
+                                 uint32_t index_bytes, const float *uvs, const uint32_t *types, const float *colors,
+                                 const int32_t *texids, uint64_t count)
+{
+    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
+    if (count && !positions) {
+        ctx->err = "positions is null";
+        return O2V_HIP_ERR_BAD_ARGUMENT;
+    }
+    if (faces && index_bytes != 4 && index_bytes != 8) {
+        ctx->err = "index_bytes must be 4 or 8";
+        return O2V_HIP_ERR_BAD_ARGUMENT;
+    }
+    if (count >= (1ull << 29)) {
+        ctx->err = "triangle count must be below 2^29";
+        return O2V_HIP_ERR_LIMIT;
+    }
+    if (faces && count && n_positions == 0) {
+        ctx->err = "n_positions is 0 but there are faces";
+        return O2V_HIP_ERR_BAD_ARGUMENT;
+    }
+    if (faces && n_positions > (~0ull >> 4)) {
+        ctx->err = "n_positions is too large";
+        return O2V_HIP_ERR_BAD_ARGUMENT;
+    }
+    O2V_CHECK(hipSetDevice(ctx->device));
+    int rc;
+    if (count) {
+        if ((rc = check_device_range(ctx, positions, faces ? n_positions * 12u : count * 36u, "positions")) ||
+            (faces && (rc = check_device_range(ctx, faces, count * 3u * index_bytes, "faces"))) ||
+            (uvs && (rc = check_device_range(ctx, uvs, count * 24u, "uvs"))) ||
+            (types && (rc = check_device_range(ctx, types, count * 4u, "types"))) ||
+            (colors && (rc = check_device_range(ctx, colors, count * 12u, "colors"))) ||
+            (texids && (rc = check_device_range(ctx, texids, count * 4u, "texids"))) || (rc = dense_ctr(ctx)))
+            return rc;
+    }
+    if ((rc = o2v::ctx_alloc_triangles(ctx, count, uvs != nullptr, types != nullptr, colors != nullptr, texids != nullptr))) return rc;
+    if (count) {
+        hipStream_t s = ctx->stream;
+        DenseCtr *const ctr = ctx->d_dense.ptr;
+        O2V_CHECK(hipMemsetAsync(ctr, 0, sizeof(DenseCtr), s));
+        if (!faces) O2V_CHECK(hipMemcpyAsync(ctx->d_verts.ptr, positions, count * 36u, hipMemcpyDeviceToDevice, s));
+        else {
+            const uint32_t grid = stream_grid(ctx, (count + 3u) / 4u * 64u, 8u);  // (one wave per 64 triangles)
+            if (index_bytes == 4)
+                hipLaunchKernelGGL(k_gather_tris<int32_t>, dim3(grid), dim3(kBlock), 0, s, positions, n_positions,
+                                   static_cast<const int32_t *>(faces), count, ctx->d_verts.ptr, ctr);
+            else
+                hipLaunchKernelGGL(k_gather_tris<int64_t>, dim3(grid), dim3(kBlock), 0, s, positions, n_positions,
+                                   static_cast<const int64_t *>(faces), count, ctx->d_verts.ptr, ctr);
+        }
+        if (uvs) O2V_CHECK(hipMemcpyAsync(ctx->d_uvs.ptr, uvs, count * 24u, hipMemcpyDeviceToDevice, s));
+        if (types) {
+            O2V_CHECK(hipMemcpyAsync(ctx->d_types.ptr, types, count * 4u, hipMemcpyDeviceToDevice, s));
+            hipLaunchKernelGGL(k_any_textured, dim3(stream_grid(ctx, count, 4u)), dim3(kBlock), 0, s, types, count, ctr);
+        }
+        if (colors) O2V_CHECK(hipMemcpyAsync(ctx->d_colors.ptr, colors, count * 12u, hipMemcpyDeviceToDevice, s));
+        if (texids) O2V_CHECK(hipMemcpyAsync(ctx->d_texids.ptr, texids, count * 4u, hipMemcpyDeviceToDevice, s));
+        O2V_CHECK(hipGetLastError());
+        O2V_CHECK(hipMemcpyAsync(ctx->h_dense.ptr, ctr, sizeof(DenseCtr), hipMemcpyDeviceToHost, s));
+    }
+    // (the flags come back in the round trip the upload's hints make anyway)
+    if ((rc = o2v::ctx_finish_triangles(ctx, false, nullptr))) return rc;
+    if (!count) return O2V_HIP_OK;
+    if (ctx->h_dense.ptr->bad_index) {
+        if ((rc = o2v::ctx_alloc_triangles(ctx, 0, false, false, false, false)) || (rc = o2v::ctx_finish_triangles(ctx, false, nullptr)))
+            return rc;
+        ctx->err = "face index out of range: an index is negative, not below n_positions (" + std::to_string(n_positions) +
+                   ") or not below 2^32; the context holds no triangles";
+        return O2V_HIP_ERR_BAD_ARGUMENT;
+    }
+    ctx->any_textured = ctx->h_dense.ptr->textured != 0;
+    return O2V_HIP_OK;
+}
+
+int o2v_hip_write_dense(o2v_hip_ctx *ctx, void *dst, uint32_t format, const uint32_t origin[3], const uint32_t dims[3],
+                        const uint64_t strides[3], uint64_t *out_outside)
+{
+    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
+    if (!dst || !origin || !dims || !strides || format > O2V_HIP_DENSE_BITS) {
+        ctx->err = "o2v_hip_write_dense: null argument or unknown format";
+        return O2V_HIP_ERR_BAD_ARGUMENT;
+    }
+    if (!dims[0] || !dims[1] || !dims[2]) {
+        ctx->err = "o2v_hip_write_dense: zero dims";
+        return O2V_HIP_ERR_BAD_ARGUMENT;
+    }
+    if (format == O2V_HIP_DENSE_BITS && strides[0] != 1) {
+        ctx->err = "o2v_hip_write_dense: BITS needs strides[0] == 1";
+        return O2V_HIP_ERR_BAD_ARGUMENT;
+    }
+    // the highest element the box can reach, in bytes past dst (128-bit: the strides are the caller's)
+    const unsigned __int128 hx = format == O2V_HIP_DENSE_BITS ? (dims[0] - 1u) / 32u : (uint64_t) (dims[0] - 1u) * (unsigned __int128) strides[0];
+    const unsigned __int128 last = hx + (unsigned __int128) (dims[1] - 1u) * strides[1] + (unsigned __int128) (dims[2] - 1u) * strides[2];
+    const uint32_t elem = format == O2V_HIP_DENSE_U8 ? 1u : 4u;
+    const unsigned __int128 bytes = (last + 1u) * elem;
+    if (bytes > (unsigned __int128) (~0ull >> 1)) {
+        ctx->err = "o2v_hip_write_dense: the box and strides reach past any allocation";
+        return O2V_HIP_ERR_BAD_ARGUMENT;
+    }
+    O2V_CHECK(hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = check_device_range(ctx, dst, (uint64_t) bytes, "dst")) || (rc = dense_ctr(ctx))) return rc;
+    if (out_outside) *out_outside = 0;
+    const uint64_t n = ctx->n_vox;
+    if (!n) return O2V_HIP_OK;
+    hipStream_t s = ctx->stream;
+    DenseCtr *const ctr = ctx->d_dense.ptr;
+    const DenseBox b{origin[0], origin[1], origin[2], dims[0], dims[1], dims[2], strides[0], strides[1], strides[2]};
+    const uint64_t n_surf = n - std::min<uint64_t>(n, ctx->stats.interior_voxels);
+    O2V_CHECK(hipMemsetAsync(&ctr->outside, 0, sizeof(ctr->outside), s));
+    const dim3 grid(stream_grid(ctx, n, 8u));
+    if (format == O2V_HIP_DENSE_U8)
+        hipLaunchKernelGGL(k_dense_scatter<kDenseU8>, grid, dim3(kBlock), 0, s, ctx->d_out.ptr, n, n_surf, b, dst, ctr);
+    else if (format == O2V_HIP_DENSE_ARGB32)
+        hipLaunchKernelGGL(k_dense_scatter<kDenseArgb32>, grid, dim3(kBlock), 0, s, ctx->d_out.ptr, n, n_surf, b, dst, ctr);
+    else
+        hipLaunchKernelGGL(k_dense_scatter<kDenseBits>, grid, dim3(kBlock), 0, s, ctx->d_out.ptr, n, n_surf, b, dst, ctr);
+    O2V_CHECK(hipGetLastError());
+    O2V_CHECK(hipMemcpyAsync(&ctx->h_dense.ptr->outside, &ctr->outside, sizeof(ctr->outside), hipMemcpyDeviceToHost, s));
+    O2V_CHECK(hipStreamSynchronize(s));
+    if (out_outside) *out_outside = ctx->h_dense.ptr->outside;
+    return O2V_HIP_OK;
+}
+
+int o2v_hip_voxels_box(o2v_hip_ctx *ctx, uint32_t lo[3], uint32_t hi[3])
+{
+    if (!ctx || !lo || !hi) return O2V_HIP_ERR_BAD_ARGUMENT;
+    for (int a = 0; a < 3; ++a) lo[a] = hi[a] = 0;
+    const uint64_t n = ctx->n_vox;
+    if (!n) return O2V_HIP_OK;
+    O2V_CHECK(hipSetDevice(ctx->device));
+    if (const int rc = dense_ctr(ctx)) return rc;
+    hipStream_t s = ctx->stream;
+    DenseCtr *const ctr = ctx->d_dense.ptr;
+    O2V_CHECK(hipMemsetAsync(ctr->lo, 0xff, sizeof(ctr->lo), s));
+    O2V_CHECK(hipMemsetAsync(ctr->hi, 0, sizeof(ctr->hi), s));
+    hipLaunchKernelGGL(k_dense_box, dim3(stream_grid(ctx, n, 4u)), dim3(kBlock), 0, s, ctx->d_out.ptr, n, ctr);
+    O2V_CHECK(hipGetLastError());
+    O2V_CHECK(hipMemcpyAsync(ctx->h_dense.ptr->lo, ctr->lo, sizeof(ctr->lo) + sizeof(ctr->hi), hipMemcpyDeviceToHost, s));
+    O2V_CHECK(hipStreamSynchronize(s));
+    for (int a = 0; a < 3; ++a) lo[a] = ctx->h_dense.ptr->lo[a], hi[a] = ctx->h_dense.ptr->hi[a] + 1u;
     return O2V_HIP_OK;
 }
 

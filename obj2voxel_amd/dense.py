@@ -1,0 +1,193 @@
+"""Dense torch grids from device-resident meshes.
+
+    import torch
+    from obj2voxel_amd import dense, hip
+    dv = hip.DeviceVoxelizer(0)
+    dense.set_mesh(dv, positions, faces)                   # cuda tensors [V, 3] float32, [F, 3] int32 / int64
+    grid, origin = dense.voxelize_dense(dv, 256, fill=True)   # bool (256, 256, 256), indexed [z, y, x]
+
+The mesh goes to the device context without a host copy (o2v_hip_set_triangles_device) and the voxels come back as a dense
+tensor written on the device (o2v_hip_write_dense); nothing of either crosses to the host.
+
+torch is imported first on purpose: the library must bind to the HIP runtime torch loaded (a process that loaded the library
+before torch holds two separate runtime copies, and this module refuses to work there).
+"""
+import torch  # first: see above
+
+from . import hip
+
+FORMATS = {  # name: (o2v_hip_write_dense format, tensor dtype)
+    "occupancy": (hip.DENSE_U8, torch.bool),
+    "labels": (hip.DENSE_U8, torch.uint8),
+    "argb": (hip.DENSE_ARGB32, torch.int32),
+    "bits": (hip.DENSE_BITS, torch.int32),
+}
+STRATEGIES = {"max": hip.STRATEGY_MAX, "blend": hip.STRATEGY_BLEND}
+MAX_SAMPLES = 65535  # samples per axis of one pass (x / y tiles above that are not supported here)
+
+
+def _require_shared_runtime():
+    if hip.torch_was_loaded_first() is False:
+        raise RuntimeError("obj2voxel_amd.dense: libobj2voxel_amd.so was loaded in this process before torch, so the two use "
+                           "separate HIP runtimes and cannot share device memory; import torch before obj2voxel_amd's bindings")
+
+
+def _device(dv):
+    return torch.device("cuda", 0 if dv.device is None else dv.device)
+
+
+def _sync(device):
+    """Everything torch has queued on its current stream of `device` has run (the library reads and writes on its own stream)."""
+    torch.cuda.current_stream(device).synchronize()
+
+
+def _check(t, name, dtypes, shape, device):
+    """t as a contiguous tensor, after its dtype, shape (None = any length) and device are checked."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch tensor")
+    if t.dtype not in dtypes:
+        raise TypeError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, not {t.dtype}")
+    if t.dim() != len(shape) or any(want is not None and have != want for have, want in zip(t.shape, shape)):
+        raise ValueError(f"{name} must have shape {tuple('*' if s is None else s for s in shape)}, not {tuple(t.shape)}")
+    if t.device != device:
+        raise ValueError(f"{name} is on {t.device}, the voxelizer on {device}")
+    return t.contiguous()
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def set_mesh(dv, positions, faces=None, *, uvs=None, types=None, colors=None, texids=None):
+    """The mesh of the next voxelize calls of `dv` (a hip.DeviceVoxelizer), from tensors on its device: positions float32
+    [V, 3] and faces int32 / int64 [F, 3], or positions [F, 9] and no faces.  uvs float32 [F, 6], types int32 [F] (hip.TRI_*),
+    colors float32 [F, 3] and texids int32 [F] are per triangle and optional.  An out-of-range face index raises
+    hip.DeviceError and leaves `dv` without triangles."""
+    _require_shared_runtime()
+    device = _device(dv)
+    if faces is None:
+        positions = _check(positions, "positions", (torch.float32,), (None, 9), device)
+        count, n_positions, index_bytes = positions.shape[0], 0, 0
+    else:
+        positions = _check(positions, "positions", (torch.float32,), (None, 3), device)
+        faces = _check(faces, "faces", (torch.int32, torch.int64), (None, 3), device)
+        count, n_positions, index_bytes = faces.shape[0], positions.shape[0], faces.element_size()
+    if uvs is not None:
+        uvs = _check(uvs, "uvs", (torch.float32,), (count, 6), device)
+    if types is not None:
+        types = _check(types, "types", (torch.int32,), (count,), device)
+    if colors is not None:
+        colors = _check(colors, "colors", (torch.float32,), (count, 3), device)
+    if texids is not None:
+        texids = _check(texids, "texids", (torch.int32,), (count,), device)
+    _sync(device)
+    dv.set_triangles_device(_ptr(positions) if count else None, n_positions, _ptr(faces) if count else None, index_bytes, count,
+                            _ptr(uvs), _ptr(types), _ptr(colors), _ptr(texids))
+
+
+def _layout(t, fmt):
+    """(write_dense strides x, y, z) of a 3-D tensor indexed [z, y, x]: elements, or 32-bit words for bits."""
+    if fmt == "bits" and t.stride(2) != 1:
+        raise ValueError("a bits grid needs unit stride along x (its last dimension)")
+    return t.stride(2), t.stride(1), t.stride(0)
+
+
+def voxelize_dense(dv, resolution, *, fmt="occupancy", box="grid", out=None, origin=None, supersampling=1, strategy="max",
+                   fill=False, fill_argb=0xFFFFFFFF, unit_transform=None, bounds=None, max_layers=None):
+    """Voxelizes the mesh of `dv` (set_mesh) and returns (tensor, origin): voxel (x, y, z) is tensor[z - oz, y - oy, x - ox],
+    origin = (ox, oy, oz).
+
+    fmt:  "occupancy" bool, "labels" uint8 (1 surface, 2 interior with fill=True), "argb" int32 (the voxel's 0xAARRGGBB bits;
+          not an occupancy: a texel of alpha 0 gives 0), "bits" int32 [nz, ny, ceil(nx / 32)], bit x % 32 of word x / 32.
+    box:  "grid" the whole resolution^3 grid at origin 0 (or `origin`), "tight" the voxels' own box.
+    out:  a 3-D tensor (any strides, e.g. a slice of a batch) of the format's dtype on the voxelizer's device, written as it
+          is and not cleared; its shape is the box's extent.  Otherwise a new zeroed contiguous tensor.
+    A grid whose dense stage does not fit the device runs as consecutive z-slabs (o2v_hip_max_slab_layers; max_layers caps
+    their height), all written into the one tensor.  A voxel outside the tensor's box raises."""
+    _require_shared_runtime()
+    if fmt not in FORMATS:
+        raise ValueError(f"fmt must be one of {sorted(FORMATS)}, not {fmt!r}")
+    if box not in ("grid", "tight"):
+        raise ValueError(f"box must be 'grid' or 'tight', not {box!r}")
+    if strategy not in STRATEGIES:
+        raise ValueError(f"strategy must be 'max' or 'blend', not {strategy!r}")
+    if resolution < 1 or supersampling not in (1, 2):
+        raise ValueError("resolution must be positive and supersampling 1 or 2")
+    if resolution * supersampling > MAX_SAMPLES:
+        raise ValueError(f"resolution x supersampling = {resolution * supersampling} is above {MAX_SAMPLES}: x / y tiles are not "
+                         "supported by the dense path")
+    if box == "tight" and origin is not None:
+        raise ValueError("origin is given by the voxels with box='tight'")
+    if max_layers is not None and max_layers < 1:
+        raise ValueError("max_layers must be positive")
+    code, dtype = FORMATS[fmt]
+    device = _device(dv)
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dim() != 3:
+            raise ValueError("out must be a 3-D tensor [z, y, x]")
+        if out.dtype != dtype:
+            raise TypeError(f"out must be {dtype} for fmt={fmt!r}, not {out.dtype}")
+        if out.device != device:
+            raise ValueError(f"out is on {out.device}, the voxelizer on {device}")
+        _layout(out, fmt)
+    kw = dict(supersampling=supersampling, strategy=STRATEGIES[strategy], unit_transform=unit_transform, fill=fill)
+
+    # z-slabs: one pass if the grid fits
+    layers = dv.max_slab_layers(resolution, bounds=bounds, **kw)
+    if max_layers is not None:
+        layers = min(layers, max(4, max_layers // 4 * 4))
+    if layers == 0:
+        raise hip.DeviceError(f"resolution {resolution}: not even one 4-layer slab of the dense grid fits the device memory")
+    if layers >= resolution:
+        slabs = [(0, 0)]
+    else:
+        slabs = [(z, min(resolution, z + layers)) for z in range(0, resolution, layers)]
+        if bounds is None:   # (the mesh bounds once for all slabs, as obj2voxel_voxelize() does)
+            _, bounds = dv.plan_slabs(resolution, 1, supersampling=supersampling, unit_transform=unit_transform)
+
+    def run(zslab):
+        return dv.voxelize(resolution, zslab=zslab, bounds=bounds, read=False, fill_argb=fill_argb, **kw)
+
+    held = None   # the slab whose records the context still holds
+    if box == "tight":
+        lo, hi = [resolution] * 3, [0] * 3
+        for zslab in slabs:
+            if run(zslab):
+                a, b = dv.voxels_box()
+                lo, hi = [min(p, q) for p, q in zip(lo, a)], [max(p, q) for p, q in zip(hi, b)]
+            held = zslab
+        if hi[0] == 0:
+            lo = hi = [0, 0, 0]
+        origin, dims = tuple(lo), tuple(h - l for h, l in zip(hi, lo))
+    else:
+        origin = tuple(int(v) for v in (origin or (0, 0, 0)))
+        dims = (resolution,) * 3 if out is None else None
+    if out is None:
+        nz, ny, nx = dims[2], dims[1], dims[0]
+        shape = (nz, ny, (nx + 31) // 32) if fmt == "bits" else (nz, ny, nx)
+        out = torch.zeros(shape, dtype=dtype, device=device)
+    else:
+        nz, ny, nx = out.shape
+        if fmt == "bits":
+            nx *= 32
+        if dims is not None and box == "tight" and (nx < dims[0] or ny < dims[1] or nz < dims[2]):
+            raise ValueError(f"out {tuple(out.shape)} is smaller than the voxels' box {dims[::-1]} [z, y, x]")
+    if 0 in out.shape:
+        if dims is not None and 0 in dims:
+            return out, origin
+        raise ValueError("out has an empty dimension")
+    strides = _layout(out, fmt)
+    # the grid as U8 for occupancy: a bool holds 0 / 1, so interior labels (2) are folded back to 1 below
+    target = out.view(torch.uint8) if fmt == "occupancy" else out
+    _sync(device)   # (torch.zeros / the caller's writes to `out` have landed)
+    interior = 0
+    for zslab in ([held] if held else []) + [z for z in slabs if z != held]:
+        if (dv.count if zslab == held else run(zslab)) == 0:
+            continue
+        interior += dv.stats()["interior_voxels"]
+        outside = dv.write_dense(target.data_ptr(), code, origin, (nx, ny, nz), strides)
+        if outside:
+            raise ValueError(f"{outside} voxels lie outside the tensor's box (origin {origin}, extent {(nx, ny, nz)} [x, y, z])")
+    if fmt == "occupancy" and interior:
+        target.clamp_(max=1)
+    return out, origin

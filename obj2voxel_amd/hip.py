@@ -3,6 +3,7 @@ import ctypes as C
 
 import numpy as np
 
+from . import _lib
 from ._lib import lib
 
 TRI_MATERIALLESS, TRI_UNTEXTURED, TRI_TEXTURED = 1, 2, 3
@@ -21,6 +22,8 @@ FLAG_KERNEL_TIMES = 2  # ... every launch bracketed by events: DeviceVoxelizer.k
 FLAG_STAGE_TIMES = 4   # ... an event between the stages of a pass: the stage times and total_ms of DeviceVoxelizer.timings()
 FLAG_EXACT_CLIP = 1  # o2v_hip_params::flags: the clip kernel without its work-removal shortcuts (include/o2v_hip.h)
 FLAG_FILL_INTERIOR = 8  # ... solid voxelization: the interior voxels (colour fill_argb) behind the surface records
+DENSE_U8, DENSE_ARGB32, DENSE_BITS = 0, 1, 2  # o2v_hip_write_dense formats
+ERR_BAD_ARGUMENT = 3
 
 
 class _Texture(C.Structure):
@@ -104,7 +107,17 @@ def _bind():
     L.o2v_mesh_arrays.restype = C.c_uint64
     L.o2v_mesh_texture.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(_Texture)]
     L.o2v_mesh_free.argtypes = [C.c_void_p]
+    L.o2v_hip_set_triangles_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32] + [C.c_void_p] * 4 + [C.c_uint64]
+    L.o2v_hip_write_dense.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    L.o2v_hip_voxels_box.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.o2v_hip_max_slab_layers.argtypes = [C.c_void_p, C.POINTER(_Params), C.POINTER(C.c_uint32)]
     return L
+
+
+def torch_was_loaded_first():
+    """True if torch was imported before this process loaded the library (the two then share one HIP runtime), False if not,
+    None if the library is not loaded yet."""
+    return _lib.torch_was_loaded_first
 
 
 def build_id():
@@ -160,6 +173,7 @@ class DeviceVoxelizer:
     def __init__(self, device=0, _borrowed_ctx=None):
         self._L = _bind()
         self._owned = _borrowed_ctx is None
+        self.device = None if _borrowed_ctx is not None else device
         self._n_out = C.c_uint64(0)
         if _borrowed_ctx is not None:       # a rank of a DeviceGroup: the group owns the context
             self._ctx = C.c_void_p(_borrowed_ctx)
@@ -195,6 +209,35 @@ class DeviceVoxelizer:
         self._check(self._L.o2v_hip_set_triangles(self._ctx, _ptr(verts), _ptr(uvs), _ptr(types), _ptr(colors),
                                                   _ptr(texids), T), "o2v_hip_set_triangles")
         self.n_tris = T
+
+    def set_triangles_device(self, positions_ptr, n_positions, faces_ptr, index_bytes, count, uvs_ptr=None, types_ptr=None,
+                             colors_ptr=None, texids_ptr=None):
+        """o2v_hip_set_triangles_device: the arrays of set_triangles as device addresses (integers) on this context's device.
+        faces_ptr None: positions_ptr is [count, 9] float32.  Else positions [n_positions, 3] float32 and faces [count, 3] of
+        index_bytes (4 or 8).  The caller must have finished writing the arrays."""
+        rc = self._L.o2v_hip_set_triangles_device(self._ctx, positions_ptr, n_positions, faces_ptr, index_bytes, uvs_ptr, types_ptr,
+                                                  colors_ptr, texids_ptr, count)
+        if rc == 0:
+            self.n_tris = count
+        elif "face index" in self._L.o2v_hip_last_error(self._ctx).decode():
+            self.n_tris = 0   # (the context was left with no triangles)
+        self._check(rc, "o2v_hip_set_triangles_device")
+
+    def write_dense(self, ptr, fmt, origin, dims, strides):
+        """o2v_hip_write_dense: the last voxelize call's records into the dense grid at device address `ptr` (DENSE_U8 /
+        DENSE_ARGB32 / DENSE_BITS; origin, dims, strides per axis x, y, z).  Returns the number of records outside the box."""
+        o = (C.c_uint32 * 3)(*[int(v) for v in origin])
+        d = (C.c_uint32 * 3)(*[int(v) for v in dims])
+        s = (C.c_uint64 * 3)(*[int(v) for v in strides])
+        outside = C.c_uint64(0)
+        self._check(self._L.o2v_hip_write_dense(self._ctx, ptr, fmt, o, d, s, C.byref(outside)), "o2v_hip_write_dense")
+        return outside.value
+
+    def voxels_box(self):
+        """o2v_hip_voxels_box: ((lo x, y, z), (hi x, y, z)), the last call's records' box [lo, hi); zeros if there are none."""
+        lo, hi = (C.c_uint32 * 3)(), (C.c_uint32 * 3)()
+        self._check(self._L.o2v_hip_voxels_box(self._ctx, lo, hi), "o2v_hip_voxels_box")
+        return tuple(lo), tuple(hi)
 
     def set_textures(self, textures):
         """textures: sequence of (uint8 [h, w, c] pixels, wrap) with c in (3, 4)."""
@@ -233,6 +276,13 @@ class DeviceVoxelizer:
         bnd = np.zeros(6, dtype=np.float32)
         self._check(self._L.o2v_hip_plan_slabs(self._ctx, C.byref(p), n_slabs, _ptr(cuts), _ptr(bnd)), "o2v_hip_plan_slabs")
         return [int(z) for z in cuts], bnd
+
+    def max_slab_layers(self, resolution, *, supersampling=1, strategy=STRATEGY_MAX, unit_transform=None, bounds=None, fill=False):
+        """o2v_hip_max_slab_layers: the thickest z-slab (output layers) a voxelize call of these settings fits the device with."""
+        p = self._params(resolution, supersampling, strategy, unit_transform, bounds, (0, 0), FLAG_FILL_INTERIOR if fill else 0)
+        layers = C.c_uint32(0)
+        self._check(self._L.o2v_hip_max_slab_layers(self._ctx, C.byref(p), C.byref(layers)), "o2v_hip_max_slab_layers")
+        return layers.value
 
     def voxelize(self, resolution, *, supersampling=1, strategy=STRATEGY_MAX, unit_transform=None, bounds=None,
                  zslab=(0, 0), read=True, exact_clip=False, kernel_times=False, stage_times=False, xtile=(0, 0), ytile=(0, 0),

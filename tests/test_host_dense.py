@@ -1,0 +1,198 @@
+"""obj2voxel_amd.dense without a GPU: the argument checks of the torch layer and its z-slab loop, with the device calls
+stubbed; and a static check of the K7 kernels in the gfx950 code object (hipcc cross-compiles)."""
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+from obj2voxel_amd import dense, hip  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "obj2voxel_amd", "csrc")
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+CPU = torch.device("cpu")
+
+
+class StubVoxelizer:
+    """Records the device calls dense.py makes.  voxelize returns `n` records per slab with box [lo, hi)."""
+
+    def __init__(self, n=10, layers=1 << 30, lo=(1, 2, 3), hi=(5, 6, 7), outside=0, interior=0):
+        self.device, self.calls, self.n, self.layers = None, [], n, layers
+        self.lo, self.hi, self.outside, self.interior = lo, hi, outside, interior
+        self.count = 0
+
+    def set_triangles_device(self, *args):
+        self.calls.append(("set", args))
+
+    def max_slab_layers(self, resolution, **kw):
+        return self.layers
+
+    def plan_slabs(self, resolution, n, **kw):
+        self.calls.append(("plan", resolution))
+        return [0, resolution], np.zeros(6, np.float32)
+
+    def voxelize(self, resolution, *, zslab, read, **kw):
+        self.calls.append(("voxelize", zslab, kw.get("fill")))
+        self.count = self.n
+        return self.n
+
+    def voxels_box(self):
+        return self.lo, self.hi
+
+    def stats(self):
+        return {"interior_voxels": self.interior}
+
+    def write_dense(self, ptr, fmt, origin, dims, strides):
+        self.calls.append(("write", fmt, tuple(origin), tuple(dims), tuple(strides)))
+        return self.outside
+
+
+@pytest.fixture(autouse=True)
+def on_cpu(monkeypatch):
+    monkeypatch.setattr(dense, "_device", lambda dv: CPU)
+    monkeypatch.setattr(dense, "_sync", lambda device: None)
+    monkeypatch.setattr(hip, "torch_was_loaded_first", lambda: True)
+
+
+def test_set_mesh_indexed_and_flat():
+    dv = StubVoxelizer()
+    p, f = torch.zeros((5, 3)), torch.zeros((4, 3), dtype=torch.int64)
+    dense.set_mesh(dv, p, f, types=torch.zeros(4, dtype=torch.int32))
+    _, args = dv.calls[-1]
+    assert args[1] == 5 and args[3] == 8 and args[4] == 4 and args[6] is not None and args[5] is None
+    dense.set_mesh(dv, torch.zeros((4, 9)), colors=torch.zeros((4, 3)))
+    _, args = dv.calls[-1]
+    assert args[2] is None and args[3] == 0 and args[4] == 4 and args[7] is not None
+    # a non-contiguous view is made contiguous
+    dense.set_mesh(dv, torch.zeros((3, 5)).t(), f.to(torch.int32))
+    assert dv.calls[-1][1][3] == 4
+
+
+@pytest.mark.parametrize("bad, exc", [
+    (dict(positions=torch.zeros((5, 3), dtype=torch.float64)), TypeError),
+    (dict(positions=torch.zeros((5, 4))), ValueError),
+    (dict(faces=torch.zeros((4, 3), dtype=torch.int16)), TypeError),
+    (dict(faces=torch.zeros((4, 2), dtype=torch.int32)), ValueError),
+    (dict(uvs=torch.zeros((3, 6))), ValueError),
+    (dict(types=torch.zeros(4, dtype=torch.int64)), TypeError),
+    (dict(colors=torch.zeros((4, 4))), ValueError),
+    (dict(texids=torch.zeros((4, 1), dtype=torch.int32)), ValueError),
+    (dict(positions=np.zeros((5, 3), np.float32)), TypeError),
+])
+def test_set_mesh_rejects(bad, exc):
+    kw = dict(positions=torch.zeros((5, 3)), faces=torch.zeros((4, 3), dtype=torch.int32))
+    kw.update(bad)
+    dv = StubVoxelizer()
+    with pytest.raises(exc):
+        dense.set_mesh(dv, kw.pop("positions"), kw.pop("faces"), **kw)
+    assert not dv.calls
+
+
+def test_set_mesh_refuses_a_device_mismatch(monkeypatch):
+    monkeypatch.setattr(dense, "_device", lambda dv: torch.device("cuda", 1))
+    with pytest.raises(ValueError, match="voxelizer"):
+        dense.set_mesh(StubVoxelizer(), torch.zeros((5, 3)), torch.zeros((4, 3), dtype=torch.int32))
+
+
+def test_refused_when_the_library_came_first(monkeypatch):
+    monkeypatch.setattr(hip, "torch_was_loaded_first", lambda: False)
+    with pytest.raises(RuntimeError, match="before torch"):
+        dense.voxelize_dense(StubVoxelizer(), 8)
+    with pytest.raises(RuntimeError, match="before torch"):
+        dense.set_mesh(StubVoxelizer(), torch.zeros((1, 9)))
+
+
+@pytest.mark.parametrize("fmt, dtype, shape", [("occupancy", torch.bool, (16, 16, 16)), ("labels", torch.uint8, (16, 16, 16)),
+                                               ("argb", torch.int32, (16, 16, 16)), ("bits", torch.int32, (16, 16, 1))])
+def test_default_tensors(fmt, dtype, shape):
+    dv = StubVoxelizer()
+    t, origin = dense.voxelize_dense(dv, 16, fmt=fmt)
+    assert t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and origin == (0, 0, 0)
+    w = [c for c in dv.calls if c[0] == "write"]
+    assert len(w) == 1
+    _, code, o, dims, strides = w[0]
+    assert code == dense.FORMATS[fmt][0] and o == (0, 0, 0)
+    assert dims == (16, 16, 16)
+    assert strides == (1, shape[2], shape[1] * shape[2])
+
+
+def test_tight_box_and_out_views():
+    dv = StubVoxelizer(lo=(1, 2, 3), hi=(5, 8, 12))
+    t, origin = dense.voxelize_dense(dv, 16, box="tight")
+    assert origin == (1, 2, 3) and tuple(t.shape) == (9, 6, 4)
+    assert [c[0] for c in dv.calls] == ["voxelize", "write"]   # (one pass: its records are written without a second run)
+    batch = torch.zeros((2, 16, 16, 16), dtype=torch.uint8)
+    dv = StubVoxelizer()
+    out, _ = dense.voxelize_dense(dv, 16, fmt="labels", out=batch[1].permute(1, 0, 2))
+    assert out.data_ptr() == batch[1].data_ptr()
+    assert dv.calls[-1][4] == (1, 256, 16)
+
+
+@pytest.mark.parametrize("kw, exc", [
+    (dict(fmt="rgb"), ValueError), (dict(box="loose"), ValueError), (dict(strategy="min"), ValueError),
+    (dict(supersampling=3), ValueError), (dict(resolution=40000, supersampling=2), ValueError),
+    (dict(resolution=65536), ValueError), (dict(box="tight", origin=(0, 0, 0)), ValueError), (dict(max_layers=0), ValueError),
+    (dict(out=torch.zeros((16, 16), dtype=torch.bool)), ValueError), (dict(out=torch.zeros((16, 16, 16), dtype=torch.uint8)), TypeError),
+    (dict(fmt="bits", out=torch.zeros((16, 1, 16), dtype=torch.int32).permute(0, 2, 1)), ValueError),
+    (dict(fmt="argb", out=torch.zeros((16, 16, 16), dtype=torch.float32)), TypeError),
+])
+def test_voxelize_dense_rejects(kw, exc):
+    dv = StubVoxelizer()
+    res = kw.pop("resolution", 16)
+    with pytest.raises(exc):
+        dense.voxelize_dense(dv, res, **kw)
+    assert not [c for c in dv.calls if c[0] in ("voxelize", "write")]
+
+
+def test_records_outside_the_tensor_raise():
+    with pytest.raises(ValueError, match="outside"):
+        dense.voxelize_dense(StubVoxelizer(outside=3), 16)
+
+
+def test_slabs_cover_the_grid_once():
+    dv = StubVoxelizer(layers=1 << 20, interior=5)
+    t, _ = dense.voxelize_dense(dv, 30, max_layers=9, fill=True)
+    vox = [c[1] for c in dv.calls if c[0] == "voxelize"]
+    assert vox == [(0, 8), (8, 16), (16, 24), (24, 30)]
+    assert len([c for c in dv.calls if c[0] == "write"]) == 4
+    assert ("plan", 30) in dv.calls      # the mesh bounds once, for every slab
+    dv = StubVoxelizer(layers=12)
+    dense.voxelize_dense(dv, 30, box="tight")
+    vox = [c[1] for c in dv.calls if c[0] == "voxelize"]
+    # the boxes of all slabs, then the writes: the last slab's records are still there and go first
+    assert vox == [(0, 12), (12, 24), (24, 30), (0, 12), (12, 24)]
+
+
+def test_empty_result_tight():
+    t, origin = dense.voxelize_dense(StubVoxelizer(n=0), 16, box="tight")
+    assert tuple(t.shape) == (0, 0, 0) and origin == (0, 0, 0)
+
+
+@pytest.fixture(scope="module")
+def device_asm(tmp_path_factory):
+    if not os.path.exists(HIPCC):
+        pytest.skip("hipcc not available")
+    out = tmp_path_factory.mktemp("isa_dense") / "o2v_device.s"
+    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-function",
+           "--cuda-device-only", "-S", "o2v_device.hip", "-o", str(out)]
+    subprocess.run(cmd, cwd=SRC, check=True, capture_output=True)
+    return out.read_text()
+
+
+@pytest.mark.parametrize("kernel", ["k_gather_trisIi", "k_gather_trisIl", "k_any_textured", "k_dense_scatterILj0E", "k_dense_scatterILj1E",
+                                    "k_dense_scatterILj2E", "k_dense_box"])
+def test_k7_kernels_in_the_code_object_without_scratch(device_asm, kernel):
+    m = re.search(r"^(_ZN\S*" + kernel + r"\S*):[^\n]*\n(.*?)^\.Lfunc_end", device_asm, re.M | re.S)
+    assert m, kernel + " is not in the gfx950 code object"
+    body = m.group(2)
+    scratch = re.findall(r"; ScratchSize: (\d+)", device_asm[m.end():m.end() + 4000])
+    assert scratch and scratch[0] == "0", scratch[:1]
+    assert "scratch_" not in body and "buffer_store_dword v" not in body.replace("buffer_store_dwordx", "")
+    if "scatter" in kernel or "box" in kernel:
+        # one vector load per record (x, y, z, argb; the compiler leaves out argb where it is unused: 12 bytes of the 16)
+        assert re.search(r"global_load_dwordx[34]", body) and not re.search(r"global_load_dword\s", body)

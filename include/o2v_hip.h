@@ -273,6 +273,30 @@ int o2v_hip_write_dense(o2v_hip_ctx *ctx, void *dst, uint32_t format, const uint
 /* The tight box [lo, hi) of the last call's records, reduced on the device; lo = hi = 0 when there are none. */
 int o2v_hip_voxels_box(o2v_hip_ctx *ctx, uint32_t lo[3], uint32_t hi[3]);
 
+/* ---- distance grids --------------------------------------------------------------------------
+ *
+ * The exact Euclidean distance transform of a U8 label grid L in device memory (0 empty, 1 surface, 2 interior: what
+ * o2v_hip_write_dense U8 writes) over the box dims = (nx, ny, nz).  Voxel (x, y, z) is labels[x * label_strides[0] +
+ * y * label_strides[1] + z * label_strides[2]] and dst[x * dst_strides[0] + ...] (strides in elements, any order).  With S the
+ * surface voxels (L == 1),
+ *   d2(v) = min over s in S of (vx - sx)^2 + (vy - sy)^2 + (vz - sz)^2,  exact integers in voxel units, over the box only;
+ *   DIST2 (int32):  d2(v); 0 on the surface; 0x7FFFFFFF everywhere if S is empty;
+ *   SDF (float32):  sgn(v) * (float) sqrt((double) d2(v)), sgn = -1 where L == 2 and +1 elsewhere; +-inf if S is empty.
+ * The call is refused with O2V_HIP_ERR_LIMIT when (nx-1)^2 + (ny-1)^2 + (nz-1)^2 is above 2^31 - 2, and with
+ * O2V_HIP_ERR_BAD_ARGUMENT for zero dims, an unknown format, overlapping labels and dst ranges, dst_strides that map two
+ * voxels of the box to one element (e.g. a stride of 0 on an axis of more than one voxel), or a pointer that is not device
+ * memory of the context's device with the box's highest address inside its allocation: all before anything is launched.
+ * Every voxel of the box in dst is written (the intermediate passes use dst itself); labels is only read.  The envelope stacks
+ * are scratch of the context, o2v_hip_distance_scratch_bytes(dims, format) bytes = 8 x the larger of min(nx * nz, 2^17) * ny
+ * (the y pass) and min(nx * ny, 2^17) * nz (the z pass), grown on demand; if it cannot be allocated the call returns O2V_HIP_ERR_OUT_OF_MEMORY and the context stays usable.  The grid is read and written
+ * on the context's stream; the call returns when the writes have landed (the caller must have finished writing labels). */
+enum { O2V_HIP_DIST_SQ_I32 = 0, O2V_HIP_DIST_SDF_F32 = 1 };
+int o2v_hip_distance_dense(o2v_hip_ctx *ctx, const void *labels, const uint64_t label_strides[3], void *dst, uint32_t format,
+                           const uint64_t dst_strides[3], const uint32_t dims[3]);
+uint64_t o2v_hip_distance_scratch_bytes(const uint32_t dims[3], uint32_t format);
+/* The device times of the last o2v_hip_distance_dense call's three passes (x, y, z), from events around each, in ms. */
+int o2v_hip_distance_times(const o2v_hip_ctx *ctx, float out_ms[3]);
+
 int o2v_hip_get_timings(const o2v_hip_ctx *ctx, o2v_hip_timings *out);
 /* Per-kernel device times of the last o2v_hip_voxelize call made with O2V_HIP_FLAG_KERNEL_TIMES (else none): up to
  * max_entries entries are written, *out_count receives how many there are. */

@@ -25,6 +25,7 @@
 //   K6  k_fill_*               O2V_HIP_FLAG_FILL_INTERIOR: parity crossings per column of the pass box, prefix XOR along z,
 //                              the surface cells removed, interior records appended behind the surface records
 //   K7  k_gather_tris, k_dense_* device-resident input (positions + faces) and dense output grids; outside the pipeline
+//   K8  k_dist_*               o2v_hip_distance_dense: exact squared distance / SDF of a label grid; outside the pipeline
 //   plan k_zhist               o2v_hip_plan_slabs: predicted hits per z layer -> work-balanced slabs for N GPUs
 // With the direct MAX path K1's counters reach the host while K2 runs, and only the stages that have work are enqueued
 // behind it.  N > 1 GPUs: o2v_hip_voxelize_sharded (bounds / work-histogram passes sharded over the ranks, RCCL).
@@ -67,6 +68,7 @@ namespace {
 #include "o2v_dev_k3_resolve.hpp"
 #include "o2v_dev_k6_fill.hpp"
 #include "o2v_dev_k7_dense.hpp"
+#include "o2v_dev_k8_distance.hpp"
 
 }  // namespace
 
@@ -241,6 +243,10 @@ struct o2v_hip_ctx {
     // K7 (o2v_hip_set_triangles_device, o2v_hip_write_dense, o2v_hip_voxels_box): flags and sums, allocated on first use
     DevArray<DenseCtr> d_dense;
     PinnedArray<DenseCtr> h_dense;
+    // K8 (o2v_hip_distance_dense): the envelope stacks, grown on demand; events around the three passes and their times
+    DevArray<uint2> d_dist_stack;
+    hipEvent_t ev_dist[4] = {nullptr, nullptr, nullptr, nullptr};
+    float dist_ms[3] = {0.f, 0.f, 0.f};
 
     // results of the last run
     uint64_t n_vox = 0;
@@ -1596,6 +1602,7 @@ void o2v_hip_destroy(o2v_hip_ctx *ctx)
     std::vector<hipEvent_t> events{std::begin(ctx->ev), std::end(ctx->ev)};
     events.insert(events.end(), {ctx->ev_coll[0], ctx->ev_coll[1], ctx->ev_stage[0], ctx->ev_stage[1], ctx->ev_fork, ctx->ev_sorted,
                                  ctx->ev_k1, ctx->ev_join[0], ctx->ev_join[1], ctx->ev_join[2], ctx->ev_fill[0], ctx->ev_fill[1]});
+    events.insert(events.end(), std::begin(ctx->ev_dist), std::end(ctx->ev_dist));
     for (const auto &b : ctx->ktimes) events.insert(events.end(), {b.e0, b.e1});
     for (hipEvent_t e : events)
         if (e) (void) hipEventDestroy(e);
@@ -2406,6 +2413,132 @@ int o2v_hip_voxels_box(o2v_hip_ctx *ctx, uint32_t lo[3], uint32_t hi[3])
     O2V_CHECK(hipMemcpyAsync(ctx->h_dense.ptr->lo, ctr->lo, sizeof(ctr->lo) + sizeof(ctr->hi), hipMemcpyDeviceToHost, s));
     O2V_CHECK(hipStreamSynchronize(s));
     for (int a = 0; a < 3; ++a) lo[a] = ctx->h_dense.ptr->lo[a], hi[a] = ctx->h_dense.ptr->hi[a] + 1u;
+    return O2V_HIP_OK;
+}
+
+}  // extern "C"
+
+// ---- K8: the distance transform of a label grid ------------------------------------------------------------------------
+
+namespace {
+
+// Lanes of an envelope pass, one line each at a time: as many as the pass has lines, at most 2^17 (8 waves per CU of the
+// MI355X).  The pass's stacks take slots x (its line length) entries of the scratch.
+constexpr uint64_t kDistMaxSlots = 1u << 17;
+
+uint64_t dist_slots(uint64_t lines) { return std::min<uint64_t>(lines, kDistMaxSlots); }
+
+// dst must not alias: along the axes of more than one voxel, taken by rising stride, each stride must step past everything
+// the axes before it reach (a stride of 0, as of an expanded tensor, fails this).
+bool dist_dst_is_distinct(const uint32_t dims[3], const uint64_t strides[3])
+{
+    int ax[3] = {0, 1, 2};
+    std::sort(ax, ax + 3, [&](int a, int b) { return strides[a] < strides[b]; });
+    unsigned __int128 reach = 0;   // the highest element offset the axes so far reach
+    for (int a : ax) {
+        if (dims[a] == 1) continue;
+        if ((unsigned __int128) strides[a] <= reach) return false;
+        reach += (unsigned __int128) (dims[a] - 1u) * strides[a];
+    }
+    return true;
+}
+
+// The bytes past p that a box of dims with these element strides reaches (128-bit: the strides are the caller's).
+unsigned __int128 box_bytes(const uint32_t dims[3], const uint64_t strides[3], uint32_t elem)
+{
+    unsigned __int128 last = 0;
+    for (int a = 0; a < 3; ++a) last += (unsigned __int128) (dims[a] - 1u) * strides[a];
+    return (last + 1u) * elem;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t o2v_hip_distance_scratch_bytes(const uint32_t dims[3], uint32_t format)
+{
+    (void) format;   // (both formats use the same stacks)
+    if (!dims || !dims[0] || !dims[1] || !dims[2]) return 0;
+    const uint64_t y = dist_slots((uint64_t) dims[0] * dims[2]) * dims[1], z = dist_slots((uint64_t) dims[0] * dims[1]) * dims[2];
+    return std::max(y, z) * sizeof(uint2);
+}
+
+int o2v_hip_distance_dense(o2v_hip_ctx *ctx, const void *labels, const uint64_t label_strides[3], void *dst, uint32_t format,
+                           const uint64_t dst_strides[3], const uint32_t dims[3])
+{
+    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
+    if (!labels || !label_strides || !dst || !dst_strides || !dims || format > O2V_HIP_DIST_SDF_F32) {
+        ctx->err = "o2v_hip_distance_dense: null argument or unknown format";
+        return O2V_HIP_ERR_BAD_ARGUMENT;
+    }
+    if (!dims[0] || !dims[1] || !dims[2]) {
+        ctx->err = "o2v_hip_distance_dense: zero dims";
+        return O2V_HIP_ERR_BAD_ARGUMENT;
+    }
+    uint64_t d2max = 0;
+    for (int a = 0; a < 3; ++a) d2max += (uint64_t) (dims[a] - 1u) * (dims[a] - 1u);
+    if (d2max > 0x7ffffffeull) {
+        ctx->err = "o2v_hip_distance_dense: (nx-1)^2 + (ny-1)^2 + (nz-1)^2 = " + std::to_string(d2max) + " does not fit below 2^31 - 1";
+        return O2V_HIP_ERR_LIMIT;
+    }
+    const unsigned __int128 lbytes = box_bytes(dims, label_strides, 1u), dbytes = box_bytes(dims, dst_strides, 4u);
+    if (lbytes > (unsigned __int128) (~0ull >> 1) || dbytes > (unsigned __int128) (~0ull >> 1)) {
+        ctx->err = "o2v_hip_distance_dense: the box and strides reach past any allocation";
+        return O2V_HIP_ERR_BAD_ARGUMENT;
+    }
+    if (!dist_dst_is_distinct(dims, dst_strides)) {
+        ctx->err = "o2v_hip_distance_dense: dst_strides map two voxels of the box to one element";
+        return O2V_HIP_ERR_BAD_ARGUMENT;
+    }
+    const uintptr_t lp = (uintptr_t) labels, dp = (uintptr_t) dst;
+    if (lp < dp + (uint64_t) dbytes && dp < lp + (uint64_t) lbytes) {
+        ctx->err = "o2v_hip_distance_dense: labels and dst overlap";
+        return O2V_HIP_ERR_BAD_ARGUMENT;
+    }
+    O2V_CHECK(hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = check_device_range(ctx, labels, (uint64_t) lbytes, "labels")) || (rc = check_device_range(ctx, dst, (uint64_t) dbytes, "dst")))
+        return rc;
+    if (const uint64_t want = o2v_hip_distance_scratch_bytes(dims, format) / sizeof(uint2); want > ctx->d_dist_stack.cap) {
+        if (const hipError_t e = ctx->d_dist_stack.alloc(want); e != hipSuccess) {
+            (void) hipGetLastError();
+            ctx->err = std::string("o2v_hip_distance_dense: scratch of ") + std::to_string(want * sizeof(uint2)) + " bytes: " + hipGetErrorString(e);
+            return e == hipErrorOutOfMemory ? O2V_HIP_ERR_OUT_OF_MEMORY : O2V_HIP_ERR_HIP;
+        }
+    }
+    for (hipEvent_t &e : ctx->ev_dist)
+        if (!e) O2V_CHECK(create_timing_event(&e));
+    hipStream_t s = ctx->stream;
+    const DistGrid g{label_strides[0], label_strides[1], label_strides[2], dst_strides[0], dst_strides[1], dst_strides[2],
+                     dims[0], dims[1], dims[2]};
+    const uint8_t *const lab = static_cast<const uint8_t *>(labels);
+    int32_t *const out = static_cast<int32_t *>(dst);
+    uint2 *const stack = ctx->d_dist_stack.ptr;
+    // passes y and z: each with its own slots (the stride of its stacks); the lanes of the last block past them have no line
+    const uint64_t sy = dist_slots((uint64_t) dims[0] * dims[2]), sz = dist_slots((uint64_t) dims[0] * dims[1]);
+    const uint32_t gy = (uint32_t) ((sy + kBlock - 1) / kBlock), gz = (uint32_t) ((sz + kBlock - 1) / kBlock);
+    const uint64_t rows = (uint64_t) dims[1] * dims[2];
+    O2V_CHECK(hipEventRecord(ctx->ev_dist[0], s));
+    hipLaunchKernelGGL(k_dist_x, dim3((uint32_t) std::min<uint64_t>((uint64_t) ctx->num_cus * 8u, (rows + 3u) / 4u)), dim3(kBlock), 0, s,
+                       lab, out, g);
+    O2V_CHECK(hipEventRecord(ctx->ev_dist[1], s));
+    hipLaunchKernelGGL(k_dist_envelope<kDistY>, dim3(gy), dim3(kBlock), 0, s, out, lab, g, stack, sy);
+    O2V_CHECK(hipEventRecord(ctx->ev_dist[2], s));
+    if (format == O2V_HIP_DIST_SQ_I32)
+        hipLaunchKernelGGL(k_dist_envelope<kDistZ>, dim3(gz), dim3(kBlock), 0, s, out, lab, g, stack, sz);
+    else
+        hipLaunchKernelGGL(k_dist_envelope<kDistZSdf>, dim3(gz), dim3(kBlock), 0, s, out, lab, g, stack, sz);
+    O2V_CHECK(hipGetLastError());
+    O2V_CHECK(hipEventRecord(ctx->ev_dist[3], s));
+    O2V_CHECK(hipStreamSynchronize(s));
+    for (int i = 0; i < 3; ++i) O2V_CHECK(hipEventElapsedTime(&ctx->dist_ms[i], ctx->ev_dist[i], ctx->ev_dist[i + 1]));
+    return O2V_HIP_OK;
+}
+
+int o2v_hip_distance_times(const o2v_hip_ctx *ctx, float out_ms[3])
+{
+    if (!ctx || !out_ms) return O2V_HIP_ERR_BAD_ARGUMENT;
+    for (int i = 0; i < 3; ++i) out_ms[i] = ctx->dist_ms[i];
     return O2V_HIP_OK;
 }
 

@@ -7,7 +7,8 @@
     grid, origin = dense.voxelize_dense(dv, 256, fill=True)   # bool (256, 256, 256), indexed [z, y, x]
 
 The mesh goes to the device context without a host copy (o2v_hip_set_triangles_device) and the voxels come back as a dense
-tensor written on the device (o2v_hip_write_dense); nothing of either crosses to the host.
+tensor written on the device (o2v_hip_write_dense); nothing of either crosses to the host.  Distance grids (fmt "dist2" /
+"sdf", and distance_transform on any label tensor) come from o2v_hip_distance_dense.
 
 torch is imported first on purpose: the library must bind to the HIP runtime torch loaded (a process that loaded the library
 before torch holds two separate runtime copies, and this module refuses to work there).
@@ -21,6 +22,10 @@ FORMATS = {  # name: (o2v_hip_write_dense format, tensor dtype)
     "labels": (hip.DENSE_U8, torch.uint8),
     "argb": (hip.DENSE_ARGB32, torch.int32),
     "bits": (hip.DENSE_BITS, torch.int32),
+}
+DISTANCE_FORMATS = {  # name: (o2v_hip_distance_dense format, tensor dtype)
+    "dist2": (hip.DIST_SQ_I32, torch.int32),
+    "sdf": (hip.DIST_SDF_F32, torch.float32),
 }
 STRATEGIES = {"max": hip.STRATEGY_MAX, "blend": hip.STRATEGY_BLEND}
 MAX_SAMPLES = 65535  # samples per axis of one pass (x / y tiles above that are not supported here)
@@ -103,8 +108,32 @@ def voxelize_dense(dv, resolution, *, fmt="occupancy", box="grid", out=None, ori
     out:  a 3-D tensor (any strides, e.g. a slice of a batch) of the format's dtype on the voxelizer's device, written as it
           is and not cleared; its shape is the box's extent.  Otherwise a new zeroed contiguous tensor.
     A grid whose dense stage does not fit the device runs as consecutive z-slabs (o2v_hip_max_slab_layers; max_layers caps
-    their height), all written into the one tensor.  A voxel outside the tensor's box raises."""
+    their height), all written into the one tensor.  A voxel outside the tensor's box raises.
+
+    fmt "dist2" int32 / "sdf" float32: the labels of the box (as fmt="labels", z-slabs included) go to a temporary uint8 tensor,
+    then one distance_transform of the whole box goes to the tensor.  "sdf" needs fill=True (its sign is the interior)."""
     _require_shared_runtime()
+    if fmt in DISTANCE_FORMATS:
+        if fmt == "sdf" and not fill:
+            raise ValueError("fmt='sdf' needs fill=True: without the interior every distance would be positive")
+        dtype = DISTANCE_FORMATS[fmt][1]
+        device = _device(dv)
+        if out is not None:
+            if not isinstance(out, torch.Tensor) or out.dim() != 3:
+                raise ValueError("out must be a 3-D tensor [z, y, x]")
+            if out.dtype != dtype:
+                raise TypeError(f"out must be {dtype} for fmt={fmt!r}, not {out.dtype}")
+            if out.device != device:
+                raise ValueError(f"out is on {out.device}, the voxelizer on {device}")
+        labels, origin = voxelize_dense(
+            dv, resolution, fmt="labels", box=box, origin=origin, supersampling=supersampling, strategy=strategy, fill=fill,
+            fill_argb=fill_argb, unit_transform=unit_transform, bounds=bounds, max_layers=max_layers,
+            out=None if out is None else torch.zeros(tuple(out.shape), dtype=torch.uint8, device=device))
+        if out is None:
+            out = torch.empty(tuple(labels.shape), dtype=dtype, device=device)
+        if 0 in labels.shape:
+            return out, origin
+        return distance_transform(dv, labels, fmt=fmt, out=out), origin
     if fmt not in FORMATS:
         raise ValueError(f"fmt must be one of {sorted(FORMATS)}, not {fmt!r}")
     if box not in ("grid", "tight"):
@@ -191,3 +220,38 @@ def voxelize_dense(dv, resolution, *, fmt="occupancy", box="grid", out=None, ori
     if fmt == "occupancy" and interior:
         target.clamp_(max=1)
     return out, origin
+
+
+def distance_transform(dv, labels, fmt="sdf", *, out=None):
+    """The exact Euclidean distance transform of `labels`, a uint8 tensor [z, y, x] of any strides on
+    the voxelizer's device (0 empty, 1 surface, 2 interior, as fmt="labels" writes), into `out` (any strides, the same shape;
+    a new contiguous tensor if None), which is returned.  Seeds are the surface voxels; distances are in voxels, over the box.
+    fmt "dist2": int32 squared distances (0x7FFFFFFF everywhere when there is no surface voxel); "sdf": float32
+    -sqrt(d2) where labels == 2, +sqrt(d2) elsewhere (+-inf without a surface voxel)."""
+    _require_shared_runtime()
+    if fmt not in DISTANCE_FORMATS:
+        raise ValueError(f"fmt must be one of {sorted(DISTANCE_FORMATS)}, not {fmt!r}")
+    code, dtype = DISTANCE_FORMATS[fmt]
+    device = _device(dv)
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 3:
+        raise ValueError("labels must be a 3-D tensor [z, y, x]")
+    if labels.dtype != torch.uint8:
+        raise TypeError(f"labels must be torch.uint8, not {labels.dtype}")
+    if labels.device != device:
+        raise ValueError(f"labels is on {labels.device}, the voxelizer on {device}")
+    if 0 in labels.shape:
+        raise ValueError("labels has an empty dimension")
+    if out is None:
+        out = torch.empty(tuple(labels.shape), dtype=dtype, device=device)
+    else:
+        if not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(labels.shape):
+            raise ValueError(f"out must be a tensor of the labels' shape {tuple(labels.shape)}")
+        if out.dtype != dtype:
+            raise TypeError(f"out must be {dtype} for fmt={fmt!r}, not {out.dtype}")
+        if out.device != device:
+            raise ValueError(f"out is on {out.device}, the voxelizer on {device}")
+    nz, ny, nx = labels.shape
+    _sync(device)   # (the caller's writes to labels and out have landed)
+    dv.distance_dense(labels.data_ptr(), (labels.stride(2), labels.stride(1), labels.stride(0)), out.data_ptr(), code,
+                      (out.stride(2), out.stride(1), out.stride(0)), (nx, ny, nz))
+    return out

@@ -23,6 +23,7 @@ FLAG_STAGE_TIMES = 4   # ... an event between the stages of a pass: the stage ti
 FLAG_EXACT_CLIP = 1  # o2v_hip_params::flags: the clip kernel without its work-removal shortcuts (include/o2v_hip.h)
 FLAG_FILL_INTERIOR = 8  # ... solid voxelization: the interior voxels (colour fill_argb) behind the surface records
 DENSE_U8, DENSE_ARGB32, DENSE_BITS = 0, 1, 2  # o2v_hip_write_dense formats
+DIST_SQ_I32, DIST_SDF_F32 = 0, 1  # o2v_hip_distance_dense formats
 ERR_BAD_ARGUMENT = 3
 
 
@@ -110,6 +111,10 @@ def _bind():
     L.o2v_hip_set_triangles_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32] + [C.c_void_p] * 4 + [C.c_uint64]
     L.o2v_hip_write_dense.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
     L.o2v_hip_voxels_box.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.o2v_hip_distance_dense.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.o2v_hip_distance_scratch_bytes.argtypes = [C.c_void_p, C.c_uint32]
+    L.o2v_hip_distance_scratch_bytes.restype = C.c_uint64
+    L.o2v_hip_distance_times.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_max_slab_layers.argtypes = [C.c_void_p, C.POINTER(_Params), C.POINTER(C.c_uint32)]
     return L
 
@@ -238,6 +243,24 @@ class DeviceVoxelizer:
         lo, hi = (C.c_uint32 * 3)(), (C.c_uint32 * 3)()
         self._check(self._L.o2v_hip_voxels_box(self._ctx, lo, hi), "o2v_hip_voxels_box")
         return tuple(lo), tuple(hi)
+
+    def distance_dense(self, labels_ptr, label_strides, dst_ptr, fmt, dst_strides, dims):
+        """o2v_hip_distance_dense: the squared distance (DIST_SQ_I32) or SDF (DIST_SDF_F32) of the uint8 label grid at device
+        address labels_ptr into dst_ptr; strides in elements and dims per axis x, y, z."""
+        ls = (C.c_uint64 * 3)(*[int(v) for v in label_strides])
+        ds = (C.c_uint64 * 3)(*[int(v) for v in dst_strides])
+        d = (C.c_uint32 * 3)(*[int(v) for v in dims])
+        self._check(self._L.o2v_hip_distance_dense(self._ctx, labels_ptr, ls, dst_ptr, fmt, ds, d), "o2v_hip_distance_dense")
+
+    def distance_scratch_bytes(self, dims, fmt):
+        """o2v_hip_distance_scratch_bytes: the context scratch a distance_dense call over dims (x, y, z) needs."""
+        return int(self._L.o2v_hip_distance_scratch_bytes((C.c_uint32 * 3)(*[int(v) for v in dims]), fmt))
+
+    def distance_times(self):
+        """o2v_hip_distance_times: the device times (ms) of the last distance_dense call's x, y and z passes."""
+        ms = (C.c_float * 3)()
+        self._check(self._L.o2v_hip_distance_times(self._ctx, ms), "o2v_hip_distance_times")
+        return tuple(float(v) for v in ms)
 
     def set_textures(self, textures):
         """textures: sequence of (uint8 [h, w, c] pixels, wrap) with c in (3, 4)."""

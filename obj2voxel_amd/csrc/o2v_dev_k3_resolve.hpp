@@ -1071,97 +1071,90 @@ __global__ __launch_bounds__(kBlock) void k_emit_max(const uint32_t *__restrict_
     if (n) flush(n);
 }
 
-// Occupancy-only mode (Params::occupancy_only): the dirty bricks of the one-byte-per-cell grid (64 bytes each: one 4-byte load
-// per lane, four bricks per wavefront load) become white (x, y, z, argb) records and are zeroed again.
-constexpr uint32_t kOccBricksPerWave = 2;  // (the staging buffer then takes 48 KiB: three workgroups per CU)
-constexpr uint32_t kOccBricksPerRound = (kBlock / 64) * kOccBricksPerWave * kBricksPerLoad;
-// A flush reserves its records with one atomic on Counters::n_out, and those serialise (~5 ns each: with 1 024 records per
-// flush they were a third of this kernel - 512: 0.088 ms, 1 024: 0.062).  The staged record is therefore 8 bytes (x | y << 16,
-// z; the colour is white) and becomes the 16-byte (x, y, z, argb) when it is written out: the same 48 KiB hold 6 144 of them, a
-// flush takes 4 096 or more.
-#ifndef O2V_OCC_FLUSH
-#define O2V_OCC_FLUSH 4096
+// Occupancy-only mode (Params::occupancy_only): the dirty bricks of the one-byte-per-cell grid become white (x, y, z, argb) records
+// and are zeroed again.  A workgroup takes a chunk of kOccChunk consecutive list entries and reads all its bricks at once (a
+// 16-byte load per lane and kOccLoads loads in flight per lane: 16 bricks per wavefront load at 4 x 4 x 4), counts their cells,
+// reserves the chunk's records with ONE atomic on Counters::n_out and writes them straight from registers - per cell position a
+// ballot, so the set lanes' 16-byte records are contiguous - with no LDS staging and no barrier between the loads and the
+// stores.  (The staged version - rounds of 32 bricks behind two workgroup barriers each, a flush of 4 096 records per atomic,
+// 48 KiB of LDS - kept ~6 KiB of loads in flight per CU: 42 us for 123 MB on the bench mesh; this: 28.6.)  Same-address atomics
+// serialise (~5 ns each), so a chunk is large: 512 bricks, ~7 000 records on the bench mesh.  Measured on the bench mesh: 4 loads
+// per lane 33 us, 16 (two workgroups per CU) 32; non-temporal record and zero stores 37 (partial lines leave L2 unmerged).
+#ifndef O2V_OCC_LOADS
+#define O2V_OCC_LOADS 8
 #endif
-constexpr uint32_t kOccFlushAt = O2V_OCC_FLUSH;
-constexpr uint32_t kOccCap = kOccFlushAt + kOccBricksPerRound * kBrickCells;
+constexpr uint32_t kOccLoads = O2V_OCC_LOADS;
+constexpr uint32_t kOccLanesPerBrick = kBrickCells / 16u, kOccBricksPerLoad = 64u / kOccLanesPerBrick;
+constexpr uint32_t kOccChunk = (kBlock / 64) * kOccLoads * kOccBricksPerLoad;
+#ifndef O2V_OCC_WGS
+#define O2V_OCC_WGS 4
+#endif
+constexpr uint32_t kOccWgsPerCu = O2V_OCC_WGS;
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(kBlock) void k_emit_occ(const uint32_t *__restrict__ dirty_list, Counters *c, uint4 *out, Params p)
 {
-    static_assert(kLanesPerBrick * 4u == kBrickCells, "one 4-byte load per lane covers four cells");
-    __shared__ uint2 s_rec[kOccCap];
-    __shared__ uint32_t s_n, s_base;
-    if (threadIdx.x == 0) s_n = 0;
-    __syncthreads();
+    static_assert(kBrickCells % 16u == 0u, "a lane reads 16 cells of one brick");
+    __shared__ uint32_t s_wave[kBlock / 64], s_base;
     const uint32_t white = pack_argb(1.f, 1.f, 1.f);  // colorAt_f of a material-less triangle, triangle.hpp:181-194
     const uint32_t n_dirty = c->n_dirty_max < p.cap_dirty ? c->n_dirty_max : p.cap_dirty;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t n_rounds = (n_dirty + kOccBricksPerRound - 1) / kOccBricksPerRound;
-    auto flush = [&](uint32_t n) {
-        if (threadIdx.x == 0) s_base = atomicAdd(&c->n_out, n);
-        __syncthreads();
-        const uint32_t base = s_base;
-        for (uint32_t i = threadIdx.x; i < n; i += kBlock)
-            if (base + i < p.cap_vox) out[base + i] = make_uint4((s_rec[i].x & 0xffffu) + p.xo0, (s_rec[i].x >> 16) + p.yo0, s_rec[i].y + p.zo0, white);
-        __syncthreads();
-        if (threadIdx.x == 0) s_n = 0;
-        __syncthreads();
-    };
-    uint32_t *grid4 = reinterpret_cast<uint32_t *>(p.occgrid);
-    // the list entries of a round are requested one round ahead (the brick loads depend on them: two round trips per round
-    // otherwise)
-    auto list_entry = [&](uint32_t r, uint32_t k) -> uint32_t {
-        const uint32_t item = r * kOccBricksPerRound + (wave * kOccBricksPerWave + k) * kBricksPerLoad + lane / kLanesPerBrick;
-        return (r < n_rounds && item < n_dirty) ? dirty_list[item] : 0xffffffffu;
-    };
-    // (... and the bricks' cells one round ahead: a round then waits for neither)
-    auto cells_of = [&](uint32_t b) -> uint32_t { return b != 0xffffffffu ? grid4[(uint64_t) b * kLanesPerBrick + lane % kLanesPerBrick] : 0u; };
-    uint32_t next_brick[kOccBricksPerWave], next_cells[kOccBricksPerWave], after_brick[kOccBricksPerWave];
+    const uint32_t part = lane % kOccLanesPerBrick;  // the lane's 16 cells: [16 part, 16 part + 16) of its brick
+    u32x4_t *grid16 = reinterpret_cast<u32x4_t *>(p.occgrid);
+    u32x4_t *out16 = reinterpret_cast<u32x4_t *>(out);
+    for (uint32_t chunk = blockIdx.x; chunk < (n_dirty + kOccChunk - 1u) / kOccChunk; chunk += gridDim.x) {
+        const uint32_t first = chunk * kOccChunk + wave * (kOccLoads * kOccBricksPerLoad) + lane / kOccLanesPerBrick;
+        uint32_t brick[kOccLoads];
 #pragma unroll
-    for (uint32_t k = 0; k < kOccBricksPerWave; ++k) {
-        next_brick[k] = list_entry(blockIdx.x, k);
-        after_brick[k] = list_entry(blockIdx.x + gridDim.x, k);
-    }
-#pragma unroll
-    for (uint32_t k = 0; k < kOccBricksPerWave; ++k) next_cells[k] = cells_of(next_brick[k]);
-    for (uint32_t r = blockIdx.x; r < n_rounds; r += gridDim.x) {
-        uint32_t brick[kOccBricksPerWave], cells4[kOccBricksPerWave];
-#pragma unroll
-        for (uint32_t k = 0; k < kOccBricksPerWave; ++k) {
-            brick[k] = next_brick[k];
-            cells4[k] = next_cells[k];
-            next_brick[k] = after_brick[k];
-            next_cells[k] = cells_of(after_brick[k]);
-            after_brick[k] = list_entry(r + 2u * gridDim.x, k);
+        for (uint32_t u = 0; u < kOccLoads; ++u) {
+            const uint32_t item = first + u * kOccBricksPerLoad;
+            brick[u] = item < n_dirty ? dirty_list[item] : 0xffffffffu;
         }
+        u32x4_t cells[kOccLoads];
 #pragma unroll
-        for (uint32_t k = 0; k < kOccBricksPerWave; ++k) {
-            // (wavefront-uniform loop over the four cells of a lane: the staging slots are reserved with one LDS atomic per
-            // wavefront and cell position, not one per voxel)
+        for (uint32_t u = 0; u < kOccLoads; ++u)
+            cells[u] = brick[u] != 0xffffffffu ? grid16[(uint64_t) brick[u] * kOccLanesPerBrick + part] : u32x4_t{0, 0, 0, 0};
+        uint32_t mine = 0;
+#pragma unroll
+        for (uint32_t u = 0; u < kOccLoads; ++u)
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k)
+                mine += (uint32_t) __popc((((cells[u][k] & 0x7f7f7f7fu) + 0x7f7f7f7fu) | cells[u][k]) & 0x80808080u);  // non-zero bytes
+        const uint32_t wave_total = __shfl(wave_inclusive_scan(mine), 63, 64);
+        if (lane == 0) s_wave[wave] = wave_total;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t total = 0;
+            for (uint32_t w = 0; w < kBlock / 64u; ++w) total += s_wave[w];
+            s_base = total ? atomicAdd(&c->n_out, total) : 0u;  // (n_out counts past cap_vox: the host grows the buffer and re-runs)
+        }
+        __syncthreads();
+        uint32_t base = s_base;
+        for (uint32_t w = 0; w < wave; ++w) base += s_wave[w];
+#pragma unroll
+        for (uint32_t u = 0; u < kOccLoads; ++u) {
             uint32_t x0, y0, z0;
-            brick_origin_rel(brick[k] == 0xffffffffu ? 0u : brick[k], p, x0, y0, z0);   // (relative to the grid's origin, which the flush adds)
+            brick_origin_rel(brick[u] == 0xffffffffu ? 0u : brick[u], p, x0, y0, z0);
+            x0 += p.xo0;
+            y0 += p.yo0;
+            z0 += p.zo0;
 #pragma unroll
-            for (uint32_t e = 0; e < 4; ++e) {
-                const bool set = ((cells4[k] >> (8u * e)) & 0xffu) != 0u;
+            for (uint32_t e = 0; e < 16; ++e) {
+                const bool set = ((cells[u][e >> 2] >> (8u * (e & 3u))) & 0xffu) != 0u;
                 const unsigned long long m = __ballot(set);
-                if (m) {
-                    uint32_t base = 0;
-                    if (lane == 0) base = atomicAdd(&s_n, (uint32_t) __popcll(m));
-                    base = __shfl(base, 0, 64);
-                    if (set) {
-                        const uint32_t local = (lane % kLanesPerBrick) * 4u + e;
-                        const uint32_t slot = base + __builtin_amdgcn_mbcnt_hi((uint32_t) (m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m, 0u));
-                        s_rec[slot] = make_uint2((x0 + (local & (kBrickX - 1u))) | ((y0 + ((local >> kBrickXs) & (kBrickY - 1u))) << 16),
-                                                 z0 + (local >> (kBrickXs + kBrickYs)));  // (a pass' box is at most 65 535 cells wide)
-                    }
+                if (m == 0ull) continue;  // (wavefront-uniform)
+                const uint32_t slot = base + __builtin_amdgcn_mbcnt_hi((uint32_t) (m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m, 0u));
+                if (set && slot < p.cap_vox) {
+                    const uint32_t local = part * 16u + e;
+                    out16[slot] = u32x4_t{x0 + (local & (kBrickX - 1u)), y0 + ((local >> kBrickXs) & (kBrickY - 1u)), z0 + (local >> (kBrickXs + kBrickYs)), white};
                 }
+                base += (uint32_t) __popcll(m);
             }
-            if (cells4[k]) grid4[(uint64_t) brick[k] * kLanesPerBrick + lane % kLanesPerBrick] = 0u;  // clean for the next run
         }
-        __syncthreads();
-        const uint32_t n = s_n;
-        __syncthreads();  // (every thread has read n before anyone adds to s_n again: the decision below must be uniform)
-        if (n >= kOccFlushAt) flush(n);
+        // leave the cells clean for the next run
+#pragma unroll
+        for (uint32_t u = 0; u < kOccLoads; ++u)
+            if ((cells[u][0] | cells[u][1] | cells[u][2] | cells[u][3]) != 0u)
+                grid16[(uint64_t) brick[u] * kOccLanesPerBrick + part] = u32x4_t{0, 0, 0, 0};
+        __syncthreads();  // (s_wave and s_base are the next chunk's)
     }
-    __syncthreads();
-    const uint32_t n = s_n;
-    if (n) flush(n);
 }

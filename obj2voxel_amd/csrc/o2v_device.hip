@@ -817,7 +817,8 @@ int run_pass(o2v_hip_ctx *ctx, const Params &p, const Switches &sw, bool use_uv,
     if (run_emit && p.pick_max)
         O2V_LAUNCH("k_pick", s, k_pick, dim3((uint32_t) ctx->num_cus * 8u), dim3(kBlock), 0, s, ctx->d_pool.ptr, ctr, p);
     if (run_emit && p.occupancy_only) {
-        O2V_LAUNCH("k_emit_occ", s, k_emit_occ, dim3((uint32_t) ctx->num_cus * 3u), dim3(kBlock), 0, s, ctx->d_dirty_list_max.ptr, ctr, ctx->d_out.ptr, p);
+        O2V_LAUNCH("k_emit_occ", s, k_emit_occ, dim3((uint32_t) ctx->num_cus * kOccWgsPerCu), dim3(kBlock), 0, s, ctx->d_dirty_list_max.ptr, ctr,
+                   ctx->d_out.ptr, p);
     }
     else if (run_emit) {
         // every voxel's winner is in the 64-bit grid now (k_voxelize: unsplit triangles, resolve: the rest)

@@ -297,6 +297,48 @@ uint64_t o2v_hip_distance_scratch_bytes(const uint32_t dims[3], uint32_t format)
 /* The device times of the last o2v_hip_distance_dense call's three passes (x, y, z), from events around each, in ms. */
 int o2v_hip_distance_times(const o2v_hip_ctx *ctx, float out_ms[3]);
 
+/* ---- narrow-band distance to the triangles ----------------------------------------------------
+ *
+ * The distance from each voxel centre of a box to the context's triangles themselves (not to surface voxels), exact in a band
+ * and truncated at it.  The mesh is the context's triangles in their order (o2v_hip_set_triangles, _device or the streamed
+ * upload).  Of params, resolution, supersampling (1 or 2), unit_transform, bounds_known and bounds are read; strategy, flags and
+ * fill_argb are ignored; z_begin .. y_end must be 0 (else O2V_HIP_ERR_BAD_ARGUMENT).  The mesh transform A is the one
+ * o2v_hip_voxelize computes for the same params and reports through o2v_hip_get_transform, bit for bit.
+ *   Vertices: sample space as K1 / K6 take them (affine_apply of A, float32); a triangle with a non-finite coordinate is ignored.
+ *   Centres: with ss = supersampling, voxel (x, y, z) has P = (x ss + ss/2, y ss + ss/2, z ss + ss/2), in double.
+ *   d2_t(P), in double, op by op, left to right, no FMA; A, B, C converted from float32; dot, cross and squared norms written
+ *   out component by component, left to right:
+ *     ab = B - A, ac = C - A, ap = P - A, n = cross(ab, ac), nn = n.n;
+ *     if nn > 0: s0 = n.cross(B - A, P - A), s1 = n.cross(C - B, P - B), s2 = n.cross(A - C, P - C); if all three are >= 0,
+ *       d2 = (h * h) / nn with h = n.ap;
+ *     otherwise (always when nn == 0): d2 = min(seg(P, A, B), seg(P, B, C), seg(P, C, A)), where seg(P, U, V): e = V - U,
+ *       w = P - U, ee = e.e, t = 0 if ee == 0 else (w.e) / ee clamped by t < 0 ? 0 : (t > 1 ? 1 : t), q = w - t * e per
+ *       component, result q.q.
+ *   D(P) = min over the triangles of d2_t(P).  A triangle takes part for P only if P lies in its sample-space AABB dilated by
+ *   band ss + ss on every side (compared in double: (double) min - m <= P <= (double) max + m, m = (double) band * ss + ss);
+ *   the extra sample is a margin above every rounding of d2, so this cut leaves D unchanged wherever D < Bs2 (below).
+ *   band (voxels) must be finite with 0 < band <= 32 (else O2V_HIP_ERR_BAD_ARGUMENT); Bs2 = (double) band * band * ss * ss.
+ *   UNSIGNED_F32: u = D < Bs2 ? (float) (sqrt(D) / ss) : band.
+ *   SIGNED_F32:   -u (float negation: a centre exactly on a triangle inside gives -0.0) where the voxel is in the parity set
+ *                 of O2V_HIP_FLAG_FILL_INTERIOR (the definition above, with the mesh's top-layer cut) - for every voxel,
+ *                 surface voxels included - else u.  An empty mesh gives +band everywhere.
+ *   closest (optional, int32): the smallest t with d2_t = D where D < Bs2, else -1.
+ * The value of a voxel depends only on its centre and the whole mesh: a box cut into z ranges gives the bits of one call.
+ * Box: origin and dims are output voxels, dims >= 1 and origin + dims <= resolution per axis (else BAD_ARGUMENT); a dim above
+ * 65 535 is refused with O2V_HIP_ERR_LIMIT.  Voxel (x, y, z) of the box is dst[(x - ox) * dst_strides[0] + (y - oy) *
+ * dst_strides[1] + (z - oz) * dst_strides[2]] (elements, any order), likewise closest with closest_strides; every voxel of the
+ * box is written to both.  Refused with O2V_HIP_ERR_BAD_ARGUMENT before any launch: an unknown format, strides that map two
+ * voxels to one element, dst and closest overlapping, a pointer that is not device memory of the context's device with the
+ * box's highest address inside its allocation.  Scratch (binned triangle lists, the parity bitmap) belongs to the context and
+ * grows on demand; a failed allocation returns O2V_HIP_ERR_OUT_OF_MEMORY and the context stays usable.  The call runs on the
+ * context's stream and returns when the writes have landed. */
+enum { O2V_HIP_MESH_DIST_UNSIGNED_F32 = 0, O2V_HIP_MESH_DIST_SIGNED_F32 = 1 };
+int o2v_hip_mesh_distance_dense(o2v_hip_ctx *ctx, const o2v_hip_params *params, float band, uint32_t format,
+                                const uint32_t origin[3], const uint32_t dims[3], float *dst, const uint64_t dst_strides[3],
+                                int32_t *closest /* may be NULL */, const uint64_t closest_strides[3]);
+/* The device times (ms) of the last o2v_hip_mesh_distance_dense call's stages: binning, parity (0 unsigned), distance. */
+int o2v_hip_mesh_distance_times(const o2v_hip_ctx *ctx, float out_ms[3]);
+
 int o2v_hip_get_timings(const o2v_hip_ctx *ctx, o2v_hip_timings *out);
 /* Per-kernel device times of the last o2v_hip_voxelize call made with O2V_HIP_FLAG_KERNEL_TIMES (else none): up to
  * max_entries entries are written, *out_count receives how many there are. */

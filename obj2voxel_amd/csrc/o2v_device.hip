@@ -26,6 +26,8 @@
 //                              the surface cells removed, interior records appended behind the surface records
 //   K7  k_gather_tris, k_dense_* device-resident input (positions + faces) and dense output grids; outside the pipeline
 //   K8  k_dist_*               o2v_hip_distance_dense: exact squared distance / SDF of a label grid; outside the pipeline
+//   K9  k_meshdist_*           o2v_hip_mesh_distance_dense: narrow-band distance to the triangles, signed by K6's parity set;
+//                              outside the pipeline
 //   plan k_zhist               o2v_hip_plan_slabs: predicted hits per z layer -> work-balanced slabs for N GPUs
 // With the direct MAX path K1's counters reach the host while K2 runs, and only the stages that have work are enqueued
 // behind it.  N > 1 GPUs: o2v_hip_voxelize_sharded (bounds / work-histogram passes sharded over the ranks, RCCL).
@@ -69,6 +71,7 @@ namespace {
 #include "o2v_dev_k6_fill.hpp"
 #include "o2v_dev_k7_dense.hpp"
 #include "o2v_dev_k8_distance.hpp"
+#include "o2v_dev_k9_mesh_distance.hpp"
 
 }  // namespace
 
@@ -247,6 +250,14 @@ struct o2v_hip_ctx {
     DevArray<uint2> d_dist_stack;
     hipEvent_t ev_dist[4] = {nullptr, nullptr, nullptr, nullptr};
     float dist_ms[3] = {0.f, 0.f, 0.f};
+    // K9 (o2v_hip_mesh_distance_dense): sample-space vertices, per-tile counters, offsets and triangle lists, grown on demand;
+    // events around the three stages and their times
+    DevArray<float> d_md_sv;
+    DevArray<uint32_t> d_md_counts, d_md_lists;
+    DevArray<unsigned long long> d_md_first, d_md_blocks, d_md_ctr;
+    PinnedArray<unsigned long long> h_md_ctr;
+    hipEvent_t ev_md[4] = {nullptr, nullptr, nullptr, nullptr};
+    float md_ms[3] = {0.f, 0.f, 0.f};
 
     // results of the last run
     uint64_t n_vox = 0;
@@ -1271,6 +1282,33 @@ int check_pass(o2v_hip_ctx *ctx, Run &r, bool &again)
 // Whether the pass that stood emitted its records from the 64-bit max grid (direct_active() on the device): h.n_out records, else h.n_vox.
 bool pass_direct(const Params &p, const Counters &h) { return p.direct_max && (p.occupancy_only || h.n_nodes[0] <= h.n_root_leaves); }
 
+// K6's parity set of box b as a bitmap in ctx->d_fill_bits ([z-word][y][x]): the crossings of the context's triangles (sample
+// space by xf) toggled and prefix-XORed along z, cut at the mesh's top layer.  Enqueued on the context's stream; the fill stage
+// and o2v_hip_mesh_distance_dense (K9) share it.
+int parity_bits(o2v_hip_ctx *ctx, const Affine &xf, const FillBox &b)
+{
+    hipStream_t s = ctx->stream;
+    const uint64_t T = ctx->n_tris, n_blocks = (T + kBlock - 1) / kBlock;
+    int rc;
+    if ((rc = grow(ctx, ctx->d_fill_bits, b.n_words, kNoLimit)) || (rc = grow(ctx, ctx->d_fill_ends, T, kNoLimit)) ||
+        (rc = grow(ctx, ctx->d_fill_blocks, n_blocks, kNoLimit)) || (rc = grow(ctx, ctx->d_fill_ctr, 3)))
+        return rc;
+    O2V_CHECK(hipMemsetAsync(ctx->d_fill_bits.ptr, 0, b.n_words * sizeof(uint32_t), s));
+    O2V_CHECK(hipMemsetAsync(ctx->d_fill_ctr.ptr, 0, 3 * sizeof(unsigned long long), s));
+    const uint32_t persistent = (uint32_t) ctx->num_cus * 8u;
+    if (T) {
+        O2V_LAUNCH("k_fill_count", s, k_fill_count, dim3((uint32_t) n_blocks), dim3(kBlock), 0, s, ctx->d_verts.ptr, T, xf, b,
+                   ctx->d_fill_ends.ptr, ctx->d_fill_blocks.ptr, ctx->d_fill_ctr.ptr + 2);
+        O2V_LAUNCH("k_fill_scan_blocks", s, k_fill_scan_blocks, dim3(1), dim3(kBlock), 0, s, ctx->d_fill_blocks.ptr, n_blocks, ctx->d_fill_ctr.ptr);
+        O2V_LAUNCH("k_fill_offsets", s, k_fill_offsets, dim3((uint32_t) n_blocks), dim3(kBlock), 0, s, ctx->d_fill_ends.ptr, T, ctx->d_fill_blocks.ptr);
+        O2V_LAUNCH("k_fill_cross", s, k_fill_cross, dim3(persistent), dim3(kBlock), 0, s, ctx->d_verts.ptr, T, xf, b, ctx->d_fill_ends.ptr,
+                   ctx->d_fill_ctr.ptr, ctx->d_fill_bits.ptr);
+    }
+    O2V_LAUNCH("k_fill_prefix", s, k_fill_prefix, dim3((uint32_t) ((b.n_cols + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, ctx->d_fill_bits.ptr, b,
+               ctx->d_fill_ctr.ptr + 2);
+    return O2V_HIP_OK;
+}
+
 // K6, the solid fill (O2V_HIP_FLAG_FILL_INTERIOR), behind the n_surf surface records of the pass that stood: appends the
 // interior records of the pass box to d_out (o2v_dev_k6_fill.hpp) and returns their number in n_interior.
 int fill_stage(o2v_hip_ctx *ctx, const o2v_hip_params *params, const Run &r, uint64_t n_surf, uint64_t &n_interior)
@@ -1306,19 +1344,8 @@ int fill_stage(o2v_hip_ctx *ctx, const o2v_hip_params *params, const Run &r, uin
     const float *x = ctx->h_ctr.ptr->xform;  // (k_setup's transform of this pass)
     for (int i = 0; i < 3; ++i) xf.m[i] = {x[i * 3], x[i * 3 + 1], x[i * 3 + 2]};
     xf.t = {x[9], x[10], x[11]};
-    O2V_CHECK(hipMemsetAsync(ctx->d_fill_bits.ptr, 0, b.n_words * sizeof(uint32_t), s));
-    O2V_CHECK(hipMemsetAsync(ctx->d_fill_ctr.ptr, 0, 3 * sizeof(unsigned long long), s));
+    if ((rc = parity_bits(ctx, xf, b))) return rc;
     const uint32_t persistent = (uint32_t) ctx->num_cus * 8u;
-    if (T) {
-        O2V_LAUNCH("k_fill_count", s, k_fill_count, dim3((uint32_t) n_blocks), dim3(kBlock), 0, s, ctx->d_verts.ptr, T, xf, b,
-                   ctx->d_fill_ends.ptr, ctx->d_fill_blocks.ptr, ctx->d_fill_ctr.ptr + 2);
-        O2V_LAUNCH("k_fill_scan_blocks", s, k_fill_scan_blocks, dim3(1), dim3(kBlock), 0, s, ctx->d_fill_blocks.ptr, n_blocks, ctx->d_fill_ctr.ptr);
-        O2V_LAUNCH("k_fill_offsets", s, k_fill_offsets, dim3((uint32_t) n_blocks), dim3(kBlock), 0, s, ctx->d_fill_ends.ptr, T, ctx->d_fill_blocks.ptr);
-        O2V_LAUNCH("k_fill_cross", s, k_fill_cross, dim3(persistent), dim3(kBlock), 0, s, ctx->d_verts.ptr, T, xf, b, ctx->d_fill_ends.ptr,
-                   ctx->d_fill_ctr.ptr, ctx->d_fill_bits.ptr);
-    }
-    O2V_LAUNCH("k_fill_prefix", s, k_fill_prefix, dim3((uint32_t) ((b.n_cols + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, ctx->d_fill_bits.ptr, b,
-               ctx->d_fill_ctr.ptr + 2);
     if (n_surf)
         O2V_LAUNCH("k_fill_unmark", s, k_fill_unmark, dim3((uint32_t) std::min<uint64_t>(persistent, (n_surf + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
                    ctx->d_out.ptr, n_surf, b, ctx->d_fill_bits.ptr);
@@ -1604,6 +1631,7 @@ void o2v_hip_destroy(o2v_hip_ctx *ctx)
     events.insert(events.end(), {ctx->ev_coll[0], ctx->ev_coll[1], ctx->ev_stage[0], ctx->ev_stage[1], ctx->ev_fork, ctx->ev_sorted,
                                  ctx->ev_k1, ctx->ev_join[0], ctx->ev_join[1], ctx->ev_join[2], ctx->ev_fill[0], ctx->ev_fill[1]});
     events.insert(events.end(), std::begin(ctx->ev_dist), std::end(ctx->ev_dist));
+    events.insert(events.end(), std::begin(ctx->ev_md), std::end(ctx->ev_md));
     for (const auto &b : ctx->ktimes) events.insert(events.end(), {b.e0, b.e1});
     for (hipEvent_t e : events)
         if (e) (void) hipEventDestroy(e);
@@ -2540,6 +2568,165 @@ int o2v_hip_distance_times(const o2v_hip_ctx *ctx, float out_ms[3])
 {
     if (!ctx || !out_ms) return O2V_HIP_ERR_BAD_ARGUMENT;
     for (int i = 0; i < 3; ++i) out_ms[i] = ctx->dist_ms[i];
+    return O2V_HIP_OK;
+}
+
+}  // extern "C"
+
+// ---- K9: narrow-band distance to the triangles -------------------------------------------------------------------------
+
+namespace {
+
+constexpr uint32_t kMdMaxDim = 65535;       // voxels per axis of one box (O2V_HIP_ERR_LIMIT above)
+constexpr uint64_t kMdMaxGrid = 1ull << 24; // workgroups of k_meshdist_tiles; more tiles are taken in turns
+
+// Room for n elements; a failed allocation leaves the array empty, the runtime's error state clear and the context usable.
+template <typename T, bool P>
+int md_grow(o2v_hip_ctx *ctx, DevArray<T, P> &a, uint64_t n, const char *what)
+{
+    n = std::max<uint64_t>(n, 1);
+    if (a.ptr && n <= a.cap) return O2V_HIP_OK;
+    if (const hipError_t e = a.alloc(n); e != hipSuccess) {
+        (void) hipGetLastError();
+        ctx->err = std::string("o2v_hip_mesh_distance_dense: ") + what + " of " + std::to_string(n * sizeof(T)) + " bytes: " + hipGetErrorString(e);
+        return e == hipErrorOutOfMemory ? O2V_HIP_ERR_OUT_OF_MEMORY : O2V_HIP_ERR_HIP;
+    }
+    return O2V_HIP_OK;
+}
+
+int md_refuse(o2v_hip_ctx *ctx, int rc, const std::string &why)
+{
+    ctx->err = "o2v_hip_mesh_distance_dense: " + why;
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int o2v_hip_mesh_distance_dense(o2v_hip_ctx *ctx, const o2v_hip_params *params, float band, uint32_t format,
+                                const uint32_t origin[3], const uint32_t dims[3], float *dst, const uint64_t dst_strides[3],
+                                int32_t *closest, const uint64_t closest_strides[3])
+{
+    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
+    if (!params || !origin || !dims || !dst || !dst_strides || (closest && !closest_strides) || format > O2V_HIP_MESH_DIST_SIGNED_F32)
+        return md_refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, "null argument or unknown format");
+    if (!(std::isfinite(band) && band > 0.f && band <= 32.f))
+        return md_refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, "band must be finite, above 0 and at most 32 voxels");
+    const uint32_t ss = params->supersampling ? params->supersampling : 1u;
+    if (ss > 2u || params->resolution == 0u)
+        return md_refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, "resolution must be positive and supersampling 1 or 2");
+    if (params->z_begin || params->z_end || params->x_begin || params->x_end || params->y_begin || params->y_end)
+        return md_refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, "the slab and tile fields of params must be 0 (the box is origin, dims)");
+    for (int a = 0; a < 3; ++a) {
+        if (!dims[a] || (uint64_t) origin[a] + dims[a] > params->resolution)
+            return md_refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, "the box must have dims >= 1 and lie within the grid");
+        if (dims[a] > kMdMaxDim) return md_refuse(ctx, O2V_HIP_ERR_LIMIT, "a box of more than 65 535 voxels along an axis");
+    }
+    const unsigned __int128 dbytes = box_bytes(dims, dst_strides, 4u), cbytes = closest ? box_bytes(dims, closest_strides, 4u) : 0u;
+    if (dbytes > (unsigned __int128) (~0ull >> 1) || cbytes > (unsigned __int128) (~0ull >> 1))
+        return md_refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, "the box and strides reach past any allocation");
+    if (!dist_dst_is_distinct(dims, dst_strides) || (closest && !dist_dst_is_distinct(dims, closest_strides)))
+        return md_refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, "strides map two voxels of the box to one element");
+    const uintptr_t dp = (uintptr_t) dst, cp = (uintptr_t) closest;
+    if (closest && cp < dp + (uint64_t) dbytes && dp < cp + (uint64_t) cbytes)
+        return md_refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, "dst and closest overlap");
+    O2V_CHECK(hipSetDevice(ctx->device));
+    ctx->ktimes_on = false;   // (no per-launch brackets here; o2v_hip_voxelize sets the flag again from its params)
+    int rc;
+    if ((rc = check_device_range(ctx, dst, (uint64_t) dbytes, "dst")) || (closest && (rc = check_device_range(ctx, closest, (uint64_t) cbytes, "closest"))))
+        return rc;
+
+    const uint64_t T = ctx->n_tris;
+    MdBox b{};
+    b.x0 = origin[0];
+    b.y0 = origin[1];
+    b.z0 = origin[2];
+    b.nx = dims[0];
+    b.ny = dims[1];
+    b.nz = dims[2];
+    b.tx = (b.nx + kMdTile - 1) / kMdTile;
+    b.ty = (b.ny + kMdTile - 1) / kMdTile;
+    b.tz = (b.nz + kMdTile - 1) / kMdTile;
+    b.ss = ss;
+    b.margin = (double) band * ss + ss;
+    b.bs2 = (double) band * band * ss * ss;
+    b.band = band;
+    b.n_tiles = (uint64_t) b.tx * b.ty * b.tz;
+    // the transform k_setup computes for these params (compute_mesh_transform of the caller's bounds or the mesh's own, which
+    // the upload reduced with k_bounds), as grid_box takes it
+    Affine xf{};
+    if (T) {
+        const float *e = params->bounds_known ? params->bounds : ctx->mesh_bounds_hint;
+        xf = compute_mesh_transform(V3{e[0], e[1], e[2]}, V3{e[3], e[4], e[5]}, params->resolution * ss, params->unit_transform);
+    }
+    const uint64_t tile_blocks = (b.n_tiles + kBlock - 1) / kBlock;
+    if ((rc = md_grow(ctx, ctx->d_md_sv, T * 9u, "vertices")) || (rc = md_grow(ctx, ctx->d_md_counts, b.n_tiles, "tile counters")) ||
+        (rc = md_grow(ctx, ctx->d_md_first, b.n_tiles + 1u, "tile offsets")) || (rc = md_grow(ctx, ctx->d_md_blocks, tile_blocks, "block sums")) ||
+        (rc = md_grow(ctx, ctx->d_md_ctr, 1u, "counter")) || (rc = md_grow(ctx, ctx->h_md_ctr, 1u, "counter")))
+        return rc;
+    for (hipEvent_t &e : ctx->ev_md)
+        if (!e) O2V_CHECK(create_timing_event(&e));
+    hipStream_t s = ctx->stream;
+    const uint64_t tri_blocks = (T + kBlock - 1) / kBlock;
+
+    // binning: (triangle, tile) pairs counted, scanned, scattered into per-tile lists
+    O2V_CHECK(hipEventRecord(ctx->ev_md[0], s));
+    O2V_CHECK(hipMemsetAsync(ctx->d_md_counts.ptr, 0, b.n_tiles * sizeof(uint32_t), s));
+    if (T)
+        O2V_LAUNCH("k_meshdist_bin_count", s, k_meshdist_bin_count, dim3((uint32_t) tri_blocks), dim3(kBlock), 0, s, ctx->d_verts.ptr, T, xf, b,
+                   ctx->d_md_sv.ptr, ctx->d_md_counts.ptr);
+    O2V_LAUNCH("k_meshdist_tile_sums", s, k_meshdist_tile_sums, dim3((uint32_t) tile_blocks), dim3(kBlock), 0, s, ctx->d_md_counts.ptr, b.n_tiles,
+               ctx->d_md_blocks.ptr);
+    O2V_LAUNCH("k_fill_scan_blocks", s, k_fill_scan_blocks, dim3(1), dim3(kBlock), 0, s, ctx->d_md_blocks.ptr, tile_blocks, ctx->d_md_ctr.ptr);
+    O2V_LAUNCH("k_meshdist_tile_offsets", s, k_meshdist_tile_offsets, dim3((uint32_t) ((b.n_tiles + kBlock) / kBlock)), dim3(kBlock), 0, s,
+               ctx->d_md_counts.ptr, b.n_tiles, ctx->d_md_blocks.ptr, ctx->d_md_ctr.ptr, ctx->d_md_first.ptr);
+    O2V_CHECK(hipMemcpyAsync(ctx->h_md_ctr.ptr, ctx->d_md_ctr.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    O2V_CHECK(hipStreamSynchronize(s));
+    const uint64_t n_pairs = ctx->h_md_ctr.ptr[0];
+    if ((rc = md_grow(ctx, ctx->d_md_lists, n_pairs, "triangle lists"))) return rc;
+    if (n_pairs)
+        O2V_LAUNCH("k_meshdist_bin_scatter", s, k_meshdist_bin_scatter, dim3((uint32_t) tri_blocks), dim3(kBlock), 0, s, ctx->d_md_sv.ptr, T, b,
+                   ctx->d_md_first.ptr, ctx->d_md_counts.ptr, ctx->d_md_lists.ptr);
+    O2V_CHECK(hipEventRecord(ctx->ev_md[1], s));
+
+    // parity (signed): K6's bitmap of the box, no unmark step
+    const uint32_t *bits = nullptr;
+    if (format == O2V_HIP_MESH_DIST_SIGNED_F32 && T) {
+        FillBox fb{};
+        fb.x0 = b.x0;
+        fb.y0 = b.y0;
+        fb.z0 = b.z0;
+        fb.nx = b.nx;
+        fb.ny = b.ny;
+        fb.nz = b.nz;
+        fb.nzw = (fb.nz + 31u) / 32u;
+        fb.ss = ss;
+        fb.n_cols = (uint64_t) fb.nx * fb.ny;
+        fb.n_words = (uint64_t) fb.nzw * fb.n_cols;
+        if ((rc = parity_bits(ctx, xf, fb))) {
+            (void) hipGetLastError();
+            return rc;
+        }
+        bits = ctx->d_fill_bits.ptr;
+    }
+    O2V_CHECK(hipEventRecord(ctx->ev_md[2], s));
+
+    // distance: one workgroup per tile
+    O2V_LAUNCH("k_meshdist_tiles", s, k_meshdist_tiles, dim3((uint32_t) std::min<uint64_t>(b.n_tiles, kMdMaxGrid)), dim3(kBlock), 0, s,
+               ctx->d_md_sv.ptr, b, ctx->d_md_first.ptr, ctx->d_md_lists.ptr, bits, dst, dst_strides[0], dst_strides[1], dst_strides[2],
+               closest, closest ? closest_strides[0] : 0u, closest ? closest_strides[1] : 0u, closest ? closest_strides[2] : 0u);
+    O2V_CHECK(hipGetLastError());
+    O2V_CHECK(hipEventRecord(ctx->ev_md[3], s));
+    O2V_CHECK(hipStreamSynchronize(s));
+    for (int i = 0; i < 3; ++i) O2V_CHECK(hipEventElapsedTime(&ctx->md_ms[i], ctx->ev_md[i], ctx->ev_md[i + 1]));
+    return O2V_HIP_OK;
+}
+
+int o2v_hip_mesh_distance_times(const o2v_hip_ctx *ctx, float out_ms[3])
+{
+    if (!ctx || !out_ms) return O2V_HIP_ERR_BAD_ARGUMENT;
+    for (int i = 0; i < 3; ++i) out_ms[i] = ctx->md_ms[i];
     return O2V_HIP_OK;
 }
 

@@ -8,11 +8,14 @@
 
 The mesh goes to the device context without a host copy (o2v_hip_set_triangles_device) and the voxels come back as a dense
 tensor written on the device (o2v_hip_write_dense); nothing of either crosses to the host.  Distance grids (fmt "dist2" /
-"sdf", and distance_transform on any label tensor) come from o2v_hip_distance_dense.
+"sdf", and distance_transform on any label tensor) come from o2v_hip_distance_dense; mesh_distance is the
+narrow-band distance to the triangles themselves (o2v_hip_mesh_distance_dense).
 
 torch is imported first on purpose: the library must bind to the HIP runtime torch loaded (a process that loaded the library
 before torch holds two separate runtime copies, and this module refuses to work there).
 """
+import numbers
+
 import torch  # first: see above
 
 from . import hip
@@ -29,6 +32,7 @@ DISTANCE_FORMATS = {  # name: (o2v_hip_distance_dense format, tensor dtype)
 }
 STRATEGIES = {"max": hip.STRATEGY_MAX, "blend": hip.STRATEGY_BLEND}
 MAX_SAMPLES = 65535  # samples per axis of one pass (x / y tiles above that are not supported here)
+MAX_BAND = 32.0      # mesh_distance: the widest band, in voxels
 
 
 def _require_shared_runtime():
@@ -255,3 +259,67 @@ def distance_transform(dv, labels, fmt="sdf", *, out=None):
     dv.distance_dense(labels.data_ptr(), (labels.stride(2), labels.stride(1), labels.stride(0)), out.data_ptr(), code,
                       (out.stride(2), out.stride(1), out.stride(0)), (nx, ny, nz))
     return out
+
+
+def mesh_distance(dv, resolution, *, band, signed=True, out=None, closest=None, origin=None, supersampling=1, unit_transform=None,
+                  bounds=None, max_layers=None):
+    """The distance from every voxel centre of a box to the triangles of `dv`'s mesh (set_mesh), exact within `band` voxels
+    (0 < band <= 32) and `band` beyond it.  Returns (dist, origin), or (dist, closest, origin) when
+    `closest` is given: voxel (x, y, z) is dist[z - oz, y - oy, x - ox].
+
+    signed:   True: negative in the solid fill's parity set (the sign fmt="labels", fill=True gives the interior, surface voxels
+              included); False: unsigned, for open meshes and triangle soups.
+    out:      a float32 3-D tensor [z, y, x] of any strides on the voxelizer's device; the box is `origin` (default 0) plus its
+              shape.  Without it the box is the grid from `origin` on, into a new contiguous tensor.
+    closest:  None; True for a new int32 tensor; or an int32 tensor of the box's shape (any strides, not in out's storage):
+              the index of the closest triangle (the smallest on a tie), -1 where the distance is the band.
+    The transform is voxelize's for the same resolution, supersampling, unit_transform and bounds.  max_layers cuts the box
+    into z ranges of at most that many layers, one call each, written into the one tensor (the same bits as one call)."""
+    _require_shared_runtime()
+    if isinstance(band, bool) or not isinstance(band, numbers.Real) or not (0.0 < float(band) <= MAX_BAND):
+        raise ValueError(f"band must be a number with 0 < band <= {MAX_BAND:g} voxels, not {band!r}")
+    if resolution < 1 or supersampling not in (1, 2):
+        raise ValueError("resolution must be positive and supersampling 1 or 2")
+    if max_layers is not None and max_layers < 1:
+        raise ValueError("max_layers must be positive")
+    device = _device(dv)
+    origin = tuple(int(v) for v in (origin or (0, 0, 0)))
+    if len(origin) != 3 or any(v < 0 or v >= resolution for v in origin):
+        raise ValueError(f"origin {origin} must be three voxel coordinates inside the grid")
+    if out is None:
+        out = torch.empty(tuple(resolution - v for v in origin[::-1]), dtype=torch.float32, device=device)
+    else:
+        if not isinstance(out, torch.Tensor) or out.dim() != 3:
+            raise ValueError("out must be a 3-D tensor [z, y, x]")
+        if out.dtype != torch.float32:
+            raise TypeError(f"out must be torch.float32, not {out.dtype}")
+        if out.device != device:
+            raise ValueError(f"out is on {out.device}, the voxelizer on {device}")
+        if 0 in out.shape:
+            raise ValueError("out has an empty dimension")
+        if any(o + n > resolution for o, n in zip(origin, out.shape[::-1])):
+            raise ValueError(f"origin {origin} + out's extent {tuple(out.shape[::-1])} [x, y, z] reaches past the grid of {resolution}")
+    want_closest = closest is not None
+    if closest is True:
+        closest = torch.empty(tuple(out.shape), dtype=torch.int32, device=device)
+    elif closest is not None:
+        if not isinstance(closest, torch.Tensor) or tuple(closest.shape) != tuple(out.shape):
+            raise ValueError(f"closest must be True or a tensor of the box's shape {tuple(out.shape)}")
+        if closest.dtype != torch.int32:
+            raise TypeError(f"closest must be torch.int32, not {closest.dtype}")
+        if closest.device != device:
+            raise ValueError(f"closest is on {closest.device}, the voxelizer on {device}")
+        if closest.untyped_storage().data_ptr() == out.untyped_storage().data_ptr():
+            raise ValueError("closest must not share out's storage")
+    fmt = hip.MESH_DIST_SIGNED_F32 if signed else hip.MESH_DIST_UNSIGNED_F32
+    nz, ny, nx = out.shape
+    step = nz if max_layers is None else max_layers
+    _sync(device)   # (the caller's writes to out and closest have landed)
+    for z in range(0, nz, step):
+        k = min(step, nz - z)
+        o = out[z:z + k]
+        c = None if closest is None else closest[z:z + k]
+        dv.mesh_distance_dense(resolution, float(band), fmt, (origin[0], origin[1], origin[2] + z), (nx, ny, k), o.data_ptr(),
+                               (o.stride(2), o.stride(1), o.stride(0)), _ptr(c), None if c is None else (c.stride(2), c.stride(1), c.stride(0)),
+                               supersampling=supersampling, unit_transform=unit_transform, bounds=bounds)
+    return (out, closest, origin) if want_closest else (out, origin)

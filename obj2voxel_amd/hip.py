@@ -24,6 +24,7 @@ FLAG_EXACT_CLIP = 1  # o2v_hip_params::flags: the clip kernel without its work-r
 FLAG_FILL_INTERIOR = 8  # ... solid voxelization: the interior voxels (colour fill_argb) behind the surface records
 DENSE_U8, DENSE_ARGB32, DENSE_BITS = 0, 1, 2  # o2v_hip_write_dense formats
 DIST_SQ_I32, DIST_SDF_F32 = 0, 1  # o2v_hip_distance_dense formats
+MESH_DIST_UNSIGNED_F32, MESH_DIST_SIGNED_F32 = 0, 1  # o2v_hip_mesh_distance_dense formats
 ERR_BAD_ARGUMENT = 3
 
 
@@ -115,6 +116,9 @@ def _bind():
     L.o2v_hip_distance_scratch_bytes.argtypes = [C.c_void_p, C.c_uint32]
     L.o2v_hip_distance_scratch_bytes.restype = C.c_uint64
     L.o2v_hip_distance_times.argtypes = [C.c_void_p, C.c_void_p]
+    L.o2v_hip_mesh_distance_dense.argtypes = [C.c_void_p, C.POINTER(_Params), C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]
+    L.o2v_hip_mesh_distance_times.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_max_slab_layers.argtypes = [C.c_void_p, C.POINTER(_Params), C.POINTER(C.c_uint32)]
     return L
 
@@ -260,6 +264,27 @@ class DeviceVoxelizer:
         """o2v_hip_distance_times: the device times (ms) of the last distance_dense call's x, y and z passes."""
         ms = (C.c_float * 3)()
         self._check(self._L.o2v_hip_distance_times(self._ctx, ms), "o2v_hip_distance_times")
+        return tuple(float(v) for v in ms)
+
+    def mesh_distance_dense(self, resolution, band, fmt, origin, dims, dst_ptr, dst_strides, closest_ptr=None, closest_strides=None, *,
+                            supersampling=1, unit_transform=None, bounds=None):
+        """o2v_hip_mesh_distance_dense: the narrow-band distance (voxels, truncated at `band`) from the centres of the box
+        origin + [0, dims) to the context's triangles, MESH_DIST_UNSIGNED_F32 or MESH_DIST_SIGNED_F32, into float32 at device
+        address dst_ptr and, if closest_ptr is given, the closest triangle's index (int32, -1 outside the band); strides in
+        elements, origin, dims and strides per axis x, y, z."""
+        p = self._params(resolution, supersampling, 0, unit_transform, bounds, (0, 0))
+        o = (C.c_uint32 * 3)(*[int(v) for v in origin])
+        d = (C.c_uint32 * 3)(*[int(v) for v in dims])
+        ds = (C.c_uint64 * 3)(*[int(v) for v in dst_strides])
+        cs = None if closest_strides is None else (C.c_uint64 * 3)(*[int(v) for v in closest_strides])
+        self._check(self._L.o2v_hip_mesh_distance_dense(self._ctx, C.byref(p), float(band), fmt, o, d, dst_ptr, ds, closest_ptr, cs),
+                    "o2v_hip_mesh_distance_dense")
+
+    def mesh_distance_times(self):
+        """o2v_hip_mesh_distance_times: the device times (ms) of the last mesh_distance_dense call's binning, parity and
+        distance stages (parity 0 when unsigned)."""
+        ms = (C.c_float * 3)()
+        self._check(self._L.o2v_hip_mesh_distance_times(self._ctx, ms), "o2v_hip_mesh_distance_times")
         return tuple(float(v) for v in ms)
 
     def set_textures(self, textures):

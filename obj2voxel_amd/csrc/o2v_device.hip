@@ -110,6 +110,41 @@ struct DevArray {
 };
 template <typename T> using PinnedArray = DevArray<T, true>;
 
+// An event that is only ever used to read a time: without the system-scope fence a default event performs when it is recorded
+// (cache write-back and invalidation in the middle of the pass; nothing on the host reads device memory on its strength).
+// Measured: the six stage events of a pass cost 0.009 ms less this way (bench headline, O2V_HIP_FLAG_STAGE_TIMES).
+hipError_t create_timing_event(hipEvent_t *e) { return hipEventCreateWithFlags(e, hipEventDisableSystemFence); }
+
+// Events around the N stages of a call and the stages' device times (ms) of the last call that finished.  mark(i) is where
+// stage i begins (mark(N): where the last one ends); the first mark(0) creates the events.
+template <int N>
+struct StageTimes {
+    hipEvent_t ev[N + 1] = {};
+    float ms[N] = {};
+
+    hipError_t mark(int i, hipStream_t s)
+    {
+        if (i == 0)
+            for (hipEvent_t &e : ev)
+                if (!e)
+                    if (const hipError_t r = create_timing_event(&e); r != hipSuccess) return r;
+        return hipEventRecord(ev[i], s);
+    }
+    // once the stream has passed mark(N)
+    hipError_t finish()
+    {
+        for (int i = 0; i < N; ++i)
+            if (const hipError_t r = hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]); r != hipSuccess) return r;
+        return hipSuccess;
+    }
+    int read(float out_ms[N]) const
+    {
+        if (!out_ms) return O2V_HIP_ERR_BAD_ARGUMENT;
+        std::copy(ms, ms + N, out_ms);
+        return O2V_HIP_OK;
+    }
+};
+
 constexpr uint64_t kStageTriangles = 1u << 16;  // per staging block: 2.25 MiB of vertices, 5 MiB with every optional array
 
 // one page-locked staging block of the streamed upload (o2v_hip_begin / commit / end_triangles)
@@ -246,18 +281,16 @@ struct o2v_hip_ctx {
     // K7 (o2v_hip_set_triangles_device, o2v_hip_write_dense, o2v_hip_voxels_box): flags and sums, allocated on first use
     DevArray<DenseCtr> d_dense;
     PinnedArray<DenseCtr> h_dense;
-    // K8 (o2v_hip_distance_dense): the envelope stacks, grown on demand; events around the three passes and their times
+    // K8 (o2v_hip_distance_dense): the envelope stacks, grown on demand; the times of the three passes
     DevArray<uint2> d_dist_stack;
-    hipEvent_t ev_dist[4] = {nullptr, nullptr, nullptr, nullptr};
-    float dist_ms[3] = {0.f, 0.f, 0.f};
+    StageTimes<3> dist_times;
     // K9 (o2v_hip_mesh_distance_dense): sample-space vertices, per-tile counters, offsets and triangle lists, grown on demand;
-    // events around the three stages and their times
+    // the times of the three stages
     DevArray<float> d_md_sv;
     DevArray<uint32_t> d_md_counts, d_md_lists;
     DevArray<unsigned long long> d_md_first, d_md_blocks, d_md_ctr;
     PinnedArray<unsigned long long> h_md_ctr;
-    hipEvent_t ev_md[4] = {nullptr, nullptr, nullptr, nullptr};
-    float md_ms[3] = {0.f, 0.f, 0.f};
+    StageTimes<3> md_times;
 
     // results of the last run
     uint64_t n_vox = 0;
@@ -377,11 +410,6 @@ bool debug_sync_enabled() { return debug_sync_level() != 0; }
             O2V_STAGE(name);                                                                                        \
         }                                                                                                           \
     } while (0)
-
-// An event that is only ever used to read a time: without the system-scope fence a default event performs when it is recorded
-// (cache write-back and invalidation in the middle of the pass; nothing on the host reads device memory on its strength).
-// Measured: the six stage events of a pass cost 0.009 ms less this way (bench headline, O2V_HIP_FLAG_STAGE_TIMES).
-hipError_t create_timing_event(hipEvent_t *e) { return hipEventCreateWithFlags(e, hipEventDisableSystemFence); }
 
 int ktime_begin(o2v_hip_ctx *ctx, const char *name, hipStream_t stream)
 {
@@ -1282,6 +1310,14 @@ int check_pass(o2v_hip_ctx *ctx, Run &r, bool &again)
 // Whether the pass that stood emitted its records from the 64-bit max grid (direct_active() on the device): h.n_out records, else h.n_vox.
 bool pass_direct(const Params &p, const Counters &h) { return p.direct_max && (p.occupancy_only || h.n_nodes[0] <= h.n_root_leaves); }
 
+// K6's box of extent n from lo (output voxels) at supersampling ss; argb: the colour of its interior records.
+FillBox fill_box(const uint32_t lo[3], const uint32_t n[3], uint32_t ss, uint32_t argb)
+{
+    const uint32_t nzw = (n[2] + 31u) / 32u;
+    const uint64_t n_cols = (uint64_t) n[0] * n[1];
+    return FillBox{lo[0], lo[1], lo[2], n[0], n[1], n[2], nzw, ss, argb, n_cols, (uint64_t) nzw * n_cols};
+}
+
 // K6's parity set of box b as a bitmap in ctx->d_fill_bits ([z-word][y][x]): the crossings of the context's triangles (sample
 // space by xf) toggled and prefix-XORed along z, cut at the mesh's top layer.  Enqueued on the context's stream; the fill stage
 // and o2v_hip_mesh_distance_dense (K9) share it.
@@ -1315,18 +1351,8 @@ int fill_stage(o2v_hip_ctx *ctx, const o2v_hip_params *params, const Run &r, uin
 {
     hipStream_t s = ctx->stream;
     n_interior = 0;
-    FillBox b{};
-    b.x0 = r.box.lo[0];
-    b.y0 = r.box.lo[1];
-    b.z0 = r.box.lo[2];
-    b.nx = r.box.hi[0] - r.box.lo[0];
-    b.ny = r.box.hi[1] - r.box.lo[1];
-    b.nz = r.box.hi[2] - r.box.lo[2];
-    b.nzw = (b.nz + 31u) / 32u;
-    b.ss = params->supersampling ? params->supersampling : 1u;
-    b.argb = params->fill_argb;
-    b.n_cols = (uint64_t) b.nx * b.ny;
-    b.n_words = (uint64_t) b.nzw * b.n_cols;
+    const uint32_t n[3] = {r.box.hi[0] - r.box.lo[0], r.box.hi[1] - r.box.lo[1], r.box.hi[2] - r.box.lo[2]};
+    const FillBox b = fill_box(r.box.lo, n, params->supersampling ? params->supersampling : 1u, params->fill_argb);
     const uint64_t T = ctx->n_tris, n_blocks = (T + kBlock - 1) / kBlock;
     const uint64_t n_chunks = (b.n_words + kFillChunk - 1) / kFillChunk;
     // (kMaxRecords: the grids' arrays of 32-bit capacity; the bitmap is indexed in 64 bits, its limit is the memory)
@@ -1630,8 +1656,8 @@ void o2v_hip_destroy(o2v_hip_ctx *ctx)
     std::vector<hipEvent_t> events{std::begin(ctx->ev), std::end(ctx->ev)};
     events.insert(events.end(), {ctx->ev_coll[0], ctx->ev_coll[1], ctx->ev_stage[0], ctx->ev_stage[1], ctx->ev_fork, ctx->ev_sorted,
                                  ctx->ev_k1, ctx->ev_join[0], ctx->ev_join[1], ctx->ev_join[2], ctx->ev_fill[0], ctx->ev_fill[1]});
-    events.insert(events.end(), std::begin(ctx->ev_dist), std::end(ctx->ev_dist));
-    events.insert(events.end(), std::begin(ctx->ev_md), std::end(ctx->ev_md));
+    events.insert(events.end(), std::begin(ctx->dist_times.ev), std::end(ctx->dist_times.ev));
+    events.insert(events.end(), std::begin(ctx->md_times.ev), std::end(ctx->md_times.ev));
     for (const auto &b : ctx->ktimes) events.insert(events.end(), {b.e0, b.e1});
     for (hipEvent_t e : events)
         if (e) (void) hipEventDestroy(e);
@@ -2255,39 +2281,88 @@ int o2v_hip_voxels_device_ptr(o2v_hip_ctx *ctx, const uint32_t **out_ptr, uint64
 
 namespace {
 
+// The refusal of a call of the entry point fn: "fn: why" becomes the context's error, rc is returned.
+int refuse(o2v_hip_ctx *ctx, int rc, const char *fn, const std::string &why)
+{
+    ctx->err = std::string(fn) + ": " + why;
+    return rc;
+}
+
 // [p, p + bytes) must be device (or managed) memory of the context's device and lie inside one allocation.  A pointer the
 // runtime does not know leaves an error in its per-thread state, which is cleared here so that the next call does not see it.
-int check_device_range(o2v_hip_ctx *ctx, const void *p, uint64_t bytes, const char *what)
+int check_device_range(o2v_hip_ctx *ctx, const char *fn, const void *p, uint64_t bytes, const char *what)
 {
     hipPointerAttribute_t a{};
     if (hipPointerGetAttributes(&a, p) != hipSuccess) {
         (void) hipGetLastError();
-        ctx->err = std::string(what) + " is not memory the HIP runtime knows";
-        return O2V_HIP_ERR_BAD_ARGUMENT;
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, std::string(what) + " is not memory the HIP runtime knows");
     }
-    if ((a.type != hipMemoryTypeDevice && a.type != hipMemoryTypeManaged && !a.isManaged) || a.device != ctx->device) {
-        ctx->err = std::string(what) + " is not device memory of the context's device " + std::to_string(ctx->device);
-        return O2V_HIP_ERR_BAD_ARGUMENT;
-    }
+    if ((a.type != hipMemoryTypeDevice && a.type != hipMemoryTypeManaged && !a.isManaged) || a.device != ctx->device)
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn,
+                      std::string(what) + " is not device memory of the context's device " + std::to_string(ctx->device));
     hipDeviceptr_t base = nullptr;
     size_t size = 0;
     if (hipMemGetAddressRange(&base, &size, const_cast<void *>(p)) != hipSuccess) {
         (void) hipGetLastError();
-        ctx->err = std::string(what) + ": the runtime does not know its allocation";
-        return O2V_HIP_ERR_BAD_ARGUMENT;
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, std::string(what) + ": the runtime does not know its allocation");
     }
     const uint64_t offset = (uint64_t) ((const char *) p - (const char *) base);
-    if (offset > size || bytes > size - offset) {
-        ctx->err = std::string(what) + ": " + std::to_string(bytes) + " bytes from its address extend past its allocation";
-        return O2V_HIP_ERR_BAD_ARGUMENT;
-    }
+    if (offset > size || bytes > size - offset)
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn,
+                      std::string(what) + ": " + std::to_string(bytes) + " bytes from its address extend past its allocation");
     return O2V_HIP_OK;
 }
 
-int dense_ctr(o2v_hip_ctx *ctx)
+// Along the axes of more than one voxel, taken by rising stride, each stride must step past everything the axes before it
+// reach, or two voxels of the box share an element (a stride of 0, as of an expanded tensor, fails this).
+bool strides_distinct(const uint32_t dims[3], const uint64_t strides[3])
 {
-    if (!ctx->d_dense.ptr) O2V_CHECK(ctx->d_dense.alloc(1));
-    if (!ctx->h_dense.ptr) O2V_CHECK(ctx->h_dense.alloc(1));
+    int ax[3] = {0, 1, 2};
+    std::sort(ax, ax + 3, [&](int a, int b) { return strides[a] < strides[b]; });
+    unsigned __int128 reach = 0;   // the highest element offset the axes so far reach
+    for (int a : ax) {
+        if (dims[a] == 1) continue;
+        if ((unsigned __int128) strides[a] <= reach) return false;
+        reach += (unsigned __int128) (dims[a] - 1u) * strides[a];
+    }
+    return true;
+}
+
+// A grid the caller owns, passed to the entry point fn as `what`: dims voxels at these element strides (x, y, z) from p, of
+// elem bytes each.  Refused if its reach (in 128 bits: the strides are the caller's) is above 2^63 - 1 bytes, if `distinct`
+// and two voxels share an element, or if check_device_range refuses it.  out_bytes: the reach, the bytes past p it touches.
+int check_grid(o2v_hip_ctx *ctx, const char *fn, const char *what, const void *p, const uint32_t dims[3], const uint64_t strides[3],
+               uint32_t elem, bool distinct, uint64_t *out_bytes = nullptr)
+{
+    unsigned __int128 last = 0;
+    for (int a = 0; a < 3; ++a) last += (unsigned __int128) (dims[a] - 1u) * strides[a];
+    const unsigned __int128 bytes = (last + 1u) * elem;
+    if (bytes > (unsigned __int128) (~0ull >> 1))
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, std::string(what) + ": the box and strides reach past any allocation");
+    if (distinct && !strides_distinct(dims, strides))
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, std::string(what) + ": strides map two voxels of the box to one element");
+    if (out_bytes) *out_bytes = (uint64_t) bytes;
+    return check_device_range(ctx, fn, p, (uint64_t) bytes, what);
+}
+
+bool ranges_overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
+{
+    const uintptr_t x = (uintptr_t) a, y = (uintptr_t) b;
+    return x < y + b_bytes && y < x + a_bytes;
+}
+
+// Room for n elements (at least one) of an array of the entry point fn.  A failed allocation leaves the array empty, the
+// runtime's error state clear and the context usable.  (The voxelize pipeline grows its arrays with grow / grow_keep.)
+template <typename T, bool P>
+int grow_scratch(o2v_hip_ctx *ctx, DevArray<T, P> &a, uint64_t n, const char *fn, const char *what)
+{
+    n = std::max<uint64_t>(n, 1);
+    if (a.ptr && n <= a.cap) return O2V_HIP_OK;
+    if (const hipError_t e = a.alloc(n); e != hipSuccess) {
+        (void) hipGetLastError();
+        return refuse(ctx, e == hipErrorOutOfMemory ? O2V_HIP_ERR_OUT_OF_MEMORY : O2V_HIP_ERR_HIP, fn,
+                      std::string(what) + " of " + std::to_string(n * sizeof(T)) + " bytes: " + hipGetErrorString(e));
+    }
     return O2V_HIP_OK;
 }
 
@@ -2304,36 +2379,23 @@ int o2v_hip_set_triangles_device(o2v_hip_ctx *ctx, const float *positions, uint6
                                  uint32_t index_bytes, const float *uvs, const uint32_t *types, const float *colors,
                                  const int32_t *texids, uint64_t count)
 {
+    static const char fn[] = "o2v_hip_set_triangles_device";
     if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
-    if (count && !positions) {
-        ctx->err = "positions is null";
-        return O2V_HIP_ERR_BAD_ARGUMENT;
-    }
-    if (faces && index_bytes != 4 && index_bytes != 8) {
-        ctx->err = "index_bytes must be 4 or 8";
-        return O2V_HIP_ERR_BAD_ARGUMENT;
-    }
-    if (count >= (1ull << 29)) {
-        ctx->err = "triangle count must be below 2^29";
-        return O2V_HIP_ERR_LIMIT;
-    }
-    if (faces && count && n_positions == 0) {
-        ctx->err = "n_positions is 0 but there are faces";
-        return O2V_HIP_ERR_BAD_ARGUMENT;
-    }
-    if (faces && n_positions > (~0ull >> 4)) {
-        ctx->err = "n_positions is too large";
-        return O2V_HIP_ERR_BAD_ARGUMENT;
-    }
+    if (count && !positions) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "positions is null");
+    if (faces && index_bytes != 4 && index_bytes != 8) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "index_bytes must be 4 or 8");
+    if (count >= (1ull << 29)) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "triangle count must be below 2^29");
+    if (faces && count && n_positions == 0) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "n_positions is 0 but there are faces");
+    if (faces && n_positions > (~0ull >> 4)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "n_positions is too large");
     O2V_CHECK(hipSetDevice(ctx->device));
     int rc;
     if (count) {
-        if ((rc = check_device_range(ctx, positions, faces ? n_positions * 12u : count * 36u, "positions")) ||
-            (faces && (rc = check_device_range(ctx, faces, count * 3u * index_bytes, "faces"))) ||
-            (uvs && (rc = check_device_range(ctx, uvs, count * 24u, "uvs"))) ||
-            (types && (rc = check_device_range(ctx, types, count * 4u, "types"))) ||
-            (colors && (rc = check_device_range(ctx, colors, count * 12u, "colors"))) ||
-            (texids && (rc = check_device_range(ctx, texids, count * 4u, "texids"))) || (rc = dense_ctr(ctx)))
+        if ((rc = check_device_range(ctx, fn, positions, faces ? n_positions * 12u : count * 36u, "positions")) ||
+            (faces && (rc = check_device_range(ctx, fn, faces, count * 3u * index_bytes, "faces"))) ||
+            (uvs && (rc = check_device_range(ctx, fn, uvs, count * 24u, "uvs"))) ||
+            (types && (rc = check_device_range(ctx, fn, types, count * 4u, "types"))) ||
+            (colors && (rc = check_device_range(ctx, fn, colors, count * 12u, "colors"))) ||
+            (texids && (rc = check_device_range(ctx, fn, texids, count * 4u, "texids"))) ||
+            (rc = grow_scratch(ctx, ctx->d_dense, 1, fn, "counters")) || (rc = grow_scratch(ctx, ctx->h_dense, 1, fn, "counters")))
             return rc;
     }
     if ((rc = o2v::ctx_alloc_triangles(ctx, count, uvs != nullptr, types != nullptr, colors != nullptr, texids != nullptr))) return rc;
@@ -2367,9 +2429,8 @@ int o2v_hip_set_triangles_device(o2v_hip_ctx *ctx, const float *positions, uint6
     if (ctx->h_dense.ptr->bad_index) {
         if ((rc = o2v::ctx_alloc_triangles(ctx, 0, false, false, false, false)) || (rc = o2v::ctx_finish_triangles(ctx, false, nullptr)))
             return rc;
-        ctx->err = "face index out of range: an index is negative, not below n_positions (" + std::to_string(n_positions) +
-                   ") or not below 2^32; the context holds no triangles";
-        return O2V_HIP_ERR_BAD_ARGUMENT;
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "face index out of range: an index is negative, not below n_positions (" +
+                      std::to_string(n_positions) + ") or not below 2^32; the context holds no triangles");
     }
     ctx->any_textured = ctx->h_dense.ptr->textured != 0;
     return O2V_HIP_OK;
@@ -2378,31 +2439,19 @@ int o2v_hip_set_triangles_device(o2v_hip_ctx *ctx, const float *positions, uint6
 int o2v_hip_write_dense(o2v_hip_ctx *ctx, void *dst, uint32_t format, const uint32_t origin[3], const uint32_t dims[3],
                         const uint64_t strides[3], uint64_t *out_outside)
 {
+    static const char fn[] = "o2v_hip_write_dense";
     if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
-    if (!dst || !origin || !dims || !strides || format > O2V_HIP_DENSE_BITS) {
-        ctx->err = "o2v_hip_write_dense: null argument or unknown format";
-        return O2V_HIP_ERR_BAD_ARGUMENT;
-    }
-    if (!dims[0] || !dims[1] || !dims[2]) {
-        ctx->err = "o2v_hip_write_dense: zero dims";
-        return O2V_HIP_ERR_BAD_ARGUMENT;
-    }
-    if (format == O2V_HIP_DENSE_BITS && strides[0] != 1) {
-        ctx->err = "o2v_hip_write_dense: BITS needs strides[0] == 1";
-        return O2V_HIP_ERR_BAD_ARGUMENT;
-    }
-    // the highest element the box can reach, in bytes past dst (128-bit: the strides are the caller's)
-    const unsigned __int128 hx = format == O2V_HIP_DENSE_BITS ? (dims[0] - 1u) / 32u : (uint64_t) (dims[0] - 1u) * (unsigned __int128) strides[0];
-    const unsigned __int128 last = hx + (unsigned __int128) (dims[1] - 1u) * strides[1] + (unsigned __int128) (dims[2] - 1u) * strides[2];
-    const uint32_t elem = format == O2V_HIP_DENSE_U8 ? 1u : 4u;
-    const unsigned __int128 bytes = (last + 1u) * elem;
-    if (bytes > (unsigned __int128) (~0ull >> 1)) {
-        ctx->err = "o2v_hip_write_dense: the box and strides reach past any allocation";
-        return O2V_HIP_ERR_BAD_ARGUMENT;
-    }
+    if (!dst || !origin || !dims || !strides || format > O2V_HIP_DENSE_BITS)
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument or unknown format");
+    if (!dims[0] || !dims[1] || !dims[2]) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "zero dims");
+    if (format == O2V_HIP_DENSE_BITS && strides[0] != 1) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "BITS needs strides[0] == 1");
     O2V_CHECK(hipSetDevice(ctx->device));
+    // (BITS: x counted in 32-bit words; aliasing strides are the caller's business here)
+    const uint32_t box[3] = {format == O2V_HIP_DENSE_BITS ? (dims[0] - 1u) / 32u + 1u : dims[0], dims[1], dims[2]};
     int rc;
-    if ((rc = check_device_range(ctx, dst, (uint64_t) bytes, "dst")) || (rc = dense_ctr(ctx))) return rc;
+    if ((rc = check_grid(ctx, fn, "dst", dst, box, strides, format == O2V_HIP_DENSE_U8 ? 1u : 4u, false)) ||
+        (rc = grow_scratch(ctx, ctx->d_dense, 1, fn, "counters")) || (rc = grow_scratch(ctx, ctx->h_dense, 1, fn, "counters")))
+        return rc;
     if (out_outside) *out_outside = 0;
     const uint64_t n = ctx->n_vox;
     if (!n) return O2V_HIP_OK;
@@ -2432,7 +2481,9 @@ int o2v_hip_voxels_box(o2v_hip_ctx *ctx, uint32_t lo[3], uint32_t hi[3])
     const uint64_t n = ctx->n_vox;
     if (!n) return O2V_HIP_OK;
     O2V_CHECK(hipSetDevice(ctx->device));
-    if (const int rc = dense_ctr(ctx)) return rc;
+    static const char fn[] = "o2v_hip_voxels_box";
+    if (int rc; (rc = grow_scratch(ctx, ctx->d_dense, 1, fn, "counters")) || (rc = grow_scratch(ctx, ctx->h_dense, 1, fn, "counters")))
+        return rc;
     hipStream_t s = ctx->stream;
     DenseCtr *const ctr = ctx->d_dense.ptr;
     O2V_CHECK(hipMemsetAsync(ctr->lo, 0xff, sizeof(ctr->lo), s));
@@ -2457,29 +2508,6 @@ constexpr uint64_t kDistMaxSlots = 1u << 17;
 
 uint64_t dist_slots(uint64_t lines) { return std::min<uint64_t>(lines, kDistMaxSlots); }
 
-// dst must not alias: along the axes of more than one voxel, taken by rising stride, each stride must step past everything
-// the axes before it reach (a stride of 0, as of an expanded tensor, fails this).
-bool dist_dst_is_distinct(const uint32_t dims[3], const uint64_t strides[3])
-{
-    int ax[3] = {0, 1, 2};
-    std::sort(ax, ax + 3, [&](int a, int b) { return strides[a] < strides[b]; });
-    unsigned __int128 reach = 0;   // the highest element offset the axes so far reach
-    for (int a : ax) {
-        if (dims[a] == 1) continue;
-        if ((unsigned __int128) strides[a] <= reach) return false;
-        reach += (unsigned __int128) (dims[a] - 1u) * strides[a];
-    }
-    return true;
-}
-
-// The bytes past p that a box of dims with these element strides reaches (128-bit: the strides are the caller's).
-unsigned __int128 box_bytes(const uint32_t dims[3], const uint64_t strides[3], uint32_t elem)
-{
-    unsigned __int128 last = 0;
-    for (int a = 0; a < 3; ++a) last += (unsigned __int128) (dims[a] - 1u) * strides[a];
-    return (last + 1u) * elem;
-}
-
 }  // namespace
 
 extern "C" {
@@ -2495,48 +2523,25 @@ uint64_t o2v_hip_distance_scratch_bytes(const uint32_t dims[3], uint32_t format)
 int o2v_hip_distance_dense(o2v_hip_ctx *ctx, const void *labels, const uint64_t label_strides[3], void *dst, uint32_t format,
                            const uint64_t dst_strides[3], const uint32_t dims[3])
 {
+    static const char fn[] = "o2v_hip_distance_dense";
     if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
-    if (!labels || !label_strides || !dst || !dst_strides || !dims || format > O2V_HIP_DIST_SDF_F32) {
-        ctx->err = "o2v_hip_distance_dense: null argument or unknown format";
-        return O2V_HIP_ERR_BAD_ARGUMENT;
-    }
-    if (!dims[0] || !dims[1] || !dims[2]) {
-        ctx->err = "o2v_hip_distance_dense: zero dims";
-        return O2V_HIP_ERR_BAD_ARGUMENT;
-    }
+    if (!labels || !label_strides || !dst || !dst_strides || !dims || format > O2V_HIP_DIST_SDF_F32)
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument or unknown format");
+    if (!dims[0] || !dims[1] || !dims[2]) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "zero dims");
     uint64_t d2max = 0;
     for (int a = 0; a < 3; ++a) d2max += (uint64_t) (dims[a] - 1u) * (dims[a] - 1u);
-    if (d2max > 0x7ffffffeull) {
-        ctx->err = "o2v_hip_distance_dense: (nx-1)^2 + (ny-1)^2 + (nz-1)^2 = " + std::to_string(d2max) + " does not fit below 2^31 - 1";
-        return O2V_HIP_ERR_LIMIT;
-    }
-    const unsigned __int128 lbytes = box_bytes(dims, label_strides, 1u), dbytes = box_bytes(dims, dst_strides, 4u);
-    if (lbytes > (unsigned __int128) (~0ull >> 1) || dbytes > (unsigned __int128) (~0ull >> 1)) {
-        ctx->err = "o2v_hip_distance_dense: the box and strides reach past any allocation";
-        return O2V_HIP_ERR_BAD_ARGUMENT;
-    }
-    if (!dist_dst_is_distinct(dims, dst_strides)) {
-        ctx->err = "o2v_hip_distance_dense: dst_strides map two voxels of the box to one element";
-        return O2V_HIP_ERR_BAD_ARGUMENT;
-    }
-    const uintptr_t lp = (uintptr_t) labels, dp = (uintptr_t) dst;
-    if (lp < dp + (uint64_t) dbytes && dp < lp + (uint64_t) lbytes) {
-        ctx->err = "o2v_hip_distance_dense: labels and dst overlap";
-        return O2V_HIP_ERR_BAD_ARGUMENT;
-    }
+    if (d2max > 0x7ffffffeull)
+        return refuse(ctx, O2V_HIP_ERR_LIMIT, fn,
+                      "(nx-1)^2 + (ny-1)^2 + (nz-1)^2 = " + std::to_string(d2max) + " does not fit below 2^31 - 1");
     O2V_CHECK(hipSetDevice(ctx->device));
+    uint64_t lbytes = 0, dbytes = 0;
     int rc;
-    if ((rc = check_device_range(ctx, labels, (uint64_t) lbytes, "labels")) || (rc = check_device_range(ctx, dst, (uint64_t) dbytes, "dst")))
+    if ((rc = check_grid(ctx, fn, "labels", labels, dims, label_strides, 1u, false, &lbytes)) ||
+        (rc = check_grid(ctx, fn, "dst", dst, dims, dst_strides, 4u, true, &dbytes)))
         return rc;
-    if (const uint64_t want = o2v_hip_distance_scratch_bytes(dims, format) / sizeof(uint2); want > ctx->d_dist_stack.cap) {
-        if (const hipError_t e = ctx->d_dist_stack.alloc(want); e != hipSuccess) {
-            (void) hipGetLastError();
-            ctx->err = std::string("o2v_hip_distance_dense: scratch of ") + std::to_string(want * sizeof(uint2)) + " bytes: " + hipGetErrorString(e);
-            return e == hipErrorOutOfMemory ? O2V_HIP_ERR_OUT_OF_MEMORY : O2V_HIP_ERR_HIP;
-        }
-    }
-    for (hipEvent_t &e : ctx->ev_dist)
-        if (!e) O2V_CHECK(create_timing_event(&e));
+    if (ranges_overlap(labels, lbytes, dst, dbytes)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "labels and dst overlap");
+    if ((rc = grow_scratch(ctx, ctx->d_dist_stack, o2v_hip_distance_scratch_bytes(dims, format) / sizeof(uint2), fn, "scratch")))
+        return rc;
     hipStream_t s = ctx->stream;
     const DistGrid g{label_strides[0], label_strides[1], label_strides[2], dst_strides[0], dst_strides[1], dst_strides[2],
                      dims[0], dims[1], dims[2]};
@@ -2547,28 +2552,26 @@ int o2v_hip_distance_dense(o2v_hip_ctx *ctx, const void *labels, const uint64_t 
     const uint64_t sy = dist_slots((uint64_t) dims[0] * dims[2]), sz = dist_slots((uint64_t) dims[0] * dims[1]);
     const uint32_t gy = (uint32_t) ((sy + kBlock - 1) / kBlock), gz = (uint32_t) ((sz + kBlock - 1) / kBlock);
     const uint64_t rows = (uint64_t) dims[1] * dims[2];
-    O2V_CHECK(hipEventRecord(ctx->ev_dist[0], s));
+    O2V_CHECK(ctx->dist_times.mark(0, s));
     hipLaunchKernelGGL(k_dist_x, dim3((uint32_t) std::min<uint64_t>((uint64_t) ctx->num_cus * 8u, (rows + 3u) / 4u)), dim3(kBlock), 0, s,
                        lab, out, g);
-    O2V_CHECK(hipEventRecord(ctx->ev_dist[1], s));
+    O2V_CHECK(ctx->dist_times.mark(1, s));
     hipLaunchKernelGGL(k_dist_envelope<kDistY>, dim3(gy), dim3(kBlock), 0, s, out, lab, g, stack, sy);
-    O2V_CHECK(hipEventRecord(ctx->ev_dist[2], s));
+    O2V_CHECK(ctx->dist_times.mark(2, s));
     if (format == O2V_HIP_DIST_SQ_I32)
         hipLaunchKernelGGL(k_dist_envelope<kDistZ>, dim3(gz), dim3(kBlock), 0, s, out, lab, g, stack, sz);
     else
         hipLaunchKernelGGL(k_dist_envelope<kDistZSdf>, dim3(gz), dim3(kBlock), 0, s, out, lab, g, stack, sz);
     O2V_CHECK(hipGetLastError());
-    O2V_CHECK(hipEventRecord(ctx->ev_dist[3], s));
+    O2V_CHECK(ctx->dist_times.mark(3, s));
     O2V_CHECK(hipStreamSynchronize(s));
-    for (int i = 0; i < 3; ++i) O2V_CHECK(hipEventElapsedTime(&ctx->dist_ms[i], ctx->ev_dist[i], ctx->ev_dist[i + 1]));
+    O2V_CHECK(ctx->dist_times.finish());
     return O2V_HIP_OK;
 }
 
 int o2v_hip_distance_times(const o2v_hip_ctx *ctx, float out_ms[3])
 {
-    if (!ctx || !out_ms) return O2V_HIP_ERR_BAD_ARGUMENT;
-    for (int i = 0; i < 3; ++i) out_ms[i] = ctx->dist_ms[i];
-    return O2V_HIP_OK;
+    return ctx ? ctx->dist_times.read(out_ms) : O2V_HIP_ERR_BAD_ARGUMENT;
 }
 
 }  // extern "C"
@@ -2580,26 +2583,6 @@ namespace {
 constexpr uint32_t kMdMaxDim = 65535;       // voxels per axis of one box (O2V_HIP_ERR_LIMIT above)
 constexpr uint64_t kMdMaxGrid = 1ull << 24; // workgroups of k_meshdist_tiles; more tiles are taken in turns
 
-// Room for n elements; a failed allocation leaves the array empty, the runtime's error state clear and the context usable.
-template <typename T, bool P>
-int md_grow(o2v_hip_ctx *ctx, DevArray<T, P> &a, uint64_t n, const char *what)
-{
-    n = std::max<uint64_t>(n, 1);
-    if (a.ptr && n <= a.cap) return O2V_HIP_OK;
-    if (const hipError_t e = a.alloc(n); e != hipSuccess) {
-        (void) hipGetLastError();
-        ctx->err = std::string("o2v_hip_mesh_distance_dense: ") + what + " of " + std::to_string(n * sizeof(T)) + " bytes: " + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? O2V_HIP_ERR_OUT_OF_MEMORY : O2V_HIP_ERR_HIP;
-    }
-    return O2V_HIP_OK;
-}
-
-int md_refuse(o2v_hip_ctx *ctx, int rc, const std::string &why)
-{
-    ctx->err = "o2v_hip_mesh_distance_dense: " + why;
-    return rc;
-}
-
 }  // namespace
 
 extern "C" {
@@ -2608,34 +2591,30 @@ int o2v_hip_mesh_distance_dense(o2v_hip_ctx *ctx, const o2v_hip_params *params, 
                                 const uint32_t origin[3], const uint32_t dims[3], float *dst, const uint64_t dst_strides[3],
                                 int32_t *closest, const uint64_t closest_strides[3])
 {
+    static const char fn[] = "o2v_hip_mesh_distance_dense";
     if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
     if (!params || !origin || !dims || !dst || !dst_strides || (closest && !closest_strides) || format > O2V_HIP_MESH_DIST_SIGNED_F32)
-        return md_refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, "null argument or unknown format");
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument or unknown format");
     if (!(std::isfinite(band) && band > 0.f && band <= 32.f))
-        return md_refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, "band must be finite, above 0 and at most 32 voxels");
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "band must be finite, above 0 and at most 32 voxels");
     const uint32_t ss = params->supersampling ? params->supersampling : 1u;
     if (ss > 2u || params->resolution == 0u)
-        return md_refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, "resolution must be positive and supersampling 1 or 2");
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "resolution must be positive and supersampling 1 or 2");
     if (params->z_begin || params->z_end || params->x_begin || params->x_end || params->y_begin || params->y_end)
-        return md_refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, "the slab and tile fields of params must be 0 (the box is origin, dims)");
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "the slab and tile fields of params must be 0 (the box is origin, dims)");
     for (int a = 0; a < 3; ++a) {
         if (!dims[a] || (uint64_t) origin[a] + dims[a] > params->resolution)
-            return md_refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, "the box must have dims >= 1 and lie within the grid");
-        if (dims[a] > kMdMaxDim) return md_refuse(ctx, O2V_HIP_ERR_LIMIT, "a box of more than 65 535 voxels along an axis");
+            return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "the box must have dims >= 1 and lie within the grid");
+        if (dims[a] > kMdMaxDim) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "a box of more than 65 535 voxels along an axis");
     }
-    const unsigned __int128 dbytes = box_bytes(dims, dst_strides, 4u), cbytes = closest ? box_bytes(dims, closest_strides, 4u) : 0u;
-    if (dbytes > (unsigned __int128) (~0ull >> 1) || cbytes > (unsigned __int128) (~0ull >> 1))
-        return md_refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, "the box and strides reach past any allocation");
-    if (!dist_dst_is_distinct(dims, dst_strides) || (closest && !dist_dst_is_distinct(dims, closest_strides)))
-        return md_refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, "strides map two voxels of the box to one element");
-    const uintptr_t dp = (uintptr_t) dst, cp = (uintptr_t) closest;
-    if (closest && cp < dp + (uint64_t) dbytes && dp < cp + (uint64_t) cbytes)
-        return md_refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, "dst and closest overlap");
     O2V_CHECK(hipSetDevice(ctx->device));
     ctx->ktimes_on = false;   // (no per-launch brackets here; o2v_hip_voxelize sets the flag again from its params)
+    uint64_t dbytes = 0, cbytes = 0;
     int rc;
-    if ((rc = check_device_range(ctx, dst, (uint64_t) dbytes, "dst")) || (closest && (rc = check_device_range(ctx, closest, (uint64_t) cbytes, "closest"))))
+    if ((rc = check_grid(ctx, fn, "dst", dst, dims, dst_strides, 4u, true, &dbytes)) ||
+        (closest && (rc = check_grid(ctx, fn, "closest", closest, dims, closest_strides, 4u, true, &cbytes))))
         return rc;
+    if (closest && ranges_overlap(dst, dbytes, closest, cbytes)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "dst and closest overlap");
 
     const uint64_t T = ctx->n_tris;
     MdBox b{};
@@ -2661,17 +2640,16 @@ int o2v_hip_mesh_distance_dense(o2v_hip_ctx *ctx, const o2v_hip_params *params, 
         xf = compute_mesh_transform(V3{e[0], e[1], e[2]}, V3{e[3], e[4], e[5]}, params->resolution * ss, params->unit_transform);
     }
     const uint64_t tile_blocks = (b.n_tiles + kBlock - 1) / kBlock;
-    if ((rc = md_grow(ctx, ctx->d_md_sv, T * 9u, "vertices")) || (rc = md_grow(ctx, ctx->d_md_counts, b.n_tiles, "tile counters")) ||
-        (rc = md_grow(ctx, ctx->d_md_first, b.n_tiles + 1u, "tile offsets")) || (rc = md_grow(ctx, ctx->d_md_blocks, tile_blocks, "block sums")) ||
-        (rc = md_grow(ctx, ctx->d_md_ctr, 1u, "counter")) || (rc = md_grow(ctx, ctx->h_md_ctr, 1u, "counter")))
+    if ((rc = grow_scratch(ctx, ctx->d_md_sv, T * 9u, fn, "vertices")) || (rc = grow_scratch(ctx, ctx->d_md_counts, b.n_tiles, fn, "tile counters")) ||
+        (rc = grow_scratch(ctx, ctx->d_md_first, b.n_tiles + 1u, fn, "tile offsets")) ||
+        (rc = grow_scratch(ctx, ctx->d_md_blocks, tile_blocks, fn, "block sums")) || (rc = grow_scratch(ctx, ctx->d_md_ctr, 1u, fn, "counter")) ||
+        (rc = grow_scratch(ctx, ctx->h_md_ctr, 1u, fn, "counter")))
         return rc;
-    for (hipEvent_t &e : ctx->ev_md)
-        if (!e) O2V_CHECK(create_timing_event(&e));
     hipStream_t s = ctx->stream;
     const uint64_t tri_blocks = (T + kBlock - 1) / kBlock;
 
     // binning: (triangle, tile) pairs counted, scanned, scattered into per-tile lists
-    O2V_CHECK(hipEventRecord(ctx->ev_md[0], s));
+    O2V_CHECK(ctx->md_times.mark(0, s));
     O2V_CHECK(hipMemsetAsync(ctx->d_md_counts.ptr, 0, b.n_tiles * sizeof(uint32_t), s));
     if (T)
         O2V_LAUNCH("k_meshdist_bin_count", s, k_meshdist_bin_count, dim3((uint32_t) tri_blocks), dim3(kBlock), 0, s, ctx->d_verts.ptr, T, xf, b,
@@ -2684,50 +2662,37 @@ int o2v_hip_mesh_distance_dense(o2v_hip_ctx *ctx, const o2v_hip_params *params, 
     O2V_CHECK(hipMemcpyAsync(ctx->h_md_ctr.ptr, ctx->d_md_ctr.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     O2V_CHECK(hipStreamSynchronize(s));
     const uint64_t n_pairs = ctx->h_md_ctr.ptr[0];
-    if ((rc = md_grow(ctx, ctx->d_md_lists, n_pairs, "triangle lists"))) return rc;
+    if ((rc = grow_scratch(ctx, ctx->d_md_lists, n_pairs, fn, "triangle lists"))) return rc;
     if (n_pairs)
         O2V_LAUNCH("k_meshdist_bin_scatter", s, k_meshdist_bin_scatter, dim3((uint32_t) tri_blocks), dim3(kBlock), 0, s, ctx->d_md_sv.ptr, T, b,
                    ctx->d_md_first.ptr, ctx->d_md_counts.ptr, ctx->d_md_lists.ptr);
-    O2V_CHECK(hipEventRecord(ctx->ev_md[1], s));
+    O2V_CHECK(ctx->md_times.mark(1, s));
 
     // parity (signed): K6's bitmap of the box, no unmark step
     const uint32_t *bits = nullptr;
     if (format == O2V_HIP_MESH_DIST_SIGNED_F32 && T) {
-        FillBox fb{};
-        fb.x0 = b.x0;
-        fb.y0 = b.y0;
-        fb.z0 = b.z0;
-        fb.nx = b.nx;
-        fb.ny = b.ny;
-        fb.nz = b.nz;
-        fb.nzw = (fb.nz + 31u) / 32u;
-        fb.ss = ss;
-        fb.n_cols = (uint64_t) fb.nx * fb.ny;
-        fb.n_words = (uint64_t) fb.nzw * fb.n_cols;
-        if ((rc = parity_bits(ctx, xf, fb))) {
+        if ((rc = parity_bits(ctx, xf, fill_box(origin, dims, ss, 0u)))) {
             (void) hipGetLastError();
             return rc;
         }
         bits = ctx->d_fill_bits.ptr;
     }
-    O2V_CHECK(hipEventRecord(ctx->ev_md[2], s));
+    O2V_CHECK(ctx->md_times.mark(2, s));
 
     // distance: one workgroup per tile
     O2V_LAUNCH("k_meshdist_tiles", s, k_meshdist_tiles, dim3((uint32_t) std::min<uint64_t>(b.n_tiles, kMdMaxGrid)), dim3(kBlock), 0, s,
                ctx->d_md_sv.ptr, b, ctx->d_md_first.ptr, ctx->d_md_lists.ptr, bits, dst, dst_strides[0], dst_strides[1], dst_strides[2],
                closest, closest ? closest_strides[0] : 0u, closest ? closest_strides[1] : 0u, closest ? closest_strides[2] : 0u);
     O2V_CHECK(hipGetLastError());
-    O2V_CHECK(hipEventRecord(ctx->ev_md[3], s));
+    O2V_CHECK(ctx->md_times.mark(3, s));
     O2V_CHECK(hipStreamSynchronize(s));
-    for (int i = 0; i < 3; ++i) O2V_CHECK(hipEventElapsedTime(&ctx->md_ms[i], ctx->ev_md[i], ctx->ev_md[i + 1]));
+    O2V_CHECK(ctx->md_times.finish());
     return O2V_HIP_OK;
 }
 
 int o2v_hip_mesh_distance_times(const o2v_hip_ctx *ctx, float out_ms[3])
 {
-    if (!ctx || !out_ms) return O2V_HIP_ERR_BAD_ARGUMENT;
-    for (int i = 0; i < 3; ++i) out_ms[i] = ctx->md_ms[i];
-    return O2V_HIP_OK;
+    return ctx ? ctx->md_times.read(out_ms) : O2V_HIP_ERR_BAD_ARGUMENT;
 }
 
 namespace {

@@ -63,8 +63,33 @@ def _check(t, name, dtypes, shape, device):
     return t.contiguous()
 
 
+def _check_grid(t, name, dtype, device, shape=None):
+    """A caller's 3-D tensor [z, y, x] of any strides (shape: the one it must have), checked as it is: it is written in place,
+    never made contiguous."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 3:
+        raise ValueError(f"{name} must be a 3-D tensor [z, y, x]")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must have the shape {tuple(shape)}, not {tuple(t.shape)}")
+    if t.dtype != dtype:
+        raise TypeError(f"{name} must be {dtype}, not {t.dtype}")
+    if t.device != device:
+        raise ValueError(f"{name} is on {t.device}, the voxelizer on {device}")
+
+
+def _check_sampling(resolution, supersampling, max_layers):
+    if resolution < 1 or supersampling not in (1, 2):
+        raise ValueError("resolution must be positive and supersampling 1 or 2")
+    if max_layers is not None and max_layers < 1:
+        raise ValueError("max_layers must be positive")
+
+
 def _ptr(t):
     return None if t is None else t.data_ptr()
+
+
+def _strides(t):
+    """(x, y, z): the element strides of a 3-D tensor indexed [z, y, x]."""
+    return t.stride(2), t.stride(1), t.stride(0)
 
 
 def set_mesh(dv, positions, faces=None, *, uvs=None, types=None, colors=None, texids=None):
@@ -98,7 +123,7 @@ def _layout(t, fmt):
     """(write_dense strides x, y, z) of a 3-D tensor indexed [z, y, x]: elements, or 32-bit words for bits."""
     if fmt == "bits" and t.stride(2) != 1:
         raise ValueError("a bits grid needs unit stride along x (its last dimension)")
-    return t.stride(2), t.stride(1), t.stride(0)
+    return _strides(t)
 
 
 def voxelize_dense(dv, resolution, *, fmt="occupancy", box="grid", out=None, origin=None, supersampling=1, strategy="max",
@@ -123,12 +148,7 @@ def voxelize_dense(dv, resolution, *, fmt="occupancy", box="grid", out=None, ori
         dtype = DISTANCE_FORMATS[fmt][1]
         device = _device(dv)
         if out is not None:
-            if not isinstance(out, torch.Tensor) or out.dim() != 3:
-                raise ValueError("out must be a 3-D tensor [z, y, x]")
-            if out.dtype != dtype:
-                raise TypeError(f"out must be {dtype} for fmt={fmt!r}, not {out.dtype}")
-            if out.device != device:
-                raise ValueError(f"out is on {out.device}, the voxelizer on {device}")
+            _check_grid(out, "out", dtype, device)
         labels, origin = voxelize_dense(
             dv, resolution, fmt="labels", box=box, origin=origin, supersampling=supersampling, strategy=strategy, fill=fill,
             fill_argb=fill_argb, unit_transform=unit_transform, bounds=bounds, max_layers=max_layers,
@@ -144,24 +164,16 @@ def voxelize_dense(dv, resolution, *, fmt="occupancy", box="grid", out=None, ori
         raise ValueError(f"box must be 'grid' or 'tight', not {box!r}")
     if strategy not in STRATEGIES:
         raise ValueError(f"strategy must be 'max' or 'blend', not {strategy!r}")
-    if resolution < 1 or supersampling not in (1, 2):
-        raise ValueError("resolution must be positive and supersampling 1 or 2")
+    _check_sampling(resolution, supersampling, max_layers)
     if resolution * supersampling > MAX_SAMPLES:
         raise ValueError(f"resolution x supersampling = {resolution * supersampling} is above {MAX_SAMPLES}: x / y tiles are not "
                          "supported by the dense path")
     if box == "tight" and origin is not None:
         raise ValueError("origin is given by the voxels with box='tight'")
-    if max_layers is not None and max_layers < 1:
-        raise ValueError("max_layers must be positive")
     code, dtype = FORMATS[fmt]
     device = _device(dv)
     if out is not None:
-        if not isinstance(out, torch.Tensor) or out.dim() != 3:
-            raise ValueError("out must be a 3-D tensor [z, y, x]")
-        if out.dtype != dtype:
-            raise TypeError(f"out must be {dtype} for fmt={fmt!r}, not {out.dtype}")
-        if out.device != device:
-            raise ValueError(f"out is on {out.device}, the voxelizer on {device}")
+        _check_grid(out, "out", dtype, device)
         _layout(out, fmt)
     kw = dict(supersampling=supersampling, strategy=STRATEGIES[strategy], unit_transform=unit_transform, fill=fill)
 
@@ -237,27 +249,16 @@ def distance_transform(dv, labels, fmt="sdf", *, out=None):
         raise ValueError(f"fmt must be one of {sorted(DISTANCE_FORMATS)}, not {fmt!r}")
     code, dtype = DISTANCE_FORMATS[fmt]
     device = _device(dv)
-    if not isinstance(labels, torch.Tensor) or labels.dim() != 3:
-        raise ValueError("labels must be a 3-D tensor [z, y, x]")
-    if labels.dtype != torch.uint8:
-        raise TypeError(f"labels must be torch.uint8, not {labels.dtype}")
-    if labels.device != device:
-        raise ValueError(f"labels is on {labels.device}, the voxelizer on {device}")
+    _check_grid(labels, "labels", torch.uint8, device)
     if 0 in labels.shape:
         raise ValueError("labels has an empty dimension")
     if out is None:
         out = torch.empty(tuple(labels.shape), dtype=dtype, device=device)
     else:
-        if not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(labels.shape):
-            raise ValueError(f"out must be a tensor of the labels' shape {tuple(labels.shape)}")
-        if out.dtype != dtype:
-            raise TypeError(f"out must be {dtype} for fmt={fmt!r}, not {out.dtype}")
-        if out.device != device:
-            raise ValueError(f"out is on {out.device}, the voxelizer on {device}")
+        _check_grid(out, "out", dtype, device, labels.shape)
     nz, ny, nx = labels.shape
     _sync(device)   # (the caller's writes to labels and out have landed)
-    dv.distance_dense(labels.data_ptr(), (labels.stride(2), labels.stride(1), labels.stride(0)), out.data_ptr(), code,
-                      (out.stride(2), out.stride(1), out.stride(0)), (nx, ny, nz))
+    dv.distance_dense(labels.data_ptr(), _strides(labels), out.data_ptr(), code, _strides(out), (nx, ny, nz))
     return out
 
 
@@ -278,10 +279,7 @@ def mesh_distance(dv, resolution, *, band, signed=True, out=None, closest=None, 
     _require_shared_runtime()
     if isinstance(band, bool) or not isinstance(band, numbers.Real) or not (0.0 < float(band) <= MAX_BAND):
         raise ValueError(f"band must be a number with 0 < band <= {MAX_BAND:g} voxels, not {band!r}")
-    if resolution < 1 or supersampling not in (1, 2):
-        raise ValueError("resolution must be positive and supersampling 1 or 2")
-    if max_layers is not None and max_layers < 1:
-        raise ValueError("max_layers must be positive")
+    _check_sampling(resolution, supersampling, max_layers)
     device = _device(dv)
     origin = tuple(int(v) for v in (origin or (0, 0, 0)))
     if len(origin) != 3 or any(v < 0 or v >= resolution for v in origin):
@@ -289,12 +287,7 @@ def mesh_distance(dv, resolution, *, band, signed=True, out=None, closest=None, 
     if out is None:
         out = torch.empty(tuple(resolution - v for v in origin[::-1]), dtype=torch.float32, device=device)
     else:
-        if not isinstance(out, torch.Tensor) or out.dim() != 3:
-            raise ValueError("out must be a 3-D tensor [z, y, x]")
-        if out.dtype != torch.float32:
-            raise TypeError(f"out must be torch.float32, not {out.dtype}")
-        if out.device != device:
-            raise ValueError(f"out is on {out.device}, the voxelizer on {device}")
+        _check_grid(out, "out", torch.float32, device)
         if 0 in out.shape:
             raise ValueError("out has an empty dimension")
         if any(o + n > resolution for o, n in zip(origin, out.shape[::-1])):
@@ -303,12 +296,7 @@ def mesh_distance(dv, resolution, *, band, signed=True, out=None, closest=None, 
     if closest is True:
         closest = torch.empty(tuple(out.shape), dtype=torch.int32, device=device)
     elif closest is not None:
-        if not isinstance(closest, torch.Tensor) or tuple(closest.shape) != tuple(out.shape):
-            raise ValueError(f"closest must be True or a tensor of the box's shape {tuple(out.shape)}")
-        if closest.dtype != torch.int32:
-            raise TypeError(f"closest must be torch.int32, not {closest.dtype}")
-        if closest.device != device:
-            raise ValueError(f"closest is on {closest.device}, the voxelizer on {device}")
+        _check_grid(closest, "closest", torch.int32, device, out.shape)
         if closest.untyped_storage().data_ptr() == out.untyped_storage().data_ptr():
             raise ValueError("closest must not share out's storage")
     fmt = hip.MESH_DIST_SIGNED_F32 if signed else hip.MESH_DIST_UNSIGNED_F32
@@ -320,6 +308,6 @@ def mesh_distance(dv, resolution, *, band, signed=True, out=None, closest=None, 
         o = out[z:z + k]
         c = None if closest is None else closest[z:z + k]
         dv.mesh_distance_dense(resolution, float(band), fmt, (origin[0], origin[1], origin[2] + z), (nx, ny, k), o.data_ptr(),
-                               (o.stride(2), o.stride(1), o.stride(0)), _ptr(c), None if c is None else (c.stride(2), c.stride(1), c.stride(0)),
-                               supersampling=supersampling, unit_transform=unit_transform, bounds=bounds)
+                               _strides(o), _ptr(c), None if c is None else _strides(c), supersampling=supersampling,
+                               unit_transform=unit_transform, bounds=bounds)
     return (out, closest, origin) if want_closest else (out, origin)

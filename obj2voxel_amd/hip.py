@@ -176,6 +176,14 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _u32x3(v):
+    return (C.c_uint32 * 3)(*[int(x) for x in v])
+
+
+def _u64x3(v):
+    return None if v is None else (C.c_uint64 * 3)(*[int(x) for x in v])
+
+
 class DeviceVoxelizer:
     """Owns one GPU's dense grid slab and work buffers; reusable across voxelize() calls."""
 
@@ -235,10 +243,7 @@ class DeviceVoxelizer:
     def write_dense(self, ptr, fmt, origin, dims, strides):
         """o2v_hip_write_dense: the last voxelize call's records into the dense grid at device address `ptr` (DENSE_U8 /
         DENSE_ARGB32 / DENSE_BITS; origin, dims, strides per axis x, y, z).  Returns the number of records outside the box."""
-        o = (C.c_uint32 * 3)(*[int(v) for v in origin])
-        d = (C.c_uint32 * 3)(*[int(v) for v in dims])
-        s = (C.c_uint64 * 3)(*[int(v) for v in strides])
-        outside = C.c_uint64(0)
+        o, d, s, outside = _u32x3(origin), _u32x3(dims), _u64x3(strides), C.c_uint64(0)
         self._check(self._L.o2v_hip_write_dense(self._ctx, ptr, fmt, o, d, s, C.byref(outside)), "o2v_hip_write_dense")
         return outside.value
 
@@ -251,20 +256,21 @@ class DeviceVoxelizer:
     def distance_dense(self, labels_ptr, label_strides, dst_ptr, fmt, dst_strides, dims):
         """o2v_hip_distance_dense: the squared distance (DIST_SQ_I32) or SDF (DIST_SDF_F32) of the uint8 label grid at device
         address labels_ptr into dst_ptr; strides in elements and dims per axis x, y, z."""
-        ls = (C.c_uint64 * 3)(*[int(v) for v in label_strides])
-        ds = (C.c_uint64 * 3)(*[int(v) for v in dst_strides])
-        d = (C.c_uint32 * 3)(*[int(v) for v in dims])
+        ls, ds, d = _u64x3(label_strides), _u64x3(dst_strides), _u32x3(dims)
         self._check(self._L.o2v_hip_distance_dense(self._ctx, labels_ptr, ls, dst_ptr, fmt, ds, d), "o2v_hip_distance_dense")
 
     def distance_scratch_bytes(self, dims, fmt):
         """o2v_hip_distance_scratch_bytes: the context scratch a distance_dense call over dims (x, y, z) needs."""
-        return int(self._L.o2v_hip_distance_scratch_bytes((C.c_uint32 * 3)(*[int(v) for v in dims]), fmt))
+        return int(self._L.o2v_hip_distance_scratch_bytes(_u32x3(dims), fmt))
+
+    def _stage_times(self, name):   # (o2v_hip_distance_times, o2v_hip_mesh_distance_times)
+        ms = (C.c_float * 3)()
+        self._check(getattr(self._L, name)(self._ctx, ms), name)
+        return tuple(float(v) for v in ms)
 
     def distance_times(self):
         """o2v_hip_distance_times: the device times (ms) of the last distance_dense call's x, y and z passes."""
-        ms = (C.c_float * 3)()
-        self._check(self._L.o2v_hip_distance_times(self._ctx, ms), "o2v_hip_distance_times")
-        return tuple(float(v) for v in ms)
+        return self._stage_times("o2v_hip_distance_times")
 
     def mesh_distance_dense(self, resolution, band, fmt, origin, dims, dst_ptr, dst_strides, closest_ptr=None, closest_strides=None, *,
                             supersampling=1, unit_transform=None, bounds=None):
@@ -273,19 +279,13 @@ class DeviceVoxelizer:
         address dst_ptr and, if closest_ptr is given, the closest triangle's index (int32, -1 outside the band); strides in
         elements, origin, dims and strides per axis x, y, z."""
         p = self._params(resolution, supersampling, 0, unit_transform, bounds, (0, 0))
-        o = (C.c_uint32 * 3)(*[int(v) for v in origin])
-        d = (C.c_uint32 * 3)(*[int(v) for v in dims])
-        ds = (C.c_uint64 * 3)(*[int(v) for v in dst_strides])
-        cs = None if closest_strides is None else (C.c_uint64 * 3)(*[int(v) for v in closest_strides])
-        self._check(self._L.o2v_hip_mesh_distance_dense(self._ctx, C.byref(p), float(band), fmt, o, d, dst_ptr, ds, closest_ptr, cs),
-                    "o2v_hip_mesh_distance_dense")
+        self._check(self._L.o2v_hip_mesh_distance_dense(self._ctx, C.byref(p), float(band), fmt, _u32x3(origin), _u32x3(dims), dst_ptr,
+                                                        _u64x3(dst_strides), closest_ptr, _u64x3(closest_strides)), "o2v_hip_mesh_distance_dense")
 
     def mesh_distance_times(self):
         """o2v_hip_mesh_distance_times: the device times (ms) of the last mesh_distance_dense call's binning, parity and
         distance stages (parity 0 when unsigned)."""
-        ms = (C.c_float * 3)()
-        self._check(self._L.o2v_hip_mesh_distance_times(self._ctx, ms), "o2v_hip_mesh_distance_times")
-        return tuple(float(v) for v in ms)
+        return self._stage_times("o2v_hip_mesh_distance_times")
 
     def set_textures(self, textures):
         """textures: sequence of (uint8 [h, w, c] pixels, wrap) with c in (3, 4)."""

@@ -110,31 +110,58 @@ struct DevArray {
 };
 template <typename T> using PinnedArray = DevArray<T, true>;
 
-// An event that is only ever used to read a time: without the system-scope fence a default event performs when it is recorded
-// (cache write-back and invalidation in the middle of the pass; nothing on the host reads device memory on its strength).
-// Measured: the six stage events of a pass cost 0.009 ms less this way (bench headline, O2V_HIP_FLAG_STAGE_TIMES).
-hipError_t create_timing_event(hipEvent_t *e) { return hipEventCreateWithFlags(e, hipEventDisableSystemFence); }
+// An event and a stream the context owns, like its arrays: destroyed with it, read as the HIP handle they hold, made by the
+// create calls (nothing if the handle exists).
+struct Event {
+    hipEvent_t h = nullptr;
+    Event() = default;
+    Event(Event &&o) noexcept : h(std::exchange(o.h, nullptr)) {}
+    Event &operator=(Event &&o) noexcept { return std::swap(h, o.h), *this; }
+    ~Event() { if (h) (void) hipEventDestroy(h); }
+    operator hipEvent_t() const { return h; }
+    // An event that is only ever used to read a time: without the system-scope fence a default event performs when it is
+    // recorded (cache write-back and invalidation in the middle of the pass; nothing on the host reads device memory on its
+    // strength).  Measured: the six stage events of a pass cost 0.009 ms less this way (bench headline, O2V_HIP_FLAG_STAGE_TIMES).
+    hipError_t create_timing() { return h ? hipSuccess : hipEventCreateWithFlags(&h, hipEventDisableSystemFence); }
+    // an event that only makes a stream or the host wait
+    hipError_t create_sync() { return h ? hipSuccess : hipEventCreateWithFlags(&h, hipEventDisableTiming); }
+};
+struct Stream {
+    hipStream_t h = nullptr;
+    Stream() = default;
+    Stream(Stream &&o) noexcept : h(std::exchange(o.h, nullptr)) {}
+    Stream &operator=(Stream &&o) noexcept { return std::swap(h, o.h), *this; }
+    ~Stream() { if (h) (void) hipStreamDestroy(h); }
+    operator hipStream_t() const { return h; }
+    hipError_t create() { return h ? hipSuccess : hipStreamCreateWithFlags(&h, hipStreamNonBlocking); }
+};
 
-// Events around the N stages of a call and the stages' device times (ms) of the last call that finished.  mark(i) is where
-// stage i begins (mark(N): where the last one ends); the first mark(0) creates the events.
+// Timing events around the N stages of a call and the stages' device times (ms) of the last call that finished.  mark(i) is
+// where stage i begins (mark(N): where the last one ends); the first mark(0) creates the events, unless create did.
 template <int N>
 struct StageTimes {
-    hipEvent_t ev[N + 1] = {};
+    Event ev[N + 1];
     float ms[N] = {};
 
+    hipError_t create()
+    {
+        for (Event &e : ev)
+            if (const hipError_t r = e.create_timing(); r != hipSuccess) return r;
+        return hipSuccess;
+    }
     hipError_t mark(int i, hipStream_t s)
     {
         if (i == 0)
-            for (hipEvent_t &e : ev)
-                if (!e)
-                    if (const hipError_t r = create_timing_event(&e); r != hipSuccess) return r;
+            if (const hipError_t r = create(); r != hipSuccess) return r;
         return hipEventRecord(ev[i], s);
     }
+    // the time from mark(i) to mark(j), once the stream has passed mark(j)
+    hipError_t elapsed(int i, int j, float &out_ms) const { return hipEventElapsedTime(&out_ms, ev[i], ev[j]); }
     // once the stream has passed mark(N)
     hipError_t finish()
     {
         for (int i = 0; i < N; ++i)
-            if (const hipError_t r = hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]); r != hipSuccess) return r;
+            if (const hipError_t r = elapsed(i, i + 1, ms[i]); r != hipSuccess) return r;
         return hipSuccess;
     }
     int read(float out_ms[N]) const
@@ -187,9 +214,9 @@ Switches read_switches() { return Switches{}; }
 struct o2v_hip_ctx {
     int device = 0;
     int num_cus = 256;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[6] = {};
-    hipEvent_t ev_coll[2] = {};                  // sharded planning: around the collectives
+    Stream stream;
+    StageTimes<5> pass_times;                    // the stages of a pass; made at once: k_voxelize's dispatch records events 2, 3 (O2V_LAUNCH_K2)
+    StageTimes<1> coll_times;                    // sharded planning: around a collective
     DevArray<unsigned long long> d_counts;       // per-rank voxel counts (all-gathered), world entries
     PinnedArray<unsigned long long> h_counts;
     DevArray<uint32_t> d_status;                 // sharded runs: "this rank is ready" word, max-reduced over the ranks
@@ -203,7 +230,7 @@ struct o2v_hip_ctx {
     uint64_t n_tris = 0;
     // streamed upload (o2v_hip_begin / commit / end_triangles): two page-locked staging blocks, filled in turn
     StageBlock stage[2];
-    hipEvent_t ev_stage[2] = {nullptr, nullptr};
+    Event ev_stage[2];
     int stage_cur = 0;
     uint64_t stream_count = 0;
     uint32_t stream_arrays = 0;
@@ -222,8 +249,8 @@ struct o2v_hip_ctx {
     bool skip_big = false;      // no leaf of the uploaded mesh can have more than four tiles (its largest triangle's extent): k_expand_big left out
     bool poisoned = false;      // a collective of a sharded run is stuck on the stream (time limit passed): o2v_hip_destroy must not wait for it
     bool ctr_clean = false;     // d_ctr was zeroed (k_init) behind the last pass and nothing has touched it since
-    hipStream_t aux[3] = {nullptr, nullptr, nullptr};  // the cooperative resolve tiers run beside tier 1
-    hipEvent_t ev_fork = nullptr, ev_sorted = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
+    Stream aux[3];                    // the cooperative resolve tiers run beside tier 1
+    Event ev_fork, ev_sorted, ev_join[3];
     DevArray<unsigned long long> d_zhist;        // kPlanBins, o2v_hip_plan_slabs
     PinnedArray<unsigned long long> h_zhist;
     DevArray<float2> d_zrange;                   // z extent per 256 triangles, written by the slab plan
@@ -267,7 +294,7 @@ struct o2v_hip_ctx {
     DevArray<uint8_t> d_maxgrid;        // direct MAX path: one 64-bit cell per output voxel (same bricked layout), or one byte
     DevArray<uint8_t> d_dirty_max;      // ... its dirty-brick flags and list
     DevArray<uint32_t> d_dirty_list_max;
-    hipEvent_t ev_k1 = nullptr;         // after K1: its counters decide which stages follow k_voxelize
+    Event ev_k1;                        // after K1: its counters decide which stages follow k_voxelize
     // solid fill (O2V_HIP_FLAG_FILL_INTERIOR, K6): allocated by the first call that asks for it
     DevArray<uint32_t> d_fill_bits;              // toggle bitmap of the pass box, [z-word][y][x]
     DevArray<unsigned long long> d_fill_ends;    // per triangle: inclusive end of its (triangle, column) items
@@ -275,7 +302,7 @@ struct o2v_hip_ctx {
     DevArray<unsigned long long> d_fill_chunks;  // per chunk of kFillChunk bitmap words: its records' offset
     DevArray<unsigned long long> d_fill_ctr;     // [0] items, [1] interior voxels, [2] the mesh's top (f2ord of its largest z)
     PinnedArray<unsigned long long> h_fill_ctr;
-    hipEvent_t ev_fill[2] = {nullptr, nullptr};  // around the stage (O2V_HIP_FLAG_STAGE_TIMES)
+    StageTimes<1> fill_times;                    // of the stage (O2V_HIP_FLAG_STAGE_TIMES)
     bool maxgrid_dirty = false;
     bool grid_dirty = false;
     // K7 (o2v_hip_set_triangles_device, o2v_hip_write_dense, o2v_hip_voxels_box): flags and sums, allocated on first use
@@ -305,7 +332,7 @@ struct o2v_hip_ctx {
     // O2V_HIP_FLAG_KERNEL_TIMES: an event pair around every launch of a pass
     struct KernelBracket {
         const char *name = nullptr;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
+        StageTimes<1> times;
     };
     std::vector<KernelBracket> ktimes;
     size_t ktimes_used = 0;
@@ -394,7 +421,7 @@ bool debug_sync_enabled() { return debug_sync_level() != 0; }
     do {                                                                         \
         const int kt_ = ktime_begin(ctx, name, stream);                          \
         hipLaunchKernelGGL(__VA_ARGS__);                                         \
-        if (kt_ >= 0) (void) hipEventRecord(ctx->ktimes[(size_t) kt_].e1, stream); \
+        if (kt_ >= 0) (void) ctx->ktimes[(size_t) kt_].times.mark(1, stream);   \
         O2V_STAGE(name);                                                         \
     } while (0)
 
@@ -406,7 +433,8 @@ bool debug_sync_enabled() { return debug_sync_level() != 0; }
     do {                                                                                                            \
         if (ctx->stage_events || ctx->ktimes_on) O2V_LAUNCH(name, s, kernel, grid, block, 0, s, __VA_ARGS__);       \
         else {                                                                                                      \
-            hipExtLaunchKernelGGL(kernel, grid, block, 0, s, ctx->ev[2], ctx->ev[3], 0, __VA_ARGS__);               \
+            hipExtLaunchKernelGGL(kernel, grid, block, 0, s, ctx->pass_times.ev[2], ctx->pass_times.ev[3], 0,           \
+                                  __VA_ARGS__);                                                                     \
             O2V_STAGE(name);                                                                                        \
         }                                                                                                           \
     } while (0)
@@ -414,14 +442,10 @@ bool debug_sync_enabled() { return debug_sync_level() != 0; }
 int ktime_begin(o2v_hip_ctx *ctx, const char *name, hipStream_t stream)
 {
     if (!ctx->ktimes_on) return -1;
-    if (ctx->ktimes_used == ctx->ktimes.size()) {
-        o2v_hip_ctx::KernelBracket b{};
-        if (create_timing_event(&b.e0) != hipSuccess || create_timing_event(&b.e1) != hipSuccess) return -1;
-        ctx->ktimes.push_back(b);
-    }
+    if (ctx->ktimes_used == ctx->ktimes.size()) ctx->ktimes.emplace_back();
     o2v_hip_ctx::KernelBracket &b = ctx->ktimes[ctx->ktimes_used];
     b.name = name;
-    if (hipEventRecord(b.e0, stream) != hipSuccess) return -1;
+    if (b.times.mark(0, stream) != hipSuccess) return -1;
     return (int) ctx->ktimes_used++;
 }
 
@@ -565,7 +589,7 @@ int launch_expand(o2v_hip_ctx *ctx, const Params &p, const Switches &sw, uint32_
     hipStream_t s = ctx->stream;
     Counters *const ctr = ctx->d_ctr.ptr;
     const uint32_t persistent = (uint32_t) ctx->num_cus * 8u;
-    if (ctx->stage_events) O2V_CHECK(hipEventRecord(ctx->ev[0], s));
+    if (ctx->stage_events) O2V_CHECK(ctx->pass_times.mark(0, s));
     // (the counters were zeroed behind the previous pass, off its critical path, unless something else used them since)
     if (!ctx->ctr_clean) O2V_LAUNCH("k_init", s, k_init, dim3(1), dim3(64), 0, s, ctr, kPassCounterWords);
     ctx->ctr_clean = false;
@@ -577,7 +601,7 @@ int launch_expand(o2v_hip_ctx *ctx, const Params &p, const Switches &sw, uint32_
     }
     // (letting the last workgroup of k_bounds compute the transform - one launch less - was measured: the stage 0.021 -> 0.027 ms)
     O2V_LAUNCH("k_setup", s, k_setup, dim3(1), dim3(64), 0, s, ctr, p);
-    if (ctx->stage_events) O2V_CHECK(hipEventRecord(ctx->ev[1], s));
+    if (ctx->stage_events) O2V_CHECK(ctx->pass_times.mark(1, s));
 
     // After a slab plan the z extent of every block of 256 triangles is known: a slab that is not the whole grid visits only
     // the blocks that meet it (on N GPUs ~1/N of the list, compacted by k_list_blocks).
@@ -672,8 +696,7 @@ int launch_resolve(o2v_hip_ctx *ctx, const Params &p, bool use_uv, uint32_t reso
     const bool fork = debug_sync_level() != 1;
     hipStream_t sw = s, sm = s, sl = s;
     if (fork) {
-        for (int j = 0; j < 3; ++j)
-            if (!ctx->aux[j]) O2V_CHECK(hipStreamCreateWithFlags(&ctx->aux[j], hipStreamNonBlocking));
+        for (Stream &q : ctx->aux) O2V_CHECK(q.create());
         sw = ctx->aux[0];
         sm = ctx->aux[1];
         sl = ctx->aux[2];
@@ -733,7 +756,7 @@ int collect_kernel_times(o2v_hip_ctx *ctx)
     for (size_t i = 0; i < ctx->ktimes_used; ++i) {
         const o2v_hip_ctx::KernelBracket &b = ctx->ktimes[i];
         float ms = 0.f;
-        O2V_CHECK(hipEventElapsedTime(&ms, b.e0, b.e1));
+        O2V_CHECK(b.times.elapsed(0, 1, ms));
         auto it = std::find_if(ctx->kernel_times.begin(), ctx->kernel_times.end(),
                                [&](const o2v_hip_kernel_time &k) { return std::strcmp(k.name, b.name) == 0; });
         if (it == ctx->kernel_times.end()) {
@@ -789,19 +812,19 @@ int run_pass(o2v_hip_ctx *ctx, const Params &p, const Switches &sw, bool use_uv,
         O2V_LAUNCH("k_scan_flags", s, k_scan_flags, dim3(std::min<uint32_t>((uint32_t) ctx->num_cus * kScanFlagsWgsPerCu, std::max<uint32_t>(1u, (flag_groups + kBlock * kFlagLoads - 1) / (kBlock * kFlagLoads)))),
                            dim3(kBlock), 0, s, ctx->d_brick_dirty.ptr, &ctr->n_dirty, ctx->d_dirty_list.ptr, ctr, ctx->d_brick_slab.ptr, ctx->force_general ? 1u : 0u, p);
     }
-    if (ctx->stage_events) O2V_CHECK(hipEventRecord(ctx->ev[2], s));
+    if (ctx->stage_events) O2V_CHECK(ctx->pass_times.mark(2, s));
     // (occupancy only: every hit takes the direct path whatever K1 counted - nothing to decide)
     const bool decide_from_k1 = p.direct_max && !(p.occupancy_only && !ctx->force_general);
     if (decide_from_k1) {
         // K1's counters go to the host on an auxiliary stream while k_voxelize runs (see below)
-        if (!ctx->aux[0]) O2V_CHECK(hipStreamCreateWithFlags(&ctx->aux[0], hipStreamNonBlocking));
+        O2V_CHECK(ctx->aux[0].create());
         O2V_CHECK(hipEventRecord(ctx->ev_k1, s));
         O2V_CHECK(hipStreamWaitEvent(ctx->aux[0], ctx->ev_k1, 0));
         O2V_CHECK(hipMemcpyAsync(ctx->h_ctr.ptr, ctr, kPassCounterWords * 4u, hipMemcpyDeviceToHost, ctx->aux[0]));
     }
 
     launch_voxelize(ctx, p, use_uv, block_list);
-    if (ctx->stage_events) O2V_CHECK(hipEventRecord(ctx->ev[3], s));
+    if (ctx->stage_events) O2V_CHECK(ctx->pass_times.mark(3, s));
 
     // With the direct MAX path the rest of the pass depends on the mesh: one whose triangles are all voxelized whole needs
     // neither the counting sort nor the replay (a dozen launches that would each find nothing), one whose triangles are
@@ -845,7 +868,7 @@ int run_pass(o2v_hip_ctx *ctx, const Params &p, const Switches &sw, bool use_uv,
                            ctx->d_dirty_list.ptr, ctr, ctx->d_occ.ptr, lists, p);
     }
     ctx->last_ran_general = run_general;
-    if (ctx->stage_events) O2V_CHECK(hipEventRecord(ctx->ev[4], s));
+    if (ctx->stage_events) O2V_CHECK(ctx->pass_times.mark(4, s));
 
     if (run_general) {
         // (tier 1 on the inline cells runs as fast with two workgroups per CU as with eight - it is not bound by the wavefronts in
@@ -864,7 +887,7 @@ int run_pass(o2v_hip_ctx *ctx, const Params &p, const Switches &sw, bool use_uv,
         O2V_LAUNCH("k_emit_max", s, k_emit_max, dim3((uint32_t) ctx->num_cus * 3u), dim3(kBlock), 0, s, ctx->d_dirty_list_max.ptr, ctr, p.mat,
                            ctx->d_out.ptr, p);
     }
-    if (ctx->stage_events) O2V_CHECK(hipEventRecord(ctx->ev[5], s));
+    if (ctx->stage_events) O2V_CHECK(ctx->pass_times.mark(5, s));
     return finish_pass(ctx);
 }
 
@@ -1361,11 +1384,7 @@ int fill_stage(o2v_hip_ctx *ctx, const o2v_hip_params *params, const Run &r, uin
         (rc = grow(ctx, ctx->d_fill_blocks, n_blocks, kNoLimit)) || (rc = grow(ctx, ctx->d_fill_chunks, n_chunks, kNoLimit)) ||
         (rc = grow(ctx, ctx->d_fill_ctr, 3)) || (rc = grow(ctx, ctx->h_fill_ctr, 2)))
         return rc;
-    const bool timed = ctx->stage_events;
-    if (timed)
-        for (hipEvent_t &e : ctx->ev_fill)
-            if (!e) O2V_CHECK(create_timing_event(&e));
-    if (timed) O2V_CHECK(hipEventRecord(ctx->ev_fill[0], s));
+    if (ctx->stage_events) O2V_CHECK(ctx->fill_times.mark(0, s));
     Affine xf;
     const float *x = ctx->h_ctr.ptr->xform;  // (k_setup's transform of this pass)
     for (int i = 0; i < 3; ++i) xf.m[i] = {x[i * 3], x[i * 3 + 1], x[i * 3 + 2]};
@@ -1398,10 +1417,10 @@ int fill_stage(o2v_hip_ctx *ctx, const o2v_hip_params *params, const Run &r, uin
         O2V_LAUNCH("k_fill_emit", s, k_fill_emit, dim3(chunk_wgs), dim3(kBlock), 0, s, ctx->d_fill_bits.ptr, b, ctx->d_fill_chunks.ptr, n_surf,
                    ctx->d_out.ptr);
     }
-    if (timed) O2V_CHECK(hipEventRecord(ctx->ev_fill[1], s));
+    if (ctx->stage_events) O2V_CHECK(ctx->fill_times.mark(1, s));
     O2V_CHECK(hipStreamSynchronize(s));
     O2V_CHECK(hipGetLastError());
-    if (timed) O2V_CHECK(hipEventElapsedTime(&ctx->timings.fill_ms, ctx->ev_fill[0], ctx->ev_fill[1]));
+    if (ctx->stage_events) O2V_CHECK(ctx->fill_times.elapsed(0, 1, ctx->timings.fill_ms));
     return collect_kernel_times(ctx);
 }
 
@@ -1435,12 +1454,12 @@ int publish(o2v_hip_ctx *ctx, const Run &r, uint64_t n_interior, uint64_t *out_v
     std::memcpy(ctx->xform, h.xform, sizeof(ctx->xform));
     for (int i = 0; i < 16; ++i) ctx->dbg[i] = h.dbg[i];
     o2v_hip_timings &t = ctx->timings;
-    float *const stage_ms[5] = {&t.bounds_ms, &t.expand_ms, &t.voxelize_ms, &t.scan_ms, &t.resolve_ms};  // (between ev[i] and ev[i + 1])
+    float *const stage_ms[5] = {&t.bounds_ms, &t.expand_ms, &t.voxelize_ms, &t.scan_ms, &t.resolve_ms};  // (between marks i and i + 1)
     if (ctx->stage_events) {
-        for (int i = 0; i < 5; ++i) O2V_CHECK(hipEventElapsedTime(stage_ms[i], ctx->ev[i], ctx->ev[i + 1]));
-        O2V_CHECK(hipEventElapsedTime(&t.total_ms, ctx->ev[0], ctx->ev[5]));
+        for (int i = 0; i < 5; ++i) O2V_CHECK(ctx->pass_times.elapsed(i, i + 1, *stage_ms[i]));
+        O2V_CHECK(ctx->pass_times.elapsed(0, 5, t.total_ms));
     }
-    else O2V_CHECK(hipEventElapsedTime(&t.voxelize_ms, ctx->ev[2], ctx->ev[3]));  // (k_voxelize's own dispatch: O2V_LAUNCH_K2)
+    else O2V_CHECK(ctx->pass_times.elapsed(2, 3, t.voxelize_ms));  // (k_voxelize's own dispatch: O2V_LAUNCH_K2)
     if (out_voxel_count) *out_voxel_count = ctx->n_vox;
     return O2V_HIP_OK;
 }
@@ -1609,19 +1628,14 @@ int o2v_hip_create(int device, o2v_hip_ctx **out_ctx)
     };
     ctx->device = device;
     ctx->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) return fail(O2V_HIP_ERR_HIP);
+    if (ctx->stream.create() != hipSuccess) return fail(O2V_HIP_ERR_HIP);
     lap("the stream");
-    for (auto &e : ctx->ev)
-        if (create_timing_event(&e) != hipSuccess) return fail(O2V_HIP_ERR_HIP);
-    bool ok = hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&ctx->ev_sorted, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&ctx->ev_k1, hipEventDisableTiming) == hipSuccess;
-    // (aux[1] and aux[2] - the cooperative resolve tiers - are created by the first pass that forks; a stream costs 0.3 ms
-    // in a warm process and several in a new one, and a mesh on the direct route never needs them)
-    for (int j = 0; j < 3 && ok; ++j) ok = hipEventCreateWithFlags(&ctx->ev_join[j], hipEventDisableTiming) == hipSuccess;
+    bool ok = ctx->pass_times.create() == hipSuccess && ctx->ev_fork.create_sync() == hipSuccess &&
+              ctx->ev_sorted.create_sync() == hipSuccess && ctx->ev_k1.create_sync() == hipSuccess;
+    for (Event &e : ctx->ev_join) ok = ok && e.create_sync() == hipSuccess;
     lap("events");
-    // (the auxiliary streams are made by the first pass that needs one - 7 - 8 ms each in a new process, and the occupancy-only
-    // route, every STL, never does)
+    // (the auxiliary streams are made by the first pass that needs one - 0.3 ms each in a warm process, 7 - 8 ms in a new one -
+    // and the occupancy-only route, every STL, never does)
     if (!ok) return fail(O2V_HIP_ERR_HIP);
     if (ctx->d_ctr.alloc(1) != hipSuccess) return fail(O2V_HIP_ERR_OUT_OF_MEMORY);
     lap("first hipMalloc");
@@ -1652,19 +1666,8 @@ void o2v_hip_destroy(o2v_hip_ctx *ctx)
         return;
     }
     (void) hipSetDevice(ctx->device);
-    if (ctx->stream) (void) hipStreamSynchronize(ctx->stream);
-    std::vector<hipEvent_t> events{std::begin(ctx->ev), std::end(ctx->ev)};
-    events.insert(events.end(), {ctx->ev_coll[0], ctx->ev_coll[1], ctx->ev_stage[0], ctx->ev_stage[1], ctx->ev_fork, ctx->ev_sorted,
-                                 ctx->ev_k1, ctx->ev_join[0], ctx->ev_join[1], ctx->ev_join[2], ctx->ev_fill[0], ctx->ev_fill[1]});
-    events.insert(events.end(), std::begin(ctx->dist_times.ev), std::end(ctx->dist_times.ev));
-    events.insert(events.end(), std::begin(ctx->md_times.ev), std::end(ctx->md_times.ev));
-    for (const auto &b : ctx->ktimes) events.insert(events.end(), {b.e0, b.e1});
-    for (hipEvent_t e : events)
-        if (e) (void) hipEventDestroy(e);
-    for (hipStream_t q : ctx->aux)
-        if (q) (void) hipStreamDestroy(q);
-    if (ctx->stream) (void) hipStreamDestroy(ctx->stream);
-    delete ctx;  // (the arrays free themselves)
+    (void) hipStreamSynchronize(ctx->stream);
+    delete ctx;  // (the arrays, events and streams free themselves)
 }
 
 const char *o2v_hip_last_error(const o2v_hip_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
@@ -1696,7 +1699,7 @@ int o2v_hip_begin_triangles(o2v_hip_ctx *ctx, o2v_hip_staging *out_block)
     if (!ctx->stage[0].verts.ptr) {
         for (int b = 0; b < 2; ++b) {
             O2V_CHECK(ctx->stage[b].verts.alloc(kStageTriangles * 9));
-            O2V_CHECK(hipEventCreateWithFlags(&ctx->ev_stage[b], hipEventDisableTiming));
+            O2V_CHECK(ctx->ev_stage[b].create_sync());
         }
     }
     ctx->stage_cur = 0;
@@ -1867,16 +1870,16 @@ int plan_passes(o2v_hip_ctx *ctx, const o2v_hip_params *params, const Switches &
 
     hipStream_t s = ctx->stream;
     float coll_ms = 0.f;
-    const bool measure = (params->flags & (O2V_HIP_FLAG_STAGE_TIMES | O2V_HIP_FLAG_KERNEL_TIMES)) != 0 && ctx->ev_coll[0] && ctx->ev_coll[1];
+    const bool measure = (params->flags & (O2V_HIP_FLAG_STAGE_TIMES | O2V_HIP_FLAG_KERNEL_TIMES)) != 0;
     auto timed = [&](int part, auto &&collectives) -> int {
         if (!measure) return collectives();
-        O2V_CHECK(hipEventRecord(ctx->ev_coll[0], s));
+        O2V_CHECK(ctx->coll_times.mark(0, s));
         const int rc = collectives();
         if (rc) return rc;
-        O2V_CHECK(hipEventRecord(ctx->ev_coll[1], s));
-        O2V_CHECK(hipEventSynchronize(ctx->ev_coll[1]));
+        O2V_CHECK(ctx->coll_times.mark(1, s));
+        O2V_CHECK(hipEventSynchronize(ctx->coll_times.ev[1]));
         float ms = 0.f;
-        O2V_CHECK(hipEventElapsedTime(&ms, ctx->ev_coll[0], ctx->ev_coll[1]));
+        O2V_CHECK(ctx->coll_times.elapsed(0, 1, ms));
         coll_ms += ms;
         if (parts_ms) parts_ms[part] += ms;
         return O2V_HIP_OK;
@@ -1988,10 +1991,8 @@ int agree_to_start(o2v_hip_ctx *ctx, o2v_hip_comm *comm, const o2v_hip_params *p
         }
     }
     const uint32_t world = (uint32_t) comm->world, rank = (uint32_t) comm->rank;
-    const bool measure_collectives = (params->flags & (O2V_HIP_FLAG_STAGE_TIMES | O2V_HIP_FLAG_KERNEL_TIMES)) != 0;
     auto prepare = [&]() -> int {
-        if (!ctx->ev_coll[0])
-            for (auto &e : ctx->ev_coll) O2V_CHECK(create_timing_event(&e));
+        O2V_CHECK(ctx->coll_times.create());
         int rc_grow;
         if ((rc_grow = grow(ctx, ctx->d_counts, world)) || (rc_grow = grow(ctx, ctx->h_counts, world))) return rc_grow;
         return size_plan_buffers(ctx, bpr * world, ((uint64_t) kPlanBins + bpr) * world);
@@ -2015,8 +2016,8 @@ int agree_to_start(o2v_hip_ctx *ctx, o2v_hip_comm *comm, const o2v_hip_params *p
     hipLaunchKernelGGL(k_pack_ready, dim3(1), dim3(64), 0, s0, ctx->d_ctr.ptr, ctx->d_status.ptr, rc_prepare ? 1u : 0u);
     // (no local HIP error may keep this rank out of the collective: its peers would wait for the time limit instead of seeing
     // the error in the status word - a timing event that cannot be recorded only switches the timing off)
-    bool time_it = measure_collectives && ctx->ev_coll[0] && ctx->ev_coll[1];
-    if (time_it && hipEventRecord(ctx->ev_coll[0], s0) != hipSuccess) {
+    bool time_it = (params->flags & (O2V_HIP_FLAG_STAGE_TIMES | O2V_HIP_FLAG_KERNEL_TIMES)) != 0;
+    if (time_it && ctx->coll_times.mark(0, s0) != hipSuccess) {
         (void) hipGetLastError();
         time_it = false;
     }
@@ -2025,7 +2026,7 @@ int agree_to_start(o2v_hip_ctx *ctx, o2v_hip_comm *comm, const o2v_hip_params *p
         ctx->err = std::string("collective failed: ") + comm->err;
         return O2V_HIP_ERR_HIP;
     }
-    if (time_it && hipEventRecord(ctx->ev_coll[1], s0) != hipSuccess) {
+    if (time_it && ctx->coll_times.mark(1, s0) != hipSuccess) {
         (void) hipGetLastError();
         time_it = false;
     }
@@ -2040,7 +2041,7 @@ int agree_to_start(o2v_hip_ctx *ctx, o2v_hip_comm *comm, const o2v_hip_params *p
         comm->poisoned = true;
         return O2V_HIP_ERR_HIP;
     }
-    if (time_it) O2V_CHECK(hipEventElapsedTime(&ready_ms, ctx->ev_coll[0], ctx->ev_coll[1]));
+    if (time_it) O2V_CHECK(ctx->coll_times.elapsed(0, 1, ready_ms));
     if (rc_prepare) {
         ctx->err = prepare_err;
         return rc_prepare;
@@ -2109,7 +2110,6 @@ int o2v_hip_voxelize_sharded(o2v_hip_ctx *ctx, o2v_hip_comm *comm, const o2v_hip
     const uint64_t T = ctx->n_tris, n_blocks = (T + kBlock - 1) / kBlock;
     const uint64_t bpr = std::max<uint64_t>(1, (n_blocks + world - 1) / world);
     float parts_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    const bool measure_collectives = (params->flags & (O2V_HIP_FLAG_STAGE_TIMES | O2V_HIP_FLAG_KERNEL_TIMES)) != 0;
     // this rank's share of the triangle list, in whole blocks of 256 (the unit of the block extents)
     const uint64_t b0 = std::min<uint64_t>(n_blocks, (uint64_t) rank * bpr), b1 = std::min<uint64_t>(n_blocks, (uint64_t) (rank + 1) * bpr);
     const uint64_t tri_begin = b0 * kBlock, tri_end = std::min<uint64_t>(T, b1 * kBlock);
@@ -2138,21 +2138,19 @@ int o2v_hip_voxelize_sharded(o2v_hip_ctx *ctx, o2v_hip_comm *comm, const o2v_hip
     ctx->h_counts.ptr[rank] = rc_vox ? ~0ull : n;
     const std::string vox_err = ctx->err;
     O2V_CHECK(hipMemcpyAsync(ctx->d_counts.ptr + rank, ctx->h_counts.ptr + rank, sizeof(unsigned long long), hipMemcpyHostToDevice, s));
-    const bool time_counts = measure_collectives && ctx->ev_coll[0] && ctx->ev_coll[1];
-    if (time_counts) O2V_CHECK(hipEventRecord(ctx->ev_coll[0], s));
+    const bool time_counts = (params->flags & (O2V_HIP_FLAG_STAGE_TIMES | O2V_HIP_FLAG_KERNEL_TIMES)) != 0;
+    if (time_counts) O2V_CHECK(ctx->coll_times.mark(0, s));
     rc = comm->allgather(ctx->d_counts.ptr, sizeof(unsigned long long), s);
     if (rc) {
         ctx->err = std::string("collective failed: ") + comm->err;
         return rc;
     }
-    if (time_counts) O2V_CHECK(hipEventRecord(ctx->ev_coll[1], s));
+    if (time_counts) O2V_CHECK(ctx->coll_times.mark(1, s));
     O2V_CHECK(hipMemcpyAsync(ctx->h_counts.ptr, ctx->d_counts.ptr, world * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     O2V_CHECK(hipStreamSynchronize(s));
-    float ms = 0.f;
-    if (time_counts) O2V_CHECK(hipEventElapsedTime(&ms, ctx->ev_coll[0], ctx->ev_coll[1]));
-    parts_ms[4] = ms;
+    if (time_counts) O2V_CHECK(ctx->coll_times.elapsed(0, 1, parts_ms[4]));
     ctx->timings.plan_ms = plan_ms;
-    ctx->timings.collective_ms = coll_ms + ms + parts_ms[0];
+    ctx->timings.collective_ms = coll_ms + parts_ms[4] + parts_ms[0];
     for (int i = 0; i < 5; ++i) ctx->timings.collective_parts_ms[i] = parts_ms[i];
     if (rc_vox) {
         ctx->err = vox_err;

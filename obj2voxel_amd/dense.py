@@ -279,6 +279,8 @@ def mesh_distance(dv, resolution, *, band, signed=True, out=None, closest=None, 
     _require_shared_runtime()
     if isinstance(band, bool) or not isinstance(band, numbers.Real) or not (0.0 < float(band) <= MAX_BAND):
         raise ValueError(f"band must be a number with 0 < band <= {MAX_BAND:g} voxels, not {band!r}")
+    if not hip.C.c_float(float(band)).value > 0.0:   # (the call takes a float: 1e-46 is 0 there)
+        raise ValueError(f"band {band!r} is 0 as a float32")
     _check_sampling(resolution, supersampling, max_layers)
     device = _device(dv)
     origin = tuple(int(v) for v in (origin or (0, 0, 0)))

@@ -237,8 +237,105 @@ def case_bench_mesh():
     print("sampled", len(pts), "surface voxels", len(seeds), "interior", int((lab == 2).sum()))
 
 
+# ---- at the limits the call documents -----------------------------------------------------------------------------------
+
+def _largest(d2):
+    finite = d2[d2 != R.INF]
+    return int(finite.max()) if finite.size else None
+
+
+def case_lane_cap():
+    """More lines than the 2^17 lanes in both envelope passes, every voxel compared: a lane's second and later lines, and the
+    few lines of a count that is no multiple of the cap or of a workgroup."""
+    dv = hip.DeviceVoxelizer(0)
+    for shape in R.LANE_CAP_SHAPES:
+        nz, ny, nx = shape
+        ly, lz = R.pass_lines(shape)
+        assert nx * nz > 2 ** 17 and nx * ny > 2 ** 17 and ny >= 5 and nz >= 5, shape
+        for density, empty_plane in ((0.01, None), (3e-6, 2)):
+            lab = R.lane_cap_labels(shape, density, seed=17, empty_plane=empty_plane)
+            dark = nx * int((~(lab == 1).any(axis=(1, 2))).sum())      # lines along y of the planes without a seed
+            assert (lab == 1).any() and (lab == 2).any() and (empty_plane is None or dark > 0), (shape, density)
+            want = R.separable_d2(lab)
+            check(dv, lab, want, f"lane cap, density {density}")
+            print("lane_cap", shape, "lines y", ly, "z", lz, "cap", R.LANE_CAP, "last turn", ly % R.LANE_CAP, lz % R.LANE_CAP,
+                  "density", density, "seeds", int((lab == 1).sum()), "y lines without a value", dark, "largest d2", _largest(want))
+    assert all(n % R.LANE_CAP and n % 256 for n in R.pass_lines(R.LANE_CAP_SHAPES[1]))
+    # labels stored [y][x][z], out stored [x][z][y], both looked at as [z, y, x]: x * d0 is a stride, the SDF reads l0, l1, l2
+    nz, ny, nx = shape = R.LANE_CAP_SHAPES[0]
+    lab = R.lane_cap_labels(shape, 0.002, seed=23)
+    want = R.separable_d2(lab)
+    lab_p = torch.from_numpy(lab).to(DEV).permute(1, 2, 0).contiguous().permute(2, 0, 1)
+    for fmt, dtype, w in (("dist2", torch.int32, want), ("sdf", torch.float32, R.sdf(lab, want).view(np.int32))):
+        out_p = torch.zeros((nx, nz, ny), dtype=dtype, device=DEV).permute(1, 2, 0)
+        dense.distance_transform(dv, lab_p, fmt, out=out_p)
+        got = out_p.cpu().numpy().view(np.int32)
+        assert np.array_equal(got, w), (fmt, "permuted", int((got != w).sum()))
+    print("lane_cap permuted", shape, "strides", tuple(lab_p.stride()), tuple(out_p.stride()))
+
+
+def case_long_lines():
+    """Lines of 46 341 voxels, the longest accepted, along z, y and x, with seeds at both ends and past position 2^15: s and t
+    of a stack entry above 2^15, through the scratch and back."""
+    dv = hip.DeviceVoxelizer(0)
+    for shape in R.LONG_SHAPES:
+        assert max(shape) == R.LONG and sum((n - 1) ** 2 for n in shape) <= R.D2_LIMIT, shape
+        lab = R.long_line_labels(shape, seed=29)
+        v = np.moveaxis(lab, int(np.argmax(shape)), 0)
+        assert v[0, 0, 0] == 1 and v[-1, 0, 0] == 1 and (lab == 2).any()
+        stats = []
+        want = R.separable_d2(lab, stats)
+        if shape[2] != R.LONG:   # a long envelope pass: its stacks, from the reference
+            depth, pops, stacks = stats[1 if shape[0] == R.LONG else 0]
+            # entries below the top two of the final stack (stored, and loaded again by the backward sweep) with s, t > 2^15
+            stacks = [R.final_stack(*stacks, line) for line in range(len(depth))]
+            high = [sum(1 for s, t in st[:-2] if s > 1 << 15 and t > 1 << 15) for st in stacks]
+            past = int((v[(1 << 15) + 1:] == 1).any(axis=(1, 2)).sum())
+            assert max(high) >= 6 and past >= 6, (shape, high, past)
+            print("long_lines", shape, "stack depth", depth.tolist(), "entries from the scratch with s, t > 2^15", high,
+                  "largest t", max(t for st in stacks for _, t in st))
+        check(dv, lab, want, "long lines")
+        print("long_lines", shape, "seeds", int((lab == 1).sum()), "largest d2", _largest(want))
+
+
+def case_value_limit():
+    """One seed in a corner of a box at the d2 limit: d2 = x^2 + y^2 + z^2 up to 2 147 483 216 of the 2 147 483 646 accepted,
+    the SDF against the float64 sqrt rounded to float32; with the long axis along x and along z."""
+    dv = hip.DeviceVoxelizer(0)
+    a, b = np.arange(R.LONG, dtype=np.int64), np.arange(297, dtype=np.int64)
+    for shape in ((1, 297, R.LONG), (R.LONG, 297, 1)):
+        lab = np.zeros(shape, np.uint8)
+        d2 = (b[None, :, None] ** 2 + a[None, None, :] ** 2) if shape[0] == 1 else (a[:, None, None] ** 2 + b[None, :, None] ** 2)
+        lab[d2 > 1 << 30] = 2                                    # the far part inside: the sign at the largest values
+        lab[(d2 % 7 == 3) & (d2 > 0)] = 2
+        lab[0, 0, 0] = 1
+        assert int(d2.max()) == 46340 ** 2 + 296 ** 2 == 2147483216 <= R.D2_LIMIT and (lab == 1).sum() == 1
+        check(dv, lab, d2.astype(np.int32), "value limit")
+        got = run(dv, lab, "sdf")
+        far = got[-1, -1, -1]
+        assert far == -np.float32(np.sqrt(np.float64(2147483216))), far
+        print("value_limit", shape, "largest d2", int(d2.max()), "limit", R.D2_LIMIT, "sdf there", float(far))
+
+
+def case_deep_stacks():
+    """An envelope a thousand entries deep that empties at one position, in the y pass and in the z pass."""
+    dv = hip.DeviceVoxelizer(0)
+    for along_z, interior in ((False, None), (True, None), (False, 41), (True, 43)):
+        lab = R.deep_stack_labels(along_z, interior)
+        stats = []
+        want = R.separable_d2(lab, stats)
+        depth, pops, _ = stats[1 if along_z else 0]
+        deep, long_runs, short_runs = int((depth >= 1000).sum()), int((pops >= 1000).sum()), int(((pops >= 1) & (pops <= 100)).sum())
+        assert deep > 0 and long_runs > 0 and short_runs > 0, (deep, long_runs, short_runs)
+        assert interior is None or (lab == 2).any()
+        check(dv, lab, want, "deep stacks")
+        print("deep_stacks", lab.shape, "interior", interior, "lines", len(depth), "depth >= 1000 on", deep, "largest", int(depth.max()),
+              ">= 1000 pops at one position on", long_runs, "1 to 100 pops on", short_runs, "largest d2", _largest(want))
+
+
 CASES = {"random": case_random, "strided": case_strided, "corner": case_corner, "refusals": case_refusals, "mesh": case_mesh,
-         "bench_mesh": case_bench_mesh}
+         "bench_mesh": case_bench_mesh, "lane_cap": case_lane_cap, "long_lines": case_long_lines, "value_limit": case_value_limit,
+         "deep_stacks": case_deep_stacks}
 
 if __name__ == "__main__":
     CASES[sys.argv[1]]()

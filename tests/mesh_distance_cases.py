@@ -38,20 +38,25 @@ def same(a, b):
     return a.shape == b.shape and np.array_equal(a, b)
 
 
-def check(dv, verts, res, band, signed, xf=None, what="", **kw):
-    """One call of the whole grid against the reference; returns the device result."""
+def check(dv, verts, res, band, signed, xf=None, what="", box=None, inside=True, want=None, **kw):
+    """One call of the whole grid, or of the box (origin, dims) in x, y, z, against the reference; returns the device result.
+    inside=False: for a band so narrow that no centre of the case lies in it.  want: the reference's (values, closest) if the
+    caller has them."""
     ss = kw.get("supersampling", 1)
     if xf is None:
         xf = xform(dv, res, **kw)
     sv = fill_ref.sample_vertices(verts, xf)
-    got, idx, _ = dense.mesh_distance(dv, res, band=band, signed=signed, closest=True, **kw)
-    vals, want_idx = R.mesh_distance(sv, res, ss, band, signed)
+    origin, dims = box if box else ((0, 0, 0), (res, res, res))
+    out = torch.empty(tuple(dims[::-1]), device=DEV) if box else None
+    got, idx, o = dense.mesh_distance(dv, res, band=band, signed=signed, closest=True, out=out, origin=origin, **kw)
+    assert o == tuple(origin)
+    vals, want_idx = want if want is not None else R.mesh_distance(sv, res, ss, band, signed, origin, dims)
     got, idx = got.cpu().numpy(), idx.cpu().numpy()
     bad = int((got.view(np.int32) != vals.view(np.int32)).sum())
     assert bad == 0, (what, res, band, signed, kw, bad, got[got.view(np.int32) != vals.view(np.int32)][:5],
                       vals[got.view(np.int32) != vals.view(np.int32)][:5])
     assert np.array_equal(idx, want_idx), (what, res, band, signed, kw, int((idx != want_idx).sum()))
-    assert (got < band).any(), (what, "nothing inside the band")
+    assert (np.abs(got) < np.float32(band)).any() or not inside, (what, "nothing inside the band")
     return got, idx
 
 
@@ -232,6 +237,7 @@ def case_refusals():
         expect_code3(call(full.data_ptr(), band=float("nan")), "band nan"),
         expect_code3(call(full.data_ptr(), band=32.5), "band above 32"),
         expect_code3(call(full.data_ptr(), band=float("inf")), "band inf"),
+        expect_code3(call(full.data_ptr(), band=1e-46), "band 0 as a float"),
         expect_code3(call(full.data_ptr(), fmt=2), "format"),
         expect_code3(call(full.data_ptr(), d=(R_, 0, R_)), "zero dims"),
         expect_code3(call(full.data_ptr(), origin=(1, 0, 0)), "box past the grid"),
@@ -294,8 +300,191 @@ def case_bench_mesh():
     print("sampled", len(pts), "in band", int((got < band).sum()), "times", dv.mesh_distance_times())
 
 
+# ---- at the limits the call documents -----------------------------------------------------------------------------------
+
+UNIT = np.array([0, 0, 0, 1, 1, 1], np.float32)
+
+
+def _through_centre(xf, voxel, ss):
+    """A model-space triangle around the centre of `voxel` (x, y, z), in the plane of constant model z through it, for a
+    transform that only scales and shifts: after the float32 rounding the centre lies within 1e-4 sample of it."""
+    m, t = np.asarray(xf, np.float64)[:9].reshape(3, 3), np.asarray(xf, np.float64)[9:]
+    assert np.count_nonzero(m - np.diag(np.diag(m))) == 0
+    c = np.linalg.solve(m, (np.asarray(voxel, np.float64) + 0.5) * ss - t)
+    return np.concatenate([c + [-0.03, -0.02, 0], c + [0.04, -0.01, 0], c + [-0.01, 0.05, 0]]).astype(np.float32)
+
+
+def case_bands():
+    """The widest band (32, with ss 1 and 2: every box dilated by up to 66 samples), bands that are no float32 (31.9, 2.6, 0.1)
+    and one of a thousandth of a voxel, on a closed sphere (signed and unsigned) and a soup, whole grid with closest."""
+    dv = hip.DeviceVoxelizer(0)
+    res = 48
+    sphere = fill_ref.weld(meshes.uv_sphere(7))
+    soup = meshes.random_soup(150, seed=3)
+    upload(dv, soup)
+    xf_soup = xform(dv, res, bounds=UNIT)
+    soup = np.concatenate([soup, _through_centre(xf_soup, (20, 31, 9), 1)[None]])
+    bands = ((32.0, 1), (32.0, 2), (31.9, 1), (0.1, 1), (2.6, 2), (1e-3, 1))
+    n = 0
+    for band, ss in bands:
+        assert 0 < band <= 32
+        upload(dv, sphere)
+        xf = xform(dv, res, supersampling=ss)
+        sv = fill_ref.sample_vertices(sphere, xf)
+        vals, idx = R.mesh_distance(sv, res, ss, band, True)     # (unsigned: the same without the sign, by R.finish)
+        got, _ = check(dv, sphere, res, band, True, xf=xf, what="sphere", inside=band > 1e-3, want=(vals, idx), supersampling=ss)
+        check(dv, sphere, res, band, False, xf=xf, what="sphere", inside=band > 1e-3, want=(np.abs(vals), idx), supersampling=ss)
+        print("bands sphere", len(sphere), "triangles, band", band, "ss", ss, "in band", int((idx >= 0).sum()), "of", idx.size,
+              "negative", int((got < 0).sum()))
+        upload(dv, soup)
+        xf = xform(dv, res, supersampling=ss, bounds=UNIT)
+        got, idx = check(dv, soup, res, band, False, xf=xf, what="soup", supersampling=ss, bounds=UNIT)
+        assert band < 32 or (idx >= 0).all()     # (at 32 voxels of a grid of 48 every centre is in some triangle's band)
+        print("bands soup", len(soup), "triangles, band", band, "ss", ss, "in band", int((idx >= 0).sum()), "of", idx.size)
+        n += 3
+    print("compared", n)
+
+
+def case_band_threshold():
+    """The in-band test to one float32 step of the band: a voxel v* whose D lies between the float32 and the double square
+    of a float32 f is inside band f (Bs2 is squared in double) and exactly at the float32 below f."""
+    dv = hip.DeviceVoxelizer(0)
+    res = 32
+    sphere = fill_ref.weld(meshes.uv_sphere(10))
+    upload(dv, sphere)
+    xf = xform(dv, res)
+    sv = fill_ref.sample_vertices(sphere, xf)
+    D, best_id = R.best_d2(sv, res, 1, 8.0)
+    found = None
+    count = 0
+    for z, y, x in np.argwhere((D >= 0.25 ** 2) & (D < 7.9 ** 2)):
+        f, narrow = R.threshold_band(D[z, y, x])
+        if narrow and 0.25 <= f <= 8:
+            count += 1
+            found = found or ((int(z), int(y), int(x)), f)
+    assert found, "no voxel whose band threshold tells a float32 square from a double one"
+    (z, y, x), f = found
+    g = np.nextafter(f, np.float32(0))
+    d = D[z, y, x]
+    assert np.float64(f) * np.float64(f) > d >= np.float64(np.float32(f * f)) and np.float64(g) * np.float64(g) <= d
+    got, idx = check(dv, sphere, res, float(f), True, xf=xf, what="band f")
+    # (inside the band: its own distance and triangle.  The distance may round to f itself; closest tells the two apart)
+    assert abs(got[z, y, x]) == np.float32(np.sqrt(d)) and idx[z, y, x] == best_id[z, y, x] >= 0, (got[z, y, x], idx[z, y, x])
+    assert (idx == -1).any() and (np.abs(got[idx == -1]) == f).all()
+    got_g, idx_g = check(dv, sphere, res, float(g), True, xf=xf, what="the float32 below f")
+    assert abs(got_g[z, y, x]) == g and idx_g[z, y, x] == -1, (got_g[z, y, x], idx_g[z, y, x])
+    print("band_threshold v* (z, y, x)", (z, y, x), "D", repr(float(d)), "f", repr(float(f)), "below", repr(float(g)), "float32 f*f",
+          repr(float(np.float32(f * f))), "voxels with such an f", count, "of", D.size, "value at f", float(got[z, y, x]),
+          "closest", int(idx[z, y, x]), "in band", int((idx >= 0).sum()), "and", int((idx_g >= 0).sum()))
+
+
+def case_cropped():
+    """bounds= strictly inside the mesh: triangles that stick out of the grid on both sides of every axis or lie wholly
+    outside it, within and beyond the margin; and two triangles with sample coordinates near 1e18."""
+    dv = hip.DeviceVoxelizer(0)
+    res = 48
+    sphere = fill_ref.weld(meshes.uv_sphere(16))
+    inner = np.array([-0.62, -0.6, -0.64, 0.6, 0.63, 0.61], np.float32)   # (the corners reach past the sphere of radius 1)
+    upload(dv, sphere)
+    n = 0
+    for ss in (1, 2):
+        xf = xform(dv, res, supersampling=ss, bounds=inner)
+        sv = fill_ref.sample_vertices(sphere, xf)
+        lo, hi = sv.min(axis=1), sv.max(axis=1)
+        S = res * ss
+        sticks = [(int(((lo[:, a] < 0) & (hi[:, a] > 0)).sum()), int(((lo[:, a] < S) & (hi[:, a] > S)).sum())) for a in range(3)]
+        outside = (hi < 0).any(axis=1) | (lo > S).any(axis=1)
+        gap = np.maximum(np.maximum(-hi, lo - S), 0).max(axis=1)           # samples between the grid and the triangle's box
+        assert all(a > 0 and b > 0 for a, b in sticks) and (outside & (gap < ss)).any() and (outside & (gap > 10 * ss)).any()
+        for band in (1.0, 8.0):
+            got, idx = check(dv, sphere, res, band, True, xf=xf, what="cropped sphere", supersampling=ss, bounds=inner)
+            assert (got < 0).any() and (got > 0).any() and (idx == -1).any()
+            n += 1
+        # a box with an origin: the clamps against o and o + n - 1 are not those against the grid
+        box = ((5, 9, 3), (30, 21, 40))
+        check(dv, sphere, res, 8.0, True, xf=xf, what="cropped sphere, box", box=box, supersampling=ss, bounds=inner)
+        n += 1
+        print("cropped sphere ss", ss, "triangles across the low / high side per axis", sticks, "wholly outside", int(outside.sum()))
+    soup = meshes.random_soup(600, seed=8)
+    inner = np.array([0.2, 0.25, 0.3, 0.8, 0.75, 0.7], np.float32)
+    far = np.float32(1e16)
+    huge = np.array([[-far, -far, 0.52, far, -far, 0.52, 0, 2 * far, 0.52],                       # spans the grid in x and y
+                     [far, far, far, far * 1.5, far, far, far, far * 1.5, far * 1.25]], np.float32)   # wholly outside
+    both = np.concatenate([soup, huge])
+    for ss in (1, 2):
+        upload(dv, soup)
+        xf = xform(dv, res, supersampling=ss, bounds=inner)      # (of the bounds alone; voxelize never sees the huge triangles)
+        sv = fill_ref.sample_vertices(both, xf)
+        assert np.isfinite(sv).all() and (np.abs(sv[-2:]).max(axis=(1, 2)) > 1e17).all(), sv[-2:]
+        upload(dv, both)
+        for band in (1.0, 8.0):
+            got, idx = check(dv, both, res, band, False, xf=xf, what="cropped soup", supersampling=ss, bounds=inner)
+            assert (idx == len(both) - 2).any() and not (idx == len(both) - 1).any()
+            n += 1
+        check(dv, both, res, 8.0, False, xf=xf, what="cropped soup, box", box=((7, 2, 11), (33, 40, 20)), supersampling=ss, bounds=inner)
+        n += 1
+        print("cropped soup ss", ss, "huge sample coordinates", float(np.abs(sv[-2:]).max()), "closest to the spanning triangle",
+              int((idx == len(both) - 2).sum()))
+    print("compared", n)
+
+
+def _line_mesh(axis):
+    """A sliver along `axis` of the unit cube and three small triangles beside it."""
+    small = np.zeros((3, 3, 3))
+    for k, t in enumerate((0.1, 0.5, 0.93)):
+        c = np.full(3, 2e-5)
+        c[axis] = t
+        small[k] = c + 1e-5 * np.array([[0, 0, 0], [3, 1, 0.5], [0.5, 2, 3]])
+    return np.concatenate([meshes.sliver(axis), small.reshape(-1, 9).astype(np.float32)])
+
+
+def case_longest_box():
+    """A box of 65 535 voxels, the most accepted, along x, then y, then z, at resolution 65 535 and, with origin 4 000, at
+    70 000.  Every voxel of the box against R.mesh_distance, and R.point_distance at 8 192 sampled voxels of it (both ends
+    and the 64 either side of each small triangle among them).  Beside it, 65 536 is refused."""
+    dv = hip.DeviceVoxelizer(0)
+    n_long, band = 65535, 2.0
+    rng = np.random.default_rng(65535)
+    for axis in range(3):
+        verts = _line_mesh(axis)
+        upload(dv, verts)
+        for res, o_long in ((65535, 0), (70000, 4000)):
+            # the transform, from a voxelize call of a thin range along the axis
+            tile = {("xtile", "ytile", "zslab")[axis]: (0, 256)}
+            dv.voxelize(res, read=False, bounds=UNIT, **tile)
+            xf = dv.transform()
+            origin, dims = [0, 0, 0], [2, 2, 2]
+            origin[axis], dims[axis], dims[(axis + 2) % 3] = o_long, n_long, 1
+            got, idx = check(dv, verts, res, band, False, xf=xf, what="longest box", box=(tuple(origin), tuple(dims)), bounds=UNIT)
+            sv = fill_ref.sample_vertices(verts, xf)
+            along = np.concatenate([[0, n_long - 1], rng.choice(n_long, 8192, replace=False)] +
+                                   [np.arange(c - 64, c + 65) for c in np.floor(sv[2:, :, axis].mean(axis=1)).astype(np.int64) - o_long])
+            along = np.unique(np.clip(along, 0, n_long - 1))
+            assert len(along) >= 8192
+            pts = np.zeros((len(along), 3), np.int64)
+            pts[:, axis] = along
+            pts[:, (axis + 1) % 3] = rng.integers(0, dims[(axis + 1) % 3], len(along))
+            want, want_idx = R.point_distance(pts + np.array(origin), sv, 1, band)
+            z, y, x = pts[:, 2], pts[:, 1], pts[:, 0]
+            assert same(got[z, y, x], want) and np.array_equal(idx[z, y, x], want_idx)
+            ends = [bool(idx.reshape(-1)[0] >= 0), bool(idx.reshape(-1)[-1] >= 0)]
+            assert (idx >= 2).any() and (idx == -1).any() and (idx[(idx >= 0)] < 2).any()
+            print("longest_box axis", axis, "res", res, "origin", tuple(origin), "dims", tuple(dims), "in band", int((idx >= 0).sum()), "of",
+                  idx.size, "closest to a small triangle", int((idx >= 2).sum()), "ends in band", ends, "sampled", len(along))
+    line = torch.full((65536,), 7.0, device=DEV)
+    torch.cuda.synchronize()
+    try:
+        dv.mesh_distance_dense(70000, band, hip.MESH_DIST_UNSIGNED_F32, (0, 0, 0), (65536, 1, 1), line.data_ptr(), (1, 65536, 65536), bounds=UNIT)
+        raise AssertionError("a box of 65 536 voxels was accepted")
+    except hip.DeviceError as e:
+        assert "code 5" in str(e), str(e)
+    assert bool((line == 7).all())
+    print("ok longest_box")
+
+
 CASES = {"shapes": case_shapes, "boxes": case_boxes, "fill_agree": case_fill_agree, "transform": case_transform,
-         "crowded": case_crowded, "empty": case_empty, "refusals": case_refusals, "bench_mesh": case_bench_mesh}
+         "crowded": case_crowded, "empty": case_empty, "refusals": case_refusals, "bench_mesh": case_bench_mesh,
+         "bands": case_bands, "band_threshold": case_band_threshold, "cropped": case_cropped, "longest_box": case_longest_box}
 
 if __name__ == "__main__":
     CASES[sys.argv[1]]()

@@ -49,6 +49,12 @@ def d2(p, a, b, c):
     return np.where(face, plane, segs)
 
 
+def f32_band(band):
+    """The band as the call takes it: a float.  Every use below widens that float32 to double, as the header writes
+    (double) band; a Python double that is no float32 (2.6, say) would put other voxels in the band."""
+    return np.float64(np.float32(band))
+
+
 def _finite(sv):
     sv = np.asarray(sv, np.float32).reshape(-1, 3, 3)
     return sv, np.all(np.isfinite(sv), axis=(1, 2))
@@ -57,7 +63,7 @@ def _finite(sv):
 def dilated_aabb(sv, band, ss):
     """[T, 3] lower and upper corners (float64) of every triangle's AABB dilated by band ss + ss."""
     sv = np.asarray(sv, np.float32).reshape(-1, 3, 3)
-    m = np.float64(band) * ss + ss
+    m = f32_band(band) * ss + ss
     return sv.min(axis=1).astype(np.float64) - m, sv.max(axis=1).astype(np.float64) + m
 
 
@@ -66,8 +72,9 @@ def centres(idx, ss):
 
 
 def finish(best, best_id, band, ss, negative=None):
-    """(values float32, closest int32) from the best d2 and index per voxel."""
-    bs2 = np.float64(band) * np.float64(band) * ss * ss
+    """(values float32, closest int32) from the best d2 and index per voxel; Bs2 = (double) band * band * ss * ss of the
+    float32 band."""
+    bs2 = f32_band(band) * f32_band(band) * ss * ss
     inside = best < bs2
     with np.errstate(invalid="ignore"):
         u = np.where(inside, (np.sqrt(best) / ss).astype(np.float32), np.float32(band)).astype(np.float32)
@@ -76,9 +83,9 @@ def finish(best, best_id, band, ss, negative=None):
     return u, np.where(inside, best_id, -1).astype(np.int32)
 
 
-def mesh_distance(sv, G, ss, band, signed, origin=(0, 0, 0), dims=None, cull=True):
-    """(values float32 [nz, ny, nx], closest int32 [nz, ny, nx]) of the box origin + [0, dims) (x, y, z) of a G^3 grid for
-    sample-space triangles sv [T, 3, 3]."""
+def best_d2(sv, G, ss, band, origin=(0, 0, 0), dims=None, cull=True):
+    """(D float64 [nz, ny, nx], index int64) of the box: per voxel the smallest d2 over the triangles whose AABB, dilated by
+    the band's margin, holds its centre (inf and -1 where there is none), before the band is applied."""
     sv, ok = _finite(sv)
     dims = (G, G, G) if dims is None else tuple(dims)
     nx, ny, nz = dims
@@ -104,12 +111,32 @@ def mesh_distance(sv, G, ss, band, signed, origin=(0, 0, 0), dims=None, cull=Tru
         take = d < sub     # (triangles in ascending order: a tie keeps the smaller index)
         best[z[take], y[take], x[take]] = d[take]
         best_id[z[take], y[take], x[take]] = t
+    return best, best_id
+
+
+def mesh_distance(sv, G, ss, band, signed, origin=(0, 0, 0), dims=None, cull=True):
+    """(values float32 [nz, ny, nx], closest int32 [nz, ny, nx]) of the box origin + [0, dims) (x, y, z) of a G^3 grid for
+    sample-space triangles sv [T, 3, 3]."""
+    best, best_id = best_d2(sv, G, ss, band, origin, dims, cull)
     negative = None
     if signed:
-        keys = fill_ref.parity_keys(sv, G, ss)
+        nx, ny, nz = (G, G, G) if dims is None else tuple(dims)
+        ox, oy, oz = origin
+        keys = fill_ref.parity_keys(_finite(sv)[0], G, ss)
         z, y, x = np.meshgrid(np.arange(oz, oz + nz), np.arange(oy, oy + ny), np.arange(ox, ox + nx), indexing="ij")
         negative = np.isin((x.astype(np.int64) * G + y) * G + z, keys)
     return finish(best, best_id, band, ss, negative)
+
+
+def threshold_band(D):
+    """(f, narrow) for a d2 value D: f, the smallest float32 band that still holds it, (double) f * f > D, and whether the
+    float32 product f * f, widened, is <= D: a Bs2 squared in float32 would then leave the voxel out of band f."""
+    f = np.float32(np.sqrt(D))
+    while np.float64(f) * np.float64(f) > D:
+        f = np.nextafter(f, np.float32(0))
+    while not np.float64(f) * np.float64(f) > D:
+        f = np.nextafter(f, np.float32(np.inf))
+    return f, bool(np.float64(f * f) <= D)
 
 
 def point_distance(pts, sv, ss, band, chunk=256):

@@ -36,3 +36,29 @@ def test_voxelize_dense_sdf_of_closed_meshes():
 
 def test_bench_mesh_sampled_brute_force():
     _run("bench_mesh")
+
+
+# ---- at the limits the call documents: more lines than lanes, the longest lines, the largest value, the deepest stacks ----
+
+def test_more_lines_than_lanes():
+    out = _run("lane_cap")
+    print(out)   # (what the case covered)
+    assert "lane_cap permuted" in out
+
+
+def test_longest_lines():
+    out = _run("long_lines")
+    print(out)   # (what the case covered)
+    assert "entries from the scratch" in out
+
+
+def test_value_limit():
+    out = _run("value_limit")
+    print(out)   # (what the case covered)
+    assert "value_limit" in out
+
+
+def test_deep_stacks_and_long_pop_runs():
+    out = _run("deep_stacks")
+    print(out)   # (what the case covered)
+    assert "deep_stacks" in out

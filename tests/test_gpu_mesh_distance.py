@@ -44,3 +44,29 @@ def test_refusals():
 
 def test_bench_mesh_sampled():
     _run("bench_mesh", timeout=900)
+
+
+# ---- at the limits the call documents ------------------------------------------------------------------------------------
+
+def test_widest_and_odd_bands():
+    out = _run("bands")
+    print(out)   # (what the case covered)
+    assert "compared" in out
+
+
+def test_band_threshold_to_one_float32_step():
+    out = _run("band_threshold")
+    print(out)   # (what the case covered)
+    assert "band_threshold v*" in out
+
+
+def test_meshes_that_leave_the_grid():
+    out = _run("cropped")
+    print(out)   # (what the case covered)
+    assert "compared" in out
+
+
+def test_longest_box():
+    out = _run("longest_box")
+    print(out)   # (what the case covered)
+    assert "longest_box axis 2 res 70000" in out

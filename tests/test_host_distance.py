@@ -46,6 +46,73 @@ def test_separable_reference_equals_scipy():
     assert np.array_equal(R.separable_d2(lab), np.rint(edt ** 2).astype(np.int32))
 
 
+# ---- the reference at the shapes of the device's limit cases (tests/distance_cases.py) -----------------------------------
+
+def _sampled(lab, want, seed, n=300):
+    """`want` against an int64 brute force over every seed at n voxels: a third near seeds, the corners, the rest anywhere."""
+    rng = np.random.default_rng(seed)
+    shape = np.array(lab.shape)
+    seeds = np.argwhere(lab == 1)
+    assert len(seeds)
+    pts = rng.integers(0, shape, (n, 3))
+    near = seeds[rng.integers(0, len(seeds), n // 3)] + rng.integers(-3, 4, (n // 3, 3))
+    pts[:n // 3] = np.clip(near, 0, shape - 1)
+    pts[-8:] = [[z, y, x] for z in (0, shape[0] - 1) for y in (0, shape[1] - 1) for x in (0, shape[2] - 1)]
+    got = want[pts[:, 0], pts[:, 1], pts[:, 2]].astype(np.int64)
+    assert np.array_equal(got, R.sampled_brute_d2(lab, pts)), lab.shape
+    return int(got.max())
+
+
+@pytest.mark.parametrize("shape, density, empty_plane", [(R.LANE_CAP_SHAPES[0], 0.01, None), (R.LANE_CAP_SHAPES[0], 3e-6, 2),
+                                                         (R.LANE_CAP_SHAPES[1], 0.01, None), (R.LANE_CAP_SHAPES[1], 3e-6, 2)])
+def test_separable_reference_above_the_lane_cap(shape, density, empty_plane):
+    assert min(R.pass_lines(shape)) > R.LANE_CAP
+    lab = R.lane_cap_labels(shape, density, seed=17, empty_plane=empty_plane)
+    _sampled(lab, R.separable_d2(lab), 1)
+
+
+@pytest.mark.parametrize("shape", R.LONG_SHAPES)
+def test_separable_reference_on_the_longest_lines(shape):
+    lab = R.long_line_labels(shape, seed=29)
+    v = np.moveaxis(lab, int(np.argmax(shape)), 0)
+    assert v.shape[0] == R.LONG and v[0, 0, 0] == 1 and v[-1, 0, 0] == 1
+    assert sum((n - 1) ** 2 for n in shape) <= R.D2_LIMIT
+    _sampled(lab, R.separable_d2(lab), 2)
+    if shape[2] == R.LONG:
+        return
+    # one seed at the far end of a long envelope line: the largest value of the box, by the closed form
+    lab[lab == 1] = 0
+    v[-1, -1, -1] = 1
+    want = R.separable_d2(lab)
+    assert int(want[0, 0, 0]) == sum((n - 1) ** 2 for n in shape) and _sampled(lab, want, 3) == want[0, 0, 0]
+
+
+@pytest.mark.parametrize("along_z, interior", [(False, None), (True, 43)])
+def test_separable_reference_on_deep_stacks(along_z, interior):
+    lab = R.deep_stack_labels(along_z, interior)
+    _sampled(lab, R.separable_d2(lab), 4)
+
+
+def test_envelope_stats_counts_depth_and_pops():
+    # 10, 10, 10, 0: three pushes, then the 0 pops all of them at one position (of 5, 5, 5, 0 the first stays: 5 < 9 at t = 0);
+    # a line without values; a line of one value; a line that only pushes
+    f = np.array([[10, 10, 10, 0], [5, 5, 5, 0], [R.INF] * 4, [R.INF, 7, R.INF, R.INF], [0, 0, 0, 0]], np.int64)
+    depth, pops, stacks = R.envelope_stats(f)
+    assert depth.tolist() == [3, 3, 0, 1, 4] and pops.tolist() == [3, 2, 0, 0, 0]
+    assert [R.final_stack(*stacks, line) for line in range(5)] == [[(3, 0)], [(0, 0), (3, 1)], [], [(1, 0)], [(0, 0), (1, 1), (2, 2), (3, 3)]]
+    assert R.envelope(f).tolist() == [[9, 4, 1, 0], [5, 4, 1, 0], [R.INF] * 4, [8, 7, 8, 11], [0, 0, 0, 0]]
+
+
+def test_deep_stack_grid_reaches_its_depth_and_pop_runs():
+    fy, fz = R.pass_inputs(R.deep_stack_labels())
+    assert fy.shape == (2100, 1024) and fz.shape == (2100 * 1024, 1)
+    depth, pops, _ = R.envelope_stats(fy)
+    assert int(depth.min()) == 1023 and int(depth.max()) == 1024
+    assert int((pops >= 1000).sum()) == 1099 and int(((pops >= 1) & (pops <= 100)).sum()) == 100 and int(pops.max()) == 1023
+    fy, fz = R.pass_inputs(R.deep_stack_labels(along_z=True))
+    assert fz.shape == (2100, 1024) and np.array_equal(R.envelope_stats(fz)[0], depth)
+
+
 class DistStub(StubVoxelizer):
     def distance_dense(self, labels_ptr, label_strides, dst_ptr, fmt, dst_strides, dims):
         self.calls.append(("distance", fmt, tuple(label_strides), tuple(dst_strides), tuple(dims)))

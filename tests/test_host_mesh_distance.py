@@ -133,6 +133,33 @@ def test_culled_reference_equals_unculled(band, ss):
     assert (got[0] < band).any() and (got[0] == np.float32(band)).any()
 
 
+def test_band_is_a_float32():
+    """The call takes the band as a float and widens that: 2.6 means float32(2.6) = 2.599999904..., which is the distance of
+    voxel (1, 1, 0) from the plane z = float32(3.1), so that voxel is at the band, not inside it."""
+    z = np.float32(3.1)
+    sv = np.array([[[0, 0, z], [4, 0, z], [0, 4, z]]], np.float32)
+    a = R.mesh_distance(sv, 8, 1, 2.6, False)
+    b = R.mesh_distance(sv, 8, 1, float(np.float32(2.6)), False)
+    assert np.array_equal(a[0].view(np.int32), b[0].view(np.int32)) and np.array_equal(a[1], b[1])
+    assert a[1][0, 1, 1] == -1 and a[0][0, 1, 1] == np.float32(2.6)
+    assert int((a[0] < np.float32(2.6)).sum()) == int((a[1] >= 0).sum()) == 116
+    pts = np.array([[1, 1, 0], [1, 1, 1], [7, 7, 7]])
+    for band in (2.6, float(np.float32(2.6))):
+        v, i = R.point_distance(pts, sv, 1, band)
+        assert i.tolist() == [-1, 0, -1] and v.tolist() == [np.float32(2.6), np.float32(z - np.float32(1.5)), np.float32(2.6)]
+    lo, hi = R.dilated_aabb(sv, 2.6, 2)
+    assert lo[0, 0] == -(np.float64(np.float32(2.6)) * 2 + 2) and hi[0, 2] == np.float64(z) + (np.float64(np.float32(2.6)) * 2 + 2)
+
+
+def test_threshold_band():
+    for D in (6.25, 2.0, 7.3, 1e-6, 63.999):
+        f, narrow = R.threshold_band(D)
+        g = np.nextafter(f, np.float32(0))
+        assert f.dtype == np.float32 and np.float64(f) * np.float64(f) > D >= np.float64(g) * np.float64(g)
+        assert narrow == (np.float64(np.float32(f * f)) <= D)
+    assert R.threshold_band(6.25)[0] == np.nextafter(np.float32(2.5), np.float32(3))
+
+
 def test_reference_box_equals_grid_and_sign():
     sv = fill_ref.sample_vertices(fill_ref.weld(meshes.uv_sphere(10)), _xform(20))
     G, band = 20, 2.5
@@ -214,6 +241,7 @@ def test_mesh_distance_max_layers_origins():
     (dict(band=1, out=torch.zeros((4, 4, 4)), closest=torch.zeros((4, 4, 5), dtype=torch.int32)), ValueError),
     (dict(band=1, supersampling=3), ValueError),
     (dict(band=1, max_layers=0), ValueError),
+    (dict(band=1e-46), ValueError),   # (0 as a float32: refused here like every other bad band, not by the device call)
 ])
 def test_mesh_distance_rejects(kw, exc):
     dv = MeshDistStub()

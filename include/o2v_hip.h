@@ -339,6 +339,63 @@ int o2v_hip_mesh_distance_dense(o2v_hip_ctx *ctx, const o2v_hip_params *params, 
 /* The device times (ms) of the last o2v_hip_mesh_distance_dense call's stages: binning, parity (0 unsigned), distance. */
 int o2v_hip_mesh_distance_times(const o2v_hip_ctx *ctx, float out_ms[3]);
 
+/* ---- surface extraction ------------------------------------------------------------------------
+ *
+ * The level set of a dense float32 grid as an indexed triangle mesh, by surface nets: one vertex per cell the surface passes
+ * through, one quad (two triangles) per grid edge it crosses.  The mesh comes out in the shape o2v_hip_set_triangles_device
+ * takes (positions [V][3] float32, faces [T][3] int32), in device memory the caller owns.
+ *
+ * Input: a grid f of dims = (nx, ny, nz) float32 samples in device memory, sample (x, y, z) at field[x * strides[0] +
+ * y * strides[1] + z * strides[2]] (elements, any order), a finite level, and origin = (ox, oy, oz) in voxels.  Sample (x, y, z)
+ * stands for the voxel centre (ox + x + 0.5, oy + y + 0.5, oz + z + 0.5): the voxel space of the sections above with
+ * supersampling 1.
+ *   inside(x, y, z) = f(x, y, z) < level (a NaN is outside; -inf inside, +inf outside).
+ *   Cells: (i, j, k) with 0 <= i < nx - 1, 0 <= j < ny - 1, 0 <= k < nz - 1; its corner (a, b, c), each 0 or 1, is sample
+ *   (i + a, j + b, k + c).  A cell is active if its eight corners are not all inside and not all outside.  A grid with a dim
+ *   of 1 has no cells.
+ *   Vertices: one per active cell, numbered in ascending cell order (k * (ny - 1) + j) * (nx - 1) + i.  Its position, all in
+ *   float32, op by op, no FMA:
+ *     the cell's 12 edges in this order: the four x edges (0,b,c)-(1,b,c) for (b, c) = (0,0), (1,0), (0,1), (1,1); the four y
+ *     edges (a,0,c)-(a,1,c) for (a, c) in the same order; the four z edges (a,b,0)-(a,b,1) for (a, b) in the same order; p is
+ *     always the end with the lower coordinate, q the other;
+ *     an edge crosses if inside(p) != inside(q); then t = (level - f(p)) / (f(q) - f(p)), and t = 0.5f unless t >= 0 && t <= 1
+ *     (this takes care of infinities and NaN); its crossing point, local to the cell, is p's (a, b, c) as floats with the
+ *     component along the edge replaced by t;
+ *     s = (0, 0, 0), then the crossing points are added component by component in edge order; n = their number;
+ *     local = s / (float) n; position = ((float) (o + cell index) + 0.5f) + local per axis, (x, y, z) order in memory.
+ *     The divisions are the correctly rounded float32 ones.
+ *   Faces: for every sample c = (x, y, z) and axis ax in 0, 1, 2 such that the edge from c to c + e_ax exists, crosses, and is
+ *   interior across (with u = (ax + 1) % 3, v = (ax + 2) % 3: 1 <= c[u] <= n_u - 2 and 1 <= c[v] <= n_v - 2), one quad of the four
+ *   cells around the edge: c0 = c - e_u - e_v, c1 = c - e_v, c2 = c, c3 = c - e_u (a cell is named by its lowest corner; all four
+ *   are active because they contain the edge).  If inside(c) the quad is (c0, c1, c2, c3), else (c0, c3, c2, c1): the normal
+ *   points from inside to outside.  It is written as the two triangles (q0, q1, q2), (q0, q2, q3) of int32 vertex numbers.  Quads
+ *   come in ascending order of ((z * ny + y) * nx + x) * 3 + ax.
+ *   A crossing edge on the border of the box has fewer than four cells and gives no quad: a surface that leaves the box is open
+ *   there, and a vertex of a border cell may be used by no face.
+ *
+ * The caller cannot know the output's size beforehand, so there are two calls.  o2v_hip_surface_count classifies the grid
+ * (its only pass over the field), keeps what the second call needs in scratch of the context - per 64 samples along x their
+ * sign bits, their active cells and two 16-bit prefixes, per 256 such words two offsets: 20 bytes per 64 samples, not an index
+ * per cell - and returns the two totals.  o2v_hip_surface_write must follow a count with the same field, strides, dims and level
+ * (else O2V_HIP_ERR_BAD_ARGUMENT, "no matching o2v_hip_surface_count"; another count, refused or not, replaces the last one) and
+ * fills positions and faces, contiguous; it may be repeated.  The field must not change between the two calls; if it does, the
+ * positions may be meaningless, but every index written is below the counted vertices and nothing is written outside the two
+ * arrays: the topology comes from the kept bits, only t and the corner values from the field.
+ * Refused before any launch: null arguments (positions or faces may be null only where the count is 0), zero dims, a level
+ * that is not finite, capacities below the counted totals, positions / faces overlapping each other or the field, a pointer
+ * that is not device memory of the context's device with its whole extent inside its allocation (O2V_HIP_ERR_BAD_ARGUMENT); a
+ * dim above 65 536, or origin[a] + dims[a] above 65 536 (positions stay exact to 2^-7 voxel), or more than 2^31 - 1 vertices
+ * (O2V_HIP_ERR_LIMIT).  A failed scratch allocation returns O2V_HIP_ERR_OUT_OF_MEMORY and the context stays usable.  Both calls
+ * run on the context's stream and return when their results have landed (the caller must have finished writing the field). */
+int o2v_hip_surface_count(o2v_hip_ctx *ctx, const float *field, const uint64_t strides[3], const uint32_t dims[3], float level,
+                          uint64_t *out_vertices, uint64_t *out_triangles);
+int o2v_hip_surface_write(o2v_hip_ctx *ctx, const float *field, const uint64_t strides[3], const uint32_t dims[3], float level,
+                          const uint32_t origin[3], float *positions, uint64_t vertex_capacity, int32_t *faces,
+                          uint64_t triangle_capacity);
+/* The device times (ms) of the stages: classify, count + scan (the last o2v_hip_surface_count), vertices, faces (the last
+ * o2v_hip_surface_write; 0 after a count). */
+int o2v_hip_surface_times(const o2v_hip_ctx *ctx, float out_ms[4]);
+
 int o2v_hip_get_timings(const o2v_hip_ctx *ctx, o2v_hip_timings *out);
 /* Per-kernel device times of the last o2v_hip_voxelize call made with O2V_HIP_FLAG_KERNEL_TIMES (else none): up to
  * max_entries entries are written, *out_count receives how many there are. */

@@ -9,7 +9,8 @@
 The mesh goes to the device context without a host copy (o2v_hip_set_triangles_device) and the voxels come back as a dense
 tensor written on the device (o2v_hip_write_dense); nothing of either crosses to the host.  Distance grids (fmt "dist2" /
 "sdf", and distance_transform on any label tensor) come from o2v_hip_distance_dense; mesh_distance is the
-narrow-band distance to the triangles themselves (o2v_hip_mesh_distance_dense).
+narrow-band distance to the triangles themselves (o2v_hip_mesh_distance_dense); extract_surface turns a
+distance grid back into an indexed mesh (o2v_hip_surface_count / _write).
 
 torch is imported first on purpose: the library must bind to the HIP runtime torch loaded (a process that loaded the library
 before torch holds two separate runtime copies, and this module refuses to work there).
@@ -33,6 +34,7 @@ DISTANCE_FORMATS = {  # name: (o2v_hip_distance_dense format, tensor dtype)
 STRATEGIES = {"max": hip.STRATEGY_MAX, "blend": hip.STRATEGY_BLEND}
 MAX_SAMPLES = 65535  # samples per axis of one pass (x / y tiles above that are not supported here)
 MAX_BAND = 32.0      # mesh_distance: the widest band, in voxels
+MAX_SURFACE_EXTENT = 65536  # extract_surface: origin + shape per axis
 
 
 def _require_shared_runtime():
@@ -313,3 +315,50 @@ def mesh_distance(dv, resolution, *, band, signed=True, out=None, closest=None, 
                                _strides(o), _ptr(c), None if c is None else _strides(c), supersampling=supersampling,
                                unit_transform=unit_transform, bounds=bounds)
     return (out, closest, origin) if want_closest else (out, origin)
+
+
+def extract_surface(dv, field, level=0.0, *, origin=(0, 0, 0), transform=None, supersampling=1):
+    """The level set `level` of `field` as an indexed triangle mesh, by surface nets: one vertex per
+    cell of 2 x 2 x 2 samples the surface passes through, one quad (two triangles) per grid edge it crosses.  Returns
+    (positions float32 [V, 3], faces int32 [T, 3]), new contiguous tensors in the shape set_mesh takes; (0, 3) both when there is
+    no surface.  Inside is field < level; the normals point from inside to outside.
+
+    field:      a float32 3-D tensor [z, y, x] of any strides on the voxelizer's device (what mesh_distance and fmt="sdf"
+                return); it is only read.  A surface that leaves the box is open there.
+    origin:     (ox, oy, oz), the one the field came with: sample (x, y, z) is the voxel centre origin + (x, y, z) + 0.5.
+    transform:  None: positions in voxel space.  dv.transform() (the 12 floats, model to sample space): positions in model
+                space, A^-1 (supersampling * p), computed in float64 and rounded once."""
+    _require_shared_runtime()
+    if isinstance(level, bool) or not isinstance(level, numbers.Real) or not float("-inf") < float(level) < float("inf"):
+        raise ValueError(f"level must be a finite number, not {level!r}")
+    level = hip.C.c_float(float(level)).value
+    if not float("-inf") < level < float("inf"):
+        raise ValueError("level is not finite as a float32")
+    if supersampling not in (1, 2):
+        raise ValueError("supersampling must be 1 or 2")
+    device = _device(dv)
+    _check_grid(field, "field", torch.float32, device)
+    if 0 in field.shape:
+        raise ValueError("field has an empty dimension")
+    origin = tuple(int(v) for v in origin)
+    if len(origin) != 3 or any(v < 0 for v in origin):
+        raise ValueError(f"origin {origin} must be three voxel coordinates, none negative")
+    if any(o + n > MAX_SURFACE_EXTENT for o, n in zip(origin, field.shape[::-1])):
+        raise ValueError(f"origin {origin} + field's extent {tuple(field.shape[::-1])} [x, y, z] is above {MAX_SURFACE_EXTENT}")
+    if transform is not None:
+        transform = torch.as_tensor(transform, dtype=torch.float64).reshape(-1)
+        if transform.numel() != 12:
+            raise ValueError("transform must hold 12 numbers: a row-major 3 x 3 matrix, then the translation")
+    nz, ny, nx = field.shape
+    args = (field.data_ptr(), _strides(field), (nx, ny, nz), level)
+    _sync(device)   # (the caller's writes to field have landed)
+    n_vertices, n_triangles = dv.surface_count(*args)
+    positions = torch.empty((n_vertices, 3), dtype=torch.float32, device=device)
+    faces = torch.empty((n_triangles, 3), dtype=torch.int32, device=device)
+    if n_vertices:
+        dv.surface_write(*args, origin, positions.data_ptr(), n_vertices, _ptr(faces) if n_triangles else None, n_triangles)
+    if transform is not None and n_vertices:
+        inverse = torch.linalg.inv(transform[:9].reshape(3, 3)).to(device)   # (3 x 3, on the host)
+        p = positions.to(torch.float64) * supersampling - transform[9:].to(device)
+        positions = (p[:, None, :] * inverse[None, :, :]).sum(dim=2).to(torch.float32).contiguous()
+    return positions, faces

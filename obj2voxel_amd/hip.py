@@ -119,6 +119,10 @@ def _bind():
     L.o2v_hip_mesh_distance_dense.argtypes = [C.c_void_p, C.POINTER(_Params), C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p]
     L.o2v_hip_mesh_distance_times.argtypes = [C.c_void_p, C.c_void_p]
+    L.o2v_hip_surface_count.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.o2v_hip_surface_write.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_uint64,
+                                        C.c_void_p, C.c_uint64]
+    L.o2v_hip_surface_times.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_max_slab_layers.argtypes = [C.c_void_p, C.POINTER(_Params), C.POINTER(C.c_uint32)]
     return L
 
@@ -263,8 +267,8 @@ class DeviceVoxelizer:
         """o2v_hip_distance_scratch_bytes: the context scratch a distance_dense call over dims (x, y, z) needs."""
         return int(self._L.o2v_hip_distance_scratch_bytes(_u32x3(dims), fmt))
 
-    def _stage_times(self, name):   # (o2v_hip_distance_times, o2v_hip_mesh_distance_times)
-        ms = (C.c_float * 3)()
+    def _stage_times(self, name, n=3):   # (o2v_hip_distance_times, o2v_hip_mesh_distance_times, o2v_hip_surface_times)
+        ms = (C.c_float * n)()
         self._check(getattr(self._L, name)(self._ctx, ms), name)
         return tuple(float(v) for v in ms)
 
@@ -286,6 +290,27 @@ class DeviceVoxelizer:
         """o2v_hip_mesh_distance_times: the device times (ms) of the last mesh_distance_dense call's binning, parity and
         distance stages (parity 0 when unsigned)."""
         return self._stage_times("o2v_hip_mesh_distance_times")
+
+    def surface_count(self, field_ptr, strides, dims, level):
+        """o2v_hip_surface_count: (vertices, triangles) of the level set `level` of the float32 grid at device address
+        field_ptr (strides in elements and dims per axis x, y, z), by surface nets; what surface_write needs stays in the
+        context."""
+        v, t = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.o2v_hip_surface_count(self._ctx, field_ptr, _u64x3(strides), _u32x3(dims), float(level), C.byref(v), C.byref(t)),
+                    "o2v_hip_surface_count")
+        return v.value, t.value
+
+    def surface_write(self, field_ptr, strides, dims, level, origin, positions_ptr, vertex_capacity, faces_ptr, triangle_capacity):
+        """o2v_hip_surface_write: the mesh surface_count counted for the same field, strides, dims and level, into float32
+        positions [vertices, 3] (voxel space, sample (x, y, z) at origin + (x, y, z) + 0.5) and int32 faces [triangles, 3] at
+        device addresses, contiguous."""
+        self._check(self._L.o2v_hip_surface_write(self._ctx, field_ptr, _u64x3(strides), _u32x3(dims), float(level), _u32x3(origin), positions_ptr,
+                                                  vertex_capacity, faces_ptr, triangle_capacity), "o2v_hip_surface_write")
+
+    def surface_times(self):
+        """o2v_hip_surface_times: the device times (ms) of the last surface_count call's classify and count + scan stages and
+        of the last surface_write call's vertex and face stages."""
+        return self._stage_times("o2v_hip_surface_times", 4)
 
     def set_textures(self, textures):
         """textures: sequence of (uint8 [h, w, c] pixels, wrap) with c in (3, 4)."""

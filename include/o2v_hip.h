@@ -346,7 +346,8 @@ int o2v_hip_mesh_distance_times(const o2v_hip_ctx *ctx, float out_ms[3]);
  * takes (positions [V][3] float32, faces [T][3] int32), in device memory the caller owns.
  *
  * Input: a grid f of dims = (nx, ny, nz) float32 samples in device memory, sample (x, y, z) at field[x * strides[0] +
- * y * strides[1] + z * strides[2]] (elements, any order), a finite level, and origin = (ox, oy, oz) in voxels.  Sample (x, y, z)
+ * y * strides[1] + z * strides[2]] (elements, any order; the field is only read, so a stride may be 0 and samples may share
+ * elements, as in an expanded tensor), a finite level, and origin = (ox, oy, oz) in voxels.  Sample (x, y, z)
  * stands for the voxel centre (ox + x + 0.5, oy + y + 0.5, oz + z + 0.5): the voxel space of the sections above with
  * supersampling 1.
  *   inside(x, y, z) = f(x, y, z) < level (a NaN is outside; -inf inside, +inf outside).

@@ -93,7 +93,12 @@ def case_strides():
     check(dv, wide[:, :, ::2], 0.5, (2, 3, 4), "every second sample")
     big = dev(R.sphere_field((60, 64, 90), 25.5))
     check(dv, big[7:41, 5:60, 13:88], 0.0, (13, 5, 7), "a box of a larger tensor")
-    print("compared", n + 3)
+    # samples that share elements (the field is only read): a layer expanded along z, a plane expanded along x
+    layer = dev(f[17:18]).expand(40, -1, -1)
+    assert layer.stride(0) == 0 and check(dv, layer, 0.5, (2, 3, 4), "stride 0 along z")[0] > 0
+    plane = dev(f[:, :, 30:31]).expand(-1, -1, 70)
+    assert plane.stride(2) == 0 and check(dv, plane, 0.5, (2, 3, 4), "stride 0 along x")[0] > 0
+    print("compared", n + 5)
 
 
 def case_rounding():
@@ -296,8 +301,209 @@ def case_bench_mesh():
               "ranges of 12 layers; times", dv.surface_times())
 
 
+# ---- the documented limits, reached with small fields: a field is only read, so its samples may share elements ----------------
+
+TURN = 2 ** 20    # kSurfMaxGrid: the workgroups of k_surf_count / _vertices / _faces; block b is taken by workgroup b % TURN
+BLOCK = 256       # kBlock: words per block
+WORKERS = 8       # threads of the reference over a grid of 10^9 samples
+
+
+def strided(base, dims, sx, s1, s2):
+    """f(x, y, z) = base[sx x + s1 y + s2 z] as [z, y, x]: a torch view of a device tensor or a numpy view of a host array;
+    neither holds the grid."""
+    nx, ny, nz = dims
+    assert sx * (nx - 1) + s1 * (ny - 1) + s2 * (nz - 1) < len(base)
+    if isinstance(base, torch.Tensor):
+        return torch.as_strided(base, (nz, ny, nx), (s2, s1, sx))
+    e = base.strides[0]
+    return np.lib.stride_tricks.as_strided(base, (nz, ny, nx), (s2 * e, s1 * e, sx * e), writeable=False)
+
+
+def turns_base(n, seed):
+    """n float32: stretches of 300 to 3 000 elements, in turn quiet (all above the level 0.125) and busy (a share p of the
+    samples below it, p drawn per stretch between 1e-4 and 8e-3; in every eighth busy stretch half of the first 150 samples,
+    for blocks with more outputs than threads)."""
+    rng = np.random.default_rng(seed)
+    base = (0.3 + np.abs(rng.normal(size=n))).astype(F)
+    at, stretch = 0, 0
+    while at < n:
+        length = int(rng.integers(300, 3000))
+        if stretch % 2:
+            part = base[at:at + length]
+            part[rng.random(len(part)) < float(np.exp(rng.uniform(np.log(1e-4), np.log(8e-3))))] *= F(-1)
+            if stretch % 16 == 1:
+                part[:150][rng.random(len(part[:150])) < 0.5] *= F(-1)
+        at, stretch = at + length, stretch + 1
+    return base
+
+
+def turn_kinds(per_block):
+    """How many workgroups with two turns have output in neither turn, in the second only, in the first only, in both: [4]."""
+    second = per_block[TURN:] > 0
+    first = per_block[:len(second)] > 0
+    return np.bincount(2 * first.astype(np.int64) + second, minlength=4)
+
+
+def case_in_turns():
+    """More than 2^20 blocks of words: the workgroups with a low number take two blocks, one after the other.  The grid is a
+    strided view of a 1-D tensor of 190 000 floats (the field is only read, so its samples may share elements); what it costs is
+    the context's 20 bytes per word.  nx = 3 keeps quads along all three axes at a word per row; ny = nz = 18 400 gives 1.26 x 2^20
+    blocks; the base's density was chosen for about 10 M vertices, at which comparing every output against the reference takes
+    about as long as the reference's passes over the 1 G samples alone."""
+    import time
+    t_start = time.time()
+    dv = hip.DeviceVoxelizer(0)
+    level, origin = 0.125, (40000, 123, 7)
+    ny = nz = 18400
+    host = turns_base(190000, 2028)
+    base = torch.from_numpy(host).to(DEV)
+    free0, total = torch.cuda.mem_get_info(DEV)
+    ins = host < F(level)
+
+    # the smaller run first: an x stride of 2 (k_surf_vertices<false>), totals and seeded ranges of 12 layers
+    dims, (sx, s1, s2) = (5, ny, nz), (2, 3, 7)
+    n_blocks = -(-ny * nz // BLOCK)
+    assert n_blocks > TURN and 1.25 * 2 ** 28 <= ny * nz <= 1.5 * 2 ** 28
+    v_layers, q_layers, v_blocks, q_blocks = R.grid_counts(R.row_tables(ins, dims[0], sx, s1, s2), ny, nz, s1, s2, workers=WORKERS)
+    kinds_v, kinds_q = turn_kinds(v_blocks), turn_kinds(q_blocks)
+    assert kinds_v.min() >= 1000 and kinds_q.min() >= 1000, (kinds_v, kinds_q)
+    V, T = int(v_layers.sum()), 2 * int(q_layers.sum())
+    p, f = dense.extract_surface(dv, strided(base, dims, sx, s1, s2), level, origin=origin)
+    assert (len(p), len(f)) == (V, T), (len(p), V, len(f), T)
+    assert int(f.min()) >= 0 and int(f.max()) < V
+    got_p, got_f = p.cpu().numpy(), f.cpu().numpy()
+    view = strided(host, dims, sx, s1, s2)
+    rng = np.random.default_rng(77)
+    first_late = TURN * BLOCK // ny + 1          # the first layer whose blocks are all taken in a second turn
+    starts = sorted(int(z) for z in np.concatenate([rng.choice(first_late - 12, 4, replace=False),
+                                                    first_late + rng.choice(nz - 13 - first_late, 3, replace=False), [nz - 13]]))
+    assert sum(z * ny // BLOCK >= TURN for z in starts) >= 4 and len(starts) == 8
+    nv = nt = 0
+    for z0 in starts:
+        v0, want_p, t0, want_f = R.extract_layers(view, level, origin, z0, z0 + 12, v_layers, q_layers)
+        assert len(want_p) > 0 and len(want_f) > 0, z0
+        assert np.array_equal(got_p[v0:v0 + len(want_p)].view(np.uint32), want_p.view(np.uint32)), ("x stride 2", z0)
+        assert np.array_equal(got_f[t0:t0 + len(want_f)], want_f), ("x stride 2", z0)
+        nv, nt = nv + len(want_p), nt + len(want_f)
+    print("in_turns x stride 2: dims", dims, "strides", (sx, s1, s2), "blocks", n_blocks, "vertices", V, "triangles", T, "workgroups with two turns"
+          " (neither turn with output, the second only, the first only, both): vertices", kinds_v.tolist(), "quads", kinds_q.tolist(), "compared", nv, "vertices and", nt,
+          "triangles in 8 ranges of 12 layers from", starts, "times", dv.surface_times(), "wall %.1f s" % (time.time() - t_start), flush=True)
+    del p, f, got_p, got_f
+
+    # every output compared: x stride 1 (k_surf_vertices<true>)
+    t_main = time.time()
+    dims, (sx, s1, s2) = (3, ny, nz), (1, 3, 5)
+    tables = R.row_tables(ins, dims[0], sx, s1, s2)
+    t_layers, tq_layers, v_blocks, q_blocks = R.grid_counts(tables, ny, nz, s1, s2, workers=WORKERS)
+    kinds_v, kinds_q = turn_kinds(v_blocks), turn_kinds(q_blocks)
+    assert kinds_v.min() >= 1000 and kinds_q.min() >= 1000, (kinds_v, kinds_q)
+    v_layers, q_layers = R.counts_per_layer_slabs(strided(ins, dims, sx, s1, s2), 64, WORKERS)
+    assert np.array_equal(v_layers, t_layers) and np.array_equal(q_layers, tq_layers)
+    V, T = int(v_layers.sum()), 2 * int(q_layers.sum())
+    assert 2_000_000 <= V <= 40_000_000, V
+    t_counts = time.time()
+    p, f = dense.extract_surface(dv, strided(base, dims, sx, s1, s2), level, origin=origin)
+    times = dv.surface_times()
+    used = total - torch.cuda.mem_get_info(DEV)[0]
+    assert (len(p), len(f)) == (V, T), (len(p), V, len(f), T)
+    assert int(f.min()) >= 0 and int(f.max()) < V
+    got_p, got_f = p.cpu().numpy(), f.cpu().numpy()
+    t_device = time.time()
+    view = strided(host, dims, sx, s1, s2)
+    v_end = t_end = 0
+    chunks = R.layer_chunks(nz, 64)
+    for at in range(0, len(chunks), 4 * WORKERS):   # (a few ranges at a time: the host holds their meshes only)
+        some = chunks[at:at + 4 * WORKERS]
+        wants = R.each(lambda z0, z1: R.extract_layers(view, level, origin, z0, z1, v_layers, q_layers), some, WORKERS)
+        for (z0, z1), (v0, want_p, t0, want_f) in zip(some, wants):
+            assert v0 <= v_end and t0 == t_end, (z0, v0, v_end, t0, t_end)
+            bad = (got_p[v0:v0 + len(want_p)].view(np.uint32) != want_p.view(np.uint32)).any(axis=1)
+            assert not bad.any(), ("vertices", z0, z1, int(bad.sum()), "first at", v0 + int(np.argmax(bad)), "of block",
+                                   int(np.searchsorted(np.cumsum(v_blocks), v0 + int(np.argmax(bad)), side="right")))
+            bad = (got_f[t0:t0 + len(want_f)] != want_f).any(axis=1)
+            assert not bad.any(), ("triangles", z0, z1, int(bad.sum()), "first at", t0 + int(np.argmax(bad)), "of block",
+                                   int(np.searchsorted(np.cumsum(q_blocks), (t0 + int(np.argmax(bad))) // 2, side="right")))
+            v_end, t_end = v0 + len(want_p), t0 + len(want_f)
+    assert (v_end, t_end) == (V, T)
+    print("in_turns: dims", dims, "strides", (sx, s1, s2), "origin", origin, "blocks", n_blocks, "of which", n_blocks - TURN, "in a second turn; vertices", V,
+          "triangles", T, "all compared; most per block", int(v_blocks.max()), "vertices", int(q_blocks.max()), "quads; workgroups with two turns"
+          " (neither turn with output, the second only, the first only, both): vertices", kinds_v.tolist(), "quads", kinds_q.tolist(), "times", times,
+          "device memory in use after the call %.2f GB (%.2f GB before the context's arrays)" % (used / 1e9, (total - free0) / 1e9),
+          "wall: counts %.1f s, device and copy %.1f s, compare %.1f s, case %.1f s" %
+          (t_counts - t_main, t_device - t_counts, time.time() - t_device, time.time() - t_start))
+
+
+def checkerboard(dims):
+    """f = (-1)^(x + y + z) as a view with strides (1, 1, 1) of an alternating device tensor: every cell is active."""
+    base = torch.ones(sum(dims), device=DEV)
+    base[1::2] = -1
+    return base
+
+
+def case_vertex_limit():
+    """2^31 vertices are refused, 2^31 - 2^21 are counted and their triangles are above 2^32: count only (the mesh would be over
+    150 GB).  The limit itself, 2^31 - 1, is a prime and no box has that many cells, so which of > and >= the check uses is not
+    tested here."""
+    dv = hip.DeviceVoxelizer(0)
+    st = (1, 1, 1)
+    dims = (2049, 1025, 1025)
+    base = checkerboard(dims)
+    torch.cuda.synchronize()
+    assert R.checkerboard_counts(*dims)[0] == 2 ** 31
+    try:
+        dv.surface_count(base.data_ptr(), st, dims, 0.0)
+        raise AssertionError("2^31 vertices were accepted")
+    except hip.DeviceError as e:
+        assert "code 5" in str(e) and str(2 ** 31) + " vertices" in str(e), str(e)
+        print(e)
+    out = torch.full((64,), 7, dtype=torch.int32, device=DEV)
+    torch.cuda.synchronize()
+    msg = expect_code3(lambda: dv.surface_write(base.data_ptr(), st, dims, 0.0, (0, 0, 0), out.data_ptr(), 1, out.data_ptr() + 128, 1),
+                       "write after a refused count")
+    assert "no matching o2v_hip_surface_count" in msg, msg
+    torch.cuda.synchronize()
+    assert bool((out == 7).all())
+    # the context still works
+    check(dv, dev(R.sphere_field(24, 8.3)), 0.0, (1, 2, 3), "after the refusal")
+    dims = (2049, 1025, 1024)
+    want_v, want_q = R.checkerboard_counts(*dims)
+    assert want_v == 2 ** 31 - 2 ** 21 and 2 * want_q > 2 ** 32 and want_q > 2 ** 32
+    V, T = dv.surface_count(base.data_ptr(), st, dims, 0.0)
+    assert (V, T) == (want_v, 2 * want_q), (V, T, want_v, 2 * want_q)
+    print("vertex_limit: dims (2049, 1025, 1025) refused at", 2 ** 31, "vertices; dims", dims, "counted", V, "vertices,", T // 2, "quads,", T,
+          "triangles; times", dv.surface_times())
+
+
+def case_full_blocks():
+    """Blocks with 2^14 vertices and 3 x 2^14 quads, the most the packed 16-bit prefixes of a block are documented for; and the
+    longest axes: 65 536 samples along x, y and z, positions up to 65 535.5."""
+    dv = hip.DeviceVoxelizer(0)
+    dims = (65536, 4, 4)
+    field = strided(checkerboard(dims), dims, 1, 1, 1)
+    v_blocks, q_blocks = R.per_block_counts(R.inside(field.cpu().numpy(), 0.0))
+    assert int(v_blocks.max()) == 2 ** 14 and int(q_blocks.max()) == 3 * 2 ** 14
+    v, tris = check(dv, field, 0.0, (0, 0, 0), "full blocks")
+    assert (v, tris) == (R.checkerboard_counts(*dims)[0], 2 * R.checkerboard_counts(*dims)[1])
+    print("full_blocks: dims", dims, "vertices", v, "triangles", tris, "blocks with 16 384 vertices:", int((v_blocks == 2 ** 14).sum()),
+          "with 49 152 quads:", int((q_blocks == 3 * 2 ** 14).sum()))
+    rng = np.random.default_rng(65536)
+    for dims in ((65536, 2, 2), (2, 65536, 2), (2, 2, 65536), (65536, 3, 3)):
+        nx, ny, nz = dims
+        z, y, x = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+        smooth = (np.sin(0.05 * (x + 2 * y + 3 * z)) + 0.2 * np.cos(0.31 * (x - y + z)) + 0.4 * np.sin(1.3 * x + 2.1 * y + 0.7 * z)).astype(F)
+        noise = rng.normal(size=(nz, ny, nx)).astype(F)
+        for name, f in (("smooth", smooth), ("noise", noise)):
+            t = dev(f)
+            v, tris = check(dv, t, 0.0, (0, 0, 0), (name, dims))
+            p, _ = dense.extract_surface(dv, t, 0.0)
+            top = float(p.max())
+            assert v > 1000 and 65500 < top <= 65535.5 and (tris > 0) == (min(dims) > 2), (name, dims, v, tris, top)
+            print("longest axes:", name, dims, "vertices", v, "triangles", tris, "largest coordinate", top)
+
+
 CASES = {"shapes": case_shapes, "strides": case_strides, "rounding": case_rounding, "pipeline": case_pipeline, "dense_field": case_dense_field,
-         "refusals": case_refusals, "bench_mesh": case_bench_mesh}
+         "refusals": case_refusals, "bench_mesh": case_bench_mesh, "in_turns": case_in_turns, "vertex_limit": case_vertex_limit,
+         "full_blocks": case_full_blocks}
 
 if __name__ == "__main__":
     CASES[sys.argv[1]]()

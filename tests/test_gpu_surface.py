@@ -47,3 +47,24 @@ def test_bench_mesh_sampled():
     out = _run("bench_mesh", timeout=900)
     print(out)
     assert out.count("bench_mesh level") == 2
+
+
+def test_strided_grid_in_turns():
+    """More than 2^20 blocks of words: k_surf_count, k_surf_vertices and k_surf_faces take their blocks in two turns."""
+    # (timeouts of the three cases below: three times their measured wall of 13.5 s, 2.1 s and 3.1 s, rounded up; a child's start,
+    # the import of torch and the device's, is 2 s of each)
+    out = _run("in_turns", timeout=60)
+    print(out)
+    assert "in_turns x stride 2:" in out and "in_turns: dims" in out and "all compared" in out
+
+
+def test_vertex_limit_and_totals_above_32_bits():
+    out = _run("vertex_limit", timeout=30)
+    print(out)
+    assert "vertex_limit: dims" in out
+
+
+def test_full_blocks_and_longest_axes():
+    out = _run("full_blocks", timeout=30)
+    print(out)
+    assert "full_blocks: dims" in out and out.count("longest axes:") == 8

@@ -118,6 +118,115 @@ def test_single_cell_and_flat_grids():
         assert p.shape == (0, 3) and f.shape == (0, 3) and p.dtype == F and f.dtype == np.int32
 
 
+# ---- the pieces the large device cases are built from: layer ranges, strided views of a 1-D array, closed forms ---------------
+
+def strided_view(base, dims, sx, s1, s2):
+    """f(x, y, z) = base[sx x + s1 y + s2 z] as an array [z, y, x] that shares base's memory."""
+    nx, ny, nz = dims
+    assert sx * (nx - 1) + s1 * (ny - 1) + s2 * (nz - 1) < len(base)
+    e = base.strides[0]
+    return np.lib.stride_tricks.as_strided(base, (nz, ny, nx), (s2 * e, s1 * e, sx * e), writeable=False)
+
+
+STRIDED = [((5, 40, 37), 1, 3, 5), ((3, 70, 29), 1, 5, 3), ((6, 33, 41), 2, 3, 7), ((2, 50, 50), 1, 2, 3), ((8, 2, 90), 3, 5, 2),
+           ((4, 90, 2), 1, 1, 1), ((7, 31, 30), 1, 0, 4), ((7, 31, 30), 0, 3, 1)]
+
+
+def strided_base(dims, sx, s1, s2, seed):
+    rng = np.random.default_rng(seed)
+    n = sx * (dims[0] - 1) + s1 * (dims[1] - 1) + s2 * (dims[2] - 1) + 1
+    base = (0.3 + np.abs(rng.normal(size=n))).astype(F)
+    busy = (np.arange(n) // 37) % 2 == 1                     # quiet and busy stretches
+    base[busy & (rng.random(n) < 0.3)] *= F(-1)
+    return base
+
+
+@pytest.mark.parametrize("dims,sx,s1,s2", STRIDED)
+def test_strided_views_count_and_extract_as_their_copies(dims, sx, s1, s2):
+    base = strided_base(dims, sx, s1, s2, 7)
+    view = strided_view(base, dims, sx, s1, s2)
+    copy = np.ascontiguousarray(view)
+    assert not view.flags.c_contiguous and np.shares_memory(view, base)
+    level, origin, nz = 0.125, (3, 4, 5), dims[2]
+    ins_view = strided_view(base < F(level), dims, sx, s1, s2)
+    v_layers, q_layers = R.counts_per_layer(ins_view)
+    v_copy, q_copy = R.counts_per_layer(R.inside(copy, level))
+    assert np.array_equal(v_layers, v_copy) and np.array_equal(q_layers, q_copy) and v_layers.sum() > 0
+    whole_p, whole_f = R.extract(copy, level, origin)
+    assert (len(whole_p), len(whole_f)) == (int(v_layers.sum()), 2 * int(q_layers.sum()))
+    for z0, z1 in ((0, nz - 1), (0, 1), (nz // 3, nz // 3 + 5), (nz - 2, nz - 1)):
+        if not 0 <= z0 < z1 < nz:
+            continue
+        got = R.extract_layers(view, level, origin, z0, z1, v_layers, q_layers)
+        want = R.extract_layers(copy, level, origin, z0, z1, v_layers, q_layers)
+        assert got[0] == want[0] and got[2] == want[2]
+        assert np.array_equal(got[1].view(np.uint32), want[1].view(np.uint32)) and np.array_equal(got[3], want[3])
+        assert np.array_equal(whole_p[got[0]:got[0] + len(got[1])].view(np.uint32), got[1].view(np.uint32))
+        assert np.array_equal(whole_f[got[2]:got[2] + len(got[3])], got[3])
+
+
+@pytest.mark.parametrize("n", [2, 3, 7, 64])
+def test_chained_overlapping_ranges_give_every_vertex_and_triangle(n):
+    """Ranges laid end to end (z1, then z1 again) would leave out the quads of sample layer z1; layer_chunks overlaps them."""
+    rng = np.random.default_rng(n)
+    f = rng.normal(size=(23, 14, 9)).astype(F)
+    level, origin = 0.2, (1, 2, 3)
+    want_p, want_f = R.extract(f, level, origin)
+    v_layers, q_layers = R.counts_per_layer(R.inside(f, level))
+    got_p, got_f = np.full(want_p.shape, np.nan, F), np.full(want_f.shape, -1, np.int32)
+    v_end = t_end = new_v = 0
+    chunks = R.layer_chunks(f.shape[0], n)
+    assert chunks[0][0] == 0 and chunks[-1][1] == f.shape[0] - 1 and all(b[0] == a[1] - 1 for a, b in zip(chunks, chunks[1:]))
+    for z0, z1 in chunks:
+        v0, p, t0, t = R.extract_layers(f, level, origin, z0, z1, v_layers, q_layers)
+        assert v0 <= v_end and t0 == t_end           # no vertex left out; the triangles follow on exactly
+        got_p[v0:v0 + len(p)], got_f[t0:t0 + len(t)] = p, t
+        new_v += v0 + len(p) - v_end
+        v_end, t_end = v0 + len(p), t0 + len(t)
+    assert (new_v, v_end, t_end) == (len(want_p), len(want_p), len(want_f)) and len(want_f) > 1000
+    assert np.array_equal(got_p.view(np.uint32), want_p.view(np.uint32)) and np.array_equal(got_f, want_f)
+    # ... and end to end they do not: layer 8 of 23 has quads that neither (0, 8) nor (8, 22) gives
+    a, b = R.extract_layers(f, level, origin, 0, 8, v_layers, q_layers), R.extract_layers(f, level, origin, 8, 22, v_layers, q_layers)
+    assert a[2] + len(a[3]) < b[2]
+
+
+@pytest.mark.parametrize("dims", [(2, 2, 2), (2, 9, 7), (9, 2, 7), (9, 7, 2), (5, 6, 7), (70, 4, 4), (3, 3, 3), (1, 5, 5), (130, 3, 5)])
+def test_checkerboard_closed_form(dims):
+    nx, ny, nz = dims
+    z, y, x = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+    ins = (x + y + z) % 2 == 1
+    v_layers, q_layers = R.counts_per_layer(ins)
+    assert R.checkerboard_counts(nx, ny, nz) == (int(v_layers.sum()), int(q_layers.sum()))
+    # the same grid as a view of an alternating 1-D array with strides (1, 1, 1)
+    alt = np.where(np.arange(nx + ny + nz) % 2 == 1, F(-1), F(1))
+    view = strided_view(alt, dims, 1, 1, 1)
+    assert np.array_equal(R.inside(view, 0.0), ins)
+    # per block of 256 words: at most 2^14 vertices and 3 x 2^14 quads, what the packed 16-bit prefixes hold
+    v_blocks, q_blocks = R.per_block_counts(ins)
+    assert v_blocks.sum() == v_layers.sum() and q_blocks.sum() == q_layers.sum() and v_blocks.max() <= 2 ** 14 and q_blocks.max() <= 3 * 2 ** 14
+
+
+@pytest.mark.parametrize("dims,sx,s1,s2", STRIDED)
+def test_row_tables_against_the_grid(dims, sx, s1, s2):
+    nx, ny, nz = dims
+    base = strided_base(dims, sx, s1, s2, 11)
+    level = 0.125
+    ins = np.ascontiguousarray(strided_view(base < F(level), dims, sx, s1, s2))
+    tables = R.row_tables(base < F(level), nx, sx, s1, s2)
+    v_rows, q_rows = R.row_counts(tables, ny, nz, s1, s2, 0, nz)
+    want_v = np.zeros((nz, ny), np.int64)
+    want_v[:nz - 1, :ny - 1] = R.active_cells(ins).sum(axis=2)
+    assert np.array_equal(v_rows, want_v) and np.array_equal(q_rows, R.quad_edges(ins).sum(axis=(2, 3))) and want_v.sum() > 0
+    for block, layers, workers in ((256, 64, 1), (16, 3, 4), (7, 5, 3)):
+        v_layers, q_layers, v_blocks, q_blocks = R.grid_counts(tables, ny, nz, s1, s2, block, layers, workers)
+        want_layers = R.counts_per_layer(ins)
+        in_slabs = R.counts_per_layer_slabs(ins, layers, workers)
+        assert np.array_equal(in_slabs[0], want_layers[0]) and np.array_equal(in_slabs[1], want_layers[1])
+        assert np.array_equal(v_layers, want_layers[0]) and np.array_equal(q_layers, want_layers[1])
+        want_blocks = R.per_block_counts(ins, block)
+        assert np.array_equal(v_blocks, want_blocks[0]) and np.array_equal(q_blocks, want_blocks[1])
+
+
 # ---- properties ----------------------------------------------------------------------------------------------------------
 
 FIELDS = {"sphere": (lambda: R.sphere_field(48, 15.2), (2,)), "torus": (lambda: R.torus_field(48, 13, 5), (0,)),

@@ -397,6 +397,75 @@ int o2v_hip_surface_write(o2v_hip_ctx *ctx, const float *field, const uint64_t s
  * o2v_hip_surface_write; 0 after a count). */
 int o2v_hip_surface_times(const o2v_hip_ctx *ctx, float out_ms[4]);
 
+/* ---- ray casting --------------------------------------------------------------------------------
+ *
+ * First hits of rays in a dense voxel grid, defined bit for bit by a walk from cell to cell; the device may skip empty space
+ * but returns what this walk returns, for every ray.
+ *
+ * Space: the voxel space of the sections above with supersampling 1.  Voxel (x, y, z) of the grid is the cube
+ * [ox + x, ox + x + 1) x [oy + y, oy + y + 1) x [oz + z, oz + z + 1), origin = (ox, oy, oz) integers, dims = (nx, ny, nz);
+ * everything outside the box is empty.  A voxel is solid, by format:
+ *   O2V_HIP_RAY_GRID_U8         grid[x * strides[0] + y * strides[1] + z * strides[2]] != 0 (bytes: bool tensors, labels; any strides)
+ *   O2V_HIP_RAY_GRID_BITS       bit x % 32 of the 32-bit word (x / 32) + y * strides[1] + z * strides[2]: what o2v_hip_write_dense
+ *                               BITS writes (strides[0] must be 1; strides in words)
+ *   O2V_HIP_RAY_GRID_F32_BELOW  f < level for the float32 f at the U8 address (elements); a NaN is empty, as `inside` above;
+ *                               level must be finite
+ * The grid is only read: a stride may be 0 and voxels may share elements.
+ *
+ * A ray has an origin o and a direction d, three float32 each, converted to double; d is not normalised, so t is in units of
+ * |d|; t_max is a float32, >= 0 or +inf, converted to double.  All arithmetic is in double, op by op, no FMA.
+ *   For an axis a with d_a != 0: inv_a = 1.0 / d_a, s_a = sgn d_a, and the parameter of plane i is
+ *     T_a(i) = ((double) i - o_a) * inv_a,
+ *   computed per plane index, never accumulated.  An axis with d_a == 0 (-0.0 too) never steps.
+ *   The start cell is c = floor(o); the next plane of axis a is n_a = c_a + 1 if d_a > 0, else c_a.
+ *   If c is in the box and solid, the ray hits with t = 0, face = -1, voxel c.  Otherwise repeat:
+ *     1. a = the axis with the smallest T_a(n_a); of equal ones the lowest axis;
+ *     2. if no axis can step, or that T > t_max, the ray misses;
+ *     3. c_a += s_a and n_a += s_a;
+ *     4. if c is in the box and solid, the ray hits: t = (float) T, face = 2 a + (s_a > 0 ? 0 : 1) - the face it entered
+ *        through: 0 / 1 the voxel's low / high x face, 2 / 3 y, 4 / 5 z -, voxel c;
+ *     5. the ray misses once it has left the box on an axis for good (it is past the box in its direction on that axis, or
+ *        beside the box on an axis it does not step on).
+ *   A ray that starts on a voxel face and points in the negative direction visits the cell floor(o) first, at t = 0, and the
+ *   cell below it next, also at T = 0: floor(o) is the start cell whatever the direction.  That is the definition.
+ *   t_max exactly equal to a plane's T still crosses it (the test is T > t_max).
+ * Output per ray: hit int32[4] = (x, y, z, face) in global voxel coordinates, and t float32.
+ *   A miss: hit = (-1, -1, -1, -1), t = +inf.
+ *   An invalid ray - a component of o or d that is not finite, or |o_a| > 2^22 -: hit = (-1, -1, -1, -2), t = NaN.
+ *   d = 0 is valid: only the start cell is tested.
+ * Why empty space can be skipped exactly: per axis T_a rises along the stepping direction, so the walk is the merge of the
+ * three plane sequences in order of (T, axis).  Leaving an empty aligned block, or entering the box from outside, is "advance
+ * to event E" - the least exit event of the block, or the greatest entry event of the axes on which the ray is still outside -
+ * after which every other axis b stands at its first plane j with (T_b(j), b) > E; that plane is found from the estimate
+ * floor(o_b + T d_b) and corrected by comparing T_b(j) itself.
+ *
+ * o2v_hip_raycast_build makes the one pass over the grid and keeps a snapshot in scratch of the context: a 64-bit word per
+ * 4^3 voxels (their solid bits), per 16^3 (its non-empty 4^3 bricks) and per 64^3 (its non-empty 16^3 blocks), aligned to the
+ * box's origin:
+ *   o2v_hip_raycast_scratch_bytes(dims) = 8 * (B(4) + B(16) + B(64)),  B(k) = ceil(nx / k) * ceil(ny / k) * ceil(nz / k)
+ * (0 for zero dims) - 1/8 byte per voxel and 1/63 more.  The grid may change or be freed afterwards: casting never reads it.
+ * A new build, refused or not, replaces the last one; o2v_hip_raycast_generation counts the builds of the context, refused ones
+ * included, so a caller can tell whether the snapshot is still the one it built.
+ * o2v_hip_raycast casts n rays (origins, directions [n][3] float32; hit [n][4] int32 and t [n] float32, contiguous, all in
+ * device memory of the context's device) through the last build; without one it returns O2V_HIP_ERR_BAD_ARGUMENT, "no
+ * o2v_hip_raycast_build".  It may be repeated; n = 0 launches nothing and reads no pointer.
+ * Refused before any launch: null arguments, zero dims, an unknown format, BITS with strides[0] != 1, a level that is not finite
+ * (F32_BELOW only; ignored otherwise), t_max NaN or negative, hit and t overlapping each other or the rays, a pointer that is not
+ * device memory of the context's device with its whole extent inside its allocation (O2V_HIP_ERR_BAD_ARGUMENT); origin[a] +
+ * dims[a] above 65 536, n above 2^31 - 1 (O2V_HIP_ERR_LIMIT).  A failed scratch allocation returns O2V_HIP_ERR_OUT_OF_MEMORY
+ * and the context stays usable.  Both calls run on the context's stream and return when their results have landed (the caller
+ * must have finished writing the grid and the rays).
+ * O2V_RAY_NO_SKIP=1 in the environment (A/B): the cast walks every fine cell; same results. */
+enum { O2V_HIP_RAY_GRID_U8 = 0, O2V_HIP_RAY_GRID_BITS = 1, O2V_HIP_RAY_GRID_F32_BELOW = 2 };
+int o2v_hip_raycast_build(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3],
+                          float level, const uint32_t origin[3]);
+int o2v_hip_raycast(o2v_hip_ctx *ctx, const float *origins /* [n][3] */, const float *directions /* [n][3] */, uint64_t n, float t_max,
+                    int32_t *hit /* [n][4] */, float *t /* [n] */);
+uint64_t o2v_hip_raycast_scratch_bytes(const uint32_t dims[3]);
+uint64_t o2v_hip_raycast_generation(const o2v_hip_ctx *ctx);
+/* The device times (ms) of the last o2v_hip_raycast_build and of the last o2v_hip_raycast. */
+int o2v_hip_raycast_times(const o2v_hip_ctx *ctx, float out_ms[2]);
+
 int o2v_hip_get_timings(const o2v_hip_ctx *ctx, o2v_hip_timings *out);
 /* Per-kernel device times of the last o2v_hip_voxelize call made with O2V_HIP_FLAG_KERNEL_TIMES (else none): up to
  * max_entries entries are written, *out_count receives how many there are. */

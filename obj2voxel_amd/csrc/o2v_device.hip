@@ -30,6 +30,8 @@
 //                              outside the pipeline
 //   K10 k_surf_*               o2v_hip_surface_count / _write: the level set of a float32 grid as an indexed mesh (surface
 //                              nets); outside the pipeline
+//   K11 k_ray_*                o2v_hip_raycast_build / o2v_hip_raycast: rays through a dense grid, a hierarchical walk over
+//                              bit-packed occupancy; outside the pipeline
 //   plan k_zhist               o2v_hip_plan_slabs: predicted hits per z layer -> work-balanced slabs for N GPUs
 // With the direct MAX path K1's counters reach the host while K2 runs, and only the stages that have work are enqueued
 // behind it.  N > 1 GPUs: o2v_hip_voxelize_sharded (bounds / work-histogram passes sharded over the ranks, RCCL).
@@ -75,6 +77,7 @@ namespace {
 #include "o2v_dev_k8_distance.hpp"
 #include "o2v_dev_k9_mesh_distance.hpp"
 #include "o2v_dev_k10_surface.hpp"
+#include "o2v_dev_k11_raycast.hpp"
 
 }  // namespace
 
@@ -204,6 +207,7 @@ struct Switches {
     bool force_solo_roots = env_on("O2V_TEST_FORCE_SOLO_ROOTS");  // test hook: solo roots whatever the extent hint says
     bool all_launches = env_on("O2V_ALL_LAUNCHES");            // A/B: no launch left out on the strength of the upload's hints
     bool no_slabs = env_on("O2V_NO_SLABS");                    // A/B: no new hit slabs, every hit pooled
+    bool ray_no_skip = env_on("O2V_RAY_NO_SKIP");              // A/B: k_ray_cast walks every fine cell, no empty block is skipped
     bool tiny_buffers = env_on("O2V_TEST_TINY_BUFFERS");       // test hook: minimal first capacities (every grow -> re-run path)
     bool block_list = env_on("O2V_TEST_BLOCK_LIST");           // test hook: the slab's block list for a mesh of any size
     int resolve_wgs_per_cu = env_int("O2V_RESOLVE_WGS_PER_CU", 0);  // A/B: workgroups per CU of resolve tier 1 (if > 0; else 2)
@@ -335,6 +339,15 @@ struct o2v_hip_ctx {
         float level = 0.f;
         uint64_t vertices = 0, quads = 0;
     } sf;
+    // K11 (o2v_hip_raycast_build / o2v_hip_raycast): the snapshot of the last build - the words of the 4^3 bricks, then of the
+    // 16^3 and the 64^3 blocks, in one array - and its identity; the times of the last build and the last cast
+    DevArray<unsigned long long> d_ray_masks;
+    StageTimes<1> ray_build_times, ray_cast_times;
+    struct RaySnapshot {
+        bool valid = false;
+        uint32_t dims[3] = {}, origin[3] = {};
+        uint64_t generation = 0;   // counts the builds, refused ones included
+    } ray;
 
     // results of the last run
     uint64_t n_vox = 0;
@@ -2853,6 +2866,163 @@ int o2v_hip_surface_times(const o2v_hip_ctx *ctx, float out_ms[4])
 {
     return ctx ? ctx->sf_times.read(out_ms) : O2V_HIP_ERR_BAD_ARGUMENT;
 }
+
+}  // extern "C"
+
+// ---- K11: rays through a dense grid ----------------------------------------------------------------------------------------
+
+namespace {
+
+constexpr uint32_t kRayMaxExtent = 65536;        // origin + dims per axis (O2V_HIP_ERR_LIMIT above)
+constexpr uint64_t kRayMaxRays = 0x7fffffffull;
+
+// the words of the three levels over dims: 4^3 bricks, 16^3 blocks, 64^3 blocks
+void ray_levels(const uint32_t dims[3], uint64_t words[3], uint32_t per_axis[3][3])
+{
+    for (int l = 0; l < 3; ++l) {
+        words[l] = 1;
+        for (int a = 0; a < 3; ++a) {
+            const uint32_t step = 4u << (2 * l);
+            per_axis[l][a] = (uint32_t) (((uint64_t) dims[a] + step - 1u) / step);
+            words[l] *= per_axis[l][a];
+        }
+    }
+}
+
+RayGrid ray_grid(const o2v_hip_ctx *ctx)
+{
+    RayGrid g{};
+    uint64_t words[3];
+    uint32_t per_axis[3][3];
+    ray_levels(ctx->ray.dims, words, per_axis);
+    for (int a = 0; a < 3; ++a) {
+        g.org[a] = (int32_t) ctx->ray.origin[a];
+        g.dim[a] = (int32_t) ctx->ray.dims[a];
+        g.b0[a] = per_axis[0][a];
+        g.b1[a] = per_axis[1][a];
+        g.b2[a] = per_axis[2][a];
+    }
+    g.m0 = ctx->d_ray_masks.ptr;
+    g.m1 = g.m0 + words[0];
+    g.m2 = g.m1 + words[1];
+    return g;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t o2v_hip_raycast_scratch_bytes(const uint32_t dims[3])
+{
+    if (!dims || !dims[0] || !dims[1] || !dims[2]) return 0;
+    uint64_t words[3];
+    uint32_t per_axis[3][3];
+    ray_levels(dims, words, per_axis);
+    return 8u * (words[0] + words[1] + words[2]);
+}
+
+int o2v_hip_raycast_build(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+                          const uint32_t origin[3])
+{
+    static const char fn[] = "o2v_hip_raycast_build";
+    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
+    ctx->ray.valid = false;
+    ++ctx->ray.generation;
+    if (!grid || !strides || !dims || !origin) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
+    if (!dims[0] || !dims[1] || !dims[2]) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "zero dims");
+    if (format != O2V_HIP_RAY_GRID_U8 && format != O2V_HIP_RAY_GRID_BITS && format != O2V_HIP_RAY_GRID_F32_BELOW)
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown format " + std::to_string(format));
+    if (format == O2V_HIP_RAY_GRID_BITS && strides[0] != 1u) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "a BITS grid needs strides[0] == 1");
+    if (format == O2V_HIP_RAY_GRID_F32_BELOW && !std::isfinite(level)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "level must be finite");
+    for (int a = 0; a < 3; ++a)
+        if ((uint64_t) origin[a] + dims[a] > kRayMaxExtent) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "origin + dims is above 65 536 voxels along an axis");
+    O2V_CHECK(hipSetDevice(ctx->device));
+    // (the elements the box reaches: words along x for BITS)
+    const uint32_t reach[3] = {format == O2V_HIP_RAY_GRID_BITS ? (dims[0] + 31u) / 32u : dims[0], dims[1], dims[2]};
+    int rc;
+    if ((rc = check_grid(ctx, fn, "grid", grid, reach, strides, format == O2V_HIP_RAY_GRID_U8 ? 1u : 4u, false))) return rc;
+    if ((rc = grow_scratch(ctx, ctx->d_ray_masks, o2v_hip_raycast_scratch_bytes(dims) / 8u, fn, "snapshot"))) return rc;
+    ctx->ktimes_on = false;   // (no per-launch brackets here; o2v_hip_voxelize sets the flag again from its params)
+    std::copy(dims, dims + 3, ctx->ray.dims);
+    std::copy(origin, origin + 3, ctx->ray.origin);
+    const RayGrid g = ray_grid(ctx);
+    uint64_t words[3];
+    uint32_t per_axis[3][3];
+    ray_levels(dims, words, per_axis);
+    unsigned long long *const m0 = ctx->d_ray_masks.ptr, *const m1 = m0 + words[0], *const m2 = m1 + words[1];
+    const RaySource src{grid, strides[0], strides[1], strides[2], level};
+    // 16-byte loads: unit x stride and every row 16-byte aligned
+    const uint64_t elem = format == O2V_HIP_RAY_GRID_U8 ? 1u : 4u;
+    const bool vec = strides[0] == 1u && (uintptr_t) grid % 16u == 0 && strides[1] * elem % 16u == 0 && strides[2] * elem % 16u == 0;
+    const uint64_t tiles = (uint64_t) ((dims[0] + 63u) / 64u) * per_axis[0][1] * per_axis[0][2];
+    const dim3 blocks(stream_grid(ctx, tiles * 64u, 8u));
+    hipStream_t s = ctx->stream;
+    O2V_CHECK(ctx->ray_build_times.mark(0, s));
+    O2V_CHECK(hipMemsetAsync(m1, 0, words[1] * 8u, s));
+    if (format == O2V_HIP_RAY_GRID_BITS)
+        O2V_LAUNCH("k_ray_build", s, (k_ray_build<kRayBits, false>), blocks, dim3(kBlock), 0, s, src, g, m0, m1);
+    else if (format == O2V_HIP_RAY_GRID_U8 && vec)
+        O2V_LAUNCH("k_ray_build", s, (k_ray_build<kRayU8, true>), blocks, dim3(kBlock), 0, s, src, g, m0, m1);
+    else if (format == O2V_HIP_RAY_GRID_U8)
+        O2V_LAUNCH("k_ray_build", s, (k_ray_build<kRayU8, false>), blocks, dim3(kBlock), 0, s, src, g, m0, m1);
+    else if (vec)
+        O2V_LAUNCH("k_ray_build", s, (k_ray_build<kRayF32Below, true>), blocks, dim3(kBlock), 0, s, src, g, m0, m1);
+    else
+        O2V_LAUNCH("k_ray_build", s, (k_ray_build<kRayF32Below, false>), blocks, dim3(kBlock), 0, s, src, g, m0, m1);
+    O2V_LAUNCH("k_ray_build_top", s, k_ray_build_top, dim3(stream_grid(ctx, words[2], 8u)), dim3(kBlock), 0, s, g, m1, m2);
+    O2V_CHECK(hipGetLastError());
+    O2V_CHECK(ctx->ray_build_times.mark(1, s));
+    O2V_CHECK(hipStreamSynchronize(s));
+    O2V_CHECK(ctx->ray_build_times.finish());
+    ctx->ray.valid = true;
+    return O2V_HIP_OK;
+}
+
+int o2v_hip_raycast(o2v_hip_ctx *ctx, const float *origins, const float *directions, uint64_t n, float t_max, int32_t *hit, float *t)
+{
+    static const char fn[] = "o2v_hip_raycast";
+    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
+    const Switches sw = read_switches();
+    if (!(t_max >= 0.f)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "t_max must be >= 0 or +inf");
+    if (n > kRayMaxRays) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "more than 2^31 - 1 rays");
+    if (!ctx->ray.valid) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "no o2v_hip_raycast_build");
+    if (n == 0) return O2V_HIP_OK;
+    if (!origins || !directions || !hit || !t) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
+    O2V_CHECK(hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = check_device_range(ctx, fn, origins, n * 12u, "origins")) || (rc = check_device_range(ctx, fn, directions, n * 12u, "directions")) ||
+        (rc = check_device_range(ctx, fn, hit, n * 16u, "hit")) || (rc = check_device_range(ctx, fn, t, n * 4u, "t")))
+        return rc;
+    if (ranges_overlap(hit, n * 16u, t, n * 4u)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "hit and t overlap");
+    if (ranges_overlap(hit, n * 16u, origins, n * 12u) || ranges_overlap(hit, n * 16u, directions, n * 12u))
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "hit overlaps the rays");
+    if (ranges_overlap(t, n * 4u, origins, n * 12u) || ranges_overlap(t, n * 4u, directions, n * 12u))
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "t overlaps the rays");
+    ctx->ktimes_on = false;
+    const RayGrid g = ray_grid(ctx);
+    const dim3 blocks((uint32_t) ((n + kBlock - 1) / kBlock));
+    hipStream_t s = ctx->stream;
+    O2V_CHECK(ctx->ray_cast_times.mark(0, s));
+    if (sw.ray_no_skip)
+        O2V_LAUNCH("k_ray_cast", s, k_ray_cast<false>, blocks, dim3(kBlock), 0, s, origins, directions, n, t_max, g, hit, t);
+    else
+        O2V_LAUNCH("k_ray_cast", s, k_ray_cast<true>, blocks, dim3(kBlock), 0, s, origins, directions, n, t_max, g, hit, t);
+    O2V_CHECK(hipGetLastError());
+    O2V_CHECK(ctx->ray_cast_times.mark(1, s));
+    O2V_CHECK(hipStreamSynchronize(s));
+    O2V_CHECK(ctx->ray_cast_times.finish());
+    return O2V_HIP_OK;
+}
+
+int o2v_hip_raycast_times(const o2v_hip_ctx *ctx, float out_ms[2])
+{
+    if (!ctx || !out_ms) return O2V_HIP_ERR_BAD_ARGUMENT;
+    out_ms[0] = ctx->ray_build_times.ms[0];
+    out_ms[1] = ctx->ray_cast_times.ms[0];
+    return O2V_HIP_OK;
+}
+
+uint64_t o2v_hip_raycast_generation(const o2v_hip_ctx *ctx) { return ctx ? ctx->ray.generation : 0; }
 
 }  // extern "C"
 

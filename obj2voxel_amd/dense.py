@@ -10,7 +10,8 @@ The mesh goes to the device context without a host copy (o2v_hip_set_triangles_d
 tensor written on the device (o2v_hip_write_dense); nothing of either crosses to the host.  Distance grids (fmt "dist2" /
 "sdf", and distance_transform on any label tensor) come from o2v_hip_distance_dense; mesh_distance is the
 narrow-band distance to the triangles themselves (o2v_hip_mesh_distance_dense); extract_surface turns a
-distance grid back into an indexed mesh (o2v_hip_surface_count / _write).
+distance grid back into an indexed mesh (o2v_hip_surface_count / _write); RayCaster / raycast find the
+first solid voxel along rays through any of these grids (o2v_hip_raycast_build / o2v_hip_raycast).
 
 torch is imported first on purpose: the library must bind to the HIP runtime torch loaded (a process that loaded the library
 before torch holds two separate runtime copies, and this module refuses to work there).
@@ -35,6 +36,7 @@ STRATEGIES = {"max": hip.STRATEGY_MAX, "blend": hip.STRATEGY_BLEND}
 MAX_SAMPLES = 65535  # samples per axis of one pass (x / y tiles above that are not supported here)
 MAX_BAND = 32.0      # mesh_distance: the widest band, in voxels
 MAX_SURFACE_EXTENT = 65536  # extract_surface: origin + shape per axis
+MAX_RAY_EXTENT = 65536      # RayCaster: origin + extent per axis
 
 
 def _require_shared_runtime():
@@ -362,3 +364,119 @@ def extract_surface(dv, field, level=0.0, *, origin=(0, 0, 0), transform=None, s
         p = positions.to(torch.float64) * supersampling - transform[9:].to(device)
         positions = (p[:, None, :] * inverse[None, :, :]).sum(dim=2).to(torch.float32).contiguous()
     return positions, faces
+
+
+class RayCaster:
+    """First hits of rays in a dense grid on the voxelizer's device.
+
+        caster = dense.RayCaster(dv, grid)                  # one pass over the grid; the snapshot stays in dv
+        hit, t = caster.cast(origins, directions)           # int32 [..., 4] = (x, y, z, face), float32 [...]
+
+    grid:    a 3-D tensor [z, y, x] of any strides: bool or uint8 (solid where != 0: occupancy, labels), int32 (the words of
+             fmt="bits": the last dimension counts 32-voxel words, unit stride along it) or float32 with `level` (solid where
+             grid < level: an SDF or TSDF with level=0).  `level` with any other dtype raises.
+    origin:  (ox, oy, oz), the one the grid came with: voxel (x, y, z) is the unit cube at origin + (x, y, z).
+    The snapshot is taken at once: the grid may change or be freed afterwards.  A voxelizer holds one snapshot; a later
+    RayCaster on the same `dv` replaces it, and casting with the earlier one raises RuntimeError."""
+
+    def __init__(self, dv, grid, *, level=None, origin=(0, 0, 0)):
+        _require_shared_runtime()
+        device = _device(dv)
+        if not isinstance(grid, torch.Tensor) or grid.dim() != 3:
+            raise ValueError("grid must be a 3-D tensor [z, y, x]")
+        if grid.dtype in (torch.bool, torch.uint8):
+            fmt = hip.RAY_GRID_U8
+        elif grid.dtype == torch.int32:
+            fmt = hip.RAY_GRID_BITS
+        elif grid.dtype == torch.float32:
+            fmt = hip.RAY_GRID_F32_BELOW
+        else:
+            raise TypeError(f"grid must be bool, uint8, int32 (bits) or float32, not {grid.dtype}")
+        if fmt == hip.RAY_GRID_F32_BELOW:
+            if level is None:
+                raise ValueError("a float32 grid needs level: a voxel is solid where grid < level")
+            if isinstance(level, bool) or not isinstance(level, numbers.Real) or not float("-inf") < float(level) < float("inf"):
+                raise ValueError(f"level must be a finite number, not {level!r}")
+            level = hip.C.c_float(float(level)).value
+            if not float("-inf") < level < float("inf"):
+                raise ValueError("level is not finite as a float32")
+        elif level is not None:
+            raise ValueError(f"level is for float32 grids, not {grid.dtype}")
+        if grid.device != device:
+            raise ValueError(f"grid is on {grid.device}, the voxelizer on {device}")
+        if 0 in grid.shape:
+            raise ValueError("grid has an empty dimension")
+        if fmt == hip.RAY_GRID_BITS and grid.stride(2) != 1:
+            raise ValueError("a bits grid needs unit stride along x (its last dimension)")
+        origin = tuple(int(v) for v in origin)
+        if len(origin) != 3 or any(v < 0 for v in origin):
+            raise ValueError(f"origin {origin} must be three voxel coordinates, none negative")
+        nz, ny, nx = grid.shape
+        if fmt == hip.RAY_GRID_BITS:
+            nx *= 32
+        if any(o + n > MAX_RAY_EXTENT for o, n in zip(origin, (nx, ny, nz))):
+            raise ValueError(f"origin {origin} + the grid's extent {(nx, ny, nz)} [x, y, z] is above {MAX_RAY_EXTENT}")
+        self.dv, self.device, self.origin, self.dims = dv, device, origin, (nx, ny, nz)
+        _sync(device)   # (the caller's writes to grid have landed)
+        self._generation = dv.raycast_build(grid.data_ptr(), fmt, _strides(grid), (nx, ny, nz), 0.0 if level is None else level, origin)
+
+    def cast(self, origins, directions, t_max=float("inf")):
+        """(hit, t) of the rays origins + t * directions, float32 tensors [..., 3] of one shape on the device, in voxel space;
+        directions need not be normalised (t is in units of their length).  hit int32 [..., 4] = (x, y, z, face): the first
+        solid voxel and the face the ray entered it through (0 / 1: low / high x, 2 / 3: y, 4 / 5: z; -1: the ray started
+        inside it, t = 0); t float32 [...].  A miss, also one past t_max (a number >= 0), is (-1, -1, -1, -1) and +inf; a ray with
+        a non-finite component or an origin beyond 2^22 is (-1, -1, -1, -2) and NaN.  New contiguous tensors."""
+        if self.dv.raycast_generation() != self._generation:
+            raise RuntimeError("this RayCaster's snapshot has been replaced by a later build on the same voxelizer")
+        if isinstance(t_max, bool) or not isinstance(t_max, numbers.Real) or not float(t_max) >= 0.0:
+            raise ValueError(f"t_max must be a number >= 0 or inf, not {t_max!r}")
+        for name, r in (("origins", origins), ("directions", directions)):
+            if not isinstance(r, torch.Tensor):
+                raise TypeError(f"{name} must be a torch tensor")
+            if r.dtype != torch.float32:
+                raise TypeError(f"{name} must be torch.float32, not {r.dtype}")
+            if r.dim() < 1 or r.shape[-1] != 3:
+                raise ValueError(f"{name} must have shape [..., 3], not {tuple(r.shape)}")
+            if r.device != self.device:
+                raise ValueError(f"{name} is on {r.device}, the voxelizer on {self.device}")
+        if origins.shape != directions.shape:
+            raise ValueError(f"origins {tuple(origins.shape)} and directions {tuple(directions.shape)} must have one shape")
+        shape = tuple(origins.shape[:-1])
+        o, d = origins.reshape(-1, 3).contiguous(), directions.reshape(-1, 3).contiguous()
+        n = o.shape[0]
+        hit = torch.empty((n, 4), dtype=torch.int32, device=self.device)
+        t = torch.empty((n,), dtype=torch.float32, device=self.device)
+        if n:
+            _sync(self.device)   # (the caller's writes to the rays have landed)
+            self.dv.raycast(o.data_ptr(), d.data_ptr(), n, float(t_max), hit.data_ptr(), t.data_ptr())
+        return hit.reshape(shape + (4,)), t.reshape(shape)
+
+
+def raycast(dv, grid, origins, directions, *, t_max=float("inf"), level=None, origin=(0, 0, 0)):
+    """RayCaster(dv, grid, level=level, origin=origin).cast(origins, directions, t_max) in one call."""
+    return RayCaster(dv, grid, level=level, origin=origin).cast(origins, directions, t_max)
+
+
+def camera_rays(width, height, eye, target, up, fov_y_degrees, device):
+    """(origins, directions), float32 [height, width, 3] each: the rays of a pinhole camera at `eye` looking at `target`
+    through the centres of width x height pixels, row 0 at the top; fov_y_degrees is the vertical field of view.  The
+    directions have unit length, so RayCaster.cast gives distances in voxels.  Plain torch."""
+    if width < 1 or height < 1 or not 0.0 < float(fov_y_degrees) < 180.0:
+        raise ValueError("width and height must be positive and 0 < fov_y_degrees < 180")
+    eye, target, up = (torch.as_tensor(v, dtype=torch.float64).reshape(3) for v in (eye, target, up))
+    forward = target - eye
+    if float(forward.norm()) == 0.0:
+        raise ValueError("eye and target coincide")
+    forward = forward / forward.norm()
+    right = torch.linalg.cross(forward, up)
+    if not float(right.norm()) > 1e-9 * float(up.norm()):
+        raise ValueError("up is parallel to the viewing direction")
+    right = right / right.norm()
+    true_up = torch.linalg.cross(right, forward)
+    half = float(torch.tan(torch.deg2rad(torch.tensor(float(fov_y_degrees), dtype=torch.float64)) / 2))
+    v = (1.0 - (torch.arange(height, dtype=torch.float64) + 0.5) * (2.0 / height)) * half
+    u = ((torch.arange(width, dtype=torch.float64) + 0.5) * (2.0 / width) - 1.0) * (half * width / height)
+    directions = forward[None, None, :] + u[None, :, None] * right[None, None, :] + v[:, None, None] * true_up[None, None, :]
+    directions = directions / directions.norm(dim=2, keepdim=True)
+    origins = eye.expand(height, width, 3)
+    return origins.to(torch.float32).contiguous().to(device), directions.to(torch.float32).contiguous().to(device)

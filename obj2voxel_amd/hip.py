@@ -24,6 +24,7 @@ FLAG_EXACT_CLIP = 1  # o2v_hip_params::flags: the clip kernel without its work-r
 FLAG_FILL_INTERIOR = 8  # ... solid voxelization: the interior voxels (colour fill_argb) behind the surface records
 DENSE_U8, DENSE_ARGB32, DENSE_BITS = 0, 1, 2  # o2v_hip_write_dense formats
 DIST_SQ_I32, DIST_SDF_F32 = 0, 1  # o2v_hip_distance_dense formats
+RAY_GRID_U8, RAY_GRID_BITS, RAY_GRID_F32_BELOW = 0, 1, 2  # o2v_hip_raycast_build formats
 MESH_DIST_UNSIGNED_F32, MESH_DIST_SIGNED_F32 = 0, 1  # o2v_hip_mesh_distance_dense formats
 ERR_BAD_ARGUMENT = 3
 
@@ -123,6 +124,13 @@ def _bind():
     L.o2v_hip_surface_write.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_uint64,
                                         C.c_void_p, C.c_uint64]
     L.o2v_hip_surface_times.argtypes = [C.c_void_p, C.c_void_p]
+    L.o2v_hip_raycast_build.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
+    L.o2v_hip_raycast.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_void_p, C.c_void_p]
+    L.o2v_hip_raycast_scratch_bytes.argtypes = [C.c_void_p]
+    L.o2v_hip_raycast_scratch_bytes.restype = C.c_uint64
+    L.o2v_hip_raycast_generation.argtypes = [C.c_void_p]
+    L.o2v_hip_raycast_generation.restype = C.c_uint64
+    L.o2v_hip_raycast_times.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_max_slab_layers.argtypes = [C.c_void_p, C.POINTER(_Params), C.POINTER(C.c_uint32)]
     return L
 
@@ -170,6 +178,11 @@ def load_mesh_file(path):
         return (np.zeros((0, 9), np.float32) if verts is None else verts), mat, textures
     finally:
         L.o2v_mesh_free(h)
+
+
+def raycast_scratch_bytes(dims):
+    """o2v_hip_raycast_scratch_bytes: the context scratch the snapshot of a raycast_build over dims (x, y, z) takes."""
+    return int(_bind().o2v_hip_raycast_scratch_bytes(_u32x3(dims)))
 
 
 def device_count():
@@ -311,6 +324,35 @@ class DeviceVoxelizer:
         """o2v_hip_surface_times: the device times (ms) of the last surface_count call's classify and count + scan stages and
         of the last surface_write call's vertex and face stages."""
         return self._stage_times("o2v_hip_surface_times", 4)
+
+    def raycast_build(self, grid_ptr, fmt, strides, dims, level=0.0, origin=(0, 0, 0)):
+        """o2v_hip_raycast_build: the snapshot of the grid at device address grid_ptr (RAY_GRID_U8: element != 0; RAY_GRID_BITS:
+        the words write_dense DENSE_BITS writes; RAY_GRID_F32_BELOW: float32 < level; strides and dims per axis x, y, z) that
+        raycast walks, kept in the context.  Returns its generation (raycast_generation): every build, refused or not, replaces
+        the last one."""
+        try:
+            self._check(self._L.o2v_hip_raycast_build(self._ctx, grid_ptr, fmt, _u64x3(strides), _u32x3(dims), float(level), _u32x3(origin)),
+                        "o2v_hip_raycast_build")
+        finally:
+            generation = self.raycast_generation()
+        return generation
+
+    def raycast_generation(self):
+        """o2v_hip_raycast_generation: the number of raycast_build calls made on this context, refused ones included."""
+        return int(self._L.o2v_hip_raycast_generation(self._ctx))
+
+    def raycast(self, origins_ptr, directions_ptr, n, t_max, hit_ptr, t_ptr):
+        """o2v_hip_raycast: n rays (float32 [n, 3] origins and directions at device addresses) through the last raycast_build,
+        into int32 hit [n, 4] = (x, y, z, face) and float32 t [n]; a miss is (-1, -1, -1, -1), +inf."""
+        self._check(self._L.o2v_hip_raycast(self._ctx, origins_ptr, directions_ptr, n, float(t_max), hit_ptr, t_ptr), "o2v_hip_raycast")
+
+    def raycast_scratch_bytes(self, dims):
+        """o2v_hip_raycast_scratch_bytes: the context scratch the snapshot of a raycast_build over dims (x, y, z) takes."""
+        return raycast_scratch_bytes(dims)
+
+    def raycast_times(self):
+        """o2v_hip_raycast_times: the device times (ms) of the last raycast_build and the last raycast."""
+        return self._stage_times("o2v_hip_raycast_times", 2)
 
     def set_textures(self, textures):
         """textures: sequence of (uint8 [h, w, c] pixels, wrap) with c in (3, 4)."""

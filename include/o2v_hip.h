@@ -466,6 +466,62 @@ uint64_t o2v_hip_raycast_generation(const o2v_hip_ctx *ctx);
 /* The device times (ms) of the last o2v_hip_raycast_build and of the last o2v_hip_raycast. */
 int o2v_hip_raycast_times(const o2v_hip_ctx *ctx, float out_ms[2]);
 
+/* ---- connected components and flood fill ------------------------------------------------------------
+ *
+ * What is connected to what in a dense voxel grid, defined so that a numpy restatement reproduces every bit.
+ *
+ * The set.  The grid, its three formats, the rules for its strides and the rule for BITS (strides[0] == 1) are those of
+ * o2v_hip_raycast_build: O2V_HIP_GRID_U8 (element != 0), O2V_HIP_GRID_BITS, O2V_HIP_GRID_F32_BELOW (f < level with a finite
+ * level; a NaN is not below it) - the values of O2V_HIP_RAY_GRID_*, which stay.  The grid is only read: a stride may be 0.
+ * Those voxels are the solid ones.  Without a flag the set S is the solid voxels of the box; with O2V_HIP_CC_INVERT it is the
+ * voxels of the box that are not solid.
+ * Connectivity is 6, 18 or 26: two voxels of S are adjacent if they differ by at most 1 on every axis and on at most 1, 2 or 3
+ * axes.  Nothing outside the box is adjacent to anything.  A component is a class of the transitive closure of adjacency.
+ *
+ * o2v_hip_components_dense writes labels(x, y, z) = labels[x * label_strides[0] + y * label_strides[1] + z * label_strides[2]]
+ * (int32, strides in elements, no two voxels on one element) for every voxel of the box: 0 outside S; inside S, 1 + the rank of
+ * the voxel's component, the components ranked by their smallest linear index (z * ny + y) * nx + x.  *out_count is the number
+ * of components.  This is the numbering of scipy.ndimage.label on a [z, y, x] array.
+ *
+ * o2v_hip_flood_dense marks the components that hold a seed.  seeds: int32 [n_seeds][3], local (x, y, z), in device memory; a
+ * seed outside the box or not in S is ignored; with n_seeds = 0 the pointer is not read.  O2V_HIP_CC_SEED_BORDER additionally
+ * seeds every voxel of S on the six faces of the box.  Every voxel of the box is written, out(x, y, z) (uint8, strides as for
+ * labels) = values[0] if it is in S and its component holds a seed, values[1] if it is in S and its component holds none,
+ * values[2] if it is not in S.  *out_reached is the number of voxels that got values[0].
+ *
+ * flags: O2V_HIP_CC_INVERT, O2V_HIP_CC_SEED_BORDER (flood only), O2V_HIP_FLAG_STAGE_TIMES (o2v_hip_components_counters counts).
+ * Refused before any launch, labels / out untouched: null arguments, zero dims, an unknown format, a connectivity other than 6,
+ * 18, 26, unknown flag bits, BITS with strides[0] != 1, a level that is not finite (F32_BELOW only), labels / out overlapping the
+ * grid or the seeds, label / out strides that map two voxels to one element, a pointer that is not device memory of the context's
+ * device with its whole extent inside its allocation (O2V_HIP_ERR_BAD_ARGUMENT); a dim above 65 536, nx * ny * nz or n_seeds above
+ * 2^31 - 1 - a linear index and a label are one int32 - (O2V_HIP_ERR_LIMIT).  A failed scratch allocation returns
+ * O2V_HIP_ERR_OUT_OF_MEMORY and the context stays usable.  After a later error labels / out are unspecified.  Both calls run on
+ * the context's stream and return when their results have landed (the caller must have finished writing the grid and the seeds).
+ *
+ * Scratch of the context, grown on demand, with words = ceil(nx / 64) * ny * nz and voxels = nx * ny * nz:
+ *   O2V_HIP_CC_SCRATCH_LABELS          20 * words + 8 * (ceil(words / 256) + 1) + 32: the set's bits, the root flags, the per-word
+ *                                      prefixes, the block offsets, counters.  No per-voxel scratch: the parents live in labels
+ *                                      until the last pass.  This holds where labels are contiguous (strides 1, nx, nx * ny);
+ *   O2V_HIP_CC_SCRATCH_LABELS_STRIDED  ... + 4 * voxels: labels of any other strides, the parents in the context;
+ *   O2V_HIP_CC_SCRATCH_FLOOD           16 * words + 4 * voxels + 32: the set's bits, the seed flags, the parents, counters.
+ * (0 for zero dims or an unknown `which`.)
+ * O2V_CC_NO_TILES=1 in the environment (A/B): no tile pass, every adjacent pair is united in global memory; same results. */
+enum { O2V_HIP_GRID_U8 = 0, O2V_HIP_GRID_BITS = 1, O2V_HIP_GRID_F32_BELOW = 2 };
+enum { O2V_HIP_CC_INVERT = 16u, O2V_HIP_CC_SEED_BORDER = 32u };
+enum { O2V_HIP_CC_SCRATCH_LABELS = 0, O2V_HIP_CC_SCRATCH_LABELS_STRIDED = 1, O2V_HIP_CC_SCRATCH_FLOOD = 2 };
+int o2v_hip_components_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3],
+                             float level, uint32_t connectivity, uint32_t flags, int32_t *labels, const uint64_t label_strides[3],
+                             uint64_t *out_count);
+int o2v_hip_flood_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+                        uint32_t connectivity, uint32_t flags, const int32_t *seeds /* [n_seeds][3] */, uint64_t n_seeds,
+                        const uint8_t values[3], uint8_t *out, const uint64_t out_strides[3], uint64_t *out_reached);
+uint64_t o2v_hip_components_scratch_bytes(const uint32_t dims[3], uint32_t which);
+/* The device times (ms) of the last of the two calls: classify, tile pass, seams, flatten (+ root count), write (+ seeds). */
+int o2v_hip_components_times(const o2v_hip_ctx *ctx, float out_ms[5]);
+/* Of the last call made with O2V_HIP_FLAG_STAGE_TIMES (else zeros): the pairs united across tile seams (every pair with
+ * O2V_CC_NO_TILES=1) and the atomic mins that did not meet a root and went round again. */
+int o2v_hip_components_counters(const o2v_hip_ctx *ctx, uint64_t out2[2]);
+
 int o2v_hip_get_timings(const o2v_hip_ctx *ctx, o2v_hip_timings *out);
 /* Per-kernel device times of the last o2v_hip_voxelize call made with O2V_HIP_FLAG_KERNEL_TIMES (else none): up to
  * max_entries entries are written, *out_count receives how many there are. */

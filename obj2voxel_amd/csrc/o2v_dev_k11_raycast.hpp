@@ -47,6 +47,41 @@ __device__ __forceinline__ uint32_t ray_bit(int32_t x, int32_t y, int32_t z) { r
 
 // ---- build ----------------------------------------------------------------------------------------------------------------
 
+// The solid bits of the n <= 16 voxels x0 .. x0 + n - 1 (x0 a multiple of 16) of the row at element offset `at`: bit i is
+// voxel x0 + i.  Vec: the x stride is 1 and every row 16-byte aligned.  (K12's classify pass reads the grid through it too.)
+template <uint32_t Format, bool Vec>
+__device__ __forceinline__ uint32_t ray_read16(const RaySource &src, uint64_t at, uint32_t x0, uint32_t n)
+{
+    uint32_t bits = 0;
+    if (Format == kRayBits) {
+        const uint32_t w = static_cast<const uint32_t *>(src.p)[at + (x0 >> 5)];
+        bits = (w >> (x0 & 16u)) & ((1u << n) - 1u);
+    } else if (Format == kRayU8) {
+        const uint8_t *p = static_cast<const uint8_t *>(src.p) + at;
+        if (Vec && n == 16u) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(p + x0);
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (uint32_t i = 0; i < 16u; ++i) bits |= (uint32_t) ((w[i >> 2] >> (8u * (i & 3u)) & 0xffu) != 0u) << i;
+        } else {
+            for (uint32_t i = 0; i < n; ++i) bits |= (uint32_t) (p[(uint64_t) (x0 + i) * src.s0] != 0) << i;
+        }
+    } else {
+        const float *p = static_cast<const float *>(src.p) + at;
+        if (Vec && n == 16u) {
+#pragma unroll
+            for (uint32_t i = 0; i < 4u; ++i) {
+                const float4 v = *reinterpret_cast<const float4 *>(p + x0 + 4u * i);
+                bits |= ((uint32_t) (v.x < src.level) | (uint32_t) (v.y < src.level) << 1 | (uint32_t) (v.z < src.level) << 2 |
+                         (uint32_t) (v.w < src.level) << 3) << (4u * i);
+            }
+        } else {
+            for (uint32_t i = 0; i < n; ++i) bits |= (uint32_t) (p[(uint64_t) (x0 + i) * src.s0] < src.level) << i;
+        }
+    }
+    return bits;
+}
+
 template <uint32_t Format, bool Vec>
 __global__ __launch_bounds__(kBlock) void k_ray_build(RaySource src, RayGrid g, unsigned long long *__restrict__ m0, unsigned long long *__restrict__ m1)
 {
@@ -61,34 +96,8 @@ __global__ __launch_bounds__(kBlock) void k_ray_build(RaySource src, RayGrid g, 
         const uint32_t x0 = tx * 64u + q * 16u, y = by * 4u + (r & 3u), z = bz * 4u + (r >> 2);
         uint32_t bits = 0;
         if (x0 < nx && y < ny && z < nz) {
-            const uint32_t n = min(16u, nx - x0);
             const uint64_t at = (uint64_t) y * src.s1 + (uint64_t) z * src.s2;
-            if (Format == kRayBits) {
-                const uint32_t w = static_cast<const uint32_t *>(src.p)[at + (x0 >> 5)];
-                bits = (w >> (x0 & 16u)) & ((1u << n) - 1u);
-            } else if (Format == kRayU8) {
-                const uint8_t *p = static_cast<const uint8_t *>(src.p) + at;
-                if (Vec && n == 16u) {
-                    const uint4 v = *reinterpret_cast<const uint4 *>(p + x0);
-                    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                    for (uint32_t i = 0; i < 16u; ++i) bits |= (uint32_t) ((w[i >> 2] >> (8u * (i & 3u)) & 0xffu) != 0u) << i;
-                } else {
-                    for (uint32_t i = 0; i < n; ++i) bits |= (uint32_t) (p[(uint64_t) (x0 + i) * src.s0] != 0) << i;
-                }
-            } else {
-                const float *p = static_cast<const float *>(src.p) + at;
-                if (Vec && n == 16u) {
-#pragma unroll
-                    for (uint32_t i = 0; i < 4u; ++i) {
-                        const float4 v = *reinterpret_cast<const float4 *>(p + x0 + 4u * i);
-                        bits |= ((uint32_t) (v.x < src.level) | (uint32_t) (v.y < src.level) << 1 | (uint32_t) (v.z < src.level) << 2 |
-                                 (uint32_t) (v.w < src.level) << 3) << (4u * i);
-                    }
-                } else {
-                    for (uint32_t i = 0; i < n; ++i) bits |= (uint32_t) (p[(uint64_t) (x0 + i) * src.s0] < src.level) << i;
-                }
-            }
+            bits = ray_read16<Format, Vec>(src, at, x0, min(16u, nx - x0));
         }
         // the nibble of brick j of this lane's four, at its row's place; OR over the 16 rows (lane bits 2 .. 5)
         unsigned long long m[4];

@@ -32,6 +32,8 @@
 //                              nets); outside the pipeline
 //   K11 k_ray_*                o2v_hip_raycast_build / o2v_hip_raycast: rays through a dense grid, a hierarchical walk over
 //                              bit-packed occupancy; outside the pipeline
+//   K12 k_cc_*                 o2v_hip_components_dense / o2v_hip_flood_dense: connected components and flood fill of a dense
+//                              grid, a union-find over its voxels ; outside the pipeline
 //   plan k_zhist               o2v_hip_plan_slabs: predicted hits per z layer -> work-balanced slabs for N GPUs
 // With the direct MAX path K1's counters reach the host while K2 runs, and only the stages that have work are enqueued
 // behind it.  N > 1 GPUs: o2v_hip_voxelize_sharded (bounds / work-histogram passes sharded over the ranks, RCCL).
@@ -78,6 +80,7 @@ namespace {
 #include "o2v_dev_k9_mesh_distance.hpp"
 #include "o2v_dev_k10_surface.hpp"
 #include "o2v_dev_k11_raycast.hpp"
+#include "o2v_dev_k12_components.hpp"
 
 }  // namespace
 
@@ -208,6 +211,7 @@ struct Switches {
     bool all_launches = env_on("O2V_ALL_LAUNCHES");            // A/B: no launch left out on the strength of the upload's hints
     bool no_slabs = env_on("O2V_NO_SLABS");                    // A/B: no new hit slabs, every hit pooled
     bool ray_no_skip = env_on("O2V_RAY_NO_SKIP");              // A/B: k_ray_cast walks every fine cell, no empty block is skipped
+    bool cc_no_tiles = env_on("O2V_CC_NO_TILES");              // A/B: no k_cc_tiles, every adjacent pair is united in global memory
     bool tiny_buffers = env_on("O2V_TEST_TINY_BUFFERS");       // test hook: minimal first capacities (every grow -> re-run path)
     bool block_list = env_on("O2V_TEST_BLOCK_LIST");           // test hook: the slab's block list for a mesh of any size
     int resolve_wgs_per_cu = env_int("O2V_RESOLVE_WGS_PER_CU", 0);  // A/B: workgroups per CU of resolve tier 1 (if > 0; else 2)
@@ -348,6 +352,15 @@ struct o2v_hip_ctx {
         uint32_t dims[3] = {}, origin[3] = {};
         uint64_t generation = 0;   // counts the builds, refused ones included
     } ray;
+
+    // K12 (o2v_hip_components_dense / o2v_hip_flood_dense): the bits of the set, the root flags (labels) or seed flags (flood),
+    // the per-word prefixes and block offsets of the root count, the parents where they cannot live in the caller's labels, grown
+    // on demand; [0] unions, [1] retries, [2] reached; the times of the five stages and the two counters of the last call
+    DevArray<unsigned long long> d_cc_bits, d_cc_flags, d_cc_boff, d_cc_ctr;
+    DevArray<uint32_t> d_cc_local, d_cc_parent;
+    PinnedArray<unsigned long long> h_cc_ctr;
+    StageTimes<5> cc_times;
+    uint64_t cc_counters[2] = {};
 
     // results of the last run
     uint64_t n_vox = 0;
@@ -3023,6 +3036,184 @@ int o2v_hip_raycast_times(const o2v_hip_ctx *ctx, float out_ms[2])
 }
 
 uint64_t o2v_hip_raycast_generation(const o2v_hip_ctx *ctx) { return ctx ? ctx->ray.generation : 0; }
+
+}  // extern "C"
+
+// ---- K12: connected components and flood fill of a dense grid ---------------------------------------------------------------
+
+namespace {
+
+constexpr uint32_t kCcMaxDim = 65536;
+constexpr uint64_t kCcMaxVoxels = 0x7fffffffull;   // a linear index and a label are one int32
+constexpr uint64_t kCcMaxGrid = 1ull << 20;        // workgroups of k_cc_tiles; more tiles are taken in turns
+constexpr uint32_t kCcFlagsKnown = O2V_HIP_CC_INVERT | O2V_HIP_CC_SEED_BORDER | O2V_HIP_FLAG_STAGE_TIMES;
+
+uint64_t cc_words(const uint32_t dims[3]) { return (uint64_t) ((dims[0] + 63u) / 64u) * dims[1] * dims[2]; }
+
+// What the two calls share.  labels != null: o2v_hip_components_dense; else o2v_hip_flood_dense.
+int cc_run(o2v_hip_ctx *ctx, const char *fn, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+           uint32_t connectivity, uint32_t flags, int32_t *labels, uint8_t *out, const uint64_t out_strides[3], const int32_t *seeds,
+           uint64_t n_seeds, const uint8_t values[3], uint64_t *result)
+{
+    const Switches sw = read_switches();
+    if (!grid || !strides || !dims || !out_strides || !result || (!labels && !out) || (out && !values) || (n_seeds && !seeds))
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
+    if (!dims[0] || !dims[1] || !dims[2]) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "zero dims");
+    if (format != O2V_HIP_GRID_U8 && format != O2V_HIP_GRID_BITS && format != O2V_HIP_GRID_F32_BELOW)
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown format " + std::to_string(format));
+    if (connectivity != 6u && connectivity != 18u && connectivity != 26u)
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "connectivity must be 6, 18 or 26, not " + std::to_string(connectivity));
+    if ((flags & ~kCcFlagsKnown) || (labels && (flags & O2V_HIP_CC_SEED_BORDER)))
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown flag bits in " + std::to_string(flags));
+    if (format == O2V_HIP_GRID_BITS && strides[0] != 1u) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "a BITS grid needs strides[0] == 1");
+    if (format == O2V_HIP_GRID_F32_BELOW && !std::isfinite(level)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "level must be finite");
+    for (int a = 0; a < 3; ++a)
+        if (dims[a] > kCcMaxDim) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "a grid of more than 65 536 voxels along an axis");
+    const uint64_t voxels = (uint64_t) dims[0] * dims[1] * dims[2];   // (below 2^48)
+    if (voxels > kCcMaxVoxels)
+        return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, std::to_string(voxels) + " voxels do not fit an int32 index (at most 2^31 - 1)");
+    if (n_seeds > kCcMaxVoxels) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "more than 2^31 - 1 seeds");
+    O2V_CHECK(hipSetDevice(ctx->device));
+    const uint32_t reach[3] = {format == O2V_HIP_GRID_BITS ? (dims[0] + 31u) / 32u : dims[0], dims[1], dims[2]};
+    uint64_t gbytes = 0, obytes = 0;
+    int rc;
+    if ((rc = check_grid(ctx, fn, "grid", grid, reach, strides, format == O2V_HIP_GRID_U8 ? 1u : 4u, false, &gbytes)) ||
+        (rc = labels ? check_grid(ctx, fn, "labels", labels, dims, out_strides, 4u, true, &obytes)
+                     : check_grid(ctx, fn, "out", out, dims, out_strides, 1u, true, &obytes)) ||
+        (n_seeds && (rc = check_device_range(ctx, fn, seeds, n_seeds * 12u, "seeds"))))
+        return rc;
+    const void *const dst = labels ? (const void *) labels : (const void *) out;
+    if (ranges_overlap(dst, obytes, grid, gbytes)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, std::string(labels ? "labels" : "out") + " and grid overlap");
+    if (n_seeds && ranges_overlap(dst, obytes, seeds, n_seeds * 12u)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "out and seeds overlap");
+
+    CcGrid g{};
+    g.nx = dims[0], g.ny = dims[1], g.nz = dims[2];
+    g.W = (dims[0] + 63u) / 64u;
+    g.tiles_y = (dims[1] + 7u) / 8u, g.tiles_z = (dims[2] + 7u) / 8u;
+    g.conn = connectivity;
+    g.words = cc_words(dims);
+    // the parents live in the caller's labels where linear index i is element i of them
+    const bool in_place = labels && (dims[0] == 1u || out_strides[0] == 1u) && (dims[1] == 1u || out_strides[1] == dims[0]) &&
+                          (dims[2] == 1u || out_strides[2] == (uint64_t) dims[0] * dims[1]);
+    const uint64_t n_blocks = (g.words + kBlock - 1) / kBlock;
+    if ((rc = grow_scratch(ctx, ctx->d_cc_bits, g.words, fn, "set bits")) || (rc = grow_scratch(ctx, ctx->d_cc_flags, g.words, fn, "flag bits")) ||
+        (rc = grow_scratch(ctx, ctx->d_cc_ctr, 4u, fn, "counters")) || (rc = grow_scratch(ctx, ctx->h_cc_ctr, 4u, fn, "counters")) ||
+        (labels && ((rc = grow_scratch(ctx, ctx->d_cc_local, g.words, fn, "prefixes")) ||
+                    (rc = grow_scratch(ctx, ctx->d_cc_boff, n_blocks + 1u, fn, "block offsets")))) ||
+        (!in_place && (rc = grow_scratch(ctx, ctx->d_cc_parent, voxels, fn, "parents"))))
+        return rc;
+    ctx->ktimes_on = false;   // (no per-launch brackets here; o2v_hip_voxelize sets the flag again from its params)
+    uint32_t *const P = in_place ? reinterpret_cast<uint32_t *>(labels) : ctx->d_cc_parent.ptr;
+    unsigned long long *const bits = ctx->d_cc_bits.ptr, *const fl = ctx->d_cc_flags.ptr, *const ctr = ctx->d_cc_ctr.ptr;
+    const RaySource src{grid, strides[0], strides[1], strides[2], level};
+    const uint64_t elem = format == O2V_HIP_GRID_U8 ? 1u : 4u;
+    const bool vec = strides[0] == 1u && (uintptr_t) grid % 16u == 0 && strides[1] * elem % 16u == 0 && strides[2] * elem % 16u == 0;
+    const uint32_t invert = (flags & O2V_HIP_CC_INVERT) ? 1u : 0u;
+    const bool count = (flags & O2V_HIP_FLAG_STAGE_TIMES) != 0;
+    const dim3 per_word(stream_grid(ctx, g.words * 64u, 16u)), per_group(stream_grid(ctx, (g.words + 15u) / 16u * 64u, 8u));
+    hipStream_t s = ctx->stream;
+    O2V_CHECK(ctx->cc_times.mark(0, s));
+    O2V_CHECK(hipMemsetAsync(ctr, 0, 4u * sizeof(unsigned long long), s));
+    if (format == O2V_HIP_GRID_BITS)
+        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayBits, false>), per_group, dim3(kBlock), 0, s, src, g, invert, bits);
+    else if (format == O2V_HIP_GRID_U8 && vec)
+        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayU8, true>), per_group, dim3(kBlock), 0, s, src, g, invert, bits);
+    else if (format == O2V_HIP_GRID_U8)
+        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayU8, false>), per_group, dim3(kBlock), 0, s, src, g, invert, bits);
+    else if (vec)
+        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayF32Below, true>), per_group, dim3(kBlock), 0, s, src, g, invert, bits);
+    else
+        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayF32Below, false>), per_group, dim3(kBlock), 0, s, src, g, invert, bits);
+    O2V_CHECK(ctx->cc_times.mark(1, s));
+    if (sw.cc_no_tiles) {
+        O2V_LAUNCH("k_cc_init", s, k_cc_init, per_word, dim3(kBlock), 0, s, g, bits, P);
+    } else {
+        const uint64_t tiles = (uint64_t) g.W * g.tiles_y * g.tiles_z;
+        O2V_LAUNCH("k_cc_tiles", s, k_cc_tiles, dim3((uint32_t) std::min<uint64_t>(tiles, kCcMaxGrid)), dim3(kBlock), 0, s, g, bits, P);
+    }
+    O2V_CHECK(ctx->cc_times.mark(2, s));
+    if (sw.cc_no_tiles && count)
+        O2V_LAUNCH("k_cc_seams", s, (k_cc_seams<true, true>), per_word, dim3(kBlock), 0, s, g, bits, P, ctr);
+    else if (sw.cc_no_tiles)
+        O2V_LAUNCH("k_cc_seams", s, (k_cc_seams<true, false>), per_word, dim3(kBlock), 0, s, g, bits, P, ctr);
+    else if (count)
+        O2V_LAUNCH("k_cc_seams", s, (k_cc_seams<false, true>), per_word, dim3(kBlock), 0, s, g, bits, P, ctr);
+    else
+        O2V_LAUNCH("k_cc_seams", s, (k_cc_seams<false, false>), per_word, dim3(kBlock), 0, s, g, bits, P, ctr);
+    O2V_CHECK(ctx->cc_times.mark(3, s));
+    if (labels) {
+        O2V_LAUNCH("k_cc_flatten", s, k_cc_flatten, per_word, dim3(kBlock), 0, s, g, bits, P, fl);
+        O2V_LAUNCH("k_cc_count", s, k_cc_count, dim3((uint32_t) n_blocks), dim3(kBlock), 0, s, fl, g.words, ctx->d_cc_local.ptr, ctx->d_cc_boff.ptr);
+        O2V_LAUNCH("k_fill_scan_blocks", s, k_fill_scan_blocks, dim3(1), dim3(kBlock), 0, s, ctx->d_cc_boff.ptr, n_blocks, ctx->d_cc_boff.ptr + n_blocks);
+        O2V_CHECK(ctx->cc_times.mark(4, s));
+        O2V_LAUNCH("k_cc_labels", s, k_cc_labels, per_word, dim3(kBlock), 0, s, g, bits, P, fl, ctx->d_cc_local.ptr, ctx->d_cc_boff.ptr, labels,
+                   out_strides[0], out_strides[1], out_strides[2]);
+        O2V_CHECK(hipMemcpyAsync(ctx->h_cc_ctr.ptr + 2, ctx->d_cc_boff.ptr + n_blocks, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    } else {
+        O2V_LAUNCH("k_cc_flatten", s, k_cc_flatten, per_word, dim3(kBlock), 0, s, g, bits, P, (unsigned long long *) nullptr);
+        O2V_CHECK(ctx->cc_times.mark(4, s));
+        O2V_CHECK(hipMemsetAsync(fl, 0, g.words * sizeof(unsigned long long), s));
+        if (n_seeds)
+            O2V_LAUNCH("k_cc_seed_list", s, k_cc_seed_list, dim3(stream_grid(ctx, n_seeds, 8u)), dim3(kBlock), 0, s, g, bits, P, seeds, n_seeds, fl);
+        if (flags & O2V_HIP_CC_SEED_BORDER) O2V_LAUNCH("k_cc_seed_border", s, k_cc_seed_border, per_word, dim3(kBlock), 0, s, g, bits, P, fl);
+        O2V_LAUNCH("k_cc_flood_out", s, k_cc_flood_out, per_word, dim3(kBlock), 0, s, g, bits, P, fl, (uint32_t) values[0], (uint32_t) values[1],
+                   (uint32_t) values[2], out, out_strides[0], out_strides[1], out_strides[2], ctr + 2);
+        O2V_CHECK(hipMemcpyAsync(ctx->h_cc_ctr.ptr + 2, ctr + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    }
+    O2V_CHECK(hipGetLastError());
+    O2V_CHECK(ctx->cc_times.mark(5, s));
+    O2V_CHECK(hipMemcpyAsync(ctx->h_cc_ctr.ptr, ctr, 2u * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    O2V_CHECK(hipStreamSynchronize(s));
+    O2V_CHECK(ctx->cc_times.finish());
+    ctx->cc_counters[0] = ctx->h_cc_ctr.ptr[0];
+    ctx->cc_counters[1] = ctx->h_cc_ctr.ptr[1];
+    *result = ctx->h_cc_ctr.ptr[2];
+    return O2V_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t o2v_hip_components_scratch_bytes(const uint32_t dims[3], uint32_t which)
+{
+    if (!dims || !dims[0] || !dims[1] || !dims[2] || which > O2V_HIP_CC_SCRATCH_FLOOD) return 0;
+    const uint64_t words = cc_words(dims), voxels = (uint64_t) dims[0] * dims[1] * dims[2];
+    if (which == O2V_HIP_CC_SCRATCH_FLOOD) return 16u * words + 4u * voxels + 32u;
+    return 20u * words + 8u * ((words + kBlock - 1) / kBlock + 1u) + 32u + (which == O2V_HIP_CC_SCRATCH_LABELS_STRIDED ? 4u * voxels : 0u);
+}
+
+int o2v_hip_components_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+                             uint32_t connectivity, uint32_t flags, int32_t *labels, const uint64_t label_strides[3], uint64_t *out_count)
+{
+    static const char fn[] = "o2v_hip_components_dense";
+    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
+    if (!labels) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
+    return cc_run(ctx, fn, grid, format, strides, dims, level, connectivity, flags, labels, nullptr, label_strides, nullptr, 0, nullptr, out_count);
+}
+
+int o2v_hip_flood_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+                        uint32_t connectivity, uint32_t flags, const int32_t *seeds, uint64_t n_seeds, const uint8_t values[3], uint8_t *out,
+                        const uint64_t out_strides[3], uint64_t *out_reached)
+{
+    static const char fn[] = "o2v_hip_flood_dense";
+    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
+    if (!out) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
+    return cc_run(ctx, fn, grid, format, strides, dims, level, connectivity, flags, nullptr, out, out_strides, seeds, n_seeds, values, out_reached);
+}
+
+int o2v_hip_components_times(const o2v_hip_ctx *ctx, float out_ms[5])
+{
+    return ctx ? ctx->cc_times.read(out_ms) : O2V_HIP_ERR_BAD_ARGUMENT;
+}
+
+int o2v_hip_components_counters(const o2v_hip_ctx *ctx, uint64_t out2[2])
+{
+    if (!ctx || !out2) return O2V_HIP_ERR_BAD_ARGUMENT;
+    out2[0] = ctx->cc_counters[0];
+    out2[1] = ctx->cc_counters[1];
+    return O2V_HIP_OK;
+}
 
 }  // extern "C"
 

@@ -11,7 +11,9 @@ tensor written on the device (o2v_hip_write_dense); nothing of either crosses to
 "sdf", and distance_transform on any label tensor) come from o2v_hip_distance_dense; mesh_distance is the
 narrow-band distance to the triangles themselves (o2v_hip_mesh_distance_dense); extract_surface turns a
 distance grid back into an indexed mesh (o2v_hip_surface_count / _write); RayCaster / raycast find the
-first solid voxel along rays through any of these grids (o2v_hip_raycast_build / o2v_hip_raycast).
+first solid voxel along rays through any of these grids (o2v_hip_raycast_build / o2v_hip_raycast, DESIGN.md section 14);
+components / flood and what is built on them (exterior, solidify, remove_small) say what is connected to what in them
+(o2v_hip_components_dense / o2v_hip_flood_dense).
 
 torch is imported first on purpose: the library must bind to the HIP runtime torch loaded (a process that loaded the library
 before torch holds two separate runtime copies, and this module refuses to work there).
@@ -37,6 +39,8 @@ MAX_SAMPLES = 65535  # samples per axis of one pass (x / y tiles above that are 
 MAX_BAND = 32.0      # mesh_distance: the widest band, in voxels
 MAX_SURFACE_EXTENT = 65536  # extract_surface: origin + shape per axis
 MAX_RAY_EXTENT = 65536      # RayCaster: origin + extent per axis
+MAX_CC_DIM = 65536          # components / flood: voxels per axis ...
+MAX_CC_VOXELS = 2 ** 31 - 1  # ... and in all: a linear index and a label are one int32
 
 
 def _require_shared_runtime():
@@ -366,6 +370,30 @@ def extract_surface(dv, field, level=0.0, *, origin=(0, 0, 0), transform=None, s
     return positions, faces
 
 
+def _grid_format(grid, level):
+    """(format, level as a float32 or None) of a grid tensor by its dtype - bool / uint8: GRID_U8, int32: GRID_BITS, float32
+    with a finite level: GRID_F32_BELOW -, as RayCaster, components and flood take it."""
+    if grid.dtype in (torch.bool, torch.uint8):
+        fmt = hip.GRID_U8
+    elif grid.dtype == torch.int32:
+        fmt = hip.GRID_BITS
+    elif grid.dtype == torch.float32:
+        fmt = hip.GRID_F32_BELOW
+    else:
+        raise TypeError(f"grid must be bool, uint8, int32 (bits) or float32, not {grid.dtype}")
+    if fmt == hip.GRID_F32_BELOW:
+        if level is None:
+            raise ValueError("a float32 grid needs level: a voxel is solid where grid < level")
+        if isinstance(level, bool) or not isinstance(level, numbers.Real) or not float("-inf") < float(level) < float("inf"):
+            raise ValueError(f"level must be a finite number, not {level!r}")
+        level = hip.C.c_float(float(level)).value
+        if not float("-inf") < level < float("inf"):
+            raise ValueError("level is not finite as a float32")
+    elif level is not None:
+        raise ValueError(f"level is for float32 grids, not {grid.dtype}")
+    return fmt, level
+
+
 class RayCaster:
     """First hits of rays in a dense grid on the voxelizer's device.
 
@@ -384,24 +412,7 @@ class RayCaster:
         device = _device(dv)
         if not isinstance(grid, torch.Tensor) or grid.dim() != 3:
             raise ValueError("grid must be a 3-D tensor [z, y, x]")
-        if grid.dtype in (torch.bool, torch.uint8):
-            fmt = hip.RAY_GRID_U8
-        elif grid.dtype == torch.int32:
-            fmt = hip.RAY_GRID_BITS
-        elif grid.dtype == torch.float32:
-            fmt = hip.RAY_GRID_F32_BELOW
-        else:
-            raise TypeError(f"grid must be bool, uint8, int32 (bits) or float32, not {grid.dtype}")
-        if fmt == hip.RAY_GRID_F32_BELOW:
-            if level is None:
-                raise ValueError("a float32 grid needs level: a voxel is solid where grid < level")
-            if isinstance(level, bool) or not isinstance(level, numbers.Real) or not float("-inf") < float(level) < float("inf"):
-                raise ValueError(f"level must be a finite number, not {level!r}")
-            level = hip.C.c_float(float(level)).value
-            if not float("-inf") < level < float("inf"):
-                raise ValueError("level is not finite as a float32")
-        elif level is not None:
-            raise ValueError(f"level is for float32 grids, not {grid.dtype}")
+        fmt, level = _grid_format(grid, level)
         if grid.device != device:
             raise ValueError(f"grid is on {grid.device}, the voxelizer on {device}")
         if 0 in grid.shape:
@@ -480,3 +491,135 @@ def camera_rays(width, height, eye, target, up, fov_y_degrees, device):
     directions = directions / directions.norm(dim=2, keepdim=True)
     origins = eye.expand(height, width, 3)
     return origins.to(torch.float32).contiguous().to(device), directions.to(torch.float32).contiguous().to(device)
+
+
+# ---- connected components and flood fill --------------------------------------------------------------
+
+def _cc_grid(dv, grid, level, connectivity):
+    """(device, format, level, (nx, ny, nz)) of a grid of components / flood, checked as RayCaster checks its own."""
+    _require_shared_runtime()
+    device = _device(dv)
+    if not isinstance(grid, torch.Tensor) or grid.dim() != 3:
+        raise ValueError("grid must be a 3-D tensor [z, y, x]")
+    fmt, level = _grid_format(grid, level)
+    if isinstance(connectivity, bool) or connectivity not in (6, 18, 26):
+        raise ValueError(f"connectivity must be 6, 18 or 26, not {connectivity!r}")
+    if grid.device != device:
+        raise ValueError(f"grid is on {grid.device}, the voxelizer on {device}")
+    if 0 in grid.shape:
+        raise ValueError("grid has an empty dimension")
+    if fmt == hip.GRID_BITS and grid.stride(2) != 1:
+        raise ValueError("a bits grid needs unit stride along x (its last dimension)")
+    nz, ny, nx = grid.shape
+    if fmt == hip.GRID_BITS:
+        nx *= 32
+    if max(nx, ny, nz) > MAX_CC_DIM or nx * ny * nz > MAX_CC_VOXELS:
+        raise ValueError(f"the grid's extent {(nx, ny, nz)} [x, y, z] is above {MAX_CC_DIM} along an axis or {MAX_CC_VOXELS} voxels in all")
+    return device, fmt, level, (nx, ny, nz)
+
+
+def components(dv, grid, *, level=None, connectivity=6, background=False, out=None):
+    """The connected components of a dense grid on the voxelizer's device.  Returns (labels, n): labels
+    int32 [z, y, x], 0 outside the set and 1 .. n inside it, the components numbered by their first voxel in [z, y, x] order -
+    the numbering of scipy.ndimage.label -, and n, their number.
+
+    grid:          as RayCaster takes it: bool or uint8 (solid where != 0), int32 (the words of fmt="bits"; labels then has 32
+                   voxels per word along x) or float32 with `level` (solid where grid < level).  It is only read.
+    connectivity:  6, 18 or 26: neighbours share a face; a face or an edge; a face, an edge or a corner.
+    background:    False: the components of the solid voxels; True: of the voxels of the box that are not solid.
+    out:           an int32 tensor of the labels' shape (any strides, not in grid's storage), written as it is; else a new
+                   contiguous tensor.  Contiguous labels need no per-voxel scratch in the context."""
+    device, fmt, level, dims = _cc_grid(dv, grid, level, connectivity)
+    shape = (dims[2], dims[1], dims[0])
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int32, device=device)
+    else:
+        _check_grid(out, "out", torch.int32, device, shape)
+    _sync(device)   # (the caller's writes to grid and out have landed)
+    n = dv.components_dense(grid.data_ptr(), fmt, _strides(grid), dims, 0.0 if level is None else level, connectivity,
+                            hip.CC_INVERT if background else 0, out.data_ptr(), _strides(out))
+    return out, n
+
+
+def _seeds(seeds, device):
+    """seeds as a contiguous int32 tensor [n, 3] on the device (None: no seeds)."""
+    if seeds is None:
+        return None
+    if not isinstance(seeds, torch.Tensor):
+        seeds = torch.as_tensor(seeds, dtype=torch.int64).reshape(-1, 3).to(device)
+    if seeds.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"seeds must be torch.int32 or torch.int64, not {seeds.dtype}")
+    if seeds.dim() != 2 or seeds.shape[1] != 3:
+        raise ValueError(f"seeds must have shape [n, 3] (x, y, z), not {tuple(seeds.shape)}")
+    if seeds.device != device:
+        raise ValueError(f"seeds is on {seeds.device}, the voxelizer on {device}")
+    if seeds.dtype == torch.int64:   # (a seed that does not fit an int32 is outside every box: it is ignored, as the call ignores it)
+        seeds = seeds.clamp(-1, 2 ** 31 - 1).to(torch.int32)
+    return seeds.contiguous()
+
+
+def flood(dv, grid, *, seeds=None, border=False, level=None, connectivity=6, background=False, values=(1, 0, 0), out=None):
+    """Flood fill from seeds: a uint8 tensor [z, y, x] that holds values[0] in the components of the
+    set that hold a seed, values[1] in its other components and values[2] outside the set.  grid, level, connectivity and
+    background as components takes them.
+
+    seeds:   an int32 / int64 tensor [n, 3] of (x, y, z) on the device, or a sequence of such triples; a seed outside the box
+             or not in the set is ignored.
+    border:  True: every voxel of the set on the six faces of the box is a seed as well.
+    values:  three integers 0 .. 255.
+    out:     a uint8 tensor of the grid's shape (any strides, not in grid's storage), or a bool tensor when the values are 0 / 1."""
+    device, fmt, level, dims = _cc_grid(dv, grid, level, connectivity)
+    shape = (dims[2], dims[1], dims[0])
+    values = tuple(values)
+    if len(values) != 3 or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 0 <= v <= 255 for v in values):
+        raise ValueError(f"values must be three integers 0 .. 255, not {values!r}")
+    seeds = _seeds(seeds, device)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=device)
+    elif isinstance(out, torch.Tensor) and out.dtype == torch.bool:
+        if any(v > 1 for v in values):
+            raise ValueError(f"a bool out needs values of 0 / 1, not {values!r}")
+        _check_grid(out, "out", torch.bool, device, shape)
+    else:
+        _check_grid(out, "out", torch.uint8, device, shape)
+    n = 0 if seeds is None else seeds.shape[0]
+    flags = (hip.CC_INVERT if background else 0) | (hip.CC_SEED_BORDER if border else 0)
+    _sync(device)   # (the caller's writes to grid, seeds and out have landed)
+    dv.flood_dense(grid.data_ptr(), fmt, _strides(grid), dims, 0.0 if level is None else level, connectivity, flags,
+                   seeds.data_ptr() if n else None, n, values, out.data_ptr(), _strides(out))
+    return out
+
+
+def exterior(dv, grid, *, level=None, connectivity=6):
+    """bool [z, y, x]: the empty voxels that reach the border of the box through empty voxels - flood with background=True,
+    border=True and values (1, 0, 0)."""
+    device, _, _, dims = _cc_grid(dv, grid, level, connectivity)
+    out = torch.empty((dims[2], dims[1], dims[0]), dtype=torch.bool, device=device)
+    return flood(dv, grid, border=True, level=level, connectivity=connectivity, background=True, values=(1, 0, 0), out=out)
+
+
+def solidify(dv, grid, *, level=None, connectivity=6, out=None):
+    """uint8 labels [z, y, x]: 1 = solid, 2 = empty but enclosed (no path of empty voxels to the border of the box), 0 =
+    exterior - one flood of the empty voxels from the border with values (0, 2, 1).  This is the format of fmt="labels",
+    fill=True, so distance_transform(..., "sdf"), RayCaster and extract_surface take it as it is, and on a single closed body it
+    is the same grid; where closed parts overlap it holds the union, which the parity rule of fill=True hollows out.
+
+    What it is not: a repair of the mesh.  A surface with a hole one voxel wide leaks - the flood gets in and the body has no
+    interior.  A pocket of outside air that surface voxels seal off - a dent closed by the voxels' thickness - counts as
+    interior.  `connectivity` is that of the empty space: 6 leaks least."""
+    return flood(dv, grid, border=True, level=level, connectivity=connectivity, background=True, values=(0, 2, 1), out=out)
+
+
+def component_sizes(labels, n):
+    """int64 [n + 1]: the voxels per label of components' (labels, n); index 0 is the background.  Plain torch."""
+    return torch.bincount(labels.reshape(-1), minlength=n + 1)
+
+
+def remove_small(dv, grid, min_voxels, *, level=None, connectivity=26):
+    """bool [z, y, x]: the solid voxels whose component has at least min_voxels voxels.  Plain torch over components."""
+    if isinstance(min_voxels, bool) or not isinstance(min_voxels, numbers.Integral) or min_voxels < 0:
+        raise ValueError(f"min_voxels must be an integer >= 0, not {min_voxels!r}")
+    labels, n = components(dv, grid, level=level, connectivity=connectivity)
+    keep = component_sizes(labels, n) >= min_voxels
+    keep[0] = False
+    return keep[labels.to(torch.int64)]

@@ -25,6 +25,9 @@ FLAG_FILL_INTERIOR = 8  # ... solid voxelization: the interior voxels (colour fi
 DENSE_U8, DENSE_ARGB32, DENSE_BITS = 0, 1, 2  # o2v_hip_write_dense formats
 DIST_SQ_I32, DIST_SDF_F32 = 0, 1  # o2v_hip_distance_dense formats
 RAY_GRID_U8, RAY_GRID_BITS, RAY_GRID_F32_BELOW = 0, 1, 2  # o2v_hip_raycast_build formats
+GRID_U8, GRID_BITS, GRID_F32_BELOW = 0, 1, 2  # the same formats, as o2v_hip_components_dense / o2v_hip_flood_dense name them
+CC_INVERT, CC_SEED_BORDER = 16, 32  # ... their flags (with FLAG_STAGE_TIMES: the counters)
+CC_SCRATCH_LABELS, CC_SCRATCH_LABELS_STRIDED, CC_SCRATCH_FLOOD = 0, 1, 2  # o2v_hip_components_scratch_bytes
 MESH_DIST_UNSIGNED_F32, MESH_DIST_SIGNED_F32 = 0, 1  # o2v_hip_mesh_distance_dense formats
 ERR_BAD_ARGUMENT = 3
 
@@ -131,6 +134,14 @@ def _bind():
     L.o2v_hip_raycast_generation.argtypes = [C.c_void_p]
     L.o2v_hip_raycast_generation.restype = C.c_uint64
     L.o2v_hip_raycast_times.argtypes = [C.c_void_p, C.c_void_p]
+    L.o2v_hip_components_dense.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_uint32, C.c_uint32,
+                                           C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    L.o2v_hip_flood_dense.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_uint32, C.c_uint32,
+                                      C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    L.o2v_hip_components_scratch_bytes.argtypes = [C.c_void_p, C.c_uint32]
+    L.o2v_hip_components_scratch_bytes.restype = C.c_uint64
+    L.o2v_hip_components_times.argtypes = [C.c_void_p, C.c_void_p]
+    L.o2v_hip_components_counters.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_max_slab_layers.argtypes = [C.c_void_p, C.POINTER(_Params), C.POINTER(C.c_uint32)]
     return L
 
@@ -183,6 +194,12 @@ def load_mesh_file(path):
 def raycast_scratch_bytes(dims):
     """o2v_hip_raycast_scratch_bytes: the context scratch the snapshot of a raycast_build over dims (x, y, z) takes."""
     return int(_bind().o2v_hip_raycast_scratch_bytes(_u32x3(dims)))
+
+
+def components_scratch_bytes(dims, which=CC_SCRATCH_LABELS):
+    """o2v_hip_components_scratch_bytes: the context scratch a components_dense (CC_SCRATCH_LABELS: contiguous labels,
+    CC_SCRATCH_LABELS_STRIDED: any other) or flood_dense (CC_SCRATCH_FLOOD) call over dims (x, y, z) takes."""
+    return int(_bind().o2v_hip_components_scratch_bytes(_u32x3(dims), which))
 
 
 def device_count():
@@ -353,6 +370,42 @@ class DeviceVoxelizer:
     def raycast_times(self):
         """o2v_hip_raycast_times: the device times (ms) of the last raycast_build and the last raycast."""
         return self._stage_times("o2v_hip_raycast_times", 2)
+
+    def components_dense(self, grid_ptr, fmt, strides, dims, level, connectivity, flags, labels_ptr, label_strides):
+        """o2v_hip_components_dense: the connected components (connectivity 6, 18 or 26) of the set of the grid at device address
+        grid_ptr (GRID_U8: element != 0; GRID_BITS; GRID_F32_BELOW: float32 < level; CC_INVERT in flags: the complement inside the
+        box) into int32 labels at labels_ptr, 1 + the rank of a voxel's component by its smallest linear index, 0 outside the
+        set; strides in elements and dims per axis x, y, z.  Returns the number of components."""
+        n = C.c_uint64(0)
+        self._check(self._L.o2v_hip_components_dense(self._ctx, grid_ptr, fmt, _u64x3(strides), _u32x3(dims), float(level), connectivity, flags,
+                                                     labels_ptr, _u64x3(label_strides), C.byref(n)), "o2v_hip_components_dense")
+        return n.value
+
+    def flood_dense(self, grid_ptr, fmt, strides, dims, level, connectivity, flags, seeds_ptr, n_seeds, values, out_ptr, out_strides):
+        """o2v_hip_flood_dense: uint8 out = values[0] in the components of the set that hold a seed (int32 [n_seeds, 3] local
+        (x, y, z) at device address seeds_ptr; CC_SEED_BORDER in flags: and the set's voxels on the box's faces), values[1] in
+        the others, values[2] outside the set.  Returns the number of voxels that got values[0]."""
+        n = C.c_uint64(0)
+        v = (C.c_uint8 * 3)(*[int(x) for x in values])
+        self._check(self._L.o2v_hip_flood_dense(self._ctx, grid_ptr, fmt, _u64x3(strides), _u32x3(dims), float(level), connectivity, flags,
+                                                seeds_ptr, n_seeds, v, out_ptr, _u64x3(out_strides), C.byref(n)), "o2v_hip_flood_dense")
+        return n.value
+
+    def components_scratch_bytes(self, dims, which=CC_SCRATCH_LABELS):
+        """o2v_hip_components_scratch_bytes: the context scratch a components_dense / flood_dense call over dims (x, y, z) takes."""
+        return components_scratch_bytes(dims, which)
+
+    def components_times(self):
+        """o2v_hip_components_times: the device times (ms) of the last components_dense / flood_dense call's classify, tile,
+        seam, flatten (+ root count) and write (+ seeds) stages."""
+        return self._stage_times("o2v_hip_components_times", 5)
+
+    def components_counters(self):
+        """o2v_hip_components_counters: (pairs united across tile seams, atomic mins that went round again) of the last call
+        made with FLAG_STAGE_TIMES in its flags."""
+        out = (C.c_uint64 * 2)()
+        self._check(self._L.o2v_hip_components_counters(self._ctx, out), "o2v_hip_components_counters")
+        return int(out[0]), int(out[1])
 
     def set_textures(self, textures):
         """textures: sequence of (uint8 [h, w, c] pixels, wrap) with c in (3, 4)."""

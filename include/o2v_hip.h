@@ -29,7 +29,8 @@ enum {
     O2V_HIP_ERR_HIP = 2,           /* a HIP call failed; see o2v_hip_last_error */
     O2V_HIP_ERR_BAD_ARGUMENT = 3,
     O2V_HIP_ERR_OUT_OF_MEMORY = 4,
-    O2V_HIP_ERR_LIMIT = 5          /* mesh exceeds an implementation limit (e.g. >= 2^29 triangles) */
+    O2V_HIP_ERR_LIMIT = 5,         /* mesh exceeds an implementation limit (e.g. >= 2^29 triangles) */
+    O2V_HIP_ERR_IO = 6             /* o2v_hip_gather_save: the file cannot be opened, is of no output type, or stopped taking voxels */
 };
 
 /* triangle material types: reference src/triangle.hpp:21-29 */
@@ -521,6 +522,69 @@ int o2v_hip_components_times(const o2v_hip_ctx *ctx, float out_ms[5]);
 /* Of the last call made with O2V_HIP_FLAG_STAGE_TIMES (else zeros): the pairs united across tile seams (every pair with
  * O2V_CC_NO_TILES=1) and the atomic mins that did not meet a root and went round again. */
 int o2v_hip_components_counters(const o2v_hip_ctx *ctx, uint64_t out2[2]);
+
+/* ---- dense grids as voxel lists and voxel files -------------------------------------------------------
+ *
+ * The way back from a dense grid to (x, y, z, argb) records - the layout of o2v_hip_read_voxels - and to the voxel files of
+ * obj2voxel_voxelize(), defined so that a numpy restatement reproduces every bit.
+ *
+ * The set.  grid, format (O2V_HIP_GRID_U8 / _BITS / _F32_BELOW), strides, dims and level are those of o2v_hip_components_dense:
+ * the grid is only read, a stride may be 0, BITS needs strides[0] == 1, a NaN is not below the level.  Voxel (x, y, z) of the
+ * box is solid by those rules.
+ *
+ * Records.  The solid voxels are taken in ascending linear index (z * ny + y) * nx + x - the order of numpy.nonzero on a
+ * [z, y, x] array.  Record i is four uint32: (origin[0] + x, origin[1] + y, origin[2] + z, argb).  The colour by color_mode:
+ *   O2V_HIP_GATHER_COLOR_CONSTANT   the call's argb;
+ *   O2V_HIP_GATHER_COLOR_GRID       colors[x * color_strides[0] + y * color_strides[1] + z * color_strides[2]]: a uint32 grid in
+ *                                   device memory, strides in elements (what o2v_hip_write_dense ARGB32 writes); only read, a
+ *                                   stride may be 0;
+ *   O2V_HIP_GATHER_COLOR_PALETTE    (format U8 only) palette[v], v the voxel's byte, palette uint32[256] in HOST memory, copied
+ *                                   by the call.
+ *
+ * o2v_hip_gather_count is the only pass over the grid.  It keeps the set's bits and the offsets of the records in scratch of the
+ * context and returns the number of solid voxels - a uint64: the count has no 32-bit limit.
+ *
+ * o2v_hip_gather_write fills records [first, first + n) of that numbering into `records` ([n][4] uint32, device memory, 16-byte
+ * aligned), contiguously; it may be repeated with any ranges in any order, so that no caller needs memory for all 16 bytes per
+ * voxel at once.  n = 0 launches nothing and reads no pointer.  It must follow an o2v_hip_gather_count with the same grid
+ * pointer, format, strides, dims and level (else O2V_HIP_ERR_BAD_ARGUMENT, "no matching o2v_hip_gather_count"; another count
+ * or save, refused or not, replaces the last one).  Occupancy comes from the kept bits only: a grid that changes between the two
+ * calls changes no coordinate and nothing is written outside `records`; with PALETTE the byte read then may give another colour
+ * (with GRID the colours are read at the time of the write), and that is all.
+ *
+ * o2v_hip_gather_save is the count, then ranges of 2^20 records written to two device buffers of 16 MiB and copied into two
+ * page-locked host buffers while the sink consumes the batch before - into the file sink of obj2voxel_voxelize() for `path`,
+ * the format from `type` (an extension without dot) or, if type is NULL, from the path's extension; `resolution` is the grid
+ * resolution the paletted formats record.  The file holds exactly what obj2voxel_voxelize() would have written for those
+ * records in that order.  *out_count: the voxels written.  O2V_HIP_ERR_IO: the path cannot be opened, the type is not an output
+ * format (VL32, PLY, XYZRGB, QEF, VOX), or the sink stopped accepting voxels; the message is in o2v_hip_last_error.
+ *
+ * Refused before any launch, records and file untouched: null arguments - except colors, color_strides and palette where the
+ * mode does not read them, and those and records where n = 0 -, zero dims, an unknown format or colour mode, PALETTE with a
+ * format other than U8, BITS with strides[0] != 1, a level that is not finite (F32_BELOW only), first + n above the counted
+ * total, records not 16-byte aligned or overlapping the grid or colors, a pointer that is not device memory of the context's
+ * device with its whole extent inside its allocation, for save origin[a] + dims[a] > resolution (O2V_HIP_ERR_BAD_ARGUMENT); a dim
+ * above 65 536, origin[a] + dims[a] above 2^32, more than 2^31 - 1 words = ceil(nx / 64) * ny * nz (O2V_HIP_ERR_LIMIT).  A failed
+ * scratch or staging allocation returns O2V_HIP_ERR_OUT_OF_MEMORY and leaves the context usable.  All calls run on the context's
+ * stream and return when their results have landed (the caller must have finished writing the grid and the colours).
+ *
+ * Scratch of the context, grown on demand (o2v_hip_gather_scratch_bytes; 0 for zero dims): 12 * words + 8 * (ceil(words / 256)
+ * + 1) + 1032 - a 64-bit word per 64 voxels along x, a 32-bit prefix per word, a 64-bit offset per block of 256 words and the
+ * count, the palette and the block of a range's first record.  o2v_hip_gather_save adds 2 x 16 MiB of device and 2 x 16 MiB of
+ * page-locked host memory, kept by the context. */
+enum { O2V_HIP_GATHER_COLOR_CONSTANT = 0, O2V_HIP_GATHER_COLOR_GRID = 1, O2V_HIP_GATHER_COLOR_PALETTE = 2 };
+int o2v_hip_gather_count(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+                         uint64_t *out_count);
+int o2v_hip_gather_write(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+                         const uint32_t origin[3], uint32_t color_mode, uint32_t argb, const uint32_t *colors, const uint64_t color_strides[3],
+                         const uint32_t *palette /* [256], host */, uint64_t first, uint64_t n, uint32_t *records /* [n][4], device */);
+int o2v_hip_gather_save(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+                        const uint32_t origin[3], uint32_t color_mode, uint32_t argb, const uint32_t *colors, const uint64_t color_strides[3],
+                        const uint32_t *palette /* [256], host */, const char *path, const char *type, uint32_t resolution, uint64_t *out_count);
+uint64_t o2v_hip_gather_scratch_bytes(const uint32_t dims[3]);
+/* The device times (ms) of the last count's classify and count + scan stages and of the last write (0 after a count; after a
+ * save: of its last batch). */
+int o2v_hip_gather_times(const o2v_hip_ctx *ctx, float out_ms[3]);
 
 int o2v_hip_get_timings(const o2v_hip_ctx *ctx, o2v_hip_timings *out);
 /* Per-kernel device times of the last o2v_hip_voxelize call made with O2V_HIP_FLAG_KERNEL_TIMES (else none): up to

@@ -34,6 +34,8 @@
 //                              bit-packed occupancy; outside the pipeline
 //   K12 k_cc_*                 o2v_hip_components_dense / o2v_hip_flood_dense: connected components and flood fill of a dense
 //                              grid, a union-find over its voxels ; outside the pipeline
+//   K13 k_gather_*             o2v_hip_gather_count / _write / _save: the solid voxels of a dense grid as (x, y, z, argb)
+//                              records, in ranges, and as a voxel file; outside the pipeline
 //   plan k_zhist               o2v_hip_plan_slabs: predicted hits per z layer -> work-balanced slabs for N GPUs
 // With the direct MAX path K1's counters reach the host while K2 runs, and only the stages that have work are enqueued
 // behind it.  N > 1 GPUs: o2v_hip_voxelize_sharded (bounds / work-histogram passes sharded over the ranks, RCCL).
@@ -44,6 +46,7 @@
 #include "../../include/o2v_hip.h"
 #include "o2v_comm.hpp"
 #include "o2v_device_internal.hpp"
+#include "o2v_io.hpp"
 
 #ifndef O2V_BUILD_ID
 #define O2V_BUILD_ID "unknown"  // the Makefile passes the hash of the device sources
@@ -81,6 +84,7 @@ namespace {
 #include "o2v_dev_k10_surface.hpp"
 #include "o2v_dev_k11_raycast.hpp"
 #include "o2v_dev_k12_components.hpp"
+#include "o2v_dev_k13_gather.hpp"
 
 }  // namespace
 
@@ -361,6 +365,27 @@ struct o2v_hip_ctx {
     PinnedArray<unsigned long long> h_cc_ctr;
     StageTimes<5> cc_times;
     uint64_t cc_counters[2] = {};
+
+    // K13 (o2v_hip_gather_count / _write / _save): the bits of the set, the per-word prefixes, the block offsets (+ the count),
+    // the block of a range's first record and the palette, grown on demand; the grid they were counted for; the two record
+    // buffers and page-locked batches of _save (allocated by its first call); the times of the three stages
+    DevArray<unsigned long long> d_ga_bits, d_ga_boff, d_ga_first;
+    DevArray<uint32_t> d_ga_local, d_ga_palette;
+    PinnedArray<unsigned long long> h_ga_ctr;
+    PinnedArray<uint32_t> h_ga_palette;
+    DevArray<uint4> d_ga_rec[2];
+    PinnedArray<uint32_t> h_ga_rec[2];
+    Event ev_ga_rec[2];
+    StageTimes<3> ga_times;
+    struct GatherCount {
+        bool valid = false;
+        const void *grid = nullptr;
+        uint32_t format = 0;
+        uint64_t strides[3] = {};
+        uint32_t dims[3] = {};
+        float level = 0.f;
+        uint64_t total = 0;
+    } ga;
 
     // results of the last run
     uint64_t n_vox = 0;
@@ -3213,6 +3238,309 @@ int o2v_hip_components_counters(const o2v_hip_ctx *ctx, uint64_t out2[2])
     out2[0] = ctx->cc_counters[0];
     out2[1] = ctx->cc_counters[1];
     return O2V_HIP_OK;
+}
+
+}  // extern "C"
+
+// ---- K13: the solid voxels of a dense grid as (x, y, z, argb) records ---------------------------------------------------------
+
+namespace {
+
+constexpr uint32_t kGaMaxDim = 65536;
+constexpr uint64_t kGaMaxWords = 0x7fffffffull;   // a word index is one uint32 in k_gather_write
+constexpr uint64_t kGaMaxGrid = 1ull << 20;       // workgroups of k_gather_count; more blocks are taken in turns
+constexpr uint64_t kGaBatch = 1u << 20;           // records per batch of o2v_hip_gather_save: the batch of drain_to_sink (o2v_api.cpp)
+
+// what the three calls check of the grid; *g: its words, *gbytes: its reach
+int ga_grid(o2v_hip_ctx *ctx, const char *fn, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+            GaGrid *g, uint64_t *gbytes)
+{
+    if (!grid || !strides || !dims) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
+    if (!dims[0] || !dims[1] || !dims[2]) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "zero dims");
+    if (format != O2V_HIP_GRID_U8 && format != O2V_HIP_GRID_BITS && format != O2V_HIP_GRID_F32_BELOW)
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown format " + std::to_string(format));
+    if (format == O2V_HIP_GRID_BITS && strides[0] != 1u) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "a BITS grid needs strides[0] == 1");
+    if (format == O2V_HIP_GRID_F32_BELOW && !std::isfinite(level)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "level must be finite");
+    for (int a = 0; a < 3; ++a)
+        if (dims[a] > kGaMaxDim) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "a grid of more than 65 536 voxels along an axis");
+    const uint64_t words = cc_words(dims);   // (below 2^43)
+    if (words > kGaMaxWords) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, std::to_string(words) + " words of 64 voxels along x (at most 2^31 - 1)");
+    O2V_CHECK(hipSetDevice(ctx->device));
+    const uint32_t reach[3] = {format == O2V_HIP_GRID_BITS ? (dims[0] + 31u) / 32u : dims[0], dims[1], dims[2]};
+    if (int rc = check_grid(ctx, fn, "grid", grid, reach, strides, format == O2V_HIP_GRID_U8 ? 1u : 4u, false, gbytes)) return rc;
+    g->nx = dims[0], g->ny = dims[1], g->nz = dims[2];
+    g->W = (dims[0] + 63u) / 64u;
+    g->words = words;
+    g->n_blocks = (words + kBlock - 1) / kBlock;
+    return O2V_HIP_OK;
+}
+
+// what _write and _save check of the origin and the colour mode (nothing is read through a pointer here)
+int ga_mode(o2v_hip_ctx *ctx, const char *fn, uint32_t format, const uint32_t dims[3], const uint32_t origin[3], uint32_t color_mode)
+{
+    if (!origin) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
+    if (color_mode != O2V_HIP_GATHER_COLOR_CONSTANT && color_mode != O2V_HIP_GATHER_COLOR_GRID && color_mode != O2V_HIP_GATHER_COLOR_PALETTE)
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown color_mode " + std::to_string(color_mode));
+    if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE && format != O2V_HIP_GRID_U8)
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "O2V_HIP_GATHER_COLOR_PALETTE needs a U8 grid");
+    for (int a = 0; a < 3; ++a)
+        if ((uint64_t) origin[a] + dims[a] > (1ull << 32)) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "origin + dims is above 2^32 along an axis");
+    return O2V_HIP_OK;
+}
+
+// the pointers the colour mode reads; *cbytes: the reach of colors (GRID)
+int ga_color_source(o2v_hip_ctx *ctx, const char *fn, const uint32_t dims[3], uint32_t color_mode, const uint32_t *colors,
+                    const uint64_t color_strides[3], const uint32_t *palette, uint64_t *cbytes)
+{
+    *cbytes = 0;
+    if (color_mode == O2V_HIP_GATHER_COLOR_GRID) {
+        if (!colors || !color_strides) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
+        return check_grid(ctx, fn, "colors", colors, dims, color_strides, 4u, false, cbytes);
+    }
+    if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE && !palette) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
+    return O2V_HIP_OK;
+}
+
+bool ga_matches(const o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level)
+{
+    const o2v_hip_ctx::GatherCount &c = ctx->ga;
+    return c.valid && c.grid == grid && c.format == format && std::equal(strides, strides + 3, c.strides) && std::equal(dims, dims + 3, c.dims) &&
+           std::memcmp(&c.level, &level, sizeof(float)) == 0;
+}
+
+// classify, count and scan; the count is kept in the context and returned
+int ga_count(o2v_hip_ctx *ctx, const char *fn, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+             const GaGrid &g, uint64_t *out_count)
+{
+    int rc;
+    if ((rc = grow_scratch(ctx, ctx->d_ga_bits, g.words, fn, "set bits")) || (rc = grow_scratch(ctx, ctx->d_ga_local, g.words, fn, "prefixes")) ||
+        (rc = grow_scratch(ctx, ctx->d_ga_boff, g.n_blocks + 1u, fn, "block offsets")) || (rc = grow_scratch(ctx, ctx->d_ga_first, 1u, fn, "range")) ||
+        (rc = grow_scratch(ctx, ctx->d_ga_palette, 256u, fn, "palette")) || (rc = grow_scratch(ctx, ctx->h_ga_palette, 256u, fn, "palette")) ||
+        (rc = grow_scratch(ctx, ctx->h_ga_ctr, 1u, fn, "counters")))
+        return rc;
+    ctx->ktimes_on = false;   // (no per-launch brackets here; o2v_hip_voxelize sets the flag again from its params)
+    CcGrid cg{};
+    cg.nx = g.nx, cg.ny = g.ny, cg.nz = g.nz, cg.W = g.W, cg.words = g.words;
+    unsigned long long *const bits = ctx->d_ga_bits.ptr, *const boff = ctx->d_ga_boff.ptr;
+    const RaySource src{grid, strides[0], strides[1], strides[2], level};
+    const uint64_t elem = format == O2V_HIP_GRID_U8 ? 1u : 4u;
+    const bool vec = strides[0] == 1u && (uintptr_t) grid % 16u == 0 && strides[1] * elem % 16u == 0 && strides[2] * elem % 16u == 0;
+    const dim3 per_group(stream_grid(ctx, (g.words + 15u) / 16u * 64u, 8u));
+    hipStream_t s = ctx->stream;
+    O2V_CHECK(ctx->ga_times.mark(0, s));
+    if (format == O2V_HIP_GRID_BITS)
+        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayBits, false>), per_group, dim3(kBlock), 0, s, src, cg, 0u, bits);
+    else if (format == O2V_HIP_GRID_U8 && vec)
+        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayU8, true>), per_group, dim3(kBlock), 0, s, src, cg, 0u, bits);
+    else if (format == O2V_HIP_GRID_U8)
+        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayU8, false>), per_group, dim3(kBlock), 0, s, src, cg, 0u, bits);
+    else if (vec)
+        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayF32Below, true>), per_group, dim3(kBlock), 0, s, src, cg, 0u, bits);
+    else
+        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayF32Below, false>), per_group, dim3(kBlock), 0, s, src, cg, 0u, bits);
+    O2V_CHECK(ctx->ga_times.mark(1, s));
+    O2V_LAUNCH("k_gather_count", s, k_gather_count, dim3((uint32_t) std::min<uint64_t>(g.n_blocks, kGaMaxGrid)), dim3(kBlock), 0, s, bits, g,
+               ctx->d_ga_local.ptr, boff);
+    // (the count goes behind the offsets: entry n_blocks)
+    O2V_LAUNCH("k_fill_scan_blocks", s, k_fill_scan_blocks, dim3(1), dim3(kBlock), 0, s, boff, g.n_blocks, boff + g.n_blocks);
+    O2V_CHECK(hipGetLastError());
+    O2V_CHECK(ctx->ga_times.mark(2, s));
+    O2V_CHECK(hipMemcpyAsync(ctx->h_ga_ctr.ptr, boff + g.n_blocks, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    O2V_CHECK(hipStreamSynchronize(s));
+    O2V_CHECK(ctx->ga_times.elapsed(0, 1, ctx->ga_times.ms[0]));
+    O2V_CHECK(ctx->ga_times.elapsed(1, 2, ctx->ga_times.ms[1]));
+    ctx->ga_times.ms[2] = 0.f;
+#ifdef O2V_GA_MUTATE_COUNT32
+    const uint64_t total = (uint32_t) ctx->h_ga_ctr.ptr[0];   // (test only: the count truncated where the host reads it)
+#else
+    const uint64_t total = ctx->h_ga_ctr.ptr[0];
+#endif
+    o2v_hip_ctx::GatherCount &c = ctx->ga;
+    c.valid = true;
+    c.grid = grid;
+    c.format = format;
+    std::copy(strides, strides + 3, c.strides);
+    std::copy(dims, dims + 3, c.dims);
+    c.level = level;
+    c.total = total;
+    *out_count = total;
+    return O2V_HIP_OK;
+}
+
+// the palette into the context's device copy (on the stream)
+int ga_upload_palette(o2v_hip_ctx *ctx, const uint32_t *palette)
+{
+    std::memcpy(ctx->h_ga_palette.ptr, palette, 256u * sizeof(uint32_t));
+    O2V_CHECK(hipMemcpyAsync(ctx->d_ga_palette.ptr, ctx->h_ga_palette.ptr, 256u * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    return O2V_HIP_OK;
+}
+
+// records [first, first + n) of the last count into `records`, enqueued on the stream (n > 0; events 2 and 3 of ga_times around it)
+int ga_launch_write(o2v_hip_ctx *ctx, const GaGrid &g, uint64_t first, uint64_t n, const uint32_t origin[3], uint32_t color_mode,
+                    const GaColor &col, uint32_t *records)
+{
+    hipStream_t s = ctx->stream;
+    const unsigned long long *const boff = ctx->d_ga_boff.ptr;
+    uint4 *const out = reinterpret_cast<uint4 *>(records);
+    // a workgroup per block the range may touch: one per 2^14 records and the two at its ends, and no more than fill the device
+    const dim3 blocks((uint32_t) std::min<uint64_t>(std::min<uint64_t>(g.n_blocks, n / 64u + 2u), (uint64_t) ctx->num_cus * 8u));
+    O2V_CHECK(hipEventRecord(ctx->ga_times.ev[2], s));
+    O2V_LAUNCH("k_gather_find", s, k_gather_find, dim3(1), dim3(kBlock), 0, s, boff, g.n_blocks, first, ctx->d_ga_first.ptr);
+    if (color_mode == O2V_HIP_GATHER_COLOR_GRID)
+        O2V_LAUNCH("k_gather_write", s, k_gather_write<kGaColorGrid>, blocks, dim3(kBlock), 0, s, g, ctx->d_ga_bits.ptr, ctx->d_ga_local.ptr, boff,
+                   ctx->d_ga_first.ptr, first, n, origin[0], origin[1], origin[2], col, out);
+    else if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE)
+        O2V_LAUNCH("k_gather_write", s, k_gather_write<kGaColorPalette>, blocks, dim3(kBlock), 0, s, g, ctx->d_ga_bits.ptr, ctx->d_ga_local.ptr, boff,
+                   ctx->d_ga_first.ptr, first, n, origin[0], origin[1], origin[2], col, out);
+    else
+        O2V_LAUNCH("k_gather_write", s, k_gather_write<kGaColorConstant>, blocks, dim3(kBlock), 0, s, g, ctx->d_ga_bits.ptr, ctx->d_ga_local.ptr, boff,
+                   ctx->d_ga_first.ptr, first, n, origin[0], origin[1], origin[2], col, out);
+    O2V_CHECK(hipGetLastError());
+    O2V_CHECK(hipEventRecord(ctx->ga_times.ev[3], s));
+    return O2V_HIP_OK;
+}
+
+GaColor ga_color(const o2v_hip_ctx *ctx, const void *grid, const uint64_t strides[3], uint32_t color_mode, uint32_t argb, const uint32_t *colors,
+                 const uint64_t color_strides[3])
+{
+    GaColor col{};
+    col.argb = argb;
+    if (color_mode == O2V_HIP_GATHER_COLOR_GRID) col.colors = colors, col.c0 = color_strides[0], col.c1 = color_strides[1], col.c2 = color_strides[2];
+    if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE) {
+        col.grid = static_cast<const uint8_t *>(grid);
+        col.s0 = strides[0], col.s1 = strides[1], col.s2 = strides[2];
+        col.palette = ctx->d_ga_palette.ptr;
+    }
+    return col;
+}
+
+bool ga_output_format(FileFormat f)
+{
+    return f == FileFormat::VL32 || f == FileFormat::PLY || f == FileFormat::XYZRGB || f == FileFormat::QEF || f == FileFormat::VOX;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t o2v_hip_gather_scratch_bytes(const uint32_t dims[3])
+{
+    if (!dims || !dims[0] || !dims[1] || !dims[2]) return 0;
+    const uint64_t words = cc_words(dims);
+    return 12u * words + 8u * ((words + kBlock - 1) / kBlock + 1u) + 1024u + 8u;
+}
+
+int o2v_hip_gather_count(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+                         uint64_t *out_count)
+{
+    static const char fn[] = "o2v_hip_gather_count";
+    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
+    ctx->ga.valid = false;
+    if (!out_count) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
+    GaGrid g{};
+    uint64_t gbytes = 0;
+    if (int rc = ga_grid(ctx, fn, grid, format, strides, dims, level, &g, &gbytes)) return rc;
+    return ga_count(ctx, fn, grid, format, strides, dims, level, g, out_count);
+}
+
+int o2v_hip_gather_write(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+                         const uint32_t origin[3], uint32_t color_mode, uint32_t argb, const uint32_t *colors, const uint64_t color_strides[3],
+                         const uint32_t *palette, uint64_t first, uint64_t n, uint32_t *records)
+{
+    static const char fn[] = "o2v_hip_gather_write";
+    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
+    GaGrid g{};
+    uint64_t gbytes = 0, cbytes = 0;
+    int rc;
+    if ((rc = ga_grid(ctx, fn, grid, format, strides, dims, level, &g, &gbytes)) || (rc = ga_mode(ctx, fn, format, dims, origin, color_mode))) return rc;
+    if (!ga_matches(ctx, grid, format, strides, dims, level))
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "no matching o2v_hip_gather_count (the same grid, format, strides, dims and level)");
+    const uint64_t total = ctx->ga.total;
+    if (first > total || n > total - first)
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn,
+                      "records " + std::to_string(first) + " + " + std::to_string(n) + " reach past the counted " + std::to_string(total));
+    if (n == 0) return O2V_HIP_OK;
+    if (!records) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
+    if ((rc = ga_color_source(ctx, fn, dims, color_mode, colors, color_strides, palette, &cbytes))) return rc;
+    if (n > (~0ull >> 4)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "records: n * 16 bytes reach past any allocation");
+    if ((uintptr_t) records % 16u) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "records must be 16-byte aligned");
+    if ((rc = check_device_range(ctx, fn, records, n * 16u, "records"))) return rc;
+    if (ranges_overlap(records, n * 16u, grid, gbytes)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "records and grid overlap");
+    if (cbytes && ranges_overlap(records, n * 16u, colors, cbytes)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "records and colors overlap");
+    ctx->ktimes_on = false;
+    if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE && (rc = ga_upload_palette(ctx, palette))) return rc;
+    if ((rc = ga_launch_write(ctx, g, first, n, origin, color_mode, ga_color(ctx, grid, strides, color_mode, argb, colors, color_strides), records)))
+        return rc;
+    O2V_CHECK(hipStreamSynchronize(ctx->stream));
+    O2V_CHECK(ctx->ga_times.elapsed(2, 3, ctx->ga_times.ms[2]));
+    return O2V_HIP_OK;
+}
+
+int o2v_hip_gather_save(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+                        const uint32_t origin[3], uint32_t color_mode, uint32_t argb, const uint32_t *colors, const uint64_t color_strides[3],
+                        const uint32_t *palette, const char *path, const char *type, uint32_t resolution, uint64_t *out_count)
+{
+    static const char fn[] = "o2v_hip_gather_save";
+    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
+    ctx->ga.valid = false;
+    if (!path || !out_count) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
+    GaGrid g{};
+    uint64_t gbytes = 0, cbytes = 0;
+    int rc;
+    if ((rc = ga_grid(ctx, fn, grid, format, strides, dims, level, &g, &gbytes)) || (rc = ga_mode(ctx, fn, format, dims, origin, color_mode)) ||
+        (rc = ga_color_source(ctx, fn, dims, color_mode, colors, color_strides, palette, &cbytes)))
+        return rc;
+    for (int a = 0; a < 3; ++a)
+        if ((uint64_t) origin[a] + dims[a] > resolution)
+            return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "origin + dims is above the resolution " + std::to_string(resolution) + " along an axis");
+    const FileFormat file_format = detect_format(path, type);
+    if (!ga_output_format(file_format))
+        return refuse(ctx, O2V_HIP_ERR_IO, fn, std::string("\"") + (type ? type : path) + "\" is not an output format (VL32, PLY, XYZRGB, QEF, VOX)");
+    uint64_t total = 0;
+    if ((rc = ga_count(ctx, fn, grid, format, strides, dims, level, g, &total))) return rc;
+    for (int k = 0; k < 2; ++k) {
+        if ((rc = grow_scratch(ctx, ctx->d_ga_rec[k], kGaBatch, fn, "record buffer")) || (rc = grow_scratch(ctx, ctx->h_ga_rec[k], kGaBatch * 4u, fn, "staging")))
+            return rc;
+        O2V_CHECK(ctx->ev_ga_rec[k].create_sync());
+    }
+    std::unique_ptr<VoxelSink> sink = open_file_sink(path, file_format, resolution);
+    if (!sink) return refuse(ctx, O2V_HIP_ERR_IO, fn, std::string("cannot open \"") + path + "\" for writing");
+    sink->expect(total);
+    const GaColor col = ga_color(ctx, grid, strides, color_mode, argb, colors, color_strides);
+    if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE && (rc = ga_upload_palette(ctx, palette))) return rc;
+    hipStream_t s = ctx->stream;
+    const uint64_t batches = (total + kGaBatch - 1) / kGaBatch;
+    // Two record buffers and two page-locked batches: while the sink consumes one batch the next is written and copied.
+    auto start = [&](uint64_t k) -> int {
+        const uint64_t first = k * kGaBatch, n = std::min<uint64_t>(kGaBatch, total - first);
+        if (int e = ga_launch_write(ctx, g, first, n, origin, color_mode, col, reinterpret_cast<uint32_t *>(ctx->d_ga_rec[k & 1].ptr))) return e;
+        O2V_CHECK(hipMemcpyAsync(ctx->h_ga_rec[k & 1].ptr, ctx->d_ga_rec[k & 1].ptr, n * 16u, hipMemcpyDeviceToHost, s));
+        O2V_CHECK(hipEventRecord(ctx->ev_ga_rec[k & 1], s));
+        return O2V_HIP_OK;
+    };
+    rc = batches ? start(0) : O2V_HIP_OK;
+    for (uint64_t k = 0; k < batches && rc == O2V_HIP_OK; ++k) {
+        if (!sink->can_write()) break;
+        if (hipEventSynchronize(ctx->ev_ga_rec[k & 1]) != hipSuccess) {
+            rc = refuse(ctx, O2V_HIP_ERR_HIP, fn, "waiting for a batch of records failed");
+            break;
+        }
+        if (k + 1 < batches && (rc = start(k + 1))) break;
+        sink->write(ctx->h_ga_rec[k & 1].ptr, (size_t) std::min<uint64_t>(kGaBatch, total - k * kGaBatch));
+    }
+    const hipError_t drained = hipStreamSynchronize(s);   // (nothing is on its way into the batches when the call returns)
+    if (rc) return rc;
+    if (drained != hipSuccess) return refuse(ctx, O2V_HIP_ERR_HIP, fn, std::string("hipStreamSynchronize: ") + hipGetErrorString(drained));
+    if (batches) O2V_CHECK(ctx->ga_times.elapsed(2, 3, ctx->ga_times.ms[2]));
+    if (sink->can_write()) sink->finalize();
+    if (!sink->can_write()) return refuse(ctx, O2V_HIP_ERR_IO, fn, std::string("writing \"") + path + "\" failed: the sink stopped accepting voxels");
+    *out_count = total;
+    return O2V_HIP_OK;
+}
+
+int o2v_hip_gather_times(const o2v_hip_ctx *ctx, float out_ms[3])
+{
+    return ctx ? ctx->ga_times.read(out_ms) : O2V_HIP_ERR_BAD_ARGUMENT;
 }
 
 }  // extern "C"

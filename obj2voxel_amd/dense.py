@@ -13,7 +13,8 @@ narrow-band distance to the triangles themselves (o2v_hip_mesh_distance_dense, D
 distance grid back into an indexed mesh (o2v_hip_surface_count / _write); RayCaster / raycast find the
 first solid voxel along rays through any of these grids (o2v_hip_raycast_build / o2v_hip_raycast, DESIGN.md section 14);
 components / flood and what is built on them (exterior, solidify, remove_small) say what is connected to what in them
-(o2v_hip_components_dense / o2v_hip_flood_dense).
+(o2v_hip_components_dense / o2v_hip_flood_dense); to_voxels / count_voxels / save_voxels turn any of these
+grids back into (x, y, z, argb) records and voxel files (o2v_hip_gather_count / _write / _save).
 
 torch is imported first on purpose: the library must bind to the HIP runtime torch loaded (a process that loaded the library
 before torch holds two separate runtime copies, and this module refuses to work there).
@@ -41,6 +42,7 @@ MAX_SURFACE_EXTENT = 65536  # extract_surface: origin + shape per axis
 MAX_RAY_EXTENT = 65536      # RayCaster: origin + extent per axis
 MAX_CC_DIM = 65536          # components / flood: voxels per axis ...
 MAX_CC_VOXELS = 2 ** 31 - 1  # ... and in all: a linear index and a label are one int32
+MAX_GATHER_WORDS = 2 ** 31 - 1  # to_voxels / save_voxels: words of 64 voxels along x, ceil(nx / 64) * ny * nz
 
 
 def _require_shared_runtime():
@@ -496,13 +498,14 @@ def camera_rays(width, height, eye, target, up, fov_y_degrees, device):
 # ---- connected components and flood fill --------------------------------------------------------------
 
 def _cc_grid(dv, grid, level, connectivity):
-    """(device, format, level, (nx, ny, nz)) of a grid of components / flood, checked as RayCaster checks its own."""
+    """(device, format, level, (nx, ny, nz)) of a grid of components / flood, checked as RayCaster checks its own.  connectivity
+    None: a grid of to_voxels / count_voxels / save_voxels, which have no connectivity and another size limit."""
     _require_shared_runtime()
     device = _device(dv)
     if not isinstance(grid, torch.Tensor) or grid.dim() != 3:
         raise ValueError("grid must be a 3-D tensor [z, y, x]")
     fmt, level = _grid_format(grid, level)
-    if isinstance(connectivity, bool) or connectivity not in (6, 18, 26):
+    if connectivity is not None and (isinstance(connectivity, bool) or connectivity not in (6, 18, 26)):
         raise ValueError(f"connectivity must be 6, 18 or 26, not {connectivity!r}")
     if grid.device != device:
         raise ValueError(f"grid is on {grid.device}, the voxelizer on {device}")
@@ -513,7 +516,11 @@ def _cc_grid(dv, grid, level, connectivity):
     nz, ny, nx = grid.shape
     if fmt == hip.GRID_BITS:
         nx *= 32
-    if max(nx, ny, nz) > MAX_CC_DIM or nx * ny * nz > MAX_CC_VOXELS:
+    if connectivity is None:   # (to_voxels / count_voxels / save_voxels: no linear index, words of 64 voxels)
+        if max(nx, ny, nz) > MAX_CC_DIM or -(-nx // 64) * ny * nz > MAX_GATHER_WORDS:
+            raise ValueError(f"the grid's extent {(nx, ny, nz)} [x, y, z] is above {MAX_CC_DIM} along an axis or {MAX_GATHER_WORDS} "
+                             "words of 64 voxels along x in all")
+    elif max(nx, ny, nz) > MAX_CC_DIM or nx * ny * nz > MAX_CC_VOXELS:
         raise ValueError(f"the grid's extent {(nx, ny, nz)} [x, y, z] is above {MAX_CC_DIM} along an axis or {MAX_CC_VOXELS} voxels in all")
     return device, fmt, level, (nx, ny, nz)
 
@@ -623,3 +630,114 @@ def remove_small(dv, grid, min_voxels, *, level=None, connectivity=26):
     keep = component_sizes(labels, n) >= min_voxels
     keep[0] = False
     return keep[labels.to(torch.int64)]
+
+
+# ---- dense grids as voxel lists and voxel files --------------------------------------------------------
+
+def _gather_args(dv, grid, level, origin, argb, colors, palette):
+    """(device, (grid_ptr, format, strides, dims, level), (origin, colour mode, argb, colors_ptr, color_strides, palette)): the
+    arguments of dv.gather_count and, with the colour part, of dv.gather_write / gather_save, checked."""
+    device, fmt, level, dims = _cc_grid(dv, grid, level, None)
+    origin = tuple(int(v) for v in origin)
+    if len(origin) != 3 or any(v < 0 for v in origin):
+        raise ValueError(f"origin {origin} must be three voxel coordinates, none negative")
+    if any(o + n > 2 ** 32 for o, n in zip(origin, dims)):
+        raise ValueError(f"origin {origin} + the grid's extent {dims} [x, y, z] is above 2^32")
+    if isinstance(argb, bool) or not isinstance(argb, numbers.Integral) or not -2 ** 31 <= argb < 2 ** 32:
+        raise ValueError(f"argb must be an integer of 32 bits, not {argb!r}")
+    if colors is not None and palette is not None:
+        raise ValueError("colors and palette exclude each other")
+    mode, colors_ptr, color_strides = hip.GATHER_COLOR_CONSTANT, None, None
+    if colors is not None:
+        _check_grid(colors, "colors", torch.int32, device, (dims[2], dims[1], dims[0]))
+        mode, colors_ptr, color_strides = hip.GATHER_COLOR_GRID, colors.data_ptr(), _strides(colors)
+    if palette is not None:
+        if fmt != hip.GRID_U8:
+            raise ValueError(f"palette needs a bool or uint8 grid, not {grid.dtype}")
+        palette = [int(v) for v in (palette.reshape(-1).tolist() if isinstance(palette, torch.Tensor) else palette)]
+        if len(palette) != 256 or any(not -2 ** 31 <= v < 2 ** 32 for v in palette):
+            raise ValueError("palette must be 256 integers of 32 bits")
+        mode = hip.GATHER_COLOR_PALETTE
+    return (device, (grid.data_ptr(), fmt, _strides(grid), dims, 0.0 if level is None else level),
+            (origin, mode, argb, colors_ptr, color_strides, palette))
+
+
+def count_voxels(dv, grid, *, level=None):
+    """The number of solid voxels of a dense grid, counted on the voxelizer's device.  grid and level as
+    to_voxels takes them."""
+    device, grid_args, _ = _gather_args(dv, grid, level, (0, 0, 0), 0, None, None)
+    _sync(device)   # (the caller's writes to grid have landed)
+    return dv.gather_count(*grid_args)
+
+
+def to_voxels(dv, grid, *, level=None, origin=(0, 0, 0), argb=0xFFFFFFFF, colors=None, palette=None, first=0, count=None):
+    """The solid voxels of a dense grid as records on the voxelizer's device: an int32 tensor [n, 4] of
+    (origin + (x, y, z), argb bits) in ascending (z, y, x) - the order of grid.nonzero(), the layout of dv.read_voxels().
+
+    grid:     as RayCaster and components take it: bool or uint8 (solid where != 0), int32 (the words of fmt="bits": 32 voxels
+              per word along x) or float32 with `level` (solid where grid < level).  It is only read.
+    argb:     the colour of every record, unless
+    colors:   an int32 tensor of the grid's voxel shape [z, y, x] (any strides: fmt="argb" grids), the colour per voxel, or
+    palette:  a sequence or tensor of 256 integers, the colour per value of a bool / uint8 grid (labels 1 / 2 -> a surface and a
+              fill colour).  colors and palette exclude each other.
+    first, count:  records [first, first + count) of the numbering only (count None: to the end), so that a list too large for
+              the device can be taken in parts; each call counts again."""
+    device, grid_args, color_args = _gather_args(dv, grid, level, origin, argb, colors, palette)
+    for name, v in (("first", first), ("count", count)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 0):
+            raise ValueError(f"{name} must be an integer >= 0, not {v!r}")
+    _sync(device)   # (the caller's writes to grid and colors have landed)
+    total = dv.gather_count(*grid_args)
+    if first > total or (count is not None and count > total - first):
+        raise ValueError(f"records [{first}, {first} + {count}) reach past the grid's {total} solid voxels")
+    n = total - first if count is None else count
+    records = torch.empty((n, 4), dtype=torch.int32, device=device)
+    if n:
+        dv.gather_write(*grid_args, *color_args, first, n, records.data_ptr())
+    return records
+
+
+def save_voxels(dv, grid, path, *, fmt=None, resolution=None, level=None, origin=(0, 0, 0), argb=0xFFFFFFFF, colors=None, palette=None):
+    """The solid voxels of a dense grid written to the voxel file `path`, in the order and with the
+    colours of to_voxels, through the writers of obj2voxel_voxelize(); the records cross to the host in batches of 2^20.
+    Returns the number of voxels.
+
+    fmt:         "vl32", "ply", "xyzrgb", "qef" or "vox"; None: the path's extension.
+    resolution:  the grid resolution the paletted formats record; None: max(origin + extent).
+    A path that cannot be opened, a type that is no output format and a writer that fails raise hip.DeviceError with the
+    library's message."""
+    device, grid_args, color_args = _gather_args(dv, grid, level, origin, argb, colors, palette)
+    reach = max(o + n for o, n in zip(color_args[0], grid_args[3]))
+    if resolution is None:
+        resolution = reach
+    if isinstance(resolution, bool) or not isinstance(resolution, numbers.Integral) or not reach <= resolution < 2 ** 32:
+        raise ValueError(f"resolution must be an integer from origin + extent = {reach} to 2^32 - 1, not {resolution!r}")
+    if fmt is not None and not isinstance(fmt, str):
+        raise TypeError(f"fmt must be a string or None, not {fmt!r}")
+    _sync(device)   # (the caller's writes to grid and colors have landed)
+    return dv.gather_save(*grid_args, *color_args, path, fmt, int(resolution))
+
+
+def from_voxels(records, shape, *, origin=(0, 0, 0), fmt="occupancy"):
+    """The inverse of to_voxels, in plain torch: a [z, y, x] tensor of `shape` on the records' device with the records' voxels
+    set - fmt "occupancy": bool, "labels": uint8 1, "argb": int32 argb (0 elsewhere).  records: an integer tensor [n, 4] of
+    (x, y, z, argb); a record outside origin + shape raises ValueError.  from_voxels(to_voxels(dv, g), g.shape) == (g != 0)."""
+    if fmt not in ("occupancy", "labels", "argb"):
+        raise ValueError(f"fmt must be 'occupancy', 'labels' or 'argb', not {fmt!r}")
+    if not isinstance(records, torch.Tensor) or records.dim() != 2 or records.shape[1] != 4 or records.dtype not in (torch.int32, torch.int64):
+        raise ValueError("records must be an int32 or int64 tensor [n, 4] of (x, y, z, argb)")
+    shape, origin = tuple(int(v) for v in shape), tuple(int(v) for v in origin)
+    if len(shape) != 3 or any(v < 1 for v in shape) or len(origin) != 3 or any(v < 0 for v in origin):
+        raise ValueError("shape must be three positive extents [z, y, x] and origin three voxel coordinates, none negative")
+    xyz = records[:, :3].to(torch.int64)
+    if records.dtype == torch.int32:
+        xyz = xyz & 0xFFFFFFFF   # (the coordinates are uint32 bits)
+    xyz = xyz - torch.tensor(origin, dtype=torch.int64, device=records.device)
+    extent = torch.tensor((shape[2], shape[1], shape[0]), dtype=torch.int64, device=records.device)
+    if bool(((xyz < 0) | (xyz >= extent)).any()):
+        raise ValueError(f"records lie outside the box of shape {shape} [z, y, x] at origin {origin}")
+    dtype = FORMATS[fmt][1]
+    grid = torch.zeros(shape, dtype=dtype, device=records.device)
+    values = records[:, 3].to(torch.int32) if fmt == "argb" else torch.ones((), dtype=dtype, device=records.device).expand(xyz.shape[0])
+    grid[xyz[:, 2], xyz[:, 1], xyz[:, 0]] = values
+    return grid

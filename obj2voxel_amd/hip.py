@@ -1,5 +1,6 @@
 """ctypes binding of the device C-ABI (include/o2v_hip.h): one DeviceVoxelizer per GPU / z-slab."""
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -29,7 +30,9 @@ GRID_U8, GRID_BITS, GRID_F32_BELOW = 0, 1, 2  # the same formats, as o2v_hip_com
 CC_INVERT, CC_SEED_BORDER = 16, 32  # ... their flags (with FLAG_STAGE_TIMES: the counters)
 CC_SCRATCH_LABELS, CC_SCRATCH_LABELS_STRIDED, CC_SCRATCH_FLOOD = 0, 1, 2  # o2v_hip_components_scratch_bytes
 MESH_DIST_UNSIGNED_F32, MESH_DIST_SIGNED_F32 = 0, 1  # o2v_hip_mesh_distance_dense formats
+GATHER_COLOR_CONSTANT, GATHER_COLOR_GRID, GATHER_COLOR_PALETTE = 0, 1, 2  # o2v_hip_gather_write / _save colour modes
 ERR_BAD_ARGUMENT = 3
+ERR_IO = 6  # o2v_hip_gather_save: the file cannot be opened, is of no output type, or stopped taking voxels
 
 
 class _Texture(C.Structure):
@@ -142,6 +145,14 @@ def _bind():
     L.o2v_hip_components_scratch_bytes.restype = C.c_uint64
     L.o2v_hip_components_times.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_components_counters.argtypes = [C.c_void_p, C.c_void_p]
+    _gather = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float]   # ctx, grid, format, strides, dims, level
+    _gather_color = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]   # origin, mode, argb, colors, strides, palette
+    L.o2v_hip_gather_count.argtypes = _gather + [C.POINTER(C.c_uint64)]
+    L.o2v_hip_gather_write.argtypes = _gather + _gather_color + [C.c_uint64, C.c_uint64, C.c_void_p]
+    L.o2v_hip_gather_save.argtypes = _gather + _gather_color + [C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.o2v_hip_gather_scratch_bytes.argtypes = [C.c_void_p]
+    L.o2v_hip_gather_scratch_bytes.restype = C.c_uint64
+    L.o2v_hip_gather_times.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_max_slab_layers.argtypes = [C.c_void_p, C.POINTER(_Params), C.POINTER(C.c_uint32)]
     return L
 
@@ -200,6 +211,11 @@ def components_scratch_bytes(dims, which=CC_SCRATCH_LABELS):
     """o2v_hip_components_scratch_bytes: the context scratch a components_dense (CC_SCRATCH_LABELS: contiguous labels,
     CC_SCRATCH_LABELS_STRIDED: any other) or flood_dense (CC_SCRATCH_FLOOD) call over dims (x, y, z) takes."""
     return int(_bind().o2v_hip_components_scratch_bytes(_u32x3(dims), which))
+
+
+def gather_scratch_bytes(dims):
+    """o2v_hip_gather_scratch_bytes: the context scratch a gather_count over dims (x, y, z) takes."""
+    return int(_bind().o2v_hip_gather_scratch_bytes(_u32x3(dims)))
 
 
 def device_count():
@@ -406,6 +422,50 @@ class DeviceVoxelizer:
         out = (C.c_uint64 * 2)()
         self._check(self._L.o2v_hip_components_counters(self._ctx, out), "o2v_hip_components_counters")
         return int(out[0]), int(out[1])
+
+    def gather_count(self, grid_ptr, fmt, strides, dims, level):
+        """o2v_hip_gather_count: the number of solid voxels of the grid at device address grid_ptr (GRID_U8 / GRID_BITS /
+        GRID_F32_BELOW with level; strides in elements and dims per axis x, y, z).  The one pass over the grid: the set's bits
+        and the records' offsets stay in the context for gather_write."""
+        n = C.c_uint64(0)
+        self._check(self._L.o2v_hip_gather_count(self._ctx, grid_ptr, fmt, _u64x3(strides), _u32x3(dims), float(level), C.byref(n)),
+                    "o2v_hip_gather_count")
+        return int(n.value)
+
+    @staticmethod
+    def _gather_color(origin, color_mode, argb, colors_ptr, color_strides, palette):
+        pal = None if palette is None else (C.c_uint32 * 256)(*[int(v) & 0xFFFFFFFF for v in palette])
+        return _u32x3(origin), color_mode, int(argb) & 0xFFFFFFFF, colors_ptr, _u64x3(color_strides), pal
+
+    def gather_write(self, grid_ptr, fmt, strides, dims, level, origin, color_mode, argb, colors_ptr, color_strides, palette, first, n,
+                     records_ptr):
+        """o2v_hip_gather_write: records [first, first + n) of the grid's solid voxels in ascending (z, y, x) - uint32 (origin +
+        (x, y, z), argb) - to the device address records_ptr.  The grid arguments are those of the gather_count before it.
+        color_mode: GATHER_COLOR_CONSTANT (argb), _GRID (colors_ptr: a uint32 grid, color_strides in elements) or _PALETTE
+        (palette: 256 integers, indexed by the voxel's byte)."""
+        self._check(self._L.o2v_hip_gather_write(self._ctx, grid_ptr, fmt, _u64x3(strides), _u32x3(dims), float(level),
+                                                 *self._gather_color(origin, color_mode, argb, colors_ptr, color_strides, palette),
+                                                 first, n, records_ptr), "o2v_hip_gather_write")
+
+    def gather_save(self, grid_ptr, fmt, strides, dims, level, origin, color_mode, argb, colors_ptr, color_strides, palette, path, file_type,
+                    resolution):
+        """o2v_hip_gather_save: the same records, all of them, into the voxel file `path` (file_type: an extension without dot, or
+        None for the path's) through the file sinks of obj2voxel_voxelize(), in batches.  Returns the number of voxels."""
+        n = C.c_uint64(0)
+        self._check(self._L.o2v_hip_gather_save(self._ctx, grid_ptr, fmt, _u64x3(strides), _u32x3(dims), float(level),
+                                                *self._gather_color(origin, color_mode, argb, colors_ptr, color_strides, palette),
+                                                None if path is None else os.fsencode(path), None if file_type is None else str(file_type).encode(), resolution,
+                                                C.byref(n)), "o2v_hip_gather_save")
+        return int(n.value)
+
+    def gather_scratch_bytes(self, dims):
+        """o2v_hip_gather_scratch_bytes: the context scratch a gather_count over dims (x, y, z) takes."""
+        return gather_scratch_bytes(dims)
+
+    def gather_times(self):
+        """o2v_hip_gather_times: the device times (ms) of the last gather_count's classify and count + scan stages and of the
+        last gather_write."""
+        return self._stage_times("o2v_hip_gather_times", 3)
 
     def set_textures(self, textures):
         """textures: sequence of (uint8 [h, w, c] pixels, wrap) with c in (3, 4)."""

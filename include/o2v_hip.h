@@ -586,6 +586,76 @@ uint64_t o2v_hip_gather_scratch_bytes(const uint32_t dims[3]);
  * save: of its last batch). */
 int o2v_hip_gather_times(const o2v_hip_ctx *ctx, float out_ms[3]);
 
+/* ---- dense grids as blocky meshes: exposed voxel faces as coloured quads -----------------------------
+ *
+ * The mesh of a voxel model: one quad per exposed voxel face, coloured by its voxel, faces of equal colour merged into runs;
+ * defined so that a numpy restatement (tests/faces_ref.py) reproduces every bit.
+ *
+ * The set.  grid, format, strides, dims and level are exactly those of o2v_hip_gather_count: the grid is only read, a stride
+ * may be 0, BITS needs strides[0] == 1, a NaN is not below the level.  Everything outside the box is empty.
+ *
+ * Colour of a voxel.  color_mode, argb, colors, color_strides and palette are those of o2v_hip_gather_write
+ * (O2V_HIP_GATHER_COLOR_CONSTANT / _GRID / _PALETTE), with the same meaning.
+ *
+ * Faces.  Direction d = 0 .. 5 is -x, +x, -y, +y, -z, +z.  Face (x, y, z, d) is exposed if voxel (x, y, z) is solid and its
+ * neighbour in direction d is not.
+ *
+ * Merging.  O2V_HIP_FACES_MERGE_NONE: one quad per exposed face.  O2V_HIP_FACES_MERGE_RUNS: one quad per maximal run.
+ * Directions 2 .. 5 run along x, directions 0 and 1 along y.  Two exposed faces of one direction belong to one run if they are
+ * neighbours along that axis and their voxels' colours are equal as uint32 (colours, not labels: two palette entries with the
+ * same word merge; with CONSTANT every pair is equal).  A run is cut nowhere else: not at a multiple of 64 and not at any
+ * boundary of the implementation.
+ *
+ * Order.  Quads ascend by the key ((z * ny + y) * 6 + d) * nx + x of the run's first face - the one of the lowest x, or of the
+ * lowest y for d < 2: row by row, direction by direction within a row, then x.
+ *
+ * Geometry.  Vertices are not shared: quad q owns vertices 4q .. 4q + 3 and triangles 2q, 2q + 1 = (4q, 4q + 1, 4q + 2),
+ * (4q, 4q + 2, 4q + 3).  With axis a = d >> 1, side s = d & 1 and (u, v) the two axes after a in cyclic order (x -> (y, z),
+ * y -> (z, x), z -> (x, y)) the quad lies in the plane a = origin[a] + voxel[a] + s and spans [u0, u1] x [v0, v1], the lattice
+ * bounds of its faces (origin included); its corners in order are (u0, v0), (u1, v0), (u1, v1), (u0, v1) for s = 1 and
+ * (u0, v0), (u0, v1), (u1, v1), (u1, v0) for s = 0, so that both triangles' normals point out of the solid voxel.  Coordinates
+ * are (float) of integers at most 65 536: exact.
+ *
+ * o2v_hip_faces_count is the only pass over the grid, and with GRID or PALETTE and MERGE_RUNS the only pass that compares
+ * colours: it keeps the solid bits, and for those a bit per voxel each for "the colour of the voxel at x - 1" and "... at
+ * y - 1", in scratch of the context, and returns the number of quads Q - a uint64: no 32-bit limit.  With MERGE_NONE and
+ * CONSTANT it is the model's surface area in voxel faces.
+ *
+ * o2v_hip_faces_write fills all Q quads: positions ([4Q][3] float32, 16-byte aligned), faces ([2Q][3] int32, 8-byte aligned,
+ * may be NULL) and quad_argb ([Q] uint32, may be NULL), device memory with room for quad_capacity >= Q quads.  It must follow an
+ * o2v_hip_faces_count with the same grid pointer, format, strides, dims, level, merge and colour arguments (argb for CONSTANT,
+ * colors and color_strides for GRID, the palette's 256 words for PALETTE), else O2V_HIP_ERR_BAD_ARGUMENT, "no matching
+ * o2v_hip_faces_count"; another count, refused or not, replaces the last one.  Q = 0 launches nothing and reads no output
+ * pointer.  The topology comes from the kept bits only; a quad's colour is read at the time of the write from the run's first
+ * voxel.  A grid or colour grid that changes between the two calls can give other colours - no other coordinate and no write
+ * outside the arrays.
+ *
+ * Refused before any launch, outputs untouched: what o2v_hip_gather_count and the colour arguments of o2v_hip_gather_write are
+ * refused for, an unknown merge, quad_capacity below Q, misaligned outputs, outputs that overlap each other, the grid or colors
+ * or are not device memory of the context's device with their whole extent inside one allocation (O2V_HIP_ERR_BAD_ARGUMENT); a
+ * dim above 65 536, more than 2^31 - 1 words, for write origin[a] + dims[a] above 65 536 - beyond it a coordinate is no longer
+ * exact in float32 - and 4 Q above 2^31 - 1, the message naming Q (O2V_HIP_ERR_LIMIT).  A failed scratch allocation returns
+ * O2V_HIP_ERR_OUT_OF_MEMORY and leaves the context usable.  Both calls run on the context's stream and return when their
+ * results have landed.
+ *
+ * Scratch of the context, grown on demand (o2v_hip_faces_scratch_bytes, an upper bound; 0 for zero dims): 8 * words - 24 *
+ * words with GRID or PALETTE, of which MERGE_NONE uses 8 - + 8 * (ceil(6 * words / 256) + 1) + 1024: a 64-bit word per 64
+ * voxels along x for the set and the two comparisons, a 64-bit offset per block of 256 (row, direction, word) items and the
+ * count, the palette. */
+enum { O2V_HIP_FACES_MERGE_NONE = 0, O2V_HIP_FACES_MERGE_RUNS = 1 };
+int o2v_hip_faces_count(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+                        uint32_t merge, uint32_t color_mode, uint32_t argb, const uint32_t *colors, const uint64_t color_strides[3],
+                        const uint32_t *palette /* [256], host */, uint64_t *out_quads);
+int o2v_hip_faces_write(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+                        uint32_t merge, uint32_t color_mode, uint32_t argb, const uint32_t *colors, const uint64_t color_strides[3],
+                        const uint32_t *palette /* [256], host */, const uint32_t origin[3], float *positions /* [4Q][3], device */,
+                        int32_t *faces /* [2Q][3], device, may be NULL */, uint32_t *quad_argb /* [Q], device, may be NULL */,
+                        uint64_t quad_capacity);
+uint64_t o2v_hip_faces_scratch_bytes(const uint32_t dims[3], uint32_t color_mode);
+/* The device times (ms) of the last count's classify (+ colour comparison) and count + scan stages and of the last write (0
+ * after a count). */
+int o2v_hip_faces_times(const o2v_hip_ctx *ctx, float out_ms[3]);
+
 int o2v_hip_get_timings(const o2v_hip_ctx *ctx, o2v_hip_timings *out);
 /* Per-kernel device times of the last o2v_hip_voxelize call made with O2V_HIP_FLAG_KERNEL_TIMES (else none): up to
  * max_entries entries are written, *out_count receives how many there are. */

@@ -36,6 +36,8 @@
 //                              grid, a union-find over its voxels ; outside the pipeline
 //   K13 k_gather_*             o2v_hip_gather_count / _write / _save: the solid voxels of a dense grid as (x, y, z, argb)
 //                              records, in ranges, and as a voxel file; outside the pipeline
+//   K14 k_faces_*              o2v_hip_faces_count / _write: the exposed voxel faces of a dense grid as coloured quads, merged
+//                              into runs; outside the pipeline
 //   plan k_zhist               o2v_hip_plan_slabs: predicted hits per z layer -> work-balanced slabs for N GPUs
 // With the direct MAX path K1's counters reach the host while K2 runs, and only the stages that have work are enqueued
 // behind it.  N > 1 GPUs: o2v_hip_voxelize_sharded (bounds / work-histogram passes sharded over the ranks, RCCL).
@@ -85,6 +87,7 @@ namespace {
 #include "o2v_dev_k11_raycast.hpp"
 #include "o2v_dev_k12_components.hpp"
 #include "o2v_dev_k13_gather.hpp"
+#include "o2v_dev_k14_faces.hpp"
 
 }  // namespace
 
@@ -386,6 +389,25 @@ struct o2v_hip_ctx {
         float level = 0.f;
         uint64_t total = 0;
     } ga;
+
+    // K14 (o2v_hip_faces_count / _write): the bits of the set, the same-colour bits along x and y (GRID / PALETTE with
+    // MERGE_RUNS), the block offsets (+ the count) and the palette, grown on demand; what they were counted for; the times of
+    // the three stages
+    DevArray<unsigned long long> d_fa_bits, d_fa_same_x, d_fa_same_y, d_fa_boff;
+    DevArray<uint32_t> d_fa_palette;
+    PinnedArray<unsigned long long> h_fa_ctr;
+    PinnedArray<uint32_t> h_fa_palette;
+    StageTimes<3> fa_times;
+    struct FacesCount {
+        bool valid = false;
+        const void *grid = nullptr, *colors = nullptr;
+        uint32_t format = 0, merge = 0, color_mode = 0, argb = 0;
+        uint64_t strides[3] = {}, color_strides[3] = {};
+        uint32_t dims[3] = {};
+        float level = 0.f;
+        uint32_t palette[256] = {};
+        uint64_t total = 0;
+    } fa;
 
     // results of the last run
     uint64_t n_vox = 0;
@@ -3541,6 +3563,240 @@ int o2v_hip_gather_save(o2v_hip_ctx *ctx, const void *grid, uint32_t format, con
 int o2v_hip_gather_times(const o2v_hip_ctx *ctx, float out_ms[3])
 {
     return ctx ? ctx->ga_times.read(out_ms) : O2V_HIP_ERR_BAD_ARGUMENT;
+}
+
+}  // extern "C"
+
+// ---- K14: the exposed voxel faces of a dense grid as coloured quads -----------------------------------------------------------
+
+namespace {
+
+constexpr uint64_t kFaMaxExtent = 65536;          // origin + dims per axis: a coordinate is an exact float32
+constexpr uint64_t kFaMaxQuads = 0x7fffffffull / 4u;   // 4 Q <= 2^31 - 1: a vertex index is one int32
+constexpr uint64_t kFaMaxGrid = 1ull << 20;       // workgroups of k_faces_count; more blocks are taken in turns
+
+// what both calls check: the grid as the gather checks it, the merge and colour modes and the pointers the colour mode reads;
+// *g: the words and items, *gbytes / *cbytes: the reach of the grid and of colors (GRID)
+int fa_args(o2v_hip_ctx *ctx, const char *fn, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+            uint32_t merge, uint32_t color_mode, const uint32_t *colors, const uint64_t color_strides[3], const uint32_t *palette, FaGrid *g,
+            uint64_t *gbytes, uint64_t *cbytes)
+{
+    GaGrid gg{};
+    static const uint32_t no_origin[3] = {0, 0, 0};
+    int rc;
+    if ((rc = ga_grid(ctx, fn, grid, format, strides, dims, level, &gg, gbytes))) return rc;
+    if (merge != O2V_HIP_FACES_MERGE_NONE && merge != O2V_HIP_FACES_MERGE_RUNS)
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown merge " + std::to_string(merge));
+    if ((rc = ga_mode(ctx, fn, format, dims, no_origin, color_mode)) ||
+        (rc = ga_color_source(ctx, fn, dims, color_mode, colors, color_strides, palette, cbytes)))
+        return rc;
+    g->nx = gg.nx, g->ny = gg.ny, g->nz = gg.nz, g->W = gg.W;
+    g->merge = merge;
+    g->colored = merge == O2V_HIP_FACES_MERGE_RUNS && color_mode != O2V_HIP_GATHER_COLOR_CONSTANT;
+    g->words = gg.words;
+    g->items = 6u * gg.words;
+    g->n_blocks = (g->items + kBlock - 1) / kBlock;
+    return O2V_HIP_OK;
+}
+
+bool fa_matches(const o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+                uint32_t merge, uint32_t color_mode, uint32_t argb, const uint32_t *colors, const uint64_t color_strides[3], const uint32_t *palette)
+{
+    const o2v_hip_ctx::FacesCount &c = ctx->fa;
+    if (!c.valid || c.grid != grid || c.format != format || !std::equal(strides, strides + 3, c.strides) || !std::equal(dims, dims + 3, c.dims) ||
+        std::memcmp(&c.level, &level, sizeof(float)) != 0 || c.merge != merge || c.color_mode != color_mode)
+        return false;
+    if (color_mode == O2V_HIP_GATHER_COLOR_GRID) return c.colors == colors && std::equal(color_strides, color_strides + 3, c.color_strides);
+    if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE) return std::equal(palette, palette + 256, c.palette);
+    return c.argb == argb;
+}
+
+FaBits fa_bits(const o2v_hip_ctx *ctx) { return FaBits{ctx->d_fa_bits.ptr, ctx->d_fa_same_x.ptr, ctx->d_fa_same_y.ptr}; }
+
+GaColor fa_color_source(const o2v_hip_ctx *ctx, const void *grid, const uint64_t strides[3], uint32_t color_mode, uint32_t argb,
+                        const uint32_t *colors, const uint64_t color_strides[3])
+{
+    GaColor col = ga_color(ctx, grid, strides, color_mode, argb, colors, color_strides);
+    if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE) col.palette = ctx->d_fa_palette.ptr;
+    return col;
+}
+
+int fa_upload_palette(o2v_hip_ctx *ctx, const uint32_t *palette)
+{
+    std::memcpy(ctx->h_fa_palette.ptr, palette, 256u * sizeof(uint32_t));
+    O2V_CHECK(hipMemcpyAsync(ctx->d_fa_palette.ptr, ctx->h_fa_palette.ptr, 256u * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    return O2V_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t o2v_hip_faces_scratch_bytes(const uint32_t dims[3], uint32_t color_mode)
+{
+    if (!dims || !dims[0] || !dims[1] || !dims[2]) return 0;
+    const uint64_t words = cc_words(dims);
+    return (color_mode == O2V_HIP_GATHER_COLOR_CONSTANT ? 8u : 24u) * words + 8u * ((6u * words + kBlock - 1) / kBlock + 1u) + 1024u;
+}
+
+int o2v_hip_faces_count(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+                        uint32_t merge, uint32_t color_mode, uint32_t argb, const uint32_t *colors, const uint64_t color_strides[3],
+                        const uint32_t *palette, uint64_t *out_quads)
+{
+    static const char fn[] = "o2v_hip_faces_count";
+    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
+    ctx->fa.valid = false;
+    if (!out_quads) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
+    FaGrid g{};
+    uint64_t gbytes = 0, cbytes = 0;
+    int rc;
+    if ((rc = fa_args(ctx, fn, grid, format, strides, dims, level, merge, color_mode, colors, color_strides, palette, &g, &gbytes, &cbytes))) return rc;
+    if ((rc = grow_scratch(ctx, ctx->d_fa_bits, g.words, fn, "set bits")) ||
+        (g.colored && ((rc = grow_scratch(ctx, ctx->d_fa_same_x, g.words, fn, "same-colour bits")) ||
+                       (rc = grow_scratch(ctx, ctx->d_fa_same_y, g.words, fn, "same-colour bits")))) ||
+        (rc = grow_scratch(ctx, ctx->d_fa_boff, g.n_blocks + 1u, fn, "block offsets")) ||
+        (rc = grow_scratch(ctx, ctx->d_fa_palette, 256u, fn, "palette")) || (rc = grow_scratch(ctx, ctx->h_fa_palette, 256u, fn, "palette")) ||
+        (rc = grow_scratch(ctx, ctx->h_fa_ctr, 1u, fn, "counters")))
+        return rc;
+    ctx->ktimes_on = false;   // (no per-launch brackets here; o2v_hip_voxelize sets the flag again from its params)
+    CcGrid cg{};
+    cg.nx = g.nx, cg.ny = g.ny, cg.nz = g.nz, cg.W = g.W, cg.words = g.words;
+    unsigned long long *const bits = ctx->d_fa_bits.ptr, *const boff = ctx->d_fa_boff.ptr;
+    const RaySource src{grid, strides[0], strides[1], strides[2], level};
+    const uint64_t elem = format == O2V_HIP_GRID_U8 ? 1u : 4u;
+    const bool vec = strides[0] == 1u && (uintptr_t) grid % 16u == 0 && strides[1] * elem % 16u == 0 && strides[2] * elem % 16u == 0;
+    const dim3 per_group(stream_grid(ctx, (g.words + 15u) / 16u * 64u, 8u));
+    hipStream_t s = ctx->stream;
+    O2V_CHECK(ctx->fa_times.mark(0, s));
+    if (format == O2V_HIP_GRID_BITS)
+        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayBits, false>), per_group, dim3(kBlock), 0, s, src, cg, 0u, bits);
+    else if (format == O2V_HIP_GRID_U8 && vec)
+        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayU8, true>), per_group, dim3(kBlock), 0, s, src, cg, 0u, bits);
+    else if (format == O2V_HIP_GRID_U8)
+        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayU8, false>), per_group, dim3(kBlock), 0, s, src, cg, 0u, bits);
+    else if (vec)
+        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayF32Below, true>), per_group, dim3(kBlock), 0, s, src, cg, 0u, bits);
+    else
+        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayF32Below, false>), per_group, dim3(kBlock), 0, s, src, cg, 0u, bits);
+    if (g.colored) {
+        // a wavefront per word in turns
+        const dim3 per_word(stream_grid(ctx, g.words * 64u, 8u));
+        const GaColor col = fa_color_source(ctx, grid, strides, color_mode, argb, colors, color_strides);
+        if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE) {
+            if ((rc = fa_upload_palette(ctx, palette))) return rc;
+            O2V_LAUNCH("k_faces_same", s, k_faces_same<kGaColorPalette>, per_word, dim3(kBlock), 0, s, g, bits, col, ctx->d_fa_same_x.ptr,
+                       ctx->d_fa_same_y.ptr);
+        } else {
+            O2V_LAUNCH("k_faces_same", s, k_faces_same<kGaColorGrid>, per_word, dim3(kBlock), 0, s, g, bits, col, ctx->d_fa_same_x.ptr,
+                       ctx->d_fa_same_y.ptr);
+        }
+    }
+    O2V_CHECK(ctx->fa_times.mark(1, s));
+    O2V_LAUNCH("k_faces_count", s, k_faces_count, dim3((uint32_t) std::min<uint64_t>(g.n_blocks, kFaMaxGrid)), dim3(kBlock), 0, s, g, fa_bits(ctx), boff);
+    // (the count goes behind the offsets: entry n_blocks)
+    O2V_LAUNCH("k_fill_scan_blocks", s, k_fill_scan_blocks, dim3(1), dim3(kBlock), 0, s, boff, g.n_blocks, boff + g.n_blocks);
+    O2V_CHECK(hipGetLastError());
+    O2V_CHECK(ctx->fa_times.mark(2, s));
+    O2V_CHECK(hipMemcpyAsync(ctx->h_fa_ctr.ptr, boff + g.n_blocks, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    O2V_CHECK(hipStreamSynchronize(s));
+    O2V_CHECK(ctx->fa_times.elapsed(0, 1, ctx->fa_times.ms[0]));
+    O2V_CHECK(ctx->fa_times.elapsed(1, 2, ctx->fa_times.ms[1]));
+    ctx->fa_times.ms[2] = 0.f;
+#ifdef O2V_FA_MUTATE_COUNT32
+    const uint64_t total = (uint32_t) ctx->h_fa_ctr.ptr[0];   // (test only: the count truncated where the host reads it)
+#else
+    const uint64_t total = ctx->h_fa_ctr.ptr[0];
+#endif
+    o2v_hip_ctx::FacesCount &c = ctx->fa;
+    c.valid = true;
+    c.grid = grid;
+    c.format = format;
+    std::copy(strides, strides + 3, c.strides);
+    std::copy(dims, dims + 3, c.dims);
+    c.level = level;
+    c.merge = merge;
+    c.color_mode = color_mode;
+    c.argb = argb;
+    c.colors = color_mode == O2V_HIP_GATHER_COLOR_GRID ? colors : nullptr;
+    if (color_mode == O2V_HIP_GATHER_COLOR_GRID) std::copy(color_strides, color_strides + 3, c.color_strides);
+    if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE) std::copy(palette, palette + 256, c.palette);
+    c.total = total;
+    *out_quads = total;
+    return O2V_HIP_OK;
+}
+
+int o2v_hip_faces_write(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+                        uint32_t merge, uint32_t color_mode, uint32_t argb, const uint32_t *colors, const uint64_t color_strides[3],
+                        const uint32_t *palette, const uint32_t origin[3], float *positions, int32_t *faces, uint32_t *quad_argb,
+                        uint64_t quad_capacity)
+{
+    static const char fn[] = "o2v_hip_faces_write";
+    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
+    FaGrid g{};
+    uint64_t gbytes = 0, cbytes = 0;
+    int rc;
+    if ((rc = fa_args(ctx, fn, grid, format, strides, dims, level, merge, color_mode, colors, color_strides, palette, &g, &gbytes, &cbytes))) return rc;
+    if (!origin) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
+    for (int a = 0; a < 3; ++a)
+        if ((uint64_t) origin[a] + dims[a] > kFaMaxExtent)
+            return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "origin + dims is above 65 536 along an axis: a coordinate would not be exact in float32");
+    if (!fa_matches(ctx, grid, format, strides, dims, level, merge, color_mode, argb, colors, color_strides, palette))
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn,
+                      "no matching o2v_hip_faces_count (the same grid, format, strides, dims, level, merge and colour arguments)");
+    const uint64_t total = ctx->fa.total;
+    if (total > kFaMaxQuads)
+        return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, std::to_string(total) + " quads: 4 vertices each are more than 2^31 - 1 int32 indices");
+    if (quad_capacity < total)
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn,
+                      "quad_capacity " + std::to_string(quad_capacity) + " is below the counted " + std::to_string(total) + " quads");
+    if (total == 0) return O2V_HIP_OK;
+    if (!positions) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
+    if ((uintptr_t) positions % 16u || (uintptr_t) faces % 8u || (uintptr_t) quad_argb % 4u)
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "positions must be 16-byte, faces 8-byte and quad_argb 4-byte aligned");
+    struct Out {
+        const void *p;
+        uint64_t bytes;
+        const char *what;
+    } outs[3] = {{positions, total * 48u, "positions"}, {faces, total * 24u, "faces"}, {quad_argb, total * 4u, "quad_argb"}};
+    for (int i = 0; i < 3; ++i) {
+        if (!outs[i].p) continue;
+        if ((rc = check_device_range(ctx, fn, outs[i].p, outs[i].bytes, outs[i].what))) return rc;
+        if (ranges_overlap(outs[i].p, outs[i].bytes, grid, gbytes))
+            return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, std::string(outs[i].what) + " and grid overlap");
+        if (cbytes && ranges_overlap(outs[i].p, outs[i].bytes, colors, cbytes))
+            return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, std::string(outs[i].what) + " and colors overlap");
+        for (int j = 0; j < i; ++j)
+            if (outs[j].p && ranges_overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes))
+                return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, std::string(outs[j].what) + " and " + outs[i].what + " overlap");
+    }
+    ctx->ktimes_on = false;
+    if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE && (rc = fa_upload_palette(ctx, palette))) return rc;
+    const GaColor col = fa_color_source(ctx, grid, strides, color_mode, argb, colors, color_strides);
+    hipStream_t s = ctx->stream;
+    // a workgroup per block of items in turns, and no more than fill the device
+    const dim3 blocks((uint32_t) std::min<uint64_t>(g.n_blocks, (uint64_t) ctx->num_cus * 8u));
+    float4 *const pos = reinterpret_cast<float4 *>(positions);
+    int2 *const tri = reinterpret_cast<int2 *>(faces);
+    O2V_CHECK(hipEventRecord(ctx->fa_times.ev[2], s));
+    if (color_mode == O2V_HIP_GATHER_COLOR_GRID)
+        O2V_LAUNCH("k_faces_write", s, k_faces_write<kGaColorGrid>, blocks, dim3(kBlock), 0, s, g, fa_bits(ctx), ctx->d_fa_boff.ptr, origin[0], origin[1],
+                   origin[2], col, pos, tri, quad_argb);
+    else if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE)
+        O2V_LAUNCH("k_faces_write", s, k_faces_write<kGaColorPalette>, blocks, dim3(kBlock), 0, s, g, fa_bits(ctx), ctx->d_fa_boff.ptr, origin[0], origin[1],
+                   origin[2], col, pos, tri, quad_argb);
+    else
+        O2V_LAUNCH("k_faces_write", s, k_faces_write<kGaColorConstant>, blocks, dim3(kBlock), 0, s, g, fa_bits(ctx), ctx->d_fa_boff.ptr, origin[0],
+                   origin[1], origin[2], col, pos, tri, quad_argb);
+    O2V_CHECK(hipGetLastError());
+    O2V_CHECK(hipEventRecord(ctx->fa_times.ev[3], s));
+    O2V_CHECK(hipStreamSynchronize(s));
+    O2V_CHECK(ctx->fa_times.elapsed(2, 3, ctx->fa_times.ms[2]));
+    return O2V_HIP_OK;
+}
+
+int o2v_hip_faces_times(const o2v_hip_ctx *ctx, float out_ms[3])
+{
+    return ctx ? ctx->fa_times.read(out_ms) : O2V_HIP_ERR_BAD_ARGUMENT;
 }
 
 }  // extern "C"

@@ -14,13 +14,17 @@ distance grid back into an indexed mesh (o2v_hip_surface_count / _write, DESIGN.
 first solid voxel along rays through any of these grids (o2v_hip_raycast_build / o2v_hip_raycast, DESIGN.md section 14);
 components / flood and what is built on them (exterior, solidify, remove_small) say what is connected to what in them
 (o2v_hip_components_dense / o2v_hip_flood_dense); to_voxels / count_voxels / save_voxels turn any of these
-grids back into (x, y, z, argb) records and voxel files (o2v_hip_gather_count / _write / _save).
+grids back into (x, y, z, argb) records and voxel files (o2v_hip_gather_count / _write / _save, DESIGN.md section 16);
+voxel_faces / count_faces turn them into the blocky mesh of the voxel model (o2v_hip_faces_count / _write)
+and save_mesh writes that mesh, or extract_surface's, as STL, PLY or OBJ + MTL.
 
 torch is imported first on purpose: the library must bind to the HIP runtime torch loaded (a process that loaded the library
 before torch holds two separate runtime copies, and this module refuses to work there).
 """
 import numbers
+import os
 
+import numpy as np
 import torch  # first: see above
 
 from . import hip
@@ -42,6 +46,8 @@ MAX_SURFACE_EXTENT = 65536  # extract_surface: origin + shape per axis
 MAX_RAY_EXTENT = 65536      # RayCaster: origin + extent per axis
 MAX_CC_DIM = 65536          # components / flood: voxels per axis ...
 MAX_CC_VOXELS = 2 ** 31 - 1  # ... and in all: a linear index and a label are one int32
+MAX_FACES_EXTENT = 65536    # voxel_faces: origin + extent per axis: a coordinate is an exact float32
+_FACES_MERGE = {"none": hip.FACES_MERGE_NONE, "runs": hip.FACES_MERGE_RUNS}
 MAX_GATHER_WORDS = 2 ** 31 - 1  # to_voxels / save_voxels: words of 64 voxels along x, ceil(nx / 64) * ny * nz
 
 
@@ -741,3 +747,204 @@ def from_voxels(records, shape, *, origin=(0, 0, 0), fmt="occupancy"):
     values = records[:, 3].to(torch.int32) if fmt == "argb" else torch.ones((), dtype=dtype, device=records.device).expand(xyz.shape[0])
     grid[xyz[:, 2], xyz[:, 1], xyz[:, 0]] = values
     return grid
+
+
+# ---- dense grids as blocky meshes -----------------------------------------------------------------------
+
+def _faces_args(dv, grid, level, origin, merge, argb, colors, palette):
+    """(device, the arguments of dv.faces_count, origin): the grid and colour arguments as to_voxels checks them, the merge
+    mode, and the origin within the box whose coordinates are exact float32."""
+    if merge not in _FACES_MERGE:
+        raise ValueError(f"merge must be 'none' or 'runs', not {merge!r}")
+    device, grid_args, (origin, mode, argb, colors_ptr, color_strides, palette) = _gather_args(dv, grid, level, origin, argb, colors, palette)
+    if any(o + n > MAX_FACES_EXTENT for o, n in zip(origin, grid_args[3])):
+        raise ValueError(f"origin {origin} + the grid's extent {grid_args[3]} [x, y, z] is above {MAX_FACES_EXTENT}")
+    return device, grid_args + (_FACES_MERGE[merge], mode, argb, colors_ptr, color_strides, palette), origin
+
+
+def count_faces(dv, grid, *, level=None, merge="none", argb=0xFFFFFFFF, colors=None, palette=None):
+    """The number of quads voxel_faces would return, counted on the voxelizer's device.  With
+    merge="none" and one colour it is the model's surface area in voxel faces.  Arguments as voxel_faces takes them."""
+    device, args, _ = _faces_args(dv, grid, level, (0, 0, 0), merge, argb, colors, palette)
+    _sync(device)   # (the caller's writes to grid and colors have landed)
+    return dv.faces_count(*args)
+
+
+def voxel_faces(dv, grid, *, level=None, origin=(0, 0, 0), merge="runs", argb=0xFFFFFFFF, colors=None, palette=None, transform=None):
+    """The voxel model of a dense grid as a mesh on the voxelizer's device: one quad per exposed voxel
+    face, coloured by its voxel.  Returns (positions float32 [4Q, 3], faces int32 [2Q, 3], quad_argb int32 [Q]), new contiguous
+    tensors in the shape set_mesh takes: quad q owns vertices 4q .. 4q + 3 and triangles 2q and 2q + 1, whose normals point out
+    of the solid voxel.  Quads come row by row, direction by direction (-x, +x, -y, +y, -z, +z) within a row, then by x.
+
+    grid, level, argb, colors, palette:  as to_voxels takes them.
+    origin:     (ox, oy, oz): voxel (x, y, z) is the cube from origin + (x, y, z) to origin + (x, y, z) + 1; origin + extent is
+                at most 65 536 per axis, so that every coordinate is an exact float32.
+    merge:      "runs": exposed faces of one direction that are neighbours along x (along y for the -x and +x faces) and whose
+                voxels have the same colour become one quad; "none": a quad per face.
+    transform:  None: positions in voxel space.  dv.transform() (the 12 floats, model to voxel space): positions in model
+                space, A^-1 p, computed in float64 and rounded once, as extract_surface does."""
+    device, args, origin = _faces_args(dv, grid, level, origin, merge, argb, colors, palette)
+    if transform is not None:
+        transform = torch.as_tensor(transform, dtype=torch.float64).reshape(-1)
+        if transform.numel() != 12:
+            raise ValueError("transform must hold 12 numbers: a row-major 3 x 3 matrix, then the translation")
+    _sync(device)   # (the caller's writes to grid and colors have landed)
+    n_quads = dv.faces_count(*args)
+    if 4 * n_quads > 2 ** 31 - 1:
+        raise ValueError(f"the grid has {n_quads} quads: 4 vertices each are more than 2^31 - 1 int32 indices")
+    positions = torch.empty((4 * n_quads, 3), dtype=torch.float32, device=device)
+    faces = torch.empty((2 * n_quads, 3), dtype=torch.int32, device=device)
+    quad_argb = torch.empty((n_quads,), dtype=torch.int32, device=device)
+    if n_quads:
+        dv.faces_write(*args, origin, positions.data_ptr(), faces.data_ptr(), quad_argb.data_ptr(), n_quads)
+    if transform is not None and n_quads:
+        inverse = torch.linalg.inv(transform[:9].reshape(3, 3)).to(device)   # (3 x 3, on the host)
+        p = positions.to(torch.float64) - transform[9:].to(device)
+        positions = (p[:, None, :] * inverse[None, :, :]).sum(dim=2).to(torch.float32).contiguous()
+    return positions, faces, quad_argb
+
+
+# ---- mesh files ------------------------------------------------------------------------------------------------------------------
+
+_MESH_BATCH = 1 << 20   # triangles (vertices) per write
+
+
+def _host_array(t, name, kinds, width):
+    a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    if a.ndim != 2 or a.shape[1] != width or a.dtype.kind not in kinds:
+        raise ValueError(f"{name} must be [n, {width}] of kind {kinds!r}, not {a.dtype} {a.shape}")
+    return a
+
+
+def _triangle_argb(argb, n_vertices, n_triangles):
+    """(per-triangle uint32 or None, per-vertex uint32 or None) of save_mesh's argb: one per triangle, per quad (two triangles
+    each, in order) or per vertex, looked for in that order."""
+    if argb is None:
+        return None, None
+    a = argb.detach().cpu().numpy() if isinstance(argb, torch.Tensor) else np.asarray(argb)
+    if a.ndim != 1 or a.dtype.kind not in "iu":
+        raise ValueError("argb must be a 1-D integer array")
+    a = (a.astype(np.int64) & 0xFFFFFFFF).astype(np.uint32)
+    if len(a) == n_triangles:
+        return a, None
+    if 2 * len(a) == n_triangles:
+        return np.repeat(a, 2), None
+    if len(a) == n_vertices:
+        return None, a
+    raise ValueError(f"argb has {len(a)} entries: neither one per triangle ({n_triangles}), per quad nor per vertex ({n_vertices})")
+
+
+def _save_stl(path, p, f):
+    rec = np.dtype([("n", "<f4", 3), ("v", "<f4", (3, 3)), ("attr", "<u2")])
+    with open(path, "wb") as out:
+        out.write(b"obj2voxel_amd dense.save_mesh".ljust(80, b" ") + np.uint32(len(f)).astype("<u4").tobytes())
+        for i in range(0, len(f), _MESH_BATCH):
+            v = p[f[i:i + _MESH_BATCH]]                                   # [n, 3, 3] float32
+            n = np.cross(v[:, 1] - v[:, 0], v[:, 2] - v[:, 0]).astype(np.float32)
+            length = np.sqrt((n * n).sum(axis=1, dtype=np.float32), dtype=np.float32)
+            n = np.where(length[:, None] > 0, n / np.where(length > 0, length, 1)[:, None], 0).astype(np.float32)
+            block = np.zeros(len(v), rec)
+            block["n"], block["v"] = n, v
+            out.write(block.tobytes())
+
+
+def _rgba(argb):
+    return np.stack([argb >> 16 & 255, argb >> 8 & 255, argb & 255, argb >> 24], axis=1).astype(np.uint8)
+
+
+def _save_ply(path, p, f, tri_argb, vert_argb):
+    if tri_argb is not None:
+        # a colour per vertex: the colour of its triangles, or - where triangles of two colours share a vertex - corners of their own
+        vert_argb = np.zeros(len(p), np.uint32)
+        vert_argb[f.reshape(-1)] = np.repeat(tri_argb, 3)
+        if not np.array_equal(vert_argb[f], np.repeat(tri_argb, 3).reshape(-1, 3)):
+            p, vert_argb = p[f.reshape(-1)], np.repeat(tri_argb, 3)
+            f = np.arange(3 * len(f), dtype=np.int64).reshape(-1, 3)
+    colored = vert_argb is not None
+    vt = np.dtype([("p", "<f4", 3)] + ([("c", "u1", 4)] if colored else []))
+    ft = np.dtype([("n", "u1"), ("i", "<i4", 3)])
+    header = ["ply", "format binary_little_endian 1.0", "comment obj2voxel_amd dense.save_mesh", f"element vertex {len(p)}",
+              "property float x", "property float y", "property float z"]
+    if colored:
+        header += ["property uchar red", "property uchar green", "property uchar blue", "property uchar alpha"]
+    header += [f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as out:
+        out.write(("\n".join(header) + "\n").encode())
+        for i in range(0, len(p), _MESH_BATCH):
+            block = np.zeros(len(p[i:i + _MESH_BATCH]), vt)
+            block["p"] = p[i:i + _MESH_BATCH]
+            if colored:
+                block["c"] = _rgba(vert_argb[i:i + _MESH_BATCH])
+            out.write(block.tobytes())
+        for i in range(0, len(f), _MESH_BATCH):
+            block = np.zeros(len(f[i:i + _MESH_BATCH]), ft)
+            block["n"], block["i"] = 3, f[i:i + _MESH_BATCH]
+            out.write(block.tobytes())
+
+
+def _save_obj(path, p, f, tri_argb):
+    mtl = os.path.splitext(path)[0] + ".mtl"
+    with open(path, "w") as out:
+        out.write("# obj2voxel_amd dense.save_mesh\n")
+        if tri_argb is not None:
+            out.write(f"mtllib {os.path.basename(mtl)}\n")
+        for i in range(0, len(p), _MESH_BATCH):
+            out.write("".join("v %.9g %.9g %.9g\n" % tuple(v) for v in p[i:i + _MESH_BATCH].tolist()))
+        if tri_argb is None:
+            order, groups = np.arange(len(f)), [(None, 0, len(f))]
+        else:
+            # the colours in order of first appearance; the triangles of a colour together, in their own order
+            colors, first, inverse = np.unique(tri_argb, return_index=True, return_inverse=True)
+            rank = np.empty(len(colors), np.int64)
+            rank[np.argsort(first, kind="stable")] = np.arange(len(colors))
+            order = np.argsort(rank[inverse], kind="stable")
+            bounds = np.concatenate([[0], np.cumsum(np.bincount(rank[inverse], minlength=len(colors)))])
+            by_rank = colors[np.argsort(first, kind="stable")]
+            groups = [(int(c), int(bounds[k]), int(bounds[k + 1])) for k, c in enumerate(by_rank)]
+        one_based = f[order] + 1
+        for c, lo, hi in groups:
+            if c is not None:
+                out.write("usemtl c_%08X\n" % c)
+            for i in range(lo, hi, _MESH_BATCH):
+                out.write("".join("f %d %d %d\n" % tuple(t) for t in one_based[i:min(hi, i + _MESH_BATCH)].tolist()))
+    if tri_argb is not None:
+        with open(mtl, "w") as out:
+            out.write("# obj2voxel_amd dense.save_mesh\n")
+            for c, _, _ in groups:
+                out.write("newmtl c_%08X\nKd %.9g %.9g %.9g\nd %.9g\n" % (c, (c >> 16 & 255) / 255, (c >> 8 & 255) / 255, (c & 255) / 255, (c >> 24) / 255))
+
+
+def save_mesh(path, positions, faces, *, argb=None, fmt=None):
+    """An indexed triangle mesh - what voxel_faces and extract_surface return - written to a mesh file,
+    on the host, in batches.
+
+    positions:  float32 [V, 3]; faces: integer [T, 3], indices into positions (tensors on any device, or arrays).
+    argb:       None, or an integer array of one colour (argb bits) per triangle, per quad (two triangles each: voxel_faces'
+                quad_argb) or per vertex - told apart by its length, in that order.
+    fmt:        "stl", "ply" or "obj"; None: the path's extension.  Anything else raises ValueError.
+      .stl  binary; the normal of a triangle is its normalised float32 cross product (v1 - v0) x (v2 - v0), zero where that
+            is zero; colours are not stored.
+      .ply  binary_little_endian 1.0: vertices float x y z, plus uchar red green blue alpha when colours are given (triangles of
+            two colours that share a vertex get corners of their own); faces list uchar int vertex_indices.
+      .obj  with a .mtl of the same name beside it when colours are given: one newmtl c_AARRGGBB with Kd (and d, the alpha) per
+            distinct colour, the triangles grouped by usemtl in order of the colours' first appearance - the form the library's
+            own OBJ reader takes.  Colours per triangle or quad only."""
+    path = os.fspath(path)
+    if fmt is not None and not isinstance(fmt, str):
+        raise TypeError(f"fmt must be a string or None, not {fmt!r}")
+    kind = (os.path.splitext(path)[1][1:] if fmt is None else fmt).lower()
+    if kind not in ("stl", "ply", "obj"):
+        raise ValueError(f"{kind!r} is not a mesh file type: stl, ply or obj")
+    p = np.ascontiguousarray(_host_array(positions, "positions", "f", 3), dtype=np.float32)
+    f = _host_array(faces, "faces", "iu", 3).astype(np.int64)
+    if len(f) and (f.min() < 0 or f.max() >= len(p)):
+        raise ValueError(f"faces index outside the {len(p)} positions")
+    tri_argb, vert_argb = _triangle_argb(argb, len(p), len(f))
+    if kind == "stl":
+        _save_stl(path, p, f)
+    elif kind == "ply":
+        _save_ply(path, p, f, tri_argb, vert_argb)
+    else:
+        if vert_argb is not None:
+            raise ValueError("an .obj file takes colours per triangle or quad (materials); per-vertex colours need .ply")
+        _save_obj(path, p, f, tri_argb)

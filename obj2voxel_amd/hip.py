@@ -31,7 +31,9 @@ CC_INVERT, CC_SEED_BORDER = 16, 32  # ... their flags (with FLAG_STAGE_TIMES: th
 CC_SCRATCH_LABELS, CC_SCRATCH_LABELS_STRIDED, CC_SCRATCH_FLOOD = 0, 1, 2  # o2v_hip_components_scratch_bytes
 MESH_DIST_UNSIGNED_F32, MESH_DIST_SIGNED_F32 = 0, 1  # o2v_hip_mesh_distance_dense formats
 GATHER_COLOR_CONSTANT, GATHER_COLOR_GRID, GATHER_COLOR_PALETTE = 0, 1, 2  # o2v_hip_gather_write / _save colour modes
+FACES_MERGE_NONE, FACES_MERGE_RUNS = 0, 1  # o2v_hip_faces_count / _write merge modes
 ERR_BAD_ARGUMENT = 3
+ERR_LIMIT = 5
 ERR_IO = 6  # o2v_hip_gather_save: the file cannot be opened, is of no output type, or stopped taking voxels
 
 
@@ -153,6 +155,12 @@ def _bind():
     L.o2v_hip_gather_scratch_bytes.argtypes = [C.c_void_p]
     L.o2v_hip_gather_scratch_bytes.restype = C.c_uint64
     L.o2v_hip_gather_times.argtypes = [C.c_void_p, C.c_void_p]
+    _faces = _gather + [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]   # ..., merge, mode, argb, colors, strides, palette
+    L.o2v_hip_faces_count.argtypes = _faces + [C.POINTER(C.c_uint64)]
+    L.o2v_hip_faces_write.argtypes = _faces + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+    L.o2v_hip_faces_scratch_bytes.argtypes = [C.c_void_p, C.c_uint32]
+    L.o2v_hip_faces_scratch_bytes.restype = C.c_uint64
+    L.o2v_hip_faces_times.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_max_slab_layers.argtypes = [C.c_void_p, C.POINTER(_Params), C.POINTER(C.c_uint32)]
     return L
 
@@ -216,6 +224,11 @@ def components_scratch_bytes(dims, which=CC_SCRATCH_LABELS):
 def gather_scratch_bytes(dims):
     """o2v_hip_gather_scratch_bytes: the context scratch a gather_count over dims (x, y, z) takes."""
     return int(_bind().o2v_hip_gather_scratch_bytes(_u32x3(dims)))
+
+
+def faces_scratch_bytes(dims, color_mode=GATHER_COLOR_CONSTANT):
+    """o2v_hip_faces_scratch_bytes: the context scratch a faces_count over dims (x, y, z) takes at most."""
+    return int(_bind().o2v_hip_faces_scratch_bytes(_u32x3(dims), color_mode))
 
 
 def device_count():
@@ -466,6 +479,38 @@ class DeviceVoxelizer:
         """o2v_hip_gather_times: the device times (ms) of the last gather_count's classify and count + scan stages and of the
         last gather_write."""
         return self._stage_times("o2v_hip_gather_times", 3)
+
+    def _faces_args(self, grid_ptr, fmt, strides, dims, level, merge, color_mode, argb, colors_ptr, color_strides, palette):
+        pal = None if palette is None else (C.c_uint32 * 256)(*[int(v) & 0xFFFFFFFF for v in palette])
+        return (self._ctx, grid_ptr, fmt, _u64x3(strides), _u32x3(dims), float(level), merge, color_mode, int(argb) & 0xFFFFFFFF, colors_ptr,
+                _u64x3(color_strides), pal)
+
+    def faces_count(self, grid_ptr, fmt, strides, dims, level, merge, color_mode, argb, colors_ptr, color_strides, palette):
+        """o2v_hip_faces_count: the number of quads of the grid's exposed voxel faces (grid arguments as gather_count takes them;
+        merge: FACES_MERGE_NONE - one per face - or FACES_MERGE_RUNS - one per run of faces of one colour; the colour arguments
+        as gather_write takes them).  The one pass over the grid: the set's bits stay in the context for faces_write."""
+        n = C.c_uint64(0)
+        self._check(self._L.o2v_hip_faces_count(*self._faces_args(grid_ptr, fmt, strides, dims, level, merge, color_mode, argb, colors_ptr,
+                                                                  color_strides, palette), C.byref(n)), "o2v_hip_faces_count")
+        return int(n.value)
+
+    def faces_write(self, grid_ptr, fmt, strides, dims, level, merge, color_mode, argb, colors_ptr, color_strides, palette, origin,
+                    positions_ptr, faces_ptr, quad_argb_ptr, quad_capacity):
+        """o2v_hip_faces_write: all quads of the faces_count before it (the same arguments) to the device addresses positions_ptr
+        (float32 [4Q, 3]), faces_ptr (int32 [2Q, 3], or None) and quad_argb_ptr (uint32 [Q], or None), each with room for
+        quad_capacity quads."""
+        self._check(self._L.o2v_hip_faces_write(*self._faces_args(grid_ptr, fmt, strides, dims, level, merge, color_mode, argb, colors_ptr,
+                                                                  color_strides, palette), _u32x3(origin), positions_ptr, faces_ptr,
+                                                quad_argb_ptr, quad_capacity), "o2v_hip_faces_write")
+
+    def faces_scratch_bytes(self, dims, color_mode=GATHER_COLOR_CONSTANT):
+        """o2v_hip_faces_scratch_bytes: the context scratch a faces_count over dims (x, y, z) takes at most."""
+        return faces_scratch_bytes(dims, color_mode)
+
+    def faces_times(self):
+        """o2v_hip_faces_times: the device times (ms) of the last faces_count's classify and count + scan stages and of the last
+        faces_write."""
+        return self._stage_times("o2v_hip_faces_times", 3)
 
     def set_textures(self, textures):
         """textures: sequence of (uint8 [h, w, c] pixels, wrap) with c in (3, 4)."""

@@ -656,6 +656,53 @@ uint64_t o2v_hip_faces_scratch_bytes(const uint32_t dims[3], uint32_t color_mode
  * after a count). */
 int o2v_hip_faces_times(const o2v_hip_ctx *ctx, float out_ms[3]);
 
+/* ---- nearest-voxel transform -------------------------------------------------------------------
+ *
+ * For every voxel of a box, which voxel of a seed set is closest to it, and optionally that seed's value: the feature
+ * transform that goes with o2v_hip_distance_dense.
+ *
+ * The seeds.  dims = (nx, ny, nz).  grid, format, strides, dims and level are those of o2v_hip_components_dense: a voxel is a
+ * seed where a O2V_HIP_GRID_U8 element is non-zero, where its O2V_HIP_GRID_BITS bit is set, where a O2V_HIP_GRID_F32_BELOW
+ * element is < level (finite).  With O2V_HIP_NEAREST_SEED_ONE in flags (U8 only) a seed is an element that is exactly 1: the
+ * rule of o2v_hip_distance_dense for label grids (1 surface, 2 interior).  S is the set of seeds; grid is only read.
+ *
+ * For every voxel v of the box:
+ *   d2(v)      = min over s in S of |v - s|^2, an exact integer, as o2v_hip_distance_dense defines it;
+ *   nearest(v) = the linear index (sz * ny + sy) * nx + sx of the seed that attains d2(v); among several at that distance the
+ *                one with the smallest linear index - the lexicographically smallest (z, y, x).  A seed is its own nearest.
+ *                -1 everywhere when S is empty.
+ *
+ * Outputs, device memory, strides in elements per axis x, y, z, any order; none may map two voxels to one element:
+ *   nearest  int32, required; every voxel of the box is written (the passes use it as their working buffer).
+ *   dist2    int32, may be NULL: d2(v), or 0x7FFFFFFF without seeds - bit for bit what o2v_hip_distance_dense DIST_SQ_I32 gives
+ *            for the same seed set.
+ *   values   int32, may be NULL, updated in place: for every voxel v that is not a seed, has nearest(v) >= 0 and
+ *            d2(v) <= max_dist2, values(v) = values(nearest(v)).  With O2V_HIP_NEAREST_VALUES_INSIDE (U8 only) also only
+ *            where the grid's element at v is non-zero - with SEED_ONE the interior voxels (2) of a label grid and nothing
+ *            else.  Every other element keeps its bits.  Seeds are only read and the others only written, so the update has
+ *            no race and one run equals another bit for bit.  max_dist2 = 0x7FFFFFFF (or more): no limit.  It limits values
+ *            only: nearest and dist2 are always complete.
+ *
+ * Refused before anything is launched, the outputs untouched.  O2V_HIP_ERR_LIMIT: nx * ny * nz above 2^31 - 1 (an index is one
+ * int32), (nx-1)^2 + (ny-1)^2 + (nz-1)^2 above 2^31 - 2 (o2v_hip_distance_dense's limit; with it an axis has at most 46 341
+ * voxels) - both before the pointers are looked at.  O2V_HIP_ERR_BAD_ARGUMENT: zero dims, a null argument, an unknown format or
+ * flag, a level that is not finite, a BITS grid with strides[0] != 1, a flag on a grid that is not U8, output strides that map
+ * two voxels to one element, any two of grid, nearest, dist2 and values overlapping, a pointer that is not device memory of the
+ * context's device with the box's highest address inside its allocation.
+ *
+ * The envelope stacks are the context's scratch of o2v_hip_distance_dense, o2v_hip_nearest_scratch_bytes(dims) =
+ * o2v_hip_distance_scratch_bytes(dims, ...) bytes, grown on demand; if it cannot be allocated the call returns
+ * O2V_HIP_ERR_OUT_OF_MEMORY and the context stays usable.  The call runs on the context's stream and returns when the writes
+ * have landed (the caller must have finished writing grid and values). */
+enum { O2V_HIP_NEAREST_SEED_ONE = 1u, O2V_HIP_NEAREST_VALUES_INSIDE = 2u };
+int o2v_hip_nearest_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+                          uint32_t flags, int32_t *nearest, const uint64_t nearest_strides[3], int32_t *dist2 /* may be NULL */,
+                          const uint64_t dist2_strides[3], int32_t *values /* may be NULL */, const uint64_t value_strides[3],
+                          uint32_t max_dist2);
+uint64_t o2v_hip_nearest_scratch_bytes(const uint32_t dims[3]);
+/* The device times of the last o2v_hip_nearest_dense call's three passes (x, y, z), from events around each, in ms. */
+int o2v_hip_nearest_times(const o2v_hip_ctx *ctx, float out_ms[3]);
+
 int o2v_hip_get_timings(const o2v_hip_ctx *ctx, o2v_hip_timings *out);
 /* Per-kernel device times of the last o2v_hip_voxelize call made with O2V_HIP_FLAG_KERNEL_TIMES (else none): up to
  * max_entries entries are written, *out_count receives how many there are. */

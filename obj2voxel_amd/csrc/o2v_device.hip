@@ -38,6 +38,8 @@
 //                              records, in ranges, and as a voxel file; outside the pipeline
 //   K14 k_faces_*              o2v_hip_faces_count / _write: the exposed voxel faces of a dense grid as coloured quads, merged
 //                              into runs; outside the pipeline
+//   K15 k_near_*               o2v_hip_nearest_dense: the nearest seed voxel of every voxel (K8's passes with the seed's
+//                              coordinates as payload) and its value spread over the grid; outside the pipeline
 //   plan k_zhist               o2v_hip_plan_slabs: predicted hits per z layer -> work-balanced slabs for N GPUs
 // With the direct MAX path K1's counters reach the host while K2 runs, and only the stages that have work are enqueued
 // behind it.  N > 1 GPUs: o2v_hip_voxelize_sharded (bounds / work-histogram passes sharded over the ranks, RCCL).
@@ -88,6 +90,7 @@ namespace {
 #include "o2v_dev_k12_components.hpp"
 #include "o2v_dev_k13_gather.hpp"
 #include "o2v_dev_k14_faces.hpp"
+#include "o2v_dev_k15_nearest.hpp"
 
 }  // namespace
 
@@ -329,6 +332,8 @@ struct o2v_hip_ctx {
     // K8 (o2v_hip_distance_dense): the envelope stacks, grown on demand; the times of the three passes
     DevArray<uint2> d_dist_stack;
     StageTimes<3> dist_times;
+    // K15 (o2v_hip_nearest_dense): its envelope stacks are K8's (d_dist_stack); the times of its three passes
+    StageTimes<3> near_times;
     // K9 (o2v_hip_mesh_distance_dense): sample-space vertices, per-tile counters, offsets and triangle lists, grown on demand;
     // the times of the three stages
     DevArray<float> d_md_sv;
@@ -2660,6 +2665,112 @@ int o2v_hip_distance_dense(o2v_hip_ctx *ctx, const void *labels, const uint64_t 
 int o2v_hip_distance_times(const o2v_hip_ctx *ctx, float out_ms[3])
 {
     return ctx ? ctx->dist_times.read(out_ms) : O2V_HIP_ERR_BAD_ARGUMENT;
+}
+
+}  // extern "C"
+
+// ---- K15: the nearest seed voxel of every voxel, and its value -----------------------------------------------------------
+
+namespace {
+
+constexpr uint32_t kNearFlagsKnown = O2V_HIP_NEAREST_SEED_ONE | O2V_HIP_NEAREST_VALUES_INSIDE;
+
+template <uint32_t Format>
+void launch_near_x(o2v_hip_ctx *ctx, hipStream_t s, uint64_t rows, int32_t *out, const NearGrid &g)
+{
+    hipLaunchKernelGGL(k_near_x<Format>, dim3((uint32_t) std::min<uint64_t>((uint64_t) ctx->num_cus * 8u, (rows + 3u) / 4u)), dim3(kBlock), 0, s,
+                       out, g);
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t o2v_hip_nearest_scratch_bytes(const uint32_t dims[3]) { return o2v_hip_distance_scratch_bytes(dims, O2V_HIP_DIST_SQ_I32); }
+
+int o2v_hip_nearest_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+                          uint32_t flags, int32_t *nearest, const uint64_t nearest_strides[3], int32_t *dist2, const uint64_t dist2_strides[3],
+                          int32_t *values, const uint64_t value_strides[3], uint32_t max_dist2)
+{
+    static const char fn[] = "o2v_hip_nearest_dense";
+    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
+    if (!grid || !strides || !dims || !nearest || !nearest_strides || (dist2 && !dist2_strides) || (values && !value_strides))
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
+    if (format != O2V_HIP_GRID_U8 && format != O2V_HIP_GRID_BITS && format != O2V_HIP_GRID_F32_BELOW)
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown format " + std::to_string(format));
+    if (flags & ~kNearFlagsKnown) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown flag bits in " + std::to_string(flags));
+    if (!dims[0] || !dims[1] || !dims[2]) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "zero dims");
+    const unsigned __int128 voxels = (unsigned __int128) dims[0] * dims[1] * dims[2];
+    if (voxels > 0x7fffffffull)
+        return refuse(ctx, O2V_HIP_ERR_LIMIT, fn,
+                      std::to_string(dims[0]) + " x " + std::to_string(dims[1]) + " x " + std::to_string(dims[2]) +
+                          " voxels do not fit an int32 index (at most 2^31 - 1)");
+    uint64_t d2max = 0;
+    for (int a = 0; a < 3; ++a) d2max += (uint64_t) (dims[a] - 1u) * (dims[a] - 1u);
+    if (d2max > 0x7ffffffeull)
+        return refuse(ctx, O2V_HIP_ERR_LIMIT, fn,
+                      "(nx-1)^2 + (ny-1)^2 + (nz-1)^2 = " + std::to_string(d2max) + " does not fit below 2^31 - 1");
+    if (format == O2V_HIP_GRID_BITS && strides[0] != 1u) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "a BITS grid needs strides[0] == 1");
+    if (format == O2V_HIP_GRID_F32_BELOW && !std::isfinite(level)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "level must be finite");
+    if (format != O2V_HIP_GRID_U8 && flags)
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "SEED_ONE and VALUES_INSIDE need a U8 grid");
+    O2V_CHECK(hipSetDevice(ctx->device));
+    const uint32_t reach[3] = {format == O2V_HIP_GRID_BITS ? (dims[0] + 31u) / 32u : dims[0], dims[1], dims[2]};
+    struct Range {
+        const char *what;
+        const void *p;
+        uint64_t bytes;
+    } r[4] = {{"grid", grid, 0}, {"nearest", nearest, 0}, {"dist2", dist2, 0}, {"values", values, 0}};
+    const uint64_t *const out_strides[4] = {nullptr, nearest_strides, dist2_strides, value_strides};
+    int rc;
+    if ((rc = check_grid(ctx, fn, "grid", grid, reach, strides, format == O2V_HIP_GRID_U8 ? 1u : 4u, false, &r[0].bytes))) return rc;
+    for (int i = 1; i < 4; ++i)
+        if (r[i].p && (rc = check_grid(ctx, fn, r[i].what, r[i].p, dims, out_strides[i], 4u, true, &r[i].bytes))) return rc;
+    for (int i = 0; i < 4; ++i)
+        for (int j = i + 1; j < 4; ++j)
+            if (r[i].p && r[j].p && ranges_overlap(r[i].p, r[i].bytes, r[j].p, r[j].bytes))
+                return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, std::string(r[i].what) + " and " + r[j].what + " overlap");
+    if ((rc = grow_scratch(ctx, ctx->d_dist_stack, o2v_hip_nearest_scratch_bytes(dims) / sizeof(uint2), fn, "scratch"))) return rc;
+    hipStream_t s = ctx->stream;
+    const NearGrid g{grid, strides[0], strides[1], strides[2], level, nearest_strides[0], nearest_strides[1], nearest_strides[2],
+                     dims[0], dims[1], dims[2]};
+    NearOut o{};
+    if (dist2) o.dist2 = dist2, o.e0 = dist2_strides[0], o.e1 = dist2_strides[1], o.e2 = dist2_strides[2];
+    if (values) o.values = values, o.v0 = value_strides[0], o.v1 = value_strides[1], o.v2 = value_strides[2];
+    o.max_dist2 = max_dist2;
+    uint2 *const stack = ctx->d_dist_stack.ptr;
+    // passes y and z: each with its own slots (the stride of its stacks), as K8's
+    const uint64_t sy = dist_slots((uint64_t) dims[0] * dims[2]), sz = dist_slots((uint64_t) dims[0] * dims[1]);
+    const uint32_t gy = (uint32_t) ((sy + kBlock - 1) / kBlock), gz = (uint32_t) ((sz + kBlock - 1) / kBlock);
+    const uint64_t rows = (uint64_t) dims[1] * dims[2];
+    O2V_CHECK(ctx->near_times.mark(0, s));
+    if (format == O2V_HIP_GRID_BITS)
+        launch_near_x<kNearBits>(ctx, s, rows, nearest, g);
+    else if (format == O2V_HIP_GRID_F32_BELOW)
+        launch_near_x<kNearF32Below>(ctx, s, rows, nearest, g);
+    else if (flags & O2V_HIP_NEAREST_SEED_ONE)
+        launch_near_x<kNearU8One>(ctx, s, rows, nearest, g);
+    else
+        launch_near_x<kNearU8>(ctx, s, rows, nearest, g);
+    O2V_CHECK(ctx->near_times.mark(1, s));
+    hipLaunchKernelGGL((k_near_envelope<kNearY, kNearNoPaint>), dim3(gy), dim3(kBlock), 0, s, nearest, g, o, stack, sy);
+    O2V_CHECK(ctx->near_times.mark(2, s));
+    if (!values)
+        hipLaunchKernelGGL((k_near_envelope<kNearZ, kNearNoPaint>), dim3(gz), dim3(kBlock), 0, s, nearest, g, o, stack, sz);
+    else if (flags & O2V_HIP_NEAREST_VALUES_INSIDE)
+        hipLaunchKernelGGL((k_near_envelope<kNearZ, kNearPaintInside>), dim3(gz), dim3(kBlock), 0, s, nearest, g, o, stack, sz);
+    else
+        hipLaunchKernelGGL((k_near_envelope<kNearZ, kNearPaint>), dim3(gz), dim3(kBlock), 0, s, nearest, g, o, stack, sz);
+    O2V_CHECK(hipGetLastError());
+    O2V_CHECK(ctx->near_times.mark(3, s));
+    O2V_CHECK(hipStreamSynchronize(s));
+    O2V_CHECK(ctx->near_times.finish());
+    return O2V_HIP_OK;
+}
+
+int o2v_hip_nearest_times(const o2v_hip_ctx *ctx, float out_ms[3])
+{
+    return ctx ? ctx->near_times.read(out_ms) : O2V_HIP_ERR_BAD_ARGUMENT;
 }
 
 }  // extern "C"

@@ -16,11 +16,14 @@ components / flood and what is built on them (exterior, solidify, remove_small) 
 (o2v_hip_components_dense / o2v_hip_flood_dense); to_voxels / count_voxels / save_voxels turn any of these
 grids back into (x, y, z, argb) records and voxel files (o2v_hip_gather_count / _write / _save, DESIGN.md section 16);
 voxel_faces / count_faces turn them into the blocky mesh of the voxel model (o2v_hip_faces_count / _write)
-and save_mesh writes that mesh, or extract_surface's, as STL, PLY or OBJ + MTL.
+and save_mesh writes that mesh, or extract_surface's, as STL, PLY or OBJ + MTL; nearest_voxel says which seed voxel of a grid is
+closest to every voxel and spread_colors carries the seeds' colours to the voxels that take them - the interior of a solid, a
+shell of a given thickness (o2v_hip_nearest_dense).
 
 torch is imported first on purpose: the library must bind to the HIP runtime torch loaded (a process that loaded the library
 before torch holds two separate runtime copies, and this module refuses to work there).
 """
+import math
 import numbers
 import os
 
@@ -49,6 +52,7 @@ MAX_CC_VOXELS = 2 ** 31 - 1  # ... and in all: a linear index and a label are on
 MAX_FACES_EXTENT = 65536    # voxel_faces: origin + extent per axis: a coordinate is an exact float32
 _FACES_MERGE = {"none": hip.FACES_MERGE_NONE, "runs": hip.FACES_MERGE_RUNS}
 MAX_GATHER_WORDS = 2 ** 31 - 1  # to_voxels / save_voxels: words of 64 voxels along x, ceil(nx / 64) * ny * nz
+MAX_NEAREST_D2 = 2 ** 31 - 2    # nearest_voxel / spread_colors: (nx-1)^2 + (ny-1)^2 + (nz-1)^2, the largest squared distance
 
 
 def _require_shared_runtime():
@@ -802,6 +806,119 @@ def voxel_faces(dv, grid, *, level=None, origin=(0, 0, 0), merge="runs", argb=0x
         p = positions.to(torch.float64) - transform[9:].to(device)
         positions = (p[:, None, :] * inverse[None, :, :]).sum(dim=2).to(torch.float32).contiguous()
     return positions, faces, quad_argb
+
+
+# ---- the nearest seed voxel and its colour ---------------------------------------------------------------
+
+def _nearest_args(dv, seeds, level, surface_only):
+    """(device, (seeds_ptr, format, strides, dims, level, flags), voxel shape) of the seed grid of nearest_voxel / spread_colors,
+    checked as components checks its grid, and against the distance limit."""
+    device, fmt, level, dims = _cc_grid(dv, seeds, level, 6)
+    if sum((n - 1) ** 2 for n in dims) > MAX_NEAREST_D2:
+        raise ValueError(f"the grid's extent {dims} [x, y, z] has (nx-1)^2 + (ny-1)^2 + (nz-1)^2 above {MAX_NEAREST_D2}")
+    if surface_only and fmt != hip.GRID_U8:
+        raise ValueError(f"surface_only needs a bool or uint8 grid (a seed is a voxel of value 1), not {seeds.dtype}")
+    flags = hip.NEAREST_SEED_ONE if surface_only else 0
+    return device, (seeds.data_ptr(), fmt, _strides(seeds), dims, 0.0 if level is None else level, flags), (dims[2], dims[1], dims[0])
+
+
+def _outside_storage(t, name, seeds):
+    if t.untyped_storage().data_ptr() == seeds.untyped_storage().data_ptr():
+        raise ValueError(f"{name} must not share the seeds' storage")
+
+
+def nearest_voxel(dv, seeds, *, level=None, surface_only=False, dist2=None, out=None):
+    """For every voxel of a dense grid the seed voxel closest to it: an int32 tensor [z, y, x] of the
+    seed's linear index (sz * ny + sy) * nx + sx - among several seeds at the same distance the smallest index, the seed itself
+    on a seed, -1 everywhere when there is no seed.  nearest_coords turns it into coordinates; colors.view(-1)[nearest] is not
+    needed for colours: spread_colors does that on the device.  Returns nearest, or (nearest, dist2) when dist2 is given.
+
+    seeds:         as components takes its grid: bool or uint8 (a seed where != 0), int32 (the words of fmt="bits": 32 voxels
+                   per word along x) or float32 with `level` (a seed where seeds < level).  It is only read.
+    surface_only:  True: a seed is a voxel of value 1 of a bool / uint8 grid - the surface of fmt="labels", whose interior is 2.
+    dist2:         None; True for a new int32 tensor; or an int32 tensor of the voxel shape (any strides): the squared distance
+                   to that seed, 0x7FFFFFFF without seeds - what distance_transform(..., "dist2") gives for the same seeds.
+    out:           an int32 tensor of the voxel shape (any strides, not in the seeds' storage), written as it is; else a new
+                   contiguous tensor."""
+    device, args, shape = _nearest_args(dv, seeds, level, surface_only)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int32, device=device)
+    else:
+        _check_grid(out, "out", torch.int32, device, shape)
+        _outside_storage(out, "out", seeds)
+    want_dist2 = dist2 is not None and dist2 is not False
+    if dist2 is True:
+        dist2 = torch.empty(shape, dtype=torch.int32, device=device)
+    elif want_dist2:
+        _check_grid(dist2, "dist2", torch.int32, device, shape)
+        _outside_storage(dist2, "dist2", seeds)
+        if dist2.untyped_storage().data_ptr() == out.untyped_storage().data_ptr():
+            raise ValueError("dist2 must not share out's storage")
+    else:
+        dist2 = None
+    _sync(device)   # (the caller's writes to seeds, out and dist2 have landed)
+    dv.nearest_dense(*args, out.data_ptr(), _strides(out), _ptr(dist2), None if dist2 is None else _strides(dist2))
+    return (out, dist2) if want_dist2 else out
+
+
+def spread_colors(dv, seeds, colors, *, level=None, surface_only=False, inside_only=False, max_distance=None, out=None):
+    """The seeds' colours carried to the voxels they are nearest to: every voxel that is not a seed takes
+    colors at its nearest seed (nearest_voxel's: the smallest index on a tie); seeds keep theirs, and without seeds nothing
+    changes.  Returns the painted tensor.
+
+        labels, origin = dense.voxelize_dense(dv, 256, fmt="labels", fill=True)
+        argb, _ = dense.voxelize_dense(dv, 256, fmt="argb", fill=True)
+        dense.spread_colors(dv, labels, argb, surface_only=True, inside_only=True, out=argb)   # the interior takes the surface's colours
+
+    seeds, level, surface_only:  as nearest_voxel takes them.
+    colors:        an int32 tensor of the voxel shape [z, y, x] (any strides: an fmt="argb" grid); any 32 bits per voxel.
+    inside_only:   True (with surface_only=True): only the voxels whose seeds element is non-zero are painted - the interior (2)
+                   of a label grid; the exterior keeps its bits.
+    max_distance:  a number >= 0, in voxels: only voxels at most that far from their seed are painted (d2 <= floor(r * r), exact:
+                   d2 is an integer) - a coloured shell of that thickness.  None: no limit.
+    out:           None: a painted contiguous copy, colors untouched; colors itself: painted in place; another int32 tensor of
+                   that shape (any strides, not in the seeds' storage): filled with colors, then painted."""
+    device, args, shape = _nearest_args(dv, seeds, level, surface_only)
+    if inside_only and not surface_only:
+        raise ValueError("inside_only needs surface_only=True: the seeds are the voxels of value 1, the inside the other non-zero ones")
+    max_dist2 = hip.NEAREST_NO_LIMIT
+    if max_distance is not None:
+        if isinstance(max_distance, bool) or not isinstance(max_distance, numbers.Real) or not float(max_distance) >= 0.0:
+            raise ValueError(f"max_distance must be a number >= 0 or None, not {max_distance!r}")
+        if float(max_distance) * float(max_distance) < hip.NEAREST_NO_LIMIT:
+            max_dist2 = math.floor(max_distance * max_distance)
+    _check_grid(colors, "colors", torch.int32, device, shape)
+    same = out is colors or (isinstance(out, torch.Tensor) and out.dtype == colors.dtype and out.data_ptr() == colors.data_ptr()
+                             and out.shape == colors.shape and out.stride() == colors.stride())
+    if out is None:
+        target = colors.clone(memory_format=torch.contiguous_format)
+    elif same:
+        target = colors
+    else:
+        _check_grid(out, "out", torch.int32, device, shape)
+        target = out
+    _outside_storage(target, "colors" if same else "out", seeds)
+    if out is not None and not same:
+        target.copy_(colors)
+    nearest = torch.empty(shape, dtype=torch.int32, device=device)
+    flags = args[5] | (hip.NEAREST_VALUES_INSIDE if inside_only else 0)
+    _sync(device)   # (the caller's writes to seeds and colors and the copy above have landed)
+    dv.nearest_dense(*args[:5], flags, nearest.data_ptr(), _strides(nearest), None, None, target.data_ptr(), _strides(target), max_dist2)
+    return target
+
+
+def nearest_coords(nearest):
+    """int32 [z, y, x, 3]: the (x, y, z) of nearest_voxel's linear indices, (-1, -1, -1) where nearest < 0.  Plain torch."""
+    if not isinstance(nearest, torch.Tensor) or nearest.dim() != 3:
+        raise ValueError("nearest must be a 3-D tensor [z, y, x]")
+    if nearest.dtype != torch.int32:
+        raise TypeError(f"nearest must be torch.int32, not {nearest.dtype}")
+    _, ny, nx = nearest.shape
+    i = nearest.clamp(min=0)
+    row = torch.div(i, nx, rounding_mode="floor")
+    xyz = torch.stack((i - row * nx, row % ny, torch.div(row, ny, rounding_mode="floor")), dim=-1).to(torch.int32)
+    xyz[nearest < 0] = -1
+    return xyz
 
 
 # ---- mesh files ------------------------------------------------------------------------------------------------------------------

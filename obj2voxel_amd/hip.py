@@ -32,6 +32,8 @@ CC_SCRATCH_LABELS, CC_SCRATCH_LABELS_STRIDED, CC_SCRATCH_FLOOD = 0, 1, 2  # o2v_
 MESH_DIST_UNSIGNED_F32, MESH_DIST_SIGNED_F32 = 0, 1  # o2v_hip_mesh_distance_dense formats
 GATHER_COLOR_CONSTANT, GATHER_COLOR_GRID, GATHER_COLOR_PALETTE = 0, 1, 2  # o2v_hip_gather_write / _save colour modes
 FACES_MERGE_NONE, FACES_MERGE_RUNS = 0, 1  # o2v_hip_faces_count / _write merge modes
+NEAREST_SEED_ONE, NEAREST_VALUES_INSIDE = 1, 2  # o2v_hip_nearest_dense flags
+NEAREST_NO_LIMIT = 0x7FFFFFFF  # ... its max_dist2 without a limit
 ERR_BAD_ARGUMENT = 3
 ERR_LIMIT = 5
 ERR_IO = 6  # o2v_hip_gather_save: the file cannot be opened, is of no output type, or stopped taking voxels
@@ -161,6 +163,10 @@ def _bind():
     L.o2v_hip_faces_scratch_bytes.argtypes = [C.c_void_p, C.c_uint32]
     L.o2v_hip_faces_scratch_bytes.restype = C.c_uint64
     L.o2v_hip_faces_times.argtypes = [C.c_void_p, C.c_void_p]
+    L.o2v_hip_nearest_dense.argtypes = _gather + [C.c_uint32] + [C.c_void_p] * 6 + [C.c_uint32]   # ..., flags, 3 x (grid, strides), max_dist2
+    L.o2v_hip_nearest_scratch_bytes.argtypes = [C.c_void_p]
+    L.o2v_hip_nearest_scratch_bytes.restype = C.c_uint64
+    L.o2v_hip_nearest_times.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_max_slab_layers.argtypes = [C.c_void_p, C.POINTER(_Params), C.POINTER(C.c_uint32)]
     return L
 
@@ -511,6 +517,25 @@ class DeviceVoxelizer:
         """o2v_hip_faces_times: the device times (ms) of the last faces_count's classify and count + scan stages and of the last
         faces_write."""
         return self._stage_times("o2v_hip_faces_times", 3)
+
+    def nearest_dense(self, grid_ptr, fmt, strides, dims, level, flags, nearest_ptr, nearest_strides, dist2_ptr=None, dist2_strides=None,
+                      values_ptr=None, value_strides=None, max_dist2=NEAREST_NO_LIMIT):
+        """o2v_hip_nearest_dense: for every voxel the linear index (z * ny + y) * nx + x of the nearest seed of the grid at device
+        address grid_ptr (grid arguments as gather_count takes them; NEAREST_SEED_ONE in flags: a uint8 element that is 1), the
+        smallest index on a tie and -1 without seeds, into int32 at nearest_ptr; if dist2_ptr is given the squared distance
+        (int32); if values_ptr is given, int32 values updated in place: a voxel that is no seed and has d2 <= max_dist2 takes its
+        nearest seed's value (NEAREST_VALUES_INSIDE: only where the uint8 grid is non-zero).  Strides in elements per axis x, y, z."""
+        self._check(self._L.o2v_hip_nearest_dense(self._ctx, grid_ptr, fmt, _u64x3(strides), _u32x3(dims), float(level), flags, nearest_ptr,
+                                                  _u64x3(nearest_strides), dist2_ptr, _u64x3(dist2_strides), values_ptr,
+                                                  _u64x3(value_strides), max_dist2), "o2v_hip_nearest_dense")
+
+    def nearest_scratch_bytes(self, dims):
+        """o2v_hip_nearest_scratch_bytes: the context scratch a nearest_dense call over dims (x, y, z) needs."""
+        return int(self._L.o2v_hip_nearest_scratch_bytes(_u32x3(dims)))
+
+    def nearest_times(self):
+        """o2v_hip_nearest_times: the device times (ms) of the last nearest_dense call's x, y and z passes."""
+        return self._stage_times("o2v_hip_nearest_times")
 
     def set_textures(self, textures):
         """textures: sequence of (uint8 [h, w, c] pixels, wrap) with c in (3, 4)."""

@@ -67,6 +67,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -230,6 +231,28 @@ struct Switches {
 };
 Switches read_switches() { return Switches{}; }
 
+// The grid a _count call counted, by which its _write knows its own: the pointer, format, strides, dims and level of the call.
+// The level is compared bit for bit, whatever the format reads of it.
+struct GridKey {
+    const void *p = nullptr;
+    uint32_t format = 0;
+    uint64_t strides[3] = {};
+    uint32_t dims[3] = {};
+    float level = 0.f;
+
+    GridKey() = default;
+    GridKey(const void *p_, uint32_t format_, const uint64_t strides_[3], const uint32_t dims_[3], float level_) : p(p_), format(format_), level(level_)
+    {
+        std::copy(strides_, strides_ + 3, strides);
+        std::copy(dims_, dims_ + 3, dims);
+    }
+    bool operator==(const GridKey &o) const
+    {
+        return p == o.p && format == o.format && std::equal(strides, strides + 3, o.strides) && std::equal(dims, dims + 3, o.dims) &&
+               std::memcmp(&level, &o.level, sizeof(float)) == 0;
+    }
+};
+
 }  // namespace
 
 struct o2v_hip_ctx {
@@ -349,10 +372,7 @@ struct o2v_hip_ctx {
     StageTimes<4> sf_times;
     struct SurfaceCount {
         bool valid = false;
-        const float *field = nullptr;
-        uint64_t strides[3] = {};
-        uint32_t dims[3] = {};
-        float level = 0.f;
+        GridKey key;   // (the field; format 0)
         uint64_t vertices = 0, quads = 0;
     } sf;
     // K11 (o2v_hip_raycast_build / o2v_hip_raycast): the snapshot of the last build - the words of the 4^3 bricks, then of the
@@ -374,42 +394,37 @@ struct o2v_hip_ctx {
     StageTimes<5> cc_times;
     uint64_t cc_counters[2] = {};
 
-    // K13 (o2v_hip_gather_count / _write / _save): the bits of the set, the per-word prefixes, the block offsets (+ the count),
-    // the block of a range's first record and the palette, grown on demand; the grid they were counted for; the two record
-    // buffers and page-locked batches of _save (allocated by its first call); the times of the three stages
+    // K13 (o2v_hip_gather_count / _write / _save): the bits of the set, the per-word prefixes, the block offsets (+ the count)
+    // and the block of a range's first record, grown on demand; the grid they were counted for; the two record buffers and
+    // page-locked batches of _save (allocated by its first call); the times of the three stages
     DevArray<unsigned long long> d_ga_bits, d_ga_boff, d_ga_first;
-    DevArray<uint32_t> d_ga_local, d_ga_palette;
+    DevArray<uint32_t> d_ga_local;
     PinnedArray<unsigned long long> h_ga_ctr;
-    PinnedArray<uint32_t> h_ga_palette;
     DevArray<uint4> d_ga_rec[2];
     PinnedArray<uint32_t> h_ga_rec[2];
     Event ev_ga_rec[2];
     StageTimes<3> ga_times;
     struct GatherCount {
         bool valid = false;
-        const void *grid = nullptr;
-        uint32_t format = 0;
-        uint64_t strides[3] = {};
-        uint32_t dims[3] = {};
-        float level = 0.f;
+        GridKey key;
         uint64_t total = 0;
     } ga;
+    // K13 and K14, O2V_HIP_GATHER_COLOR_PALETTE: the palette of the call that is running (upload_palette), allocated on first use
+    DevArray<uint32_t> d_palette;
+    PinnedArray<uint32_t> h_palette;
 
     // K14 (o2v_hip_faces_count / _write): the bits of the set, the same-colour bits along x and y (GRID / PALETTE with
-    // MERGE_RUNS), the block offsets (+ the count) and the palette, grown on demand; what they were counted for; the times of
-    // the three stages
+    // MERGE_RUNS) and the block offsets (+ the count), grown on demand; what they were counted for; the times of the three
+    // stages
     DevArray<unsigned long long> d_fa_bits, d_fa_same_x, d_fa_same_y, d_fa_boff;
-    DevArray<uint32_t> d_fa_palette;
     PinnedArray<unsigned long long> h_fa_ctr;
-    PinnedArray<uint32_t> h_fa_palette;
     StageTimes<3> fa_times;
     struct FacesCount {
         bool valid = false;
-        const void *grid = nullptr, *colors = nullptr;
-        uint32_t format = 0, merge = 0, color_mode = 0, argb = 0;
-        uint64_t strides[3] = {}, color_strides[3] = {};
-        uint32_t dims[3] = {};
-        float level = 0.f;
+        GridKey key;
+        const void *colors = nullptr;
+        uint32_t merge = 0, color_mode = 0, argb = 0;
+        uint64_t color_strides[3] = {};
         uint32_t palette[256] = {};
         uint64_t total = 0;
     } fa;
@@ -2464,6 +2479,110 @@ uint32_t stream_grid(const o2v_hip_ctx *ctx, uint64_t items, uint32_t per_cu)
     return (uint32_t) std::max<uint64_t>(1, std::min<uint64_t>((uint64_t) ctx->num_cus * per_cu, (items + kBlock - 1) / kBlock));
 }
 
+// A range of device memory that an entry point reads or writes, as refuse_overlap takes it.
+struct Span {
+    const char *what;
+    const void *p;
+    uint64_t bytes;
+};
+
+// Refuses the first pair of spans that overlap, among the pairs with a written span: the first n_out are written, the others
+// only read (and may share memory).  A span with a null pointer or no bytes is not there.
+template <size_t N>
+int refuse_overlap(o2v_hip_ctx *ctx, const char *fn, const Span (&spans)[N], size_t n_out)
+{
+    for (size_t i = 0; i < n_out; ++i)
+        for (size_t j = i + 1; j < N; ++j) {
+            const Span &a = spans[i], &b = spans[j];
+            if (a.p && a.bytes && b.p && b.bytes && ranges_overlap(a.p, a.bytes, b.p, b.bytes))
+                return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, std::string(a.what) + " and " + b.what + " overlap");
+        }
+    return O2V_HIP_OK;
+}
+
+// ---- the set grid: the input of K11 - K15 ----------------------------------------------------------------------------------
+
+// Which voxels of a box are solid (include/o2v_hip.h, o2v_hip_raycast_build), as set_grid checked it.
+struct SetGrid {
+    GridKey key;          // the caller's pointer, format, strides, dims and level
+    uint64_t bytes = 0;   // the reach: the bytes from key.p on that the box touches
+    uint32_t elem = 1;    // bytes per element: 1 (U8) or 4 (a word of BITS, a float of F32_BELOW)
+    bool vec = false;     // 16-byte loads: unit x stride and every row 16-byte aligned
+
+    RaySource source() const { return RaySource{key.p, key.strides[0], key.strides[1], key.strides[2], key.level}; }
+};
+
+static_assert((int) O2V_HIP_RAY_GRID_U8 == (int) O2V_HIP_GRID_U8 && (int) O2V_HIP_RAY_GRID_BITS == (int) O2V_HIP_GRID_BITS &&
+                  (int) O2V_HIP_RAY_GRID_F32_BELOW == (int) O2V_HIP_GRID_F32_BELOW && kRayU8 == O2V_HIP_GRID_U8 && kRayBits == O2V_HIP_GRID_BITS &&
+                  kRayF32Below == O2V_HIP_GRID_F32_BELOW,
+              "one set of format values for the callers of K11 and of K12 - K15 and for the kernels");
+
+// The checks of a set grid that look at the arguments alone, in this order: null argument, zero dims, unknown format, a BITS
+// grid's x stride, a level that is not finite (F32_BELOW).  *g: everything but the reach.
+int set_grid_args(o2v_hip_ctx *ctx, const char *fn, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+                  SetGrid *g)
+{
+    if (!grid || !strides || !dims) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
+    if (!dims[0] || !dims[1] || !dims[2]) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "zero dims");
+    if (format != O2V_HIP_GRID_U8 && format != O2V_HIP_GRID_BITS && format != O2V_HIP_GRID_F32_BELOW)
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown format " + std::to_string(format));
+    if (format == O2V_HIP_GRID_BITS && strides[0] != 1u) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "a BITS grid needs strides[0] == 1");
+    if (format == O2V_HIP_GRID_F32_BELOW && !std::isfinite(level)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "level must be finite");
+    g->key = GridKey(grid, format, strides, dims, level);
+    g->elem = format == O2V_HIP_GRID_U8 ? 1u : 4u;
+    g->vec = strides[0] == 1u && (uintptr_t) grid % 16u == 0 && strides[1] * g->elem % 16u == 0 && strides[2] * g->elem % 16u == 0;
+    return O2V_HIP_OK;
+}
+
+// ... and the one that looks at its memory (check_grid; the context's device is made current for it).  *g: the reach.
+int set_grid_memory(o2v_hip_ctx *ctx, const char *fn, SetGrid *g)
+{
+    O2V_CHECK(hipSetDevice(ctx->device));
+    // (the elements the box reaches: 32-bit words along x for BITS)
+    const uint32_t *const dims = g->key.dims;
+    const uint32_t reach[3] = {g->key.format == O2V_HIP_GRID_BITS ? (dims[0] + 31u) / 32u : dims[0], dims[1], dims[2]};
+    return check_grid(ctx, fn, "grid", g->key.p, reach, g->key.strides, g->elem, false, &g->bytes);
+}
+
+// The set grid of the entry point fn, checked: set_grid_args, then set_grid_memory.  An entry point's own limits and modes come
+// after it (o2v_hip_nearest_dense alone has its size limits between the two).
+int set_grid(o2v_hip_ctx *ctx, const char *fn, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+             SetGrid *g)
+{
+    if (int rc = set_grid_args(ctx, fn, grid, format, strides, dims, level, g)) return rc;
+    return set_grid_memory(ctx, fn, g);
+}
+
+// f(format, vec) with the template arguments <Format, Vec> of the kernels that read a set grid, as integral constants.
+template <typename F>
+void with_set_format(const SetGrid &g, F &&f)
+{
+    using Bits = std::integral_constant<uint32_t, kRayBits>;
+    using U8 = std::integral_constant<uint32_t, kRayU8>;
+    using F32Below = std::integral_constant<uint32_t, kRayF32Below>;
+    if (g.key.format == O2V_HIP_GRID_BITS) return f(Bits{}, std::false_type{});   // (words: no 16-byte variant)
+    if (g.key.format == O2V_HIP_GRID_U8) return g.vec ? f(U8{}, std::true_type{}) : f(U8{}, std::false_type{});
+    return g.vec ? f(F32Below{}, std::true_type{}) : f(F32Below{}, std::false_type{});
+}
+
+// The tail of a count of K13 and K14, whose stage marks 0 and 1 the caller has set: the block sums boff[0, n_blocks) scanned in
+// place, their total into entry n_blocks and from there to the host, which waits for it.  Stage 2 (the write) has not run.
+int count_total(o2v_hip_ctx *ctx, unsigned long long *boff, uint64_t n_blocks, PinnedArray<unsigned long long> &h_ctr, StageTimes<3> &times,
+                uint64_t *total)
+{
+    hipStream_t s = ctx->stream;
+    O2V_LAUNCH("k_fill_scan_blocks", s, k_fill_scan_blocks, dim3(1), dim3(kBlock), 0, s, boff, n_blocks, boff + n_blocks);
+    O2V_CHECK(hipGetLastError());
+    O2V_CHECK(times.mark(2, s));
+    O2V_CHECK(hipMemcpyAsync(h_ctr.ptr, boff + n_blocks, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    O2V_CHECK(hipStreamSynchronize(s));
+    O2V_CHECK(times.elapsed(0, 1, times.ms[0]));
+    O2V_CHECK(times.elapsed(1, 2, times.ms[1]));
+    times.ms[2] = 0.f;
+    *total = h_ctr.ptr[0];
+    return O2V_HIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2694,12 +2813,12 @@ int o2v_hip_nearest_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format, c
 {
     static const char fn[] = "o2v_hip_nearest_dense";
     if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
-    if (!grid || !strides || !dims || !nearest || !nearest_strides || (dist2 && !dist2_strides) || (values && !value_strides))
+    if (!nearest || !nearest_strides || (dist2 && !dist2_strides) || (values && !value_strides))
         return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    if (format != O2V_HIP_GRID_U8 && format != O2V_HIP_GRID_BITS && format != O2V_HIP_GRID_F32_BELOW)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown format " + std::to_string(format));
+    SetGrid sg;
+    int rc;
+    if ((rc = set_grid_args(ctx, fn, grid, format, strides, dims, level, &sg))) return rc;
     if (flags & ~kNearFlagsKnown) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown flag bits in " + std::to_string(flags));
-    if (!dims[0] || !dims[1] || !dims[2]) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "zero dims");
     const unsigned __int128 voxels = (unsigned __int128) dims[0] * dims[1] * dims[2];
     if (voxels > 0x7fffffffull)
         return refuse(ctx, O2V_HIP_ERR_LIMIT, fn,
@@ -2710,26 +2829,15 @@ int o2v_hip_nearest_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format, c
     if (d2max > 0x7ffffffeull)
         return refuse(ctx, O2V_HIP_ERR_LIMIT, fn,
                       "(nx-1)^2 + (ny-1)^2 + (nz-1)^2 = " + std::to_string(d2max) + " does not fit below 2^31 - 1");
-    if (format == O2V_HIP_GRID_BITS && strides[0] != 1u) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "a BITS grid needs strides[0] == 1");
-    if (format == O2V_HIP_GRID_F32_BELOW && !std::isfinite(level)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "level must be finite");
     if (format != O2V_HIP_GRID_U8 && flags)
         return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "SEED_ONE and VALUES_INSIDE need a U8 grid");
-    O2V_CHECK(hipSetDevice(ctx->device));
-    const uint32_t reach[3] = {format == O2V_HIP_GRID_BITS ? (dims[0] + 31u) / 32u : dims[0], dims[1], dims[2]};
-    struct Range {
-        const char *what;
-        const void *p;
-        uint64_t bytes;
-    } r[4] = {{"grid", grid, 0}, {"nearest", nearest, 0}, {"dist2", dist2, 0}, {"values", values, 0}};
-    const uint64_t *const out_strides[4] = {nullptr, nearest_strides, dist2_strides, value_strides};
-    int rc;
-    if ((rc = check_grid(ctx, fn, "grid", grid, reach, strides, format == O2V_HIP_GRID_U8 ? 1u : 4u, false, &r[0].bytes))) return rc;
-    for (int i = 1; i < 4; ++i)
-        if (r[i].p && (rc = check_grid(ctx, fn, r[i].what, r[i].p, dims, out_strides[i], 4u, true, &r[i].bytes))) return rc;
-    for (int i = 0; i < 4; ++i)
-        for (int j = i + 1; j < 4; ++j)
-            if (r[i].p && r[j].p && ranges_overlap(r[i].p, r[i].bytes, r[j].p, r[j].bytes))
-                return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, std::string(r[i].what) + " and " + r[j].what + " overlap");
+    // (the size limits stand before the look at the grid's memory: a box that is too large is refused as that, whatever it reaches)
+    if ((rc = set_grid_memory(ctx, fn, &sg))) return rc;
+    Span spans[4] = {{"nearest", nearest, 0}, {"dist2", dist2, 0}, {"values", values, 0}, {"grid", grid, sg.bytes}};
+    const uint64_t *const out_strides[3] = {nearest_strides, dist2_strides, value_strides};
+    for (int i = 0; i < 3; ++i)
+        if (spans[i].p && (rc = check_grid(ctx, fn, spans[i].what, spans[i].p, dims, out_strides[i], 4u, true, &spans[i].bytes))) return rc;
+    if ((rc = refuse_overlap(ctx, fn, spans, 3))) return rc;
     if ((rc = grow_scratch(ctx, ctx->d_dist_stack, o2v_hip_nearest_scratch_bytes(dims) / sizeof(uint2), fn, "scratch"))) return rc;
     hipStream_t s = ctx->stream;
     const NearGrid g{grid, strides[0], strides[1], strides[2], level, nearest_strides[0], nearest_strides[1], nearest_strides[2],
@@ -2973,10 +3081,7 @@ int o2v_hip_surface_count(o2v_hip_ctx *ctx, const float *field, const uint64_t s
     if (V > kSurfMaxVertices)
         return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, std::to_string(V) + " vertices do not fit an int32 index (at most 2^31 - 1)");
     ctx->sf.valid = true;
-    ctx->sf.field = field;
-    std::copy(strides, strides + 3, ctx->sf.strides);
-    std::copy(dims, dims + 3, ctx->sf.dims);
-    ctx->sf.level = level;
+    ctx->sf.key = GridKey(field, 0u, strides, dims, level);
     ctx->sf.vertices = V;
     ctx->sf.quads = Q;
     *out_vertices = V;
@@ -2998,8 +3103,7 @@ int o2v_hip_surface_write(o2v_hip_ctx *ctx, const float *field, const uint64_t s
         if ((uint64_t) origin[a] + dims[a] > kSurfMaxExtent)
             return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "origin + dims is above 65 536 samples along an axis");
     const o2v_hip_ctx::SurfaceCount &c = ctx->sf;
-    if (!c.valid || c.field != field || !std::equal(strides, strides + 3, c.strides) || !std::equal(dims, dims + 3, c.dims) ||
-        std::memcmp(&c.level, &level, sizeof(float)) != 0)
+    if (!c.valid || !(c.key == GridKey(field, 0u, strides, dims, level)))
         return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "no matching o2v_hip_surface_count (the same field, strides, dims and level)");
     const uint64_t V = c.vertices, T = 2u * c.quads;
     if (vertex_capacity < V || triangle_capacity < T)
@@ -3009,9 +3113,8 @@ int o2v_hip_surface_write(o2v_hip_ctx *ctx, const float *field, const uint64_t s
     if ((V && !positions) || (T && !faces)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
     if ((V && (rc = check_device_range(ctx, fn, positions, V * 12u, "positions"))) || (T && (rc = check_device_range(ctx, fn, faces, T * 12u, "faces"))))
         return rc;
-    if (V && ranges_overlap(positions, V * 12u, field, fbytes)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "positions and field overlap");
-    if (T && ranges_overlap(faces, T * 12u, field, fbytes)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "faces and field overlap");
-    if (T && ranges_overlap(positions, V * 12u, faces, T * 12u)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "positions and faces overlap");
+    const Span spans[] = {{"positions", positions, V * 12u}, {"faces", faces, T * 12u}, {"field", field, fbytes}};
+    if ((rc = refuse_overlap(ctx, fn, spans, 2))) return rc;
     ctx->ktimes_on = false;
     hipStream_t s = ctx->stream;
     O2V_CHECK(ctx->sf_times.mark(2, s));
@@ -3099,19 +3202,12 @@ int o2v_hip_raycast_build(o2v_hip_ctx *ctx, const void *grid, uint32_t format, c
     if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
     ctx->ray.valid = false;
     ++ctx->ray.generation;
-    if (!grid || !strides || !dims || !origin) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    if (!dims[0] || !dims[1] || !dims[2]) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "zero dims");
-    if (format != O2V_HIP_RAY_GRID_U8 && format != O2V_HIP_RAY_GRID_BITS && format != O2V_HIP_RAY_GRID_F32_BELOW)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown format " + std::to_string(format));
-    if (format == O2V_HIP_RAY_GRID_BITS && strides[0] != 1u) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "a BITS grid needs strides[0] == 1");
-    if (format == O2V_HIP_RAY_GRID_F32_BELOW && !std::isfinite(level)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "level must be finite");
+    SetGrid sg;
+    int rc;
+    if ((rc = set_grid(ctx, fn, grid, format, strides, dims, level, &sg))) return rc;
+    if (!origin) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
     for (int a = 0; a < 3; ++a)
         if ((uint64_t) origin[a] + dims[a] > kRayMaxExtent) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "origin + dims is above 65 536 voxels along an axis");
-    O2V_CHECK(hipSetDevice(ctx->device));
-    // (the elements the box reaches: words along x for BITS)
-    const uint32_t reach[3] = {format == O2V_HIP_RAY_GRID_BITS ? (dims[0] + 31u) / 32u : dims[0], dims[1], dims[2]};
-    int rc;
-    if ((rc = check_grid(ctx, fn, "grid", grid, reach, strides, format == O2V_HIP_RAY_GRID_U8 ? 1u : 4u, false))) return rc;
     if ((rc = grow_scratch(ctx, ctx->d_ray_masks, o2v_hip_raycast_scratch_bytes(dims) / 8u, fn, "snapshot"))) return rc;
     ctx->ktimes_on = false;   // (no per-launch brackets here; o2v_hip_voxelize sets the flag again from its params)
     std::copy(dims, dims + 3, ctx->ray.dims);
@@ -3121,25 +3217,15 @@ int o2v_hip_raycast_build(o2v_hip_ctx *ctx, const void *grid, uint32_t format, c
     uint32_t per_axis[3][3];
     ray_levels(dims, words, per_axis);
     unsigned long long *const m0 = ctx->d_ray_masks.ptr, *const m1 = m0 + words[0], *const m2 = m1 + words[1];
-    const RaySource src{grid, strides[0], strides[1], strides[2], level};
-    // 16-byte loads: unit x stride and every row 16-byte aligned
-    const uint64_t elem = format == O2V_HIP_RAY_GRID_U8 ? 1u : 4u;
-    const bool vec = strides[0] == 1u && (uintptr_t) grid % 16u == 0 && strides[1] * elem % 16u == 0 && strides[2] * elem % 16u == 0;
+    const RaySource src = sg.source();
     const uint64_t tiles = (uint64_t) ((dims[0] + 63u) / 64u) * per_axis[0][1] * per_axis[0][2];
     const dim3 blocks(stream_grid(ctx, tiles * 64u, 8u));
     hipStream_t s = ctx->stream;
     O2V_CHECK(ctx->ray_build_times.mark(0, s));
     O2V_CHECK(hipMemsetAsync(m1, 0, words[1] * 8u, s));
-    if (format == O2V_HIP_RAY_GRID_BITS)
-        O2V_LAUNCH("k_ray_build", s, (k_ray_build<kRayBits, false>), blocks, dim3(kBlock), 0, s, src, g, m0, m1);
-    else if (format == O2V_HIP_RAY_GRID_U8 && vec)
-        O2V_LAUNCH("k_ray_build", s, (k_ray_build<kRayU8, true>), blocks, dim3(kBlock), 0, s, src, g, m0, m1);
-    else if (format == O2V_HIP_RAY_GRID_U8)
-        O2V_LAUNCH("k_ray_build", s, (k_ray_build<kRayU8, false>), blocks, dim3(kBlock), 0, s, src, g, m0, m1);
-    else if (vec)
-        O2V_LAUNCH("k_ray_build", s, (k_ray_build<kRayF32Below, true>), blocks, dim3(kBlock), 0, s, src, g, m0, m1);
-    else
-        O2V_LAUNCH("k_ray_build", s, (k_ray_build<kRayF32Below, false>), blocks, dim3(kBlock), 0, s, src, g, m0, m1);
+    with_set_format(sg, [&](auto fmt, auto vec) {
+        O2V_LAUNCH("k_ray_build", s, (k_ray_build<decltype(fmt)::value, decltype(vec)::value>), blocks, dim3(kBlock), 0, s, src, g, m0, m1);
+    });
     O2V_LAUNCH("k_ray_build_top", s, k_ray_build_top, dim3(stream_grid(ctx, words[2], 8u)), dim3(kBlock), 0, s, g, m1, m2);
     O2V_CHECK(hipGetLastError());
     O2V_CHECK(ctx->ray_build_times.mark(1, s));
@@ -3164,11 +3250,8 @@ int o2v_hip_raycast(o2v_hip_ctx *ctx, const float *origins, const float *directi
     if ((rc = check_device_range(ctx, fn, origins, n * 12u, "origins")) || (rc = check_device_range(ctx, fn, directions, n * 12u, "directions")) ||
         (rc = check_device_range(ctx, fn, hit, n * 16u, "hit")) || (rc = check_device_range(ctx, fn, t, n * 4u, "t")))
         return rc;
-    if (ranges_overlap(hit, n * 16u, t, n * 4u)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "hit and t overlap");
-    if (ranges_overlap(hit, n * 16u, origins, n * 12u) || ranges_overlap(hit, n * 16u, directions, n * 12u))
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "hit overlaps the rays");
-    if (ranges_overlap(t, n * 4u, origins, n * 12u) || ranges_overlap(t, n * 4u, directions, n * 12u))
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "t overlaps the rays");
+    const Span spans[] = {{"hit", hit, n * 16u}, {"t", t, n * 4u}, {"origins", origins, n * 12u}, {"directions", directions, n * 12u}};
+    if ((rc = refuse_overlap(ctx, fn, spans, 2))) return rc;
     ctx->ktimes_on = false;
     const RayGrid g = ray_grid(ctx);
     const dim3 blocks((uint32_t) ((n + kBlock - 1) / kBlock));
@@ -3208,41 +3291,50 @@ constexpr uint32_t kCcFlagsKnown = O2V_HIP_CC_INVERT | O2V_HIP_CC_SEED_BORDER | 
 
 uint64_t cc_words(const uint32_t dims[3]) { return (uint64_t) ((dims[0] + 63u) / 64u) * dims[1] * dims[2]; }
 
+// k_cc_classify on the context's stream, for K12, K13 and K14: the set (its complement inside the box if invert) as one bit per
+// voxel, words of 64 voxels along x, [z][y][W].
+void launch_classify(o2v_hip_ctx *ctx, const SetGrid &sg, uint32_t invert, unsigned long long *bits)
+{
+    const uint32_t *const dims = sg.key.dims;
+    CcGrid g{};   // (what the kernel reads of it)
+    g.nx = dims[0], g.ny = dims[1], g.nz = dims[2], g.W = (dims[0] + 63u) / 64u, g.words = cc_words(dims);
+    const RaySource src = sg.source();
+    const dim3 per_group(stream_grid(ctx, (g.words + 15u) / 16u * 64u, 8u));
+    hipStream_t s = ctx->stream;
+    with_set_format(sg, [&](auto format, auto vec) {
+        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<decltype(format)::value, decltype(vec)::value>), per_group, dim3(kBlock), 0, s, src, g, invert, bits);
+    });
+}
+
 // What the two calls share.  labels != null: o2v_hip_components_dense; else o2v_hip_flood_dense.
 int cc_run(o2v_hip_ctx *ctx, const char *fn, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
            uint32_t connectivity, uint32_t flags, int32_t *labels, uint8_t *out, const uint64_t out_strides[3], const int32_t *seeds,
            uint64_t n_seeds, const uint8_t values[3], uint64_t *result)
 {
     const Switches sw = read_switches();
-    if (!grid || !strides || !dims || !out_strides || !result || (!labels && !out) || (out && !values) || (n_seeds && !seeds))
+    if (!out_strides || !result || (!labels && !out) || (out && !values) || (n_seeds && !seeds))
         return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    if (!dims[0] || !dims[1] || !dims[2]) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "zero dims");
-    if (format != O2V_HIP_GRID_U8 && format != O2V_HIP_GRID_BITS && format != O2V_HIP_GRID_F32_BELOW)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown format " + std::to_string(format));
+    SetGrid sg;
+    int rc;
+    if ((rc = set_grid(ctx, fn, grid, format, strides, dims, level, &sg))) return rc;
     if (connectivity != 6u && connectivity != 18u && connectivity != 26u)
         return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "connectivity must be 6, 18 or 26, not " + std::to_string(connectivity));
     if ((flags & ~kCcFlagsKnown) || (labels && (flags & O2V_HIP_CC_SEED_BORDER)))
         return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown flag bits in " + std::to_string(flags));
-    if (format == O2V_HIP_GRID_BITS && strides[0] != 1u) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "a BITS grid needs strides[0] == 1");
-    if (format == O2V_HIP_GRID_F32_BELOW && !std::isfinite(level)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "level must be finite");
     for (int a = 0; a < 3; ++a)
         if (dims[a] > kCcMaxDim) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "a grid of more than 65 536 voxels along an axis");
     const uint64_t voxels = (uint64_t) dims[0] * dims[1] * dims[2];   // (below 2^48)
     if (voxels > kCcMaxVoxels)
         return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, std::to_string(voxels) + " voxels do not fit an int32 index (at most 2^31 - 1)");
     if (n_seeds > kCcMaxVoxels) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "more than 2^31 - 1 seeds");
-    O2V_CHECK(hipSetDevice(ctx->device));
-    const uint32_t reach[3] = {format == O2V_HIP_GRID_BITS ? (dims[0] + 31u) / 32u : dims[0], dims[1], dims[2]};
-    uint64_t gbytes = 0, obytes = 0;
-    int rc;
-    if ((rc = check_grid(ctx, fn, "grid", grid, reach, strides, format == O2V_HIP_GRID_U8 ? 1u : 4u, false, &gbytes)) ||
-        (rc = labels ? check_grid(ctx, fn, "labels", labels, dims, out_strides, 4u, true, &obytes)
+    uint64_t obytes = 0;
+    if ((rc = labels ? check_grid(ctx, fn, "labels", labels, dims, out_strides, 4u, true, &obytes)
                      : check_grid(ctx, fn, "out", out, dims, out_strides, 1u, true, &obytes)) ||
         (n_seeds && (rc = check_device_range(ctx, fn, seeds, n_seeds * 12u, "seeds"))))
         return rc;
-    const void *const dst = labels ? (const void *) labels : (const void *) out;
-    if (ranges_overlap(dst, obytes, grid, gbytes)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, std::string(labels ? "labels" : "out") + " and grid overlap");
-    if (n_seeds && ranges_overlap(dst, obytes, seeds, n_seeds * 12u)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "out and seeds overlap");
+    const Span spans[] = {{labels ? "labels" : "out", labels ? (const void *) labels : (const void *) out, obytes}, {"grid", grid, sg.bytes},
+                          {"seeds", seeds, n_seeds * 12u}};
+    if ((rc = refuse_overlap(ctx, fn, spans, 1))) return rc;
 
     CcGrid g{};
     g.nx = dims[0], g.ny = dims[1], g.nz = dims[2];
@@ -3263,25 +3355,13 @@ int cc_run(o2v_hip_ctx *ctx, const char *fn, const void *grid, uint32_t format, 
     ctx->ktimes_on = false;   // (no per-launch brackets here; o2v_hip_voxelize sets the flag again from its params)
     uint32_t *const P = in_place ? reinterpret_cast<uint32_t *>(labels) : ctx->d_cc_parent.ptr;
     unsigned long long *const bits = ctx->d_cc_bits.ptr, *const fl = ctx->d_cc_flags.ptr, *const ctr = ctx->d_cc_ctr.ptr;
-    const RaySource src{grid, strides[0], strides[1], strides[2], level};
-    const uint64_t elem = format == O2V_HIP_GRID_U8 ? 1u : 4u;
-    const bool vec = strides[0] == 1u && (uintptr_t) grid % 16u == 0 && strides[1] * elem % 16u == 0 && strides[2] * elem % 16u == 0;
     const uint32_t invert = (flags & O2V_HIP_CC_INVERT) ? 1u : 0u;
     const bool count = (flags & O2V_HIP_FLAG_STAGE_TIMES) != 0;
-    const dim3 per_word(stream_grid(ctx, g.words * 64u, 16u)), per_group(stream_grid(ctx, (g.words + 15u) / 16u * 64u, 8u));
+    const dim3 per_word(stream_grid(ctx, g.words * 64u, 16u));
     hipStream_t s = ctx->stream;
     O2V_CHECK(ctx->cc_times.mark(0, s));
     O2V_CHECK(hipMemsetAsync(ctr, 0, 4u * sizeof(unsigned long long), s));
-    if (format == O2V_HIP_GRID_BITS)
-        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayBits, false>), per_group, dim3(kBlock), 0, s, src, g, invert, bits);
-    else if (format == O2V_HIP_GRID_U8 && vec)
-        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayU8, true>), per_group, dim3(kBlock), 0, s, src, g, invert, bits);
-    else if (format == O2V_HIP_GRID_U8)
-        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayU8, false>), per_group, dim3(kBlock), 0, s, src, g, invert, bits);
-    else if (vec)
-        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayF32Below, true>), per_group, dim3(kBlock), 0, s, src, g, invert, bits);
-    else
-        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayF32Below, false>), per_group, dim3(kBlock), 0, s, src, g, invert, bits);
+    launch_classify(ctx, sg, invert, bits);
     O2V_CHECK(ctx->cc_times.mark(1, s));
     if (sw.cc_no_tiles) {
         O2V_LAUNCH("k_cc_init", s, k_cc_init, per_word, dim3(kBlock), 0, s, g, bits, P);
@@ -3384,23 +3464,15 @@ constexpr uint64_t kGaMaxWords = 0x7fffffffull;   // a word index is one uint32 
 constexpr uint64_t kGaMaxGrid = 1ull << 20;       // workgroups of k_gather_count; more blocks are taken in turns
 constexpr uint64_t kGaBatch = 1u << 20;           // records per batch of o2v_hip_gather_save: the batch of drain_to_sink (o2v_api.cpp)
 
-// what the three calls check of the grid; *g: its words, *gbytes: its reach
+// what the three calls check of the grid; *sg: the set grid, *g: its words
 int ga_grid(o2v_hip_ctx *ctx, const char *fn, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
-            GaGrid *g, uint64_t *gbytes)
+            SetGrid *sg, GaGrid *g)
 {
-    if (!grid || !strides || !dims) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    if (!dims[0] || !dims[1] || !dims[2]) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "zero dims");
-    if (format != O2V_HIP_GRID_U8 && format != O2V_HIP_GRID_BITS && format != O2V_HIP_GRID_F32_BELOW)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown format " + std::to_string(format));
-    if (format == O2V_HIP_GRID_BITS && strides[0] != 1u) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "a BITS grid needs strides[0] == 1");
-    if (format == O2V_HIP_GRID_F32_BELOW && !std::isfinite(level)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "level must be finite");
+    if (int rc = set_grid(ctx, fn, grid, format, strides, dims, level, sg)) return rc;
     for (int a = 0; a < 3; ++a)
         if (dims[a] > kGaMaxDim) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "a grid of more than 65 536 voxels along an axis");
     const uint64_t words = cc_words(dims);   // (below 2^43)
     if (words > kGaMaxWords) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, std::to_string(words) + " words of 64 voxels along x (at most 2^31 - 1)");
-    O2V_CHECK(hipSetDevice(ctx->device));
-    const uint32_t reach[3] = {format == O2V_HIP_GRID_BITS ? (dims[0] + 31u) / 32u : dims[0], dims[1], dims[2]};
-    if (int rc = check_grid(ctx, fn, "grid", grid, reach, strides, format == O2V_HIP_GRID_U8 ? 1u : 4u, false, gbytes)) return rc;
     g->nx = dims[0], g->ny = dims[1], g->nz = dims[2];
     g->W = (dims[0] + 63u) / 64u;
     g->words = words;
@@ -3434,77 +3506,43 @@ int ga_color_source(o2v_hip_ctx *ctx, const char *fn, const uint32_t dims[3], ui
     return O2V_HIP_OK;
 }
 
-bool ga_matches(const o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level)
-{
-    const o2v_hip_ctx::GatherCount &c = ctx->ga;
-    return c.valid && c.grid == grid && c.format == format && std::equal(strides, strides + 3, c.strides) && std::equal(dims, dims + 3, c.dims) &&
-           std::memcmp(&c.level, &level, sizeof(float)) == 0;
-}
+bool ga_matches(const o2v_hip_ctx *ctx, const SetGrid &sg) { return ctx->ga.valid && ctx->ga.key == sg.key; }
 
 // classify, count and scan; the count is kept in the context and returned
-int ga_count(o2v_hip_ctx *ctx, const char *fn, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
-             const GaGrid &g, uint64_t *out_count)
+int ga_count(o2v_hip_ctx *ctx, const char *fn, const SetGrid &sg, const GaGrid &g, uint64_t *out_count)
 {
     int rc;
     if ((rc = grow_scratch(ctx, ctx->d_ga_bits, g.words, fn, "set bits")) || (rc = grow_scratch(ctx, ctx->d_ga_local, g.words, fn, "prefixes")) ||
         (rc = grow_scratch(ctx, ctx->d_ga_boff, g.n_blocks + 1u, fn, "block offsets")) || (rc = grow_scratch(ctx, ctx->d_ga_first, 1u, fn, "range")) ||
-        (rc = grow_scratch(ctx, ctx->d_ga_palette, 256u, fn, "palette")) || (rc = grow_scratch(ctx, ctx->h_ga_palette, 256u, fn, "palette")) ||
         (rc = grow_scratch(ctx, ctx->h_ga_ctr, 1u, fn, "counters")))
         return rc;
     ctx->ktimes_on = false;   // (no per-launch brackets here; o2v_hip_voxelize sets the flag again from its params)
-    CcGrid cg{};
-    cg.nx = g.nx, cg.ny = g.ny, cg.nz = g.nz, cg.W = g.W, cg.words = g.words;
     unsigned long long *const bits = ctx->d_ga_bits.ptr, *const boff = ctx->d_ga_boff.ptr;
-    const RaySource src{grid, strides[0], strides[1], strides[2], level};
-    const uint64_t elem = format == O2V_HIP_GRID_U8 ? 1u : 4u;
-    const bool vec = strides[0] == 1u && (uintptr_t) grid % 16u == 0 && strides[1] * elem % 16u == 0 && strides[2] * elem % 16u == 0;
-    const dim3 per_group(stream_grid(ctx, (g.words + 15u) / 16u * 64u, 8u));
     hipStream_t s = ctx->stream;
     O2V_CHECK(ctx->ga_times.mark(0, s));
-    if (format == O2V_HIP_GRID_BITS)
-        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayBits, false>), per_group, dim3(kBlock), 0, s, src, cg, 0u, bits);
-    else if (format == O2V_HIP_GRID_U8 && vec)
-        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayU8, true>), per_group, dim3(kBlock), 0, s, src, cg, 0u, bits);
-    else if (format == O2V_HIP_GRID_U8)
-        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayU8, false>), per_group, dim3(kBlock), 0, s, src, cg, 0u, bits);
-    else if (vec)
-        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayF32Below, true>), per_group, dim3(kBlock), 0, s, src, cg, 0u, bits);
-    else
-        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayF32Below, false>), per_group, dim3(kBlock), 0, s, src, cg, 0u, bits);
+    launch_classify(ctx, sg, 0u, bits);
     O2V_CHECK(ctx->ga_times.mark(1, s));
     O2V_LAUNCH("k_gather_count", s, k_gather_count, dim3((uint32_t) std::min<uint64_t>(g.n_blocks, kGaMaxGrid)), dim3(kBlock), 0, s, bits, g,
                ctx->d_ga_local.ptr, boff);
-    // (the count goes behind the offsets: entry n_blocks)
-    O2V_LAUNCH("k_fill_scan_blocks", s, k_fill_scan_blocks, dim3(1), dim3(kBlock), 0, s, boff, g.n_blocks, boff + g.n_blocks);
-    O2V_CHECK(hipGetLastError());
-    O2V_CHECK(ctx->ga_times.mark(2, s));
-    O2V_CHECK(hipMemcpyAsync(ctx->h_ga_ctr.ptr, boff + g.n_blocks, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    O2V_CHECK(hipStreamSynchronize(s));
-    O2V_CHECK(ctx->ga_times.elapsed(0, 1, ctx->ga_times.ms[0]));
-    O2V_CHECK(ctx->ga_times.elapsed(1, 2, ctx->ga_times.ms[1]));
-    ctx->ga_times.ms[2] = 0.f;
+    uint64_t total = 0;
+    if ((rc = count_total(ctx, boff, g.n_blocks, ctx->h_ga_ctr, ctx->ga_times, &total))) return rc;
 #ifdef O2V_GA_MUTATE_COUNT32
-    const uint64_t total = (uint32_t) ctx->h_ga_ctr.ptr[0];   // (test only: the count truncated where the host reads it)
-#else
-    const uint64_t total = ctx->h_ga_ctr.ptr[0];
+    total = (uint32_t) total;   // (test only: the count truncated where the host reads it)
 #endif
-    o2v_hip_ctx::GatherCount &c = ctx->ga;
-    c.valid = true;
-    c.grid = grid;
-    c.format = format;
-    std::copy(strides, strides + 3, c.strides);
-    std::copy(dims, dims + 3, c.dims);
-    c.level = level;
-    c.total = total;
+    ctx->ga.valid = true;
+    ctx->ga.key = sg.key;
+    ctx->ga.total = total;
     *out_count = total;
     return O2V_HIP_OK;
 }
 
-// the palette into the context's device copy (on the stream)
-int ga_upload_palette(o2v_hip_ctx *ctx, const uint32_t *palette)
+// The 256 colours of a PALETTE call into the context's device copy, on the stream.  K13 and K14 share the copy: every call that
+// reads it uploads its own palette ahead of its launches and has waited for the stream when it returns.
+int upload_palette(o2v_hip_ctx *ctx, const char *fn, const uint32_t *palette)
 {
-    std::memcpy(ctx->h_ga_palette.ptr, palette, 256u * sizeof(uint32_t));
-    O2V_CHECK(hipMemcpyAsync(ctx->d_ga_palette.ptr, ctx->h_ga_palette.ptr, 256u * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc; (rc = grow_scratch(ctx, ctx->d_palette, 256u, fn, "palette")) || (rc = grow_scratch(ctx, ctx->h_palette, 256u, fn, "palette"))) return rc;
+    std::memcpy(ctx->h_palette.ptr, palette, 256u * sizeof(uint32_t));
+    O2V_CHECK(hipMemcpyAsync(ctx->d_palette.ptr, ctx->h_palette.ptr, 256u * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     return O2V_HIP_OK;
 }
 
@@ -3533,18 +3571,20 @@ int ga_launch_write(o2v_hip_ctx *ctx, const GaGrid &g, uint64_t first, uint64_t 
     return O2V_HIP_OK;
 }
 
-GaColor ga_color(const o2v_hip_ctx *ctx, const void *grid, const uint64_t strides[3], uint32_t color_mode, uint32_t argb, const uint32_t *colors,
-                 const uint64_t color_strides[3])
+// *col: what the colour mode reads, as the kernels of K13 and K14 take it; PALETTE: uploaded first
+int ga_color(o2v_hip_ctx *ctx, const char *fn, const SetGrid &sg, uint32_t color_mode, uint32_t argb, const uint32_t *colors,
+             const uint64_t color_strides[3], const uint32_t *palette, GaColor *col)
 {
-    GaColor col{};
-    col.argb = argb;
-    if (color_mode == O2V_HIP_GATHER_COLOR_GRID) col.colors = colors, col.c0 = color_strides[0], col.c1 = color_strides[1], col.c2 = color_strides[2];
+    *col = GaColor{};
+    col->argb = argb;
+    if (color_mode == O2V_HIP_GATHER_COLOR_GRID) col->colors = colors, col->c0 = color_strides[0], col->c1 = color_strides[1], col->c2 = color_strides[2];
     if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE) {
-        col.grid = static_cast<const uint8_t *>(grid);
-        col.s0 = strides[0], col.s1 = strides[1], col.s2 = strides[2];
-        col.palette = ctx->d_ga_palette.ptr;
+        if (int rc = upload_palette(ctx, fn, palette)) return rc;
+        col->grid = static_cast<const uint8_t *>(sg.key.p);
+        col->s0 = sg.key.strides[0], col->s1 = sg.key.strides[1], col->s2 = sg.key.strides[2];
+        col->palette = ctx->d_palette.ptr;
     }
-    return col;
+    return O2V_HIP_OK;
 }
 
 bool ga_output_format(FileFormat f)
@@ -3570,10 +3610,10 @@ int o2v_hip_gather_count(o2v_hip_ctx *ctx, const void *grid, uint32_t format, co
     if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
     ctx->ga.valid = false;
     if (!out_count) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
+    SetGrid sg;
     GaGrid g{};
-    uint64_t gbytes = 0;
-    if (int rc = ga_grid(ctx, fn, grid, format, strides, dims, level, &g, &gbytes)) return rc;
-    return ga_count(ctx, fn, grid, format, strides, dims, level, g, out_count);
+    if (int rc = ga_grid(ctx, fn, grid, format, strides, dims, level, &sg, &g)) return rc;
+    return ga_count(ctx, fn, sg, g, out_count);
 }
 
 int o2v_hip_gather_write(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
@@ -3582,11 +3622,12 @@ int o2v_hip_gather_write(o2v_hip_ctx *ctx, const void *grid, uint32_t format, co
 {
     static const char fn[] = "o2v_hip_gather_write";
     if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
+    SetGrid sg;
     GaGrid g{};
-    uint64_t gbytes = 0, cbytes = 0;
+    uint64_t cbytes = 0;
     int rc;
-    if ((rc = ga_grid(ctx, fn, grid, format, strides, dims, level, &g, &gbytes)) || (rc = ga_mode(ctx, fn, format, dims, origin, color_mode))) return rc;
-    if (!ga_matches(ctx, grid, format, strides, dims, level))
+    if ((rc = ga_grid(ctx, fn, grid, format, strides, dims, level, &sg, &g)) || (rc = ga_mode(ctx, fn, format, dims, origin, color_mode))) return rc;
+    if (!ga_matches(ctx, sg))
         return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "no matching o2v_hip_gather_count (the same grid, format, strides, dims and level)");
     const uint64_t total = ctx->ga.total;
     if (first > total || n > total - first)
@@ -3598,11 +3639,12 @@ int o2v_hip_gather_write(o2v_hip_ctx *ctx, const void *grid, uint32_t format, co
     if (n > (~0ull >> 4)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "records: n * 16 bytes reach past any allocation");
     if ((uintptr_t) records % 16u) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "records must be 16-byte aligned");
     if ((rc = check_device_range(ctx, fn, records, n * 16u, "records"))) return rc;
-    if (ranges_overlap(records, n * 16u, grid, gbytes)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "records and grid overlap");
-    if (cbytes && ranges_overlap(records, n * 16u, colors, cbytes)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "records and colors overlap");
+    const Span spans[] = {{"records", records, n * 16u}, {"grid", grid, sg.bytes}, {"colors", colors, cbytes}};
+    if ((rc = refuse_overlap(ctx, fn, spans, 1))) return rc;
     ctx->ktimes_on = false;
-    if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE && (rc = ga_upload_palette(ctx, palette))) return rc;
-    if ((rc = ga_launch_write(ctx, g, first, n, origin, color_mode, ga_color(ctx, grid, strides, color_mode, argb, colors, color_strides), records)))
+    GaColor col;
+    if ((rc = ga_color(ctx, fn, sg, color_mode, argb, colors, color_strides, palette, &col)) ||
+        (rc = ga_launch_write(ctx, g, first, n, origin, color_mode, col, records)))
         return rc;
     O2V_CHECK(hipStreamSynchronize(ctx->stream));
     O2V_CHECK(ctx->ga_times.elapsed(2, 3, ctx->ga_times.ms[2]));
@@ -3617,10 +3659,11 @@ int o2v_hip_gather_save(o2v_hip_ctx *ctx, const void *grid, uint32_t format, con
     if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
     ctx->ga.valid = false;
     if (!path || !out_count) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
+    SetGrid sg;
     GaGrid g{};
-    uint64_t gbytes = 0, cbytes = 0;
+    uint64_t cbytes = 0;
     int rc;
-    if ((rc = ga_grid(ctx, fn, grid, format, strides, dims, level, &g, &gbytes)) || (rc = ga_mode(ctx, fn, format, dims, origin, color_mode)) ||
+    if ((rc = ga_grid(ctx, fn, grid, format, strides, dims, level, &sg, &g)) || (rc = ga_mode(ctx, fn, format, dims, origin, color_mode)) ||
         (rc = ga_color_source(ctx, fn, dims, color_mode, colors, color_strides, palette, &cbytes)))
         return rc;
     for (int a = 0; a < 3; ++a)
@@ -3630,7 +3673,7 @@ int o2v_hip_gather_save(o2v_hip_ctx *ctx, const void *grid, uint32_t format, con
     if (!ga_output_format(file_format))
         return refuse(ctx, O2V_HIP_ERR_IO, fn, std::string("\"") + (type ? type : path) + "\" is not an output format (VL32, PLY, XYZRGB, QEF, VOX)");
     uint64_t total = 0;
-    if ((rc = ga_count(ctx, fn, grid, format, strides, dims, level, g, &total))) return rc;
+    if ((rc = ga_count(ctx, fn, sg, g, &total))) return rc;
     for (int k = 0; k < 2; ++k) {
         if ((rc = grow_scratch(ctx, ctx->d_ga_rec[k], kGaBatch, fn, "record buffer")) || (rc = grow_scratch(ctx, ctx->h_ga_rec[k], kGaBatch * 4u, fn, "staging")))
             return rc;
@@ -3639,8 +3682,8 @@ int o2v_hip_gather_save(o2v_hip_ctx *ctx, const void *grid, uint32_t format, con
     std::unique_ptr<VoxelSink> sink = open_file_sink(path, file_format, resolution);
     if (!sink) return refuse(ctx, O2V_HIP_ERR_IO, fn, std::string("cannot open \"") + path + "\" for writing");
     sink->expect(total);
-    const GaColor col = ga_color(ctx, grid, strides, color_mode, argb, colors, color_strides);
-    if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE && (rc = ga_upload_palette(ctx, palette))) return rc;
+    GaColor col;
+    if ((rc = ga_color(ctx, fn, sg, color_mode, argb, colors, color_strides, palette, &col))) return rc;
     hipStream_t s = ctx->stream;
     const uint64_t batches = (total + kGaBatch - 1) / kGaBatch;
     // Two record buffers and two page-locked batches: while the sink consumes one batch the next is written and copied.
@@ -3687,15 +3730,15 @@ constexpr uint64_t kFaMaxQuads = 0x7fffffffull / 4u;   // 4 Q <= 2^31 - 1: a ver
 constexpr uint64_t kFaMaxGrid = 1ull << 20;       // workgroups of k_faces_count; more blocks are taken in turns
 
 // what both calls check: the grid as the gather checks it, the merge and colour modes and the pointers the colour mode reads;
-// *g: the words and items, *gbytes / *cbytes: the reach of the grid and of colors (GRID)
+// *sg: the set grid, *g: the words and items, *cbytes: the reach of colors (GRID)
 int fa_args(o2v_hip_ctx *ctx, const char *fn, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
-            uint32_t merge, uint32_t color_mode, const uint32_t *colors, const uint64_t color_strides[3], const uint32_t *palette, FaGrid *g,
-            uint64_t *gbytes, uint64_t *cbytes)
+            uint32_t merge, uint32_t color_mode, const uint32_t *colors, const uint64_t color_strides[3], const uint32_t *palette, SetGrid *sg,
+            FaGrid *g, uint64_t *cbytes)
 {
     GaGrid gg{};
     static const uint32_t no_origin[3] = {0, 0, 0};
     int rc;
-    if ((rc = ga_grid(ctx, fn, grid, format, strides, dims, level, &gg, gbytes))) return rc;
+    if ((rc = ga_grid(ctx, fn, grid, format, strides, dims, level, sg, &gg))) return rc;
     if (merge != O2V_HIP_FACES_MERGE_NONE && merge != O2V_HIP_FACES_MERGE_RUNS)
         return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown merge " + std::to_string(merge));
     if ((rc = ga_mode(ctx, fn, format, dims, no_origin, color_mode)) ||
@@ -3710,34 +3753,17 @@ int fa_args(o2v_hip_ctx *ctx, const char *fn, const void *grid, uint32_t format,
     return O2V_HIP_OK;
 }
 
-bool fa_matches(const o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
-                uint32_t merge, uint32_t color_mode, uint32_t argb, const uint32_t *colors, const uint64_t color_strides[3], const uint32_t *palette)
+bool fa_matches(const o2v_hip_ctx *ctx, const SetGrid &sg, uint32_t merge, uint32_t color_mode, uint32_t argb, const uint32_t *colors,
+                const uint64_t color_strides[3], const uint32_t *palette)
 {
     const o2v_hip_ctx::FacesCount &c = ctx->fa;
-    if (!c.valid || c.grid != grid || c.format != format || !std::equal(strides, strides + 3, c.strides) || !std::equal(dims, dims + 3, c.dims) ||
-        std::memcmp(&c.level, &level, sizeof(float)) != 0 || c.merge != merge || c.color_mode != color_mode)
-        return false;
+    if (!c.valid || !(c.key == sg.key) || c.merge != merge || c.color_mode != color_mode) return false;
     if (color_mode == O2V_HIP_GATHER_COLOR_GRID) return c.colors == colors && std::equal(color_strides, color_strides + 3, c.color_strides);
     if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE) return std::equal(palette, palette + 256, c.palette);
     return c.argb == argb;
 }
 
 FaBits fa_bits(const o2v_hip_ctx *ctx) { return FaBits{ctx->d_fa_bits.ptr, ctx->d_fa_same_x.ptr, ctx->d_fa_same_y.ptr}; }
-
-GaColor fa_color_source(const o2v_hip_ctx *ctx, const void *grid, const uint64_t strides[3], uint32_t color_mode, uint32_t argb,
-                        const uint32_t *colors, const uint64_t color_strides[3])
-{
-    GaColor col = ga_color(ctx, grid, strides, color_mode, argb, colors, color_strides);
-    if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE) col.palette = ctx->d_fa_palette.ptr;
-    return col;
-}
-
-int fa_upload_palette(o2v_hip_ctx *ctx, const uint32_t *palette)
-{
-    std::memcpy(ctx->h_fa_palette.ptr, palette, 256u * sizeof(uint32_t));
-    O2V_CHECK(hipMemcpyAsync(ctx->d_fa_palette.ptr, ctx->h_fa_palette.ptr, 256u * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    return O2V_HIP_OK;
-}
 
 }  // namespace
 
@@ -3758,43 +3784,27 @@ int o2v_hip_faces_count(o2v_hip_ctx *ctx, const void *grid, uint32_t format, con
     if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
     ctx->fa.valid = false;
     if (!out_quads) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
+    SetGrid sg;
     FaGrid g{};
-    uint64_t gbytes = 0, cbytes = 0;
+    uint64_t cbytes = 0;
     int rc;
-    if ((rc = fa_args(ctx, fn, grid, format, strides, dims, level, merge, color_mode, colors, color_strides, palette, &g, &gbytes, &cbytes))) return rc;
+    if ((rc = fa_args(ctx, fn, grid, format, strides, dims, level, merge, color_mode, colors, color_strides, palette, &sg, &g, &cbytes))) return rc;
     if ((rc = grow_scratch(ctx, ctx->d_fa_bits, g.words, fn, "set bits")) ||
         (g.colored && ((rc = grow_scratch(ctx, ctx->d_fa_same_x, g.words, fn, "same-colour bits")) ||
                        (rc = grow_scratch(ctx, ctx->d_fa_same_y, g.words, fn, "same-colour bits")))) ||
-        (rc = grow_scratch(ctx, ctx->d_fa_boff, g.n_blocks + 1u, fn, "block offsets")) ||
-        (rc = grow_scratch(ctx, ctx->d_fa_palette, 256u, fn, "palette")) || (rc = grow_scratch(ctx, ctx->h_fa_palette, 256u, fn, "palette")) ||
-        (rc = grow_scratch(ctx, ctx->h_fa_ctr, 1u, fn, "counters")))
+        (rc = grow_scratch(ctx, ctx->d_fa_boff, g.n_blocks + 1u, fn, "block offsets")) || (rc = grow_scratch(ctx, ctx->h_fa_ctr, 1u, fn, "counters")))
         return rc;
     ctx->ktimes_on = false;   // (no per-launch brackets here; o2v_hip_voxelize sets the flag again from its params)
-    CcGrid cg{};
-    cg.nx = g.nx, cg.ny = g.ny, cg.nz = g.nz, cg.W = g.W, cg.words = g.words;
     unsigned long long *const bits = ctx->d_fa_bits.ptr, *const boff = ctx->d_fa_boff.ptr;
-    const RaySource src{grid, strides[0], strides[1], strides[2], level};
-    const uint64_t elem = format == O2V_HIP_GRID_U8 ? 1u : 4u;
-    const bool vec = strides[0] == 1u && (uintptr_t) grid % 16u == 0 && strides[1] * elem % 16u == 0 && strides[2] * elem % 16u == 0;
-    const dim3 per_group(stream_grid(ctx, (g.words + 15u) / 16u * 64u, 8u));
     hipStream_t s = ctx->stream;
     O2V_CHECK(ctx->fa_times.mark(0, s));
-    if (format == O2V_HIP_GRID_BITS)
-        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayBits, false>), per_group, dim3(kBlock), 0, s, src, cg, 0u, bits);
-    else if (format == O2V_HIP_GRID_U8 && vec)
-        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayU8, true>), per_group, dim3(kBlock), 0, s, src, cg, 0u, bits);
-    else if (format == O2V_HIP_GRID_U8)
-        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayU8, false>), per_group, dim3(kBlock), 0, s, src, cg, 0u, bits);
-    else if (vec)
-        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayF32Below, true>), per_group, dim3(kBlock), 0, s, src, cg, 0u, bits);
-    else
-        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<kRayF32Below, false>), per_group, dim3(kBlock), 0, s, src, cg, 0u, bits);
+    launch_classify(ctx, sg, 0u, bits);
     if (g.colored) {
         // a wavefront per word in turns
         const dim3 per_word(stream_grid(ctx, g.words * 64u, 8u));
-        const GaColor col = fa_color_source(ctx, grid, strides, color_mode, argb, colors, color_strides);
+        GaColor col;
+        if ((rc = ga_color(ctx, fn, sg, color_mode, argb, colors, color_strides, palette, &col))) return rc;
         if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE) {
-            if ((rc = fa_upload_palette(ctx, palette))) return rc;
             O2V_LAUNCH("k_faces_same", s, k_faces_same<kGaColorPalette>, per_word, dim3(kBlock), 0, s, g, bits, col, ctx->d_fa_same_x.ptr,
                        ctx->d_fa_same_y.ptr);
         } else {
@@ -3804,27 +3814,14 @@ int o2v_hip_faces_count(o2v_hip_ctx *ctx, const void *grid, uint32_t format, con
     }
     O2V_CHECK(ctx->fa_times.mark(1, s));
     O2V_LAUNCH("k_faces_count", s, k_faces_count, dim3((uint32_t) std::min<uint64_t>(g.n_blocks, kFaMaxGrid)), dim3(kBlock), 0, s, g, fa_bits(ctx), boff);
-    // (the count goes behind the offsets: entry n_blocks)
-    O2V_LAUNCH("k_fill_scan_blocks", s, k_fill_scan_blocks, dim3(1), dim3(kBlock), 0, s, boff, g.n_blocks, boff + g.n_blocks);
-    O2V_CHECK(hipGetLastError());
-    O2V_CHECK(ctx->fa_times.mark(2, s));
-    O2V_CHECK(hipMemcpyAsync(ctx->h_fa_ctr.ptr, boff + g.n_blocks, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    O2V_CHECK(hipStreamSynchronize(s));
-    O2V_CHECK(ctx->fa_times.elapsed(0, 1, ctx->fa_times.ms[0]));
-    O2V_CHECK(ctx->fa_times.elapsed(1, 2, ctx->fa_times.ms[1]));
-    ctx->fa_times.ms[2] = 0.f;
+    uint64_t total = 0;
+    if ((rc = count_total(ctx, boff, g.n_blocks, ctx->h_fa_ctr, ctx->fa_times, &total))) return rc;
 #ifdef O2V_FA_MUTATE_COUNT32
-    const uint64_t total = (uint32_t) ctx->h_fa_ctr.ptr[0];   // (test only: the count truncated where the host reads it)
-#else
-    const uint64_t total = ctx->h_fa_ctr.ptr[0];
+    total = (uint32_t) total;   // (test only: the count truncated where the host reads it)
 #endif
     o2v_hip_ctx::FacesCount &c = ctx->fa;
     c.valid = true;
-    c.grid = grid;
-    c.format = format;
-    std::copy(strides, strides + 3, c.strides);
-    std::copy(dims, dims + 3, c.dims);
-    c.level = level;
+    c.key = sg.key;
     c.merge = merge;
     c.color_mode = color_mode;
     c.argb = argb;
@@ -3843,15 +3840,16 @@ int o2v_hip_faces_write(o2v_hip_ctx *ctx, const void *grid, uint32_t format, con
 {
     static const char fn[] = "o2v_hip_faces_write";
     if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
+    SetGrid sg;
     FaGrid g{};
-    uint64_t gbytes = 0, cbytes = 0;
+    uint64_t cbytes = 0;
     int rc;
-    if ((rc = fa_args(ctx, fn, grid, format, strides, dims, level, merge, color_mode, colors, color_strides, palette, &g, &gbytes, &cbytes))) return rc;
+    if ((rc = fa_args(ctx, fn, grid, format, strides, dims, level, merge, color_mode, colors, color_strides, palette, &sg, &g, &cbytes))) return rc;
     if (!origin) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
     for (int a = 0; a < 3; ++a)
         if ((uint64_t) origin[a] + dims[a] > kFaMaxExtent)
             return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "origin + dims is above 65 536 along an axis: a coordinate would not be exact in float32");
-    if (!fa_matches(ctx, grid, format, strides, dims, level, merge, color_mode, argb, colors, color_strides, palette))
+    if (!fa_matches(ctx, sg, merge, color_mode, argb, colors, color_strides, palette))
         return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn,
                       "no matching o2v_hip_faces_count (the same grid, format, strides, dims, level, merge and colour arguments)");
     const uint64_t total = ctx->fa.total;
@@ -3864,25 +3862,14 @@ int o2v_hip_faces_write(o2v_hip_ctx *ctx, const void *grid, uint32_t format, con
     if (!positions) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
     if ((uintptr_t) positions % 16u || (uintptr_t) faces % 8u || (uintptr_t) quad_argb % 4u)
         return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "positions must be 16-byte, faces 8-byte and quad_argb 4-byte aligned");
-    struct Out {
-        const void *p;
-        uint64_t bytes;
-        const char *what;
-    } outs[3] = {{positions, total * 48u, "positions"}, {faces, total * 24u, "faces"}, {quad_argb, total * 4u, "quad_argb"}};
-    for (int i = 0; i < 3; ++i) {
-        if (!outs[i].p) continue;
-        if ((rc = check_device_range(ctx, fn, outs[i].p, outs[i].bytes, outs[i].what))) return rc;
-        if (ranges_overlap(outs[i].p, outs[i].bytes, grid, gbytes))
-            return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, std::string(outs[i].what) + " and grid overlap");
-        if (cbytes && ranges_overlap(outs[i].p, outs[i].bytes, colors, cbytes))
-            return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, std::string(outs[i].what) + " and colors overlap");
-        for (int j = 0; j < i; ++j)
-            if (outs[j].p && ranges_overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes))
-                return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, std::string(outs[j].what) + " and " + outs[i].what + " overlap");
-    }
+    const Span spans[] = {{"positions", positions, total * 48u}, {"faces", faces, total * 24u}, {"quad_argb", quad_argb, total * 4u},
+                          {"grid", grid, sg.bytes}, {"colors", colors, cbytes}};
+    for (int i = 0; i < 3; ++i)
+        if (spans[i].p && (rc = check_device_range(ctx, fn, spans[i].p, spans[i].bytes, spans[i].what))) return rc;
+    if ((rc = refuse_overlap(ctx, fn, spans, 3))) return rc;
     ctx->ktimes_on = false;
-    if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE && (rc = fa_upload_palette(ctx, palette))) return rc;
-    const GaColor col = fa_color_source(ctx, grid, strides, color_mode, argb, colors, color_strides);
+    GaColor col;
+    if ((rc = ga_color(ctx, fn, sg, color_mode, argb, colors, color_strides, palette, &col))) return rc;
     hipStream_t s = ctx->stream;
     // a workgroup per block of items in turns, and no more than fill the device
     const dim3 blocks((uint32_t) std::min<uint64_t>(g.n_blocks, (uint64_t) ctx->num_cus * 8u));

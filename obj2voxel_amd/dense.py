@@ -358,9 +358,7 @@ def extract_surface(dv, field, level=0.0, *, origin=(0, 0, 0), transform=None, s
     _check_grid(field, "field", torch.float32, device)
     if 0 in field.shape:
         raise ValueError("field has an empty dimension")
-    origin = tuple(int(v) for v in origin)
-    if len(origin) != 3 or any(v < 0 for v in origin):
-        raise ValueError(f"origin {origin} must be three voxel coordinates, none negative")
+    origin = _origin(origin)
     if any(o + n > MAX_SURFACE_EXTENT for o, n in zip(origin, field.shape[::-1])):
         raise ValueError(f"origin {origin} + field's extent {tuple(field.shape[::-1])} [x, y, z] is above {MAX_SURFACE_EXTENT}")
     if transform is not None:
@@ -380,6 +378,14 @@ def extract_surface(dv, field, level=0.0, *, origin=(0, 0, 0), transform=None, s
         p = positions.to(torch.float64) * supersampling - transform[9:].to(device)
         positions = (p[:, None, :] * inverse[None, :, :]).sum(dim=2).to(torch.float32).contiguous()
     return positions, faces
+
+
+def _origin(origin):
+    """The origin of a box as three ints, none negative."""
+    origin = tuple(int(v) for v in origin)
+    if len(origin) != 3 or any(v < 0 for v in origin):
+        raise ValueError(f"origin {origin} must be three voxel coordinates, none negative")
+    return origin
 
 
 def _grid_format(grid, level):
@@ -420,28 +426,14 @@ class RayCaster:
     RayCaster on the same `dv` replaces it, and casting with the earlier one raises RuntimeError."""
 
     def __init__(self, dv, grid, *, level=None, origin=(0, 0, 0)):
-        _require_shared_runtime()
-        device = _device(dv)
-        if not isinstance(grid, torch.Tensor) or grid.dim() != 3:
-            raise ValueError("grid must be a 3-D tensor [z, y, x]")
-        fmt, level = _grid_format(grid, level)
-        if grid.device != device:
-            raise ValueError(f"grid is on {grid.device}, the voxelizer on {device}")
-        if 0 in grid.shape:
-            raise ValueError("grid has an empty dimension")
-        if fmt == hip.RAY_GRID_BITS and grid.stride(2) != 1:
-            raise ValueError("a bits grid needs unit stride along x (its last dimension)")
-        origin = tuple(int(v) for v in origin)
-        if len(origin) != 3 or any(v < 0 for v in origin):
-            raise ValueError(f"origin {origin} must be three voxel coordinates, none negative")
-        nz, ny, nx = grid.shape
-        if fmt == hip.RAY_GRID_BITS:
-            nx *= 32
-        if any(o + n > MAX_RAY_EXTENT for o, n in zip(origin, (nx, ny, nz))):
-            raise ValueError(f"origin {origin} + the grid's extent {(nx, ny, nz)} [x, y, z] is above {MAX_RAY_EXTENT}")
-        self.dv, self.device, self.origin, self.dims = dv, device, origin, (nx, ny, nz)
+        def limit(dims):
+            if any(o + n > MAX_RAY_EXTENT for o, n in zip(origin, dims)):
+                raise ValueError(f"origin {origin} + the grid's extent {dims} [x, y, z] is above {MAX_RAY_EXTENT}")
+        origin = _origin(origin)
+        device, fmt, level, dims = _set_grid(dv, grid, level, limit)
+        self.dv, self.device, self.origin, self.dims = dv, device, origin, dims
         _sync(device)   # (the caller's writes to grid have landed)
-        self._generation = dv.raycast_build(grid.data_ptr(), fmt, _strides(grid), (nx, ny, nz), 0.0 if level is None else level, origin)
+        self._generation = dv.raycast_build(grid.data_ptr(), fmt, _strides(grid), dims, 0.0 if level is None else level, origin)
 
     def cast(self, origins, directions, t_max=float("inf")):
         """(hit, t) of the rays origins + t * directions, float32 tensors [..., 3] of one shape on the device, in voxel space;
@@ -507,9 +499,22 @@ def camera_rays(width, height, eye, target, up, fov_y_degrees, device):
 
 # ---- connected components and flood fill --------------------------------------------------------------
 
-def _cc_grid(dv, grid, level, connectivity):
-    """(device, format, level, (nx, ny, nz)) of a grid of components / flood, checked as RayCaster checks its own.  connectivity
-    None: a grid of to_voxels / count_voxels / save_voxels, which have no connectivity and another size limit."""
+def _limit_voxels(dims):
+    """The size limit of components / flood / nearest_voxel: a linear index and a label are one int32."""
+    if max(dims) > MAX_CC_DIM or dims[0] * dims[1] * dims[2] > MAX_CC_VOXELS:
+        raise ValueError(f"the grid's extent {dims} [x, y, z] is above {MAX_CC_DIM} along an axis or {MAX_CC_VOXELS} voxels in all")
+
+
+def _limit_words(dims):
+    """The size limit of to_voxels / count_voxels / save_voxels and voxel_faces: no linear index, words of 64 voxels."""
+    if max(dims) > MAX_CC_DIM or -(-dims[0] // 64) * dims[1] * dims[2] > MAX_GATHER_WORDS:
+        raise ValueError(f"the grid's extent {dims} [x, y, z] is above {MAX_CC_DIM} along an axis or {MAX_GATHER_WORDS} "
+                         "words of 64 voxels along x in all")
+
+
+def _set_grid(dv, grid, level, limit, connectivity=None):
+    """(device, format, level, (nx, ny, nz)) of a set grid - the grid of RayCaster, components, flood, to_voxels, voxel_faces and
+    nearest_voxel -, checked.  limit((nx, ny, nz)) raises where the extent is above the caller's size limit."""
     _require_shared_runtime()
     device = _device(dv)
     if not isinstance(grid, torch.Tensor) or grid.dim() != 3:
@@ -526,12 +531,7 @@ def _cc_grid(dv, grid, level, connectivity):
     nz, ny, nx = grid.shape
     if fmt == hip.GRID_BITS:
         nx *= 32
-    if connectivity is None:   # (to_voxels / count_voxels / save_voxels: no linear index, words of 64 voxels)
-        if max(nx, ny, nz) > MAX_CC_DIM or -(-nx // 64) * ny * nz > MAX_GATHER_WORDS:
-            raise ValueError(f"the grid's extent {(nx, ny, nz)} [x, y, z] is above {MAX_CC_DIM} along an axis or {MAX_GATHER_WORDS} "
-                             "words of 64 voxels along x in all")
-    elif max(nx, ny, nz) > MAX_CC_DIM or nx * ny * nz > MAX_CC_VOXELS:
-        raise ValueError(f"the grid's extent {(nx, ny, nz)} [x, y, z] is above {MAX_CC_DIM} along an axis or {MAX_CC_VOXELS} voxels in all")
+    limit((nx, ny, nz))
     return device, fmt, level, (nx, ny, nz)
 
 
@@ -546,7 +546,7 @@ def components(dv, grid, *, level=None, connectivity=6, background=False, out=No
     background:    False: the components of the solid voxels; True: of the voxels of the box that are not solid.
     out:           an int32 tensor of the labels' shape (any strides, not in grid's storage), written as it is; else a new
                    contiguous tensor.  Contiguous labels need no per-voxel scratch in the context."""
-    device, fmt, level, dims = _cc_grid(dv, grid, level, connectivity)
+    device, fmt, level, dims = _set_grid(dv, grid, level, _limit_voxels, connectivity)
     shape = (dims[2], dims[1], dims[0])
     if out is None:
         out = torch.empty(shape, dtype=torch.int32, device=device)
@@ -585,7 +585,7 @@ def flood(dv, grid, *, seeds=None, border=False, level=None, connectivity=6, bac
     border:  True: every voxel of the set on the six faces of the box is a seed as well.
     values:  three integers 0 .. 255.
     out:     a uint8 tensor of the grid's shape (any strides, not in grid's storage), or a bool tensor when the values are 0 / 1."""
-    device, fmt, level, dims = _cc_grid(dv, grid, level, connectivity)
+    device, fmt, level, dims = _set_grid(dv, grid, level, _limit_voxels, connectivity)
     shape = (dims[2], dims[1], dims[0])
     values = tuple(values)
     if len(values) != 3 or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 0 <= v <= 255 for v in values):
@@ -610,7 +610,7 @@ def flood(dv, grid, *, seeds=None, border=False, level=None, connectivity=6, bac
 def exterior(dv, grid, *, level=None, connectivity=6):
     """bool [z, y, x]: the empty voxels that reach the border of the box through empty voxels - flood with background=True,
     border=True and values (1, 0, 0)."""
-    device, _, _, dims = _cc_grid(dv, grid, level, connectivity)
+    device, _, _, dims = _set_grid(dv, grid, level, _limit_voxels, connectivity)
     out = torch.empty((dims[2], dims[1], dims[0]), dtype=torch.bool, device=device)
     return flood(dv, grid, border=True, level=level, connectivity=connectivity, background=True, values=(1, 0, 0), out=out)
 
@@ -647,10 +647,8 @@ def remove_small(dv, grid, min_voxels, *, level=None, connectivity=26):
 def _gather_args(dv, grid, level, origin, argb, colors, palette):
     """(device, (grid_ptr, format, strides, dims, level), (origin, colour mode, argb, colors_ptr, color_strides, palette)): the
     arguments of dv.gather_count and, with the colour part, of dv.gather_write / gather_save, checked."""
-    device, fmt, level, dims = _cc_grid(dv, grid, level, None)
-    origin = tuple(int(v) for v in origin)
-    if len(origin) != 3 or any(v < 0 for v in origin):
-        raise ValueError(f"origin {origin} must be three voxel coordinates, none negative")
+    device, fmt, level, dims = _set_grid(dv, grid, level, _limit_words)
+    origin = _origin(origin)
     if any(o + n > 2 ** 32 for o, n in zip(origin, dims)):
         raise ValueError(f"origin {origin} + the grid's extent {dims} [x, y, z] is above 2^32")
     if isinstance(argb, bool) or not isinstance(argb, numbers.Integral) or not -2 ** 31 <= argb < 2 ** 32:
@@ -813,7 +811,7 @@ def voxel_faces(dv, grid, *, level=None, origin=(0, 0, 0), merge="runs", argb=0x
 def _nearest_args(dv, seeds, level, surface_only):
     """(device, (seeds_ptr, format, strides, dims, level, flags), voxel shape) of the seed grid of nearest_voxel / spread_colors,
     checked as components checks its grid, and against the distance limit."""
-    device, fmt, level, dims = _cc_grid(dv, seeds, level, 6)
+    device, fmt, level, dims = _set_grid(dv, seeds, level, _limit_voxels)
     if sum((n - 1) ** 2 for n in dims) > MAX_NEAREST_D2:
         raise ValueError(f"the grid's extent {dims} [x, y, z] has (nx-1)^2 + (ny-1)^2 + (nz-1)^2 above {MAX_NEAREST_D2}")
     if surface_only and fmt != hip.GRID_U8:

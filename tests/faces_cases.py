@@ -16,6 +16,7 @@ from obj2voxel_amd import dense, hip, meshes
 from tests import components_ref as CR
 from tests import faces_ref as FR
 from tests import fill_ref
+from tests import gather_ref as GR
 from tests.gather_cases import FMT, grid_args
 from tests.raycast_cases import dev, expect_code, formats, layouts
 
@@ -262,6 +263,54 @@ def case_pipeline():
         rgb = np.unique(np.stack([want[2] >> 16 & 255, want[2] >> 8 & 255, want[2] & 255], axis=1).astype(np.int64), axis=0)
         assert np.array_equal(kd, rgb)
     print("sphere at 96:", len(want[2]), "quads,", len(back), "triangles through the OBJ reader")
+
+
+# ---- interleaved -----------------------------------------------------------------------------------------------------------------------
+
+def case_interleaved():
+    """Calls of the faces and of the gather in turns on one context.  The two share the device copy of the palette and the host
+    code of their counts, while each keeps the arrays of its own count: a _write must find its _count's bits and offsets, and its
+    own palette, after the other feature has counted and written in between."""
+    dv = hip.DeviceVoxelizer(0)
+    rng = np.random.default_rng(2028)
+    shape = (2, 3, 130)                                            # two full words of 64 voxels and a tail of 2 per row
+    A, B = (rng.integers(0, 4, shape).astype(np.uint8) for _ in range(2))
+    PA, PB = (rng.integers(0, 2 ** 32, 256, dtype=np.uint64).astype(np.uint32) for _ in range(2))
+    assert not np.array_equal(A, B) and not np.array_equal(PA[:4], PB[:4])
+    ta, tb = dev(A), dev(B)
+    want_quads = FR.quads(A, FR.U8, merge=FR.RUNS, palette=PA)
+    want_records = GR.records(B, GR.U8, palette=PB)
+    Q, n = len(want_quads[2]), len(want_records)
+    assert Q > 100 and n > 100
+    faces_a = grid_args(ta, FR.U8) + (hip.FACES_MERGE_RUNS, hip.GATHER_COLOR_PALETTE, 0, None, None, PA.tolist())
+    faces_b = grid_args(tb, FR.U8) + (hip.FACES_MERGE_RUNS, hip.GATHER_COLOR_PALETTE, 0, None, None, PB.tolist())
+    gather_b = grid_args(tb, GR.U8)
+    pos = torch.full((4 * Q, 3), 7.0, dtype=torch.float32, device=DEV)
+    fac = torch.full((2 * Q, 3), 7, dtype=torch.int32, device=DEV)
+    col = torch.full((Q,), 7, dtype=torch.int32, device=DEV)
+    rec = torch.full((2, n, 4), 7, dtype=torch.int32, device=DEV)
+    torch.cuda.synchronize()
+
+    def write_b(k):
+        dv.gather_write(*gather_b, (0, 0, 0), hip.GATHER_COLOR_PALETTE, 0, None, None, PB.tolist(), 0, n, rec[k].data_ptr())
+
+    assert dv.faces_count(*faces_a) == Q                                                              # 1
+    msg = expect_code(hip.ERR_BAD_ARGUMENT, lambda: dv.faces_write(*faces_b, (0, 0, 0), pos.data_ptr(), fac.data_ptr(), col.data_ptr(), Q),
+                      "faces_write(B) after faces_count(A)")
+    assert "no matching o2v_hip_faces_count" in msg
+    torch.cuda.synchronize()
+    assert bool((pos == 7).all()) and bool((fac == 7).all()) and bool((col == 7).all()), "the refused write wrote something"
+    assert dv.gather_count(*gather_b) == n                                                            # 2
+    write_b(0)                                                                                        # 3
+    dv.faces_write(*faces_a, (0, 0, 0), pos.data_ptr(), fac.data_ptr(), col.data_ptr(), Q)            # 4
+    write_b(1)                                                                                        # 5
+    torch.cuda.synchronize()
+    assert np.array_equal(pos.cpu().numpy().view(np.uint32), want_quads[0].view(np.uint32)), "positions of A"
+    assert np.array_equal(fac.cpu().numpy(), want_quads[1]), "faces of A"
+    assert np.array_equal(col.cpu().numpy().view(np.uint32), want_quads[2]), "colours of A: palette PA"
+    for k in range(2):
+        assert np.array_equal(rec[k].cpu().numpy().view(np.uint32), want_records), ("records of B: palette PB, write", k)
+    print("interleaved:", Q, "quads of A and twice", n, "records of B compared; refused:", msg)
 
 
 # ---- refusals --------------------------------------------------------------------------------------------------------------------------

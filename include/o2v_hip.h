@@ -641,8 +641,36 @@ int o2v_hip_gather_times(const o2v_hip_ctx *ctx, float out_ms[3]);
  * Scratch of the context, grown on demand (o2v_hip_faces_scratch_bytes, an upper bound; 0 for zero dims): 8 * words - 24 *
  * words with GRID or PALETTE, of which MERGE_NONE uses 8 - + 8 * (ceil(6 * words / 256) + 1) + 1024: a 64-bit word per 64
  * voxels along x for the set and the two comparisons, a 64-bit offset per block of 256 (row, direction, word) items and the
- * count, the palette. */
-enum { O2V_HIP_FACES_MERGE_NONE = 0, O2V_HIP_FACES_MERGE_RUNS = 1 };
+ * count, the palette.
+ *
+ * Rectangles.  O2V_HIP_FACES_MERGE_RECTS = 3: one quad per maximal chain of equal runs.  The merge value
+ * is read as flags, bit 0 "runs" and bit 1 "stack the runs"; 2 alone - stacking without runs - means nothing and stays refused
+ * ("unknown merge 2").  The set, the colours, the exposed faces, the runs, the order key, the corner order and every refusal are
+ * those above.
+ *   The stack axis of direction d is y for d = 4, 5 (the -z / +z faces, runs along x) and z for d = 0 .. 3 (-y / +y, runs along
+ * x; -x / +x, runs along y).  The row before a run's row is the one at y - 1 for d = 4, 5 and at z - 1 otherwise, the other
+ * coordinates and the plane the same.
+ *   Two runs of one direction in neighbouring rows are equal if they begin at the same coordinate along the run axis, have the
+ * same length and their voxels have the same colour as uint32 (a run has one colour, so the first voxels decide; colours, not
+ * labels, and with CONSTANT every pair is equal).
+ *   A rectangle is a maximal chain of equal runs in consecutive rows, emitted as one quad over the lattice bounds of all its
+ * faces.  Its key is that of the chain's first run - the lowest row -, ((z * ny + y) * 6 + d) * nx + x of its lowest face; its
+ * colour is read at the time of the write at that run's first voxel; its corners are (u0, v0), (u1, v0), (u1, v1), (u0, v1) or
+ * the mirrored order by the rule above, on the larger bounds.
+ *   This is not the sequential greedy mesher, which depends on its scan order and cannot run in parallel: a rectangle never
+ * joins runs of different extent, so an L-shaped wall keeps a quad per row of its narrow part.  The rule is a function of the set
+ * and the colours alone, so two calls agree bit for bit and a numpy restatement (tests/rects_ref.py) reproduces it.
+ * Rectangles, like runs, leave T-junctions.  Nothing is cut at a word, a block of items, the row y = ny - 1 or any other
+ * boundary of the implementation, and nothing is joined across one: row (y = 0, z + 1) is not the row after (y = ny - 1, z).
+ *   The limits, the alignment of the outputs, "no matching o2v_hip_faces_count" (the merge value is part of what must match)
+ * and quad_capacity hold as above.
+ *   Scratch: o2v_hip_faces_scratch_bytes keeps its values and is the bound of MERGE_NONE and MERGE_RUNS;
+ * o2v_hip_faces_scratch_bytes_merge(dims, color_mode, merge) returns it for those, and for MERGE_RECTS
+ *     o2v_hip_faces_scratch_bytes(dims, color_mode) + 48 * words + (8 * words with GRID or PALETTE):
+ * the kept rectangle-start masks, a 64-bit word per (row, direction, word) item, and a bit per voxel for "the colour of the
+ * voxel at z - 1".  These arrays belong to MERGE_RECTS alone: a count with another merge mode between a MERGE_RECTS count and
+ * its write replaces the count (the write is then refused), but no other call of the context touches them. */
+enum { O2V_HIP_FACES_MERGE_NONE = 0, O2V_HIP_FACES_MERGE_RUNS = 1, O2V_HIP_FACES_MERGE_RECTS = 3 };
 int o2v_hip_faces_count(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
                         uint32_t merge, uint32_t color_mode, uint32_t argb, const uint32_t *colors, const uint64_t color_strides[3],
                         const uint32_t *palette /* [256], host */, uint64_t *out_quads);
@@ -652,6 +680,7 @@ int o2v_hip_faces_write(o2v_hip_ctx *ctx, const void *grid, uint32_t format, con
                         int32_t *faces /* [2Q][3], device, may be NULL */, uint32_t *quad_argb /* [Q], device, may be NULL */,
                         uint64_t quad_capacity);
 uint64_t o2v_hip_faces_scratch_bytes(const uint32_t dims[3], uint32_t color_mode);
+uint64_t o2v_hip_faces_scratch_bytes_merge(const uint32_t dims[3], uint32_t color_mode, uint32_t merge);
 /* The device times (ms) of the last count's classify (+ colour comparison) and count + scan stages and of the last write (0
  * after a count). */
 int o2v_hip_faces_times(const o2v_hip_ctx *ctx, float out_ms[3]);

@@ -22,7 +22,7 @@
 //                         lane's before, so a wavefront writes 64 x 48, 64 x 24 and 64 x 4 contiguous bytes.
 // No atomics, no private segment: every order comes from the scans.
 
-constexpr uint32_t kFaMergeNone = 0, kFaMergeRuns = 1;   // O2V_HIP_FACES_MERGE_*
+constexpr uint32_t kFaMergeNone = 0, kFaMergeRuns = 1, kFaMergeRects = 3;   // O2V_HIP_FACES_MERGE_*
 
 #ifndef O2V_FA_HOST
 #define O2V_FA_FN __device__ __forceinline__

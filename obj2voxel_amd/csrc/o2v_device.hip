@@ -40,6 +40,8 @@
 //                              into runs; outside the pipeline
 //   K15 k_near_*               o2v_hip_nearest_dense: the nearest seed voxel of every voxel (K8's passes with the seed's
 //                              coordinates as payload) and its value spread over the grid; outside the pipeline
+//   K16 k_rects_*              O2V_HIP_FACES_MERGE_RECTS of K14's calls: equal runs of neighbouring rows stacked into
+//                              rectangles; outside the pipeline
 //   plan k_zhist               o2v_hip_plan_slabs: predicted hits per z layer -> work-balanced slabs for N GPUs
 // With the direct MAX path K1's counters reach the host while K2 runs, and only the stages that have work are enqueued
 // behind it.  N > 1 GPUs: o2v_hip_voxelize_sharded (bounds / work-histogram passes sharded over the ranks, RCCL).
@@ -91,6 +93,7 @@ namespace {
 #include "o2v_dev_k12_components.hpp"
 #include "o2v_dev_k13_gather.hpp"
 #include "o2v_dev_k14_faces.hpp"
+#include "o2v_dev_k16_rects.hpp"
 #include "o2v_dev_k15_nearest.hpp"
 
 }  // namespace
@@ -419,6 +422,9 @@ struct o2v_hip_ctx {
     DevArray<unsigned long long> d_fa_bits, d_fa_same_x, d_fa_same_y, d_fa_boff;
     PinnedArray<unsigned long long> h_fa_ctr;
     StageTimes<3> fa_times;
+    // K16 (O2V_HIP_FACES_MERGE_RECTS): the same-colour bits along z (GRID / PALETTE) and the kept rectangle-start masks, a
+    // word per item; grown only by a count with that merge mode
+    DevArray<unsigned long long> d_rc_same_z, d_rc_starts;
     struct FacesCount {
         bool valid = false;
         GridKey key;
@@ -3739,14 +3745,14 @@ int fa_args(o2v_hip_ctx *ctx, const char *fn, const void *grid, uint32_t format,
     static const uint32_t no_origin[3] = {0, 0, 0};
     int rc;
     if ((rc = ga_grid(ctx, fn, grid, format, strides, dims, level, sg, &gg))) return rc;
-    if (merge != O2V_HIP_FACES_MERGE_NONE && merge != O2V_HIP_FACES_MERGE_RUNS)
+    if (merge != O2V_HIP_FACES_MERGE_NONE && merge != O2V_HIP_FACES_MERGE_RUNS && merge != O2V_HIP_FACES_MERGE_RECTS)
         return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown merge " + std::to_string(merge));
     if ((rc = ga_mode(ctx, fn, format, dims, no_origin, color_mode)) ||
         (rc = ga_color_source(ctx, fn, dims, color_mode, colors, color_strides, palette, cbytes)))
         return rc;
     g->nx = gg.nx, g->ny = gg.ny, g->nz = gg.nz, g->W = gg.W;
     g->merge = merge;
-    g->colored = merge == O2V_HIP_FACES_MERGE_RUNS && color_mode != O2V_HIP_GATHER_COLOR_CONSTANT;
+    g->colored = merge != O2V_HIP_FACES_MERGE_NONE && color_mode != O2V_HIP_GATHER_COLOR_CONSTANT;
     g->words = gg.words;
     g->items = 6u * gg.words;
     g->n_blocks = (g->items + kBlock - 1) / kBlock;
@@ -3776,6 +3782,13 @@ uint64_t o2v_hip_faces_scratch_bytes(const uint32_t dims[3], uint32_t color_mode
     return (color_mode == O2V_HIP_GATHER_COLOR_CONSTANT ? 8u : 24u) * words + 8u * ((6u * words + kBlock - 1) / kBlock + 1u) + 1024u;
 }
 
+uint64_t o2v_hip_faces_scratch_bytes_merge(const uint32_t dims[3], uint32_t color_mode, uint32_t merge)
+{
+    const uint64_t bytes = o2v_hip_faces_scratch_bytes(dims, color_mode);
+    if (!bytes || merge != O2V_HIP_FACES_MERGE_RECTS) return bytes;
+    return bytes + (color_mode == O2V_HIP_GATHER_COLOR_CONSTANT ? 48u : 56u) * cc_words(dims);
+}
+
 int o2v_hip_faces_count(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
                         uint32_t merge, uint32_t color_mode, uint32_t argb, const uint32_t *colors, const uint64_t color_strides[3],
                         const uint32_t *palette, uint64_t *out_quads)
@@ -3789,9 +3802,12 @@ int o2v_hip_faces_count(o2v_hip_ctx *ctx, const void *grid, uint32_t format, con
     uint64_t cbytes = 0;
     int rc;
     if ((rc = fa_args(ctx, fn, grid, format, strides, dims, level, merge, color_mode, colors, color_strides, palette, &sg, &g, &cbytes))) return rc;
+    const bool rects = merge == O2V_HIP_FACES_MERGE_RECTS;
     if ((rc = grow_scratch(ctx, ctx->d_fa_bits, g.words, fn, "set bits")) ||
         (g.colored && ((rc = grow_scratch(ctx, ctx->d_fa_same_x, g.words, fn, "same-colour bits")) ||
                        (rc = grow_scratch(ctx, ctx->d_fa_same_y, g.words, fn, "same-colour bits")))) ||
+        (rects && ((g.colored && (rc = grow_scratch(ctx, ctx->d_rc_same_z, g.words, fn, "same-colour bits"))) ||
+                   (rc = grow_scratch(ctx, ctx->d_rc_starts, g.items, fn, "rectangle starts")))) ||
         (rc = grow_scratch(ctx, ctx->d_fa_boff, g.n_blocks + 1u, fn, "block offsets")) || (rc = grow_scratch(ctx, ctx->h_fa_ctr, 1u, fn, "counters")))
         return rc;
     ctx->ktimes_on = false;   // (no per-launch brackets here; o2v_hip_voxelize sets the flag again from its params)
@@ -3811,9 +3827,17 @@ int o2v_hip_faces_count(o2v_hip_ctx *ctx, const void *grid, uint32_t format, con
             O2V_LAUNCH("k_faces_same", s, k_faces_same<kGaColorGrid>, per_word, dim3(kBlock), 0, s, g, bits, col, ctx->d_fa_same_x.ptr,
                        ctx->d_fa_same_y.ptr);
         }
+        if (rects && color_mode == O2V_HIP_GATHER_COLOR_PALETTE)
+            O2V_LAUNCH("k_rects_same_z", s, k_rects_same_z<kGaColorPalette>, per_word, dim3(kBlock), 0, s, g, bits, col, ctx->d_rc_same_z.ptr);
+        else if (rects)
+            O2V_LAUNCH("k_rects_same_z", s, k_rects_same_z<kGaColorGrid>, per_word, dim3(kBlock), 0, s, g, bits, col, ctx->d_rc_same_z.ptr);
     }
     O2V_CHECK(ctx->fa_times.mark(1, s));
-    O2V_LAUNCH("k_faces_count", s, k_faces_count, dim3((uint32_t) std::min<uint64_t>(g.n_blocks, kFaMaxGrid)), dim3(kBlock), 0, s, g, fa_bits(ctx), boff);
+    const dim3 count_grid((uint32_t) std::min<uint64_t>(g.n_blocks, kFaMaxGrid));
+    if (rects)
+        O2V_LAUNCH("k_rects_count", s, k_rects_count, count_grid, dim3(kBlock), 0, s, g, fa_bits(ctx), ctx->d_rc_same_z.ptr, ctx->d_rc_starts.ptr, boff);
+    else
+        O2V_LAUNCH("k_faces_count", s, k_faces_count, count_grid, dim3(kBlock), 0, s, g, fa_bits(ctx), boff);
     uint64_t total = 0;
     if ((rc = count_total(ctx, boff, g.n_blocks, ctx->h_fa_ctr, ctx->fa_times, &total))) return rc;
 #ifdef O2V_FA_MUTATE_COUNT32
@@ -3876,7 +3900,17 @@ int o2v_hip_faces_write(o2v_hip_ctx *ctx, const void *grid, uint32_t format, con
     float4 *const pos = reinterpret_cast<float4 *>(positions);
     int2 *const tri = reinterpret_cast<int2 *>(faces);
     O2V_CHECK(hipEventRecord(ctx->fa_times.ev[2], s));
-    if (color_mode == O2V_HIP_GATHER_COLOR_GRID)
+    const unsigned long long *const rstarts = ctx->d_rc_starts.ptr, *const boff = ctx->d_fa_boff.ptr;
+    if (merge == O2V_HIP_FACES_MERGE_RECTS && color_mode == O2V_HIP_GATHER_COLOR_GRID)
+        O2V_LAUNCH("k_rects_write", s, k_rects_write<kGaColorGrid>, blocks, dim3(kBlock), 0, s, g, fa_bits(ctx), rstarts, boff, origin[0], origin[1],
+                   origin[2], col, pos, tri, quad_argb);
+    else if (merge == O2V_HIP_FACES_MERGE_RECTS && color_mode == O2V_HIP_GATHER_COLOR_PALETTE)
+        O2V_LAUNCH("k_rects_write", s, k_rects_write<kGaColorPalette>, blocks, dim3(kBlock), 0, s, g, fa_bits(ctx), rstarts, boff, origin[0], origin[1],
+                   origin[2], col, pos, tri, quad_argb);
+    else if (merge == O2V_HIP_FACES_MERGE_RECTS)
+        O2V_LAUNCH("k_rects_write", s, k_rects_write<kGaColorConstant>, blocks, dim3(kBlock), 0, s, g, fa_bits(ctx), rstarts, boff, origin[0], origin[1],
+                   origin[2], col, pos, tri, quad_argb);
+    else if (color_mode == O2V_HIP_GATHER_COLOR_GRID)
         O2V_LAUNCH("k_faces_write", s, k_faces_write<kGaColorGrid>, blocks, dim3(kBlock), 0, s, g, fa_bits(ctx), ctx->d_fa_boff.ptr, origin[0], origin[1],
                    origin[2], col, pos, tri, quad_argb);
     else if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE)

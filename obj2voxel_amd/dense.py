@@ -50,7 +50,7 @@ MAX_RAY_EXTENT = 65536      # RayCaster: origin + extent per axis
 MAX_CC_DIM = 65536          # components / flood: voxels per axis ...
 MAX_CC_VOXELS = 2 ** 31 - 1  # ... and in all: a linear index and a label are one int32
 MAX_FACES_EXTENT = 65536    # voxel_faces: origin + extent per axis: a coordinate is an exact float32
-_FACES_MERGE = {"none": hip.FACES_MERGE_NONE, "runs": hip.FACES_MERGE_RUNS}
+_FACES_MERGE = {"none": hip.FACES_MERGE_NONE, "runs": hip.FACES_MERGE_RUNS, "rects": hip.FACES_MERGE_RECTS}
 MAX_GATHER_WORDS = 2 ** 31 - 1  # to_voxels / save_voxels: words of 64 voxels along x, ceil(nx / 64) * ny * nz
 MAX_NEAREST_D2 = 2 ** 31 - 2    # nearest_voxel / spread_colors: (nx-1)^2 + (ny-1)^2 + (nz-1)^2, the largest squared distance
 
@@ -757,7 +757,7 @@ def _faces_args(dv, grid, level, origin, merge, argb, colors, palette):
     """(device, the arguments of dv.faces_count, origin): the grid and colour arguments as to_voxels checks them, the merge
     mode, and the origin within the box whose coordinates are exact float32."""
     if merge not in _FACES_MERGE:
-        raise ValueError(f"merge must be 'none' or 'runs', not {merge!r}")
+        raise ValueError(f"merge must be 'none', 'runs' or 'rects', not {merge!r}")
     device, grid_args, (origin, mode, argb, colors_ptr, color_strides, palette) = _gather_args(dv, grid, level, origin, argb, colors, palette)
     if any(o + n > MAX_FACES_EXTENT for o, n in zip(origin, grid_args[3])):
         raise ValueError(f"origin {origin} + the grid's extent {grid_args[3]} [x, y, z] is above {MAX_FACES_EXTENT}")
@@ -782,7 +782,9 @@ def voxel_faces(dv, grid, *, level=None, origin=(0, 0, 0), merge="runs", argb=0x
     origin:     (ox, oy, oz): voxel (x, y, z) is the cube from origin + (x, y, z) to origin + (x, y, z) + 1; origin + extent is
                 at most 65 536 per axis, so that every coordinate is an exact float32.
     merge:      "runs": exposed faces of one direction that are neighbours along x (along y for the -x and +x faces) and whose
-                voxels have the same colour become one quad; "none": a quad per face.
+                voxels have the same colour become one quad; "rects": and runs of neighbouring rows (along y for the -z and
+                +z faces, along z for the others) that begin together, are equally long and of one colour become one
+                rectangle, so that a flat wall is one quad; "none": a quad per face.
     transform:  None: positions in voxel space.  dv.transform() (the 12 floats, model to voxel space): positions in model
                 space, A^-1 p, computed in float64 and rounded once, as extract_surface does."""
     device, args, origin = _faces_args(dv, grid, level, origin, merge, argb, colors, palette)

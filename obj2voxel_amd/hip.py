@@ -31,7 +31,7 @@ CC_INVERT, CC_SEED_BORDER = 16, 32  # ... their flags (with FLAG_STAGE_TIMES: th
 CC_SCRATCH_LABELS, CC_SCRATCH_LABELS_STRIDED, CC_SCRATCH_FLOOD = 0, 1, 2  # o2v_hip_components_scratch_bytes
 MESH_DIST_UNSIGNED_F32, MESH_DIST_SIGNED_F32 = 0, 1  # o2v_hip_mesh_distance_dense formats
 GATHER_COLOR_CONSTANT, GATHER_COLOR_GRID, GATHER_COLOR_PALETTE = 0, 1, 2  # o2v_hip_gather_write / _save colour modes
-FACES_MERGE_NONE, FACES_MERGE_RUNS = 0, 1  # o2v_hip_faces_count / _write merge modes
+FACES_MERGE_NONE, FACES_MERGE_RUNS, FACES_MERGE_RECTS = 0, 1, 3  # o2v_hip_faces_count / _write merge modes
 NEAREST_SEED_ONE, NEAREST_VALUES_INSIDE = 1, 2  # o2v_hip_nearest_dense flags
 NEAREST_NO_LIMIT = 0x7FFFFFFF  # ... its max_dist2 without a limit
 ERR_BAD_ARGUMENT = 3
@@ -162,6 +162,8 @@ def _bind():
     L.o2v_hip_faces_write.argtypes = _faces + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
     L.o2v_hip_faces_scratch_bytes.argtypes = [C.c_void_p, C.c_uint32]
     L.o2v_hip_faces_scratch_bytes.restype = C.c_uint64
+    L.o2v_hip_faces_scratch_bytes_merge.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+    L.o2v_hip_faces_scratch_bytes_merge.restype = C.c_uint64
     L.o2v_hip_faces_times.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_nearest_dense.argtypes = _gather + [C.c_uint32] + [C.c_void_p] * 6 + [C.c_uint32]   # ..., flags, 3 x (grid, strides), max_dist2
     L.o2v_hip_nearest_scratch_bytes.argtypes = [C.c_void_p]
@@ -232,9 +234,12 @@ def gather_scratch_bytes(dims):
     return int(_bind().o2v_hip_gather_scratch_bytes(_u32x3(dims)))
 
 
-def faces_scratch_bytes(dims, color_mode=GATHER_COLOR_CONSTANT):
-    """o2v_hip_faces_scratch_bytes: the context scratch a faces_count over dims (x, y, z) takes at most."""
-    return int(_bind().o2v_hip_faces_scratch_bytes(_u32x3(dims), color_mode))
+def faces_scratch_bytes(dims, color_mode=GATHER_COLOR_CONSTANT, merge=None):
+    """o2v_hip_faces_scratch_bytes: the context scratch a faces_count over dims (x, y, z) takes at most; with a merge mode
+    o2v_hip_faces_scratch_bytes_merge: FACES_MERGE_RECTS takes more than the other two."""
+    if merge is None:
+        return int(_bind().o2v_hip_faces_scratch_bytes(_u32x3(dims), color_mode))
+    return int(_bind().o2v_hip_faces_scratch_bytes_merge(_u32x3(dims), color_mode, merge))
 
 
 def device_count():
@@ -493,7 +498,8 @@ class DeviceVoxelizer:
 
     def faces_count(self, grid_ptr, fmt, strides, dims, level, merge, color_mode, argb, colors_ptr, color_strides, palette):
         """o2v_hip_faces_count: the number of quads of the grid's exposed voxel faces (grid arguments as gather_count takes them;
-        merge: FACES_MERGE_NONE - one per face - or FACES_MERGE_RUNS - one per run of faces of one colour; the colour arguments
+        merge: FACES_MERGE_NONE - one per face -, FACES_MERGE_RUNS - one per run of faces of one colour - or FACES_MERGE_RECTS - one
+        per chain of equal runs in neighbouring rows; the colour arguments
         as gather_write takes them).  The one pass over the grid: the set's bits stay in the context for faces_write."""
         n = C.c_uint64(0)
         self._check(self._L.o2v_hip_faces_count(*self._faces_args(grid_ptr, fmt, strides, dims, level, merge, color_mode, argb, colors_ptr,
@@ -509,9 +515,9 @@ class DeviceVoxelizer:
                                                                   color_strides, palette), _u32x3(origin), positions_ptr, faces_ptr,
                                                 quad_argb_ptr, quad_capacity), "o2v_hip_faces_write")
 
-    def faces_scratch_bytes(self, dims, color_mode=GATHER_COLOR_CONSTANT):
-        """o2v_hip_faces_scratch_bytes: the context scratch a faces_count over dims (x, y, z) takes at most."""
-        return faces_scratch_bytes(dims, color_mode)
+    def faces_scratch_bytes(self, dims, color_mode=GATHER_COLOR_CONSTANT, merge=None):
+        """o2v_hip_faces_scratch_bytes (merge None) / _merge: the context scratch a faces_count over dims (x, y, z) takes at most."""
+        return faces_scratch_bytes(dims, color_mode, merge)
 
     def faces_times(self):
         """o2v_hip_faces_times: the device times (ms) of the last faces_count's classify and count + scan stages and of the last

@@ -1,5 +1,7 @@
 """obj2voxel_amd.dense without a GPU: the argument checks of the torch layer and its z-slab loop, with the device calls
-stubbed; and a static check of the K7 kernels in the gfx950 code object (hipcc cross-compiles)."""
+stubbed; the wait for torch's stream in front of every function's first library call that takes a tensor; and a static check of
+the K7 kernels in the gfx950 code object (hipcc cross-compiles)."""
+import ctypes as C
 import os
 import re
 import shutil
@@ -50,6 +52,64 @@ class StubVoxelizer:
     def write_dense(self, ptr, fmt, origin, dims, strides):
         self.calls.append(("write", fmt, tuple(origin), tuple(dims), tuple(strides)))
         return self.outside
+
+    # the entry points of the other families: their names go to `calls`; the counts are `n`
+    def distance_dense(self, *args):
+        self.calls.append(("distance",))
+
+    def mesh_distance_dense(self, *args, **kw):
+        self.calls.append(("mesh_distance",))
+
+    def surface_count(self, *args):
+        self.calls.append(("surface_count",))
+        return self.n, self.n
+
+    def surface_write(self, *args):
+        self.calls.append(("surface_write",))
+
+    def raycast_build(self, *args):
+        self.calls.append(("raycast_build",))
+        return 7
+
+    def raycast_generation(self):
+        return 7
+
+    def raycast(self, *args):
+        self.calls.append(("raycast",))
+
+    def components_dense(self, grid_ptr, fmt, strides, dims, level, connectivity, flags, labels_ptr, label_strides):
+        self.calls.append(("components",))
+        C.memset(labels_ptr, 0, 4 * dims[0] * dims[1] * dims[2])   # (a new contiguous tensor: every voxel background)
+        return 0
+
+    def flood_dense(self, *args):
+        self.calls.append(("flood",))
+
+    def gather_count(self, *args):
+        self.calls.append(("gather_count",))
+        return self.n
+
+    def gather_write(self, *args):
+        self.calls.append(("gather_write",))
+
+    def gather_save(self, *args):
+        self.calls.append(("gather_save",))
+        return self.n
+
+    def faces_count(self, *args):
+        self.calls.append(("faces_count",))
+        return self.n
+
+    def faces_write(self, *args):
+        self.calls.append(("faces_write",))
+
+    def nearest_dense(self, *args):
+        self.calls.append(("nearest",))
+
+
+# the stub's calls that hand a tensor's pointer to the library
+POINTER_CALLS = {"set", "write", "distance", "mesh_distance", "surface_count", "surface_write", "raycast_build", "raycast", "components", "flood",
+                 "gather_count", "gather_write", "gather_save", "faces_count", "faces_write", "nearest"}
 
 
 @pytest.fixture(autouse=True)
@@ -171,6 +231,94 @@ def test_slabs_cover_the_grid_once():
 def test_empty_result_tight():
     t, origin = dense.voxelize_dense(StubVoxelizer(n=0), 16, box="tight")
     assert tuple(t.shape) == (0, 0, 0) and origin == (0, 0, 0)
+
+
+# ---- the wait in front of the library ----------------------------------------------------------------------------------------------
+
+def _grids():
+    g = torch.zeros((4, 5, 6), dtype=torch.bool)
+    g[1:3, 1:4, 2:5] = True
+    rays = torch.ones((3, 3))
+    return dict(g=g, labels=g.to(torch.uint8), field=torch.where(g, -1.0, 1.0), colors=torch.zeros(g.shape, dtype=torch.int32), o=rays, d=rays.clone(),
+                seeds=torch.tensor([[2, 1, 1]], dtype=torch.int32))
+
+
+def _caster(dv, t):
+    return dense.RayCaster(dv, t["g"])
+
+
+# (name, what runs before the log starts or None, the call): every public function of dense.py that hands a tensor to the library
+WAIT_CASES = [
+    ("set_mesh", None, lambda dv, t, _: dense.set_mesh(dv, torch.zeros((4, 9)))),
+    ("voxelize_dense", None, lambda dv, t, _: dense.voxelize_dense(dv, 16)),
+    ("voxelize_dense out=", None, lambda dv, t, _: dense.voxelize_dense(dv, 16, fmt="argb", out=torch.zeros((16, 16, 16), dtype=torch.int32))),
+    ("voxelize_dense sdf", None, lambda dv, t, _: dense.voxelize_dense(dv, 16, fmt="sdf", fill=True)),
+    ("distance_transform", None, lambda dv, t, _: dense.distance_transform(dv, t["labels"])),
+    ("mesh_distance", None, lambda dv, t, _: dense.mesh_distance(dv, 16, band=2.0, closest=True, max_layers=4)),
+    ("extract_surface", None, lambda dv, t, _: dense.extract_surface(dv, t["field"])),
+    ("RayCaster", None, lambda dv, t, _: dense.RayCaster(dv, t["g"])),
+    ("RayCaster.cast", _caster, lambda dv, t, caster: caster.cast(t["o"], t["d"])),
+    ("raycast", None, lambda dv, t, _: dense.raycast(dv, t["field"], t["o"], t["d"], level=0.0)),
+    ("components", None, lambda dv, t, _: dense.components(dv, t["g"])),
+    ("flood", None, lambda dv, t, _: dense.flood(dv, t["g"], seeds=t["seeds"])),
+    ("exterior", None, lambda dv, t, _: dense.exterior(dv, t["g"])),
+    ("solidify", None, lambda dv, t, _: dense.solidify(dv, t["g"])),
+    ("remove_small", None, lambda dv, t, _: dense.remove_small(dv, t["g"], 2)),
+    ("count_voxels", None, lambda dv, t, _: dense.count_voxels(dv, t["g"])),
+    ("to_voxels", None, lambda dv, t, _: dense.to_voxels(dv, t["g"], colors=t["colors"])),
+    ("save_voxels", None, lambda dv, t, _: dense.save_voxels(dv, t["g"], "never_written.vl32")),
+    ("count_faces", None, lambda dv, t, _: dense.count_faces(dv, t["g"], merge="rects")),
+    ("voxel_faces", None, lambda dv, t, _: dense.voxel_faces(dv, t["g"], merge="rects", colors=t["colors"])),
+    ("nearest_voxel", None, lambda dv, t, _: dense.nearest_voxel(dv, t["g"], dist2=True)),
+    ("spread_colors", None, lambda dv, t, _: dense.spread_colors(dv, t["g"], t["colors"])),
+]
+
+
+def _check_wait(monkeypatch, before, call):
+    """Runs one dense call on a stub whose log also takes the waits, and asserts that the first library call that is handed a
+    tensor comes behind a wait, and that every wait before it is on the voxelizer's device: the very object dense._device gave
+    for this voxelizer, not a device made from torch's current one.  Returns the names logged."""
+    dv = StubVoxelizer(n=3)
+    own = torch.device("cpu")
+    monkeypatch.setattr(dense, "_device", lambda v: own if v is dv else None)
+    monkeypatch.setattr(dense, "_sync", lambda device: dv.calls.append(("sync", device)))
+    t = _grids()
+    state = before(dv, t) if before else None
+    del dv.calls[:]
+    call(dv, t, state)
+    names = [c[0] for c in dv.calls]
+    first = next((i for i, name in enumerate(names) if name in POINTER_CALLS), None)
+    assert first is not None, "no library call was handed a tensor"
+    waits = [c for c in dv.calls[:first] if c[0] == "sync"]
+    assert waits, f"{names[first]} was called before any wait: {names}"
+    assert all(c[1] is own for c in waits), "a wait on another device than the voxelizer's"
+    return names
+
+
+@pytest.mark.parametrize("name, before, call", WAIT_CASES, ids=[c[0] for c in WAIT_CASES])
+def test_a_wait_comes_before_the_first_library_call_that_takes_a_tensor(monkeypatch, name, before, call):
+    """The context's stream does not wait for torch's (it is created non-blocking), so dense._sync(device) is all that keeps a
+    kernel of the library from reading a tensor torch has not finished writing, or a queued torch.zeros from landing on its
+    output.  Every public function that hands a tensor to the library must wait on the voxelizer's device before its first such
+    call; the write of a count / write pair needs no wait of its own.  (The mutation below, a count_voxels without its wait, was
+    seen to fail this check - "gather_count was called before any wait" - when the test was written.)"""
+    names = _check_wait(monkeypatch, before, call)
+    pairs = {"extract_surface": ("surface_count", "surface_write"), "to_voxels": ("gather_count", "gather_write"),
+             "voxel_faces": ("faces_count", "faces_write")}
+    if name in pairs:   # (both calls of the pair were made, behind one wait)
+        count, write = pairs[name]
+        assert names.index("sync") < names.index(count) < names.index(write)
+
+
+def test_the_wait_check_fails_a_count_voxels_without_its_wait(monkeypatch):
+    def count_voxels(dv, grid, *, level=None):
+        _, grid_args, _ = dense._gather_args(dv, grid, level, (0, 0, 0), 0, None, None)
+        return dv.gather_count(*grid_args)
+
+    _check_wait(monkeypatch, None, lambda dv, t, _: dense.count_voxels(dv, t["g"]))
+    monkeypatch.setattr(dense, "count_voxels", count_voxels)
+    with pytest.raises(AssertionError, match="gather_count was called before any wait"):
+        _check_wait(monkeypatch, None, lambda dv, t, _: dense.count_voxels(dv, t["g"]))
 
 
 @pytest.fixture(scope="module")

@@ -732,6 +732,58 @@ uint64_t o2v_hip_nearest_scratch_bytes(const uint32_t dims[3]);
 /* The device times of the last o2v_hip_nearest_dense call's three passes (x, y, z), from events around each, in ms. */
 int o2v_hip_nearest_times(const o2v_hip_ctx *ctx, float out_ms[3]);
 
+/* ---- downsampling: a dense grid merged into a coarser one ------------------------------------------
+ *
+ * Blocks of f x f x f fine voxels become one coarse voxel each: its coverage count, its occupancy by a threshold on that count,
+ * the smallest or largest label of the block and the mean colour of the block's solid voxels.  Supersampling is this operation
+ * behind a voxelization at f times the resolution.
+ *
+ * The set.  grid, format (O2V_HIP_GRID_U8 / _BITS / _F32_BELOW), strides, dims = (nx, ny, nz) and level are those of
+ * o2v_hip_components_dense: a fine voxel is solid where a U8 element is non-zero, where its BITS bit is set (strides[0] == 1),
+ * where an F32_BELOW element is < level (finite; a NaN is not below it).  A stride may be 0.  grid is only read.
+ * origin[3] holds the global fine-lattice coordinates of the box's voxel (0, 0, 0).  factor f is 2 ... 8.
+ *
+ * The coarse box.  Per axis a: corigin[a] = floor(origin[a] / f), cdims[a] = ceil((origin[a] + dims[a]) / f) - corigin[a];
+ * o2v_hip_downsample_box computes both (O2V_HIP_ERR_BAD_ARGUMENT for a null argument, zero dims or a factor outside 2 ... 8,
+ * O2V_HIP_ERR_LIMIT for origin + dims above 2^32).  Coarse voxel X = (X0, X1, X2) of the coarse box covers the fine voxels with
+ * global coordinates in [(corigin[a] + Xa) f, (corigin[a] + Xa + 1) f) on each axis: blocks are aligned to the global lattice,
+ * not to the box, and the fine voxels of a block that lie outside the box count as empty.  So the downsampled box of a
+ * voxelization at 2R lines up with the voxelization at R with supersampling 2.
+ *
+ *   c(X) = the number of solid fine voxels of the block of X, 0 ... f^3 <= 512.
+ *
+ * Outputs over the coarse box, device memory, strides in elements per axis x, y, z, any order; none may map two coarse voxels
+ * to one element; each may be NULL, but not all of them; every element of every given output is written:
+ *   count   int16: c(X).
+ *   solid   uint8: 1 if c(X) >= min_count, else 0.  min_count is 1 ... f^3: 1 is "any", f^3 "all", ceil(f^3 / 2) "majority".
+ *   values  uint8, U8 grids only: where solid(X) the smallest (value_mode O2V_HIP_DOWN_VALUE_MIN) or largest (_MAX) non-zero
+ *           byte of the block's fine voxels inside the box, else 0.  With label grids (1 surface, 2 interior) MIN gives "surface
+ *           if any sub-voxel is surface".  value_mode is looked at only when values is given.
+ *   argb    uint32, needs colors: a uint32 grid over the fine box, strides in elements as in o2v_hip_gather_write (a stride may
+ *           be 0).  Where solid(X), each of the four 8-bit channels is the mean of that channel over the block's solid fine
+ *           voxels, rounded half up: (2 sum + c) / (2 c) in integers, c = c(X); elsewhere 0.  The colours of fine voxels that
+ *           are not solid are never used (and not read).  Without argb the memory at colors is not looked at.
+ * All sums are integers, so the result does not depend on any order and one run equals another bit for bit.  No scratch.
+ *
+ * Refused before anything is launched, the outputs untouched.  O2V_HIP_ERR_BAD_ARGUMENT: a null grid, strides, dims or origin, a
+ * given output or colors without its strides, zero dims, an unknown format, a BITS grid with strides[0] != 1, a level that is
+ * not finite, no output at all, a factor outside 2 ... 8, min_count outside 1 ... f^3, values with a format other than U8 or an
+ * unknown value_mode, argb without colors, output strides that map two coarse voxels to one element, an output overlapping the
+ * grid, the colours or another output, a pointer that is not device memory of the context's device with its whole reach inside
+ * its allocation.  O2V_HIP_ERR_LIMIT: a dim above 65 536, origin[a] + dims[a] above 2^32 - both before the pointers are looked
+ * at.  The call runs on the context's stream and returns when the writes have landed (the caller must have finished writing
+ * grid and colors). */
+enum { O2V_HIP_DOWN_VALUE_MIN = 0, O2V_HIP_DOWN_VALUE_MAX = 1 };
+int o2v_hip_downsample_box(const uint32_t origin[3], const uint32_t dims[3], uint32_t factor, uint32_t out_origin[3], uint32_t out_dims[3]);
+int o2v_hip_downsample(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+                       const uint32_t origin[3], uint32_t factor, uint32_t min_count, uint32_t value_mode,
+                       const uint32_t *colors /* may be NULL */, const uint64_t color_strides[3], int16_t *count /* may be NULL */,
+                       const uint64_t count_strides[3], uint8_t *solid /* may be NULL */, const uint64_t solid_strides[3],
+                       uint8_t *values /* may be NULL */, const uint64_t value_strides[3], uint32_t *argb /* may be NULL */,
+                       const uint64_t argb_strides[3]);
+/* The device time of the last o2v_hip_downsample call's one launch, from events around it, in ms. */
+int o2v_hip_downsample_times(const o2v_hip_ctx *ctx, float out_ms[1]);
+
 int o2v_hip_get_timings(const o2v_hip_ctx *ctx, o2v_hip_timings *out);
 /* Per-kernel device times of the last o2v_hip_voxelize call made with O2V_HIP_FLAG_KERNEL_TIMES (else none): up to
  * max_entries entries are written, *out_count receives how many there are. */

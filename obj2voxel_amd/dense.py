@@ -18,7 +18,9 @@ grids back into (x, y, z, argb) records and voxel files (o2v_hip_gather_count / 
 voxel_faces / count_faces turn them into the blocky mesh of the voxel model (o2v_hip_faces_count / _write)
 and save_mesh writes that mesh, or extract_surface's, as STL, PLY or OBJ + MTL; nearest_voxel says which seed voxel of a grid is
 closest to every voxel and spread_colors carries the seeds' colours to the voxels that take them - the interior of a solid, a
-shell of a given thickness (o2v_hip_nearest_dense).
+shell of a given thickness (o2v_hip_nearest_dense); downsample merges blocks of f^3 voxels of any of these
+grids into a coarser grid - coverage counts, occupancy by a threshold, labels and mean colours: supersampling at 4x or 8x, LOD
+chains (o2v_hip_downsample).
 
 torch is imported first on purpose: the library must bind to the HIP runtime torch loaded (a process that loaded the library
 before torch holds two separate runtime copies, and this module refuses to work there).
@@ -53,6 +55,8 @@ MAX_FACES_EXTENT = 65536    # voxel_faces: origin + extent per axis: a coordinat
 _FACES_MERGE = {"none": hip.FACES_MERGE_NONE, "runs": hip.FACES_MERGE_RUNS, "rects": hip.FACES_MERGE_RECTS}
 MAX_GATHER_WORDS = 2 ** 31 - 1  # to_voxels / save_voxels: words of 64 voxels along x, ceil(nx / 64) * ny * nz
 MAX_NEAREST_D2 = 2 ** 31 - 2    # nearest_voxel / spread_colors: (nx-1)^2 + (ny-1)^2 + (nz-1)^2, the largest squared distance
+MIN_DOWN_FACTOR, MAX_DOWN_FACTOR = 2, 8  # downsample: fine voxels per coarse voxel and axis
+_DOWN_VALUES = {"min": hip.DOWN_VALUE_MIN, "max": hip.DOWN_VALUE_MAX}
 
 
 def _require_shared_runtime():
@@ -919,6 +923,113 @@ def nearest_coords(nearest):
     xyz = torch.stack((i - row * nx, row % ny, torch.div(row, ny, rounding_mode="floor")), dim=-1).to(torch.int32)
     xyz[nearest < 0] = -1
     return xyz
+
+
+# ---- downsampling: coverage, LODs, mean colours ---------------------------------------------------------
+
+def _limit_dim(dims):
+    """The size limit of downsample: no linear index, only the extent per axis."""
+    if max(dims) > MAX_CC_DIM:
+        raise ValueError(f"the grid's extent {dims} [x, y, z] is above {MAX_CC_DIM} along an axis")
+
+
+def _down_factor(factor):
+    if isinstance(factor, bool) or not isinstance(factor, numbers.Integral) or not MIN_DOWN_FACTOR <= factor <= MAX_DOWN_FACTOR:
+        raise ValueError(f"factor must be an integer {MIN_DOWN_FACTOR} ... {MAX_DOWN_FACTOR}, not {factor!r}")
+    return int(factor)
+
+
+def downsample_box(origin, shape, factor):
+    """(coarse origin (x, y, z), coarse shape (nz, ny, nx)) of the box of `shape` (nz, ny, nx) fine voxels whose voxel (0, 0, 0)
+    is `origin` (x, y, z) of the fine lattice, merged in blocks of factor^3 aligned to that lattice: per axis
+    floor(origin / factor) and ceil((origin + n) / factor) - floor(origin / factor).  Needs no device."""
+    factor = _down_factor(factor)
+    origin = _origin(origin)
+    shape = tuple(int(n) for n in shape)
+    if len(shape) != 3 or any(n < 1 for n in shape):
+        raise ValueError(f"shape {shape} must be three positive extents (nz, ny, nx)")
+    dims = shape[::-1]
+    if any(o + n > 2 ** 32 for o, n in zip(origin, dims)):
+        raise ValueError(f"origin {origin} + the extent {dims} [x, y, z] is above 2^32")
+    corigin = tuple(o // factor for o in origin)
+    cdims = tuple(-(-(o + n) // factor) - c for o, n, c in zip(origin, dims, corigin))
+    return corigin, cdims[::-1]
+
+
+def downsample(dv, grid, factor, *, level=None, origin=(0, 0, 0), reduce="any", count=False, values=None, colors=None, out=None,
+               out_count=None, out_values=None, out_colors=None):
+    """A dense grid merged into a coarser one on the voxelizer's device: blocks of factor^3 fine voxels,
+    aligned to the global lattice (the block of coarse voxel X covers the fine coordinates [X factor, (X + 1) factor) per axis;
+    what lies outside the grid's box is empty), become one coarse voxel each.  Returns (solid[, count][, values][, argb],
+    coarse_origin) in that order: solid bool, count int16, values uint8, argb int32, all indexed [z, y, x] over the box of
+    downsample_box(origin, grid's voxel shape, factor), and that box's origin (x, y, z).
+
+        fine, o = dense.voxelize_dense(dv, 2 * R)
+        half, o2 = dense.downsample(dv, fine, 2, origin=o)            # what voxelize_dense(dv, R, supersampling=2) gives
+        solid, n, o4 = dense.downsample(dv, fine, 4, origin=o, count=True)
+        coverage = n.float() / 4 ** 3                                  # the soft occupancy: count.float() / factor ** 3
+
+    grid:     as components takes it: bool or uint8 (solid where != 0), int32 (the words of fmt="bits": 32 voxels per word along
+              x) or float32 with `level` (solid where grid < level).  Any 3-D view; it is only read.
+    factor:   2 ... 8.
+    origin:   the fine-lattice coordinates (x, y, z) of grid[0, 0, 0]: voxelize_dense's origin.
+    reduce:   "any": a coarse voxel is solid if a fine voxel of its block is; "all": if all factor^3 are; "majority": if at
+              least ceil(factor^3 / 2) are; or that threshold itself, an integer 1 ... factor^3.
+    count:    True: also the number of solid fine voxels per block.
+    values:   "min" / "max" (bool / uint8 grids): also, where solid, the smallest / largest non-zero byte of the block, else 0.
+              With the labels of fill=True (1 surface, 2 interior) "min" gives "surface if any sub-voxel is surface".
+    colors:   an int32 tensor of the grid's voxel shape (any strides: an fmt="argb" grid): also, where solid, the mean per 8-bit
+              channel over the block's solid fine voxels, rounded half up, else 0.  Colours of voxels that are not solid are not used.
+    out, out_count, out_values, out_colors:  tensors of the coarse shape to write (bool or uint8, int16, uint8, int32; any
+              strides, as they are); else new contiguous ones.  out_count, out_values and out_colors ask for their output too.
+
+    Halving repeatedly - downsample(downsample(g, 2), 2) - gives "any of any" occupancy, which for reduce="any" is the occupancy
+    of one step by 4; with another threshold it is not, and its colours are a mean of means, not the mean: each level weighs its
+    solid children equally, however many fine voxels they stood for.  Take every level of a chain from the finest grid instead."""
+    factor = _down_factor(factor)
+    device, fmt, level, dims = _set_grid(dv, grid, level, _limit_dim)
+    cube = factor ** 3
+    if isinstance(reduce, str):
+        if reduce not in ("any", "majority", "all"):
+            raise ValueError(f"reduce must be 'any', 'majority', 'all' or an integer 1 ... {cube}, not {reduce!r}")
+        min_count = {"any": 1, "majority": (cube + 1) // 2, "all": cube}[reduce]
+    elif isinstance(reduce, bool) or not isinstance(reduce, numbers.Integral) or not 1 <= reduce <= cube:
+        raise ValueError(f"reduce must be 'any', 'majority', 'all' or an integer 1 ... {cube}, not {reduce!r}")
+    else:
+        min_count = int(reduce)
+    corigin, cshape = downsample_box(origin, (dims[2], dims[1], dims[0]), factor)
+    origin = _origin(origin)
+    if values is None and out_values is not None:
+        raise ValueError("out_values needs values='min' or 'max'")
+    if values is not None:
+        if values not in _DOWN_VALUES:
+            raise ValueError(f"values must be None, 'min' or 'max', not {values!r}")
+        if fmt != hip.GRID_U8:
+            raise ValueError(f"values needs a bool or uint8 grid, not {grid.dtype}")
+    if colors is None and out_colors is not None:
+        raise ValueError("out_colors needs colors")
+    if colors is not None:
+        _check_grid(colors, "colors", torch.int32, device, (dims[2], dims[1], dims[0]))
+    if not isinstance(count, bool):
+        raise ValueError(f"count must be True or False, not {count!r}")
+
+    def output(t, name, *dtypes):
+        """The caller's tensor for an output, checked (its dtype one of dtypes), or a new contiguous one of the first dtype."""
+        if t is None:
+            return torch.empty(cshape, dtype=dtypes[0], device=device)
+        _check_grid(t, name, t.dtype if isinstance(t, torch.Tensor) and t.dtype in dtypes else dtypes[0], device, cshape)
+        return t
+
+    solid = output(out, "out", torch.bool, torch.uint8)
+    n = output(out_count, "out_count", torch.int16) if count or out_count is not None else None
+    val = output(out_values, "out_values", torch.uint8) if values is not None else None
+    argb = output(out_colors, "out_colors", torch.int32) if colors is not None else None
+    _sync(device)   # (the caller's writes to grid, colors and the outputs have landed)
+    dv.downsample(grid.data_ptr(), fmt, _strides(grid), dims, 0.0 if level is None else level, origin, factor, min_count,
+                  _DOWN_VALUES.get(values, hip.DOWN_VALUE_MIN), _ptr(colors), None if colors is None else _strides(colors),
+                  _ptr(n), None if n is None else _strides(n), solid.data_ptr(), _strides(solid),
+                  _ptr(val), None if val is None else _strides(val), _ptr(argb), None if argb is None else _strides(argb))
+    return tuple(t for t in (solid, n, val, argb) if t is not None) + (corigin,)
 
 
 # ---- mesh files ------------------------------------------------------------------------------------------------------------------

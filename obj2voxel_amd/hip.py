@@ -34,6 +34,7 @@ GATHER_COLOR_CONSTANT, GATHER_COLOR_GRID, GATHER_COLOR_PALETTE = 0, 1, 2  # o2v_
 FACES_MERGE_NONE, FACES_MERGE_RUNS, FACES_MERGE_RECTS = 0, 1, 3  # o2v_hip_faces_count / _write merge modes
 NEAREST_SEED_ONE, NEAREST_VALUES_INSIDE = 1, 2  # o2v_hip_nearest_dense flags
 NEAREST_NO_LIMIT = 0x7FFFFFFF  # ... its max_dist2 without a limit
+DOWN_VALUE_MIN, DOWN_VALUE_MAX = 0, 1  # o2v_hip_downsample value modes
 ERR_BAD_ARGUMENT = 3
 ERR_LIMIT = 5
 ERR_IO = 6  # o2v_hip_gather_save: the file cannot be opened, is of no output type, or stopped taking voxels
@@ -169,6 +170,10 @@ def _bind():
     L.o2v_hip_nearest_scratch_bytes.argtypes = [C.c_void_p]
     L.o2v_hip_nearest_scratch_bytes.restype = C.c_uint64
     L.o2v_hip_nearest_times.argtypes = [C.c_void_p, C.c_void_p]
+    # ..., origin, factor, min_count, value_mode, 5 x (grid, strides): colors, count, solid, values, argb
+    L.o2v_hip_downsample.argtypes = _gather + [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 10
+    L.o2v_hip_downsample_box.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.o2v_hip_downsample_times.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_max_slab_layers.argtypes = [C.c_void_p, C.POINTER(_Params), C.POINTER(C.c_uint32)]
     return L
 
@@ -256,6 +261,19 @@ def _u32x3(v):
 
 def _u64x3(v):
     return None if v is None else (C.c_uint64 * 3)(*[int(x) for x in v])
+
+
+def downsample_box(origin, dims, factor):
+    """o2v_hip_downsample_box: (coarse origin, coarse dims), each (x, y, z), of the box origin + [0, dims) of the fine lattice
+    merged in blocks of factor^3 aligned to the global lattice.  Needs no device."""
+    co, cd = (C.c_uint32 * 3)(), (C.c_uint32 * 3)()
+    if any(not 0 <= int(v) < 2 ** 32 for v in tuple(origin) + tuple(dims)) or not 0 <= int(factor) < 2 ** 32:
+        raise DeviceError("o2v_hip_downsample_box failed (code %d): an argument does not fit 32 bits" % ERR_BAD_ARGUMENT)
+    rc = _bind().o2v_hip_downsample_box(_u32x3(origin), _u32x3(dims), int(factor), co, cd)
+    if rc != 0:
+        raise DeviceError("o2v_hip_downsample_box failed (code %d): the factor must be 2 ... 8, the dims positive and origin + dims at "
+                          "most 2^32" % rc)
+    return tuple(int(v) for v in co), tuple(int(v) for v in cd)
 
 
 class DeviceVoxelizer:
@@ -534,6 +552,24 @@ class DeviceVoxelizer:
         self._check(self._L.o2v_hip_nearest_dense(self._ctx, grid_ptr, fmt, _u64x3(strides), _u32x3(dims), float(level), flags, nearest_ptr,
                                                   _u64x3(nearest_strides), dist2_ptr, _u64x3(dist2_strides), values_ptr,
                                                   _u64x3(value_strides), max_dist2), "o2v_hip_nearest_dense")
+
+    def downsample(self, grid_ptr, fmt, strides, dims, level, origin, factor, min_count, value_mode=DOWN_VALUE_MIN, colors_ptr=None,
+                   color_strides=None, count_ptr=None, count_strides=None, solid_ptr=None, solid_strides=None, values_ptr=None,
+                   value_strides=None, argb_ptr=None, argb_strides=None):
+        """o2v_hip_downsample: the grid at device address grid_ptr (GRID_U8 / GRID_BITS / GRID_F32_BELOW with `level`), whose voxel
+        (0, 0, 0) is `origin` of the fine lattice, merged in blocks of factor^3 aligned to that lattice, over the coarse box of
+        downsample_box: the solid fine voxels per block (int16 at count_ptr), 1 where they are at least min_count (uint8 at
+        solid_ptr), the smallest / largest non-zero byte of such a block (DOWN_VALUE_MIN / _MAX, uint8 at values_ptr, U8 grids)
+        and the mean colour of its solid voxels (uint32 at argb_ptr, from the uint32 grid at colors_ptr).  At least one output;
+        strides in elements per axis x, y, z."""
+        self._check(self._L.o2v_hip_downsample(self._ctx, grid_ptr, fmt, _u64x3(strides), _u32x3(dims), float(level), _u32x3(origin), factor,
+                                               min_count, value_mode, colors_ptr, _u64x3(color_strides), count_ptr, _u64x3(count_strides),
+                                               solid_ptr, _u64x3(solid_strides), values_ptr, _u64x3(value_strides), argb_ptr,
+                                               _u64x3(argb_strides)), "o2v_hip_downsample")
+
+    def downsample_times(self):
+        """o2v_hip_downsample_times: the device time (ms) of the last downsample call's launch, as a 1-tuple."""
+        return self._stage_times("o2v_hip_downsample_times", 1)
 
     def nearest_scratch_bytes(self, dims):
         """o2v_hip_nearest_scratch_bytes: the context scratch a nearest_dense call over dims (x, y, z) needs."""

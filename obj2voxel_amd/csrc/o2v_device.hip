@@ -42,6 +42,10 @@
 //                              coordinates as payload) and its value spread over the grid; outside the pipeline
 //   K16 k_rects_*              O2V_HIP_FACES_MERGE_RECTS of K14's calls: equal runs of neighbouring rows stacked into
 //                              rectangles; outside the pipeline
+//   K17 k_downsample           o2v_hip_downsample: blocks of f^3 voxels of a dense grid merged into one coarse voxel each;
+//                              outside the pipeline
+//   K18 k_cross_*              o2v_hip_crossings_dense: signed crossing numbers of the triangles along x, y and z rays, from
+//                              both ends of every line (K6's exact column test, keeping the sign); outside the pipeline
 //   plan k_zhist               o2v_hip_plan_slabs: predicted hits per z layer -> work-balanced slabs for N GPUs
 // With the direct MAX path K1's counters reach the host while K2 runs, and only the stages that have work are enqueued
 // behind it.  N > 1 GPUs: o2v_hip_voxelize_sharded (bounds / work-histogram passes sharded over the ranks, RCCL).
@@ -96,6 +100,7 @@ namespace {
 #include "o2v_dev_k16_rects.hpp"
 #include "o2v_dev_k15_nearest.hpp"
 #include "o2v_dev_k17_downsample.hpp"
+#include "o2v_dev_k18_crossings.hpp"
 
 }  // namespace
 
@@ -227,6 +232,7 @@ struct Switches {
     bool no_slabs = env_on("O2V_NO_SLABS");                    // A/B: no new hit slabs, every hit pooled
     bool ray_no_skip = env_on("O2V_RAY_NO_SKIP");              // A/B: k_ray_cast walks every fine cell, no empty block is skipped
     bool cc_no_tiles = env_on("O2V_CC_NO_TILES");              // A/B: no k_cc_tiles, every adjacent pair is united in global memory
+    bool cross_no_tile = env_on("O2V_CROSS_NO_TILE");          // A/B: no k_cross_prefix_tile, a lane per line stores along the ray
     bool tiny_buffers = env_on("O2V_TEST_TINY_BUFFERS");       // test hook: minimal first capacities (every grow -> re-run path)
     bool block_list = env_on("O2V_TEST_BLOCK_LIST");           // test hook: the slab's block list for a mesh of any size
     int resolve_wgs_per_cu = env_int("O2V_RESOLVE_WGS_PER_CU", 0);  // A/B: workgroups per CU of resolve tier 1 (if > 0; else 2)
@@ -437,6 +443,12 @@ struct o2v_hip_ctx {
     } fa;
     // K17 (o2v_hip_downsample): no scratch; the time of the one launch
     StageTimes<1> ds_times;
+    // K18 (o2v_hip_crossings_dense): the delta grid of the box ([w][line]) and the totals per line of the axis in work, per
+    // triangle the inclusive end of its (triangle, line) items, per block of kBlock triangles its items' offset, the number of
+    // items, grown on demand; the times of the three axes
+    DevArray<int32_t> d_cr_delta, d_cr_totals;
+    DevArray<unsigned long long> d_cr_ends, d_cr_blocks, d_cr_ctr;
+    StageTimes<3> cr_times;
 
     // results of the last run
     uint64_t n_vox = 0;
@@ -4035,6 +4047,138 @@ int o2v_hip_downsample(o2v_hip_ctx *ctx, const void *grid, uint32_t format, cons
 int o2v_hip_downsample_times(const o2v_hip_ctx *ctx, float out_ms[1])
 {
     return ctx ? ctx->ds_times.read(out_ms) : O2V_HIP_ERR_BAD_ARGUMENT;
+}
+
+}  // extern "C"
+
+// ---- K18: signed crossing numbers ------------------------------------------------------------------------------------------
+
+namespace {
+
+// One axis of o2v_hip_crossings_dense, enqueued on the context's stream: the delta grid and totals cleared, the (triangle, line)
+// items enumerated and marked, the lines summed into dst.
+template <int A>
+int crossings_axis(o2v_hip_ctx *ctx, const Switches &sw, const Affine &xf, const uint32_t origin[3], const uint32_t dims[3], uint32_t ss,
+                   int32_t *dst, const uint64_t dst_strides[3], bool add)
+{
+    hipStream_t s = ctx->stream;
+    constexpr int U = (A + 1) % 3, V = (A + 2) % 3;
+    CrBox b{};
+    b.u0 = origin[U], b.v0 = origin[V], b.w0 = origin[A];
+    b.nu = dims[U], b.nv = dims[V], b.nw = dims[A];
+    b.ss = ss;
+    b.v_first = V == 0;   // (x first where a line has an x: the y rays' v)
+    b.n_lines = (uint64_t) b.nu * b.nv;
+    const uint64_t T = ctx->n_tris, n_blocks = (T + kBlock - 1) / kBlock;
+    O2V_CHECK(hipMemsetAsync(ctx->d_cr_delta.ptr, 0, b.n_lines * b.nw * sizeof(int32_t), s));
+    O2V_CHECK(hipMemsetAsync(ctx->d_cr_totals.ptr, 0, b.n_lines * sizeof(int32_t), s));
+    if (T) {
+        O2V_LAUNCH("k_cross_count", s, k_cross_count<A>, dim3((uint32_t) n_blocks), dim3(kBlock), 0, s, ctx->d_verts.ptr, T, xf, b, ctx->d_cr_ends.ptr,
+                   ctx->d_cr_blocks.ptr);
+        O2V_LAUNCH("k_fill_scan_blocks", s, k_fill_scan_blocks, dim3(1), dim3(kBlock), 0, s, ctx->d_cr_blocks.ptr, n_blocks, ctx->d_cr_ctr.ptr);
+        O2V_LAUNCH("k_fill_offsets", s, k_fill_offsets, dim3((uint32_t) n_blocks), dim3(kBlock), 0, s, ctx->d_cr_ends.ptr, T, ctx->d_cr_blocks.ptr);
+        O2V_LAUNCH("k_cross_mark", s, k_cross_mark<A>, dim3((uint32_t) ctx->num_cus * 8u), dim3(kBlock), 0, s, ctx->d_verts.ptr, T, xf, b,
+                   ctx->d_cr_ends.ptr, ctx->d_cr_ctr.ptr, ctx->d_cr_delta.ptr, ctx->d_cr_totals.ptr);
+    }
+    const dim3 line_blocks((uint32_t) ((b.n_lines + kBlock - 1) / kBlock));
+    const uint64_t s_first = dst_strides[b.v_first ? V : U], s_slow = dst_strides[b.v_first ? U : V], s_w = dst_strides[A];
+    // (the ray along dst's unit stride and the lines not: the lanes of k_cross_prefix would each write a row of their own)
+    if (s_w == 1u && s_first != 1u && !sw.cross_no_tile) {
+        if (add)
+            O2V_LAUNCH("k_cross_prefix_tile", s, k_cross_prefix_tile<true>, line_blocks, dim3(kBlock), 0, s, ctx->d_cr_delta.ptr, ctx->d_cr_totals.ptr, b,
+                       dst, s_first, s_slow);
+        else
+            O2V_LAUNCH("k_cross_prefix_tile", s, k_cross_prefix_tile<false>, line_blocks, dim3(kBlock), 0, s, ctx->d_cr_delta.ptr, ctx->d_cr_totals.ptr, b,
+                       dst, s_first, s_slow);
+    } else if (add)
+        O2V_LAUNCH("k_cross_prefix", s, k_cross_prefix<true>, line_blocks, dim3(kBlock), 0, s, ctx->d_cr_delta.ptr, ctx->d_cr_totals.ptr, b, dst, s_first,
+                   s_slow, s_w);
+    else
+        O2V_LAUNCH("k_cross_prefix", s, k_cross_prefix<false>, line_blocks, dim3(kBlock), 0, s, ctx->d_cr_delta.ptr, ctx->d_cr_totals.ptr, b, dst, s_first,
+                   s_slow, s_w);
+    O2V_CHECK(hipGetLastError());
+    return O2V_HIP_OK;
+}
+
+// An axis failed part-way: the runtime's error state is cleared, as o2v_hip_mesh_distance_dense does on its parity path (dst may
+// hold the earlier axes' sums by then).
+int axis_failed(o2v_hip_ctx *, int rc)
+{
+    (void) hipGetLastError();
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int o2v_hip_crossings_dense(o2v_hip_ctx *ctx, const o2v_hip_params *params, uint32_t axes, const uint32_t origin[3], const uint32_t dims[3],
+                            int32_t *dst, const uint64_t dst_strides[3])
+{
+    static const char fn[] = "o2v_hip_crossings_dense";
+    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
+    if (!params || !origin || !dims || !dst || !dst_strides) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
+    if (axes < 1u || axes > 7u) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "axes must be 1 ... 7 (bit 0 x, 1 y, 2 z), not " + std::to_string(axes));
+    const uint32_t ss = params->supersampling ? params->supersampling : 1u;
+    if (ss > 2u || params->resolution == 0u)
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "resolution must be positive and supersampling 1 or 2");
+    if (params->z_begin || params->z_end || params->x_begin || params->x_end || params->y_begin || params->y_end)
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "the slab and tile fields of params must be 0 (the box is origin, dims)");
+    for (int a = 0; a < 3; ++a) {
+        if (!dims[a] || (uint64_t) origin[a] + dims[a] > params->resolution)
+            return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "the box must have dims >= 1 and lie within the grid");
+        if (dims[a] > kMdMaxDim) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "a box of more than 65 535 voxels along an axis");
+    }
+    const uint64_t T = ctx->n_tris;
+    const uint32_t n_axes = (uint32_t) __builtin_popcount(axes);
+    // (a voxel's value is bounded by two rays per axis and one crossing per triangle and ray)
+    if (T > 0x7fffffffull / (2u * n_axes))
+        return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "2 x " + std::to_string(n_axes) + " rays x " + std::to_string(T) + " triangles is above 2^31 - 1");
+    O2V_CHECK(hipSetDevice(ctx->device));
+    ctx->ktimes_on = false;   // (no per-launch brackets here; o2v_hip_voxelize sets the flag again from its params)
+    int rc;
+    if ((rc = check_grid(ctx, fn, "dst", dst, dims, dst_strides, 4u, true))) return rc;
+    // the transform k_setup computes for these params, as o2v_hip_mesh_distance_dense takes it
+    Affine xf{};
+    if (T) {
+        const float *e = params->bounds_known ? params->bounds : ctx->mesh_bounds_hint;
+        xf = compute_mesh_transform(V3{e[0], e[1], e[2]}, V3{e[3], e[4], e[5]}, params->resolution * ss, params->unit_transform);
+    }
+    const uint64_t voxels = (uint64_t) dims[0] * dims[1] * dims[2];
+    uint64_t lines = 0;   // of the axis with the most
+    for (int a = 0; a < 3; ++a)
+        if (axes >> a & 1u) lines = std::max(lines, voxels / dims[a]);
+    if ((rc = grow_scratch(ctx, ctx->d_cr_delta, voxels, fn, "delta grid")) || (rc = grow_scratch(ctx, ctx->d_cr_totals, lines, fn, "line totals")) ||
+        (rc = grow_scratch(ctx, ctx->d_cr_ends, T, fn, "item ends")) || (rc = grow_scratch(ctx, ctx->d_cr_blocks, (T + kBlock - 1) / kBlock, fn, "block sums")) ||
+        (rc = grow_scratch(ctx, ctx->d_cr_ctr, 1u, fn, "counter")))
+        return rc;
+    hipStream_t s = ctx->stream;
+    const Switches sw = read_switches();
+    bool add = false;
+    O2V_CHECK(ctx->cr_times.mark(0, s));
+    if (axes & 1u) {
+        if ((rc = crossings_axis<0>(ctx, sw, xf, origin, dims, ss, dst, dst_strides, add))) return axis_failed(ctx, rc);
+        add = true;
+    }
+    O2V_CHECK(ctx->cr_times.mark(1, s));
+    if (axes & 2u) {
+        if ((rc = crossings_axis<1>(ctx, sw, xf, origin, dims, ss, dst, dst_strides, add))) return axis_failed(ctx, rc);
+        add = true;
+    }
+    O2V_CHECK(ctx->cr_times.mark(2, s));
+    if (axes & 4u)
+        if ((rc = crossings_axis<2>(ctx, sw, xf, origin, dims, ss, dst, dst_strides, add))) return axis_failed(ctx, rc);
+    O2V_CHECK(ctx->cr_times.mark(3, s));
+    O2V_CHECK(hipStreamSynchronize(s));
+    O2V_CHECK(ctx->cr_times.finish());
+    for (int a = 0; a < 3; ++a)
+        if (!(axes >> a & 1u)) ctx->cr_times.ms[a] = 0.f;
+    return O2V_HIP_OK;
+}
+
+int o2v_hip_crossings_times(const o2v_hip_ctx *ctx, float out_ms[3])
+{
+    return ctx ? ctx->cr_times.read(out_ms) : O2V_HIP_ERR_BAD_ARGUMENT;
 }
 
 }  // extern "C"

@@ -20,7 +20,9 @@ and save_mesh writes that mesh, or extract_surface's, as STL, PLY or OBJ + MTL; 
 closest to every voxel and spread_colors carries the seeds' colours to the voxels that take them - the interior of a solid, a
 shell of a given thickness (o2v_hip_nearest_dense); downsample merges blocks of f^3 voxels of any of these
 grids into a coarser grid - coverage counts, occupancy by a threshold, labels and mean colours: supersampling at 4x or 8x, LOD
-chains (o2v_hip_downsample).
+chains (o2v_hip_downsample); crossing_numbers counts the signed crossings of the triangles along the x, y
+and z rays through every voxel centre, from both ends, and winding_fill votes on them: a solid fill that keeps the overlap of
+parts pushed into each other and outvotes a ray that slips through a hole (o2v_hip_crossings_dense).
 
 torch is imported first on purpose: the library must bind to the HIP runtime torch loaded (a process that loaded the library
 before torch holds two separate runtime copies, and this module refuses to work there).
@@ -57,6 +59,7 @@ MAX_GATHER_WORDS = 2 ** 31 - 1  # to_voxels / save_voxels: words of 64 voxels al
 MAX_NEAREST_D2 = 2 ** 31 - 2    # nearest_voxel / spread_colors: (nx-1)^2 + (ny-1)^2 + (nz-1)^2, the largest squared distance
 MIN_DOWN_FACTOR, MAX_DOWN_FACTOR = 2, 8  # downsample: fine voxels per coarse voxel and axis
 _DOWN_VALUES = {"min": hip.DOWN_VALUE_MIN, "max": hip.DOWN_VALUE_MAX}
+_AXIS_BITS = {"x": hip.AXIS_X, "y": hip.AXIS_Y, "z": hip.AXIS_Z}  # crossing_numbers / winding_fill: the rays of an axis
 
 
 def _require_shared_runtime():
@@ -337,6 +340,115 @@ def mesh_distance(dv, resolution, *, band, signed=True, out=None, closest=None, 
                                _strides(o), _ptr(c), None if c is None else _strides(c), supersampling=supersampling,
                                unit_transform=unit_transform, bounds=bounds)
     return (out, closest, origin) if want_closest else (out, origin)
+
+
+def _axes_mask(axes):
+    """o2v_hip_crossings_dense's bits of a non-empty subset of "xyz" (any order, no letter twice)."""
+    if not isinstance(axes, str):
+        raise TypeError(f"axes must be a string of the letters x, y, z, not {type(axes).__name__}")
+    if not axes or any(a not in _AXIS_BITS for a in axes) or len(set(axes)) != len(axes):
+        raise ValueError(f"axes must be a non-empty subset of 'xyz', not {axes!r}")
+    return sum(_AXIS_BITS[a] for a in axes)
+
+
+def crossing_numbers(dv, resolution, *, axes="xyz", out=None, origin=None, supersampling=1, unit_transform=None, bounds=None,
+                     max_layers=None):
+    """The signed crossing numbers of `dv`'s mesh (set_mesh) at every voxel centre of a box: along each
+    axis of `axes` the triangles that the line through the centre crosses are counted with the sign of their orientation, below
+    the centre and above it, and the two counts of every axis are added.  Returns (S, origin), S int32 [z, y, x]: voxel
+    (x, y, z) is S[z - oz, y - oy, x - ox].  An outward-wound closed mesh gives 2 len(axes) inside and 0 outside, an
+    inward-wound one the negative; parts pushed into each other add up; a ray through a hole is off by one.
+
+    axes:  any non-empty subset of "xyz".
+    out:   an int32 3-D tensor [z, y, x] of any strides on the voxelizer's device; the box is `origin` (default 0) plus its
+           shape.  Without it the box is the grid from `origin` on, into a new contiguous tensor.
+    The transform is voxelize's for the same resolution, supersampling, unit_transform and bounds.  max_layers cuts the box
+    into z ranges of at most that many layers, one call each, written into the one tensor (the same bits as one call)."""
+    _require_shared_runtime()
+    mask = _axes_mask(axes)
+    _check_sampling(resolution, supersampling, max_layers)
+    device = _device(dv)
+    origin = tuple(int(v) for v in (origin or (0, 0, 0)))
+    if len(origin) != 3 or any(v < 0 or v >= resolution for v in origin):
+        raise ValueError(f"origin {origin} must be three voxel coordinates inside the grid")
+    if out is None:
+        out = torch.empty(tuple(resolution - v for v in origin[::-1]), dtype=torch.int32, device=device)
+    else:
+        _check_grid(out, "out", torch.int32, device)
+        if 0 in out.shape:
+            raise ValueError("out has an empty dimension")
+        if any(o + n > resolution for o, n in zip(origin, out.shape[::-1])):
+            raise ValueError(f"origin {origin} + out's extent {tuple(out.shape[::-1])} [x, y, z] reaches past the grid of {resolution}")
+    nz, ny, nx = out.shape
+    step = nz if max_layers is None else max_layers
+    _sync(device)   # (the caller's writes to out have landed)
+    for z in range(0, nz, step):
+        k = min(step, nz - z)
+        o = out[z:z + k]
+        dv.crossings_dense(resolution, mask, (origin[0], origin[1], origin[2] + z), (nx, ny, k), o.data_ptr(), _strides(o),
+                           supersampling=supersampling, unit_transform=unit_transform, bounds=bounds)
+    return out, origin
+
+
+def winding_fill(dv, resolution, *, axes="xyz", rule="nonzero", min_sum=None, box="grid", out=None, origin=None, supersampling=1,
+                 strategy="max", unit_transform=None, bounds=None, max_layers=None):
+    """A solid fill by a vote of axis rays: uint8 labels in the format of voxelize_dense(fmt="labels",
+    fill=True), so distance_transform, RayCaster, to_voxels, voxel_faces, downsample and spread_colors take the result as they
+    take fill=True's.  Returns (labels, origin).  Label 1 is the surface voxels of voxelize_dense(fmt="labels") for the same
+    arguments and box; label 2 every other voxel of the box whose crossing number S (crossing_numbers, the same axes) says
+    inside:
+
+    rule "nonzero":   |S| >= min_sum.  It does not depend on the mesh's winding, and it keeps the overlap of closed parts that
+                      are pushed into each other, which the z-parity rule of fill=True hollows out.
+    rule "positive":  S >= min_sum.  Inward-wound shells carve: a cavity wound inwards inside an outward-wound body is empty.
+    min_sum:          an integer in 1 ... 2 len(axes); the default len(axes) + 1 is more than half of the 2 len(axes) rays, so
+                      a ray that slips through a hole of an open mesh is outvoted.
+    box, out, origin, supersampling, strategy, unit_transform, bounds, max_layers are voxelize_dense's; every voxel of `out`
+    is written: it is cleared once the arguments have been checked, so an error raised after that by a device call (a voxel
+    outside the tensor's box, an `out` smaller than the tight box) leaves it cleared.  With box="tight" the box is the surface's
+    tight box.  The thresholding is plain torch on the two grids."""
+    _require_shared_runtime()
+    _axes_mask(axes)
+    if rule not in ("nonzero", "positive"):
+        raise ValueError(f"rule must be 'nonzero' or 'positive', not {rule!r}")
+    if min_sum is None:
+        min_sum = len(axes) + 1
+    if isinstance(min_sum, bool) or not isinstance(min_sum, numbers.Integral):
+        raise TypeError(f"min_sum must be an integer, not {min_sum!r}")
+    if not 1 <= min_sum <= 2 * len(axes):
+        raise ValueError(f"min_sum must be 1 ... {2 * len(axes)} for axes {axes!r}, not {min_sum}")
+    if box not in ("grid", "tight"):
+        raise ValueError(f"box must be 'grid' or 'tight', not {box!r}")
+    if strategy not in STRATEGIES:
+        raise ValueError(f"strategy must be 'max' or 'blend', not {strategy!r}")
+    _check_sampling(resolution, supersampling, max_layers)
+    if resolution * supersampling > MAX_SAMPLES:
+        raise ValueError(f"resolution x supersampling = {resolution * supersampling} is above {MAX_SAMPLES}: x / y tiles are not "
+                         "supported by the dense path")
+    if box == "tight" and origin is not None:
+        raise ValueError("origin is given by the voxels with box='tight'")
+    device = _device(dv)
+    if out is not None:
+        _check_grid(out, "out", torch.uint8, device)
+        if 0 in out.shape:
+            raise ValueError("out has an empty dimension")
+        if box == "grid":
+            o = tuple(int(v) for v in (origin or (0, 0, 0)))
+            if len(o) != 3 or any(v < 0 for v in o) or any(a + n > resolution for a, n in zip(o, out.shape[::-1])):
+                raise ValueError(f"origin {o} + out's extent {tuple(out.shape[::-1])} [x, y, z] reaches past the grid of {resolution}")
+        out.zero_()
+    labels, origin = voxelize_dense(dv, resolution, fmt="labels", box=box, out=out, origin=origin, supersampling=supersampling,
+                                    strategy=strategy, unit_transform=unit_transform, bounds=bounds, max_layers=max_layers)
+    if 0 in labels.shape:
+        return labels, origin
+    # (an `out` larger than the tight box may reach past the grid: the part within it)
+    ext = [min(n, resolution - o) for n, o in zip(labels.shape, origin[::-1])]
+    part = labels[:ext[0], :ext[1], :ext[2]]
+    S, _ = crossing_numbers(dv, resolution, axes=axes, origin=origin, supersampling=supersampling, unit_transform=unit_transform,
+                            bounds=bounds, max_layers=max_layers, out=torch.empty(tuple(part.shape), dtype=torch.int32, device=device))
+    inside = (S.abs() >= min_sum) if rule == "nonzero" else (S >= min_sum)
+    part.masked_fill_(inside & (part == 0), 2)
+    return labels, origin
 
 
 def extract_surface(dv, field, level=0.0, *, origin=(0, 0, 0), transform=None, supersampling=1):

@@ -35,6 +35,7 @@ FACES_MERGE_NONE, FACES_MERGE_RUNS, FACES_MERGE_RECTS = 0, 1, 3  # o2v_hip_faces
 NEAREST_SEED_ONE, NEAREST_VALUES_INSIDE = 1, 2  # o2v_hip_nearest_dense flags
 NEAREST_NO_LIMIT = 0x7FFFFFFF  # ... its max_dist2 without a limit
 DOWN_VALUE_MIN, DOWN_VALUE_MAX = 0, 1  # o2v_hip_downsample value modes
+AXIS_X, AXIS_Y, AXIS_Z = 1, 2, 4  # o2v_hip_crossings_dense: the bits of `axes`
 ERR_BAD_ARGUMENT = 3
 ERR_LIMIT = 5
 ERR_IO = 6  # o2v_hip_gather_save: the file cannot be opened, is of no output type, or stopped taking voxels
@@ -174,6 +175,8 @@ def _bind():
     L.o2v_hip_downsample.argtypes = _gather + [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 10
     L.o2v_hip_downsample_box.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     L.o2v_hip_downsample_times.argtypes = [C.c_void_p, C.c_void_p]
+    L.o2v_hip_crossings_dense.argtypes = [C.c_void_p, C.POINTER(_Params), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.o2v_hip_crossings_times.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_max_slab_layers.argtypes = [C.c_void_p, C.POINTER(_Params), C.POINTER(C.c_uint32)]
     return L
 
@@ -570,6 +573,19 @@ class DeviceVoxelizer:
     def downsample_times(self):
         """o2v_hip_downsample_times: the device time (ms) of the last downsample call's launch, as a 1-tuple."""
         return self._stage_times("o2v_hip_downsample_times", 1)
+
+    def crossings_dense(self, resolution, axes, origin, dims, dst_ptr, dst_strides, *, supersampling=1, unit_transform=None, bounds=None):
+        """o2v_hip_crossings_dense: the signed crossing numbers of the context's triangles along the rays of `axes` (AXIS_X |
+        AXIS_Y | AXIS_Z), from both ends of every line, at the voxel centres of the box origin + [0, dims), into int32 at device
+        address dst_ptr; strides in elements, origin, dims and strides per axis x, y, z."""
+        p = self._params(resolution, supersampling, 0, unit_transform, bounds, (0, 0))
+        self._check(self._L.o2v_hip_crossings_dense(self._ctx, C.byref(p), int(axes), _u32x3(origin), _u32x3(dims), dst_ptr, _u64x3(dst_strides)),
+                    "o2v_hip_crossings_dense")
+
+    def crossings_times(self):
+        """o2v_hip_crossings_times: the device times (ms) of the last crossings_dense call's x, y and z rays (0 for an axis not
+        asked for)."""
+        return self._stage_times("o2v_hip_crossings_times")
 
     def nearest_scratch_bytes(self, dims):
         """o2v_hip_nearest_scratch_bytes: the context scratch a nearest_dense call over dims (x, y, z) needs."""

@@ -821,6 +821,50 @@ int o2v_hip_crossings_dense(o2v_hip_ctx *ctx, const o2v_hip_params *params, uint
 /* The device times (ms) of the last o2v_hip_crossings_dense call per axis x, y, z; 0 for an axis not asked for. */
 int o2v_hip_crossings_times(const o2v_hip_ctx *ctx, float out_ms[3]);
 
+/* ---- per-label statistics of a dense grid ---------------------------------------------------------------
+ *
+ * One read of a label grid gives, per value L = 0 ... n_labels, the number of voxels that hold L, their bounding box, the sums of
+ * their coordinates and of the coordinates' products, and their exposed faces: what a crop, a centroid, a covariance, an inertia
+ * tensor and a surface area per part are derived from.
+ *
+ * The grid.  labels is device memory of the context's device, only read; format O2V_HIP_LABELS_I32 (int32 elements: what
+ * o2v_hip_components_dense writes) or O2V_HIP_LABELS_U8 (uint8: occupancy, the labels of O2V_HIP_FLAG_FILL_INTERIOR, of a flood);
+ * voxel (x, y, z) of the box dims = (nx, ny, nz) is labels[x * strides[0] + y * strides[1] + z * strides[2]] (elements, any order;
+ * a stride may be 0).  origin[3] holds the global coordinates of voxel (0, 0, 0): a voxel's coordinates are origin + index.
+ * A voxel whose value is negative or above n_labels adds nothing to any row; *out_outside receives how many there are.
+ *
+ * The table.  int64 [n_labels + 1][O2V_HIP_STATS_COLUMNS], contiguous, device memory; row L is for the value L, and row 0 is
+ * treated like every other row.  The call writes every element.  `which` is a set of O2V_HIP_STATS_* bits; the count is always
+ * made, and the columns of a group that is not asked for hold 0:
+ *    0        the number of voxels.
+ *    1 - 3    BOX: the smallest x, y, z;  4 - 6: the largest x, y, z.  Both inclusive, in global coordinates.  A row without
+ *             voxels holds min = 2^31 - 1 and max = -1.
+ *    7 - 9    SUMS: the sums of x, y, z.
+ *    10 - 15  MOMENTS: the sums of xx, yy, zz, xy, xz, yz.
+ *    16       FACES: the sum, over the row's voxels, of the voxel's six neighbours whose value differs from its own (the values
+ *             as they are, counted or not); a neighbour outside the box differs.  On a 0 / 1 grid table[1][16] is
+ *             o2v_hip_faces_count with O2V_HIP_FACES_MERGE_NONE.
+ * Coordinates are the integer voxel coordinates; the + 0.5 of the voxel's centre is added by whoever derives a centroid.
+ * No overflow: with every coordinate below 2^16 and fewer than 2^31 voxels (the limits below), a product of two coordinates is at
+ * most (2^16 - 1)^2 = 2^32 - 131 071, and a sum of at most 2^31 - 1 of them is at most (2^32 - 131 071) (2^31 - 1) < 2^63.
+ * Every column is an integer sum, minimum or maximum: the table does not depend on any order, one run equals another bit for bit.
+ *
+ * Refused before anything is launched, table and *out_outside untouched.  O2V_HIP_ERR_BAD_ARGUMENT: a null argument, zero dims,
+ * an unknown format, an unknown bit in which, n_labels above 255 with U8, a table that is not 8-byte aligned or an I32 grid that
+ * is not 4-byte aligned, a table that overlaps the grid, a pointer that is not
+ * device memory of the context's device with its whole reach inside its allocation.  O2V_HIP_ERR_LIMIT (before the pointers are
+ * looked at): a dim above 65 536, origin[a] + dims[a] above 65 536, more than 2^31 - 1 voxels, n_labels above 2^31 - 2.
+ * O2V_HIP_ERR_OUT_OF_MEMORY, with the context usable, if the context's scratch (one counter) cannot be allocated.  The call runs on
+ * the context's stream and returns when the table is written (the caller must have finished writing labels). */
+enum { O2V_HIP_LABELS_I32 = 0, O2V_HIP_LABELS_U8 = 1 };
+enum { O2V_HIP_STATS_BOX = 1, O2V_HIP_STATS_SUMS = 2, O2V_HIP_STATS_MOMENTS = 4, O2V_HIP_STATS_FACES = 8 };
+enum { O2V_HIP_STATS_COLUMNS = 17 };
+int o2v_hip_label_stats(o2v_hip_ctx *ctx, const void *labels, uint32_t format, const uint64_t strides[3], const uint32_t dims[3],
+                        const uint32_t origin[3], uint32_t n_labels, uint32_t which, int64_t *table, uint64_t *out_outside);
+/* The device times (ms) of the last o2v_hip_label_stats call, from events around them: [0] the table's initialisation, [1] the
+ * pass over the grid. */
+int o2v_hip_label_stats_times(const o2v_hip_ctx *ctx, float out_ms[2]);
+
 int o2v_hip_get_timings(const o2v_hip_ctx *ctx, o2v_hip_timings *out);
 /* Per-kernel device times of the last o2v_hip_voxelize call made with O2V_HIP_FLAG_KERNEL_TIMES (else none): up to
  * max_entries entries are written, *out_count receives how many there are. */

@@ -82,6 +82,25 @@ __device__ __forceinline__ uint32_t ray_read16(const RaySource &src, uint64_t at
     return bits;
 }
 
+// The n <= 16 / Elem elements x0 .. x0 + n - 1 (x0 a multiple of 16 / Elem) of the row at element offset `at`, of Elem = 1 or 4
+// bytes each, as they are: element i in bits [8 Elem i, 8 Elem (i + 1)) of the 16 bytes, zero behind the n-th.  Vec as above.
+// (K19 reads its label grid through it.)
+template <uint32_t Elem, bool Vec>
+__device__ __forceinline__ uint4 ray_read16_raw(const RaySource &src, uint64_t at, uint32_t x0, uint32_t n)
+{
+    constexpr uint32_t K = 16u / Elem;
+    const uint8_t *p = static_cast<const uint8_t *>(src.p) + at * Elem;
+    if (Vec && n == K) return *reinterpret_cast<const uint4 *>(p + (uint64_t) x0 * Elem);
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (uint32_t i = 0; i < K; ++i)
+        if (i < n) {
+            const uint8_t *q = p + (uint64_t) (x0 + i) * src.s0 * Elem;
+            w[i * Elem / 4u] |= Elem == 4u ? *reinterpret_cast<const uint32_t *>(q) : (uint32_t) *q << (8u * (i & 3u));
+        }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
 template <uint32_t Format, bool Vec>
 __global__ __launch_bounds__(kBlock) void k_ray_build(RaySource src, RayGrid g, unsigned long long *__restrict__ m0, unsigned long long *__restrict__ m1)
 {

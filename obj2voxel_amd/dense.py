@@ -22,11 +22,16 @@ shell of a given thickness (o2v_hip_nearest_dense); downsa
 grids into a coarser grid - coverage counts, occupancy by a threshold, labels and mean colours: supersampling at 4x or 8x, LOD
 chains (o2v_hip_downsample); crossing_numbers counts the signed crossings of the triangles along the x, y
 and z rays through every voxel centre, from both ends, and winding_fill votes on them: a solid fill that keeps the overlap of
-parts pushed into each other and outvotes a ray that slips through a hole (o2v_hip_crossings_dense).
+parts pushed into each other and outvotes a ray that slips through a hole (o2v_hip_crossings_dense, DESIGN.md section 21);
+label_stats reads a label grid once and gives, per label, the voxel count, the bounding box, the coordinate sums, the second
+moments and the exposed faces as exact integers, and component_stats, centroids, covariances, mass_properties, keep_largest and
+crop are built on them: the parts of a scan cropped one by one, the largest body kept, a solid's volume, centre of mass and inertia
+tensor (o2v_hip_label_stats).
 
 torch is imported first on purpose: the library must bind to the HIP runtime torch loaded (a process that loaded the library
 before torch holds two separate runtime copies, and this module refuses to work there).
 """
+import dataclasses
 import math
 import numbers
 import os
@@ -60,6 +65,8 @@ MAX_NEAREST_D2 = 2 ** 31 - 2    # nearest_voxel / spread_colors: (nx-1)^2 + (ny-
 MIN_DOWN_FACTOR, MAX_DOWN_FACTOR = 2, 8  # downsample: fine voxels per coarse voxel and axis
 _DOWN_VALUES = {"min": hip.DOWN_VALUE_MIN, "max": hip.DOWN_VALUE_MAX}
 _AXIS_BITS = {"x": hip.AXIS_X, "y": hip.AXIS_Y, "z": hip.AXIS_Z}  # crossing_numbers / winding_fill: the rays of an axis
+MAX_STATS_EXTENT = 65536    # label_stats: origin + extent per axis: with fewer than 2^31 voxels no sum reaches 2^63
+MAX_STATS_LABELS = 2 ** 31 - 2  # ... and its highest label
 
 
 def _require_shared_runtime():
@@ -1142,6 +1149,194 @@ def downsample(dv, grid, factor, *, level=None, origin=(0, 0, 0), reduce="any", 
                   _ptr(n), None if n is None else _strides(n), solid.data_ptr(), _strides(solid),
                   _ptr(val), None if val is None else _strides(val), _ptr(argb), None if argb is None else _strides(argb))
     return tuple(t for t in (solid, n, val, argb) if t is not None) + (corigin,)
+
+
+# ---- per-label statistics -------------------------------------------------------------------------------
+
+@dataclasses.dataclass(frozen=True)
+class LabelStats:
+    """What label_stats returns: row L of every tensor is for the value L of the grid, row 0 like every other; all int64, on the
+    grid's device, exact.  A field that was not asked for is None."""
+    count: torch.Tensor      # [n + 1]: the voxels that hold L
+    lo: torch.Tensor         # [n + 1, 3]: the smallest (x, y, z), global coordinates; 0 for a row without voxels
+    hi: torch.Tensor         # [n + 1, 3]: the largest (x, y, z) + 1 - exclusive -; 0 for a row without voxels
+    sum: torch.Tensor        # [n + 1, 3]: the sums of x, y, z (integer voxel coordinates, without the centre's + 0.5)
+    moment: torch.Tensor     # [n + 1, 6]: the sums of xx, yy, zz, xy, xz, yz
+    faces: torch.Tensor      # [n + 1]: the voxel faces of L whose neighbour holds another value or lies outside the box
+    outside: int             # the voxels whose value is negative or above n: they are in no row
+    origin: tuple            # (x, y, z) of grid[0, 0, 0]
+
+    @property
+    def n(self):
+        return self.count.shape[0] - 1
+
+
+def label_stats(dv, labels, n=None, *, origin=(0, 0, 0), box=True, sums=True, moments=False, faces=False):
+    """Per value of a label grid, in one read of it on the voxelizer's device: a LabelStats with the
+    count, the bounding box (box), the coordinate sums (sums), the sums of the coordinates' products (moments) and the exposed
+    faces (faces) of every value 0 ... n.  Everything is an integer and exact; one run equals another bit for bit.
+
+        labels, n = dense.components(dv, grid)
+        st = dense.label_stats(dv, labels, n, moments=True)
+        dense.centroids(st)[1:]                      # float64 [n, 3], voxel centres
+        part, o = dense.crop(grid, st, 3)            # the view of grid that holds component 3, and its origin
+
+    labels:  int32 (what components returns), uint8 (the labels of fill=True, of solidify, of flood) or bool (occupancy: row 1
+             is the solid, row 0 the empty space); any 3-D view [z, y, x]; it is only read.
+    n:       the highest value that is counted; None: 255 for uint8, 1 for bool, max(labels.max(), 0) for int32 (a device
+             reduction and a wait).  A voxel whose value is negative or above n is counted in `outside` and nowhere else.
+    origin:  (x, y, z) of labels[0, 0, 0]; the box and the sums are in these global coordinates.  origin + extent may not be
+             above 65 536 on any axis, nor the grid hold more than 2^31 - 1 voxels: then no sum can reach 2^63."""
+    _require_shared_runtime()
+    device = _device(dv)
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 3:
+        raise ValueError("labels must be a 3-D tensor [z, y, x]")
+    if labels.dtype not in (torch.int32, torch.uint8, torch.bool):
+        raise TypeError(f"labels must be int32, uint8 or bool, not {labels.dtype}")
+    _check_grid(labels, "labels", labels.dtype, device)
+    if 0 in labels.shape:
+        raise ValueError("labels has an empty dimension")
+    for name, flag in (("box", box), ("sums", sums), ("moments", moments), ("faces", faces)):
+        if not isinstance(flag, bool):
+            raise ValueError(f"{name} must be True or False, not {flag!r}")
+    origin = _origin(origin)
+    nz, ny, nx = labels.shape
+    dims = (nx, ny, nz)
+    _limit_voxels(dims)
+    if any(o + d > MAX_STATS_EXTENT for o, d in zip(origin, dims)):
+        raise ValueError(f"origin {origin} + the grid's extent {dims} [x, y, z] is above {MAX_STATS_EXTENT}")
+    top = MAX_STATS_LABELS if labels.dtype == torch.int32 else 1 if labels.dtype == torch.bool else 255
+    if n is None:
+        n = max(int(labels.max()), 0) if labels.dtype == torch.int32 else top
+    elif isinstance(n, bool) or not isinstance(n, numbers.Integral) or not 0 <= n <= top:
+        raise ValueError(f"n must be an integer 0 ... {top} for {labels.dtype} labels, not {n!r}")
+    n = int(n)
+    which = (hip.STATS_BOX if box else 0) | (hip.STATS_SUMS if sums else 0) | (hip.STATS_MOMENTS if moments else 0) | (hip.STATS_FACES if faces else 0)
+    table = torch.empty((n + 1, hip.STATS_COLUMNS), dtype=torch.int64, device=device)
+    _sync(device)   # (the caller's writes to labels have landed)
+    outside = dv.label_stats(labels.data_ptr(), hip.LABELS_I32 if labels.dtype == torch.int32 else hip.LABELS_U8, _strides(labels), dims, origin,
+                             n, which, table.data_ptr())
+    count = table[:, 0]
+    lo = hi = None
+    if box:
+        some = (count > 0)[:, None]
+        lo, hi = torch.where(some, table[:, 1:4], 0), torch.where(some, table[:, 4:7] + 1, 0)
+    return LabelStats(count=count, lo=lo, hi=hi, sum=table[:, 7:10] if sums else None, moment=table[:, 10:16] if moments else None,
+                      faces=table[:, 16] if faces else None, outside=outside, origin=origin)
+
+
+def component_stats(dv, grid, *, level=None, connectivity=6, background=False, **which):
+    """(labels, n, stats): components(dv, grid, ...) and label_stats of its labels; `which` are label_stats' origin, box, sums,
+    moments and faces.  Row 0 of stats is what is not in the set."""
+    labels, n = components(dv, grid, level=level, connectivity=connectivity, background=background)
+    return labels, n, label_stats(dv, labels, n, **which)
+
+
+def _need(stats, *fields):
+    if not isinstance(stats, LabelStats):
+        raise TypeError("stats must be a LabelStats, what label_stats returns")
+    for f in fields:
+        if getattr(stats, f) is None:
+            raise ValueError(f"the statistics were made without {f}: ask label_stats for " + {"lo": "box", "hi": "box", "sum": "sums", "moment": "moments"}[f])
+
+
+def centroids(stats):
+    """float64 [n + 1, 3]: the mean voxel centre (x, y, z) of every row, sum / count + 0.5; NaN for a row without voxels."""
+    _need(stats, "sum")
+    count = stats.count.to(torch.float64)[:, None]
+    return torch.where(count > 0, stats.sum.to(torch.float64) / count + 0.5, float("nan"))
+
+
+def _second_moments(moment):
+    """[..., 6] sums of xx, yy, zz, xy, xz, yz as symmetric matrices [..., 3, 3]."""
+    m = moment
+    return torch.stack([m[..., 0], m[..., 3], m[..., 4], m[..., 3], m[..., 1], m[..., 5], m[..., 4], m[..., 5], m[..., 2]], dim=-1).reshape(m.shape[:-1] + (3, 3))
+
+
+def covariances(stats):
+    """float64 [n + 1, 3, 3]: the covariance of the positions of every row's solid about its centroid, the row taken as a union of
+    unit cubes: E[p p^T] - E[p] E[p]^T over the voxel coordinates, plus the cube's own 1/12 on the diagonal.  NaN for a row
+    without voxels."""
+    _need(stats, "sum", "moment")
+    count = stats.count.to(torch.float64)
+    mean = stats.sum.to(torch.float64) / count[:, None]
+    cov = _second_moments(stats.moment.to(torch.float64)) / count[:, None, None] - mean[:, :, None] * mean[:, None, :]
+    cov = cov + torch.eye(3, dtype=torch.float64, device=cov.device) / 12.0
+    return torch.where((count > 0)[:, None, None], cov, float("nan"))
+
+
+def mass_properties(stats, rows, *, transform=None, supersampling=1):
+    """(volume, centre of mass float64 [3], inertia tensor float64 [3, 3] about that centre) of the union of the rows `rows` at
+    unit density - rows=(1, 2) for the labels of a filled model, surface and interior.  The body is the union of the rows' unit
+    cubes, so each voxel brings its own 1/12 per axis.
+
+    transform:  None: voxel units.  dv.transform() (12 floats, model to sample space) with the run's supersampling: model space,
+                p -> A^-1 (supersampling * p - t) as extract_surface maps its vertices, in float64; the volume scales by the
+                |det| of that map and the inertia tensor with it."""
+    _need(stats, "sum", "moment")
+    rows = [int(r) for r in rows]
+    if not rows or any(not 0 <= r <= stats.n for r in rows) or len(set(rows)) != len(rows):
+        raise ValueError(f"rows {rows} must be distinct rows 0 ... {stats.n}, at least one")
+    if supersampling not in (1, 2):
+        raise ValueError("supersampling must be 1 or 2")
+    idx = torch.tensor(rows, dtype=torch.int64, device=stats.count.device)
+    count = int(stats.count[idx].sum())
+    s1 = stats.sum[idx].sum(dim=0).cpu().to(torch.float64)            # (exact integers up to here)
+    s2 = _second_moments(stats.moment[idx].sum(dim=0)).cpu().to(torch.float64)
+    if count == 0:
+        nan = float("nan")
+        return 0.0, torch.full((3,), nan, dtype=torch.float64), torch.full((3, 3), nan, dtype=torch.float64)
+    v = float(count)
+    centre = s1 / v + 0.5
+    # the second moments of the cubes about the origin: sum (c c^T) over the centres c = p + 0.5, and V / 12 on the diagonal
+    half = 0.5 * (s1[:, None] + s1[None, :]) + 0.25 * v
+    about_origin = s2 + half + torch.eye(3, dtype=torch.float64) * (v / 12.0)
+    central = about_origin - v * centre[:, None] * centre[None, :]
+    volume = v
+    if transform is not None:
+        transform = torch.as_tensor(transform, dtype=torch.float64).reshape(-1)
+        if transform.numel() != 12:
+            raise ValueError("transform must hold 12 numbers: a row-major 3 x 3 matrix, then the translation")
+        inverse = torch.linalg.inv(transform[:9].reshape(3, 3))
+        b = inverse * float(supersampling)                              # the linear part of voxel -> model
+        det = abs(float(torch.linalg.det(b)))
+        centre = inverse @ (centre * supersampling - transform[9:])
+        central = det * (b @ central @ b.T)
+        volume = v * det
+    inertia = torch.eye(3, dtype=torch.float64) * torch.trace(central) - central
+    return volume, centre, inertia
+
+
+def keep_largest(dv, grid, k=1, *, level=None, connectivity=26):
+    """bool [z, y, x]: the solid voxels of the k largest components of the grid; of components of one size the one with the
+    smaller label - the first in [z, y, x] order - comes first.  The empty space (row 0) is never a candidate; with fewer than k
+    components all are kept."""
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or k < 1:
+        raise ValueError(f"k must be an integer >= 1, not {k!r}")
+    labels, n = components(dv, grid, level=level, connectivity=connectivity)
+    stats = label_stats(dv, labels, n, box=False, sums=False)
+    order = torch.sort(stats.count[1:], descending=True, stable=True).indices[:k] + 1   # (stable: ties stay in label order)
+    keep = torch.zeros(n + 1, dtype=torch.bool, device=labels.device)
+    keep[order] = True
+    return keep[labels.to(torch.int64)]
+
+
+def crop(grid, stats, label):
+    """(view, origin): the part of `grid` - any tensor [z, y, x] of the shape the statistics were made of - inside the bounding
+    box of `label`, as a view, and the global (x, y, z) of its voxel (0, 0, 0).  An empty view at the grid's origin for a row
+    without voxels."""
+    _need(stats, "lo", "hi")
+    if isinstance(label, bool) or not isinstance(label, numbers.Integral) or not 0 <= label <= stats.n:
+        raise ValueError(f"label must be a row 0 ... {stats.n}, not {label!r}")
+    if not isinstance(grid, torch.Tensor) or grid.dim() != 3:
+        raise ValueError("grid must be a 3-D tensor [z, y, x]")
+    lo, hi = stats.lo[label].tolist(), stats.hi[label].tolist()
+    if lo == hi:
+        return grid[:0, :0, :0], stats.origin
+    ox, oy, oz = stats.origin
+    if hi[0] - ox > grid.shape[2] or hi[1] - oy > grid.shape[1] or hi[2] - oz > grid.shape[0]:
+        raise ValueError(f"grid's shape {tuple(grid.shape)} does not hold the box of label {label}")
+    return grid[lo[2] - oz:hi[2] - oz, lo[1] - oy:hi[1] - oy, lo[0] - ox:hi[0] - ox], tuple(lo)
 
 
 # ---- mesh files ------------------------------------------------------------------------------------------------------------------

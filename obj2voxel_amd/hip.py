@@ -36,6 +36,9 @@ NEAREST_SEED_ONE, NEAREST_VALUES_INSIDE = 1, 2  # o2v_hip_nearest_dense flags
 NEAREST_NO_LIMIT = 0x7FFFFFFF  # ... its max_dist2 without a limit
 DOWN_VALUE_MIN, DOWN_VALUE_MAX = 0, 1  # o2v_hip_downsample value modes
 AXIS_X, AXIS_Y, AXIS_Z = 1, 2, 4  # o2v_hip_crossings_dense: the bits of `axes`
+LABELS_I32, LABELS_U8 = 0, 1  # o2v_hip_label_stats formats
+STATS_BOX, STATS_SUMS, STATS_MOMENTS, STATS_FACES = 1, 2, 4, 8  # ... the bits of `which`
+STATS_COLUMNS = 17  # ... the int64 columns of a row of its table
 ERR_BAD_ARGUMENT = 3
 ERR_LIMIT = 5
 ERR_IO = 6  # o2v_hip_gather_save: the file cannot be opened, is of no output type, or stopped taking voxels
@@ -177,6 +180,10 @@ def _bind():
     L.o2v_hip_downsample_times.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_crossings_dense.argtypes = [C.c_void_p, C.POINTER(_Params), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.o2v_hip_crossings_times.argtypes = [C.c_void_p, C.c_void_p]
+    # ctx, labels, format, strides, dims, origin, n_labels, which, table, out_outside
+    L.o2v_hip_label_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                      C.POINTER(C.c_uint64)]
+    L.o2v_hip_label_stats_times.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_max_slab_layers.argtypes = [C.c_void_p, C.POINTER(_Params), C.POINTER(C.c_uint32)]
     return L
 
@@ -586,6 +593,21 @@ class DeviceVoxelizer:
         """o2v_hip_crossings_times: the device times (ms) of the last crossings_dense call's x, y and z rays (0 for an axis not
         asked for)."""
         return self._stage_times("o2v_hip_crossings_times")
+
+    def label_stats(self, labels_ptr, fmt, strides, dims, origin, n_labels, which, table_ptr):
+        """o2v_hip_label_stats: per value 0 ... n_labels of the label grid at device address labels_ptr (LABELS_I32 / LABELS_U8;
+        strides in elements, strides, dims and origin per axis x, y, z) a row of STATS_COLUMNS int64 at device address table_ptr
+        ([n_labels + 1, 17], contiguous): the count, and of `which` (STATS_BOX | STATS_SUMS | STATS_MOMENTS | STATS_FACES) the
+        inclusive box in global coordinates, the sums of x, y, z, of xx, yy, zz, xy, xz, yz and the exposed faces; columns not asked
+        for hold 0.  Returns the number of voxels whose value is negative or above n_labels (they add to no row)."""
+        outside = C.c_uint64(0)
+        self._check(self._L.o2v_hip_label_stats(self._ctx, labels_ptr, fmt, _u64x3(strides), _u32x3(dims), _u32x3(origin), n_labels, which,
+                                                table_ptr, C.byref(outside)), "o2v_hip_label_stats")
+        return int(outside.value)
+
+    def label_stats_times(self):
+        """o2v_hip_label_stats_times: the device times (ms) of the last label_stats call's table initialisation and pass."""
+        return self._stage_times("o2v_hip_label_stats_times", 2)
 
     def nearest_scratch_bytes(self, dims):
         """o2v_hip_nearest_scratch_bytes: the context scratch a nearest_dense call over dims (x, y, z) needs."""

@@ -865,6 +865,74 @@ int o2v_hip_label_stats(o2v_hip_ctx *ctx, const void *labels, uint32_t format, c
  * pass over the grid. */
 int o2v_hip_label_stats_times(const o2v_hip_ctx *ctx, float out_ms[2]);
 
+/* ---- geodesic distances and shortest paths through a dense grid -----------------------------------------
+ *
+ * How far it is from A to B without leaving the set: single- or multi-source shortest path lengths on the voxel adjacency graph
+ * of a set, with small integer edge weights, and the walk back along them; defined so that a numpy restatement reproduces every bit.
+ *
+ * The set.  grid, format, strides, dims and level are those of o2v_hip_components_dense: the grid is only read, a stride may be 0,
+ * BITS needs strides[0] == 1, a NaN is not below the level.  S is the solid voxels of the box, or with O2V_HIP_CC_INVERT the
+ * voxels of the box that are not solid.
+ * The steps.  weights[3] (uint32, each 0 ... 65 535 = O2V_HIP_GEO_MAX_WEIGHT, not all 0) are the costs of a step to a neighbour
+ * that differs by at most 1 on every axis and on exactly 1, 2 or 3 axes (face, edge, corner); a weight of 0 means that kind of
+ * step does not exist.  (1, 0, 0) counts hops at connectivity 6, (1, 1, 0) at 18, (1, 1, 1) at 26; (3, 4, 5) is the chamfer
+ * metric, whose thirds approximate Euclidean length.  A diagonal step needs only its two end voxels in S (the adjacency of
+ * o2v_hip_components_dense).  Nothing outside the box is adjacent to anything.
+ * The seeds.  int32 [n_seeds][3], local (x, y, z), in device memory; a seed outside the box or not in S is ignored; with
+ * n_seeds = 0 the pointer is not read.  O2V_HIP_CC_SEED_BORDER additionally seeds every voxel of S on the six faces of the box.
+ * The distance.  d(v) is the smallest sum of weights over all paths inside S from any seed to v; 0 at a seed.  max_distance
+ * (uint32, at most 2^31 - 2 = O2V_HIP_GEO_MAX_DISTANCE; pass that for "no cap"): a voxel whose d is above it counts as not
+ * reached, and nothing is propagated through it - which changes no other voxel's d, every weight being positive.  With d at most
+ * 2^31 - 2 (2^31 - 1 while a voxel is not reached) and a weight at most 65 535, every d + w of the relaxation fits a uint32.
+ * d is the least fixed point of a monotone integer relaxation: unique, the same bits on every run and under every schedule.
+ *
+ * o2v_hip_geodesic_dense writes dist(x, y, z) = dist[x * dist_strides[0] + y * dist_strides[1] + z * dist_strides[2]] (int32,
+ * strides in elements, no two voxels on one element) for every voxel of the box: d(v) where v is reached, -1 everywhere else -
+ * outside S, and in S but not reached.  *out_reached is the number of voxels with dist >= 0.
+ * flags: O2V_HIP_CC_INVERT, O2V_HIP_CC_SEED_BORDER, O2V_HIP_FLAG_STAGE_TIMES (o2v_hip_geodesic_counters counts).
+ *
+ * o2v_hip_geodesic_paths walks back through a grid that o2v_hip_geodesic_dense wrote (dist >= 0 says "in S and reached": it takes
+ * no set grid).  targets: int32 [n_targets][3]; paths: int32 [n_targets][max_len][3]; lengths: int32 [n_targets]; all contiguous
+ * device memory.  For target i: outside the box, or dist < 0 there: lengths[i] = -1.  Otherwise the path starts at the target and
+ * goes, until dist = 0, from v to the first neighbour u in the box with dist[u] >= 0 and dist[u] + w(u, v) == dist[v], the
+ * neighbours taken in ascending (dz, dy, dx) order of their offsets and only the step kinds with a weight tried.  lengths[i] is
+ * the number of voxels of the whole path, both ends included; the first min(lengths[i], max_len) of them are written,
+ * paths[i][k] = (x, y, z), the rest of the row is left alone.  If no such neighbour exists, the grid was not made with these
+ * weights: lengths[i] = -2 and the walk ends (what it had written of the row stays).  Every walk ends: dist strictly decreases.
+ *
+ * Refused before any launch, the outputs untouched.  O2V_HIP_ERR_BAD_ARGUMENT: null arguments, zero dims, an unknown format,
+ * unknown flag bits, BITS with strides[0] != 1, a level that is not finite (F32_BELOW only), a weight above 65 535 or all three 0,
+ * max_distance above 2^31 - 2, a dist that is not 4-byte aligned, an output overlapping an input or another output, dist strides
+ * that map two voxels to one element (o2v_hip_geodesic_dense; the paths call only reads dist), a pointer that is not device memory
+ * of the context's device with its whole extent inside its allocation.  O2V_HIP_ERR_LIMIT: a dim above 65 536, nx * ny * nz,
+ * n_seeds or n_targets above 2^31 - 1.  A failed scratch allocation returns O2V_HIP_ERR_OUT_OF_MEMORY and the context stays
+ * usable.  After a later error the outputs are unspecified.  Both calls run on the context's stream and return when their results
+ * have landed (the caller must have finished writing their inputs).
+ *
+ * Scratch of the context, grown on demand, with words = ceil(nx / 64) * ny * nz, tiles = ceil(nx / 64) * ceil(ny / 8) *
+ * ceil(nz / 8) and voxels = nx * ny * nz:
+ *   O2V_HIP_GEO_SCRATCH_CONTIGUOUS  8 * words + 16 * tiles + 64: the set's bits, per tile two flag words and two list places,
+ *                                   counters.  No per-voxel scratch: the distances live in dist.  This holds where dist is
+ *                                   contiguous (strides 1, nx, nx * ny);
+ *   O2V_HIP_GEO_SCRATCH_STRIDED     ... + 4 * voxels: a dist of any other strides, the distances in the context.
+ * (0 for zero dims or an unknown `which`.)  o2v_hip_geodesic_paths takes none.
+ * O2V_GEO_NO_TILES=1 in the environment (A/B): no tile pass, whole-grid sweeps until one changes nothing; same results. */
+enum { O2V_HIP_GEO_MAX_WEIGHT = 65535u, O2V_HIP_GEO_MAX_DISTANCE = 0x7ffffffeu };
+enum { O2V_HIP_GEO_SCRATCH_CONTIGUOUS = 0, O2V_HIP_GEO_SCRATCH_STRIDED = 1 };
+int o2v_hip_geodesic_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+                           const uint32_t weights[3], uint32_t flags, const int32_t *seeds /* [n_seeds][3] */, uint64_t n_seeds,
+                           uint32_t max_distance, int32_t *dist, const uint64_t dist_strides[3], uint64_t *out_reached);
+int o2v_hip_geodesic_paths(o2v_hip_ctx *ctx, const int32_t *dist, const uint64_t dist_strides[3], const uint32_t dims[3], const uint32_t weights[3],
+                           const int32_t *targets /* [n_targets][3] */, uint64_t n_targets, uint32_t max_len, int32_t *paths, int32_t *lengths);
+uint64_t o2v_hip_geodesic_scratch_bytes(const uint32_t dims[3], uint32_t which);
+/* The device times (ms) of the last o2v_hip_geodesic_dense call: classify, initialisation + seeds, propagation (the host's reads
+ * between the rounds included), write. */
+int o2v_hip_geodesic_times(const o2v_hip_ctx *ctx, float out_ms[4]);
+/* Of the last o2v_hip_geodesic_dense call made with O2V_HIP_FLAG_STAGE_TIMES (else zeros): the rounds (launches of the
+ * propagation), the tile visits over all rounds, the sweeps inside the tiles over all visits, and the host's 4-byte reads during
+ * the propagation.  With O2V_GEO_NO_TILES=1: the whole-grid sweeps, 0, 0, the reads. */
+int o2v_hip_geodesic_counters(const o2v_hip_ctx *ctx, uint64_t out4[4]);
+
 int o2v_hip_get_timings(const o2v_hip_ctx *ctx, o2v_hip_timings *out);
 /* Per-kernel device times of the last o2v_hip_voxelize call made with O2V_HIP_FLAG_KERNEL_TIMES (else none): up to
  * max_entries entries are written, *out_count receives how many there are. */

@@ -48,6 +48,8 @@
 //                              both ends of every line (K6's exact column test, keeping the sign); outside the pipeline
 //   K19 k_label_stats          o2v_hip_label_stats: per value of a label grid its voxel count, bounding box, coordinate sums,
 //                              second moments and exposed faces, one pass of runs into a table in LDS; outside the pipeline
+//   K20 k_geo_*                o2v_hip_geodesic_dense / o2v_hip_geodesic_paths: shortest path lengths through the set of a dense
+//                              grid, a relaxation tile by tile in LDS, round by round; the walk back; outside the pipeline
 //   plan k_zhist               o2v_hip_plan_slabs: predicted hits per z layer -> work-balanced slabs for N GPUs
 // With the direct MAX path K1's counters reach the host while K2 runs, and only the stages that have work are enqueued
 // behind it.  N > 1 GPUs: o2v_hip_voxelize_sharded (bounds / work-histogram passes sharded over the ranks, RCCL).
@@ -104,6 +106,7 @@ namespace {
 #include "o2v_dev_k17_downsample.hpp"
 #include "o2v_dev_k18_crossings.hpp"
 #include "o2v_dev_k19_label_stats.hpp"
+#include "o2v_dev_k20_geodesic.hpp"
 
 }  // namespace
 
@@ -237,6 +240,7 @@ struct Switches {
     bool cc_no_tiles = env_on("O2V_CC_NO_TILES");              // A/B: no k_cc_tiles, every adjacent pair is united in global memory
     bool cross_no_tile = env_on("O2V_CROSS_NO_TILE");          // A/B: no k_cross_prefix_tile, a lane per line stores along the ray
     bool ls_no_table = env_on("O2V_LS_NO_TABLE");              // A/B: k_label_stats without its table in LDS, every run to global memory
+    bool geo_no_tiles = env_on("O2V_GEO_NO_TILES");            // A/B: no k_geo_tiles, whole-grid sweeps with atomic mins in global memory
     bool tiny_buffers = env_on("O2V_TEST_TINY_BUFFERS");       // test hook: minimal first capacities (every grow -> re-run path)
     bool block_list = env_on("O2V_TEST_BLOCK_LIST");           // test hook: the slab's block list for a mesh of any size
     int resolve_wgs_per_cu = env_int("O2V_RESOLVE_WGS_PER_CU", 0);  // A/B: workgroups per CU of resolve tier 1 (if > 0; else 2)
@@ -457,6 +461,15 @@ struct o2v_hip_ctx {
     DevArray<unsigned long long> d_ls_ctr;
     PinnedArray<unsigned long long> h_ls_ctr;
     StageTimes<2> ls_times;
+    // K20 (o2v_hip_geodesic_dense / o2v_hip_geodesic_paths): the bits of the set; per tile its flag words of two rounds and its
+    // places in the two rounds' lists ([4][tiles]); the distances where they cannot live in the caller's dist; [0] in-tile
+    // sweeps, [1] reached, then as uint32 the two lists' lengths and the changed word; grown on demand; the times of the four
+    // stages and the four counters of the last call
+    DevArray<unsigned long long> d_geo_bits, d_geo_ctr;
+    DevArray<uint32_t> d_geo_tiles, d_geo_dist;
+    PinnedArray<unsigned long long> h_geo_ctr;
+    StageTimes<4> geo_times;
+    uint64_t geo_counters[4] = {};
 
     // results of the last run
     uint64_t n_vox = 0;
@@ -4283,6 +4296,196 @@ int o2v_hip_label_stats(o2v_hip_ctx *ctx, const void *labels, uint32_t format, c
 int o2v_hip_label_stats_times(const o2v_hip_ctx *ctx, float out_ms[2])
 {
     return ctx ? ctx->ls_times.read(out_ms) : O2V_HIP_ERR_BAD_ARGUMENT;
+}
+
+}  // extern "C"
+
+// ---- K20: geodesic distances and shortest paths through a dense grid -----------------------------------------------------------
+
+namespace {
+
+constexpr uint32_t kGeoFlagsKnown = O2V_HIP_CC_INVERT | O2V_HIP_CC_SEED_BORDER | O2V_HIP_FLAG_STAGE_TIMES;
+
+static_assert(kGeoMaxDistance == O2V_HIP_GEO_MAX_DISTANCE && kGeoMaxWeight == O2V_HIP_GEO_MAX_WEIGHT, "one set of limits for the callers and the kernels");
+
+uint64_t geo_tiles(const uint32_t dims[3]) { return (uint64_t) ((dims[0] + 63u) / 64u) * ((dims[1] + 7u) / 8u) * ((dims[2] + 7u) / 8u); }
+
+// weights: each 0 ... 65 535, not all 0
+int geo_weights(o2v_hip_ctx *ctx, const char *fn, const uint32_t weights[3])
+{
+    for (int a = 0; a < 3; ++a)
+        if (weights[a] > kGeoMaxWeight) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "a weight of " + std::to_string(weights[a]) + " is above 65 535");
+    if (!(weights[0] | weights[1] | weights[2])) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "the weights are all 0: no step exists");
+    return O2V_HIP_OK;
+}
+
+// the size limits of both calls: a linear index is one int32
+int geo_limits(o2v_hip_ctx *ctx, const char *fn, const uint32_t dims[3], uint64_t n, const char *what)
+{
+    for (int a = 0; a < 3; ++a)
+        if (dims[a] > kCcMaxDim) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "a grid of more than 65 536 voxels along an axis");
+    const uint64_t voxels = (uint64_t) dims[0] * dims[1] * dims[2];   // (below 2^48)
+    if (voxels > kCcMaxVoxels)
+        return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, std::to_string(voxels) + " voxels do not fit an int32 index (at most 2^31 - 1)");
+    if (n > kCcMaxVoxels) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, std::string("more than 2^31 - 1 ") + what);
+    return O2V_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t o2v_hip_geodesic_scratch_bytes(const uint32_t dims[3], uint32_t which)
+{
+    if (!dims || !dims[0] || !dims[1] || !dims[2] || which > O2V_HIP_GEO_SCRATCH_STRIDED) return 0;
+    return 8u * cc_words(dims) + 16u * geo_tiles(dims) + 64u + (which == O2V_HIP_GEO_SCRATCH_STRIDED ? 4u * (uint64_t) dims[0] * dims[1] * dims[2] : 0u);
+}
+
+int o2v_hip_geodesic_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+                           const uint32_t weights[3], uint32_t flags, const int32_t *seeds, uint64_t n_seeds, uint32_t max_distance, int32_t *dist,
+                           const uint64_t dist_strides[3], uint64_t *out_reached)
+{
+    static const char fn[] = "o2v_hip_geodesic_dense";
+    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
+    const Switches sw = read_switches();
+    if (!dist || !dist_strides || !out_reached || !weights || (n_seeds && !seeds)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
+    SetGrid sg;
+    int rc;
+    if ((rc = set_grid(ctx, fn, grid, format, strides, dims, level, &sg)) || (rc = geo_weights(ctx, fn, weights))) return rc;
+    if (max_distance > kGeoMaxDistance) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "max_distance is above 2^31 - 2");
+    if (flags & ~kGeoFlagsKnown) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown flag bits in " + std::to_string(flags));
+    if ((uintptr_t) dist % sizeof(int32_t)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "dist must be 4-byte aligned");
+    if ((rc = geo_limits(ctx, fn, dims, n_seeds, "seeds"))) return rc;
+    uint64_t obytes = 0;
+    if ((rc = check_grid(ctx, fn, "dist", dist, dims, dist_strides, 4u, true, &obytes)) ||
+        (n_seeds && (rc = check_device_range(ctx, fn, seeds, n_seeds * 12u, "seeds"))))
+        return rc;
+    const Span spans[] = {{"dist", dist, obytes}, {"grid", grid, sg.bytes}, {"seeds", seeds, n_seeds * 12u}};
+    if ((rc = refuse_overlap(ctx, fn, spans, 1))) return rc;
+
+    GeoGrid g{};
+    g.nx = dims[0], g.ny = dims[1], g.nz = dims[2];
+    g.W = (dims[0] + 63u) / 64u;
+    g.tiles_y = (dims[1] + 7u) / 8u, g.tiles_z = (dims[2] + 7u) / 8u;
+    std::copy(weights, weights + 3, g.w);
+    g.max_distance = max_distance;
+    g.words = cc_words(dims);
+    const uint64_t voxels = (uint64_t) dims[0] * dims[1] * dims[2], tiles = geo_tiles(dims);   // (tiles: at most the words, below 2^31)
+    // the distances live in the caller's dist where linear index i is element i of it
+    const bool in_place = (dims[0] == 1u || dist_strides[0] == 1u) && (dims[1] == 1u || dist_strides[1] == dims[0]) &&
+                          (dims[2] == 1u || dist_strides[2] == (uint64_t) dims[0] * dims[1]);
+    if ((rc = grow_scratch(ctx, ctx->d_geo_bits, g.words, fn, "set bits")) || (rc = grow_scratch(ctx, ctx->d_geo_tiles, 4u * tiles, fn, "tile flags and lists")) ||
+        (rc = grow_scratch(ctx, ctx->d_geo_ctr, 8u, fn, "counters")) || (rc = grow_scratch(ctx, ctx->h_geo_ctr, 8u, fn, "counters")) ||
+        (!in_place && (rc = grow_scratch(ctx, ctx->d_geo_dist, voxels, fn, "distances"))))
+        return rc;
+    ctx->ktimes_on = false;   // (no per-launch brackets here; o2v_hip_voxelize sets the flag again from its params)
+    uint32_t *const D = in_place ? reinterpret_cast<uint32_t *>(dist) : ctx->d_geo_dist.ptr;
+    unsigned long long *const bits = ctx->d_geo_bits.ptr, *const ctr = ctx->d_geo_ctr.ptr;
+    uint32_t *const tile_flags[2] = {ctx->d_geo_tiles.ptr, ctx->d_geo_tiles.ptr + tiles};
+    uint32_t *const tile_list[2] = {ctx->d_geo_tiles.ptr + 2u * tiles, ctx->d_geo_tiles.ptr + 3u * tiles};
+    uint32_t *const cnt = reinterpret_cast<uint32_t *>(ctr + 2);                                   // the lists' lengths, the changed word
+    volatile uint32_t *const h_cnt = reinterpret_cast<volatile uint32_t *>(ctx->h_geo_ctr.ptr + 2);
+    const bool count = (flags & O2V_HIP_FLAG_STAGE_TIMES) != 0, use_tiles = !sw.geo_no_tiles;
+    const dim3 per_word(stream_grid(ctx, g.words * 64u, 16u));
+    hipStream_t s = ctx->stream;
+    O2V_CHECK(ctx->geo_times.mark(0, s));
+    O2V_CHECK(hipMemsetAsync(ctr, 0, 8u * sizeof(unsigned long long), s));
+    launch_classify(ctx, sg, (flags & O2V_HIP_CC_INVERT) ? 1u : 0u, bits);
+    O2V_CHECK(ctx->geo_times.mark(1, s));
+    O2V_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(D), (int) kGeoInf, voxels, s));
+    if (use_tiles) O2V_CHECK(hipMemsetAsync(tile_flags[0], 0, 2u * tiles * sizeof(uint32_t), s));
+    uint32_t *const fl0 = use_tiles ? tile_flags[0] : nullptr;
+    if (n_seeds)
+        O2V_LAUNCH("k_geo_seed_list", s, k_geo_seed_list, dim3(stream_grid(ctx, n_seeds, 8u)), dim3(kBlock), 0, s, g, bits, seeds, n_seeds, D, fl0, tile_list[0], cnt);
+    if (flags & O2V_HIP_CC_SEED_BORDER) O2V_LAUNCH("k_geo_seed_border", s, k_geo_seed_border, per_word, dim3(kBlock), 0, s, g, bits, D, fl0, tile_list[0], cnt);
+    O2V_CHECK(ctx->geo_times.mark(2, s));
+    // The rounds.  No cap: a round is launched only if the last one decreased a distance on a tile's rim (tiles) or anywhere
+    // (sweeps), and distances are whole numbers that only decrease.
+    uint64_t rounds = 0, visits = 0, reads = 0;
+    if (use_tiles) {
+        O2V_CHECK(hipMemcpyAsync(const_cast<uint32_t *>(h_cnt), cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        O2V_CHECK(hipStreamSynchronize(s));
+        ++reads;
+        for (uint32_t cur = 0, n = h_cnt[0]; n; cur ^= 1u, n = h_cnt[cur]) {
+            const uint32_t nxt = cur ^ 1u;
+            const dim3 blocks((uint32_t) std::min<uint64_t>(n, kCcMaxGrid));
+            O2V_CHECK(hipMemsetAsync(cnt + nxt, 0, sizeof(uint32_t), s));
+            if (count)
+                O2V_LAUNCH("k_geo_tiles", s, k_geo_tiles<true>, blocks, dim3(kBlock), 0, s, g, bits, D, tile_list[cur], n, tile_flags[cur], tile_flags[nxt],
+                           tile_list[nxt], cnt + nxt, ctr);
+            else
+                O2V_LAUNCH("k_geo_tiles", s, k_geo_tiles<false>, blocks, dim3(kBlock), 0, s, g, bits, D, tile_list[cur], n, tile_flags[cur], tile_flags[nxt],
+                           tile_list[nxt], cnt + nxt, ctr);
+            O2V_CHECK(hipMemcpyAsync(const_cast<uint32_t *>(h_cnt) + nxt, cnt + nxt, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            O2V_CHECK(hipStreamSynchronize(s));
+            ++rounds, ++reads, visits += n;
+        }
+    } else {
+        do {
+            O2V_CHECK(hipMemsetAsync(cnt + 2, 0, sizeof(uint32_t), s));
+            O2V_LAUNCH("k_geo_sweep", s, k_geo_sweep, per_word, dim3(kBlock), 0, s, g, bits, D, cnt + 2);
+            O2V_CHECK(hipMemcpyAsync(const_cast<uint32_t *>(h_cnt) + 2, cnt + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            O2V_CHECK(hipStreamSynchronize(s));
+            ++rounds, ++reads;
+        } while (h_cnt[2]);
+    }
+    O2V_CHECK(ctx->geo_times.mark(3, s));
+    O2V_LAUNCH("k_geo_write", s, k_geo_write, per_word, dim3(kBlock), 0, s, g, D, dist, dist_strides[0], dist_strides[1], dist_strides[2], ctr + 1);
+    O2V_CHECK(hipGetLastError());
+    O2V_CHECK(ctx->geo_times.mark(4, s));
+    O2V_CHECK(hipMemcpyAsync(ctx->h_geo_ctr.ptr, ctr, 2u * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    O2V_CHECK(hipStreamSynchronize(s));
+    O2V_CHECK(ctx->geo_times.finish());
+    const uint64_t counters[4] = {rounds, visits, ctx->h_geo_ctr.ptr[0], reads};
+    for (int i = 0; i < 4; ++i) ctx->geo_counters[i] = count ? counters[i] : 0u;
+    *out_reached = ctx->h_geo_ctr.ptr[1];
+    return O2V_HIP_OK;
+}
+
+int o2v_hip_geodesic_paths(o2v_hip_ctx *ctx, const int32_t *dist, const uint64_t dist_strides[3], const uint32_t dims[3], const uint32_t weights[3],
+                           const int32_t *targets, uint64_t n_targets, uint32_t max_len, int32_t *paths, int32_t *lengths)
+{
+    static const char fn[] = "o2v_hip_geodesic_paths";
+    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
+    if (!dist || !dist_strides || !dims || !weights || (n_targets && (!targets || !lengths || (max_len && !paths))))
+        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
+    if (!dims[0] || !dims[1] || !dims[2]) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "zero dims");
+    int rc;
+    if ((rc = geo_weights(ctx, fn, weights))) return rc;
+    if ((uintptr_t) dist % sizeof(int32_t)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "dist must be 4-byte aligned");
+    if ((rc = geo_limits(ctx, fn, dims, n_targets, "targets"))) return rc;
+    O2V_CHECK(hipSetDevice(ctx->device));
+    const unsigned __int128 want = (unsigned __int128) n_targets * max_len * 12u;
+    if (want > (unsigned __int128) (~0ull >> 1)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "paths: n_targets rows of max_len voxels reach past any allocation");
+    const uint64_t pbytes = (uint64_t) want;
+    uint64_t dbytes = 0;
+    if ((rc = check_grid(ctx, fn, "dist", dist, dims, dist_strides, 4u, false, &dbytes))) return rc;
+    if (!n_targets) return O2V_HIP_OK;
+    if ((rc = check_device_range(ctx, fn, targets, n_targets * 12u, "targets")) || (rc = check_device_range(ctx, fn, lengths, n_targets * 4u, "lengths")) ||
+        (pbytes && (rc = check_device_range(ctx, fn, paths, pbytes, "paths"))))
+        return rc;
+    const Span spans[] = {{"paths", paths, pbytes}, {"lengths", lengths, n_targets * 4u}, {"dist", dist, dbytes}, {"targets", targets, n_targets * 12u}};
+    if ((rc = refuse_overlap(ctx, fn, spans, 2))) return rc;
+    ctx->ktimes_on = false;   // (no per-launch brackets here; o2v_hip_voxelize sets the flag again from its params)
+    GeoTrace t{};
+    for (int a = 0; a < 3; ++a) t.dims[a] = dims[a], t.w[a] = weights[a], t.s[a] = dist_strides[a];
+    hipStream_t s = ctx->stream;
+    O2V_LAUNCH("k_geo_trace", s, k_geo_trace, dim3(stream_grid(ctx, n_targets, 8u)), dim3(kBlock), 0, s, t, dist, targets, n_targets, max_len, paths, lengths);
+    O2V_CHECK(hipGetLastError());
+    O2V_CHECK(hipStreamSynchronize(s));
+    return O2V_HIP_OK;
+}
+
+int o2v_hip_geodesic_times(const o2v_hip_ctx *ctx, float out_ms[4])
+{
+    return ctx ? ctx->geo_times.read(out_ms) : O2V_HIP_ERR_BAD_ARGUMENT;
+}
+
+int o2v_hip_geodesic_counters(const o2v_hip_ctx *ctx, uint64_t out4[4])
+{
+    if (!ctx || !out4) return O2V_HIP_ERR_BAD_ARGUMENT;
+    std::copy(ctx->geo_counters, ctx->geo_counters + 4, out4);
+    return O2V_HIP_OK;
 }
 
 }  // extern "C"

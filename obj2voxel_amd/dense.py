@@ -26,7 +26,9 @@ parts pushed into each other and outvotes a ray that slips through a hole (o2v_h
 label_stats reads a label grid once and gives, per label, the voxel count, the bounding box, the coordinate sums, the second
 moments and the exposed faces as exact integers, and component_stats, centroids, covariances, mass_properties, keep_largest and
 crop are built on them: the parts of a scan cropped one by one, the largest body kept, a solid's volume, centre of mass and inertia
-tensor (o2v_hip_label_stats).
+tensor (o2v_hip_label_stats); geodesic_distance says how far every voxel of a set is from the nearest seed
+without leaving the set - hop counts, the chamfer metric or any integer step costs, from listed seeds or the border - and
+shortest_paths walks back along those distances (o2v_hip_geodesic_dense / o2v_hip_geodesic_paths).
 
 torch is imported first on purpose: the library must bind to the HIP runtime torch loaded (a process that loaded the library
 before torch holds two separate runtime copies, and this module refuses to work there).
@@ -763,6 +765,111 @@ def remove_small(dv, grid, min_voxels, *, level=None, connectivity=26):
     keep = component_sizes(labels, n) >= min_voxels
     keep[0] = False
     return keep[labels.to(torch.int64)]
+
+
+# ---- geodesic distances and shortest paths ---------------------------------------------------------------
+
+CHAMFER_UNIT = 3   # the chamfer metric's face step: dist.float() / CHAMFER_UNIT reads in voxels
+_GEO_WEIGHTS = {("steps", 6): (1, 0, 0), ("steps", 18): (1, 1, 0), ("steps", 26): (1, 1, 1),
+                ("chamfer", 6): (3, 0, 0), ("chamfer", 18): (3, 4, 0), ("chamfer", 26): (3, 4, 5)}
+
+
+def _geo_weights(metric, connectivity, weights):
+    """The (face, edge, corner) step costs of geodesic_distance / shortest_paths: `weights` if given, else the metric's, cut to
+    the connectivity."""
+    if weights is not None:
+        if isinstance(weights, (str, bytes)) or not hasattr(weights, "__iter__"):
+            raise ValueError(f"weights must be three integers 0 .. {hip.GEO_MAX_WEIGHT}, not {weights!r}")
+        weights = tuple(weights)
+        if len(weights) != 3 or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 0 <= v <= hip.GEO_MAX_WEIGHT for v in weights) \
+                or not any(weights):
+            raise ValueError(f"weights must be three integers 0 .. {hip.GEO_MAX_WEIGHT}, not all 0, not {weights!r}")
+        return tuple(int(v) for v in weights)
+    if isinstance(connectivity, bool) or connectivity not in (6, 18, 26):
+        raise ValueError(f"connectivity must be 6, 18 or 26, not {connectivity!r}")
+    if metric not in ("steps", "chamfer"):
+        raise ValueError(f"metric must be 'steps' or 'chamfer', not {metric!r}")
+    return _GEO_WEIGHTS[metric, connectivity]
+
+
+def geodesic_distance(dv, grid, seeds=None, *, border=False, metric="chamfer", connectivity=26, weights=None, background=False,
+                      max_distance=None, level=None, out=None):
+    """How far every voxel of the set is from the nearest seed without leaving the set: an int32 tensor
+    [z, y, x] of the smallest sum of step costs over all paths inside the set, 0 at a seed, -1 where the voxel is not in the
+    set, not reached, or further than max_distance.  grid, level and background as components takes them.
+
+    seeds:         an int32 / int64 tensor [n, 3] of (x, y, z) on the device, or a sequence of such triples; a seed outside the
+                   box or not in the set is ignored.
+    border:        True: every voxel of the set on the six faces of the box is a seed as well.
+    metric:        "chamfer": a face, edge, corner step costs 3, 4, 5 - dist.float() / CHAMFER_UNIT approximates the Euclidean
+                   length in voxels; "steps": every step costs 1 (hop counts).
+    connectivity:  6, 18 or 26: the steps that exist - faces; faces and edges; faces, edges and corners.  A diagonal step
+                   needs only its two end voxels in the set.
+    weights:       (face, edge, corner) costs, integers 0 .. 65 535, 0 = no such step, not all 0; overrides metric and connectivity.
+    max_distance:  an integer 0 .. 2^31 - 2: nothing further than that is reached, and nothing is propagated through such a
+                   voxel (bounded region growing); None: no cap.
+    out:           an int32 tensor of the grid's shape (any strides, not in grid's storage), written as it is; else a new
+                   contiguous tensor.  A contiguous out needs no per-voxel scratch in the context."""
+    device, fmt, level, dims = _set_grid(dv, grid, level, _limit_voxels, connectivity)
+    shape = (dims[2], dims[1], dims[0])
+    weights = _geo_weights(metric, connectivity, weights)
+    if max_distance is None:
+        max_distance = hip.GEO_MAX_DISTANCE
+    elif isinstance(max_distance, bool) or not isinstance(max_distance, numbers.Integral) or not 0 <= max_distance <= hip.GEO_MAX_DISTANCE:
+        raise ValueError(f"max_distance must be an integer 0 .. {hip.GEO_MAX_DISTANCE}, not {max_distance!r}")
+    seeds = _seeds(seeds, device)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int32, device=device)
+    else:
+        _check_grid(out, "out", torch.int32, device, shape)
+    n = 0 if seeds is None else seeds.shape[0]
+    flags = (hip.CC_INVERT if background else 0) | (hip.CC_SEED_BORDER if border else 0)
+    _sync(device)   # (the caller's writes to grid, seeds and out have landed)
+    dv.geodesic_dense(grid.data_ptr(), fmt, _strides(grid), dims, 0.0 if level is None else level, weights, flags,
+                      seeds.data_ptr() if n else None, n, int(max_distance), out.data_ptr(), _strides(out))
+    return out
+
+
+def shortest_paths(dv, dist, targets, *, metric="chamfer", connectivity=26, weights=None, max_len=None):
+    """The shortest paths from targets back to the seeds of a geodesic_distance grid.  Returns (paths,
+    lengths): paths int32 [n, L, 3], row i the voxels (x, y, z) of target i's path from the target to a seed, padded with -1;
+    lengths int32 [n], the voxels of the whole path with both ends, -1 for a target outside the box or not reached, -2 where the
+    grid was not made with these weights.  Of a path longer than L its first L voxels are there; lengths holds the true length.
+    Among equally short ways the walk takes the first neighbour in ascending (dz, dy, dx) order.
+
+    dist:      what geodesic_distance returned (int32 [z, y, x], any strides); metric, connectivity and weights as given there.
+    targets:   an int32 / int64 tensor [n, 3] of (x, y, z) on the device, or a sequence of such triples.
+    max_len:   L; None: max(dist at the targets) // (the smallest weight above 0) + 1, which holds every path - one small read."""
+    _require_shared_runtime()
+    device = _device(dv)
+    _check_grid(dist, "dist", torch.int32, device)
+    if 0 in dist.shape:
+        raise ValueError("dist has an empty dimension")
+    dims = (dist.shape[2], dist.shape[1], dist.shape[0])
+    _limit_voxels(dims)
+    weights = _geo_weights(metric, connectivity, weights)
+    if targets is None:
+        raise ValueError("targets must be a tensor [n, 3] or a sequence of (x, y, z)")
+    targets = _seeds(targets, device)
+    n = targets.shape[0]
+    if max_len is not None and (isinstance(max_len, bool) or not isinstance(max_len, numbers.Integral) or not 0 <= max_len <= 2 ** 31 - 1):
+        raise ValueError(f"max_len must be an integer 0 .. {2 ** 31 - 1}, not {max_len!r}")
+    _sync(device)   # (the caller's writes to dist and targets have landed)
+    if max_len is None:
+        max_len = 1
+        if n:
+            t = targets.to(torch.int64)
+            inside = ((t >= 0) & (t < torch.tensor(dims, dtype=torch.int64, device=device))).all(dim=1)
+            t = t[inside]
+            if t.shape[0]:
+                max_len = max(int(dist[t[:, 2], t[:, 1], t[:, 0]].max()), 0) // min(w for w in weights if w) + 1
+    paths = torch.full((n, max_len, 3), -1, dtype=torch.int32, device=device)
+    lengths = torch.full((n,), -1, dtype=torch.int32, device=device)
+    _sync(device)   # (the fills have landed)
+    if n:
+        dv.geodesic_paths(dist.data_ptr(), _strides(dist), dims, weights, targets.data_ptr(), n, int(max_len), paths.data_ptr() if max_len else None,
+                          lengths.data_ptr())
+    return paths, lengths
 
 
 # ---- dense grids as voxel lists and voxel files (DESIGN.md section 16) --------------------------------------------------------

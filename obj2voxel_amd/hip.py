@@ -37,6 +37,8 @@ NEAREST_NO_LIMIT = 0x7FFFFFFF  # ... its max_dist2 without a limit
 DOWN_VALUE_MIN, DOWN_VALUE_MAX = 0, 1  # o2v_hip_downsample value modes
 AXIS_X, AXIS_Y, AXIS_Z = 1, 2, 4  # o2v_hip_crossings_dense: the bits of `axes`
 LABELS_I32, LABELS_U8 = 0, 1  # o2v_hip_label_stats formats
+GEO_MAX_WEIGHT, GEO_MAX_DISTANCE = 65535, 2 ** 31 - 2  # o2v_hip_geodesic_dense: the largest weight, the largest (and default) max_distance
+GEO_SCRATCH_CONTIGUOUS, GEO_SCRATCH_STRIDED = 0, 1  # o2v_hip_geodesic_scratch_bytes
 STATS_BOX, STATS_SUMS, STATS_MOMENTS, STATS_FACES = 1, 2, 4, 8  # ... the bits of `which`
 STATS_COLUMNS = 17  # ... the int64 columns of a row of its table
 ERR_BAD_ARGUMENT = 3
@@ -184,6 +186,16 @@ def _bind():
     L.o2v_hip_label_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
                                       C.POINTER(C.c_uint64)]
     L.o2v_hip_label_stats_times.argtypes = [C.c_void_p, C.c_void_p]
+    # ctx, grid, format, strides, dims, level, weights, flags, seeds, n_seeds, max_distance, dist, dist_strides, out_reached
+    L.o2v_hip_geodesic_dense.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_uint32, C.c_void_p,
+                                         C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    # ctx, dist, dist_strides, dims, weights, targets, n_targets, max_len, paths, lengths
+    L.o2v_hip_geodesic_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
+                                         C.c_void_p]
+    L.o2v_hip_geodesic_scratch_bytes.argtypes = [C.c_void_p, C.c_uint32]
+    L.o2v_hip_geodesic_scratch_bytes.restype = C.c_uint64
+    L.o2v_hip_geodesic_times.argtypes = [C.c_void_p, C.c_void_p]
+    L.o2v_hip_geodesic_counters.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_max_slab_layers.argtypes = [C.c_void_p, C.POINTER(_Params), C.POINTER(C.c_uint32)]
     return L
 
@@ -242,6 +254,12 @@ def components_scratch_bytes(dims, which=CC_SCRATCH_LABELS):
     """o2v_hip_components_scratch_bytes: the context scratch a components_dense (CC_SCRATCH_LABELS: contiguous labels,
     CC_SCRATCH_LABELS_STRIDED: any other) or flood_dense (CC_SCRATCH_FLOOD) call over dims (x, y, z) takes."""
     return int(_bind().o2v_hip_components_scratch_bytes(_u32x3(dims), which))
+
+
+def geodesic_scratch_bytes(dims, which=GEO_SCRATCH_CONTIGUOUS):
+    """o2v_hip_geodesic_scratch_bytes: the context scratch a geodesic_dense call over dims (x, y, z) takes with a contiguous dist
+    (GEO_SCRATCH_CONTIGUOUS) or any other (GEO_SCRATCH_STRIDED)."""
+    return int(_bind().o2v_hip_geodesic_scratch_bytes(_u32x3(dims), which))
 
 
 def gather_scratch_bytes(dims):
@@ -608,6 +626,42 @@ class DeviceVoxelizer:
     def label_stats_times(self):
         """o2v_hip_label_stats_times: the device times (ms) of the last label_stats call's table initialisation and pass."""
         return self._stage_times("o2v_hip_label_stats_times", 2)
+
+    def geodesic_dense(self, grid_ptr, fmt, strides, dims, level, weights, flags, seeds_ptr, n_seeds, max_distance, dist_ptr, dist_strides):
+        """o2v_hip_geodesic_dense: int32 dist = the smallest sum of weights (face, edge, corner step; 0: no such step) over the
+        paths inside the set from a seed (int32 [n_seeds, 3] local (x, y, z) at device address seeds_ptr; with CC_SEED_BORDER every
+        voxel of the set on the box's faces too), -1 where the voxel is not in the set, not reached or further than max_distance.
+        flags: CC_INVERT | CC_SEED_BORDER | FLAG_STAGE_TIMES.  Returns the number of voxels reached."""
+        n = C.c_uint64(0)
+        w = (C.c_uint32 * 3)(*[int(v) for v in weights])
+        self._check(self._L.o2v_hip_geodesic_dense(self._ctx, grid_ptr, fmt, _u64x3(strides), _u32x3(dims), float(level), w, flags, seeds_ptr, n_seeds,
+                                                   max_distance, dist_ptr, _u64x3(dist_strides), C.byref(n)), "o2v_hip_geodesic_dense")
+        return int(n.value)
+
+    def geodesic_paths(self, dist_ptr, dist_strides, dims, weights, targets_ptr, n_targets, max_len, paths_ptr, lengths_ptr):
+        """o2v_hip_geodesic_paths: the walk back through a dist grid of geodesic_dense from each of the int32 [n_targets, 3]
+        targets to a seed: lengths int32 [n_targets] (the voxels of the path; -1: not reached or outside the box; -2: the grid
+        was not made with these weights), paths int32 [n_targets, max_len, 3], of which the first min(length, max_len) voxels of
+        a row are written."""
+        w = (C.c_uint32 * 3)(*[int(v) for v in weights])
+        self._check(self._L.o2v_hip_geodesic_paths(self._ctx, dist_ptr, _u64x3(dist_strides), _u32x3(dims), w, targets_ptr, n_targets, max_len,
+                                                   paths_ptr, lengths_ptr), "o2v_hip_geodesic_paths")
+
+    def geodesic_scratch_bytes(self, dims, which=GEO_SCRATCH_CONTIGUOUS):
+        """o2v_hip_geodesic_scratch_bytes: the context scratch a geodesic_dense call over dims (x, y, z) takes."""
+        return geodesic_scratch_bytes(dims, which)
+
+    def geodesic_times(self):
+        """o2v_hip_geodesic_times: the device times (ms) of the last geodesic_dense call's classify, initialisation + seeds,
+        propagation and write stages."""
+        return self._stage_times("o2v_hip_geodesic_times", 4)
+
+    def geodesic_counters(self):
+        """o2v_hip_geodesic_counters: (rounds, tile visits, in-tile sweeps, host reads during the propagation) of the last
+        geodesic_dense call made with FLAG_STAGE_TIMES (else zeros)."""
+        out = (C.c_uint64 * 4)()
+        self._check(self._L.o2v_hip_geodesic_counters(self._ctx, out), "o2v_hip_geodesic_counters")
+        return tuple(int(v) for v in out)
 
     def nearest_scratch_bytes(self, dims):
         """o2v_hip_nearest_scratch_bytes: the context scratch a nearest_dense call over dims (x, y, z) needs."""

@@ -566,9 +566,9 @@ bool debug_sync_enabled() { return debug_sync_level() != 0; }
         }                                                                        \
     } while (0)
 
-// One kernel launch of the pipeline.  With O2V_HIP_FLAG_KERNEL_TIMES the launch is bracketed by two events on the stream
-// it goes to (o2v_hip_get_kernel_times; the brackets cost a few microseconds per launch, so bench.py times its steps
-// without the flag and collects the per-kernel times in extra steps).
+// One kernel launch.  Within o2v_hip_voxelize with O2V_HIP_FLAG_KERNEL_TIMES (KernelTimesScope) the launch is bracketed by two
+// events on the stream it goes to (o2v_hip_get_kernel_times; the brackets cost a few microseconds per launch, so bench.py
+// times its steps without the flag and collects the per-kernel times in extra steps).
 #define O2V_LAUNCH(name, stream, ...)                                            \
     do {                                                                         \
         const int kt_ = ktime_begin(ctx, name, stream);                          \
@@ -1616,15 +1616,24 @@ int publish(o2v_hip_ctx *ctx, const Run &r, uint64_t n_interior, uint64_t *out_v
     return O2V_HIP_OK;
 }
 
+// O2V_HIP_FLAG_KERNEL_TIMES holds while voxelize() runs and no longer: the launches of every other call go unbracketed.
+struct KernelTimesScope {
+    o2v_hip_ctx *ctx;
+    KernelTimesScope(o2v_hip_ctx *c, bool on) : ctx(c) { ctx->ktimes_on = on; }
+    ~KernelTimesScope() { ctx->ktimes_on = false; }
+    KernelTimesScope(const KernelTimesScope &) = delete;
+    KernelTimesScope &operator=(const KernelTimesScope &) = delete;
+};
+
 // o2v_hip_voxelize with the switches read by the caller (o2v_hip_voxelize_sharded reads them once for the whole call).
 int voxelize(o2v_hip_ctx *ctx, const o2v_hip_params *params, const Switches &sw, uint64_t *out_voxel_count)
 {
     if (out_voxel_count) *out_voxel_count = 0;
+    const KernelTimesScope kernel_times(ctx, (params->flags & O2V_HIP_FLAG_KERNEL_TIMES) != 0);
     Run r;
     bool empty = false;
     int rc;
     if ((rc = pass_geometry(ctx, params, sw, r, empty)) || empty) return rc;
-    ctx->ktimes_on = (params->flags & O2V_HIP_FLAG_KERNEL_TIMES) != 0;
     ctx->stage_events = (params->flags & (O2V_HIP_FLAG_STAGE_TIMES | O2V_HIP_FLAG_KERNEL_TIMES)) != 0;
     ctx->kernel_times.clear();
     choose_routes(ctx, params, sw, r);
@@ -2427,2068 +2436,18 @@ int o2v_hip_voxels_device_ptr(o2v_hip_ctx *ctx, const uint32_t **out_ptr, uint64
 
 }  // extern "C"
 
-// ---- K7: device-resident input, dense output -------------------------------------------------------------------------
-
-namespace {
-
-// The refusal of a call of the entry point fn: "fn: why" becomes the context's error, rc is returned.
-int refuse(o2v_hip_ctx *ctx, int rc, const char *fn, const std::string &why)
-{
-    ctx->err = std::string(fn) + ": " + why;
-    return rc;
-}
-
-// [p, p + bytes) must be device (or managed) memory of the context's device and lie inside one allocation.  A pointer the
-// runtime does not know leaves an error in its per-thread state, which is cleared here so that the next call does not see it.
-int check_device_range(o2v_hip_ctx *ctx, const char *fn, const void *p, uint64_t bytes, const char *what)
-{
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void) hipGetLastError();
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, std::string(what) + " is not memory the HIP runtime knows");
-    }
-    if ((a.type != hipMemoryTypeDevice && a.type != hipMemoryTypeManaged && !a.isManaged) || a.device != ctx->device)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn,
-                      std::string(what) + " is not device memory of the context's device " + std::to_string(ctx->device));
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(p)) != hipSuccess) {
-        (void) hipGetLastError();
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, std::string(what) + ": the runtime does not know its allocation");
-    }
-    const uint64_t offset = (uint64_t) ((const char *) p - (const char *) base);
-    if (offset > size || bytes > size - offset)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn,
-                      std::string(what) + ": " + std::to_string(bytes) + " bytes from its address extend past its allocation");
-    return O2V_HIP_OK;
-}
-
-// Along the axes of more than one voxel, taken by rising stride, each stride must step past everything the axes before it
-// reach, or two voxels of the box share an element (a stride of 0, as of an expanded tensor, fails this).
-bool strides_distinct(const uint32_t dims[3], const uint64_t strides[3])
-{
-    int ax[3] = {0, 1, 2};
-    std::sort(ax, ax + 3, [&](int a, int b) { return strides[a] < strides[b]; });
-    unsigned __int128 reach = 0;   // the highest element offset the axes so far reach
-    for (int a : ax) {
-        if (dims[a] == 1) continue;
-        if ((unsigned __int128) strides[a] <= reach) return false;
-        reach += (unsigned __int128) (dims[a] - 1u) * strides[a];
-    }
-    return true;
-}
-
-// A grid the caller owns, passed to the entry point fn as `what`: dims voxels at these element strides (x, y, z) from p, of
-// elem bytes each.  Refused if its reach (in 128 bits: the strides are the caller's) is above 2^63 - 1 bytes, if `distinct`
-// and two voxels share an element, or if check_device_range refuses it.  out_bytes: the reach, the bytes past p it touches.
-int check_grid(o2v_hip_ctx *ctx, const char *fn, const char *what, const void *p, const uint32_t dims[3], const uint64_t strides[3],
-               uint32_t elem, bool distinct, uint64_t *out_bytes = nullptr)
-{
-    unsigned __int128 last = 0;
-    for (int a = 0; a < 3; ++a) last += (unsigned __int128) (dims[a] - 1u) * strides[a];
-    const unsigned __int128 bytes = (last + 1u) * elem;
-    if (bytes > (unsigned __int128) (~0ull >> 1))
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, std::string(what) + ": the box and strides reach past any allocation");
-    if (distinct && !strides_distinct(dims, strides))
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, std::string(what) + ": strides map two voxels of the box to one element");
-    if (out_bytes) *out_bytes = (uint64_t) bytes;
-    return check_device_range(ctx, fn, p, (uint64_t) bytes, what);
-}
-
-bool ranges_overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
-{
-    const uintptr_t x = (uintptr_t) a, y = (uintptr_t) b;
-    return x < y + b_bytes && y < x + a_bytes;
-}
-
-// Room for n elements (at least one) of an array of the entry point fn.  A failed allocation leaves the array empty, the
-// runtime's error state clear and the context usable.  (The voxelize pipeline grows its arrays with grow / grow_keep.)
-template <typename T, bool P>
-int grow_scratch(o2v_hip_ctx *ctx, DevArray<T, P> &a, uint64_t n, const char *fn, const char *what)
-{
-    n = std::max<uint64_t>(n, 1);
-    if (a.ptr && n <= a.cap) return O2V_HIP_OK;
-    if (const hipError_t e = a.alloc(n); e != hipSuccess) {
-        (void) hipGetLastError();
-        return refuse(ctx, e == hipErrorOutOfMemory ? O2V_HIP_ERR_OUT_OF_MEMORY : O2V_HIP_ERR_HIP, fn,
-                      std::string(what) + " of " + std::to_string(n * sizeof(T)) + " bytes: " + hipGetErrorString(e));
-    }
-    return O2V_HIP_OK;
-}
-
-uint32_t stream_grid(const o2v_hip_ctx *ctx, uint64_t items, uint32_t per_cu)
-{
-    return (uint32_t) std::max<uint64_t>(1, std::min<uint64_t>((uint64_t) ctx->num_cus * per_cu, (items + kBlock - 1) / kBlock));
-}
-
-// A range of device memory that an entry point reads or writes, as refuse_overlap takes it.
-struct Span {
-    const char *what;
-    const void *p;
-    uint64_t bytes;
-};
-
-// Refuses the first pair of spans that overlap, among the pairs with a written span: the first n_out are written, the others
-// only read (and may share memory).  A span with a null pointer or no bytes is not there.
-template <size_t N>
-int refuse_overlap(o2v_hip_ctx *ctx, const char *fn, const Span (&spans)[N], size_t n_out)
-{
-    for (size_t i = 0; i < n_out; ++i)
-        for (size_t j = i + 1; j < N; ++j) {
-            const Span &a = spans[i], &b = spans[j];
-            if (a.p && a.bytes && b.p && b.bytes && ranges_overlap(a.p, a.bytes, b.p, b.bytes))
-                return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, std::string(a.what) + " and " + b.what + " overlap");
-        }
-    return O2V_HIP_OK;
-}
-
-// ---- the set grid: the input of K11 - K15 ----------------------------------------------------------------------------------
-
-// Which voxels of a box are solid (include/o2v_hip.h, o2v_hip_raycast_build), as set_grid checked it.
-struct SetGrid {
-    GridKey key;          // the caller's pointer, format, strides, dims and level
-    uint64_t bytes = 0;   // the reach: the bytes from key.p on that the box touches
-    uint32_t elem = 1;    // bytes per element: 1 (U8) or 4 (a word of BITS, a float of F32_BELOW)
-    bool vec = false;     // 16-byte loads: unit x stride and every row 16-byte aligned
-
-    RaySource source() const { return RaySource{key.p, key.strides[0], key.strides[1], key.strides[2], key.level}; }
-};
-
-static_assert((int) O2V_HIP_RAY_GRID_U8 == (int) O2V_HIP_GRID_U8 && (int) O2V_HIP_RAY_GRID_BITS == (int) O2V_HIP_GRID_BITS &&
-                  (int) O2V_HIP_RAY_GRID_F32_BELOW == (int) O2V_HIP_GRID_F32_BELOW && kRayU8 == O2V_HIP_GRID_U8 && kRayBits == O2V_HIP_GRID_BITS &&
-                  kRayF32Below == O2V_HIP_GRID_F32_BELOW,
-              "one set of format values for the callers of K11 and of K12 - K15 and for the kernels");
-
-// The checks of a set grid that look at the arguments alone, in this order: null argument, zero dims, unknown format, a BITS
-// grid's x stride, a level that is not finite (F32_BELOW).  *g: everything but the reach.
-int set_grid_args(o2v_hip_ctx *ctx, const char *fn, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
-                  SetGrid *g)
-{
-    if (!grid || !strides || !dims) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    if (!dims[0] || !dims[1] || !dims[2]) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "zero dims");
-    if (format != O2V_HIP_GRID_U8 && format != O2V_HIP_GRID_BITS && format != O2V_HIP_GRID_F32_BELOW)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown format " + std::to_string(format));
-    if (format == O2V_HIP_GRID_BITS && strides[0] != 1u) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "a BITS grid needs strides[0] == 1");
-    if (format == O2V_HIP_GRID_F32_BELOW && !std::isfinite(level)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "level must be finite");
-    g->key = GridKey(grid, format, strides, dims, level);
-    g->elem = format == O2V_HIP_GRID_U8 ? 1u : 4u;
-    g->vec = strides[0] == 1u && (uintptr_t) grid % 16u == 0 && strides[1] * g->elem % 16u == 0 && strides[2] * g->elem % 16u == 0;
-    return O2V_HIP_OK;
-}
-
-// ... and the one that looks at its memory (check_grid; the context's device is made current for it).  *g: the reach.
-int set_grid_memory(o2v_hip_ctx *ctx, const char *fn, SetGrid *g)
-{
-    O2V_CHECK(hipSetDevice(ctx->device));
-    // (the elements the box reaches: 32-bit words along x for BITS)
-    const uint32_t *const dims = g->key.dims;
-    const uint32_t reach[3] = {g->key.format == O2V_HIP_GRID_BITS ? (dims[0] + 31u) / 32u : dims[0], dims[1], dims[2]};
-    return check_grid(ctx, fn, "grid", g->key.p, reach, g->key.strides, g->elem, false, &g->bytes);
-}
-
-// The set grid of the entry point fn, checked: set_grid_args, then set_grid_memory.  An entry point's own limits and modes come
-// after it (o2v_hip_nearest_dense alone has its size limits between the two).
-int set_grid(o2v_hip_ctx *ctx, const char *fn, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
-             SetGrid *g)
-{
-    if (int rc = set_grid_args(ctx, fn, grid, format, strides, dims, level, g)) return rc;
-    return set_grid_memory(ctx, fn, g);
-}
-
-// f(format, vec) with the template arguments <Format, Vec> of the kernels that read a set grid, as integral constants.
-template <typename F>
-void with_set_format(const SetGrid &g, F &&f)
-{
-    using Bits = std::integral_constant<uint32_t, kRayBits>;
-    using U8 = std::integral_constant<uint32_t, kRayU8>;
-    using F32Below = std::integral_constant<uint32_t, kRayF32Below>;
-    if (g.key.format == O2V_HIP_GRID_BITS) return f(Bits{}, std::false_type{});   // (words: no 16-byte variant)
-    if (g.key.format == O2V_HIP_GRID_U8) return g.vec ? f(U8{}, std::true_type{}) : f(U8{}, std::false_type{});
-    return g.vec ? f(F32Below{}, std::true_type{}) : f(F32Below{}, std::false_type{});
-}
-
-// The tail of a count of K13 and K14, whose stage marks 0 and 1 the caller has set: the block sums boff[0, n_blocks) scanned in
-// place, their total into entry n_blocks and from there to the host, which waits for it.  Stage 2 (the write) has not run.
-int count_total(o2v_hip_ctx *ctx, unsigned long long *boff, uint64_t n_blocks, PinnedArray<unsigned long long> &h_ctr, StageTimes<3> &times,
-                uint64_t *total)
-{
-    hipStream_t s = ctx->stream;
-    O2V_LAUNCH("k_fill_scan_blocks", s, k_fill_scan_blocks, dim3(1), dim3(kBlock), 0, s, boff, n_blocks, boff + n_blocks);
-    O2V_CHECK(hipGetLastError());
-    O2V_CHECK(times.mark(2, s));
-    O2V_CHECK(hipMemcpyAsync(h_ctr.ptr, boff + n_blocks, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    O2V_CHECK(hipStreamSynchronize(s));
-    O2V_CHECK(times.elapsed(0, 1, times.ms[0]));
-    O2V_CHECK(times.elapsed(1, 2, times.ms[1]));
-    times.ms[2] = 0.f;
-    *total = h_ctr.ptr[0];
-    return O2V_HIP_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int o2v_hip_set_triangles_device(o2v_hip_ctx *ctx, const float *positions, uint64_t n_positions, const void *faces,
-                                 uint32_t index_bytes, const float *uvs, const uint32_t *types, const float *colors,
-                                 const int32_t *texids, uint64_t count)
-{
-    static const char fn[] = "o2v_hip_set_triangles_device";
-    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
-    if (count && !positions) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "positions is null");
-    if (faces && index_bytes != 4 && index_bytes != 8) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "index_bytes must be 4 or 8");
-    if (count >= (1ull << 29)) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "triangle count must be below 2^29");
-    if (faces && count && n_positions == 0) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "n_positions is 0 but there are faces");
-    if (faces && n_positions > (~0ull >> 4)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "n_positions is too large");
-    O2V_CHECK(hipSetDevice(ctx->device));
-    int rc;
-    if (count) {
-        if ((rc = check_device_range(ctx, fn, positions, faces ? n_positions * 12u : count * 36u, "positions")) ||
-            (faces && (rc = check_device_range(ctx, fn, faces, count * 3u * index_bytes, "faces"))) ||
-            (uvs && (rc = check_device_range(ctx, fn, uvs, count * 24u, "uvs"))) ||
-            (types && (rc = check_device_range(ctx, fn, types, count * 4u, "types"))) ||
-            (colors && (rc = check_device_range(ctx, fn, colors, count * 12u, "colors"))) ||
-            (texids && (rc = check_device_range(ctx, fn, texids, count * 4u, "texids"))) ||
-            (rc = grow_scratch(ctx, ctx->d_dense, 1, fn, "counters")) || (rc = grow_scratch(ctx, ctx->h_dense, 1, fn, "counters")))
-            return rc;
-    }
-    if ((rc = o2v::ctx_alloc_triangles(ctx, count, uvs != nullptr, types != nullptr, colors != nullptr, texids != nullptr))) return rc;
-    if (count) {
-        hipStream_t s = ctx->stream;
-        DenseCtr *const ctr = ctx->d_dense.ptr;
-        O2V_CHECK(hipMemsetAsync(ctr, 0, sizeof(DenseCtr), s));
-        if (!faces) O2V_CHECK(hipMemcpyAsync(ctx->d_verts.ptr, positions, count * 36u, hipMemcpyDeviceToDevice, s));
-        else {
-            const uint32_t grid = stream_grid(ctx, (count + 3u) / 4u * 64u, 8u);  // (one wave per 64 triangles)
-            if (index_bytes == 4)
-                hipLaunchKernelGGL(k_gather_tris<int32_t>, dim3(grid), dim3(kBlock), 0, s, positions, n_positions,
-                                   static_cast<const int32_t *>(faces), count, ctx->d_verts.ptr, ctr);
-            else
-                hipLaunchKernelGGL(k_gather_tris<int64_t>, dim3(grid), dim3(kBlock), 0, s, positions, n_positions,
-                                   static_cast<const int64_t *>(faces), count, ctx->d_verts.ptr, ctr);
-        }
-        if (uvs) O2V_CHECK(hipMemcpyAsync(ctx->d_uvs.ptr, uvs, count * 24u, hipMemcpyDeviceToDevice, s));
-        if (types) {
-            O2V_CHECK(hipMemcpyAsync(ctx->d_types.ptr, types, count * 4u, hipMemcpyDeviceToDevice, s));
-            hipLaunchKernelGGL(k_any_textured, dim3(stream_grid(ctx, count, 4u)), dim3(kBlock), 0, s, types, count, ctr);
-        }
-        if (colors) O2V_CHECK(hipMemcpyAsync(ctx->d_colors.ptr, colors, count * 12u, hipMemcpyDeviceToDevice, s));
-        if (texids) O2V_CHECK(hipMemcpyAsync(ctx->d_texids.ptr, texids, count * 4u, hipMemcpyDeviceToDevice, s));
-        O2V_CHECK(hipGetLastError());
-        O2V_CHECK(hipMemcpyAsync(ctx->h_dense.ptr, ctr, sizeof(DenseCtr), hipMemcpyDeviceToHost, s));
-    }
-    // (the flags come back in the round trip the upload's hints make anyway)
-    if ((rc = o2v::ctx_finish_triangles(ctx, false, nullptr))) return rc;
-    if (!count) return O2V_HIP_OK;
-    if (ctx->h_dense.ptr->bad_index) {
-        if ((rc = o2v::ctx_alloc_triangles(ctx, 0, false, false, false, false)) || (rc = o2v::ctx_finish_triangles(ctx, false, nullptr)))
-            return rc;
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "face index out of range: an index is negative, not below n_positions (" +
-                      std::to_string(n_positions) + ") or not below 2^32; the context holds no triangles");
-    }
-    ctx->any_textured = ctx->h_dense.ptr->textured != 0;
-    return O2V_HIP_OK;
-}
-
-int o2v_hip_write_dense(o2v_hip_ctx *ctx, void *dst, uint32_t format, const uint32_t origin[3], const uint32_t dims[3],
-                        const uint64_t strides[3], uint64_t *out_outside)
-{
-    static const char fn[] = "o2v_hip_write_dense";
-    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
-    if (!dst || !origin || !dims || !strides || format > O2V_HIP_DENSE_BITS)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument or unknown format");
-    if (!dims[0] || !dims[1] || !dims[2]) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "zero dims");
-    if (format == O2V_HIP_DENSE_BITS && strides[0] != 1) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "BITS needs strides[0] == 1");
-    O2V_CHECK(hipSetDevice(ctx->device));
-    // (BITS: x counted in 32-bit words; aliasing strides are the caller's business here)
-    const uint32_t box[3] = {format == O2V_HIP_DENSE_BITS ? (dims[0] - 1u) / 32u + 1u : dims[0], dims[1], dims[2]};
-    int rc;
-    if ((rc = check_grid(ctx, fn, "dst", dst, box, strides, format == O2V_HIP_DENSE_U8 ? 1u : 4u, false)) ||
-        (rc = grow_scratch(ctx, ctx->d_dense, 1, fn, "counters")) || (rc = grow_scratch(ctx, ctx->h_dense, 1, fn, "counters")))
-        return rc;
-    if (out_outside) *out_outside = 0;
-    const uint64_t n = ctx->n_vox;
-    if (!n) return O2V_HIP_OK;
-    hipStream_t s = ctx->stream;
-    DenseCtr *const ctr = ctx->d_dense.ptr;
-    const DenseBox b{origin[0], origin[1], origin[2], dims[0], dims[1], dims[2], strides[0], strides[1], strides[2]};
-    const uint64_t n_surf = n - std::min<uint64_t>(n, ctx->stats.interior_voxels);
-    O2V_CHECK(hipMemsetAsync(&ctr->outside, 0, sizeof(ctr->outside), s));
-    const dim3 grid(stream_grid(ctx, n, 8u));
-    if (format == O2V_HIP_DENSE_U8)
-        hipLaunchKernelGGL(k_dense_scatter<kDenseU8>, grid, dim3(kBlock), 0, s, ctx->d_out.ptr, n, n_surf, b, dst, ctr);
-    else if (format == O2V_HIP_DENSE_ARGB32)
-        hipLaunchKernelGGL(k_dense_scatter<kDenseArgb32>, grid, dim3(kBlock), 0, s, ctx->d_out.ptr, n, n_surf, b, dst, ctr);
-    else
-        hipLaunchKernelGGL(k_dense_scatter<kDenseBits>, grid, dim3(kBlock), 0, s, ctx->d_out.ptr, n, n_surf, b, dst, ctr);
-    O2V_CHECK(hipGetLastError());
-    O2V_CHECK(hipMemcpyAsync(&ctx->h_dense.ptr->outside, &ctr->outside, sizeof(ctr->outside), hipMemcpyDeviceToHost, s));
-    O2V_CHECK(hipStreamSynchronize(s));
-    if (out_outside) *out_outside = ctx->h_dense.ptr->outside;
-    return O2V_HIP_OK;
-}
-
-int o2v_hip_voxels_box(o2v_hip_ctx *ctx, uint32_t lo[3], uint32_t hi[3])
-{
-    if (!ctx || !lo || !hi) return O2V_HIP_ERR_BAD_ARGUMENT;
-    for (int a = 0; a < 3; ++a) lo[a] = hi[a] = 0;
-    const uint64_t n = ctx->n_vox;
-    if (!n) return O2V_HIP_OK;
-    O2V_CHECK(hipSetDevice(ctx->device));
-    static const char fn[] = "o2v_hip_voxels_box";
-    if (int rc; (rc = grow_scratch(ctx, ctx->d_dense, 1, fn, "counters")) || (rc = grow_scratch(ctx, ctx->h_dense, 1, fn, "counters")))
-        return rc;
-    hipStream_t s = ctx->stream;
-    DenseCtr *const ctr = ctx->d_dense.ptr;
-    O2V_CHECK(hipMemsetAsync(ctr->lo, 0xff, sizeof(ctr->lo), s));
-    O2V_CHECK(hipMemsetAsync(ctr->hi, 0, sizeof(ctr->hi), s));
-    hipLaunchKernelGGL(k_dense_box, dim3(stream_grid(ctx, n, 4u)), dim3(kBlock), 0, s, ctx->d_out.ptr, n, ctr);
-    O2V_CHECK(hipGetLastError());
-    O2V_CHECK(hipMemcpyAsync(ctx->h_dense.ptr->lo, ctr->lo, sizeof(ctr->lo) + sizeof(ctr->hi), hipMemcpyDeviceToHost, s));
-    O2V_CHECK(hipStreamSynchronize(s));
-    for (int a = 0; a < 3; ++a) lo[a] = ctx->h_dense.ptr->lo[a], hi[a] = ctx->h_dense.ptr->hi[a] + 1u;
-    return O2V_HIP_OK;
-}
-
-}  // extern "C"
-
-// ---- K8: the distance transform of a label grid ------------------------------------------------------------------------
-
-namespace {
-
-// Lanes of an envelope pass, one line each at a time: as many as the pass has lines, at most 2^17 (8 waves per CU of the
-// MI355X).  The pass's stacks take slots x (its line length) entries of the scratch.
-constexpr uint64_t kDistMaxSlots = 1u << 17;
-
-uint64_t dist_slots(uint64_t lines) { return std::min<uint64_t>(lines, kDistMaxSlots); }
-
-}  // namespace
-
-extern "C" {
-
-uint64_t o2v_hip_distance_scratch_bytes(const uint32_t dims[3], uint32_t format)
-{
-    (void) format;   // (both formats use the same stacks)
-    if (!dims || !dims[0] || !dims[1] || !dims[2]) return 0;
-    const uint64_t y = dist_slots((uint64_t) dims[0] * dims[2]) * dims[1], z = dist_slots((uint64_t) dims[0] * dims[1]) * dims[2];
-    return std::max(y, z) * sizeof(uint2);
-}
-
-int o2v_hip_distance_dense(o2v_hip_ctx *ctx, const void *labels, const uint64_t label_strides[3], void *dst, uint32_t format,
-                           const uint64_t dst_strides[3], const uint32_t dims[3])
-{
-    static const char fn[] = "o2v_hip_distance_dense";
-    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
-    if (!labels || !label_strides || !dst || !dst_strides || !dims || format > O2V_HIP_DIST_SDF_F32)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument or unknown format");
-    if (!dims[0] || !dims[1] || !dims[2]) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "zero dims");
-    uint64_t d2max = 0;
-    for (int a = 0; a < 3; ++a) d2max += (uint64_t) (dims[a] - 1u) * (dims[a] - 1u);
-    if (d2max > 0x7ffffffeull)
-        return refuse(ctx, O2V_HIP_ERR_LIMIT, fn,
-                      "(nx-1)^2 + (ny-1)^2 + (nz-1)^2 = " + std::to_string(d2max) + " does not fit below 2^31 - 1");
-    O2V_CHECK(hipSetDevice(ctx->device));
-    uint64_t lbytes = 0, dbytes = 0;
-    int rc;
-    if ((rc = check_grid(ctx, fn, "labels", labels, dims, label_strides, 1u, false, &lbytes)) ||
-        (rc = check_grid(ctx, fn, "dst", dst, dims, dst_strides, 4u, true, &dbytes)))
-        return rc;
-    if (ranges_overlap(labels, lbytes, dst, dbytes)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "labels and dst overlap");
-    if ((rc = grow_scratch(ctx, ctx->d_dist_stack, o2v_hip_distance_scratch_bytes(dims, format) / sizeof(uint2), fn, "scratch")))
-        return rc;
-    hipStream_t s = ctx->stream;
-    const DistGrid g{label_strides[0], label_strides[1], label_strides[2], dst_strides[0], dst_strides[1], dst_strides[2],
-                     dims[0], dims[1], dims[2]};
-    const uint8_t *const lab = static_cast<const uint8_t *>(labels);
-    int32_t *const out = static_cast<int32_t *>(dst);
-    uint2 *const stack = ctx->d_dist_stack.ptr;
-    // passes y and z: each with its own slots (the stride of its stacks); the lanes of the last block past them have no line
-    const uint64_t sy = dist_slots((uint64_t) dims[0] * dims[2]), sz = dist_slots((uint64_t) dims[0] * dims[1]);
-    const uint32_t gy = (uint32_t) ((sy + kBlock - 1) / kBlock), gz = (uint32_t) ((sz + kBlock - 1) / kBlock);
-    const uint64_t rows = (uint64_t) dims[1] * dims[2];
-    O2V_CHECK(ctx->dist_times.mark(0, s));
-    hipLaunchKernelGGL(k_dist_x, dim3((uint32_t) std::min<uint64_t>((uint64_t) ctx->num_cus * 8u, (rows + 3u) / 4u)), dim3(kBlock), 0, s,
-                       lab, out, g);
-    O2V_CHECK(ctx->dist_times.mark(1, s));
-    hipLaunchKernelGGL(k_dist_envelope<kDistY>, dim3(gy), dim3(kBlock), 0, s, out, lab, g, stack, sy);
-    O2V_CHECK(ctx->dist_times.mark(2, s));
-    if (format == O2V_HIP_DIST_SQ_I32)
-        hipLaunchKernelGGL(k_dist_envelope<kDistZ>, dim3(gz), dim3(kBlock), 0, s, out, lab, g, stack, sz);
-    else
-        hipLaunchKernelGGL(k_dist_envelope<kDistZSdf>, dim3(gz), dim3(kBlock), 0, s, out, lab, g, stack, sz);
-    O2V_CHECK(hipGetLastError());
-    O2V_CHECK(ctx->dist_times.mark(3, s));
-    O2V_CHECK(hipStreamSynchronize(s));
-    O2V_CHECK(ctx->dist_times.finish());
-    return O2V_HIP_OK;
-}
-
-int o2v_hip_distance_times(const o2v_hip_ctx *ctx, float out_ms[3])
-{
-    return ctx ? ctx->dist_times.read(out_ms) : O2V_HIP_ERR_BAD_ARGUMENT;
-}
-
-}  // extern "C"
-
-// ---- K15: the nearest seed voxel of every voxel, and its value -----------------------------------------------------------
-
-namespace {
-
-constexpr uint32_t kNearFlagsKnown = O2V_HIP_NEAREST_SEED_ONE | O2V_HIP_NEAREST_VALUES_INSIDE;
-
-template <uint32_t Format>
-void launch_near_x(o2v_hip_ctx *ctx, hipStream_t s, uint64_t rows, int32_t *out, const NearGrid &g)
-{
-    hipLaunchKernelGGL(k_near_x<Format>, dim3((uint32_t) std::min<uint64_t>((uint64_t) ctx->num_cus * 8u, (rows + 3u) / 4u)), dim3(kBlock), 0, s,
-                       out, g);
-}
-
-}  // namespace
-
-extern "C" {
-
-uint64_t o2v_hip_nearest_scratch_bytes(const uint32_t dims[3]) { return o2v_hip_distance_scratch_bytes(dims, O2V_HIP_DIST_SQ_I32); }
-
-int o2v_hip_nearest_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
-                          uint32_t flags, int32_t *nearest, const uint64_t nearest_strides[3], int32_t *dist2, const uint64_t dist2_strides[3],
-                          int32_t *values, const uint64_t value_strides[3], uint32_t max_dist2)
-{
-    static const char fn[] = "o2v_hip_nearest_dense";
-    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
-    if (!nearest || !nearest_strides || (dist2 && !dist2_strides) || (values && !value_strides))
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    SetGrid sg;
-    int rc;
-    if ((rc = set_grid_args(ctx, fn, grid, format, strides, dims, level, &sg))) return rc;
-    if (flags & ~kNearFlagsKnown) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown flag bits in " + std::to_string(flags));
-    const unsigned __int128 voxels = (unsigned __int128) dims[0] * dims[1] * dims[2];
-    if (voxels > 0x7fffffffull)
-        return refuse(ctx, O2V_HIP_ERR_LIMIT, fn,
-                      std::to_string(dims[0]) + " x " + std::to_string(dims[1]) + " x " + std::to_string(dims[2]) +
-                          " voxels do not fit an int32 index (at most 2^31 - 1)");
-    uint64_t d2max = 0;
-    for (int a = 0; a < 3; ++a) d2max += (uint64_t) (dims[a] - 1u) * (dims[a] - 1u);
-    if (d2max > 0x7ffffffeull)
-        return refuse(ctx, O2V_HIP_ERR_LIMIT, fn,
-                      "(nx-1)^2 + (ny-1)^2 + (nz-1)^2 = " + std::to_string(d2max) + " does not fit below 2^31 - 1");
-    if (format != O2V_HIP_GRID_U8 && flags)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "SEED_ONE and VALUES_INSIDE need a U8 grid");
-    // (the size limits stand before the look at the grid's memory: a box that is too large is refused as that, whatever it reaches)
-    if ((rc = set_grid_memory(ctx, fn, &sg))) return rc;
-    Span spans[4] = {{"nearest", nearest, 0}, {"dist2", dist2, 0}, {"values", values, 0}, {"grid", grid, sg.bytes}};
-    const uint64_t *const out_strides[3] = {nearest_strides, dist2_strides, value_strides};
-    for (int i = 0; i < 3; ++i)
-        if (spans[i].p && (rc = check_grid(ctx, fn, spans[i].what, spans[i].p, dims, out_strides[i], 4u, true, &spans[i].bytes))) return rc;
-    if ((rc = refuse_overlap(ctx, fn, spans, 3))) return rc;
-    if ((rc = grow_scratch(ctx, ctx->d_dist_stack, o2v_hip_nearest_scratch_bytes(dims) / sizeof(uint2), fn, "scratch"))) return rc;
-    hipStream_t s = ctx->stream;
-    const NearGrid g{grid, strides[0], strides[1], strides[2], level, nearest_strides[0], nearest_strides[1], nearest_strides[2],
-                     dims[0], dims[1], dims[2]};
-    NearOut o{};
-    if (dist2) o.dist2 = dist2, o.e0 = dist2_strides[0], o.e1 = dist2_strides[1], o.e2 = dist2_strides[2];
-    if (values) o.values = values, o.v0 = value_strides[0], o.v1 = value_strides[1], o.v2 = value_strides[2];
-    o.max_dist2 = max_dist2;
-    uint2 *const stack = ctx->d_dist_stack.ptr;
-    // passes y and z: each with its own slots (the stride of its stacks), as K8's
-    const uint64_t sy = dist_slots((uint64_t) dims[0] * dims[2]), sz = dist_slots((uint64_t) dims[0] * dims[1]);
-    const uint32_t gy = (uint32_t) ((sy + kBlock - 1) / kBlock), gz = (uint32_t) ((sz + kBlock - 1) / kBlock);
-    const uint64_t rows = (uint64_t) dims[1] * dims[2];
-    O2V_CHECK(ctx->near_times.mark(0, s));
-    if (format == O2V_HIP_GRID_BITS)
-        launch_near_x<kNearBits>(ctx, s, rows, nearest, g);
-    else if (format == O2V_HIP_GRID_F32_BELOW)
-        launch_near_x<kNearF32Below>(ctx, s, rows, nearest, g);
-    else if (flags & O2V_HIP_NEAREST_SEED_ONE)
-        launch_near_x<kNearU8One>(ctx, s, rows, nearest, g);
-    else
-        launch_near_x<kNearU8>(ctx, s, rows, nearest, g);
-    O2V_CHECK(ctx->near_times.mark(1, s));
-    hipLaunchKernelGGL((k_near_envelope<kNearY, kNearNoPaint>), dim3(gy), dim3(kBlock), 0, s, nearest, g, o, stack, sy);
-    O2V_CHECK(ctx->near_times.mark(2, s));
-    if (!values)
-        hipLaunchKernelGGL((k_near_envelope<kNearZ, kNearNoPaint>), dim3(gz), dim3(kBlock), 0, s, nearest, g, o, stack, sz);
-    else if (flags & O2V_HIP_NEAREST_VALUES_INSIDE)
-        hipLaunchKernelGGL((k_near_envelope<kNearZ, kNearPaintInside>), dim3(gz), dim3(kBlock), 0, s, nearest, g, o, stack, sz);
-    else
-        hipLaunchKernelGGL((k_near_envelope<kNearZ, kNearPaint>), dim3(gz), dim3(kBlock), 0, s, nearest, g, o, stack, sz);
-    O2V_CHECK(hipGetLastError());
-    O2V_CHECK(ctx->near_times.mark(3, s));
-    O2V_CHECK(hipStreamSynchronize(s));
-    O2V_CHECK(ctx->near_times.finish());
-    return O2V_HIP_OK;
-}
-
-int o2v_hip_nearest_times(const o2v_hip_ctx *ctx, float out_ms[3])
-{
-    return ctx ? ctx->near_times.read(out_ms) : O2V_HIP_ERR_BAD_ARGUMENT;
-}
-
-}  // extern "C"
-
-// ---- K9: narrow-band distance to the triangles -------------------------------------------------------------------------
-
-namespace {
-
-constexpr uint32_t kMdMaxDim = 65535;       // voxels per axis of one box (O2V_HIP_ERR_LIMIT above)
-constexpr uint64_t kMdMaxGrid = 1ull << 24; // workgroups of k_meshdist_tiles; more tiles are taken in turns
-
-}  // namespace
-
-extern "C" {
-
-int o2v_hip_mesh_distance_dense(o2v_hip_ctx *ctx, const o2v_hip_params *params, float band, uint32_t format,
-                                const uint32_t origin[3], const uint32_t dims[3], float *dst, const uint64_t dst_strides[3],
-                                int32_t *closest, const uint64_t closest_strides[3])
-{
-    static const char fn[] = "o2v_hip_mesh_distance_dense";
-    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
-    if (!params || !origin || !dims || !dst || !dst_strides || (closest && !closest_strides) || format > O2V_HIP_MESH_DIST_SIGNED_F32)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument or unknown format");
-    if (!(std::isfinite(band) && band > 0.f && band <= 32.f))
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "band must be finite, above 0 and at most 32 voxels");
-    const uint32_t ss = params->supersampling ? params->supersampling : 1u;
-    if (ss > 2u || params->resolution == 0u)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "resolution must be positive and supersampling 1 or 2");
-    if (params->z_begin || params->z_end || params->x_begin || params->x_end || params->y_begin || params->y_end)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "the slab and tile fields of params must be 0 (the box is origin, dims)");
-    for (int a = 0; a < 3; ++a) {
-        if (!dims[a] || (uint64_t) origin[a] + dims[a] > params->resolution)
-            return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "the box must have dims >= 1 and lie within the grid");
-        if (dims[a] > kMdMaxDim) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "a box of more than 65 535 voxels along an axis");
-    }
-    O2V_CHECK(hipSetDevice(ctx->device));
-    ctx->ktimes_on = false;   // (no per-launch brackets here; o2v_hip_voxelize sets the flag again from its params)
-    uint64_t dbytes = 0, cbytes = 0;
-    int rc;
-    if ((rc = check_grid(ctx, fn, "dst", dst, dims, dst_strides, 4u, true, &dbytes)) ||
-        (closest && (rc = check_grid(ctx, fn, "closest", closest, dims, closest_strides, 4u, true, &cbytes))))
-        return rc;
-    if (closest && ranges_overlap(dst, dbytes, closest, cbytes)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "dst and closest overlap");
-
-    const uint64_t T = ctx->n_tris;
-    MdBox b{};
-    b.x0 = origin[0];
-    b.y0 = origin[1];
-    b.z0 = origin[2];
-    b.nx = dims[0];
-    b.ny = dims[1];
-    b.nz = dims[2];
-    b.tx = (b.nx + kMdTile - 1) / kMdTile;
-    b.ty = (b.ny + kMdTile - 1) / kMdTile;
-    b.tz = (b.nz + kMdTile - 1) / kMdTile;
-    b.ss = ss;
-    b.margin = (double) band * ss + ss;
-    b.bs2 = (double) band * band * ss * ss;
-    b.band = band;
-    b.n_tiles = (uint64_t) b.tx * b.ty * b.tz;
-    // the transform k_setup computes for these params (compute_mesh_transform of the caller's bounds or the mesh's own, which
-    // the upload reduced with k_bounds), as grid_box takes it
-    Affine xf{};
-    if (T) {
-        const float *e = params->bounds_known ? params->bounds : ctx->mesh_bounds_hint;
-        xf = compute_mesh_transform(V3{e[0], e[1], e[2]}, V3{e[3], e[4], e[5]}, params->resolution * ss, params->unit_transform);
-    }
-    const uint64_t tile_blocks = (b.n_tiles + kBlock - 1) / kBlock;
-    if ((rc = grow_scratch(ctx, ctx->d_md_sv, T * 9u, fn, "vertices")) || (rc = grow_scratch(ctx, ctx->d_md_counts, b.n_tiles, fn, "tile counters")) ||
-        (rc = grow_scratch(ctx, ctx->d_md_first, b.n_tiles + 1u, fn, "tile offsets")) ||
-        (rc = grow_scratch(ctx, ctx->d_md_blocks, tile_blocks, fn, "block sums")) || (rc = grow_scratch(ctx, ctx->d_md_ctr, 1u, fn, "counter")) ||
-        (rc = grow_scratch(ctx, ctx->h_md_ctr, 1u, fn, "counter")))
-        return rc;
-    hipStream_t s = ctx->stream;
-    const uint64_t tri_blocks = (T + kBlock - 1) / kBlock;
-
-    // binning: (triangle, tile) pairs counted, scanned, scattered into per-tile lists
-    O2V_CHECK(ctx->md_times.mark(0, s));
-    O2V_CHECK(hipMemsetAsync(ctx->d_md_counts.ptr, 0, b.n_tiles * sizeof(uint32_t), s));
-    if (T)
-        O2V_LAUNCH("k_meshdist_bin_count", s, k_meshdist_bin_count, dim3((uint32_t) tri_blocks), dim3(kBlock), 0, s, ctx->d_verts.ptr, T, xf, b,
-                   ctx->d_md_sv.ptr, ctx->d_md_counts.ptr);
-    O2V_LAUNCH("k_meshdist_tile_sums", s, k_meshdist_tile_sums, dim3((uint32_t) tile_blocks), dim3(kBlock), 0, s, ctx->d_md_counts.ptr, b.n_tiles,
-               ctx->d_md_blocks.ptr);
-    O2V_LAUNCH("k_fill_scan_blocks", s, k_fill_scan_blocks, dim3(1), dim3(kBlock), 0, s, ctx->d_md_blocks.ptr, tile_blocks, ctx->d_md_ctr.ptr);
-    O2V_LAUNCH("k_meshdist_tile_offsets", s, k_meshdist_tile_offsets, dim3((uint32_t) ((b.n_tiles + kBlock) / kBlock)), dim3(kBlock), 0, s,
-               ctx->d_md_counts.ptr, b.n_tiles, ctx->d_md_blocks.ptr, ctx->d_md_ctr.ptr, ctx->d_md_first.ptr);
-    O2V_CHECK(hipMemcpyAsync(ctx->h_md_ctr.ptr, ctx->d_md_ctr.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    O2V_CHECK(hipStreamSynchronize(s));
-    const uint64_t n_pairs = ctx->h_md_ctr.ptr[0];
-    if ((rc = grow_scratch(ctx, ctx->d_md_lists, n_pairs, fn, "triangle lists"))) return rc;
-    if (n_pairs)
-        O2V_LAUNCH("k_meshdist_bin_scatter", s, k_meshdist_bin_scatter, dim3((uint32_t) tri_blocks), dim3(kBlock), 0, s, ctx->d_md_sv.ptr, T, b,
-                   ctx->d_md_first.ptr, ctx->d_md_counts.ptr, ctx->d_md_lists.ptr);
-    O2V_CHECK(ctx->md_times.mark(1, s));
-
-    // parity (signed): K6's bitmap of the box, no unmark step
-    const uint32_t *bits = nullptr;
-    if (format == O2V_HIP_MESH_DIST_SIGNED_F32 && T) {
-        if ((rc = parity_bits(ctx, xf, fill_box(origin, dims, ss, 0u)))) {
-            (void) hipGetLastError();
-            return rc;
-        }
-        bits = ctx->d_fill_bits.ptr;
-    }
-    O2V_CHECK(ctx->md_times.mark(2, s));
-
-    // distance: one workgroup per tile
-    O2V_LAUNCH("k_meshdist_tiles", s, k_meshdist_tiles, dim3((uint32_t) std::min<uint64_t>(b.n_tiles, kMdMaxGrid)), dim3(kBlock), 0, s,
-               ctx->d_md_sv.ptr, b, ctx->d_md_first.ptr, ctx->d_md_lists.ptr, bits, dst, dst_strides[0], dst_strides[1], dst_strides[2],
-               closest, closest ? closest_strides[0] : 0u, closest ? closest_strides[1] : 0u, closest ? closest_strides[2] : 0u);
-    O2V_CHECK(hipGetLastError());
-    O2V_CHECK(ctx->md_times.mark(3, s));
-    O2V_CHECK(hipStreamSynchronize(s));
-    O2V_CHECK(ctx->md_times.finish());
-    return O2V_HIP_OK;
-}
-
-int o2v_hip_mesh_distance_times(const o2v_hip_ctx *ctx, float out_ms[3])
-{
-    return ctx ? ctx->md_times.read(out_ms) : O2V_HIP_ERR_BAD_ARGUMENT;
-}
-
-}  // extern "C"
-
-// ---- K10: the level set of a dense grid as an indexed mesh --------------------------------------------------------------
-
-namespace {
-
-constexpr uint32_t kSurfMaxExtent = 65536;        // origin + dims per axis (O2V_HIP_ERR_LIMIT above): positions exact to 2^-7 voxel
-constexpr uint64_t kSurfMaxVertices = 0x7fffffffull;
-constexpr uint64_t kSurfMaxGrid = 1ull << 20;     // workgroups of the per-block kernels; more blocks are taken in turns
-
-// what o2v_hip_surface_count and _write both check of the grid; *g: its words
-int surf_grid(o2v_hip_ctx *ctx, const char *fn, const float *field, const uint64_t strides[3], const uint32_t dims[3], float level,
-              SurfGrid *g, uint64_t *field_bytes)
-{
-    if (!field || !strides || !dims) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    if (!dims[0] || !dims[1] || !dims[2]) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "zero dims");
-    if (!std::isfinite(level)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "level must be finite");
-    for (int a = 0; a < 3; ++a)
-        if (dims[a] > kSurfMaxExtent) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "a grid of more than 65 536 samples along an axis");
-    O2V_CHECK(hipSetDevice(ctx->device));
-    if (int rc = check_grid(ctx, fn, "field", field, dims, strides, 4u, false, field_bytes)) return rc;
-    g->s0 = strides[0];
-    g->s1 = strides[1];
-    g->s2 = strides[2];
-    g->nx = dims[0];
-    g->ny = dims[1];
-    g->nz = dims[2];
-    g->W = (dims[0] + 63u) / 64u;
-    g->items = (uint64_t) dims[1] * dims[2] * g->W;
-    g->n_blocks = (g->items + kBlock - 1) / kBlock;
-    g->level = level;
-    return O2V_HIP_OK;
-}
-
-uint32_t surf_blocks(const SurfGrid &g) { return (uint32_t) std::min<uint64_t>(g.n_blocks, kSurfMaxGrid); }
-
-}  // namespace
-
-extern "C" {
-
-int o2v_hip_surface_count(o2v_hip_ctx *ctx, const float *field, const uint64_t strides[3], const uint32_t dims[3], float level,
-                          uint64_t *out_vertices, uint64_t *out_triangles)
-{
-    static const char fn[] = "o2v_hip_surface_count";
-    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
-    if (!out_vertices || !out_triangles) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    ctx->sf.valid = false;
-    SurfGrid g{};
-    uint64_t fbytes = 0;
-    int rc;
-    if ((rc = surf_grid(ctx, fn, field, strides, dims, level, &g, &fbytes))) return rc;
-    ctx->ktimes_on = false;   // (no per-launch brackets here; o2v_hip_voxelize sets the flag again from its params)
-    if ((rc = grow_scratch(ctx, ctx->d_sf_signs, g.items, fn, "sign words")) || (rc = grow_scratch(ctx, ctx->d_sf_active, g.items, fn, "cell words")) ||
-        (rc = grow_scratch(ctx, ctx->d_sf_local, g.items, fn, "prefixes")) || (rc = grow_scratch(ctx, ctx->d_sf_voff, g.n_blocks + 1u, fn, "vertex offsets")) ||
-        (rc = grow_scratch(ctx, ctx->d_sf_qoff, g.n_blocks + 1u, fn, "quad offsets")) || (rc = grow_scratch(ctx, ctx->h_sf_ctr, 2u, fn, "counters")))
-        return rc;
-    hipStream_t s = ctx->stream;
-    unsigned long long *const voff = ctx->d_sf_voff.ptr, *const qoff = ctx->d_sf_qoff.ptr;
-    O2V_CHECK(ctx->sf_times.mark(0, s));
-    O2V_LAUNCH("k_surf_signs", s, k_surf_signs, dim3(stream_grid(ctx, (g.items + kSurfInFlight - 1) / kSurfInFlight * 64u, 8u)), dim3(kBlock), 0, s,
-               field, g, ctx->d_sf_signs.ptr);
-    O2V_CHECK(ctx->sf_times.mark(1, s));
-    O2V_LAUNCH("k_surf_count", s, k_surf_count, dim3(surf_blocks(g)), dim3(kBlock), 0, s, ctx->d_sf_signs.ptr, g, ctx->d_sf_active.ptr,
-               ctx->d_sf_local.ptr, voff, qoff);
-    // (the totals go behind the offsets: entry n_blocks)
-    O2V_LAUNCH("k_fill_scan_blocks", s, k_fill_scan_blocks, dim3(1), dim3(kBlock), 0, s, voff, g.n_blocks, voff + g.n_blocks);
-    O2V_LAUNCH("k_fill_scan_blocks", s, k_fill_scan_blocks, dim3(1), dim3(kBlock), 0, s, qoff, g.n_blocks, qoff + g.n_blocks);
-    O2V_CHECK(hipGetLastError());
-    O2V_CHECK(ctx->sf_times.mark(2, s));
-    O2V_CHECK(hipMemcpyAsync(ctx->h_sf_ctr.ptr, voff + g.n_blocks, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    O2V_CHECK(hipMemcpyAsync(ctx->h_sf_ctr.ptr + 1, qoff + g.n_blocks, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    O2V_CHECK(hipStreamSynchronize(s));
-    O2V_CHECK(ctx->sf_times.elapsed(0, 1, ctx->sf_times.ms[0]));
-    O2V_CHECK(ctx->sf_times.elapsed(1, 2, ctx->sf_times.ms[1]));
-    ctx->sf_times.ms[2] = ctx->sf_times.ms[3] = 0.f;
-    const uint64_t V = ctx->h_sf_ctr.ptr[0], Q = ctx->h_sf_ctr.ptr[1];
-    if (V > kSurfMaxVertices)
-        return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, std::to_string(V) + " vertices do not fit an int32 index (at most 2^31 - 1)");
-    ctx->sf.valid = true;
-    ctx->sf.key = GridKey(field, 0u, strides, dims, level);
-    ctx->sf.vertices = V;
-    ctx->sf.quads = Q;
-    *out_vertices = V;
-    *out_triangles = 2u * Q;
-    return O2V_HIP_OK;
-}
-
-int o2v_hip_surface_write(o2v_hip_ctx *ctx, const float *field, const uint64_t strides[3], const uint32_t dims[3], float level,
-                          const uint32_t origin[3], float *positions, uint64_t vertex_capacity, int32_t *faces, uint64_t triangle_capacity)
-{
-    static const char fn[] = "o2v_hip_surface_write";
-    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
-    if (!origin) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    SurfGrid g{};
-    uint64_t fbytes = 0;
-    int rc;
-    if ((rc = surf_grid(ctx, fn, field, strides, dims, level, &g, &fbytes))) return rc;
-    for (int a = 0; a < 3; ++a)
-        if ((uint64_t) origin[a] + dims[a] > kSurfMaxExtent)
-            return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "origin + dims is above 65 536 samples along an axis");
-    const o2v_hip_ctx::SurfaceCount &c = ctx->sf;
-    if (!c.valid || !(c.key == GridKey(field, 0u, strides, dims, level)))
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "no matching o2v_hip_surface_count (the same field, strides, dims and level)");
-    const uint64_t V = c.vertices, T = 2u * c.quads;
-    if (vertex_capacity < V || triangle_capacity < T)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn,
-                      "capacities " + std::to_string(vertex_capacity) + ", " + std::to_string(triangle_capacity) + " are below the counted " +
-                          std::to_string(V) + " vertices, " + std::to_string(T) + " triangles");
-    if ((V && !positions) || (T && !faces)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    if ((V && (rc = check_device_range(ctx, fn, positions, V * 12u, "positions"))) || (T && (rc = check_device_range(ctx, fn, faces, T * 12u, "faces"))))
-        return rc;
-    const Span spans[] = {{"positions", positions, V * 12u}, {"faces", faces, T * 12u}, {"field", field, fbytes}};
-    if ((rc = refuse_overlap(ctx, fn, spans, 2))) return rc;
-    ctx->ktimes_on = false;
-    hipStream_t s = ctx->stream;
-    O2V_CHECK(ctx->sf_times.mark(2, s));
-    if (V && g.s0 == 1u)
-        O2V_LAUNCH("k_surf_vertices", s, k_surf_vertices<true>, dim3(surf_blocks(g)), dim3(kBlock), 0, s, field, g, ctx->d_sf_signs.ptr,
-                   ctx->d_sf_active.ptr, ctx->d_sf_local.ptr, ctx->d_sf_voff.ptr, origin[0], origin[1], origin[2], positions);
-    else if (V)
-        O2V_LAUNCH("k_surf_vertices", s, k_surf_vertices<false>, dim3(surf_blocks(g)), dim3(kBlock), 0, s, field, g, ctx->d_sf_signs.ptr,
-                   ctx->d_sf_active.ptr, ctx->d_sf_local.ptr, ctx->d_sf_voff.ptr, origin[0], origin[1], origin[2], positions);
-    O2V_CHECK(ctx->sf_times.mark(3, s));
-    if (T)
-        O2V_LAUNCH("k_surf_faces", s, k_surf_faces, dim3(surf_blocks(g)), dim3(kBlock), 0, s, g, ctx->d_sf_signs.ptr, ctx->d_sf_active.ptr,
-                   ctx->d_sf_local.ptr, ctx->d_sf_voff.ptr, ctx->d_sf_qoff.ptr, faces);
-    O2V_CHECK(hipGetLastError());
-    O2V_CHECK(ctx->sf_times.mark(4, s));
-    O2V_CHECK(hipStreamSynchronize(s));
-    O2V_CHECK(ctx->sf_times.elapsed(2, 3, ctx->sf_times.ms[2]));
-    O2V_CHECK(ctx->sf_times.elapsed(3, 4, ctx->sf_times.ms[3]));
-    return O2V_HIP_OK;
-}
-
-int o2v_hip_surface_times(const o2v_hip_ctx *ctx, float out_ms[4])
-{
-    return ctx ? ctx->sf_times.read(out_ms) : O2V_HIP_ERR_BAD_ARGUMENT;
-}
-
-}  // extern "C"
-
-// ---- K11: rays through a dense grid ----------------------------------------------------------------------------------------
-
-namespace {
-
-constexpr uint32_t kRayMaxExtent = 65536;        // origin + dims per axis (O2V_HIP_ERR_LIMIT above)
-constexpr uint64_t kRayMaxRays = 0x7fffffffull;
-
-// the words of the three levels over dims: 4^3 bricks, 16^3 blocks, 64^3 blocks
-void ray_levels(const uint32_t dims[3], uint64_t words[3], uint32_t per_axis[3][3])
-{
-    for (int l = 0; l < 3; ++l) {
-        words[l] = 1;
-        for (int a = 0; a < 3; ++a) {
-            const uint32_t step = 4u << (2 * l);
-            per_axis[l][a] = (uint32_t) (((uint64_t) dims[a] + step - 1u) / step);
-            words[l] *= per_axis[l][a];
-        }
-    }
-}
-
-RayGrid ray_grid(const o2v_hip_ctx *ctx)
-{
-    RayGrid g{};
-    uint64_t words[3];
-    uint32_t per_axis[3][3];
-    ray_levels(ctx->ray.dims, words, per_axis);
-    for (int a = 0; a < 3; ++a) {
-        g.org[a] = (int32_t) ctx->ray.origin[a];
-        g.dim[a] = (int32_t) ctx->ray.dims[a];
-        g.b0[a] = per_axis[0][a];
-        g.b1[a] = per_axis[1][a];
-        g.b2[a] = per_axis[2][a];
-    }
-    g.m0 = ctx->d_ray_masks.ptr;
-    g.m1 = g.m0 + words[0];
-    g.m2 = g.m1 + words[1];
-    return g;
-}
-
-}  // namespace
-
-extern "C" {
-
-uint64_t o2v_hip_raycast_scratch_bytes(const uint32_t dims[3])
-{
-    if (!dims || !dims[0] || !dims[1] || !dims[2]) return 0;
-    uint64_t words[3];
-    uint32_t per_axis[3][3];
-    ray_levels(dims, words, per_axis);
-    return 8u * (words[0] + words[1] + words[2]);
-}
-
-int o2v_hip_raycast_build(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
-                          const uint32_t origin[3])
-{
-    static const char fn[] = "o2v_hip_raycast_build";
-    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
-    ctx->ray.valid = false;
-    ++ctx->ray.generation;
-    SetGrid sg;
-    int rc;
-    if ((rc = set_grid(ctx, fn, grid, format, strides, dims, level, &sg))) return rc;
-    if (!origin) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    for (int a = 0; a < 3; ++a)
-        if ((uint64_t) origin[a] + dims[a] > kRayMaxExtent) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "origin + dims is above 65 536 voxels along an axis");
-    if ((rc = grow_scratch(ctx, ctx->d_ray_masks, o2v_hip_raycast_scratch_bytes(dims) / 8u, fn, "snapshot"))) return rc;
-    ctx->ktimes_on = false;   // (no per-launch brackets here; o2v_hip_voxelize sets the flag again from its params)
-    std::copy(dims, dims + 3, ctx->ray.dims);
-    std::copy(origin, origin + 3, ctx->ray.origin);
-    const RayGrid g = ray_grid(ctx);
-    uint64_t words[3];
-    uint32_t per_axis[3][3];
-    ray_levels(dims, words, per_axis);
-    unsigned long long *const m0 = ctx->d_ray_masks.ptr, *const m1 = m0 + words[0], *const m2 = m1 + words[1];
-    const RaySource src = sg.source();
-    const uint64_t tiles = (uint64_t) ((dims[0] + 63u) / 64u) * per_axis[0][1] * per_axis[0][2];
-    const dim3 blocks(stream_grid(ctx, tiles * 64u, 8u));
-    hipStream_t s = ctx->stream;
-    O2V_CHECK(ctx->ray_build_times.mark(0, s));
-    O2V_CHECK(hipMemsetAsync(m1, 0, words[1] * 8u, s));
-    with_set_format(sg, [&](auto fmt, auto vec) {
-        O2V_LAUNCH("k_ray_build", s, (k_ray_build<decltype(fmt)::value, decltype(vec)::value>), blocks, dim3(kBlock), 0, s, src, g, m0, m1);
-    });
-    O2V_LAUNCH("k_ray_build_top", s, k_ray_build_top, dim3(stream_grid(ctx, words[2], 8u)), dim3(kBlock), 0, s, g, m1, m2);
-    O2V_CHECK(hipGetLastError());
-    O2V_CHECK(ctx->ray_build_times.mark(1, s));
-    O2V_CHECK(hipStreamSynchronize(s));
-    O2V_CHECK(ctx->ray_build_times.finish());
-    ctx->ray.valid = true;
-    return O2V_HIP_OK;
-}
-
-int o2v_hip_raycast(o2v_hip_ctx *ctx, const float *origins, const float *directions, uint64_t n, float t_max, int32_t *hit, float *t)
-{
-    static const char fn[] = "o2v_hip_raycast";
-    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
-    const Switches sw = read_switches();
-    if (!(t_max >= 0.f)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "t_max must be >= 0 or +inf");
-    if (n > kRayMaxRays) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "more than 2^31 - 1 rays");
-    if (!ctx->ray.valid) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "no o2v_hip_raycast_build");
-    if (n == 0) return O2V_HIP_OK;
-    if (!origins || !directions || !hit || !t) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    O2V_CHECK(hipSetDevice(ctx->device));
-    int rc;
-    if ((rc = check_device_range(ctx, fn, origins, n * 12u, "origins")) || (rc = check_device_range(ctx, fn, directions, n * 12u, "directions")) ||
-        (rc = check_device_range(ctx, fn, hit, n * 16u, "hit")) || (rc = check_device_range(ctx, fn, t, n * 4u, "t")))
-        return rc;
-    const Span spans[] = {{"hit", hit, n * 16u}, {"t", t, n * 4u}, {"origins", origins, n * 12u}, {"directions", directions, n * 12u}};
-    if ((rc = refuse_overlap(ctx, fn, spans, 2))) return rc;
-    ctx->ktimes_on = false;
-    const RayGrid g = ray_grid(ctx);
-    const dim3 blocks((uint32_t) ((n + kBlock - 1) / kBlock));
-    hipStream_t s = ctx->stream;
-    O2V_CHECK(ctx->ray_cast_times.mark(0, s));
-    if (sw.ray_no_skip)
-        O2V_LAUNCH("k_ray_cast", s, k_ray_cast<false>, blocks, dim3(kBlock), 0, s, origins, directions, n, t_max, g, hit, t);
-    else
-        O2V_LAUNCH("k_ray_cast", s, k_ray_cast<true>, blocks, dim3(kBlock), 0, s, origins, directions, n, t_max, g, hit, t);
-    O2V_CHECK(hipGetLastError());
-    O2V_CHECK(ctx->ray_cast_times.mark(1, s));
-    O2V_CHECK(hipStreamSynchronize(s));
-    O2V_CHECK(ctx->ray_cast_times.finish());
-    return O2V_HIP_OK;
-}
-
-int o2v_hip_raycast_times(const o2v_hip_ctx *ctx, float out_ms[2])
-{
-    if (!ctx || !out_ms) return O2V_HIP_ERR_BAD_ARGUMENT;
-    out_ms[0] = ctx->ray_build_times.ms[0];
-    out_ms[1] = ctx->ray_cast_times.ms[0];
-    return O2V_HIP_OK;
-}
-
-uint64_t o2v_hip_raycast_generation(const o2v_hip_ctx *ctx) { return ctx ? ctx->ray.generation : 0; }
-
-}  // extern "C"
-
-// ---- K12: connected components and flood fill of a dense grid ---------------------------------------------------------------
-
-namespace {
-
-constexpr uint32_t kCcMaxDim = 65536;
-constexpr uint64_t kCcMaxVoxels = 0x7fffffffull;   // a linear index and a label are one int32
-constexpr uint64_t kCcMaxGrid = 1ull << 20;        // workgroups of k_cc_tiles; more tiles are taken in turns
-constexpr uint32_t kCcFlagsKnown = O2V_HIP_CC_INVERT | O2V_HIP_CC_SEED_BORDER | O2V_HIP_FLAG_STAGE_TIMES;
-
-uint64_t cc_words(const uint32_t dims[3]) { return (uint64_t) ((dims[0] + 63u) / 64u) * dims[1] * dims[2]; }
-
-// k_cc_classify on the context's stream, for K12, K13 and K14: the set (its complement inside the box if invert) as one bit per
-// voxel, words of 64 voxels along x, [z][y][W].
-void launch_classify(o2v_hip_ctx *ctx, const SetGrid &sg, uint32_t invert, unsigned long long *bits)
-{
-    const uint32_t *const dims = sg.key.dims;
-    CcGrid g{};   // (what the kernel reads of it)
-    g.nx = dims[0], g.ny = dims[1], g.nz = dims[2], g.W = (dims[0] + 63u) / 64u, g.words = cc_words(dims);
-    const RaySource src = sg.source();
-    const dim3 per_group(stream_grid(ctx, (g.words + 15u) / 16u * 64u, 8u));
-    hipStream_t s = ctx->stream;
-    with_set_format(sg, [&](auto format, auto vec) {
-        O2V_LAUNCH("k_cc_classify", s, (k_cc_classify<decltype(format)::value, decltype(vec)::value>), per_group, dim3(kBlock), 0, s, src, g, invert, bits);
-    });
-}
-
-// What the two calls share.  labels != null: o2v_hip_components_dense; else o2v_hip_flood_dense.
-int cc_run(o2v_hip_ctx *ctx, const char *fn, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
-           uint32_t connectivity, uint32_t flags, int32_t *labels, uint8_t *out, const uint64_t out_strides[3], const int32_t *seeds,
-           uint64_t n_seeds, const uint8_t values[3], uint64_t *result)
-{
-    const Switches sw = read_switches();
-    if (!out_strides || !result || (!labels && !out) || (out && !values) || (n_seeds && !seeds))
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    SetGrid sg;
-    int rc;
-    if ((rc = set_grid(ctx, fn, grid, format, strides, dims, level, &sg))) return rc;
-    if (connectivity != 6u && connectivity != 18u && connectivity != 26u)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "connectivity must be 6, 18 or 26, not " + std::to_string(connectivity));
-    if ((flags & ~kCcFlagsKnown) || (labels && (flags & O2V_HIP_CC_SEED_BORDER)))
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown flag bits in " + std::to_string(flags));
-    for (int a = 0; a < 3; ++a)
-        if (dims[a] > kCcMaxDim) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "a grid of more than 65 536 voxels along an axis");
-    const uint64_t voxels = (uint64_t) dims[0] * dims[1] * dims[2];   // (below 2^48)
-    if (voxels > kCcMaxVoxels)
-        return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, std::to_string(voxels) + " voxels do not fit an int32 index (at most 2^31 - 1)");
-    if (n_seeds > kCcMaxVoxels) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "more than 2^31 - 1 seeds");
-    uint64_t obytes = 0;
-    if ((rc = labels ? check_grid(ctx, fn, "labels", labels, dims, out_strides, 4u, true, &obytes)
-                     : check_grid(ctx, fn, "out", out, dims, out_strides, 1u, true, &obytes)) ||
-        (n_seeds && (rc = check_device_range(ctx, fn, seeds, n_seeds * 12u, "seeds"))))
-        return rc;
-    const Span spans[] = {{labels ? "labels" : "out", labels ? (const void *) labels : (const void *) out, obytes}, {"grid", grid, sg.bytes},
-                          {"seeds", seeds, n_seeds * 12u}};
-    if ((rc = refuse_overlap(ctx, fn, spans, 1))) return rc;
-
-    CcGrid g{};
-    g.nx = dims[0], g.ny = dims[1], g.nz = dims[2];
-    g.W = (dims[0] + 63u) / 64u;
-    g.tiles_y = (dims[1] + 7u) / 8u, g.tiles_z = (dims[2] + 7u) / 8u;
-    g.conn = connectivity;
-    g.words = cc_words(dims);
-    // the parents live in the caller's labels where linear index i is element i of them
-    const bool in_place = labels && (dims[0] == 1u || out_strides[0] == 1u) && (dims[1] == 1u || out_strides[1] == dims[0]) &&
-                          (dims[2] == 1u || out_strides[2] == (uint64_t) dims[0] * dims[1]);
-    const uint64_t n_blocks = (g.words + kBlock - 1) / kBlock;
-    if ((rc = grow_scratch(ctx, ctx->d_cc_bits, g.words, fn, "set bits")) || (rc = grow_scratch(ctx, ctx->d_cc_flags, g.words, fn, "flag bits")) ||
-        (rc = grow_scratch(ctx, ctx->d_cc_ctr, 4u, fn, "counters")) || (rc = grow_scratch(ctx, ctx->h_cc_ctr, 4u, fn, "counters")) ||
-        (labels && ((rc = grow_scratch(ctx, ctx->d_cc_local, g.words, fn, "prefixes")) ||
-                    (rc = grow_scratch(ctx, ctx->d_cc_boff, n_blocks + 1u, fn, "block offsets")))) ||
-        (!in_place && (rc = grow_scratch(ctx, ctx->d_cc_parent, voxels, fn, "parents"))))
-        return rc;
-    ctx->ktimes_on = false;   // (no per-launch brackets here; o2v_hip_voxelize sets the flag again from its params)
-    uint32_t *const P = in_place ? reinterpret_cast<uint32_t *>(labels) : ctx->d_cc_parent.ptr;
-    unsigned long long *const bits = ctx->d_cc_bits.ptr, *const fl = ctx->d_cc_flags.ptr, *const ctr = ctx->d_cc_ctr.ptr;
-    const uint32_t invert = (flags & O2V_HIP_CC_INVERT) ? 1u : 0u;
-    const bool count = (flags & O2V_HIP_FLAG_STAGE_TIMES) != 0;
-    const dim3 per_word(stream_grid(ctx, g.words * 64u, 16u));
-    hipStream_t s = ctx->stream;
-    O2V_CHECK(ctx->cc_times.mark(0, s));
-    O2V_CHECK(hipMemsetAsync(ctr, 0, 4u * sizeof(unsigned long long), s));
-    launch_classify(ctx, sg, invert, bits);
-    O2V_CHECK(ctx->cc_times.mark(1, s));
-    if (sw.cc_no_tiles) {
-        O2V_LAUNCH("k_cc_init", s, k_cc_init, per_word, dim3(kBlock), 0, s, g, bits, P);
-    } else {
-        const uint64_t tiles = (uint64_t) g.W * g.tiles_y * g.tiles_z;
-        O2V_LAUNCH("k_cc_tiles", s, k_cc_tiles, dim3((uint32_t) std::min<uint64_t>(tiles, kCcMaxGrid)), dim3(kBlock), 0, s, g, bits, P);
-    }
-    O2V_CHECK(ctx->cc_times.mark(2, s));
-    if (sw.cc_no_tiles && count)
-        O2V_LAUNCH("k_cc_seams", s, (k_cc_seams<true, true>), per_word, dim3(kBlock), 0, s, g, bits, P, ctr);
-    else if (sw.cc_no_tiles)
-        O2V_LAUNCH("k_cc_seams", s, (k_cc_seams<true, false>), per_word, dim3(kBlock), 0, s, g, bits, P, ctr);
-    else if (count)
-        O2V_LAUNCH("k_cc_seams", s, (k_cc_seams<false, true>), per_word, dim3(kBlock), 0, s, g, bits, P, ctr);
-    else
-        O2V_LAUNCH("k_cc_seams", s, (k_cc_seams<false, false>), per_word, dim3(kBlock), 0, s, g, bits, P, ctr);
-    O2V_CHECK(ctx->cc_times.mark(3, s));
-    if (labels) {
-        O2V_LAUNCH("k_cc_flatten", s, k_cc_flatten, per_word, dim3(kBlock), 0, s, g, bits, P, fl);
-        O2V_LAUNCH("k_cc_count", s, k_cc_count, dim3((uint32_t) n_blocks), dim3(kBlock), 0, s, fl, g.words, ctx->d_cc_local.ptr, ctx->d_cc_boff.ptr);
-        O2V_LAUNCH("k_fill_scan_blocks", s, k_fill_scan_blocks, dim3(1), dim3(kBlock), 0, s, ctx->d_cc_boff.ptr, n_blocks, ctx->d_cc_boff.ptr + n_blocks);
-        O2V_CHECK(ctx->cc_times.mark(4, s));
-        O2V_LAUNCH("k_cc_labels", s, k_cc_labels, per_word, dim3(kBlock), 0, s, g, bits, P, fl, ctx->d_cc_local.ptr, ctx->d_cc_boff.ptr, labels,
-                   out_strides[0], out_strides[1], out_strides[2]);
-        O2V_CHECK(hipMemcpyAsync(ctx->h_cc_ctr.ptr + 2, ctx->d_cc_boff.ptr + n_blocks, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    } else {
-        O2V_LAUNCH("k_cc_flatten", s, k_cc_flatten, per_word, dim3(kBlock), 0, s, g, bits, P, (unsigned long long *) nullptr);
-        O2V_CHECK(ctx->cc_times.mark(4, s));
-        O2V_CHECK(hipMemsetAsync(fl, 0, g.words * sizeof(unsigned long long), s));
-        if (n_seeds)
-            O2V_LAUNCH("k_cc_seed_list", s, k_cc_seed_list, dim3(stream_grid(ctx, n_seeds, 8u)), dim3(kBlock), 0, s, g, bits, P, seeds, n_seeds, fl);
-        if (flags & O2V_HIP_CC_SEED_BORDER) O2V_LAUNCH("k_cc_seed_border", s, k_cc_seed_border, per_word, dim3(kBlock), 0, s, g, bits, P, fl);
-        O2V_LAUNCH("k_cc_flood_out", s, k_cc_flood_out, per_word, dim3(kBlock), 0, s, g, bits, P, fl, (uint32_t) values[0], (uint32_t) values[1],
-                   (uint32_t) values[2], out, out_strides[0], out_strides[1], out_strides[2], ctr + 2);
-        O2V_CHECK(hipMemcpyAsync(ctx->h_cc_ctr.ptr + 2, ctr + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    }
-    O2V_CHECK(hipGetLastError());
-    O2V_CHECK(ctx->cc_times.mark(5, s));
-    O2V_CHECK(hipMemcpyAsync(ctx->h_cc_ctr.ptr, ctr, 2u * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    O2V_CHECK(hipStreamSynchronize(s));
-    O2V_CHECK(ctx->cc_times.finish());
-    ctx->cc_counters[0] = ctx->h_cc_ctr.ptr[0];
-    ctx->cc_counters[1] = ctx->h_cc_ctr.ptr[1];
-    *result = ctx->h_cc_ctr.ptr[2];
-    return O2V_HIP_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-uint64_t o2v_hip_components_scratch_bytes(const uint32_t dims[3], uint32_t which)
-{
-    if (!dims || !dims[0] || !dims[1] || !dims[2] || which > O2V_HIP_CC_SCRATCH_FLOOD) return 0;
-    const uint64_t words = cc_words(dims), voxels = (uint64_t) dims[0] * dims[1] * dims[2];
-    if (which == O2V_HIP_CC_SCRATCH_FLOOD) return 16u * words + 4u * voxels + 32u;
-    return 20u * words + 8u * ((words + kBlock - 1) / kBlock + 1u) + 32u + (which == O2V_HIP_CC_SCRATCH_LABELS_STRIDED ? 4u * voxels : 0u);
-}
-
-int o2v_hip_components_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
-                             uint32_t connectivity, uint32_t flags, int32_t *labels, const uint64_t label_strides[3], uint64_t *out_count)
-{
-    static const char fn[] = "o2v_hip_components_dense";
-    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
-    if (!labels) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    return cc_run(ctx, fn, grid, format, strides, dims, level, connectivity, flags, labels, nullptr, label_strides, nullptr, 0, nullptr, out_count);
-}
-
-int o2v_hip_flood_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
-                        uint32_t connectivity, uint32_t flags, const int32_t *seeds, uint64_t n_seeds, const uint8_t values[3], uint8_t *out,
-                        const uint64_t out_strides[3], uint64_t *out_reached)
-{
-    static const char fn[] = "o2v_hip_flood_dense";
-    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
-    if (!out) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    return cc_run(ctx, fn, grid, format, strides, dims, level, connectivity, flags, nullptr, out, out_strides, seeds, n_seeds, values, out_reached);
-}
-
-int o2v_hip_components_times(const o2v_hip_ctx *ctx, float out_ms[5])
-{
-    return ctx ? ctx->cc_times.read(out_ms) : O2V_HIP_ERR_BAD_ARGUMENT;
-}
-
-int o2v_hip_components_counters(const o2v_hip_ctx *ctx, uint64_t out2[2])
-{
-    if (!ctx || !out2) return O2V_HIP_ERR_BAD_ARGUMENT;
-    out2[0] = ctx->cc_counters[0];
-    out2[1] = ctx->cc_counters[1];
-    return O2V_HIP_OK;
-}
-
-}  // extern "C"
-
-// ---- K13: the solid voxels of a dense grid as (x, y, z, argb) records ---------------------------------------------------------
-
-namespace {
-
-constexpr uint32_t kGaMaxDim = 65536;
-constexpr uint64_t kGaMaxWords = 0x7fffffffull;   // a word index is one uint32 in k_gather_write
-constexpr uint64_t kGaMaxGrid = 1ull << 20;       // workgroups of k_gather_count; more blocks are taken in turns
-constexpr uint64_t kGaBatch = 1u << 20;           // records per batch of o2v_hip_gather_save: the batch of drain_to_sink (o2v_api.cpp)
-
-// what the three calls check of the grid; *sg: the set grid, *g: its words
-int ga_grid(o2v_hip_ctx *ctx, const char *fn, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
-            SetGrid *sg, GaGrid *g)
-{
-    if (int rc = set_grid(ctx, fn, grid, format, strides, dims, level, sg)) return rc;
-    for (int a = 0; a < 3; ++a)
-        if (dims[a] > kGaMaxDim) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "a grid of more than 65 536 voxels along an axis");
-    const uint64_t words = cc_words(dims);   // (below 2^43)
-    if (words > kGaMaxWords) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, std::to_string(words) + " words of 64 voxels along x (at most 2^31 - 1)");
-    g->nx = dims[0], g->ny = dims[1], g->nz = dims[2];
-    g->W = (dims[0] + 63u) / 64u;
-    g->words = words;
-    g->n_blocks = (words + kBlock - 1) / kBlock;
-    return O2V_HIP_OK;
-}
-
-// what _write and _save check of the origin and the colour mode (nothing is read through a pointer here)
-int ga_mode(o2v_hip_ctx *ctx, const char *fn, uint32_t format, const uint32_t dims[3], const uint32_t origin[3], uint32_t color_mode)
-{
-    if (!origin) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    if (color_mode != O2V_HIP_GATHER_COLOR_CONSTANT && color_mode != O2V_HIP_GATHER_COLOR_GRID && color_mode != O2V_HIP_GATHER_COLOR_PALETTE)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown color_mode " + std::to_string(color_mode));
-    if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE && format != O2V_HIP_GRID_U8)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "O2V_HIP_GATHER_COLOR_PALETTE needs a U8 grid");
-    for (int a = 0; a < 3; ++a)
-        if ((uint64_t) origin[a] + dims[a] > (1ull << 32)) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "origin + dims is above 2^32 along an axis");
-    return O2V_HIP_OK;
-}
-
-// the pointers the colour mode reads; *cbytes: the reach of colors (GRID)
-int ga_color_source(o2v_hip_ctx *ctx, const char *fn, const uint32_t dims[3], uint32_t color_mode, const uint32_t *colors,
-                    const uint64_t color_strides[3], const uint32_t *palette, uint64_t *cbytes)
-{
-    *cbytes = 0;
-    if (color_mode == O2V_HIP_GATHER_COLOR_GRID) {
-        if (!colors || !color_strides) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-        return check_grid(ctx, fn, "colors", colors, dims, color_strides, 4u, false, cbytes);
-    }
-    if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE && !palette) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    return O2V_HIP_OK;
-}
-
-bool ga_matches(const o2v_hip_ctx *ctx, const SetGrid &sg) { return ctx->ga.valid && ctx->ga.key == sg.key; }
-
-// classify, count and scan; the count is kept in the context and returned
-int ga_count(o2v_hip_ctx *ctx, const char *fn, const SetGrid &sg, const GaGrid &g, uint64_t *out_count)
-{
-    int rc;
-    if ((rc = grow_scratch(ctx, ctx->d_ga_bits, g.words, fn, "set bits")) || (rc = grow_scratch(ctx, ctx->d_ga_local, g.words, fn, "prefixes")) ||
-        (rc = grow_scratch(ctx, ctx->d_ga_boff, g.n_blocks + 1u, fn, "block offsets")) || (rc = grow_scratch(ctx, ctx->d_ga_first, 1u, fn, "range")) ||
-        (rc = grow_scratch(ctx, ctx->h_ga_ctr, 1u, fn, "counters")))
-        return rc;
-    ctx->ktimes_on = false;   // (no per-launch brackets here; o2v_hip_voxelize sets the flag again from its params)
-    unsigned long long *const bits = ctx->d_ga_bits.ptr, *const boff = ctx->d_ga_boff.ptr;
-    hipStream_t s = ctx->stream;
-    O2V_CHECK(ctx->ga_times.mark(0, s));
-    launch_classify(ctx, sg, 0u, bits);
-    O2V_CHECK(ctx->ga_times.mark(1, s));
-    O2V_LAUNCH("k_gather_count", s, k_gather_count, dim3((uint32_t) std::min<uint64_t>(g.n_blocks, kGaMaxGrid)), dim3(kBlock), 0, s, bits, g,
-               ctx->d_ga_local.ptr, boff);
-    uint64_t total = 0;
-    if ((rc = count_total(ctx, boff, g.n_blocks, ctx->h_ga_ctr, ctx->ga_times, &total))) return rc;
-#ifdef O2V_GA_MUTATE_COUNT32
-    total = (uint32_t) total;   // (test only: the count truncated where the host reads it)
-#endif
-    ctx->ga.valid = true;
-    ctx->ga.key = sg.key;
-    ctx->ga.total = total;
-    *out_count = total;
-    return O2V_HIP_OK;
-}
-
-// The 256 colours of a PALETTE call into the context's device copy, on the stream.  K13 and K14 share the copy: every call that
-// reads it uploads its own palette ahead of its launches and has waited for the stream when it returns.
-int upload_palette(o2v_hip_ctx *ctx, const char *fn, const uint32_t *palette)
-{
-    if (int rc; (rc = grow_scratch(ctx, ctx->d_palette, 256u, fn, "palette")) || (rc = grow_scratch(ctx, ctx->h_palette, 256u, fn, "palette"))) return rc;
-    std::memcpy(ctx->h_palette.ptr, palette, 256u * sizeof(uint32_t));
-    O2V_CHECK(hipMemcpyAsync(ctx->d_palette.ptr, ctx->h_palette.ptr, 256u * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    return O2V_HIP_OK;
-}
-
-// records [first, first + n) of the last count into `records`, enqueued on the stream (n > 0; events 2 and 3 of ga_times around it)
-int ga_launch_write(o2v_hip_ctx *ctx, const GaGrid &g, uint64_t first, uint64_t n, const uint32_t origin[3], uint32_t color_mode,
-                    const GaColor &col, uint32_t *records)
-{
-    hipStream_t s = ctx->stream;
-    const unsigned long long *const boff = ctx->d_ga_boff.ptr;
-    uint4 *const out = reinterpret_cast<uint4 *>(records);
-    // a workgroup per block the range may touch: one per 2^14 records and the two at its ends, and no more than fill the device
-    const dim3 blocks((uint32_t) std::min<uint64_t>(std::min<uint64_t>(g.n_blocks, n / 64u + 2u), (uint64_t) ctx->num_cus * 8u));
-    O2V_CHECK(hipEventRecord(ctx->ga_times.ev[2], s));
-    O2V_LAUNCH("k_gather_find", s, k_gather_find, dim3(1), dim3(kBlock), 0, s, boff, g.n_blocks, first, ctx->d_ga_first.ptr);
-    if (color_mode == O2V_HIP_GATHER_COLOR_GRID)
-        O2V_LAUNCH("k_gather_write", s, k_gather_write<kGaColorGrid>, blocks, dim3(kBlock), 0, s, g, ctx->d_ga_bits.ptr, ctx->d_ga_local.ptr, boff,
-                   ctx->d_ga_first.ptr, first, n, origin[0], origin[1], origin[2], col, out);
-    else if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE)
-        O2V_LAUNCH("k_gather_write", s, k_gather_write<kGaColorPalette>, blocks, dim3(kBlock), 0, s, g, ctx->d_ga_bits.ptr, ctx->d_ga_local.ptr, boff,
-                   ctx->d_ga_first.ptr, first, n, origin[0], origin[1], origin[2], col, out);
-    else
-        O2V_LAUNCH("k_gather_write", s, k_gather_write<kGaColorConstant>, blocks, dim3(kBlock), 0, s, g, ctx->d_ga_bits.ptr, ctx->d_ga_local.ptr, boff,
-                   ctx->d_ga_first.ptr, first, n, origin[0], origin[1], origin[2], col, out);
-    O2V_CHECK(hipGetLastError());
-    O2V_CHECK(hipEventRecord(ctx->ga_times.ev[3], s));
-    return O2V_HIP_OK;
-}
-
-// *col: what the colour mode reads, as the kernels of K13 and K14 take it; PALETTE: uploaded first
-int ga_color(o2v_hip_ctx *ctx, const char *fn, const SetGrid &sg, uint32_t color_mode, uint32_t argb, const uint32_t *colors,
-             const uint64_t color_strides[3], const uint32_t *palette, GaColor *col)
-{
-    *col = GaColor{};
-    col->argb = argb;
-    if (color_mode == O2V_HIP_GATHER_COLOR_GRID) col->colors = colors, col->c0 = color_strides[0], col->c1 = color_strides[1], col->c2 = color_strides[2];
-    if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE) {
-        if (int rc = upload_palette(ctx, fn, palette)) return rc;
-        col->grid = static_cast<const uint8_t *>(sg.key.p);
-        col->s0 = sg.key.strides[0], col->s1 = sg.key.strides[1], col->s2 = sg.key.strides[2];
-        col->palette = ctx->d_palette.ptr;
-    }
-    return O2V_HIP_OK;
-}
-
-bool ga_output_format(FileFormat f)
-{
-    return f == FileFormat::VL32 || f == FileFormat::PLY || f == FileFormat::XYZRGB || f == FileFormat::QEF || f == FileFormat::VOX;
-}
-
-}  // namespace
-
-extern "C" {
-
-uint64_t o2v_hip_gather_scratch_bytes(const uint32_t dims[3])
-{
-    if (!dims || !dims[0] || !dims[1] || !dims[2]) return 0;
-    const uint64_t words = cc_words(dims);
-    return 12u * words + 8u * ((words + kBlock - 1) / kBlock + 1u) + 1024u + 8u;
-}
-
-int o2v_hip_gather_count(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
-                         uint64_t *out_count)
-{
-    static const char fn[] = "o2v_hip_gather_count";
-    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
-    ctx->ga.valid = false;
-    if (!out_count) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    SetGrid sg;
-    GaGrid g{};
-    if (int rc = ga_grid(ctx, fn, grid, format, strides, dims, level, &sg, &g)) return rc;
-    return ga_count(ctx, fn, sg, g, out_count);
-}
-
-int o2v_hip_gather_write(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
-                         const uint32_t origin[3], uint32_t color_mode, uint32_t argb, const uint32_t *colors, const uint64_t color_strides[3],
-                         const uint32_t *palette, uint64_t first, uint64_t n, uint32_t *records)
-{
-    static const char fn[] = "o2v_hip_gather_write";
-    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
-    SetGrid sg;
-    GaGrid g{};
-    uint64_t cbytes = 0;
-    int rc;
-    if ((rc = ga_grid(ctx, fn, grid, format, strides, dims, level, &sg, &g)) || (rc = ga_mode(ctx, fn, format, dims, origin, color_mode))) return rc;
-    if (!ga_matches(ctx, sg))
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "no matching o2v_hip_gather_count (the same grid, format, strides, dims and level)");
-    const uint64_t total = ctx->ga.total;
-    if (first > total || n > total - first)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn,
-                      "records " + std::to_string(first) + " + " + std::to_string(n) + " reach past the counted " + std::to_string(total));
-    if (n == 0) return O2V_HIP_OK;
-    if (!records) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    if ((rc = ga_color_source(ctx, fn, dims, color_mode, colors, color_strides, palette, &cbytes))) return rc;
-    if (n > (~0ull >> 4)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "records: n * 16 bytes reach past any allocation");
-    if ((uintptr_t) records % 16u) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "records must be 16-byte aligned");
-    if ((rc = check_device_range(ctx, fn, records, n * 16u, "records"))) return rc;
-    const Span spans[] = {{"records", records, n * 16u}, {"grid", grid, sg.bytes}, {"colors", colors, cbytes}};
-    if ((rc = refuse_overlap(ctx, fn, spans, 1))) return rc;
-    ctx->ktimes_on = false;
-    GaColor col;
-    if ((rc = ga_color(ctx, fn, sg, color_mode, argb, colors, color_strides, palette, &col)) ||
-        (rc = ga_launch_write(ctx, g, first, n, origin, color_mode, col, records)))
-        return rc;
-    O2V_CHECK(hipStreamSynchronize(ctx->stream));
-    O2V_CHECK(ctx->ga_times.elapsed(2, 3, ctx->ga_times.ms[2]));
-    return O2V_HIP_OK;
-}
-
-int o2v_hip_gather_save(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
-                        const uint32_t origin[3], uint32_t color_mode, uint32_t argb, const uint32_t *colors, const uint64_t color_strides[3],
-                        const uint32_t *palette, const char *path, const char *type, uint32_t resolution, uint64_t *out_count)
-{
-    static const char fn[] = "o2v_hip_gather_save";
-    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
-    ctx->ga.valid = false;
-    if (!path || !out_count) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    SetGrid sg;
-    GaGrid g{};
-    uint64_t cbytes = 0;
-    int rc;
-    if ((rc = ga_grid(ctx, fn, grid, format, strides, dims, level, &sg, &g)) || (rc = ga_mode(ctx, fn, format, dims, origin, color_mode)) ||
-        (rc = ga_color_source(ctx, fn, dims, color_mode, colors, color_strides, palette, &cbytes)))
-        return rc;
-    for (int a = 0; a < 3; ++a)
-        if ((uint64_t) origin[a] + dims[a] > resolution)
-            return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "origin + dims is above the resolution " + std::to_string(resolution) + " along an axis");
-    const FileFormat file_format = detect_format(path, type);
-    if (!ga_output_format(file_format))
-        return refuse(ctx, O2V_HIP_ERR_IO, fn, std::string("\"") + (type ? type : path) + "\" is not an output format (VL32, PLY, XYZRGB, QEF, VOX)");
-    uint64_t total = 0;
-    if ((rc = ga_count(ctx, fn, sg, g, &total))) return rc;
-    for (int k = 0; k < 2; ++k) {
-        if ((rc = grow_scratch(ctx, ctx->d_ga_rec[k], kGaBatch, fn, "record buffer")) || (rc = grow_scratch(ctx, ctx->h_ga_rec[k], kGaBatch * 4u, fn, "staging")))
-            return rc;
-        O2V_CHECK(ctx->ev_ga_rec[k].create_sync());
-    }
-    std::unique_ptr<VoxelSink> sink = open_file_sink(path, file_format, resolution);
-    if (!sink) return refuse(ctx, O2V_HIP_ERR_IO, fn, std::string("cannot open \"") + path + "\" for writing");
-    sink->expect(total);
-    GaColor col;
-    if ((rc = ga_color(ctx, fn, sg, color_mode, argb, colors, color_strides, palette, &col))) return rc;
-    hipStream_t s = ctx->stream;
-    const uint64_t batches = (total + kGaBatch - 1) / kGaBatch;
-    // Two record buffers and two page-locked batches: while the sink consumes one batch the next is written and copied.
-    auto start = [&](uint64_t k) -> int {
-        const uint64_t first = k * kGaBatch, n = std::min<uint64_t>(kGaBatch, total - first);
-        if (int e = ga_launch_write(ctx, g, first, n, origin, color_mode, col, reinterpret_cast<uint32_t *>(ctx->d_ga_rec[k & 1].ptr))) return e;
-        O2V_CHECK(hipMemcpyAsync(ctx->h_ga_rec[k & 1].ptr, ctx->d_ga_rec[k & 1].ptr, n * 16u, hipMemcpyDeviceToHost, s));
-        O2V_CHECK(hipEventRecord(ctx->ev_ga_rec[k & 1], s));
-        return O2V_HIP_OK;
-    };
-    rc = batches ? start(0) : O2V_HIP_OK;
-    for (uint64_t k = 0; k < batches && rc == O2V_HIP_OK; ++k) {
-        if (!sink->can_write()) break;
-        if (hipEventSynchronize(ctx->ev_ga_rec[k & 1]) != hipSuccess) {
-            rc = refuse(ctx, O2V_HIP_ERR_HIP, fn, "waiting for a batch of records failed");
-            break;
-        }
-        if (k + 1 < batches && (rc = start(k + 1))) break;
-        sink->write(ctx->h_ga_rec[k & 1].ptr, (size_t) std::min<uint64_t>(kGaBatch, total - k * kGaBatch));
-    }
-    const hipError_t drained = hipStreamSynchronize(s);   // (nothing is on its way into the batches when the call returns)
-    if (rc) return rc;
-    if (drained != hipSuccess) return refuse(ctx, O2V_HIP_ERR_HIP, fn, std::string("hipStreamSynchronize: ") + hipGetErrorString(drained));
-    if (batches) O2V_CHECK(ctx->ga_times.elapsed(2, 3, ctx->ga_times.ms[2]));
-    if (sink->can_write()) sink->finalize();
-    if (!sink->can_write()) return refuse(ctx, O2V_HIP_ERR_IO, fn, std::string("writing \"") + path + "\" failed: the sink stopped accepting voxels");
-    *out_count = total;
-    return O2V_HIP_OK;
-}
-
-int o2v_hip_gather_times(const o2v_hip_ctx *ctx, float out_ms[3])
-{
-    return ctx ? ctx->ga_times.read(out_ms) : O2V_HIP_ERR_BAD_ARGUMENT;
-}
-
-}  // extern "C"
-
-// ---- K14: the exposed voxel faces of a dense grid as coloured quads -----------------------------------------------------------
-
-namespace {
-
-constexpr uint64_t kFaMaxExtent = 65536;          // origin + dims per axis: a coordinate is an exact float32
-constexpr uint64_t kFaMaxQuads = 0x7fffffffull / 4u;   // 4 Q <= 2^31 - 1: a vertex index is one int32
-constexpr uint64_t kFaMaxGrid = 1ull << 20;       // workgroups of k_faces_count; more blocks are taken in turns
-
-// what both calls check: the grid as the gather checks it, the merge and colour modes and the pointers the colour mode reads;
-// *sg: the set grid, *g: the words and items, *cbytes: the reach of colors (GRID)
-int fa_args(o2v_hip_ctx *ctx, const char *fn, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
-            uint32_t merge, uint32_t color_mode, const uint32_t *colors, const uint64_t color_strides[3], const uint32_t *palette, SetGrid *sg,
-            FaGrid *g, uint64_t *cbytes)
-{
-    GaGrid gg{};
-    static const uint32_t no_origin[3] = {0, 0, 0};
-    int rc;
-    if ((rc = ga_grid(ctx, fn, grid, format, strides, dims, level, sg, &gg))) return rc;
-    if (merge != O2V_HIP_FACES_MERGE_NONE && merge != O2V_HIP_FACES_MERGE_RUNS && merge != O2V_HIP_FACES_MERGE_RECTS)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown merge " + std::to_string(merge));
-    if ((rc = ga_mode(ctx, fn, format, dims, no_origin, color_mode)) ||
-        (rc = ga_color_source(ctx, fn, dims, color_mode, colors, color_strides, palette, cbytes)))
-        return rc;
-    g->nx = gg.nx, g->ny = gg.ny, g->nz = gg.nz, g->W = gg.W;
-    g->merge = merge;
-    g->colored = merge != O2V_HIP_FACES_MERGE_NONE && color_mode != O2V_HIP_GATHER_COLOR_CONSTANT;
-    g->words = gg.words;
-    g->items = 6u * gg.words;
-    g->n_blocks = (g->items + kBlock - 1) / kBlock;
-    return O2V_HIP_OK;
-}
-
-bool fa_matches(const o2v_hip_ctx *ctx, const SetGrid &sg, uint32_t merge, uint32_t color_mode, uint32_t argb, const uint32_t *colors,
-                const uint64_t color_strides[3], const uint32_t *palette)
-{
-    const o2v_hip_ctx::FacesCount &c = ctx->fa;
-    if (!c.valid || !(c.key == sg.key) || c.merge != merge || c.color_mode != color_mode) return false;
-    if (color_mode == O2V_HIP_GATHER_COLOR_GRID) return c.colors == colors && std::equal(color_strides, color_strides + 3, c.color_strides);
-    if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE) return std::equal(palette, palette + 256, c.palette);
-    return c.argb == argb;
-}
-
-FaBits fa_bits(const o2v_hip_ctx *ctx) { return FaBits{ctx->d_fa_bits.ptr, ctx->d_fa_same_x.ptr, ctx->d_fa_same_y.ptr}; }
-
-}  // namespace
-
-extern "C" {
-
-uint64_t o2v_hip_faces_scratch_bytes(const uint32_t dims[3], uint32_t color_mode)
-{
-    if (!dims || !dims[0] || !dims[1] || !dims[2]) return 0;
-    const uint64_t words = cc_words(dims);
-    return (color_mode == O2V_HIP_GATHER_COLOR_CONSTANT ? 8u : 24u) * words + 8u * ((6u * words + kBlock - 1) / kBlock + 1u) + 1024u;
-}
-
-uint64_t o2v_hip_faces_scratch_bytes_merge(const uint32_t dims[3], uint32_t color_mode, uint32_t merge)
-{
-    const uint64_t bytes = o2v_hip_faces_scratch_bytes(dims, color_mode);
-    if (!bytes || merge != O2V_HIP_FACES_MERGE_RECTS) return bytes;
-    return bytes + (color_mode == O2V_HIP_GATHER_COLOR_CONSTANT ? 48u : 56u) * cc_words(dims);
-}
-
-int o2v_hip_faces_count(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
-                        uint32_t merge, uint32_t color_mode, uint32_t argb, const uint32_t *colors, const uint64_t color_strides[3],
-                        const uint32_t *palette, uint64_t *out_quads)
-{
-    static const char fn[] = "o2v_hip_faces_count";
-    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
-    ctx->fa.valid = false;
-    if (!out_quads) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    SetGrid sg;
-    FaGrid g{};
-    uint64_t cbytes = 0;
-    int rc;
-    if ((rc = fa_args(ctx, fn, grid, format, strides, dims, level, merge, color_mode, colors, color_strides, palette, &sg, &g, &cbytes))) return rc;
-    const bool rects = merge == O2V_HIP_FACES_MERGE_RECTS;
-    if ((rc = grow_scratch(ctx, ctx->d_fa_bits, g.words, fn, "set bits")) ||
-        (g.colored && ((rc = grow_scratch(ctx, ctx->d_fa_same_x, g.words, fn, "same-colour bits")) ||
-                       (rc = grow_scratch(ctx, ctx->d_fa_same_y, g.words, fn, "same-colour bits")))) ||
-        (rects && ((g.colored && (rc = grow_scratch(ctx, ctx->d_rc_same_z, g.words, fn, "same-colour bits"))) ||
-                   (rc = grow_scratch(ctx, ctx->d_rc_starts, g.items, fn, "rectangle starts")))) ||
-        (rc = grow_scratch(ctx, ctx->d_fa_boff, g.n_blocks + 1u, fn, "block offsets")) || (rc = grow_scratch(ctx, ctx->h_fa_ctr, 1u, fn, "counters")))
-        return rc;
-    ctx->ktimes_on = false;   // (no per-launch brackets here; o2v_hip_voxelize sets the flag again from its params)
-    unsigned long long *const bits = ctx->d_fa_bits.ptr, *const boff = ctx->d_fa_boff.ptr;
-    hipStream_t s = ctx->stream;
-    O2V_CHECK(ctx->fa_times.mark(0, s));
-    launch_classify(ctx, sg, 0u, bits);
-    if (g.colored) {
-        // a wavefront per word in turns
-        const dim3 per_word(stream_grid(ctx, g.words * 64u, 8u));
-        GaColor col;
-        if ((rc = ga_color(ctx, fn, sg, color_mode, argb, colors, color_strides, palette, &col))) return rc;
-        if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE) {
-            O2V_LAUNCH("k_faces_same", s, k_faces_same<kGaColorPalette>, per_word, dim3(kBlock), 0, s, g, bits, col, ctx->d_fa_same_x.ptr,
-                       ctx->d_fa_same_y.ptr);
-        } else {
-            O2V_LAUNCH("k_faces_same", s, k_faces_same<kGaColorGrid>, per_word, dim3(kBlock), 0, s, g, bits, col, ctx->d_fa_same_x.ptr,
-                       ctx->d_fa_same_y.ptr);
-        }
-        if (rects && color_mode == O2V_HIP_GATHER_COLOR_PALETTE)
-            O2V_LAUNCH("k_rects_same_z", s, k_rects_same_z<kGaColorPalette>, per_word, dim3(kBlock), 0, s, g, bits, col, ctx->d_rc_same_z.ptr);
-        else if (rects)
-            O2V_LAUNCH("k_rects_same_z", s, k_rects_same_z<kGaColorGrid>, per_word, dim3(kBlock), 0, s, g, bits, col, ctx->d_rc_same_z.ptr);
-    }
-    O2V_CHECK(ctx->fa_times.mark(1, s));
-    const dim3 count_grid((uint32_t) std::min<uint64_t>(g.n_blocks, kFaMaxGrid));
-    if (rects)
-        O2V_LAUNCH("k_rects_count", s, k_rects_count, count_grid, dim3(kBlock), 0, s, g, fa_bits(ctx), ctx->d_rc_same_z.ptr, ctx->d_rc_starts.ptr, boff);
-    else
-        O2V_LAUNCH("k_faces_count", s, k_faces_count, count_grid, dim3(kBlock), 0, s, g, fa_bits(ctx), boff);
-    uint64_t total = 0;
-    if ((rc = count_total(ctx, boff, g.n_blocks, ctx->h_fa_ctr, ctx->fa_times, &total))) return rc;
-#ifdef O2V_FA_MUTATE_COUNT32
-    total = (uint32_t) total;   // (test only: the count truncated where the host reads it)
-#endif
-    o2v_hip_ctx::FacesCount &c = ctx->fa;
-    c.valid = true;
-    c.key = sg.key;
-    c.merge = merge;
-    c.color_mode = color_mode;
-    c.argb = argb;
-    c.colors = color_mode == O2V_HIP_GATHER_COLOR_GRID ? colors : nullptr;
-    if (color_mode == O2V_HIP_GATHER_COLOR_GRID) std::copy(color_strides, color_strides + 3, c.color_strides);
-    if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE) std::copy(palette, palette + 256, c.palette);
-    c.total = total;
-    *out_quads = total;
-    return O2V_HIP_OK;
-}
-
-int o2v_hip_faces_write(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
-                        uint32_t merge, uint32_t color_mode, uint32_t argb, const uint32_t *colors, const uint64_t color_strides[3],
-                        const uint32_t *palette, const uint32_t origin[3], float *positions, int32_t *faces, uint32_t *quad_argb,
-                        uint64_t quad_capacity)
-{
-    static const char fn[] = "o2v_hip_faces_write";
-    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
-    SetGrid sg;
-    FaGrid g{};
-    uint64_t cbytes = 0;
-    int rc;
-    if ((rc = fa_args(ctx, fn, grid, format, strides, dims, level, merge, color_mode, colors, color_strides, palette, &sg, &g, &cbytes))) return rc;
-    if (!origin) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    for (int a = 0; a < 3; ++a)
-        if ((uint64_t) origin[a] + dims[a] > kFaMaxExtent)
-            return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "origin + dims is above 65 536 along an axis: a coordinate would not be exact in float32");
-    if (!fa_matches(ctx, sg, merge, color_mode, argb, colors, color_strides, palette))
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn,
-                      "no matching o2v_hip_faces_count (the same grid, format, strides, dims, level, merge and colour arguments)");
-    const uint64_t total = ctx->fa.total;
-    if (total > kFaMaxQuads)
-        return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, std::to_string(total) + " quads: 4 vertices each are more than 2^31 - 1 int32 indices");
-    if (quad_capacity < total)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn,
-                      "quad_capacity " + std::to_string(quad_capacity) + " is below the counted " + std::to_string(total) + " quads");
-    if (total == 0) return O2V_HIP_OK;
-    if (!positions) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    if ((uintptr_t) positions % 16u || (uintptr_t) faces % 8u || (uintptr_t) quad_argb % 4u)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "positions must be 16-byte, faces 8-byte and quad_argb 4-byte aligned");
-    const Span spans[] = {{"positions", positions, total * 48u}, {"faces", faces, total * 24u}, {"quad_argb", quad_argb, total * 4u},
-                          {"grid", grid, sg.bytes}, {"colors", colors, cbytes}};
-    for (int i = 0; i < 3; ++i)
-        if (spans[i].p && (rc = check_device_range(ctx, fn, spans[i].p, spans[i].bytes, spans[i].what))) return rc;
-    if ((rc = refuse_overlap(ctx, fn, spans, 3))) return rc;
-    ctx->ktimes_on = false;
-    GaColor col;
-    if ((rc = ga_color(ctx, fn, sg, color_mode, argb, colors, color_strides, palette, &col))) return rc;
-    hipStream_t s = ctx->stream;
-    // a workgroup per block of items in turns, and no more than fill the device
-    const dim3 blocks((uint32_t) std::min<uint64_t>(g.n_blocks, (uint64_t) ctx->num_cus * 8u));
-    float4 *const pos = reinterpret_cast<float4 *>(positions);
-    int2 *const tri = reinterpret_cast<int2 *>(faces);
-    O2V_CHECK(hipEventRecord(ctx->fa_times.ev[2], s));
-    const unsigned long long *const rstarts = ctx->d_rc_starts.ptr, *const boff = ctx->d_fa_boff.ptr;
-    if (merge == O2V_HIP_FACES_MERGE_RECTS && color_mode == O2V_HIP_GATHER_COLOR_GRID)
-        O2V_LAUNCH("k_rects_write", s, k_rects_write<kGaColorGrid>, blocks, dim3(kBlock), 0, s, g, fa_bits(ctx), rstarts, boff, origin[0], origin[1],
-                   origin[2], col, pos, tri, quad_argb);
-    else if (merge == O2V_HIP_FACES_MERGE_RECTS && color_mode == O2V_HIP_GATHER_COLOR_PALETTE)
-        O2V_LAUNCH("k_rects_write", s, k_rects_write<kGaColorPalette>, blocks, dim3(kBlock), 0, s, g, fa_bits(ctx), rstarts, boff, origin[0], origin[1],
-                   origin[2], col, pos, tri, quad_argb);
-    else if (merge == O2V_HIP_FACES_MERGE_RECTS)
-        O2V_LAUNCH("k_rects_write", s, k_rects_write<kGaColorConstant>, blocks, dim3(kBlock), 0, s, g, fa_bits(ctx), rstarts, boff, origin[0], origin[1],
-                   origin[2], col, pos, tri, quad_argb);
-    else if (color_mode == O2V_HIP_GATHER_COLOR_GRID)
-        O2V_LAUNCH("k_faces_write", s, k_faces_write<kGaColorGrid>, blocks, dim3(kBlock), 0, s, g, fa_bits(ctx), ctx->d_fa_boff.ptr, origin[0], origin[1],
-                   origin[2], col, pos, tri, quad_argb);
-    else if (color_mode == O2V_HIP_GATHER_COLOR_PALETTE)
-        O2V_LAUNCH("k_faces_write", s, k_faces_write<kGaColorPalette>, blocks, dim3(kBlock), 0, s, g, fa_bits(ctx), ctx->d_fa_boff.ptr, origin[0], origin[1],
-                   origin[2], col, pos, tri, quad_argb);
-    else
-        O2V_LAUNCH("k_faces_write", s, k_faces_write<kGaColorConstant>, blocks, dim3(kBlock), 0, s, g, fa_bits(ctx), ctx->d_fa_boff.ptr, origin[0],
-                   origin[1], origin[2], col, pos, tri, quad_argb);
-    O2V_CHECK(hipGetLastError());
-    O2V_CHECK(hipEventRecord(ctx->fa_times.ev[3], s));
-    O2V_CHECK(hipStreamSynchronize(s));
-    O2V_CHECK(ctx->fa_times.elapsed(2, 3, ctx->fa_times.ms[2]));
-    return O2V_HIP_OK;
-}
-
-int o2v_hip_faces_times(const o2v_hip_ctx *ctx, float out_ms[3])
-{
-    return ctx ? ctx->fa_times.read(out_ms) : O2V_HIP_ERR_BAD_ARGUMENT;
-}
-
-}  // extern "C"
-
-// ---- K17: a dense grid merged into a coarser one ------------------------------------------------------------------------------
-
-namespace {
-
-constexpr uint32_t kDsMaxDim = 65536;
-
-static_assert(kDsValueMin == O2V_HIP_DOWN_VALUE_MIN && kDsValueMax == O2V_HIP_DOWN_VALUE_MAX, "one set of value modes for the callers and the kernel");
-
-}  // namespace
-
-extern "C" {
-
-int o2v_hip_downsample_box(const uint32_t origin[3], const uint32_t dims[3], uint32_t factor, uint32_t out_origin[3], uint32_t out_dims[3])
-{
-    if (!origin || !dims || !out_origin || !out_dims || factor < kDsMinFactor || factor > kDsMaxFactor || !dims[0] || !dims[1] || !dims[2])
-        return O2V_HIP_ERR_BAD_ARGUMENT;
-    for (int a = 0; a < 3; ++a)
-        if ((uint64_t) origin[a] + dims[a] > (1ull << 32)) return O2V_HIP_ERR_LIMIT;
-    for (int a = 0; a < 3; ++a) {
-        out_origin[a] = ds_corigin(origin[a], factor);
-        out_dims[a] = ds_cdim(origin[a], dims[a], factor);
-    }
-    return O2V_HIP_OK;
-}
-
-int o2v_hip_downsample(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
-                       const uint32_t origin[3], uint32_t factor, uint32_t min_count, uint32_t value_mode, const uint32_t *colors,
-                       const uint64_t color_strides[3], int16_t *count, const uint64_t count_strides[3], uint8_t *solid,
-                       const uint64_t solid_strides[3], uint8_t *values, const uint64_t value_strides[3], uint32_t *argb,
-                       const uint64_t argb_strides[3])
-{
-    static const char fn[] = "o2v_hip_downsample";
-    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
-    SetGrid sg;
-    int rc;
-    if ((rc = set_grid_args(ctx, fn, grid, format, strides, dims, level, &sg))) return rc;
-    if (!origin || (count && !count_strides) || (solid && !solid_strides) || (values && !value_strides) || (argb && !argb_strides) ||
-        (colors && !color_strides))
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    if (!count && !solid && !values && !argb) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "no output: count, solid, values and argb are all null");
-    if (factor < kDsMinFactor || factor > kDsMaxFactor)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "factor must be 2 ... 8, not " + std::to_string(factor));
-    if (min_count < 1u || min_count > factor * factor * factor)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn,
-                      "min_count must be 1 ... factor^3 = " + std::to_string(factor * factor * factor) + ", not " + std::to_string(min_count));
-    if (values && format != O2V_HIP_GRID_U8) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "values needs a U8 grid");
-    if (values && value_mode != O2V_HIP_DOWN_VALUE_MIN && value_mode != O2V_HIP_DOWN_VALUE_MAX)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown value_mode " + std::to_string(value_mode));
-    if (argb && !colors) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "argb needs colors");
-    for (int a = 0; a < 3; ++a) {
-        if (dims[a] > kDsMaxDim) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "a grid of more than 65 536 voxels along an axis");
-        if ((uint64_t) origin[a] + dims[a] > (1ull << 32)) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "origin + dims is above 2^32 along an axis");
-    }
-    // (the limits stand before the look at the memory: a box that is too large is refused as that, whatever it reaches)
-    if ((rc = set_grid_memory(ctx, fn, &sg))) return rc;
-    DsGrid g{};
-    for (int a = 0; a < 3; ++a) g.n[a] = dims[a], g.o[a] = origin[a], g.cn[a] = ds_cdim(origin[a], dims[a], factor);
-    g.f = factor, g.min_count = min_count, g.value_mode = value_mode;
-    g.spans = (g.cn[0] + kDsSpan - 1u) / kDsSpan;
-    g.ry = std::max(1u, kDsRows / (factor * factor));
-    g.ygroups = (g.cn[1] + g.ry - 1u) / g.ry;
-    g.items = (uint64_t) g.spans * g.ygroups * g.cn[2];
-    // colours are read only where argb is written
-    Span spans[6] = {{"count", count, 0}, {"solid", solid, 0}, {"values", values, 0}, {"argb", argb, 0}, {"grid", grid, sg.bytes}, {"colors", nullptr, 0}};
-    const uint64_t *const out_strides[4] = {count_strides, solid_strides, value_strides, argb_strides};
-    const uint32_t out_elem[4] = {2u, 1u, 1u, 4u};
-    if (argb) {
-        spans[5].p = colors;
-        if ((rc = check_grid(ctx, fn, "colors", colors, dims, color_strides, 4u, false, &spans[5].bytes))) return rc;
-    }
-    for (int i = 0; i < 4; ++i)
-        if (spans[i].p && (rc = check_grid(ctx, fn, spans[i].what, spans[i].p, g.cn, out_strides[i], out_elem[i], true, &spans[i].bytes))) return rc;
-    if ((rc = refuse_overlap(ctx, fn, spans, 4))) return rc;
-    ctx->ktimes_on = false;   // (no per-launch brackets here; o2v_hip_voxelize sets the flag again from its params)
-    DsOut o{};
-    if (count) o.count = count, o.k0 = count_strides[0], o.k1 = count_strides[1], o.k2 = count_strides[2];
-    if (solid) o.solid = solid, o.s0 = solid_strides[0], o.s1 = solid_strides[1], o.s2 = solid_strides[2];
-    if (values) o.values = values, o.v0 = value_strides[0], o.v1 = value_strides[1], o.v2 = value_strides[2];
-    if (argb) {
-        o.argb = argb, o.a0 = argb_strides[0], o.a1 = argb_strides[1], o.a2 = argb_strides[2];
-        o.colors = colors, o.c0 = color_strides[0], o.c1 = color_strides[1], o.c2 = color_strides[2];
-    }
-    hipStream_t s = ctx->stream;
-    // a workgroup per item, and no more than keep every CU's LDS full (16.6 KB each)
-    const dim3 blocks((uint32_t) std::min<uint64_t>(g.items, (uint64_t) ctx->num_cus * 8u));
-    O2V_CHECK(ctx->ds_times.mark(0, s));
-    with_set_format(sg, [&](auto fmt, auto vec) {
-        O2V_LAUNCH("k_downsample", s, (k_downsample<decltype(fmt)::value, decltype(vec)::value>), blocks, dim3(kBlock), 0, s, sg.source(), g, o);
-    });
-    O2V_CHECK(hipGetLastError());
-    O2V_CHECK(ctx->ds_times.mark(1, s));
-    O2V_CHECK(hipStreamSynchronize(s));
-    O2V_CHECK(ctx->ds_times.finish());
-    return O2V_HIP_OK;
-}
-
-int o2v_hip_downsample_times(const o2v_hip_ctx *ctx, float out_ms[1])
-{
-    return ctx ? ctx->ds_times.read(out_ms) : O2V_HIP_ERR_BAD_ARGUMENT;
-}
-
-}  // extern "C"
-
-// ---- K18: signed crossing numbers ------------------------------------------------------------------------------------------
-
-namespace {
-
-// One axis of o2v_hip_crossings_dense, enqueued on the context's stream: the delta grid and totals cleared, the (triangle, line)
-// items enumerated and marked, the lines summed into dst.
-template <int A>
-int crossings_axis(o2v_hip_ctx *ctx, const Switches &sw, const Affine &xf, const uint32_t origin[3], const uint32_t dims[3], uint32_t ss,
-                   int32_t *dst, const uint64_t dst_strides[3], bool add)
-{
-    hipStream_t s = ctx->stream;
-    constexpr int U = (A + 1) % 3, V = (A + 2) % 3;
-    CrBox b{};
-    b.u0 = origin[U], b.v0 = origin[V], b.w0 = origin[A];
-    b.nu = dims[U], b.nv = dims[V], b.nw = dims[A];
-    b.ss = ss;
-    b.v_first = V == 0;   // (x first where a line has an x: the y rays' v)
-    b.n_lines = (uint64_t) b.nu * b.nv;
-    const uint64_t T = ctx->n_tris, n_blocks = (T + kBlock - 1) / kBlock;
-    O2V_CHECK(hipMemsetAsync(ctx->d_cr_delta.ptr, 0, b.n_lines * b.nw * sizeof(int32_t), s));
-    O2V_CHECK(hipMemsetAsync(ctx->d_cr_totals.ptr, 0, b.n_lines * sizeof(int32_t), s));
-    if (T) {
-        O2V_LAUNCH("k_cross_count", s, k_cross_count<A>, dim3((uint32_t) n_blocks), dim3(kBlock), 0, s, ctx->d_verts.ptr, T, xf, b, ctx->d_cr_ends.ptr,
-                   ctx->d_cr_blocks.ptr);
-        O2V_LAUNCH("k_fill_scan_blocks", s, k_fill_scan_blocks, dim3(1), dim3(kBlock), 0, s, ctx->d_cr_blocks.ptr, n_blocks, ctx->d_cr_ctr.ptr);
-        O2V_LAUNCH("k_fill_offsets", s, k_fill_offsets, dim3((uint32_t) n_blocks), dim3(kBlock), 0, s, ctx->d_cr_ends.ptr, T, ctx->d_cr_blocks.ptr);
-        O2V_LAUNCH("k_cross_mark", s, k_cross_mark<A>, dim3((uint32_t) ctx->num_cus * 8u), dim3(kBlock), 0, s, ctx->d_verts.ptr, T, xf, b,
-                   ctx->d_cr_ends.ptr, ctx->d_cr_ctr.ptr, ctx->d_cr_delta.ptr, ctx->d_cr_totals.ptr);
-    }
-    const dim3 line_blocks((uint32_t) ((b.n_lines + kBlock - 1) / kBlock));
-    const uint64_t s_first = dst_strides[b.v_first ? V : U], s_slow = dst_strides[b.v_first ? U : V], s_w = dst_strides[A];
-    // (the ray along dst's unit stride and the lines not: the lanes of k_cross_prefix would each write a row of their own)
-    if (s_w == 1u && s_first != 1u && !sw.cross_no_tile) {
-        if (add)
-            O2V_LAUNCH("k_cross_prefix_tile", s, k_cross_prefix_tile<true>, line_blocks, dim3(kBlock), 0, s, ctx->d_cr_delta.ptr, ctx->d_cr_totals.ptr, b,
-                       dst, s_first, s_slow);
-        else
-            O2V_LAUNCH("k_cross_prefix_tile", s, k_cross_prefix_tile<false>, line_blocks, dim3(kBlock), 0, s, ctx->d_cr_delta.ptr, ctx->d_cr_totals.ptr, b,
-                       dst, s_first, s_slow);
-    } else if (add)
-        O2V_LAUNCH("k_cross_prefix", s, k_cross_prefix<true>, line_blocks, dim3(kBlock), 0, s, ctx->d_cr_delta.ptr, ctx->d_cr_totals.ptr, b, dst, s_first,
-                   s_slow, s_w);
-    else
-        O2V_LAUNCH("k_cross_prefix", s, k_cross_prefix<false>, line_blocks, dim3(kBlock), 0, s, ctx->d_cr_delta.ptr, ctx->d_cr_totals.ptr, b, dst, s_first,
-                   s_slow, s_w);
-    O2V_CHECK(hipGetLastError());
-    return O2V_HIP_OK;
-}
-
-// An axis failed part-way: the runtime's error state is cleared, as o2v_hip_mesh_distance_dense does on its parity path (dst may
-// hold the earlier axes' sums by then).
-int axis_failed(o2v_hip_ctx *, int rc)
-{
-    (void) hipGetLastError();
-    return rc;
-}
-
-}  // namespace
-
-extern "C" {
-
-int o2v_hip_crossings_dense(o2v_hip_ctx *ctx, const o2v_hip_params *params, uint32_t axes, const uint32_t origin[3], const uint32_t dims[3],
-                            int32_t *dst, const uint64_t dst_strides[3])
-{
-    static const char fn[] = "o2v_hip_crossings_dense";
-    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
-    if (!params || !origin || !dims || !dst || !dst_strides) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    if (axes < 1u || axes > 7u) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "axes must be 1 ... 7 (bit 0 x, 1 y, 2 z), not " + std::to_string(axes));
-    const uint32_t ss = params->supersampling ? params->supersampling : 1u;
-    if (ss > 2u || params->resolution == 0u)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "resolution must be positive and supersampling 1 or 2");
-    if (params->z_begin || params->z_end || params->x_begin || params->x_end || params->y_begin || params->y_end)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "the slab and tile fields of params must be 0 (the box is origin, dims)");
-    for (int a = 0; a < 3; ++a) {
-        if (!dims[a] || (uint64_t) origin[a] + dims[a] > params->resolution)
-            return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "the box must have dims >= 1 and lie within the grid");
-        if (dims[a] > kMdMaxDim) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "a box of more than 65 535 voxels along an axis");
-    }
-    const uint64_t T = ctx->n_tris;
-    const uint32_t n_axes = (uint32_t) __builtin_popcount(axes);
-    // (a voxel's value is bounded by two rays per axis and one crossing per triangle and ray)
-    if (T > 0x7fffffffull / (2u * n_axes))
-        return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "2 x " + std::to_string(n_axes) + " rays x " + std::to_string(T) + " triangles is above 2^31 - 1");
-    O2V_CHECK(hipSetDevice(ctx->device));
-    ctx->ktimes_on = false;   // (no per-launch brackets here; o2v_hip_voxelize sets the flag again from its params)
-    int rc;
-    if ((rc = check_grid(ctx, fn, "dst", dst, dims, dst_strides, 4u, true))) return rc;
-    // the transform k_setup computes for these params, as o2v_hip_mesh_distance_dense takes it
-    Affine xf{};
-    if (T) {
-        const float *e = params->bounds_known ? params->bounds : ctx->mesh_bounds_hint;
-        xf = compute_mesh_transform(V3{e[0], e[1], e[2]}, V3{e[3], e[4], e[5]}, params->resolution * ss, params->unit_transform);
-    }
-    const uint64_t voxels = (uint64_t) dims[0] * dims[1] * dims[2];
-    uint64_t lines = 0;   // of the axis with the most
-    for (int a = 0; a < 3; ++a)
-        if (axes >> a & 1u) lines = std::max(lines, voxels / dims[a]);
-    if ((rc = grow_scratch(ctx, ctx->d_cr_delta, voxels, fn, "delta grid")) || (rc = grow_scratch(ctx, ctx->d_cr_totals, lines, fn, "line totals")) ||
-        (rc = grow_scratch(ctx, ctx->d_cr_ends, T, fn, "item ends")) || (rc = grow_scratch(ctx, ctx->d_cr_blocks, (T + kBlock - 1) / kBlock, fn, "block sums")) ||
-        (rc = grow_scratch(ctx, ctx->d_cr_ctr, 1u, fn, "counter")))
-        return rc;
-    hipStream_t s = ctx->stream;
-    const Switches sw = read_switches();
-    bool add = false;
-    O2V_CHECK(ctx->cr_times.mark(0, s));
-    if (axes & 1u) {
-        if ((rc = crossings_axis<0>(ctx, sw, xf, origin, dims, ss, dst, dst_strides, add))) return axis_failed(ctx, rc);
-        add = true;
-    }
-    O2V_CHECK(ctx->cr_times.mark(1, s));
-    if (axes & 2u) {
-        if ((rc = crossings_axis<1>(ctx, sw, xf, origin, dims, ss, dst, dst_strides, add))) return axis_failed(ctx, rc);
-        add = true;
-    }
-    O2V_CHECK(ctx->cr_times.mark(2, s));
-    if (axes & 4u)
-        if ((rc = crossings_axis<2>(ctx, sw, xf, origin, dims, ss, dst, dst_strides, add))) return axis_failed(ctx, rc);
-    O2V_CHECK(ctx->cr_times.mark(3, s));
-    O2V_CHECK(hipStreamSynchronize(s));
-    O2V_CHECK(ctx->cr_times.finish());
-    for (int a = 0; a < 3; ++a)
-        if (!(axes >> a & 1u)) ctx->cr_times.ms[a] = 0.f;
-    return O2V_HIP_OK;
-}
-
-int o2v_hip_crossings_times(const o2v_hip_ctx *ctx, float out_ms[3])
-{
-    return ctx ? ctx->cr_times.read(out_ms) : O2V_HIP_ERR_BAD_ARGUMENT;
-}
-
-}  // extern "C"
-
-// ---- K19: per-label statistics of a dense grid -------------------------------------------------------------------------------
-
-namespace {
-
-constexpr uint32_t kLsMaxExtent = 65536;           // origin + dims per axis: a coordinate is below 2^16 ...
-constexpr uint64_t kLsMaxVoxels = 0x7fffffffull;   // ... and there are fewer than 2^31 voxels, so no sum reaches 2^63 (include/o2v_hip.h)
-constexpr uint32_t kLsMaxLabels = 0x7ffffffeu;     // n_labels + 1 rows, the highest value an int32
-constexpr uint32_t kLsWhichKnown = O2V_HIP_STATS_BOX | O2V_HIP_STATS_SUMS | O2V_HIP_STATS_MOMENTS | O2V_HIP_STATS_FACES;
-
-static_assert(kLsI32 == O2V_HIP_LABELS_I32 && kLsU8 == O2V_HIP_LABELS_U8 && kLsBox == O2V_HIP_STATS_BOX && kLsSums == O2V_HIP_STATS_SUMS &&
-                  kLsMoments == O2V_HIP_STATS_MOMENTS && kLsFaces == O2V_HIP_STATS_FACES && kLsCols == O2V_HIP_STATS_COLUMNS,
-              "one set of formats, bits and columns for the callers and the kernel");
-
-}  // namespace
-
-extern "C" {
-
-int o2v_hip_label_stats(o2v_hip_ctx *ctx, const void *labels, uint32_t format, const uint64_t strides[3], const uint32_t dims[3],
-                        const uint32_t origin[3], uint32_t n_labels, uint32_t which, int64_t *table, uint64_t *out_outside)
-{
-    static const char fn[] = "o2v_hip_label_stats";
-    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
-    const Switches sw = read_switches();
-    if (!labels || !strides || !dims || !origin || !table || !out_outside) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    if (!dims[0] || !dims[1] || !dims[2]) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "zero dims");
-    if (format != O2V_HIP_LABELS_I32 && format != O2V_HIP_LABELS_U8)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown format " + std::to_string(format));
-    if (which & ~kLsWhichKnown) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown bits in which = " + std::to_string(which));
-    if (format == O2V_HIP_LABELS_U8 && n_labels > 255u)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "n_labels " + std::to_string(n_labels) + " is above 255, the highest value of a U8 grid");
-    if ((uintptr_t) table % sizeof(int64_t) || (format == O2V_HIP_LABELS_I32 && (uintptr_t) labels % sizeof(int32_t)))
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "table must be 8-byte aligned and an I32 grid 4-byte aligned");
-    for (int a = 0; a < 3; ++a) {
-        if (dims[a] > kLsMaxExtent) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "a grid of more than 65 536 voxels along an axis");
-        if ((uint64_t) origin[a] + dims[a] > kLsMaxExtent) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "origin + dims is above 65 536 along an axis");
-    }
-    const uint64_t voxels = (uint64_t) dims[0] * dims[1] * dims[2];   // (below 2^48)
-    if (voxels > kLsMaxVoxels) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, std::to_string(voxels) + " voxels: the sums hold at most 2^31 - 1");
-    if (n_labels > kLsMaxLabels) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "n_labels is above 2^31 - 2");
-    // (the limits stand before the look at the memory: a box that is too large is refused as that, whatever it reaches)
-    O2V_CHECK(hipSetDevice(ctx->device));
-    const uint32_t elem = format == O2V_HIP_LABELS_I32 ? 4u : 1u;
-    const uint64_t rows = (uint64_t) n_labels + 1u, tbytes = rows * kLsCols * sizeof(int64_t);
-    uint64_t gbytes = 0;
-    int rc;
-    if ((rc = check_grid(ctx, fn, "labels", labels, dims, strides, elem, false, &gbytes)) || (rc = check_device_range(ctx, fn, table, tbytes, "table")))
-        return rc;
-    const Span spans[] = {{"table", table, tbytes}, {"labels", labels, gbytes}};
-    if ((rc = refuse_overlap(ctx, fn, spans, 1))) return rc;
-    if ((rc = grow_scratch(ctx, ctx->d_ls_ctr, 1u, fn, "counter")) || (rc = grow_scratch(ctx, ctx->h_ls_ctr, 1u, fn, "counter"))) return rc;
-    ctx->ktimes_on = false;   // (no per-launch brackets here; o2v_hip_voxelize sets the flag again from its params)
-    const uint32_t lane = format == O2V_HIP_LABELS_I32 ? ls_lane<kLsI32>() : ls_lane<kLsU8>();
-    LsGrid g{};
-    for (int a = 0; a < 3; ++a) g.n[a] = dims[a], g.o[a] = origin[a];
-    g.n_labels = n_labels, g.which = which;
-    g.cpr = (dims[0] + lane - 1u) / lane;
-    g.chunks = (uint32_t) ((uint64_t) g.cpr * dims[1] * dims[2]);   // (at most the voxels)
-    g.groups = (g.chunks + kBlock - 1u) / kBlock;
-    // a range of groups per workgroup, and no more workgroups than keep every CU's LDS full (17.5 KB each)
-    const uint32_t max_blocks = std::max(1u, (uint32_t) ctx->num_cus * 8u);
-    g.per_wg = (g.groups + max_blocks - 1u) / max_blocks;
-    const dim3 blocks((g.groups + g.per_wg - 1u) / g.per_wg);
-    g.table = sw.ls_no_table ? 0u : 1u;
-    // 16-byte loads: unit x stride and every row 16-byte aligned
-    const bool vec = strides[0] == 1u && (uintptr_t) labels % 16u == 0 && strides[1] * elem % 16u == 0 && strides[2] * elem % 16u == 0;
-    const RaySource src{labels, strides[0], strides[1], strides[2], 0.f};
-    long long *const tab = reinterpret_cast<long long *>(table);
-    unsigned long long *const ctr = ctx->d_ls_ctr.ptr;
-    hipStream_t s = ctx->stream;
-    O2V_CHECK(ctx->ls_times.mark(0, s));
-    O2V_LAUNCH("k_ls_init", s, k_ls_init, dim3(stream_grid(ctx, rows * kLsCols, 8u)), dim3(kBlock), 0, s, tab, rows, which, ctr);
-    O2V_CHECK(ctx->ls_times.mark(1, s));
-    auto launch = [&](auto fmt, auto v, auto faces) {
-        O2V_LAUNCH("k_label_stats", s, (k_label_stats<decltype(fmt)::value, decltype(v)::value, decltype(faces)::value>), blocks, dim3(kBlock), 0, s, src,
-                   g, tab, ctr);
-    };
-    auto with_faces = [&](auto fmt, auto v) { (which & O2V_HIP_STATS_FACES) ? launch(fmt, v, std::true_type{}) : launch(fmt, v, std::false_type{}); };
-    auto with_vec = [&](auto fmt) { vec ? with_faces(fmt, std::true_type{}) : with_faces(fmt, std::false_type{}); };
-    if (format == O2V_HIP_LABELS_I32) with_vec(std::integral_constant<uint32_t, kLsI32>{});
-    else with_vec(std::integral_constant<uint32_t, kLsU8>{});
-    O2V_CHECK(hipGetLastError());
-    O2V_CHECK(ctx->ls_times.mark(2, s));
-    O2V_CHECK(hipMemcpyAsync(ctx->h_ls_ctr.ptr, ctr, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    O2V_CHECK(hipStreamSynchronize(s));
-    O2V_CHECK(ctx->ls_times.finish());
-    *out_outside = ctx->h_ls_ctr.ptr[0];
-    return O2V_HIP_OK;
-}
-
-int o2v_hip_label_stats_times(const o2v_hip_ctx *ctx, float out_ms[2])
-{
-    return ctx ? ctx->ls_times.read(out_ms) : O2V_HIP_ERR_BAD_ARGUMENT;
-}
-
-}  // extern "C"
-
-// ---- K20: geodesic distances and shortest paths through a dense grid -----------------------------------------------------------
-
-namespace {
-
-constexpr uint32_t kGeoFlagsKnown = O2V_HIP_CC_INVERT | O2V_HIP_CC_SEED_BORDER | O2V_HIP_FLAG_STAGE_TIMES;
-
-static_assert(kGeoMaxDistance == O2V_HIP_GEO_MAX_DISTANCE && kGeoMaxWeight == O2V_HIP_GEO_MAX_WEIGHT, "one set of limits for the callers and the kernels");
-
-uint64_t geo_tiles(const uint32_t dims[3]) { return (uint64_t) ((dims[0] + 63u) / 64u) * ((dims[1] + 7u) / 8u) * ((dims[2] + 7u) / 8u); }
-
-// weights: each 0 ... 65 535, not all 0
-int geo_weights(o2v_hip_ctx *ctx, const char *fn, const uint32_t weights[3])
-{
-    for (int a = 0; a < 3; ++a)
-        if (weights[a] > kGeoMaxWeight) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "a weight of " + std::to_string(weights[a]) + " is above 65 535");
-    if (!(weights[0] | weights[1] | weights[2])) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "the weights are all 0: no step exists");
-    return O2V_HIP_OK;
-}
-
-// the size limits of both calls: a linear index is one int32
-int geo_limits(o2v_hip_ctx *ctx, const char *fn, const uint32_t dims[3], uint64_t n, const char *what)
-{
-    for (int a = 0; a < 3; ++a)
-        if (dims[a] > kCcMaxDim) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "a grid of more than 65 536 voxels along an axis");
-    const uint64_t voxels = (uint64_t) dims[0] * dims[1] * dims[2];   // (below 2^48)
-    if (voxels > kCcMaxVoxels)
-        return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, std::to_string(voxels) + " voxels do not fit an int32 index (at most 2^31 - 1)");
-    if (n > kCcMaxVoxels) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, std::string("more than 2^31 - 1 ") + what);
-    return O2V_HIP_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-uint64_t o2v_hip_geodesic_scratch_bytes(const uint32_t dims[3], uint32_t which)
-{
-    if (!dims || !dims[0] || !dims[1] || !dims[2] || which > O2V_HIP_GEO_SCRATCH_STRIDED) return 0;
-    return 8u * cc_words(dims) + 16u * geo_tiles(dims) + 64u + (which == O2V_HIP_GEO_SCRATCH_STRIDED ? 4u * (uint64_t) dims[0] * dims[1] * dims[2] : 0u);
-}
-
-int o2v_hip_geodesic_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
-                           const uint32_t weights[3], uint32_t flags, const int32_t *seeds, uint64_t n_seeds, uint32_t max_distance, int32_t *dist,
-                           const uint64_t dist_strides[3], uint64_t *out_reached)
-{
-    static const char fn[] = "o2v_hip_geodesic_dense";
-    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
-    const Switches sw = read_switches();
-    if (!dist || !dist_strides || !out_reached || !weights || (n_seeds && !seeds)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    SetGrid sg;
-    int rc;
-    if ((rc = set_grid(ctx, fn, grid, format, strides, dims, level, &sg)) || (rc = geo_weights(ctx, fn, weights))) return rc;
-    if (max_distance > kGeoMaxDistance) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "max_distance is above 2^31 - 2");
-    if (flags & ~kGeoFlagsKnown) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown flag bits in " + std::to_string(flags));
-    if ((uintptr_t) dist % sizeof(int32_t)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "dist must be 4-byte aligned");
-    if ((rc = geo_limits(ctx, fn, dims, n_seeds, "seeds"))) return rc;
-    uint64_t obytes = 0;
-    if ((rc = check_grid(ctx, fn, "dist", dist, dims, dist_strides, 4u, true, &obytes)) ||
-        (n_seeds && (rc = check_device_range(ctx, fn, seeds, n_seeds * 12u, "seeds"))))
-        return rc;
-    const Span spans[] = {{"dist", dist, obytes}, {"grid", grid, sg.bytes}, {"seeds", seeds, n_seeds * 12u}};
-    if ((rc = refuse_overlap(ctx, fn, spans, 1))) return rc;
-
-    GeoGrid g{};
-    g.nx = dims[0], g.ny = dims[1], g.nz = dims[2];
-    g.W = (dims[0] + 63u) / 64u;
-    g.tiles_y = (dims[1] + 7u) / 8u, g.tiles_z = (dims[2] + 7u) / 8u;
-    std::copy(weights, weights + 3, g.w);
-    g.max_distance = max_distance;
-    g.words = cc_words(dims);
-    const uint64_t voxels = (uint64_t) dims[0] * dims[1] * dims[2], tiles = geo_tiles(dims);   // (tiles: at most the words, below 2^31)
-    // the distances live in the caller's dist where linear index i is element i of it
-    const bool in_place = (dims[0] == 1u || dist_strides[0] == 1u) && (dims[1] == 1u || dist_strides[1] == dims[0]) &&
-                          (dims[2] == 1u || dist_strides[2] == (uint64_t) dims[0] * dims[1]);
-    if ((rc = grow_scratch(ctx, ctx->d_geo_bits, g.words, fn, "set bits")) || (rc = grow_scratch(ctx, ctx->d_geo_tiles, 4u * tiles, fn, "tile flags and lists")) ||
-        (rc = grow_scratch(ctx, ctx->d_geo_ctr, 8u, fn, "counters")) || (rc = grow_scratch(ctx, ctx->h_geo_ctr, 8u, fn, "counters")) ||
-        (!in_place && (rc = grow_scratch(ctx, ctx->d_geo_dist, voxels, fn, "distances"))))
-        return rc;
-    ctx->ktimes_on = false;   // (no per-launch brackets here; o2v_hip_voxelize sets the flag again from its params)
-    uint32_t *const D = in_place ? reinterpret_cast<uint32_t *>(dist) : ctx->d_geo_dist.ptr;
-    unsigned long long *const bits = ctx->d_geo_bits.ptr, *const ctr = ctx->d_geo_ctr.ptr;
-    uint32_t *const tile_flags[2] = {ctx->d_geo_tiles.ptr, ctx->d_geo_tiles.ptr + tiles};
-    uint32_t *const tile_list[2] = {ctx->d_geo_tiles.ptr + 2u * tiles, ctx->d_geo_tiles.ptr + 3u * tiles};
-    uint32_t *const cnt = reinterpret_cast<uint32_t *>(ctr + 2);                                   // the lists' lengths, the changed word
-    volatile uint32_t *const h_cnt = reinterpret_cast<volatile uint32_t *>(ctx->h_geo_ctr.ptr + 2);
-    const bool count = (flags & O2V_HIP_FLAG_STAGE_TIMES) != 0, use_tiles = !sw.geo_no_tiles;
-    const dim3 per_word(stream_grid(ctx, g.words * 64u, 16u));
-    hipStream_t s = ctx->stream;
-    O2V_CHECK(ctx->geo_times.mark(0, s));
-    O2V_CHECK(hipMemsetAsync(ctr, 0, 8u * sizeof(unsigned long long), s));
-    launch_classify(ctx, sg, (flags & O2V_HIP_CC_INVERT) ? 1u : 0u, bits);
-    O2V_CHECK(ctx->geo_times.mark(1, s));
-    O2V_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(D), (int) kGeoInf, voxels, s));
-    if (use_tiles) O2V_CHECK(hipMemsetAsync(tile_flags[0], 0, 2u * tiles * sizeof(uint32_t), s));
-    uint32_t *const fl0 = use_tiles ? tile_flags[0] : nullptr;
-    if (n_seeds)
-        O2V_LAUNCH("k_geo_seed_list", s, k_geo_seed_list, dim3(stream_grid(ctx, n_seeds, 8u)), dim3(kBlock), 0, s, g, bits, seeds, n_seeds, D, fl0, tile_list[0], cnt);
-    if (flags & O2V_HIP_CC_SEED_BORDER) O2V_LAUNCH("k_geo_seed_border", s, k_geo_seed_border, per_word, dim3(kBlock), 0, s, g, bits, D, fl0, tile_list[0], cnt);
-    O2V_CHECK(ctx->geo_times.mark(2, s));
-    // The rounds.  No cap: a round is launched only if the last one decreased a distance on a tile's rim (tiles) or anywhere
-    // (sweeps), and distances are whole numbers that only decrease.
-    uint64_t rounds = 0, visits = 0, reads = 0;
-    if (use_tiles) {
-        O2V_CHECK(hipMemcpyAsync(const_cast<uint32_t *>(h_cnt), cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        O2V_CHECK(hipStreamSynchronize(s));
-        ++reads;
-        for (uint32_t cur = 0, n = h_cnt[0]; n; cur ^= 1u, n = h_cnt[cur]) {
-            const uint32_t nxt = cur ^ 1u;
-            const dim3 blocks((uint32_t) std::min<uint64_t>(n, kCcMaxGrid));
-            O2V_CHECK(hipMemsetAsync(cnt + nxt, 0, sizeof(uint32_t), s));
-            if (count)
-                O2V_LAUNCH("k_geo_tiles", s, k_geo_tiles<true>, blocks, dim3(kBlock), 0, s, g, bits, D, tile_list[cur], n, tile_flags[cur], tile_flags[nxt],
-                           tile_list[nxt], cnt + nxt, ctr);
-            else
-                O2V_LAUNCH("k_geo_tiles", s, k_geo_tiles<false>, blocks, dim3(kBlock), 0, s, g, bits, D, tile_list[cur], n, tile_flags[cur], tile_flags[nxt],
-                           tile_list[nxt], cnt + nxt, ctr);
-            O2V_CHECK(hipMemcpyAsync(const_cast<uint32_t *>(h_cnt) + nxt, cnt + nxt, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            O2V_CHECK(hipStreamSynchronize(s));
-            ++rounds, ++reads, visits += n;
-        }
-    } else {
-        do {
-            O2V_CHECK(hipMemsetAsync(cnt + 2, 0, sizeof(uint32_t), s));
-            O2V_LAUNCH("k_geo_sweep", s, k_geo_sweep, per_word, dim3(kBlock), 0, s, g, bits, D, cnt + 2);
-            O2V_CHECK(hipMemcpyAsync(const_cast<uint32_t *>(h_cnt) + 2, cnt + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            O2V_CHECK(hipStreamSynchronize(s));
-            ++rounds, ++reads;
-        } while (h_cnt[2]);
-    }
-    O2V_CHECK(ctx->geo_times.mark(3, s));
-    O2V_LAUNCH("k_geo_write", s, k_geo_write, per_word, dim3(kBlock), 0, s, g, D, dist, dist_strides[0], dist_strides[1], dist_strides[2], ctr + 1);
-    O2V_CHECK(hipGetLastError());
-    O2V_CHECK(ctx->geo_times.mark(4, s));
-    O2V_CHECK(hipMemcpyAsync(ctx->h_geo_ctr.ptr, ctr, 2u * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    O2V_CHECK(hipStreamSynchronize(s));
-    O2V_CHECK(ctx->geo_times.finish());
-    const uint64_t counters[4] = {rounds, visits, ctx->h_geo_ctr.ptr[0], reads};
-    for (int i = 0; i < 4; ++i) ctx->geo_counters[i] = count ? counters[i] : 0u;
-    *out_reached = ctx->h_geo_ctr.ptr[1];
-    return O2V_HIP_OK;
-}
-
-int o2v_hip_geodesic_paths(o2v_hip_ctx *ctx, const int32_t *dist, const uint64_t dist_strides[3], const uint32_t dims[3], const uint32_t weights[3],
-                           const int32_t *targets, uint64_t n_targets, uint32_t max_len, int32_t *paths, int32_t *lengths)
-{
-    static const char fn[] = "o2v_hip_geodesic_paths";
-    if (!ctx) return O2V_HIP_ERR_BAD_ARGUMENT;
-    if (!dist || !dist_strides || !dims || !weights || (n_targets && (!targets || !lengths || (max_len && !paths))))
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
-    if (!dims[0] || !dims[1] || !dims[2]) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "zero dims");
-    int rc;
-    if ((rc = geo_weights(ctx, fn, weights))) return rc;
-    if ((uintptr_t) dist % sizeof(int32_t)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "dist must be 4-byte aligned");
-    if ((rc = geo_limits(ctx, fn, dims, n_targets, "targets"))) return rc;
-    O2V_CHECK(hipSetDevice(ctx->device));
-    const unsigned __int128 want = (unsigned __int128) n_targets * max_len * 12u;
-    if (want > (unsigned __int128) (~0ull >> 1)) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "paths: n_targets rows of max_len voxels reach past any allocation");
-    const uint64_t pbytes = (uint64_t) want;
-    uint64_t dbytes = 0;
-    if ((rc = check_grid(ctx, fn, "dist", dist, dims, dist_strides, 4u, false, &dbytes))) return rc;
-    if (!n_targets) return O2V_HIP_OK;
-    if ((rc = check_device_range(ctx, fn, targets, n_targets * 12u, "targets")) || (rc = check_device_range(ctx, fn, lengths, n_targets * 4u, "lengths")) ||
-        (pbytes && (rc = check_device_range(ctx, fn, paths, pbytes, "paths"))))
-        return rc;
-    const Span spans[] = {{"paths", paths, pbytes}, {"lengths", lengths, n_targets * 4u}, {"dist", dist, dbytes}, {"targets", targets, n_targets * 12u}};
-    if ((rc = refuse_overlap(ctx, fn, spans, 2))) return rc;
-    ctx->ktimes_on = false;   // (no per-launch brackets here; o2v_hip_voxelize sets the flag again from its params)
-    GeoTrace t{};
-    for (int a = 0; a < 3; ++a) t.dims[a] = dims[a], t.w[a] = weights[a], t.s[a] = dist_strides[a];
-    hipStream_t s = ctx->stream;
-    O2V_LAUNCH("k_geo_trace", s, k_geo_trace, dim3(stream_grid(ctx, n_targets, 8u)), dim3(kBlock), 0, s, t, dist, targets, n_targets, max_len, paths, lengths);
-    O2V_CHECK(hipGetLastError());
-    O2V_CHECK(hipStreamSynchronize(s));
-    return O2V_HIP_OK;
-}
-
-int o2v_hip_geodesic_times(const o2v_hip_ctx *ctx, float out_ms[4])
-{
-    return ctx ? ctx->geo_times.read(out_ms) : O2V_HIP_ERR_BAD_ARGUMENT;
-}
-
-int o2v_hip_geodesic_counters(const o2v_hip_ctx *ctx, uint64_t out4[4])
-{
-    if (!ctx || !out4) return O2V_HIP_ERR_BAD_ARGUMENT;
-    std::copy(ctx->geo_counters, ctx->geo_counters + 4, out4);
-    return O2V_HIP_OK;
-}
-
-}  // extern "C"
+// ---- K7 - K20: the dense-grid entry points, a host header per family (what they share: o2v_dev_host_args.hpp) -----------
+
+#include "o2v_dev_host_args.hpp"
+#include "o2v_dev_host_k7_dense.hpp"
+#include "o2v_dev_host_k8_distance.hpp"
+#include "o2v_dev_host_k9_mesh.hpp"
+#include "o2v_dev_host_k10_surface.hpp"
+#include "o2v_dev_host_k11_raycast.hpp"
+#include "o2v_dev_host_k12_components.hpp"
+#include "o2v_dev_host_k13_gather.hpp"
+#include "o2v_dev_host_k17_downsample.hpp"
+#include "o2v_dev_host_k19_label_stats.hpp"
 
 extern "C" {
 

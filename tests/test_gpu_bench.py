@@ -89,6 +89,50 @@ def test_kernel_times_cover_the_pipeline():
     assert abs(kt["k_voxelize<false>"][0] - tm["voxelize_ms"]) < 0.05 + 0.2 * tm["voxelize_ms"]
 
 
+# (a child process: obj2voxel_amd.dense needs torch imported before the library is loaded, which this process may have loaded already)
+_KERNEL_TIMES_SCOPE_CHILD = """
+import json
+import torch  # first
+from obj2voxel_amd import dense, hip, meshes
+d = hip.DeviceVoxelizer(0)
+try:
+    d.set_triangles(meshes.unit_cube())                    # a closed cube of 12 triangles
+    d.voxelize(32, read=False)                             # (a context's first pass zeroes its counters with a launch of its own)
+    d.voxelize(32, read=False, kernel_times=True)
+    first = d.kernel_times()
+    grid = torch.zeros((8, 8, 64), dtype=torch.uint8, device="cuda")   # one tile of K12
+    grid[1:3, 2, 5:9] = 1
+    grid[6, 6, 60] = 1
+    labels, n = dense.components(d, grid)
+    cuts, _ = d.plan_slabs(32, 2)
+    after_dense = d.kernel_times()
+    d.voxelize(32, read=False)
+    plain = d.kernel_times()
+    d.voxelize(32, read=False, kernel_times=True)
+    again = d.kernel_times()
+finally:
+    d.close()
+print(json.dumps({"first": first, "components": n, "cuts": cuts, "after_dense": after_dense, "plain": plain, "again": again}))
+"""
+
+
+def test_kernel_times_belong_to_the_voxelize_call():
+    """O2V_HIP_FLAG_KERNEL_TIMES holds for the o2v_hip_voxelize call that names it and for nothing else: a dense-grid call
+    (o2v_hip_components_dense) and o2v_hip_plan_slabs behind it leave o2v_hip_get_kernel_times as it was - the same names, launch
+    counts and times -, the next call without the flag empties it, and the next one with the flag brackets the pipeline's launches
+    again and none of the dense call's."""
+    r = subprocess.run([sys.executable, "-c", _KERNEL_TIMES_SCOPE_CHILD], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    got = json.loads(r.stdout.strip().splitlines()[-1])
+    first, again = got["first"], got["again"]
+    assert first and all(launches >= 1 for _, launches in first.values()), first
+    assert got["components"] == 2 and len(got["cuts"]) == 3
+    assert got["after_dense"] == first
+    assert got["plain"] == {}
+    assert {k: v[1] for k, v in again.items()} == {k: v[1] for k, v in first.items()}, (first, again)
+    assert not any(k.startswith("k_cc_") for k in again), again
+
+
 def test_stage_times_only_on_request():
     """o2v_hip_timings: the clip kernel's duration is measured in every call (events on its own dispatch), the stage intervals and
     total_ms only with O2V_HIP_FLAG_STAGE_TIMES (an event between two kernels costs device time)."""

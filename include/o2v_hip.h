@@ -933,6 +933,70 @@ int o2v_hip_geodesic_times(const o2v_hip_ctx *ctx, float out_ms[4]);
  * the propagation.  With O2V_GEO_NO_TILES=1: the whole-grid sweeps, 0, 0, the reads. */
 int o2v_hip_geodesic_counters(const o2v_hip_ctx *ctx, uint64_t out4[4]);
 
+/* ---- local thickness and ball morphology of a dense grid ---------------------------------------------------
+ *
+ * How thick is the model here, and where is it thinner than t: for every voxel of a set the largest inscribed ball that holds it,
+ * and the opening, erosion, dilation and closing by a ball that fall out of the same passes.  Exact integers (squared radii),
+ * the same bits on every run, defined so that a numpy restatement reproduces every bit.
+ *
+ * The set.  grid, format, strides, dims and level are those of o2v_hip_components_dense (U8, BITS, F32_BELOW with a level); the
+ * grid is only read.  S is the solid voxels of the box, or with O2V_HIP_THICK_BACKGROUND the voxels of the box that are not solid.
+ * cap = max_radius2, 1 <= cap <= 2^14 = O2V_HIP_THICK_MAX_RADIUS2.
+ *
+ *   depth2(p)  for p in S: the smallest |p - e|^2 over the voxels e of the box that are not in S.  With O2V_HIP_THICK_BORDER the
+ *              voxels outside the box count as not in S: a pointwise min with (x+1)^2, (nx-x)^2, (y+1)^2, (ny-y)^2, (z+1)^2,
+ *              (nz-z)^2 (the nearest outside voxel lies along an axis).  0x7FFFFFFF where there is no such voxel; 0 for p not in S.
+ *   R(c)       = min(depth2(c), cap).
+ *   T(p)       = max { R(c) : c in S, |p - c|^2 < R(c) } for p in S; 0 otherwise.  So 1 <= T <= cap on S, and T(p) == cap exactly
+ *              when p lies in the opening of S by the ball {q : |q|^2 < cap}: a value at the cap means "at least".  Without BORDER
+ *              the balls are clipped to the box.
+ *
+ * Outputs, device memory, strides in elements per axis x, y, z, any order; neither may map two voxels to one element:
+ *   dst     int32 T.  With O2V_HIP_THICK_F32: float32 (float) (2.0 * sqrt((double) T) - 1.0), 0 outside S - the diameter in voxels
+ *           of the largest inscribed ball, bit-identical to the same expression in numpy float64 -> float32.  A wall w voxels
+ *           wide reads w for odd w and w - 1 for even w: the centre of a digital ball is a voxel, so its diameter is odd.
+ *           With O2V_HIP_THICK_OPEN_ONLY the ball stage is skipped: dst is cap inside the opening and R(p) elsewhere in S, a lower
+ *           bound of T that costs two distance transforms.
+ *   depth2  int32, may be NULL: the values above (with BORDER: after the min).
+ *
+ * Stages: depth2 (an x pass and o2v_hip_distance_dense's two envelope passes); the core {depth2 >= cap} and the squared distance to
+ * it (the same three passes), which gives the opening; the ball centres - the voxels of S with depth2 < cap, less those whose ball
+ * a 26-neighbour's ball covers (o2v_hip_thickness_cover_table) - counted and listed in ascending linear index; an atomic max of
+ * R(c) over the ball of every listed centre; the float conversion.  The ball stage writes about half the local thickness squared
+ * per voxel of the regions thinner than the cap: that is why the cap is mandatory and bounded.
+ * flags: O2V_HIP_THICK_BACKGROUND, _BORDER, _F32, _OPEN_ONLY, O2V_HIP_FLAG_STAGE_TIMES (o2v_hip_thickness_counters counts the ball voxels).
+ *
+ * Refused before any launch, the outputs untouched, in this order: null arguments; the set grid's checks (zero dims, an unknown
+ * format, BITS with strides[0] != 1, a level that is not finite, a grid that is not device memory of the context's device inside
+ * one allocation); unknown flag bits; max_radius2 of 0 (O2V_HIP_ERR_BAD_ARGUMENT) or above 2^14 (O2V_HIP_ERR_LIMIT); nx * ny * nz
+ * above 2^31 - 1 (O2V_HIP_ERR_LIMIT: a centre is one int32 index); (nx-1)^2 + (ny-1)^2 + (nz-1)^2 above 2^31 - 2
+ * (o2v_hip_distance_dense's limit); dst or depth2 strides that map two voxels to one element, or memory that is not the device's;
+ * any two of grid, dst and depth2 overlapping.  A failed scratch allocation returns O2V_HIP_ERR_OUT_OF_MEMORY and the context stays
+ * usable; after such an error the outputs are unspecified.  The call runs on the context's stream and returns when the writes have
+ * landed (the caller must have finished writing grid).
+ *
+ * Scratch of the context, grown on demand: o2v_hip_thickness_scratch_bytes(dims, max_radius2, have_depth2) =
+ *   4 * nx * ny * nz if have_depth2 is 0 (the depth grid)  +  o2v_hip_distance_scratch_bytes(dims, ...) (the envelope stacks, shared
+ *   with o2v_hip_distance_dense)  +  8 * (ceil(nx * ny * nz / 256) + 1) (block offsets)  +  12 * (max_radius2 + 1) (the cover table)
+ *   +  64; on top of that 4 bytes per kept centre, known only once they are counted.  (0 for zero dims or a cap out of range.) */
+enum { O2V_HIP_THICK_BACKGROUND = 16u, O2V_HIP_THICK_BORDER = 32u, O2V_HIP_THICK_F32 = 64u, O2V_HIP_THICK_OPEN_ONLY = 128u };
+enum { O2V_HIP_THICK_MAX_RADIUS2 = 1u << 14 };
+int o2v_hip_thickness_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+                            uint32_t flags, uint32_t max_radius2, void *dst, const uint64_t dst_strides[3], int32_t *depth2 /* may be NULL */,
+                            const uint64_t depth2_strides[3]);
+uint64_t o2v_hip_thickness_scratch_bytes(const uint32_t dims[3], uint32_t max_radius2, int have_depth2);
+/* The device times (ms) of the last o2v_hip_thickness_dense call: depth, opening, initialisation + list (the host's read of the
+ * count included), balls, conversion. */
+int o2v_hip_thickness_times(const o2v_hip_ctx *ctx, float out_ms[5]);
+/* Of the last o2v_hip_thickness_dense call: the candidate centres (the voxels of S with depth2 < cap), the centres kept, and the
+ * ball voxels visited - the last only with O2V_HIP_FLAG_STAGE_TIMES, else 0.  With OPEN_ONLY all three are 0. */
+int o2v_hip_thickness_counters(const o2v_hip_ctx *ctx, uint64_t out3[3]);
+/* The cover table of max_radius2 (1 ... 2^14), on the host; needs no context and no device: out[(k - 1) * (max_radius2 + 1) + R] =
+ * L_k[R] = 1 + max { |q - v|^2 : q in Z^3, |q|^2 < R } for v = (1, 0, 0), (1, 1, 0), (1, 1, 1) (k = |v|^2) and R = 1 ... max_radius2 -
+ * the smallest radius^2 at which the discrete ball of a neighbour at offset v contains the ball of radius^2 R; L_k[0] = 0.
+ * L_k[R] > R.  O2V_HIP_ERR_BAD_ARGUMENT for a null out or a max_radius2 out of range. */
+int o2v_hip_thickness_cover_table(uint32_t max_radius2, uint32_t *out /* [3][max_radius2 + 1] */);
+
 int o2v_hip_get_timings(const o2v_hip_ctx *ctx, o2v_hip_timings *out);
 /* Per-kernel device times of the last o2v_hip_voxelize call made with O2V_HIP_FLAG_KERNEL_TIMES (else none): up to
  * max_entries entries are written, *out_count receives how many there are. */

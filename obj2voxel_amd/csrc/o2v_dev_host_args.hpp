@@ -1,4 +1,4 @@
-// Host side of the dense-grid entry points (K7 - K20): what they share.  Refusals, the checks of the caller's memory, scratch,
+// Host side of the dense-grid entry points (K7 - K21): what they share.  Refusals, the checks of the caller's memory, scratch,
 // the set grid, the limits, run-time values as template arguments.  Included by o2v_device.hip only, once, like the kernels'
 // headers: it needs the context and the launch macros defined there.
 

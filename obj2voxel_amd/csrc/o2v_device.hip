@@ -50,6 +50,8 @@
 //                              second moments and exposed faces, one pass of runs into a table in LDS; outside the pipeline
 //   K20 k_geo_*                o2v_hip_geodesic_dense / o2v_hip_geodesic_paths: shortest path lengths through the set of a dense
 //                              grid, a relaxation tile by tile in LDS, round by round; the walk back; outside the pipeline
+//   K21 k_thick_*              o2v_hip_thickness_dense: local thickness, opening and erosion by a ball - two of K8's distance
+//                              transforms, a pruned list of ball centres, an atomicMax per ball voxel; outside the pipeline
 //   plan k_zhist               o2v_hip_plan_slabs: predicted hits per z layer -> work-balanced slabs for N GPUs
 // With the direct MAX path K1's counters reach the host while K2 runs, and only the stages that have work are enqueued
 // behind it.  N > 1 GPUs: o2v_hip_voxelize_sharded (bounds / work-histogram passes sharded over the ranks, RCCL).
@@ -107,6 +109,7 @@ namespace {
 #include "o2v_dev_k18_crossings.hpp"
 #include "o2v_dev_k19_label_stats.hpp"
 #include "o2v_dev_k20_geodesic.hpp"
+#include "o2v_dev_k21_thickness.hpp"
 
 }  // namespace
 
@@ -470,6 +473,18 @@ struct o2v_hip_ctx {
     PinnedArray<unsigned long long> h_geo_ctr;
     StageTimes<4> geo_times;
     uint64_t geo_counters[4] = {};
+    // K21 (o2v_hip_thickness_dense): the depth grid where the caller passes none, the block offsets (+ the count) and the list
+    // of the kept ball centres, [0] candidates, [2] ball voxels visited, grown on demand; the envelope stacks are K8's
+    // (d_dist_stack); the cover table of the last cap, on the device and page-locked; the times of the five stages and the
+    // three counters of the last call
+    DevArray<int32_t> d_thick_depth, d_thick_list;
+    DevArray<unsigned long long> d_thick_boff, d_thick_ctr;
+    PinnedArray<unsigned long long> h_thick_ctr;
+    DevArray<uint32_t> d_thick_table;
+    PinnedArray<uint32_t> h_thick_table;
+    uint32_t thick_table_cap = 0;
+    StageTimes<5> thick_times;
+    uint64_t thick_counters[3] = {};
 
     // results of the last run
     uint64_t n_vox = 0;
@@ -2436,7 +2451,7 @@ int o2v_hip_voxels_device_ptr(o2v_hip_ctx *ctx, const uint32_t **out_ptr, uint64
 
 }  // extern "C"
 
-// ---- K7 - K20: the dense-grid entry points, a host header per family (what they share: o2v_dev_host_args.hpp) -----------
+// ---- K7 - K21: the dense-grid entry points, a host header per family (what they share: o2v_dev_host_args.hpp) -----------
 
 #include "o2v_dev_host_args.hpp"
 #include "o2v_dev_host_k7_dense.hpp"
@@ -2448,6 +2463,7 @@ int o2v_hip_voxels_device_ptr(o2v_hip_ctx *ctx, const uint32_t **out_ptr, uint64
 #include "o2v_dev_host_k13_gather.hpp"
 #include "o2v_dev_host_k17_downsample.hpp"
 #include "o2v_dev_host_k19_label_stats.hpp"
+#include "o2v_dev_host_k21_thickness.hpp"
 
 extern "C" {
 

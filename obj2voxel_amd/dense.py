@@ -28,7 +28,10 @@ moments and the exposed faces as exact integers, and component_stats, centroids,
 crop are built on them: the parts of a scan cropped one by one, the largest body kept, a solid's volume, centre of mass and inertia
 tensor (o2v_hip_label_stats); geodesic_distance says how far every voxel of a set is from the nearest seed
 without leaving the set - hop counts, the chamfer metric or any integer step costs, from listed seeds or the border - and
-shortest_paths walks back along those distances (o2v_hip_geodesic_dense / o2v_hip_geodesic_paths).
+shortest_paths walks back along those distances (o2v_hip_geodesic_dense / o2v_hip_geodesic_paths, DESIGN.md section 23);
+local_thickness says how thick a solid is at every voxel - the largest inscribed ball that holds it -, thin_regions where it is
+thinner than t, and inner_distance, erode, dilate, opening and closing are the ball morphology that falls out of the same passes
+(o2v_hip_thickness_dense).
 
 torch is imported first on purpose: the library must bind to the HIP runtime torch loaded (a process that loaded the library
 before torch holds two separate runtime copies, and this module refuses to work there).
@@ -870,6 +873,145 @@ def shortest_paths(dv, dist, targets, *, metric="chamfer", connectivity=26, weig
         dv.geodesic_paths(dist.data_ptr(), _strides(dist), dims, weights, targets.data_ptr(), n, int(max_len), paths.data_ptr() if max_len else None,
                           lengths.data_ptr())
     return paths, lengths
+
+
+# ---- local thickness and ball morphology -----------------------------------------------------------------
+
+MAX_THICK_RADIUS2 = hip.THICK_MAX_RADIUS2   # local_thickness and the morphology: floor(radius^2) + 1 is at most this (radius < 128)
+_THICK_FORMATS = {"r2": (0, torch.int32), "thickness": (hip.THICK_F32, torch.float32)}
+
+
+def _limit_thickness(dims):
+    """The size limits of local_thickness and the morphology: a centre is one int32 index, a squared distance one int32."""
+    _limit_voxels(dims)
+    if sum((n - 1) ** 2 for n in dims) > MAX_NEAREST_D2:
+        raise ValueError(f"the grid's extent {dims} [x, y, z] has (nx-1)^2 + (ny-1)^2 + (nz-1)^2 above {MAX_NEAREST_D2}")
+
+
+def _radius_cap(radius, name="radius"):
+    """cap = floor(radius^2) + 1 of a radius in voxels: the ball {|q|^2 < cap} is {|q| <= radius}."""
+    if isinstance(radius, bool) or not isinstance(radius, numbers.Real) or not float(radius) >= 0.0:
+        raise ValueError(f"{name} must be a number >= 0, not {radius!r}")
+    r2 = float(radius) * float(radius)
+    if not r2 < MAX_THICK_RADIUS2:
+        raise ValueError(f"{name} {radius!r}: floor({name}^2) + 1 is above {MAX_THICK_RADIUS2} (at most {math.sqrt(MAX_THICK_RADIUS2 - 1):.2f} voxels)")
+    return math.floor(r2) + 1
+
+
+def _byte_ranges_overlap(a, b):
+    """Whether the address ranges two tensors reach overlap - what o2v_hip_thickness_dense refuses of its two outputs (two
+    slices of one batch tensor share a storage and do not overlap)."""
+    def span(t):
+        reach = sum((n - 1) * abs(st) for n, st in zip(t.shape, t.stride())) + 1
+        return t.data_ptr(), t.data_ptr() + reach * t.element_size()
+    (a0, a1), (b0, b1) = span(a), span(b)
+    return a0 < b1 and b0 < a1
+
+
+def _thickness(dv, grid, cap, level, background, border, flags, dst_dtype, out, depth2, out_name="out", depth2_name="depth2"):
+    """One o2v_hip_thickness_dense call: (dst, depth2 or None), new contiguous tensors where out / depth2 is None / True."""
+    device, fmt, level, dims = _set_grid(dv, grid, level, _limit_thickness)
+    shape = (dims[2], dims[1], dims[0])
+    if out is None:
+        out = torch.empty(shape, dtype=dst_dtype, device=device)
+    else:
+        _check_grid(out, out_name, dst_dtype, device, shape)
+        _outside_storage(out, out_name, grid)
+    if depth2 is True:
+        depth2 = torch.empty(shape, dtype=torch.int32, device=device)
+    elif depth2 is not None and depth2 is not False:
+        _check_grid(depth2, depth2_name, torch.int32, device, shape)
+        _outside_storage(depth2, depth2_name, grid)
+        if _byte_ranges_overlap(depth2, out):
+            raise ValueError(f"{depth2_name} must not overlap {out_name}")
+    else:
+        depth2 = None
+    flags |= (hip.THICK_BACKGROUND if background else 0) | (hip.THICK_BORDER if border else 0)
+    _sync(device)   # (the caller's writes to grid, out and depth2 have landed)
+    dv.thickness_dense(grid.data_ptr(), fmt, _strides(grid), dims, 0.0 if level is None else level, flags, cap, out.data_ptr(), _strides(out),
+                       _ptr(depth2), None if depth2 is None else _strides(depth2))
+    return out, depth2
+
+
+def local_thickness(dv, grid, max_radius, *, level=None, background=False, border=True, fmt="r2", depth2=None, out=None):
+    """How thick the set is at every voxel: the largest ball that lies inside the set and holds the voxel,
+    as the squared radius T = max { min(depth2(c), cap) : |p - c|^2 < min(depth2(c), cap) } - exact integers, the same bits on
+    every run.  Returns the tensor [z, y, x], 0 outside the set, or (thickness, depth2) when depth2 is given.
+
+        solid, origin = dense.voxelize_dense(dv, 512, fill=True)
+        t = dense.local_thickness(dv, solid, 8, fmt="thickness")      # float32, in voxels; 15.1 (the cap) means "a ball of radius 8 fits"
+        thin = dense.thin_regions(dv, solid, 5)                       # bool: thinner than 5 voxels
+
+    grid, level, background:  as components takes them: the set is the solid voxels, or with background=True the others.
+    max_radius:  a number >= 0 and below 128, in voxels: the largest ball looked for is {|q| <= max_radius}, cap =
+                 floor(max_radius^2) + 1.  Values at the cap (T == cap) mean "at least": the voxel lies in the opening by that
+                 ball.  The ball stage costs about half the local thickness squared in writes per voxel of the regions thinner
+                 than the cap, so the cap is mandatory: set it to the largest thickness that matters.
+    border:      True: the world outside the box is not in the set, so the box's faces are skin; False: the box is a window
+                 into a larger body and the balls are clipped to it.
+    fmt:         "r2": int32 T; "thickness": float32 2 sqrt(T) - 1, the diameter of that ball in voxels.  A wall w voxels wide
+                 reads w for odd w and w - 1 for even w: a digital ball is centred on a voxel, so its diameter is odd.
+    depth2:      None; True for a new int32 tensor; or an int32 tensor of the voxel shape (any strides): the squared distance
+                 to the nearest voxel that is not in the set (border=True: the outside of the box included), 0 outside the set,
+                 0x7FFFFFFF where there is no such voxel.  Passing it saves the context 4 bytes of scratch per voxel.
+    out:         a tensor of the voxel shape and fmt's dtype (any strides, not in grid's storage), written as it is; else a new
+                 contiguous tensor."""
+    if fmt not in _THICK_FORMATS:
+        raise ValueError(f"fmt must be one of {sorted(_THICK_FORMATS)}, not {fmt!r}")
+    flag, dtype = _THICK_FORMATS[fmt]
+    cap = _radius_cap(max_radius, "max_radius")
+    want_depth2 = depth2 is not None and depth2 is not False
+    out, depth2 = _thickness(dv, grid, cap, level, background, border, flag, dtype, out, depth2)
+    return (out, depth2) if want_depth2 else out
+
+
+def inner_distance(dv, grid, *, level=None, background=False, border=True, out=None):
+    """int32 [z, y, x]: for every voxel of the set the squared distance to the nearest voxel that is not in it - depth2 of
+    local_thickness alone; 0 outside the set, 0x7FFFFFFF where there is no such voxel.  With border=True
+    the world outside the box is not in the set.  distance_transform measures from the surface voxels outwards and inwards; this
+    is the depth of the solid itself.  out: an int32 tensor of the voxel shape (any strides, not in grid's storage)."""
+    _, depth2 = _thickness(dv, grid, 1, level, background, border, hip.THICK_OPEN_ONLY, torch.int32, None, True if out is None else out, depth2_name="out")
+    return depth2
+
+
+def erode(dv, grid, radius, *, level=None, background=False, border=True):
+    """bool [z, y, x]: the erosion of the set by the ball {|q| <= radius}: the voxels whose whole ball lies
+    in the set, depth2 > radius^2.  border=True: the world outside the box is empty, so the set is eroded from the box's faces too."""
+    r2 = _radius_cap(radius) - 1
+    return inner_distance(dv, grid, level=level, background=background, border=border) > r2
+
+
+def opening(dv, grid, radius, *, level=None, background=False, border=True):
+    """bool [z, y, x]: the opening of the set by the ball {|q| <= radius}: the union of the balls of that
+    radius that lie inside the set - what is left when everything thinner is shaved off.  Two distance transforms, no ball stage."""
+    cap = _radius_cap(radius)
+    dst, _ = _thickness(dv, grid, cap, level, background, border, hip.THICK_OPEN_ONLY, torch.int32, None, None)
+    return dst == cap
+
+
+def dilate(dv, grid, radius, *, level=None):
+    """bool [z, y, x]: the dilation of the set by the ball {|q| <= radius}: the complement of the background's erosion.  It works
+    on the background with border=False - the world outside the box is empty space like any other, nothing there pushes back -,
+    and a body cannot grow past the box: pad the grid first if it should."""
+    return ~erode(dv, grid, radius, level=level, background=True, border=False)
+
+
+def closing(dv, grid, radius, *, level=None):
+    """bool [z, y, x]: the closing of the set by the ball {|q| <= radius}: the complement of the background's opening - gaps and
+    holes that no ball of that radius fits into are filled.  Like dilate it works on the background with border=False: a gap
+    between the body and the box's face counts as open to the outside only if a ball clipped to the box fits into it."""
+    return ~opening(dv, grid, radius, level=level, background=True, border=False)
+
+
+def thin_regions(dv, grid, min_thickness, *, level=None, background=False, border=True):
+    """bool [z, y, x]: the voxels of the set where it is thinner than min_thickness voxels: the set less its
+    opening by the ball of radius (min_thickness - 1) / 2, the largest ball whose diameter 2 r + 1 stays within min_thickness.  Two
+    distance transforms and no ball stage, whatever the thickness: the check to run before printing or milling a model."""
+    if isinstance(min_thickness, bool) or not isinstance(min_thickness, numbers.Real) or not float(min_thickness) >= 1.0:
+        raise ValueError(f"min_thickness must be a number >= 1 (voxels), not {min_thickness!r}")
+    cap = _radius_cap((float(min_thickness) - 1.0) / 2.0, "(min_thickness - 1) / 2")
+    dst, _ = _thickness(dv, grid, cap, level, background, border, hip.THICK_OPEN_ONLY, torch.int32, None, None)
+    return (dst > 0) & (dst < cap)
 
 
 # ---- dense grids as voxel lists and voxel files (DESIGN.md section 16) --------------------------------------------------------

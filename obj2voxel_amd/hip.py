@@ -39,6 +39,8 @@ AXIS_X, AXIS_Y, AXIS_Z = 1, 2, 4  # o2v_hip_crossings_dense: the bits of `axes`
 LABELS_I32, LABELS_U8 = 0, 1  # o2v_hip_label_stats formats
 GEO_MAX_WEIGHT, GEO_MAX_DISTANCE = 65535, 2 ** 31 - 2  # o2v_hip_geodesic_dense: the largest weight, the largest (and default) max_distance
 GEO_SCRATCH_CONTIGUOUS, GEO_SCRATCH_STRIDED = 0, 1  # o2v_hip_geodesic_scratch_bytes
+THICK_BACKGROUND, THICK_BORDER, THICK_F32, THICK_OPEN_ONLY = 16, 32, 64, 128  # o2v_hip_thickness_dense flags (with FLAG_STAGE_TIMES: the ball voxels counted)
+THICK_MAX_RADIUS2 = 1 << 14  # ... its largest max_radius2
 STATS_BOX, STATS_SUMS, STATS_MOMENTS, STATS_FACES = 1, 2, 4, 8  # ... the bits of `which`
 STATS_COLUMNS = 17  # ... the int64 columns of a row of its table
 ERR_BAD_ARGUMENT = 3
@@ -196,6 +198,13 @@ def _bind():
     L.o2v_hip_geodesic_scratch_bytes.restype = C.c_uint64
     L.o2v_hip_geodesic_times.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_geodesic_counters.argtypes = [C.c_void_p, C.c_void_p]
+    # ..., flags, max_radius2, dst, dst_strides, depth2, depth2_strides
+    L.o2v_hip_thickness_dense.argtypes = _gather + [C.c_uint32, C.c_uint32] + [C.c_void_p] * 4
+    L.o2v_hip_thickness_scratch_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_int]
+    L.o2v_hip_thickness_scratch_bytes.restype = C.c_uint64
+    L.o2v_hip_thickness_times.argtypes = [C.c_void_p, C.c_void_p]
+    L.o2v_hip_thickness_counters.argtypes = [C.c_void_p, C.c_void_p]
+    L.o2v_hip_thickness_cover_table.argtypes = [C.c_uint32, C.c_void_p]
     L.o2v_hip_max_slab_layers.argtypes = [C.c_void_p, C.POINTER(_Params), C.POINTER(C.c_uint32)]
     return L
 
@@ -260,6 +269,25 @@ def geodesic_scratch_bytes(dims, which=GEO_SCRATCH_CONTIGUOUS):
     """o2v_hip_geodesic_scratch_bytes: the context scratch a geodesic_dense call over dims (x, y, z) takes with a contiguous dist
     (GEO_SCRATCH_CONTIGUOUS) or any other (GEO_SCRATCH_STRIDED)."""
     return int(_bind().o2v_hip_geodesic_scratch_bytes(_u32x3(dims), which))
+
+
+def thickness_scratch_bytes(dims, max_radius2, have_depth2=False):
+    """o2v_hip_thickness_scratch_bytes: the context scratch a thickness_dense call over dims (x, y, z) with that cap takes, with
+    (have_depth2) or without a depth2 grid of the caller's; on top of it 4 bytes per kept ball centre."""
+    return int(_bind().o2v_hip_thickness_scratch_bytes(_u32x3(dims), int(max_radius2), 1 if have_depth2 else 0))
+
+
+def thickness_cover_table(max_radius2):
+    """o2v_hip_thickness_cover_table: uint32 [3, max_radius2 + 1], row k - 1 the smallest radius^2 L_k[R] at which the discrete
+    ball {|q|^2 < L} of a neighbour at (1, 0, 0), (1, 1, 0), (1, 1, 1) (k = 1, 2, 3) contains the ball of radius^2 R; column 0 is
+    0.  Needs no device."""
+    if isinstance(max_radius2, bool) or not isinstance(max_radius2, int) or not 1 <= max_radius2 <= THICK_MAX_RADIUS2:
+        raise ValueError(f"max_radius2 must be an int 1 ... {THICK_MAX_RADIUS2}, not {max_radius2!r}")
+    out = np.zeros((3, max_radius2 + 1), np.uint32)
+    rc = _bind().o2v_hip_thickness_cover_table(max_radius2, _ptr(out))
+    if rc != 0:
+        raise DeviceError("o2v_hip_thickness_cover_table failed (code %d)" % rc)
+    return out
 
 
 def gather_scratch_bytes(dims):
@@ -661,6 +689,32 @@ class DeviceVoxelizer:
         geodesic_dense call made with FLAG_STAGE_TIMES (else zeros)."""
         out = (C.c_uint64 * 4)()
         self._check(self._L.o2v_hip_geodesic_counters(self._ctx, out), "o2v_hip_geodesic_counters")
+        return tuple(int(v) for v in out)
+
+    def thickness_dense(self, grid_ptr, fmt, strides, dims, level, flags, max_radius2, dst_ptr, dst_strides, depth2_ptr=None, depth2_strides=None):
+        """o2v_hip_thickness_dense: the local thickness of the set of the grid at device pointer grid_ptr (dims, strides, fmt and
+        level as components_dense takes them; THICK_BACKGROUND: its complement) as squared radii: int32 T = the largest
+        min(depth2, max_radius2) over the inscribed balls that hold the voxel, 0 outside the set, into dst_ptr (THICK_F32: float32
+        2 sqrt(T) - 1; THICK_OPEN_ONLY: max_radius2 inside the opening, min(depth2, max_radius2) elsewhere); if depth2_ptr is given
+        the squared distance to the nearest voxel that is not in the set (THICK_BORDER: the outside of the box included) into
+        int32 there.  Strides in elements per axis x, y, z."""
+        self._check(self._L.o2v_hip_thickness_dense(self._ctx, grid_ptr, fmt, _u64x3(strides), _u32x3(dims), float(level), flags, max_radius2, dst_ptr,
+                                                    _u64x3(dst_strides), depth2_ptr, _u64x3(depth2_strides)), "o2v_hip_thickness_dense")
+
+    def thickness_scratch_bytes(self, dims, max_radius2, have_depth2=False):
+        """o2v_hip_thickness_scratch_bytes: the context scratch a thickness_dense call over dims (x, y, z) takes."""
+        return thickness_scratch_bytes(dims, max_radius2, have_depth2)
+
+    def thickness_times(self):
+        """o2v_hip_thickness_times: the device times (ms) of the last thickness_dense call's depth, opening, list, ball and
+        conversion stages."""
+        return self._stage_times("o2v_hip_thickness_times", 5)
+
+    def thickness_counters(self):
+        """o2v_hip_thickness_counters: (candidate centres, centres kept, ball voxels visited) of the last thickness_dense call;
+        the last only with FLAG_STAGE_TIMES (else 0)."""
+        out = (C.c_uint64 * 3)()
+        self._check(self._L.o2v_hip_thickness_counters(self._ctx, out), "o2v_hip_thickness_counters")
         return tuple(int(v) for v in out)
 
     def nearest_scratch_bytes(self, dims):

@@ -1,5 +1,6 @@
 // Host side of K21 (o2v_dev_k21_thickness.hpp): local thickness and ball morphology.  It runs K8's envelope passes on its own
-// grids, so it comes after o2v_dev_host_k8_distance.hpp (dist_passes, dist2_limit, o2v_hip_distance_scratch_bytes).
+// grids, so it comes after o2v_dev_host_k8_distance.hpp (dist_passes, dist_envelopes_yz, with_seed_format, the two limits,
+// o2v_hip_distance_scratch_bytes).
 
 namespace {
 
@@ -85,17 +86,12 @@ int o2v_hip_thickness_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format,
     if (flags & ~kThickFlagsKnown) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown flag bits in " + std::to_string(flags));
     if (max_radius2 == 0u) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "max_radius2 must be at least 1");
     if (max_radius2 > kThickMaxCap) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "max_radius2 " + std::to_string(max_radius2) + " is above 2^14");
-    const unsigned __int128 voxels128 = (unsigned __int128) dims[0] * dims[1] * dims[2];
-    if (voxels128 > kMaxInt32)
-        return refuse(ctx, O2V_HIP_ERR_LIMIT, fn,
-                      std::to_string(dims[0]) + " x " + std::to_string(dims[1]) + " x " + std::to_string(dims[2]) +
-                          " voxels do not fit an int32 index (at most 2^31 - 1)");
-    if ((rc = dist2_limit(ctx, fn, dims))) return rc;
+    if ((rc = voxel_index_limit(ctx, fn, dims)) || (rc = dist2_limit(ctx, fn, dims))) return rc;
     const OutGrid outs[] = {{"dst", dst, dst_strides, 4u}, {"depth2", depth2, depth2_strides, 4u}};
     Span spans[3] = {{}, {}, {"grid", grid, sg.bytes}};
     if ((rc = check_outputs(ctx, fn, outs, dims, spans)) || (rc = refuse_overlap(ctx, fn, spans, 2))) return rc;
 
-    const uint64_t voxels = (uint64_t) voxels128, n_blocks = thick_blocks(dims);
+    const uint64_t voxels = (uint64_t) dims[0] * dims[1] * dims[2], n_blocks = thick_blocks(dims);
     const bool open_only = (flags & kThickOpenOnly) != 0, count = (flags & O2V_HIP_FLAG_STAGE_TIMES) != 0;
     if ((rc = grow_scratch(ctx, ctx->d_dist_stack, o2v_hip_distance_scratch_bytes(dims, O2V_HIP_DIST_SQ_I32) / sizeof(uint2), fn, "scratch")) ||
         (!depth2 && (rc = grow_scratch(ctx, ctx->d_thick_depth, voxels, fn, "depth grid"))) ||
@@ -104,7 +100,7 @@ int o2v_hip_thickness_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format,
         return rc;
 
     ThickGrid g{};
-    g.src = grid, g.l0 = strides[0], g.l1 = strides[1], g.l2 = strides[2], g.level = level;
+    g.src = sg.source();
     g.invert = (flags & kThickBackground) ? 1u : 0u, g.border = (flags & kThickBorder) ? 1u : 0u, g.cap = max_radius2;
     if (depth2) g.e0 = depth2_strides[0], g.e1 = depth2_strides[1], g.e2 = depth2_strides[2];
     else g.e0 = 1u, g.e1 = dims[0], g.e2 = (uint64_t) dims[0] * dims[1];
@@ -112,10 +108,7 @@ int o2v_hip_thickness_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format,
     g.nx = dims[0], g.ny = dims[1], g.nz = dims[2];
     int32_t *const depth = depth2 ? depth2 : ctx->d_thick_depth.ptr;
     int32_t *const out = static_cast<int32_t *>(dst);
-    // K8's envelope passes take their grid as the destination of a DistGrid; they read no labels (kDistY, kDistZ)
-    const DistGrid on_depth{0, 0, 0, g.e0, g.e1, g.e2, g.nx, g.ny, g.nz}, on_dst{0, 0, 0, g.d0, g.d1, g.d2, g.nx, g.ny, g.nz};
-    const uint8_t *const no_labels = nullptr;
-    uint2 *const stack = ctx->d_dist_stack.ptr;
+    const DtGrid on_depth{g.e0, g.e1, g.e2, g.nx, g.ny, g.nz}, on_dst{g.d0, g.d1, g.d2, g.nx, g.ny, g.nz};
     unsigned long long *const boff = ctx->d_thick_boff.ptr, *const ctr = ctx->d_thick_ctr.ptr;
     const uint32_t *const table = ctx->d_thick_table.ptr;
     const DistPasses p = dist_passes(ctx, dims);
@@ -124,16 +117,14 @@ int o2v_hip_thickness_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format,
 
     // 1. depth2: the squared distance to the nearest voxel of the box that is not in S
     O2V_CHECK(ctx->thick_times.mark(0, s));
-    if (format == O2V_HIP_GRID_BITS) O2V_LAUNCH("k_thick_depth_x", s, k_thick_depth_x<kNearBits>, p.gx, dim3(kBlock), 0, s, depth, g);
-    else if (format == O2V_HIP_GRID_F32_BELOW) O2V_LAUNCH("k_thick_depth_x", s, k_thick_depth_x<kNearF32Below>, p.gx, dim3(kBlock), 0, s, depth, g);
-    else O2V_LAUNCH("k_thick_depth_x", s, k_thick_depth_x<kNearU8>, p.gx, dim3(kBlock), 0, s, depth, g);
-    O2V_LAUNCH("k_dist_envelope", s, k_dist_envelope<kDistY>, p.gy, dim3(kBlock), 0, s, depth, no_labels, on_depth, stack, p.sy);
-    O2V_LAUNCH("k_dist_envelope", s, k_dist_envelope<kDistZ>, p.gz, dim3(kBlock), 0, s, depth, no_labels, on_depth, stack, p.sz);
+    with_seed_format(format, [&](auto fmt) {
+        O2V_LAUNCH("k_thick_depth_x", s, k_thick_depth_x<decltype(fmt)::value>, p.gx, dim3(kBlock), 0, s, depth, g);
+    });
+    dist_envelopes_yz(ctx, depth, on_depth, p);
     // 2. the core M = {depth2' >= cap} and the squared distance to it
     O2V_CHECK(ctx->thick_times.mark(1, s));
     O2V_LAUNCH("k_thick_core_x", s, k_thick_core_x, p.gx, dim3(kBlock), 0, s, depth, out, g);
-    O2V_LAUNCH("k_dist_envelope", s, k_dist_envelope<kDistY>, p.gy, dim3(kBlock), 0, s, out, no_labels, on_dst, stack, p.sy);
-    O2V_LAUNCH("k_dist_envelope", s, k_dist_envelope<kDistZ>, p.gz, dim3(kBlock), 0, s, out, no_labels, on_dst, stack, p.sz);
+    dist_envelopes_yz(ctx, out, on_dst, p);
     // 3. dst initialised; the kept centres counted and listed
     O2V_CHECK(ctx->thick_times.mark(2, s));
     O2V_CHECK(hipMemsetAsync(ctr, 0, 4u * sizeof(unsigned long long), s));

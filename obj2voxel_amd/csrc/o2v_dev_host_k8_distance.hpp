@@ -38,6 +38,34 @@ int dist2_limit(o2v_hip_ctx *ctx, const char *fn, const uint32_t dims[3])
     return O2V_HIP_OK;
 }
 
+// A linear index of the grid's voxels is one int32 (K15's nearest, K21's centre list).
+int voxel_index_limit(o2v_hip_ctx *ctx, const char *fn, const uint32_t dims[3])
+{
+    if ((unsigned __int128) dims[0] * dims[1] * dims[2] > kMaxInt32)
+        return refuse(ctx, O2V_HIP_ERR_LIMIT, fn,
+                      std::to_string(dims[0]) + " x " + std::to_string(dims[1]) + " x " + std::to_string(dims[2]) +
+                          " voxels do not fit an int32 index (at most 2^31 - 1)");
+    return O2V_HIP_OK;
+}
+
+// f(format) with a set grid's format as the template argument <Format> of dt_seed, an integral constant.
+template <typename F>
+void with_seed_format(uint32_t format, F &&f)
+{
+    if (format == O2V_HIP_GRID_BITS) return f(std::integral_constant<uint32_t, kRayBits>{});
+    if (format == O2V_HIP_GRID_F32_BELOW) return f(std::integral_constant<uint32_t, kRayF32Below>{});
+    return f(std::integral_constant<uint32_t, kRayU8>{});
+}
+
+// The envelope along y, then along z, over the int32 grid `grid` in place (K21's depth and core stages).
+void dist_envelopes_yz(o2v_hip_ctx *ctx, int32_t *grid, const DtGrid &g, const DistPasses &p)
+{
+    hipStream_t s = ctx->stream;
+    uint2 *const stack = ctx->d_dist_stack.ptr;
+    O2V_LAUNCH("k_dist_envelope", s, k_dist_envelope<kDistY>, p.gy, dim3(kBlock), 0, s, grid, g, RaySource{}, stack, p.sy);
+    O2V_LAUNCH("k_dist_envelope", s, k_dist_envelope<kDistZ>, p.gz, dim3(kBlock), 0, s, grid, g, RaySource{}, stack, p.sz);
+}
+
 }  // namespace
 
 extern "C" {
@@ -70,21 +98,20 @@ int o2v_hip_distance_dense(o2v_hip_ctx *ctx, const void *labels, const uint64_t 
     if ((rc = grow_scratch(ctx, ctx->d_dist_stack, o2v_hip_distance_scratch_bytes(dims, format) / sizeof(uint2), fn, "scratch")))
         return rc;
     hipStream_t s = ctx->stream;
-    const DistGrid g{label_strides[0], label_strides[1], label_strides[2], dst_strides[0], dst_strides[1], dst_strides[2],
-                     dims[0], dims[1], dims[2]};
-    const uint8_t *const lab = static_cast<const uint8_t *>(labels);
+    const DtGrid g{dst_strides[0], dst_strides[1], dst_strides[2], dims[0], dims[1], dims[2]};
+    const RaySource lab = ray_source(labels, label_strides, 0.f);
     int32_t *const out = static_cast<int32_t *>(dst);
     uint2 *const stack = ctx->d_dist_stack.ptr;
     const DistPasses p = dist_passes(ctx, dims);
     O2V_CHECK(ctx->dist_times.mark(0, s));
     O2V_LAUNCH("k_dist_x", s, k_dist_x, p.gx, dim3(kBlock), 0, s, lab, out, g);
     O2V_CHECK(ctx->dist_times.mark(1, s));
-    O2V_LAUNCH("k_dist_envelope", s, k_dist_envelope<kDistY>, p.gy, dim3(kBlock), 0, s, out, lab, g, stack, p.sy);
+    O2V_LAUNCH("k_dist_envelope", s, k_dist_envelope<kDistY>, p.gy, dim3(kBlock), 0, s, out, g, lab, stack, p.sy);
     O2V_CHECK(ctx->dist_times.mark(2, s));
     if (format == O2V_HIP_DIST_SQ_I32)
-        O2V_LAUNCH("k_dist_envelope", s, k_dist_envelope<kDistZ>, p.gz, dim3(kBlock), 0, s, out, lab, g, stack, p.sz);
+        O2V_LAUNCH("k_dist_envelope", s, k_dist_envelope<kDistZ>, p.gz, dim3(kBlock), 0, s, out, g, lab, stack, p.sz);
     else
-        O2V_LAUNCH("k_dist_envelope", s, k_dist_envelope<kDistZSdf>, p.gz, dim3(kBlock), 0, s, out, lab, g, stack, p.sz);
+        O2V_LAUNCH("k_dist_envelope", s, k_dist_envelope<kDistZSdf>, p.gz, dim3(kBlock), 0, s, out, g, lab, stack, p.sz);
     O2V_CHECK(hipGetLastError());
     return finish_stages(ctx, ctx->dist_times);
 }
@@ -117,12 +144,7 @@ int o2v_hip_nearest_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format, c
     int rc;
     if ((rc = set_grid_args(ctx, fn, grid, format, strides, dims, level, &sg))) return rc;
     if (flags & ~kNearFlagsKnown) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown flag bits in " + std::to_string(flags));
-    const unsigned __int128 voxels = (unsigned __int128) dims[0] * dims[1] * dims[2];
-    if (voxels > 0x7fffffffull)
-        return refuse(ctx, O2V_HIP_ERR_LIMIT, fn,
-                      std::to_string(dims[0]) + " x " + std::to_string(dims[1]) + " x " + std::to_string(dims[2]) +
-                          " voxels do not fit an int32 index (at most 2^31 - 1)");
-    if ((rc = dist2_limit(ctx, fn, dims))) return rc;
+    if ((rc = voxel_index_limit(ctx, fn, dims)) || (rc = dist2_limit(ctx, fn, dims))) return rc;
     if (format != O2V_HIP_GRID_U8 && flags)
         return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "SEED_ONE and VALUES_INSIDE need a U8 grid");
     // (the size limits stand before the look at the grid's memory: a box that is too large is refused as that, whatever it reaches)
@@ -132,8 +154,7 @@ int o2v_hip_nearest_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format, c
     if ((rc = check_outputs(ctx, fn, outs, dims, spans)) || (rc = refuse_overlap(ctx, fn, spans, 3))) return rc;
     if ((rc = grow_scratch(ctx, ctx->d_dist_stack, o2v_hip_nearest_scratch_bytes(dims) / sizeof(uint2), fn, "scratch"))) return rc;
     hipStream_t s = ctx->stream;
-    const NearGrid g{grid, strides[0], strides[1], strides[2], level, nearest_strides[0], nearest_strides[1], nearest_strides[2],
-                     dims[0], dims[1], dims[2]};
+    const NearGrid g{sg.source(), {nearest_strides[0], nearest_strides[1], nearest_strides[2], dims[0], dims[1], dims[2]}};
     NearOut o{};
     if (dist2) o.dist2 = dist2, o.e0 = dist2_strides[0], o.e1 = dist2_strides[1], o.e2 = dist2_strides[2];
     if (values) o.values = values, o.v0 = value_strides[0], o.v1 = value_strides[1], o.v2 = value_strides[2];
@@ -141,14 +162,9 @@ int o2v_hip_nearest_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format, c
     uint2 *const stack = ctx->d_dist_stack.ptr;
     const DistPasses p = dist_passes(ctx, dims);
     O2V_CHECK(ctx->near_times.mark(0, s));
-    if (format == O2V_HIP_GRID_BITS)
-        O2V_LAUNCH("k_near_x", s, k_near_x<kNearBits>, p.gx, dim3(kBlock), 0, s, nearest, g);
-    else if (format == O2V_HIP_GRID_F32_BELOW)
-        O2V_LAUNCH("k_near_x", s, k_near_x<kNearF32Below>, p.gx, dim3(kBlock), 0, s, nearest, g);
-    else if (flags & O2V_HIP_NEAREST_SEED_ONE)
-        O2V_LAUNCH("k_near_x", s, k_near_x<kNearU8One>, p.gx, dim3(kBlock), 0, s, nearest, g);
-    else
-        O2V_LAUNCH("k_near_x", s, k_near_x<kNearU8>, p.gx, dim3(kBlock), 0, s, nearest, g);
+    const auto scan_x = [&](auto fmt) { O2V_LAUNCH("k_near_x", s, k_near_x<decltype(fmt)::value>, p.gx, dim3(kBlock), 0, s, nearest, g); };
+    if (flags & O2V_HIP_NEAREST_SEED_ONE) scan_x(std::integral_constant<uint32_t, kSeedU8One>{});   // (a U8 grid: checked above)
+    else with_seed_format(format, scan_x);
     O2V_CHECK(ctx->near_times.mark(1, s));
     O2V_LAUNCH("k_near_envelope", s, (k_near_envelope<kNearY, kNearNoPaint>), p.gy, dim3(kBlock), 0, s, nearest, g, o, stack, p.sy);
     O2V_CHECK(ctx->near_times.mark(2, s));

@@ -1,15 +1,14 @@
 // o2v_dev_k21_thickness.hpp -- K21: local thickness and ball morphology of a dense grid (o2v_hip_thickness_dense).
-// Included from o2v_device.hip inside its anonymous namespace, after K6 (the block scans), K8 (the envelope passes) and K15 (the
-// per-format seed tests); none of the pipeline's kernels use it.
+// Included from o2v_device.hip inside its anonymous namespace, after K6 (the block scans) and K8 (the seed tests, the row scan
+// and the envelope passes); none of the pipeline's kernels use it.
 //
 // T(p) = max { R(c) : c in S, |p - c|^2 < R(c) } with R(c) = min(depth2(c), cap): the largest (capped) inscribed ball that holds
 // the voxel (include/o2v_hip.h).  Exact integers; the same bits on every run.
-//   k_thick_depth_x<Format>  per row along x: the squared distance to the nearest voxel of the row that is NOT in S, k_dist_x's
-//                            ballot scheme with K15's seed tests negated (plain with BACKGROUND).  K8's k_dist_envelope<kDistY>
-//                            and <kDistZ> follow unchanged: depth2.
-//   k_thick_core_x           per row along x of the depth grid: the border's min applied and written back (depth2'), then the
-//                            same ballot scheme with M = {depth2' >= cap} as seeds, g^2 into dst.  The two envelope passes on
-//                            dst give the squared distance to M: a voxel of S is in the opening where that is below cap.
+//   k_thick_depth_x<Format>  dt_scan_row with the per-format seed test negated (plain with BACKGROUND): g^2 to the nearest voxel of
+//                            the row that is NOT in S.  K8's k_dist_envelope<kDistY> and <kDistZ> on the depth grid follow: depth2.
+//   k_thick_core_x           dt_scan_row on the depth grid with M = {depth2' >= cap} as seeds, g^2 into dst; the seed test
+//                            applies the border's min and writes depth2' back.  The two envelope passes on dst give the
+//                            squared distance to M: a voxel of S is in the opening where that is below cap.
 //   k_thick_init<List>       per voxel: dst = 0 outside S, cap inside the opening, R(p) elsewhere.  List: a voxel of S with
 //                            depth2' < cap is a ball centre unless a 26-neighbour's ball covers its own (thick_keep); the kept
 //                            centres of a block of kBlock voxels are counted (k_fill_scan_blocks turns the counts into offsets).
@@ -23,11 +22,9 @@
 constexpr uint32_t kThickMaxCap = 1u << 14;   // the largest max_radius2: a ball of 255 voxels across
 constexpr uint32_t kThickBackground = 16u, kThickBorder = 32u, kThickF32 = 64u, kThickOpenOnly = 128u;   // O2V_HIP_THICK_*
 
-// The set grid, the depth grid and dst: strides in elements (words for BITS), per axis x, y, z.
+// The set grid (strides in words for BITS), the depth grid and dst: strides in elements, per axis x, y, z.
 struct ThickGrid {
-    const void *src;
-    uint64_t l0, l1, l2;
-    float level;
+    RaySource src;
     uint32_t invert;        // BACKGROUND: S is the complement
     uint32_t border;        // BORDER: the voxels outside the box are not in S
     uint32_t cap;
@@ -35,11 +32,6 @@ struct ThickGrid {
     uint64_t d0, d1, d2;    // dst
     uint32_t nx, ny, nz;
 };
-
-__device__ __forceinline__ NearGrid thick_source(const ThickGrid &g)
-{
-    return NearGrid{g.src, g.l0, g.l1, g.l2, g.level, 0, 0, 0, g.nx, g.ny, g.nz};
-}
 
 // depth2' of a voxel of depth2 d: the min with the squared distances to the nearest voxel outside the box along the axes
 __device__ __forceinline__ uint32_t thick_border(const ThickGrid &g, uint32_t x, uint32_t y, uint32_t z, uint32_t d)
@@ -49,51 +41,17 @@ __device__ __forceinline__ uint32_t thick_border(const ThickGrid &g, uint32_t x,
     return min(d, m * m);
 }
 
-// One chunk of 64 positions of a row in k_dist_x's scheme: m the seeds of the chunk, left the last seed of the chunks before,
-// ahead the first seed behind the chunk (kDistNone: none) -> g^2 at x = x0 + lane, kDistInf without a seed in the row.
-__device__ __forceinline__ int32_t thick_row_d2(unsigned long long m, uint32_t x0, uint32_t lane, uint32_t left, uint32_t ahead)
-{
-    const unsigned long long upto = lane == 63u ? ~0ull : (2ull << lane) - 1ull;   // bits 0 .. lane
-    const unsigned long long ml = m & upto, mr = m >> lane;
-    const uint32_t x = x0 + lane;
-    const uint32_t l = ml ? x0 + 63u - (uint32_t) __builtin_clzll(ml) : left;
-    const uint32_t r = mr ? x + (uint32_t) __builtin_ctzll(mr) : ahead;
-    uint32_t d = kDistNone;
-    if (l != kDistNone) d = x - l;
-    if (r != kDistNone) d = min(d, r - x);
-    return d == kDistNone ? kDistInf : (int32_t) (d * d);
-}
-
 template <uint32_t Format>
 __global__ __launch_bounds__(kBlock) void k_thick_depth_x(int32_t *__restrict__ depth, ThickGrid g)
 {
-    const NearGrid src = thick_source(g);
     const bool in_set = g.invert == 0u;   // a voxel is in S where its seed test gives this
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t waves = (uint64_t) gridDim.x * (kBlock / 64u);
     const uint64_t rows = (uint64_t) g.ny * g.nz;
-    for (uint64_t row = (uint64_t) blockIdx.x * (kBlock / 64u) + (threadIdx.x >> 6); row < rows; row += waves) {
+    for (uint64_t row = dt_first_row(); row < rows; row += dt_row_stride()) {
         const uint64_t y = row % g.ny, z = row / g.ny;
-        const uint64_t lrow = y * g.l1 + z * g.l2;
+        const uint64_t lrow = y * g.src.s1 + z * g.src.s2;
         int32_t *drow = depth + y * g.e1 + z * g.e2;
-        uint32_t left = kDistNone;   // the last voxel outside S of the chunks before
-        uint32_t ahead = 0;          // the first one at or after the next chunk when >= x0 + 64 (kDistNone: none to the end)
-        for (uint32_t x0 = 0; x0 < g.nx; x0 += 64u) {
-            const uint32_t x = x0 + lane;
-            const unsigned long long m = __ballot(x < g.nx && near_seed<Format>(src, lrow, x) != in_set);
-            if (ahead < x0 + 64u) {   // (wave-uniform) look ahead for the first one behind this chunk
-                ahead = kDistNone;
-                for (uint32_t c = x0 + 64u; c < g.nx; c += 64u) {
-                    const unsigned long long mc = __ballot(c + lane < g.nx && near_seed<Format>(src, lrow, c + lane) != in_set);
-                    if (mc) {
-                        ahead = c + (uint32_t) __builtin_ctzll(mc);
-                        break;
-                    }
-                }
-            }
-            if (x < g.nx) drow[(uint64_t) x * g.e0] = thick_row_d2(m, x0, lane, left, ahead);
-            if (m) left = x0 + 63u - (uint32_t) __builtin_clzll(m);
-        }
+        dt_scan_row(g.nx, lane, [&](uint32_t x, bool) { return dt_seed<Format>(g.src, lrow, x) != in_set; }, dt_row_d2, drow, g.e0);
     }
 }
 
@@ -102,35 +60,19 @@ __global__ __launch_bounds__(kBlock) void k_thick_depth_x(int32_t *__restrict__ 
 __global__ __launch_bounds__(kBlock) void k_thick_core_x(int32_t *__restrict__ depth, int32_t *__restrict__ dst, ThickGrid g)
 {
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t waves = (uint64_t) gridDim.x * (kBlock / 64u);
     const uint64_t rows = (uint64_t) g.ny * g.nz;
-    for (uint64_t row = (uint64_t) blockIdx.x * (kBlock / 64u) + (threadIdx.x >> 6); row < rows; row += waves) {
+    for (uint64_t row = dt_first_row(); row < rows; row += dt_row_stride()) {
         const uint32_t y = (uint32_t) (row % g.ny), z = (uint32_t) (row / g.ny);
         int32_t *erow = depth + (uint64_t) y * g.e1 + (uint64_t) z * g.e2;
         int32_t *drow = dst + (uint64_t) y * g.d1 + (uint64_t) z * g.d2;
-        uint32_t left = kDistNone, ahead = 0;
-        for (uint32_t x0 = 0; x0 < g.nx; x0 += 64u) {
-            const uint32_t x = x0 + lane;
-            uint32_t r = 0;
-            if (x < g.nx) {
-                r = thick_border(g, x, y, z, (uint32_t) erow[(uint64_t) x * g.e0]);
-                erow[(uint64_t) x * g.e0] = (int32_t) r;
-            }
-            const unsigned long long m = __ballot(r >= g.cap);   // (cap >= 1: a lane past the row, r = 0, is no seed)
-            if (ahead < x0 + 64u) {
-                ahead = kDistNone;
-                for (uint32_t c = x0 + 64u; c < g.nx; c += 64u) {
-                    const uint32_t xc = c + lane;
-                    const unsigned long long mc = __ballot(xc < g.nx && thick_border(g, xc, y, z, (uint32_t) erow[(uint64_t) xc * g.e0]) >= g.cap);
-                    if (mc) {
-                        ahead = c + (uint32_t) __builtin_ctzll(mc);
-                        break;
-                    }
-                }
-            }
-            if (x < g.nx) drow[(uint64_t) x * g.d0] = thick_row_d2(m, x0, lane, left, ahead);
-            if (m) left = x0 + 63u - (uint32_t) __builtin_clzll(m);
-        }
+        dt_scan_row(
+            g.nx, lane,
+            [&](uint32_t x, bool ahead) {
+                const uint32_t r = thick_border(g, x, y, z, (uint32_t) erow[(uint64_t) x * g.e0]);
+                if (!ahead) erow[(uint64_t) x * g.e0] = (int32_t) r;
+                return r >= g.cap;
+            },
+            dt_row_d2, drow, g.d0);
     }
 }
 

@@ -25,7 +25,8 @@
 //   K6  k_fill_*               O2V_HIP_FLAG_FILL_INTERIOR: parity crossings per column of the pass box, prefix XOR along z,
 //                              the surface cells removed, interior records appended behind the surface records
 //   K7  k_gather_tris, k_dense_* device-resident input (positions + faces) and dense output grids; outside the pipeline
-//   K8  k_dist_*               o2v_hip_distance_dense: exact squared distance / SDF of a label grid; outside the pipeline
+//   K8  k_dist_*               o2v_hip_distance_dense: exact squared distance / SDF of a label grid; its header holds the row
+//                              scan and the envelope that K15 and K21 run too (dt_*); outside the pipeline
 //   K9  k_meshdist_*           o2v_hip_mesh_distance_dense: narrow-band distance to the triangles, signed by K6's parity set;
 //                              outside the pipeline
 //   K10 k_surf_*               o2v_hip_surface_count / _write: the level set of a float32 grid as an indexed mesh (surface
@@ -96,10 +97,10 @@ namespace {
 #include "o2v_dev_k3_resolve.hpp"
 #include "o2v_dev_k6_fill.hpp"
 #include "o2v_dev_k7_dense.hpp"
-#include "o2v_dev_k8_distance.hpp"
 #include "o2v_dev_k9_mesh_distance.hpp"
 #include "o2v_dev_k10_surface.hpp"
 #include "o2v_dev_k11_raycast.hpp"
+#include "o2v_dev_k8_distance.hpp"   // (behind K11: its seed test reads a set grid, K11's RaySource and kRay* formats)
 #include "o2v_dev_k12_components.hpp"
 #include "o2v_dev_k13_gather.hpp"
 #include "o2v_dev_k14_faces.hpp"

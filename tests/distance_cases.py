@@ -64,7 +64,9 @@ def case_random():
     lab[:, :, 199] = 1     # one seed per row, at its far end: the look-ahead crosses every chunk
     lab[3, 5, 0] = 1
     check(dv, lab, what="far seeds")
-    print("compared", n + 4)
+    lab = np.where(R.scan_rows(), 1, np.where(rng.random((3, 2, 193)) < 0.3, 2, 0)).astype(np.uint8)
+    check(dv, lab, what="scan rows")
+    print("compared", n + 5)
 
 
 def case_strided():

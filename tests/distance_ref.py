@@ -147,6 +147,16 @@ def sdf(labels, d2):
     return np.where(np.asarray(labels) == 2, -r, r)
 
 
+def scan_rows():
+    """Seeds, bool [3, 2, 193]: the smallest box whose rows put the row scan's left carry, a look-ahead across more than one
+    empty chunk and a last chunk one lane wide (four chunks of 64) into one row.  Its six rows: no seed; only x = 0; only
+    x = 192; only x = 63 and 64, either side of a chunk's edge; every voxel; x = 5 and 133, equally far from x = 69."""
+    seed = np.zeros((6, 193), bool)
+    seed[1, 0] = seed[2, 192] = seed[3, 63] = seed[3, 64] = seed[5, 5] = seed[5, 133] = True
+    seed[4] = True
+    return seed.reshape(3, 2, 193)
+
+
 def random_labels(rng, shape, density, interior=0.3):
     """Labels with surface voxels at `density` and interior (2) labels at random elsewhere."""
     u = rng.random(shape)

@@ -107,37 +107,41 @@ def pack_bits(seed):
 def case_formats():
     dv = hip.DeviceVoxelizer(0)
     rng = np.random.default_rng(16)
-    shape = nz, ny, nx = (7, 9, 70)     # nx a multiple of neither 32 nor 64: the last word of a row is part empty
-    for density in (0.004, 0.1):
-        seed = rng.random(shape) < density
+    shape = (7, 9, 70)     # nx a multiple of neither 32 nor 64: the last word of a row is part empty
+    shapes = []
+    for density in (0.004, 0.1, None):
+        seed = R.scan_rows() if density is None else rng.random(shape) < density
+        shapes.append(seed.shape)
+        nz, ny, nx = seed.shape
+        words = (nx + 31) // 32
         assert seed.any()
         want = N.separable_nearest(seed)
         check(dv, seed, want, "bool")
-        labels = np.where(seed, 1, np.where(rng.random(shape) < 0.4, 2, 0)).astype(np.uint8)
+        labels = np.where(seed, 1, np.where(rng.random(seed.shape) < 0.4, 2, 0)).astype(np.uint8)
         assert (labels == 2).any()
         check(dv, labels, want, "labels, surface_only", surface_only=True)
         check(dv, labels, None, "labels, every non-zero voxel a seed")
         level = 0.25
-        field = np.where(seed, level - rng.random(shape) - 1e-3, level + rng.random(shape)).astype(np.float32)
-        field[~seed & (rng.random(shape) < 0.2)] = level           # (at the level: not below it)
+        field = np.where(seed, level - rng.random(seed.shape) - 1e-3, level + rng.random(seed.shape)).astype(np.float32)
+        field[~seed & (rng.random(seed.shape) < 0.2)] = level           # (at the level: not below it)
         near, d2 = dense.nearest_voxel(dv, dev(field), level=level, dist2=True)
         assert np.array_equal(host(near), want[0]) and np.array_equal(host(d2), want[1]), "float32 with a level"
-        # bits at the C level: dims of 70 voxels over rows of 3 words
+        # bits at the C level: dims of nx voxels over rows of whole words (70 voxels: 3 words)
         bits = dev(pack_bits(seed))
-        assert tuple(bits.shape) == (nz, ny, 3)
-        near = torch.full(shape, -5, dtype=torch.int32, device=DEV)
-        d2 = torch.full(shape, -5, dtype=torch.int32, device=DEV)
+        assert tuple(bits.shape) == (nz, ny, words)
+        near = torch.full(seed.shape, -5, dtype=torch.int32, device=DEV)
+        d2 = torch.full(seed.shape, -5, dtype=torch.int32, device=DEV)
         torch.cuda.synchronize()
-        dv.nearest_dense(bits.data_ptr(), hip.GRID_BITS, (1, 3, 3 * ny), (nx, ny, nz), 0.0, 0, near.data_ptr(), (1, nx, nx * ny),
+        dv.nearest_dense(bits.data_ptr(), hip.GRID_BITS, (1, words, words * ny), (nx, ny, nz), 0.0, 0, near.data_ptr(), (1, nx, nx * ny),
                          d2.data_ptr(), (1, nx, nx * ny))
-        assert np.array_equal(host(near), want[0]) and np.array_equal(host(d2), want[1]), "bits, 70 voxels"
-        # ... and through dense: 32 voxels per word, the box 96 wide and its last 26 columns without seeds
-        padded = np.zeros((nz, ny, 96), bool)
+        assert np.array_equal(host(near), want[0]) and np.array_equal(host(d2), want[1]), ("bits", nx, "voxels")
+        # ... and through dense: 32 voxels per word, the box as wide as its words (70 voxels: 96) and its last columns without seeds
+        padded = np.zeros((nz, ny, 32 * words), bool)
         padded[:, :, :nx] = seed
-        want96 = N.separable_nearest(padded)
+        want_padded = N.separable_nearest(padded)
         near, d2 = dense.nearest_voxel(dv, bits, dist2=True)
-        assert tuple(near.shape) == (nz, ny, 96) and np.array_equal(host(near), want96[0]) and np.array_equal(host(d2), want96[1]), "bits, 96 voxels"
-    print("formats", shape, "bool, labels, float32, bits at 70 and 96 voxels")
+        assert tuple(near.shape) == padded.shape and np.array_equal(host(near), want_padded[0]) and np.array_equal(host(d2), want_padded[1]), ("bits", 32 * words, "voxels")
+    print("formats", shapes, "bool, labels, float32, bits at nx voxels and at whole words")
 
 
 def case_strided():

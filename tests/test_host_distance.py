@@ -181,7 +181,8 @@ def test_existing_formats_do_not_run_the_transform():
     assert "distance" not in [c[0] for c in dv.calls]
 
 
-@pytest.mark.parametrize("kernel", ["k_dist_x", "k_dist_envelopeILj0E", "k_dist_envelopeILj1E", "k_dist_envelopeILj2E"])
+@pytest.mark.parametrize("kernel", ["k_dist_x", "k_dist_envelopeILj0E", "k_dist_envelopeILj1E", "k_dist_envelopeILj2E", "k_near_x", "k_near_envelope",
+                                    "k_thick_depth_x", "k_thick_core_x"])
 def test_k8_kernels_in_the_code_object_without_scratch(device_asm, kernel):  # noqa: F811
     import re
     m = re.search(r"^(_ZN\S*" + kernel + r"\S*):[^\n]*\n(.*?)^\.Lfunc_end", device_asm, re.M | re.S)

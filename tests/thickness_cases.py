@@ -16,6 +16,7 @@ import numpy as np
 
 from obj2voxel_amd import dense, hip, meshes
 from tests import components_ref as CR
+from tests import distance_ref as DR
 from tests import thickness_ref as TR
 from tests.components_cases import SHAPES, indexed, set_of
 from tests.dense_cases import expect_code3
@@ -153,6 +154,12 @@ def case_formats_and_layouts():
         check(dv, t, r, cap, border, out=swapped, depth2=None, what=(dims, "dst with x and z swapped in memory, no depth2"))
         check(dv, t, r, cap, border, kind="thickness", out=swapped_f, depth2=swapped, what=(dims, "float dst with y and z swapped, depth2 with x and z swapped"))
         n += 4
+    # the row scan's box at cap 1, where the core is the set itself: both of K21's scans on its six rows
+    for fmt, t, level in formats(DR.scan_rows(), rng):
+        S = set_of(fmt, t, level)
+        for border, background in ((False, False), (True, True)):
+            check(dv, t, Ref(~S if background else S), 1, border, background, level, "r2", what=("scan rows", fmt))
+            n += 1
     assert {c[0] for c in seen} == set(CAPS) and {c[3] for c in seen} == {"r2", "thickness", "open"} and {c[1:3] for c in seen} == {(a, b) for a in (False, True) for b in (False, True)}
     print("compared", n, "calls in", f"{time.time() - t0:.1f} s; times", dv.thickness_times())
 

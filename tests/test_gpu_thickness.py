@@ -58,3 +58,32 @@ def test_refusals():
     # (torch's caching allocator off: each tensor is an allocation of its own, so a short one is short)
     out = _run("refusals", timeout=30, env={"PYTORCH_NO_HIP_MEMORY_CACHING": "1", "PYTORCH_NO_CUDA_MEMORY_CACHING": "1"})
     assert "ok refusals" in out and "voxels do not fit an int32 index" in out
+
+
+# ---- at the limits the call documents: block turns past 2^28 voxels, the largest box, the longest axes, a core made by the border ----
+# (Each case prints what it covered.  Measured on the MI355X, DESIGN.md section 24: the four children take 2.4, 3.7, 2.8 and 3.4 s, most
+# of it the child's start and the reference, so the rule above gives the floor of 30 s.  The largest box's two calls take 356 and
+# 343 ms and its child 3.7 s: three times that is below the floor, which holds.)
+
+def test_block_turns_past_2_28_voxels():
+    out = _run("block_turns", timeout=30)
+    print(out)   # (the voxels and block turns, the counters, the call times)
+    assert "blocks 1051648 = 2^20 + 3072 in a second turn" in out and "twice the same bits" in out
+
+
+def test_largest_box_next_to_2_31_voxels():
+    out = _run("largest_box", timeout=30)
+    print(out)   # (the counters, the largest centre index, the call times)
+    assert "voxels 2146689000" in out and "largest centre index 2145023608" in out
+
+
+def test_longest_axes():
+    out = _run("long_axes", timeout=30)
+    print(out)   # (what the case covered, per axis)
+    assert all(f"taken past 2^15 along axis {a}" in out for a in "xyz")
+
+
+def test_a_core_made_by_the_border_alone():
+    out = _run("border_core", timeout=30)
+    print(out)
+    assert "the core starts at x = 64 of the row y = 64, z = 64" in out

@@ -2,6 +2,7 @@
 stubbed; the wait for torch's stream in front of every function's first library call that takes a tensor; and a static check of
 the K7 kernels in the gfx950 code object (hipcc cross-compiles)."""
 import ctypes as C
+import inspect
 import os
 import re
 import shutil
@@ -106,10 +107,31 @@ class StubVoxelizer:
     def nearest_dense(self, *args):
         self.calls.append(("nearest",))
 
+    def downsample(self, *args):
+        self.calls.append(("downsample",))
+
+    def crossings_dense(self, *args, **kw):
+        self.calls.append(("crossings",))
+
+    def label_stats(self, labels_ptr, fmt, strides, dims, origin, n, which, table_ptr):
+        self.calls.append(("label_stats",))
+        C.memset(table_ptr, 0, 8 * (n + 1) * hip.STATS_COLUMNS)   # (a new contiguous table: no voxel counted)
+        return 0
+
+    def geodesic_dense(self, *args):
+        self.calls.append(("geodesic",))
+
+    def geodesic_paths(self, *args):
+        self.calls.append(("geodesic_paths",))
+
+    def thickness_dense(self, *args):
+        self.calls.append(("thickness",))
+
 
 # the stub's calls that hand a tensor's pointer to the library
 POINTER_CALLS = {"set", "write", "distance", "mesh_distance", "surface_count", "surface_write", "raycast_build", "raycast", "components", "flood",
-                 "gather_count", "gather_write", "gather_save", "faces_count", "faces_write", "nearest"}
+                 "gather_count", "gather_write", "gather_save", "faces_count", "faces_write", "nearest", "downsample", "crossings", "label_stats",
+                 "geodesic", "geodesic_paths", "thickness"}
 
 
 @pytest.fixture(autouse=True)
@@ -271,7 +293,37 @@ WAIT_CASES = [
     ("voxel_faces", None, lambda dv, t, _: dense.voxel_faces(dv, t["g"], merge="rects", colors=t["colors"])),
     ("nearest_voxel", None, lambda dv, t, _: dense.nearest_voxel(dv, t["g"], dist2=True)),
     ("spread_colors", None, lambda dv, t, _: dense.spread_colors(dv, t["g"], t["colors"])),
+    ("crossing_numbers", None, lambda dv, t, _: dense.crossing_numbers(dv, 16, max_layers=5)),
+    ("crossing_numbers out=", None, lambda dv, t, _: dense.crossing_numbers(dv, 16, axes="zx", out=torch.zeros((4, 5, 6), dtype=torch.int32))),
+    ("winding_fill", None, lambda dv, t, _: dense.winding_fill(dv, 16)),
+    ("downsample", None, lambda dv, t, _: dense.downsample(dv, t["g"], 2)),
+    ("downsample values, colours, out=", None, lambda dv, t, _: dense.downsample(
+        dv, t["labels"], 2, count=True, values="max", colors=t["colors"], out=torch.zeros((2, 3, 3), dtype=torch.uint8),
+        out_count=torch.zeros((2, 3, 3), dtype=torch.int16), out_values=torch.zeros((2, 3, 3), dtype=torch.uint8),
+        out_colors=torch.zeros((2, 3, 3), dtype=torch.int32))),
+    ("label_stats", None, lambda dv, t, _: dense.label_stats(dv, t["labels"], moments=True, faces=True)),
+    ("label_stats int32", None, lambda dv, t, _: dense.label_stats(dv, t["colors"])),   # (n from labels.max(): a read before the call)
+    ("component_stats", None, lambda dv, t, _: dense.component_stats(dv, t["g"])),
+    ("keep_largest", None, lambda dv, t, _: dense.keep_largest(dv, t["g"])),
+    ("geodesic_distance", None, lambda dv, t, _: dense.geodesic_distance(dv, t["g"], t["seeds"])),
+    ("geodesic_distance border, out=", None, lambda dv, t, _: dense.geodesic_distance(dv, t["g"], border=True, out=torch.zeros(t["g"].shape, dtype=torch.int32))),
+    ("shortest_paths", None, lambda dv, t, _: dense.shortest_paths(dv, t["colors"], t["seeds"])),
+    ("shortest_paths max_len=", None, lambda dv, t, _: dense.shortest_paths(dv, t["colors"], [(2, 1, 1), (0, 0, 0)], max_len=7)),
+    ("local_thickness", None, lambda dv, t, _: dense.local_thickness(dv, t["g"], 3)),
+    ("local_thickness depth2=, out=", None, lambda dv, t, _: dense.local_thickness(
+        dv, t["field"], 3, level=0.0, fmt="thickness", depth2=torch.zeros(t["g"].shape, dtype=torch.int32), out=torch.zeros(t["g"].shape))),
+    ("inner_distance", None, lambda dv, t, _: dense.inner_distance(dv, t["g"])),
+    ("inner_distance out=", None, lambda dv, t, _: dense.inner_distance(dv, t["g"], out=torch.zeros(t["g"].shape, dtype=torch.int32))),
+    ("erode", None, lambda dv, t, _: dense.erode(dv, t["g"], 1)),
+    ("dilate", None, lambda dv, t, _: dense.dilate(dv, t["g"], 1)),
+    ("opening", None, lambda dv, t, _: dense.opening(dv, t["g"], 1)),
+    ("closing", None, lambda dv, t, _: dense.closing(dv, t["g"], 1)),
+    ("thin_regions", None, lambda dv, t, _: dense.thin_regions(dv, t["g"], 3)),
 ]
+
+# the public callables of dense.py that take a voxelizer and hand nothing to the library: none so far.  (One that only reads the
+# context - its limits, its transform - would go here, with the reason.)
+NO_TENSOR_TO_THE_LIBRARY = set()
 
 
 def _check_wait(monkeypatch, before, call):
@@ -308,6 +360,26 @@ def test_a_wait_comes_before_the_first_library_call_that_takes_a_tensor(monkeypa
     if name in pairs:   # (both calls of the pair were made, behind one wait)
         count, write = pairs[name]
         assert names.index("sync") < names.index(count) < names.index(write)
+
+
+def test_the_wait_table_holds_every_public_function_that_takes_a_voxelizer():
+    """WAIT_CASES by introspection: every public function or class of dense.py whose first parameter is `dv` is in the table under
+    its own name, or in NO_TENSOR_TO_THE_LIBRARY; and the table names nothing else."""
+    takes_dv = set()
+    for name, f in vars(dense).items():
+        if name.startswith("_") or not (inspect.isfunction(f) or inspect.isclass(f)) or getattr(f, "__module__", None) != dense.__name__:
+            continue
+        try:
+            params = list(inspect.signature(f).parameters)
+        except (TypeError, ValueError):
+            continue
+        if params and params[0] == "dv":
+            takes_dv.add(name)
+    assert len(takes_dv) >= 34 and {"set_mesh", "RayCaster", "thin_regions", "keep_largest"} <= takes_dv, sorted(takes_dv)
+    in_table = {c[0].split()[0].split(".")[0] for c in WAIT_CASES}
+    assert not NO_TENSOR_TO_THE_LIBRARY & in_table
+    assert takes_dv - in_table - NO_TENSOR_TO_THE_LIBRARY == set(), "public functions of dense.py without a wait case"
+    assert in_table | NO_TENSOR_TO_THE_LIBRARY <= takes_dv, sorted((in_table | NO_TENSOR_TO_THE_LIBRARY) - takes_dv)
 
 
 def test_the_wait_check_fails_a_count_voxels_without_its_wait(monkeypatch):

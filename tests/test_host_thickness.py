@@ -1,7 +1,8 @@
 """Local thickness and ball morphology without a GPU: the numpy reference of tests/thickness_ref.py against a
 brute force of the definition and against a sweep over the levels; the library's cover table (host code, no device) against
 enumeration; the pruning rule; the torch layer of obj2voxel_amd.dense against a stand-in for the device; the scratch formula;
-closed forms."""
+closed forms; what the GPU cases at the call's limits rest on: tiles with an empty outer layer do not see each other, and sets that are
+constant over a box's cross-section reduce to a line."""
 import math
 
 import numpy as np
@@ -361,3 +362,114 @@ def test_scratch_bytes_formula(dims):
         assert hip.thickness_scratch_bytes(dims, cap, True) == want and hip.thickness_scratch_bytes(dims, cap) == want + 4 * voxels
         assert hip.DeviceVoxelizer.thickness_scratch_bytes(None, dims, cap, False) == want + 4 * voxels
     assert hip.thickness_scratch_bytes((4, 0, 4), 5) == 0 and hip.thickness_scratch_bytes(dims, 0) == 0 and hip.thickness_scratch_bytes(dims, (1 << 14) + 1) == 0
+
+
+# ---- tiles that do not see each other: what the GPU cases past 2^28 voxels rest on -------------------------------------------------
+
+TILES = {(11, 9, 7): (((4, 4, 3), 2.5), ((8, 3, 3), 1.5)), (13, 8, 9): (((5, 4, 4), 3.0), ((10, 3, 5), 1.8))}   # dims (x, y, z): the balls
+TILE_CAPS = (1, 2, 5, 17, 26, 65, 400)
+
+
+def check_tiles(P, reps, caps=TILE_CAPS):
+    """All five quantities of np.tile(P, reps) by the literal reference, both borders, against the tile's (border off) repeated."""
+    G = np.tile(P, reps)
+    n = int(np.prod(reps))
+    d2 = TR.depth2(P, False)
+    for border in (False, True):
+        D2 = TR.depth2(G, border)
+        assert np.array_equal(D2, np.tile(d2, reps)), ("depth2", border)
+        for cap in caps:
+            table = hip.thickness_cover_table(cap)
+            assert np.array_equal(TR.thickness(G, cap, border, D2), np.tile(TR.thickness(P, cap, False, d2), reps)), ("T", cap, border)
+            assert np.array_equal(TR.open_only(G, cap, border, D2), np.tile(TR.open_only(P, cap, False, d2), reps)), ("open", cap, border)
+            for got, want in zip(TR.kept_centres(G, cap, border, table, D2), TR.kept_centres(P, cap, False, table, d2)):
+                assert np.array_equal(got, np.tile(want, reps)), ("centres", cap, border)
+            assert TR.visited(G, cap, border, table) == n * TR.visited(P, cap, False, table), ("visited", cap, border)
+
+
+@pytest.mark.parametrize("dims, reps", [((11, 9, 7), (2, 3, 2)), ((13, 8, 9), (3, 2, 2))])
+def test_tiles_with_an_empty_outer_layer_do_not_see_each_other(dims, reps):
+    P = TR.tile(dims, 5, seed=sum(dims), balls=TILES[dims], noise=0.05, holes=0.02)
+    top = int(TR.depth2(P, False).max())
+    assert TR.outer_layer_empty(P) and min(TILE_CAPS) < top < max(TILE_CAPS) and any(1 < c <= top for c in TILE_CAPS), top
+    check_tiles(P, reps)
+    # what the cases compare against is the same thing
+    cap = 5
+    table = hip.thickness_cover_table(cap)
+    want, G = TR.tiled(P, reps, cap, table), np.tile(P, reps)
+    cand, kept = TR.kept_centres(G, cap, True, table)
+    assert (want["candidates"], want["kept"], want["visited"]) == (int(cand.sum()), int(kept.sum()), TR.visited(G, cap, True, table))
+    assert want["last"] == int(np.flatnonzero(kept)[-1]) and np.array_equal(np.tile(want["T"], reps), TR.thickness(G, cap, True))
+
+
+@pytest.mark.parametrize("face", range(6))
+def test_a_tile_that_touches_its_face_fails_the_tile_check(face):
+    """The property needs the empty layer: a ball through one face of the tile joins its neighbour's, and the check says so."""
+    dims = (11, 9, 7)
+    centre = [5, 4, 3]
+    centre[face // 2] = 0 if face % 2 == 0 else dims[face // 2] - 1
+    P = TR.tile(dims, 5, seed=27, balls=TILES[dims], noise=0.05, holes=0.02) | TR.digital_ball(dims, centre, 2.5)
+    assert not TR.outer_layer_empty(P)
+    with pytest.raises(AssertionError):
+        check_tiles(P, (2, 3, 2), caps=(5, 17))
+    with pytest.raises(AssertionError):
+        TR.tiled(P, (2, 3, 2), 5)
+
+
+@pytest.mark.parametrize("dims", [(12, 7, 5), (9, 9, 9), (20, 3, 6), (1, 8, 8), (15, 14, 13)])
+def test_full_box_by_levels_in_closed_form(dims):
+    S = np.ones(dims[::-1], bool)
+    for cap in (1, 2, 5, 10, 17, 36, 37, 50):
+        assert np.array_equal(TR.full_box_thickness(dims, cap), TR.thickness(S, cap, True)), (dims, cap)
+
+
+# ---- sets constant over the cross-section: the reduction to a line, what the GPU case on the longest axes rests on ------------------
+
+@pytest.fixture(scope="module")
+def short_line():
+    line = TR.runs_line(640, seed=7, longest=120)
+    line[400:] = False
+    line[404:] = True      # the last run, 236 long, through the far end: its depth passes 128, a core at cap 2^14
+    return line
+
+
+def line_against_the_literal_reference(line, axis, shape, caps):
+    """The reduction of `line` against the literal reference on the box of `shape` with the line along `axis`, all five quantities
+    and the ball voxels at every cap; returns, per cap, whether depths below it, depths at or above it and kept centres occur."""
+    S = TR.along(line, shape, axis)
+    cross = tuple(n for a, n in enumerate(shape) if a != axis)
+    d2 = TR.depth2(S, False)
+    depths = np.unique(d2[S])
+    seen = set()
+    for cap in caps:
+        table = hip.thickness_cover_table(cap)
+        red = TR.line_reduction(line, cap, table)
+        for key, want in (("depth2", d2), ("T", TR.thickness(S, cap, False, d2)), ("open", TR.open_only(S, cap, False, d2))):
+            assert red[key].dtype == np.int32 and np.array_equal(TR.along(red[key], shape, axis), want), (key, cap)
+        for key, want in zip(("candidates", "kept"), TR.kept_centres(S, cap, False, table, d2)):
+            assert np.array_equal(TR.along(red[key], shape, axis), want), (key, cap)
+        assert TR.line_visited(red, cross) == TR.visited(S, cap, False, table), cap
+        seen.add((bool((depths < cap).any()), bool((depths >= cap).any()), bool(red["kept"].any())))
+    return seen
+
+
+@pytest.mark.parametrize("axis, shape", list(zip((2, 1, 0), TR.SHORT_SHAPES)))
+def test_line_reduction_against_the_literal_reference(short_line, axis, shape):
+    # caps below, among (twice) and - but for the run through the end, which gives cap 2^14 its core - above the run depths
+    seen = line_against_the_literal_reference(short_line, axis, shape, (1, 5, 401, hip.THICK_MAX_RADIUS2))
+    assert {s[:2] for s in seen} == {(False, True), (True, True)} and (True, True, True) in seen
+    # without that run every depth is below 2^14 (the run from position 0 reaches 120^2): a cap above them all, no core, no opening
+    inner = short_line[:403]
+    assert inner[0] and not inner[-1] and len(inner) > 128
+    short = tuple(len(inner) if a == axis else n for a, n in enumerate(shape))
+    assert line_against_the_literal_reference(inner, axis, short, (401, hip.THICK_MAX_RADIUS2)) == {(True, True, True), (True, False, True)}
+    red = TR.line_reduction(inner, hip.THICK_MAX_RADIUS2, hip.thickness_cover_table(hip.THICK_MAX_RADIUS2))
+    assert not (red["open"] == hip.THICK_MAX_RADIUS2).any() and np.array_equal(red["open"], red["depth2"])
+    S = TR.along(short_line, shape, axis)
+    d2 = TR.depth2(S, False)
+    # with the border on depth2' is the line's, min the border term: at most 4 on these cross-sections
+    want = TR.depth2(S, True)
+    assert np.array_equal(np.where(S, np.minimum(d2, TR.border_term(shape)), 0), want) and int(want.max()) == 4
+    table = hip.thickness_cover_table(401)
+    _, kept = TR.kept_centres(S, 401, True, table, want)
+    assert kept.any() and TR.visited_small(want, kept) == TR.visited(S, 401, True, table)

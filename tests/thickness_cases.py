@@ -5,7 +5,8 @@ torch is imported before the library is loaded (see tests/dense_cases.py).  Ever
 every thickness call is made with O2V_HIP_FLAG_STAGE_TIMES where the counters are compared: candidates, kept centres and visited
 ball voxels must be the reference's, which is how a case knows it went through the list and the ball stage (or around them).
 The shapes are the smallest at which the passes can go wrong, not workload sizes; a reference is computed once per set and
-shared.  A case prints what it covered and "ok" last when everything held."""
+shared; the cases at the limits the call documents (the last four) are as large as the limit they are about.  A case prints what it
+covered and "ok" last when everything held."""
 import math
 import sys
 import time
@@ -50,31 +51,38 @@ class Ref:
                 self.memo[key] = TR.thickness(self.S, cap, border, d2)
             elif what == "open":
                 self.memo[key] = TR.open_only(self.S, cap, border, d2)
+            elif what == "visited":
+                self.memo[key] = TR.visited(self.S, cap, border, hip.thickness_cover_table(cap))
             else:
                 cand, kept = TR.kept_centres(self.S, cap, border, hip.thickness_cover_table(cap), d2)
                 self.memo[key] = (int(cand.sum()), int(kept.sum()))
         return self.memo[key]
 
 
-def raw(dv, t, level, cap, border, background, flags, out, depth2):
-    """One o2v_hip_thickness_dense call on tensors, with O2V_HIP_FLAG_STAGE_TIMES."""
+def raw(dv, t, level, cap, border, background, flags, out, depth2, nx=None):
+    """One o2v_hip_thickness_dense call on tensors, with O2V_HIP_FLAG_STAGE_TIMES.  nx: the voxels along x of a bits grid whose last
+    word is part padding (else 32 per word)."""
     _, fmt, lvl, dims = dense._set_grid(dv, t, level, dense._limit_thickness)
+    if nx is not None:
+        assert fmt == hip.GRID_BITS and dims[0] - 32 < nx <= dims[0]
+        dims = (nx,) + dims[1:]
     flags |= hip.FLAG_STAGE_TIMES | (hip.THICK_BORDER if border else 0) | (hip.THICK_BACKGROUND if background else 0)
     torch.cuda.synchronize()
     dv.thickness_dense(t.data_ptr(), fmt, dense._strides(t), dims, 0.0 if lvl is None else lvl, flags, cap, out.data_ptr(), dense._strides(out),
                        None if depth2 is None else depth2.data_ptr(), None if depth2 is None else dense._strides(depth2))
 
 
-def check(dv, t, ref, cap, border=True, background=False, level=None, kind="r2", out=None, depth2=True, what=""):
+def check(dv, t, ref, cap, border=True, background=False, level=None, kind="r2", out=None, depth2=True, what="", nx=None, visited=False):
     """One call against the reference of the set (ref: a Ref of S, or of its complement with background): T (kind "r2"), its
-    float32 form ("thickness") or the OPEN_ONLY grid ("open"); depth2 if asked for; the counters."""
+    float32 form ("thickness") or the OPEN_ONLY grid ("open"); depth2 if asked for; the counters - the ball voxels too with
+    visited=True (the reference walks every kept centre's ball: for sets where that is affordable)."""
     shape = ref.S.shape
     if out is None:
         out = torch.full(shape, -3, dtype=torch.float32 if kind == "thickness" else torch.int32, device=DEV)
     if depth2 is True:
         depth2 = torch.full(shape, -3, dtype=torch.int32, device=DEV)
     flags = {"r2": 0, "thickness": hip.THICK_F32, "open": hip.THICK_OPEN_ONLY}[kind]
-    raw(dv, t, level, cap, border, background, flags, out, depth2)
+    raw(dv, t, level, cap, border, background, flags, out, depth2, nx)
     want = ref.get("open" if kind == "open" else "T", cap, border)
     got = out.cpu().numpy()
     if kind == "thickness":
@@ -83,12 +91,14 @@ def check(dv, t, ref, cap, border=True, background=False, level=None, kind="r2",
         assert np.array_equal(got, want), (what, cap, border, background, kind, int((got != want).sum()), "voxels differ")
     if depth2 is not None:
         assert np.array_equal(depth2.cpu().numpy(), ref.depth2(border)), (what, cap, border, background, "depth2 differs")
-    cand, kept, visited = dv.thickness_counters()
+    cand, kept, balls = dv.thickness_counters()
     if kind == "open":
-        assert (cand, kept, visited) == (0, 0, 0), (what, cand, kept, visited)
+        assert (cand, kept, balls) == (0, 0, 0), (what, cand, kept, balls)
     else:
         assert (cand, kept) == ref.get("centres", cap, border), (what, cap, border, (cand, kept), ref.get("centres", cap, border))
-        assert (visited > 0) == (kept > 0)
+        assert (balls > 0) == (kept > 0)
+        if visited:
+            assert balls == ref.get("visited", cap, border), (what, cap, border, "ball voxels", balls, ref.get("visited", cap, border))
     return out
 
 
@@ -409,8 +419,255 @@ def case_refusals():
     print("ok refusals")
 
 
+# ---- at the limits the call documents --------------------------------------------------------------------------------------------------
+#
+# The two large boxes are repetitions of a tile whose outer voxel layer is empty, so that the tile's reference, repeated, is the
+# box's (tests/thickness_ref.py, held against the literal reference by tests/test_host_thickness.py); the longest axes carry sets
+# that are constant over the cross-section, which reduce to a line (the same two files).
+
+SMALL_TILE = ((33, 19, 27), (((9, 9, 13), 6.0), ((22, 8, 8), 3.0), ((27, 12, 20), 2.0)))                       # dims (x, y, z), balls
+LARGE_TILE = ((43, 30, 30), (((12, 12, 14), 9.0), ((30, 10, 9), 5.0), ((33, 22, 20), 3.5), ((20, 24, 24), 2.0)))
+
+
+def timed(dv, *args):
+    """raw(dv, *args): (the counters, the wall time in ms, the stage times)."""
+    t0 = time.time()
+    raw(dv, *args)
+    return dv.thickness_counters(), round((time.time() - t0) * 1e3, 1), [round(ms, 1) for ms in dv.thickness_times()]
+
+
+def slabs_equal(got, tile_grid, reps, what):
+    """got [z, y, x] on the device against the tile's grid repeated: one tile-thick slab of z at a time, every voxel."""
+    tz = tile_grid.shape[0]
+    slab = torch.from_numpy(np.ascontiguousarray(tile_grid)).to(DEV).repeat(1, reps[1], reps[2])
+    assert got.dtype == slab.dtype and got.shape[0] == tz * reps[0] and got.shape[1:] == slab.shape[1:], what
+    for k in range(reps[0]):
+        assert torch.equal(got[k * tz:(k + 1) * tz], slab), (what, "slab", k, int((got[k * tz:(k + 1) * tz] != slab).sum()), "voxels differ")
+
+
+def repeated(tile_spec, reps, cap, seed):
+    """(the tile's repetition uint8 [z, y, x] built on the device, what it must give (TR.tiled), dims (x, y, z))."""
+    dims, balls = tile_spec
+    table = hip.thickness_cover_table(cap)
+    P = TR.tile(dims, cap, seed, balls, table=table)
+    want = TR.tiled(P, reps, cap, table)
+    grid = torch.from_numpy(P.astype(np.uint8)).to(DEV).repeat(*reps)
+    return grid, want, tuple(n * r for n, r in zip(dims, reps[::-1]))
+
+
+def case_block_turns():
+    """Just past 2^28 voxels: k_thick_init and k_thick_list take a second turn of 3 072 blocks, the last of them one voxel short, the block
+    offsets go through 4 108 rounds of the one-workgroup scan, both envelope passes have more lines than lanes on the context's
+    depth grid and on a dst / depth2 whose axes are swapped in memory.
+
+    It bites: with the turns dropped (`for (b = blockIdx.x; b < n_blocks; b += gridDim.x)` of k_thick_init and k_thick_list made
+    `if (b < n_blocks)`, the skipped blocks' sums zeroed so that the list stays one), the case failed at its first call with
+    ('counters', (18703943, 5138684, 250617392), (18717831, 5152572, 250631280)) - the 13 888 centres of the last 3 072 blocks
+    were never counted or listed."""
+    dv = hip.DeviceVoxelizer(0)
+    cap, reps = 17, (19, 27, 31)
+    grid, want, (nx, ny, nz) = repeated(SMALL_TILE, reps, cap, seed=1)
+    voxels = nx * ny * nz
+    blocks = -(-voxels // 256)
+    assert (nx, ny, nz) == (1023, 513, 513) and voxels == 269221887 and voxels > 1 << 28 and voxels % 256 != 0
+    assert blocks == 1051648 and blocks - (1 << 20) == 3072 and voxels % 256 == 255 and nx * nz > 1 << 17 and nx * ny > 1 << 17
+    assert want["last"] > 1 << 28 and want["last"] // 256 >= 1 << 20      # (a centre listed in the second turn)
+    counters = (want["candidates"], want["kept"], want["visited"])
+    shape = tuple(grid.shape)
+    a = torch.full(shape, -3, dtype=torch.int32, device=DEV)
+    got = timed(dv, grid, None, cap, False, False, 0, a, None)            # (the depth grid is the context's)
+    assert got[0] == counters, ("counters", got[0], counters)
+    slabs_equal(a, want["T"], reps, "r2, the context's depth grid")
+    b = torch.full(shape, -3, dtype=torch.int32, device=DEV)
+    again = timed(dv, grid, None, cap, False, False, 0, b, None)
+    assert again[0] == counters and torch.equal(a, b), "the second run differs"
+    # dst with y and z swapped in memory, depth2 with x and z swapped: more lines than lanes on strided grids
+    del b
+    b = torch.full((ny, nz, nx), -3, dtype=torch.int32, device=DEV).permute(1, 0, 2)
+    d2 = torch.full((nx, ny, nz), -3, dtype=torch.int32, device=DEV).permute(2, 1, 0)
+    assert tuple(b.shape) == tuple(d2.shape) == shape and not b.is_contiguous() and d2.stride(2) == ny * nz
+    with_d2 = timed(dv, grid, None, cap, True, False, 0, b, d2)
+    assert with_d2[0] == counters, ("counters, border on", with_d2[0], counters)
+    slabs_equal(b, want["T"], reps, "r2 with depth2, border on")
+    slabs_equal(d2, want["depth2"], reps, "depth2, border on")
+    low = timed(dv, grid, None, cap, True, False, hip.THICK_OPEN_ONLY, b, d2)
+    assert low[0] == (0, 0, 0), low[0]
+    slabs_equal(b, want["open"], reps, "open")
+    slabs_equal(d2, want["depth2"], reps, "depth2 of open")
+    print(f"block_turns {nx} x {ny} x {nz}: voxels {voxels}, blocks {blocks} = 2^20 + {blocks - (1 << 20)} in a second turn, lines per envelope pass {nx * nz} and "
+          f"{nx * ny}; candidates, kept, ball voxels {counters}, largest centre index {want['last']}, twice the same bits; "
+          f"ms (wall, stages): r2 {got[1:]}, r2 with a strided dst and depth2 {with_d2[1:]}, open on the same {low[1:]}")
+
+
+def case_largest_box():
+    """1290^3 = 2 146 689 000 voxels, the largest cube under 2^31 - 1 (K15's): the centre list's int32 indices, c / nx in the ball
+    stage, k_thick_convert's grid stride and byte offsets above 2^33 in dst and depth2, 8 385 504 blocks in eight turns.  One call in
+    the float format with depth2 and the border on, one r2 call on the context's depth grid.
+
+    No kept centre can lie within 2^20 of 2^31: the tile's empty outer layer puts the last content at z = 1288, and a z layer is
+    1290^2 > 2^20 voxels.  The largest listed index is that of the last voxel inside the outer layer, (1288, 1288, 1288) =
+    2 145 023 608 = 2^31 - 2 460 040, which is asserted exactly.
+
+    Measured on the MI355X (50 588 640 kept centres, 3 578 036 880 ball voxels; ms, wall and then the stages depth2 / core /
+    list / balls / convert): the float call with depth2 355.8 (67.1 / 31.9 / 216.0 / 31.3 / 6.4), the r2 call 342.6 (62.1 / 32.1 /
+    215.3 / 31.0 / 0); the case with its comparisons 0.9 s, its child 3.7 s.  The ball stage is a tenth of the call; counting and
+    listing the centres (the keep test twice over 2^31 voxels) is two thirds.
+
+    It bites: with the centre index held in 30 bits (`list[...] = (int32_t) (i & 0x3fffffff)` in k_thick_list) the case failed at
+    its first call with ('counters', (196252860, 50588640, 1825923900), (196252860, 50588640, 3578036880)): the balls of the
+    centres past 2^30 were drawn around other voxels."""
+    dv = hip.DeviceVoxelizer(0)
+    cap, reps = 17, (43, 43, 30)
+    t0 = time.time()
+    grid, want, (nx, ny, nz) = repeated(LARGE_TILE, reps, cap, seed=2)
+    voxels = nx * ny * nz
+    assert (nx, ny, nz) == (1290, 1290, 1290) and voxels == 2146689000 and voxels <= 2 ** 31 - 1 < 1291 ** 3
+    assert want["last"] == 1288 * (1290 * 1290 + 1290 + 1) == 2145023608 and want["last"] > 2 ** 31 - 2 ** 22
+    counters = (want["candidates"], want["kept"], want["visited"])
+    shape = tuple(grid.shape)
+    out = torch.full(shape, -3.0, dtype=torch.float32, device=DEV)
+    d2 = torch.full(shape, -3, dtype=torch.int32, device=DEV)
+    as_float = timed(dv, grid, None, cap, True, False, hip.THICK_F32, out, d2)
+    assert as_float[0] == counters, ("counters", as_float[0], counters)
+    slabs_equal(out.view(torch.int32), TR.as_float(want["T"]).view(np.int32), reps, "the float bits")
+    slabs_equal(d2, want["depth2"], reps, "depth2")
+    del d2
+    out = out.view(torch.int32).fill_(-3)
+    r2 = timed(dv, grid, None, cap, False, False, 0, out, None)
+    assert r2[0] == counters, ("counters, r2", r2[0], counters)
+    slabs_equal(out, want["T"], reps, "r2, the context's depth grid")
+    print(f"largest_box {nx} x {ny} x {nz}: voxels {voxels}, blocks {-(-voxels // 256)}; candidates, kept, ball voxels {counters}, largest centre index {want['last']} "
+          f"= 2^31 - {2 ** 31 - want['last']}; ms (wall, stages): float with depth2 {as_float[1:]}, r2 {r2[1:]}; the case {time.time() - t0:.1f} s")
+
+
+def case_long_axes():
+    """46 341 voxels, the longest axis accepted, along x, y and z: 725 chunks per row in K21's two row scans, envelope lines whose
+    stack entries use all 16 bits.  Sets constant over the cross-section, border off: T, depth2, OPEN_ONLY and the centres are
+    TR.line_reduction's; with the border on depth2' is at most 4, the balls are small and the literal scatter is affordable.
+
+    It bites: with thick_border skipped in the look-ahead of k_thick_core_x (`return erow[x] >= cap` when ahead) the case failed
+    at the call with the border on: ((3, 5, 46341), 'T with the border').  (With the border off thick_border changes nothing.)"""
+    dv = hip.DeviceVoxelizer(0)
+    top = hip.THICK_MAX_RADIUS2
+    tables = {cap: hip.thickness_cover_table(cap) for cap in (top, 401)}
+    past = 1 << 15
+    for axis, shape in zip((2, 1, 0), TR.LONG_SHAPES):
+        assert max(shape) == shape[axis] == TR.LONG and sum((n - 1) ** 2 for n in shape) <= 2 ** 31 - 2, shape
+        line = TR.runs_line(TR.LONG, seed=31 + axis)
+        cross = tuple(n for a, n in enumerate(shape) if a != axis)
+        S = TR.along(line, shape, axis)
+        t = dev(S)
+        spread = lambda v: dev(TR.along(v, shape, axis))   # noqa: E731
+        out = torch.full(shape, -3, dtype=torch.int32, device=DEV)
+        d2 = torch.full(shape, -3, dtype=torch.int32, device=DEV)
+        # cap 2^14, border off
+        red = TR.line_reduction(line, top, tables[top])
+        raw(dv, t, None, top, False, False, 0, out, d2)
+        assert torch.equal(out, spread(red["T"])), (shape, "T", int((out != spread(red["T"])).sum()), "voxels differ")
+        assert torch.equal(d2, spread(red["depth2"])), (shape, "depth2")
+        n = cross[0] * cross[1]
+        counters = (n * int(red["candidates"].sum()), n * int(red["kept"].sum()), TR.line_visited(red, cross))
+        assert dv.thickness_counters() == counters, (shape, dv.thickness_counters(), counters)
+        mid = (red["T"] > 1) & (red["T"] < top)
+        assert (red["T"] == top).any() and mid[past + 1:].any() and red["kept"][past + 1:].any()
+        # cap 401, OPEN_ONLY
+        low = TR.line_reduction(line, 401, tables[401])
+        raw(dv, t, None, 401, False, False, hip.THICK_OPEN_ONLY, out, d2)
+        assert torch.equal(out, spread(low["open"])) and torch.equal(d2, spread(low["depth2"])) and dv.thickness_counters() == (0, 0, 0), (shape, "open")
+        assert (low["open"] == 401).any() and ((low["open"] > 0) & (low["open"] < 401)).any()
+        # cap 2^14, border on: depth2' = min(the line's depth2, the border term) <= 4
+        d2b = np.where(S, np.minimum(TR.along(red["depth2"], shape, axis), TR.border_term(shape)), 0).astype(np.int32)
+        assert int(d2b.max()) == 4
+        cand, kept = TR.kept_centres(S, top, True, tables[top], d2b)
+        raw(dv, t, None, top, True, False, 0, out, d2)
+        assert torch.equal(d2, dev(d2b)), (shape, "depth2 with the border")
+        assert torch.equal(out, dev(TR.thickness(S, top, True, d2b))), (shape, "T with the border")
+        with_border = (int(cand.sum()), int(kept.sum()), TR.visited_small(d2b, kept))
+        assert dv.thickness_counters() == with_border, (shape, dv.thickness_counters(), with_border)
+        print(f"long_axes {shape}: {int(line.sum())} of {TR.LONG} positions in {int((np.diff(line.astype(np.int8)) == 1).sum()) + 1} runs, T reaches the cap 2^14 at "
+              f"{int((red['T'] == top).sum())}; taken past 2^15 along axis {'zyx'[axis]}: {int(red['kept'][past + 1:].sum())} kept centres per cross-section "
+              f"position, {int(mid[past + 1:].sum())} positions with 1 < T < cap; counters {counters}, with the border {with_border}; times {dv.thickness_times()}", flush=True)
+
+
+def case_border_core():
+    """Full boxes with the border on: depth2 is 0x7FFFFFFF everywhere and the core {depth2' >= cap} exists through thick_border
+    alone, which k_thick_core_x evaluates once in the look-ahead (no write) and once in the chunk's own turn.  Rows of 200 and 131
+    voxels: four and three chunks.  One empty voxel at the far end of the middle row is the row's only voxel outside S, which the
+    depth scan's look-ahead has to find two chunks on - but in the two small boxes the border's min (m <= 4, m <= 2) hides what the
+    depth scan gave everywhere but within a few voxels of the hole, so a look-ahead that missed it from chunks 0 - 2 would go
+    unnoticed there.  Only the 131 x 129 x 129 box below shows it: with the hole, depth2 at x = 66 .. 127 of its middle rows
+    is (130 - x)^2 from the look-ahead into chunk 2.  That box is not to be trimmed.
+
+    m = min(x + 1, nx - x, y + 1, ny - y, z + 1, nz - z) is at most 4 in the 200 x 9 x 7 box (its rows y = 4, z = 3) and at most 2
+    in the 131 x 70 x 3 box (z = 1): the core is empty at cap 17 in the first and from cap 5 on in the second, and where it is
+    not empty it starts at x = 1 or 2.  A core that starts past the first chunk needs m >= 65: the 131 x 129 x 129 box at cap
+    65^2 = 4225, whose core is the three voxels x = 64 .. 66 of its middle row y = 64, z = 64 alone (two with the empty voxel).  There depth2 and OPEN_ONLY are
+    compared against the reference, and T of the full box - balls of up to 129 voxels across in three dimensions - against its closed
+    form by levels (TR.full_box_thickness: the literal scatter of two million centres is out of reach).
+
+    It bites: with thick_border skipped in the look-ahead of k_thick_core_x (`return erow[x] >= cap` when ahead) the case failed
+    at its first call: (((200, 9, 7), False, 'u8'), 2, True, False, 'r2', 12, 'voxels differ')."""
+    dv = hip.DeviceVoxelizer(0)
+    n, empty_cores, late = 0, 0, None
+    for dims, caps in (((200, 9, 7), (2, 5, 17)), ((131, 70, 3), (2, 5, 17, 1000))):
+        nx, ny, nz = dims
+        for hole in (False, True):
+            S = np.ones(dims[::-1], bool)
+            if hole:
+                S[nz // 2, ny // 2, nx - 1] = False      # the only voxel outside S, in the last chunk of the middle row
+            r = Ref(S)
+            for fmt, t, width in (("u8", dev(S.astype(np.uint8)), None), ("bits", dev(pack_padded(S)), nx)):
+                for cap in caps:
+                    for kind in ("r2", "open"):
+                        check(dv, t, r, cap, border=True, kind=kind, what=(dims, hole, fmt), nx=width, visited=True)
+                        n += 1
+                    core = r.depth2(True) >= cap
+                    empty_cores += not core.any()
+                    assert core.any() == (cap <= ((min(dims) + 1) // 2) ** 2), (dims, cap)
+    assert empty_cores > 0
+    dims, cap = (131, 129, 129), 65 * 65
+    nx, ny, nz = dims
+    for hole in (False, True):
+        S = np.ones(dims[::-1], bool)
+        if hole:
+            S[nz // 2, ny // 2, nx - 1] = False
+        r = Ref(S)
+        core = np.argwhere(r.depth2(True) >= cap)
+        # (z, y, x): found by the look-ahead of chunk 0 in chunk 1; the empty voxel at x = 130 is 64 from x = 66, which leaves the core
+        assert core.tolist() == [[64, 64, x] for x in ((64, 65) if hole else (64, 65, 66))], core
+        late = int(core[0][2])
+        check(dv, dev(S), r, cap, border=True, kind="open", what=(dims, hole))
+        n += 1
+        if not hole:   # T of the full box by levels in closed form (held against the scatter by tests/test_host_thickness.py)
+            r.memo["T", cap, True] = TR.full_box_thickness(dims, cap)
+            check(dv, dev(S), r, cap, border=True, kind="r2", what=(dims, "the full box"))
+            # the ball voxels per radius class: depth2' = m^2 puts the centre m - 1 voxels or more from every face and its ball
+            # {|q|^2 < m^2} reaches m - 1, so no ball of the full box is clipped and each holds the whole digital ball of its radius
+            _, kept = TR.kept_centres(S, cap, True, hip.thickness_cover_table(cap), r.depth2(True))
+            radii, counts = np.unique(r.depth2(True)[kept], return_counts=True)
+            balls = sum(int(c) * int(TR.ball(int(R))[0].sum()) for R, c in zip(radii, counts))
+            assert int(radii.max()) == 64 * 64 and dv.thickness_counters()[2] == balls, ("ball voxels of the full box", dv.thickness_counters()[2], balls)
+            big = (r.get("centres", cap, True), balls, [round(ms, 1) for ms in dv.thickness_times()])
+            assert big[0][1] > 0
+            n += 1
+    assert late >= 64
+    print(f"border_core: compared {n} calls on full boxes with the border on, u8 and bits, with and without one empty voxel at the far end of the middle row; "
+          f"{empty_cores} of the 28 boxes / formats / caps without a core; in the 131 x 129 x 129 box at cap 4225 the core starts at x = {late} of the row y = 64, z = 64; its full box: candidates and kept {big[0]}, {big[1]} ball voxels, ms {big[2]}")
+
+
+def pack_padded(S):
+    """int32 [z, y, ceil(nx / 32)]: bit x % 32 of word x / 32, the padding of the last word set (it is not part of the box)."""
+    nz, ny, nx = S.shape
+    words = (nx + 31) // 32
+    padded = np.ones((nz, ny, words * 32), np.uint64)
+    padded[:, :, :nx] = S
+    w = (padded.reshape(nz, ny, words, 32) << np.arange(32, dtype=np.uint64)).sum(-1)
+    return w.astype(np.uint32).view(np.int32)
+
+
 CASES = {"formats_and_layouts": case_formats_and_layouts, "large_radii": case_large_radii, "many_centres": case_many_centres, "clipping": case_clipping,
-         "morphology": case_morphology, "pipeline": case_pipeline, "refusals": case_refusals}
+         "morphology": case_morphology, "pipeline": case_pipeline, "refusals": case_refusals, "block_turns": case_block_turns, "largest_box": case_largest_box,
+         "long_axes": case_long_axes, "border_core": case_border_core}
 
 if __name__ == "__main__":
     CASES[sys.argv[1]]()

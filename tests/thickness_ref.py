@@ -8,6 +8,9 @@ closing and thin_regions, on bool sets S [z, y, x].  nump
     by_levels    T as a sweep over the distinct radii, one dilation each
     cover_table  L_k[R] by enumeration
     kept_centres the centres that the cover table does not prune, and their count: what the device's counters must show
+    tile, tiled  a tile with an empty outer layer, and what its repetition gives: the reference of the boxes past 2^28 voxels
+    line_reduction, line_visited   sets constant over a long box's cross-section, reduced to a line
+    full_box_thickness             T of a full box with the border on, by levels in closed form
 tests/test_host_thickness.py holds them against each other."""
 import numpy as np
 
@@ -192,6 +195,21 @@ def visited(S, cap, border, table=None):
     return n
 
 
+def visited_small(d2, kept):
+    """visited() from depth2 and the kept centres, per ball offset and all centres of a radius at once: for many centres of small
+    balls (the long boxes, where the border keeps every radius^2 at most 4)."""
+    d2, kept = np.asarray(d2), np.asarray(kept, bool)
+    nz, ny, nx = d2.shape
+    n = 0
+    for R in np.unique(d2[kept]).tolist():
+        mask, r = ball(R)
+        at = kept & (d2 == R)
+        for dz, dy, dx in (np.argwhere(mask) - r).tolist():
+            if abs(dz) < nz and abs(dy) < ny and abs(dx) < nx:
+                n += int(at[max(0, -dz):nz - max(0, dz), max(0, -dy):ny - max(0, dy), max(0, -dx):nx - max(0, dx)].sum())
+    return n
+
+
 # ---- the derived grids of obj2voxel_amd.dense -----------------------------------------------------------------------------------
 
 def erode(S, radius, border=True):
@@ -231,3 +249,178 @@ def plate(dims, axis, first, width):
     sl[2 - axis] = slice(first, first + width)
     S[tuple(sl)] = True
     return S
+
+
+# ---- tiles that do not see each other -------------------------------------------------------------------------------------------
+#
+# A tile P whose outermost voxel layer is empty on all six sides, repeated: G = np.tile(P, reps).  The clamp of a voxel outside a tile
+# to the tile's box is an empty voxel of that tile and at least as near, coordinate by coordinate, so depth2 of a voxel of S is
+# decided inside its own tile, every ball stays inside its tile's content, and the neighbours across a tile boundary have depth 0
+# and cover nothing: T, depth2 and OPEN_ONLY of G are the tile's repeated, the candidates, kept centres and ball voxels prod(reps)
+# times the tile's, with the border on or off (the tile's values are those of border=False).  tests/test_host_thickness.py holds
+# this against the literal reference; the GPU cases past 2^28 voxels rest on it.
+
+def outer_layer_empty(P):
+    P = np.asarray(P, bool)
+    return not (P[0].any() or P[-1].any() or P[:, 0].any() or P[:, -1].any() or P[:, :, 0].any() or P[:, :, -1].any())
+
+
+def tile(dims, cap, seed, balls, noise=0.004, holes=0.002, table=None):
+    """bool [z, y, x] of dims (nx, ny, nz): the digital balls ((cx, cy, cz), radius), a one-voxel plate, a rod along x in the last
+    row of content (y = ny - 2, z = nz - 2), some noise and a few holes, the outer layer cleared.  Asserts what the large cases rely
+    on at `cap`: a core (depth2 >= cap somewhere), voxels of S outside the opening, 0 < kept centres < candidates, a kept centre in
+    the last row of content (so the largest listed index of a repetition lies in its last row of content).  table: the cover table
+    of cap (by enumeration when None)."""
+    nx, ny, nz = dims
+    rng = np.random.default_rng(seed)
+    S = rng.random(dims[::-1]) < noise
+    for c, rad in balls:
+        S |= digital_ball(dims, c, rad)
+    S[nz // 3, 2:ny // 2, nx // 2:] = True
+    S &= ~(rng.random(dims[::-1]) < holes)
+    S[nz - 2, ny - 2, :] = True
+    S[0] = S[-1] = S[:, 0] = S[:, -1] = S[:, :, 0] = S[:, :, -1] = False
+    assert outer_layer_empty(S)
+    d2 = depth2(S, False)
+    assert np.array_equal(d2, depth2(S, True))
+    low = open_only(S, cap, False, d2)
+    cand, kept = kept_centres(S, cap, False, table, d2)
+    assert (d2 >= cap).any() and (low == cap).any() and (S & (low != cap)).any(), "the tile needs a core and voxels outside its opening"
+    assert 0 < kept.sum() < cand.sum() and kept[nz - 2, ny - 2].any(), (int(kept.sum()), int(cand.sum()))
+    return S
+
+
+def tiled(P, reps, cap, table=None):
+    """What the repetition np.tile(P, reps) (reps along z, y, x) must give at `cap`, from the tile alone: dict of T, depth2, open
+    (int32 [z, y, x] of the tile, to be repeated), candidates, kept, visited (counts of the whole repetition), and last: the
+    largest linear index of a kept centre in the repetition."""
+    P = np.asarray(P, bool)
+    assert outer_layer_empty(P)
+    d2 = depth2(P, False)
+    cand, kept = kept_centres(P, cap, False, table, d2)
+    n = int(np.prod(reps))
+    nz, ny, nx = P.shape
+    z, y, x = np.argwhere(kept)[-1].tolist()   # (row-major: the last kept centre of the tile, so of the last tile)
+    Z, Y, X = z + (reps[0] - 1) * nz, y + (reps[1] - 1) * ny, x + (reps[2] - 1) * nx
+    return dict(T=thickness(P, cap, False, d2), depth2=d2, open=open_only(P, cap, False, d2), candidates=n * int(cand.sum()), kept=n * int(kept.sum()),
+                visited=n * visited(P, cap, False, table), last=(Z * reps[1] * ny + Y) * reps[2] * nx + X)
+
+
+# ---- sets that are constant over the cross-section of a long box ------------------------------------------------------------------
+#
+# S = {voxels whose coordinate u along one axis lies in a set of runs}, border off.  Everything reduces to the line along u:
+# depth(u) is the distance to the nearest gap position (the ends of the box do not count), R = min(depth^2, cap),
+# T(u) = max { R(u') : (u - u')^2 < R(u') } (the centre with the same cross-section offset is the best one), the opening is what
+# lies within (u - u')^2 < cap of a u' with R(u') = cap, and a centre is kept exactly when neither axis neighbour reaches
+# L_1[R(u)] (the off-axis neighbours have the axis neighbours' radii and need L_2, L_3 >= L_1; a neighbour at the same u has
+# R(u) < L_k[R(u)]).  tests/test_host_thickness.py holds this against the literal reference on a short box.
+
+LONG = 46341   # the longest axis accepted: (LONG - 1)^2 + 20 <= 2^31 - 2
+LONG_SHAPES = [(3, 5, LONG), (3, LONG, 5), (LONG, 3, 4)]   # [z, y, x]: x, y, z long
+SHORT_SHAPES = [(3, 5, 640), (3, 640, 5), (640, 3, 4)]
+
+
+def runs_line(n, seed, longest=300):
+    """bool [n]: runs of 1 .. longest positions separated by gaps of 1 .. 3; the first starts at 0, the last goes through the end."""
+    rng = np.random.default_rng(seed)
+    line = np.zeros(n, bool)
+    u = 0
+    while u < n:
+        run = int(rng.integers(1, longest + 1))
+        if n - (u + run) < 4:      # (no gap left behind it: the run goes through the far end, at least 4 long)
+            run = n - u
+        line[u:u + run] = True
+        u += run + int(rng.integers(1, 4))
+    assert line[0] and line[-1] and not line.all()
+    return line
+
+
+def _shifted(a, k, fill=0):
+    """b[u] = a[u + k], fill past the ends."""
+    out = np.full_like(a, fill)
+    if k >= 0:
+        out[:len(a) - k] = a[k:]
+    else:
+        out[-k:] = a[:len(a) + k]
+    return out
+
+
+def line_reduction(line, cap, table):
+    """Per position u of the line (bool [n], at least one gap), border off: dict of int32 T, depth2, open, and bool candidates,
+    kept.  table: the cover table of cap ([3, cap + 1])."""
+    line = np.asarray(line, bool)
+    n = len(line)
+    assert not line.all()
+    idx = np.arange(n, dtype=np.int64)
+    big = np.int64(1) << 40
+    left = np.maximum.accumulate(np.where(~line, idx, -big))
+    right = np.minimum.accumulate(np.where(~line, idx, big)[::-1])[::-1]
+    d = np.minimum(idx - left, right - idx)
+    d2 = np.where(line, d * d, 0)
+    R = np.minimum(d2, cap)
+    w = int(np.floor(np.sqrt(cap - 1)))
+    while w * w > cap - 1:
+        w -= 1
+    T = np.zeros(n, np.int64)
+    near = np.zeros(n, bool)
+    for k in range(-min(w, n - 1), min(w, n - 1) + 1):
+        Rk = _shifted(R, k)
+        T = np.maximum(T, np.where(k * k < Rk, Rk, 0))
+        if k * k < cap:
+            near |= Rk == cap
+    cand = line & (d2 < cap)
+    need = np.asarray(table)[0].astype(np.int64)[R]
+    kept = cand & (np.maximum(_shifted(R, -1), _shifted(R, 1)) < need)
+    return dict(T=np.where(line, T, 0).astype(np.int32), depth2=d2.astype(np.int32), open=np.where(line, np.where(near, cap, R), 0).astype(np.int32),
+                candidates=cand, kept=kept)
+
+
+def line_visited(red, cross):
+    """The ball voxels inside a box of cross-section `cross` (a, b) of the kept centres of a line_reduction: for the centre at
+    (u, c) and the cross-section position c', the positions u' with (u - u')^2 < R(u) - |c - c'|^2, clipped to the line."""
+    n = len(red["kept"])
+    u = np.nonzero(red["kept"])[0].astype(np.int64)
+    R = red["depth2"].astype(np.int64)[u]
+    total = 0
+    a, b = cross
+    for da in range(-(a - 1), a):
+        for db in range(-(b - 1), b):
+            pairs = (a - abs(da)) * (b - abs(db))      # ordered pairs (c, c') of the cross-section with this offset
+            rem = R - (da * da + db * db)
+            ok = rem > 0
+            h = np.floor(np.sqrt(np.maximum(rem - 1, 0).astype(np.float64))).astype(np.int64)
+            h = np.where(h * h > rem - 1, h - 1, h)
+            h = np.where((h + 1) * (h + 1) <= rem - 1, h + 1, h)
+            cnt = np.minimum(u + h, n - 1) - np.maximum(u - h, 0) + 1
+            total += pairs * int(cnt[ok].sum())
+    return total
+
+
+def full_box_thickness(dims, cap):
+    """int32 T [z, y, x] of the full box of dims (nx, ny, nz) with the border on, by levels in closed form: depth2' is m^2, the level
+    set {m >= k} is the box shrunk by k - 1 voxels on every side, and the squared distance to a box is the sum of the squared
+    overshoots per axis: T = max { min(k^2, cap) : dist2(p, {m >= k}) < min(k^2, cap) }.  (Past k^2 >= cap the level sets only
+    shrink and R stays the cap, so they add nothing.)  For boxes whose literal scatter is out of reach."""
+    nx, ny, nz = dims
+    z, y, x = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij", sparse=True)
+    T = np.zeros((nz, ny, nx), np.int64)
+    for k in range(1, (min(dims) + 1) // 2 + 1):
+        R = min(k * k, cap)
+        over = [np.maximum(np.maximum(k - 1 - c, c - (n - k)), 0) for c, n in ((x, nx), (y, ny), (z, nz))]
+        T = np.where(over[0] ** 2 + over[1] ** 2 + over[2] ** 2 < R, R, T)
+    return T.astype(np.int32)
+
+
+def along(v, shape, axis):
+    """The values v [n] of a line along `axis` of [z, y, x] (0: z) spread over a box of `shape`, a copy."""
+    sl = [None, None, None]
+    sl[axis] = slice(None)
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(v)[tuple(sl)], shape))
+
+
+def border_term(shape):
+    """int64 [z, y, x]: m^2 with m = the distance to the nearest voxel outside the box along the axes."""
+    nz, ny, nx = shape
+    z, y, x = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij", sparse=True)
+    m = np.minimum(np.minimum(np.minimum(x + 1, nx - x), np.minimum(y + 1, ny - y)), np.minimum(z + 1, nz - z)).astype(np.int64)
+    return m * m

@@ -1,4 +1,4 @@
-// Host side of K12 and K20 (o2v_dev_k12_components.hpp, o2v_dev_k20_geodesic.hpp): they share launch_classify, cc_words and the limits.
+// Host side of K12 and K20 (o2v_dev_k12_components.hpp, o2v_dev_k20_geodesic.hpp): they share bit_grid, launch_classify and the limits.
 
 // ---- K12: connected components and flood fill of a dense grid ---------------------------------------------------------------
 
@@ -7,15 +7,26 @@ namespace {
 constexpr uint64_t kCcMaxGrid = 1ull << 20;   // workgroups of k_cc_tiles; more tiles are taken in turns
 constexpr uint32_t kCcFlagsKnown = O2V_HIP_CC_INVERT | O2V_HIP_CC_SEED_BORDER | O2V_HIP_FLAG_STAGE_TIMES;
 
-uint64_t cc_words(const uint32_t dims[3]) { return (uint64_t) ((dims[0] + 63u) / 64u) * dims[1] * dims[2]; }
+// The bit grid (o2v_dev_bits.hpp) of a box, for every family that reads one.  words is 64-bit: the *_scratch_bytes functions ask
+// for it with dims that nothing has checked.
+BitGrid bit_grid(const uint32_t dims[3])
+{
+    const uint32_t W = (dims[0] + 63u) / 64u;
+    return BitGrid{dims[0], dims[1], dims[2], W, (uint64_t) W * dims[1] * dims[2]};
+}
+
+uint64_t cc_words(const uint32_t dims[3]) { return bit_grid(dims).words; }
+
+// its tiles of 64 x 8 x 8 voxels: along y, along z (along x: W), all of them
+uint32_t bit_tiles_y(const BitGrid &g) { return (g.ny + 7u) / 8u; }
+uint32_t bit_tiles_z(const BitGrid &g) { return (g.nz + 7u) / 8u; }
+uint64_t bit_tiles(const BitGrid &g) { return (uint64_t) g.W * bit_tiles_y(g) * bit_tiles_z(g); }
 
 // k_cc_classify on the context's stream, for K12, K13 and K14: the set (its complement inside the box if invert) as one bit per
 // voxel, words of 64 voxels along x, [z][y][W].
 void launch_classify(o2v_hip_ctx *ctx, const SetGrid &sg, uint32_t invert, unsigned long long *bits)
 {
-    const uint32_t *const dims = sg.key.dims;
-    CcGrid g{};   // (what the kernel reads of it)
-    g.nx = dims[0], g.ny = dims[1], g.nz = dims[2], g.W = (dims[0] + 63u) / 64u, g.words = cc_words(dims);
+    const BitGrid g = bit_grid(sg.key.dims);
     const RaySource src = sg.source();
     const dim3 per_group(stream_grid(ctx, (g.words + 15u) / 16u * 64u, 8u));
     hipStream_t s = ctx->stream;
@@ -47,12 +58,8 @@ int cc_run(o2v_hip_ctx *ctx, const char *fn, const void *grid, uint32_t format, 
         (rc = refuse_overlap(ctx, fn, spans, 1)))
         return rc;
 
-    CcGrid g{};
-    g.nx = dims[0], g.ny = dims[1], g.nz = dims[2];
-    g.W = (dims[0] + 63u) / 64u;
-    g.tiles_y = (dims[1] + 7u) / 8u, g.tiles_z = (dims[2] + 7u) / 8u;
-    g.conn = connectivity;
-    g.words = cc_words(dims);
+    const BitGrid bg = bit_grid(dims);
+    const CcGrid g{bg, bit_tiles_y(bg), bit_tiles_z(bg), connectivity};
     // the parents live in the caller's labels where linear index i is element i of them
     const bool in_place = labels && linear_layout(dims, out_strides);
     const uint64_t n_blocks = (g.words + kBlock - 1) / kBlock;
@@ -75,7 +82,7 @@ int cc_run(o2v_hip_ctx *ctx, const char *fn, const void *grid, uint32_t format, 
     if (sw.cc_no_tiles) {
         O2V_LAUNCH("k_cc_init", s, k_cc_init, per_word, dim3(kBlock), 0, s, g, bits, P);
     } else {
-        const uint64_t tiles = (uint64_t) g.W * g.tiles_y * g.tiles_z;
+        const uint64_t tiles = bit_tiles(g);
         O2V_LAUNCH("k_cc_tiles", s, k_cc_tiles, dim3((uint32_t) std::min<uint64_t>(tiles, kCcMaxGrid)), dim3(kBlock), 0, s, g, bits, P);
     }
     O2V_CHECK(ctx->cc_times.mark(2, s));
@@ -166,7 +173,7 @@ constexpr uint32_t kGeoFlagsKnown = O2V_HIP_CC_INVERT | O2V_HIP_CC_SEED_BORDER |
 
 static_assert(kGeoMaxDistance == O2V_HIP_GEO_MAX_DISTANCE && kGeoMaxWeight == O2V_HIP_GEO_MAX_WEIGHT, "one set of limits for the callers and the kernels");
 
-uint64_t geo_tiles(const uint32_t dims[3]) { return (uint64_t) ((dims[0] + 63u) / 64u) * ((dims[1] + 7u) / 8u) * ((dims[2] + 7u) / 8u); }
+uint64_t geo_tiles(const uint32_t dims[3]) { return bit_tiles(bit_grid(dims)); }
 
 // weights: each 0 ... 65 535, not all 0
 int geo_weights(o2v_hip_ctx *ctx, const char *fn, const uint32_t weights[3])
@@ -208,13 +215,8 @@ int o2v_hip_geodesic_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format, 
         (rc = refuse_overlap(ctx, fn, spans, 1)))
         return rc;
 
-    GeoGrid g{};
-    g.nx = dims[0], g.ny = dims[1], g.nz = dims[2];
-    g.W = (dims[0] + 63u) / 64u;
-    g.tiles_y = (dims[1] + 7u) / 8u, g.tiles_z = (dims[2] + 7u) / 8u;
-    std::copy(weights, weights + 3, g.w);
-    g.max_distance = max_distance;
-    g.words = cc_words(dims);
+    const BitGrid bg = bit_grid(dims);
+    const GeoGrid g{bg, bit_tiles_y(bg), bit_tiles_z(bg), {weights[0], weights[1], weights[2]}, max_distance};
     const uint64_t voxels = (uint64_t) dims[0] * dims[1] * dims[2], tiles = geo_tiles(dims);   // (tiles: at most the words, below 2^31)
     // the distances live in the caller's dist where linear index i is element i of it
     const bool in_place = linear_layout(dims, dist_strides);

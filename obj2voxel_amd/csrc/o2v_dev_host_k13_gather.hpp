@@ -4,7 +4,7 @@
 
 namespace {
 
-constexpr uint64_t kGaMaxWords = 0x7fffffffull;   // a word index is one uint32 in k_gather_write
+constexpr uint64_t kGaMaxWords = 0x7fffffffull;   // a word index is one uint32 in bits_word_at (o2v_dev_bits.hpp)
 constexpr uint64_t kGaMaxGrid = 1ull << 20;       // workgroups of k_gather_count; more blocks are taken in turns
 constexpr uint64_t kGaBatch = 1u << 20;           // records per batch of o2v_hip_gather_save: the batch of drain_to_sink (o2v_api.cpp)
 
@@ -13,12 +13,9 @@ int ga_grid(o2v_hip_ctx *ctx, const char *fn, const void *grid, uint32_t format,
             SetGrid *sg, GaGrid *g)
 {
     if (int rc; (rc = set_grid(ctx, fn, grid, format, strides, dims, level, sg)) || (rc = axis_limit(ctx, fn, dims))) return rc;
-    const uint64_t words = cc_words(dims);   // (below 2^43)
-    if (words > kGaMaxWords) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, std::to_string(words) + " words of 64 voxels along x (at most 2^31 - 1)");
-    g->nx = dims[0], g->ny = dims[1], g->nz = dims[2];
-    g->W = (dims[0] + 63u) / 64u;
-    g->words = words;
-    g->n_blocks = (words + kBlock - 1) / kBlock;
+    const BitGrid bg = bit_grid(dims);   // (words: below 2^43)
+    if (bg.words > kGaMaxWords) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, std::to_string(bg.words) + " words of 64 voxels along x (at most 2^31 - 1)");
+    *g = GaGrid{bg, (bg.words + kBlock - 1) / kBlock};
     return O2V_HIP_OK;
 }
 
@@ -274,12 +271,8 @@ int fa_args(o2v_hip_ctx *ctx, const char *fn, const void *grid, uint32_t format,
     if ((rc = ga_mode(ctx, fn, format, dims, no_origin, color_mode)) ||
         (rc = ga_color_source(ctx, fn, dims, color_mode, colors, color_strides, palette, cbytes)))
         return rc;
-    g->nx = gg.nx, g->ny = gg.ny, g->nz = gg.nz, g->W = gg.W;
-    g->merge = merge;
-    g->colored = merge != O2V_HIP_FACES_MERGE_NONE && color_mode != O2V_HIP_GATHER_COLOR_CONSTANT;
-    g->words = gg.words;
-    g->items = 6u * gg.words;
-    g->n_blocks = (g->items + kBlock - 1) / kBlock;
+    const uint64_t items = 6u * gg.words;
+    *g = FaGrid{gg, merge, merge != O2V_HIP_FACES_MERGE_NONE && color_mode != O2V_HIP_GATHER_COLOR_CONSTANT, items, (items + kBlock - 1) / kBlock};
     return O2V_HIP_OK;
 }
 

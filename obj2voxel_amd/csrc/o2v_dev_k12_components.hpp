@@ -1,8 +1,9 @@
 // o2v_dev_k12_components.hpp -- K12: connected components and flood fill of a dense grid (o2v_hip_components_dense /
-// o2v_hip_flood_dense).  Included from o2v_device.hip inside its anonymous namespace, after K11 (whose reader it uses).
+// o2v_hip_flood_dense).  Included from o2v_device.hip inside its anonymous namespace, after K11 (whose reader it uses) and
+// o2v_dev_bits.hpp (the bit grid, its words, tiles and walk).
 //
-// The set S (include/o2v_hip.h) is classified once into one bit per voxel, 64-bit words along x, [z][y][ceil(nx / 64)], padding
-// bits 0; every later pass reads these bits.  A voxel's linear index is i = (z * ny + y) * nx + x, below 2^31; P[i] is its
+// The set S (include/o2v_hip.h) is classified once into the bit grid of o2v_dev_bits.hpp; every later pass reads these bits.  A
+// voxel's linear index is i = (z * ny + y) * nx + x, below 2^31; P[i] is its
 // parent, P[i] <= i, a root has P[i] == i.  Hooking always puts the larger root under the smaller, so the root of a finished
 // component is its smallest linear index and the numbering of the header falls out of a prefix count over the root flags.
 //
@@ -44,11 +45,9 @@ O2V_CC_FN uint32_t cc_clz64(uint64_t v) { return (uint32_t) __clzll((long long) 
 // (Plain C++ from here to the kernels: tests/test_host_components.py compiles this part for the host, with O2V_CC_FN, cc_load,
 // cc_store, cc_min and cc_clz64 of its own, runs it tile by tile against the reference and checks that two changes are caught.)
 
-struct CcGrid {
-    uint32_t nx, ny, nz, W;      // W = ceil(nx / 64) words per row
+struct CcGrid : BitGrid {
     uint32_t tiles_y, tiles_z;   // ceil(ny / 8), ceil(nz / 8); tiles along x: W
     uint32_t conn;               // 6, 18 or 26
-    uint64_t words;              // W * ny * nz
 };
 
 struct CcRow {
@@ -182,7 +181,7 @@ O2V_CC_FN CcRow cc_grid_row(const CcGrid &g, const uint64_t *bits, uint32_t wx, 
 {
     CcRow r = {0ull, 0u, 0u};
     if ((uint32_t) y >= g.ny || (uint32_t) z >= g.nz) return r;
-    const uint64_t *row = bits + ((uint64_t) z * g.ny + (uint32_t) y) * g.W;
+    const uint64_t *row = bits + bits_word_index(g, 0u, (uint32_t) y, (uint32_t) z);
     r.w = row[wx];
     r.lo = wx > 0u ? (uint32_t) (row[wx - 1u] >> 63) : 0u;
     r.hi = wx + 1u < g.W ? (uint32_t) (row[wx + 1u] & 1ull) : 0u;
@@ -229,15 +228,6 @@ O2V_CC_FN CcCount cc_seam(const CcGrid &g, const uint64_t *bits, uint32_t *P, ui
 // ---- kernels -----------------------------------------------------------------------------------------------------------------
 #ifndef O2V_CC_HOST
 
-// word wi -> (wx, y, z)
-__device__ __forceinline__ void cc_word_at(const CcGrid &g, uint64_t wi, uint32_t &wx, uint32_t &y, uint32_t &z)
-{
-    const uint64_t row = wi / g.W;
-    wx = (uint32_t) (wi - row * g.W);
-    z = (uint32_t) (row / g.ny);
-    y = (uint32_t) (row - (uint64_t) z * g.ny);
-}
-
 // the word of the root r and the bit below which its rank within the word is counted
 __device__ __forceinline__ uint64_t cc_root_word(const CcGrid &g, uint32_t r, uint32_t &bit)
 {
@@ -247,21 +237,18 @@ __device__ __forceinline__ uint64_t cc_root_word(const CcGrid &g, uint32_t r, ui
 }
 
 template <uint32_t Format, bool Vec>
-__global__ __launch_bounds__(kBlock) void k_cc_classify(RaySource src, CcGrid g, uint32_t invert, unsigned long long *__restrict__ bits)
+__global__ __launch_bounds__(kBlock) void k_cc_classify(RaySource src, BitGrid g, uint32_t invert, unsigned long long *__restrict__ bits)
 {
     const uint32_t lane = threadIdx.x & 63u, q = lane & 3u, j = lane >> 2;
-    const uint64_t wave = (uint64_t) blockIdx.x * (kBlock / 64u) + (threadIdx.x >> 6), n_waves = (uint64_t) gridDim.x * (kBlock / 64u);
-    const uint64_t groups = (g.words + 15u) / 16u;   // a wavefront takes 16 words
-    for (uint64_t grp = wave; grp < groups; grp += n_waves) {
+    for (const uint64_t grp : WaveTurns{(g.words + 15u) / 16u}) {   // a wavefront takes 16 words
         const uint64_t wi = grp * 16u + j;
         uint32_t b = 0;
         if (wi < g.words) {
-            uint32_t wx, y, z;
-            cc_word_at(g, wi, wx, y, z);
-            const uint32_t x0 = wx * 64u + q * 16u;
+            const BitWord at = bits_word_at(g, wi);
+            const uint32_t x0 = at.wx * 64u + q * 16u;
             if (x0 < g.nx) {
                 const uint32_t n = min(16u, g.nx - x0);
-                b = ray_read16<Format, Vec>(src, (uint64_t) y * src.s1 + (uint64_t) z * src.s2, x0, n);
+                b = ray_read16<Format, Vec>(src, (uint64_t) at.y * src.s1 + (uint64_t) at.z * src.s2, x0, n);
                 if (invert) b = ~b & ((1u << n) - 1u);
             }
         }
@@ -278,17 +265,13 @@ __global__ __launch_bounds__(kBlock) void k_cc_tiles(CcGrid g, const unsigned lo
     __shared__ uint32_t s_lab[kCcTileVoxels];
     __shared__ uint32_t s_any;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t tiles = (uint64_t) g.W * g.tiles_y * g.tiles_z;
-    for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const uint64_t trow = tile / g.W;
-        const uint32_t tx = (uint32_t) (tile - trow * g.W), tz = (uint32_t) (trow / g.tiles_y), ty = (uint32_t) (trow - (uint64_t) tz * g.tiles_y);
-        const uint32_t x0 = tx * 64u, y0 = ty * 8u, z0 = tz * 8u;
+    const uint32_t tiles = g.W * g.tiles_y * g.tiles_z;   // (no more than the words)
+    for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        uint32_t tx, ty, tz;
+        bits_tile_at(g, g.tiles_y, tile, tx, ty, tz);
         __syncthreads();   // (the last tile's words and labels are no longer read)
-        uint64_t w = 0;
         if (threadIdx.x < kCcTileRows) {
-            const uint32_t y = y0 + (threadIdx.x & 7u), z = z0 + (threadIdx.x >> 3);
-            if (y < g.ny && z < g.nz) w = bits[((uint64_t) z * g.ny + y) * g.W + tx];
-            s_w[threadIdx.x] = w;
+            const uint64_t w = s_w[threadIdx.x] = bits_tile_word(g, bits, tx, ty, tz, threadIdx.x);
             const unsigned long long any = __ballot(w != 0ull);   // (the 64 rows are the first wavefront's lanes)
             if (threadIdx.x == 0) s_any = any != 0ull;
         }
@@ -298,7 +281,7 @@ __global__ __launch_bounds__(kBlock) void k_cc_tiles(CcGrid g, const unsigned lo
         __syncthreads();
         for (uint32_t row = wave; row < kCcTileRows; row += kBlock / 64u) cc_tile_merge(g.conn, s_w, s_lab, row, lane);
         __syncthreads();
-        for (uint32_t row = wave; row < kCcTileRows; row += kBlock / 64u) cc_tile_out(g, s_w, s_lab, P, x0, y0, z0, row, lane);
+        for (uint32_t row = wave; row < kCcTileRows; row += kBlock / 64u) cc_tile_out(g, s_w, s_lab, P, tx * 64u, ty * 8u, tz * 8u, row, lane);
     }
 }
 
@@ -306,12 +289,10 @@ __global__ __launch_bounds__(kBlock) void k_cc_tiles(CcGrid g, const unsigned lo
 __global__ __launch_bounds__(kBlock) void k_cc_init(CcGrid g, const unsigned long long *__restrict__ bits, uint32_t *__restrict__ P)
 {
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t wave = (uint64_t) blockIdx.x * (kBlock / 64u) + (threadIdx.x >> 6), n_waves = (uint64_t) gridDim.x * (kBlock / 64u);
-    for (uint64_t wi = wave; wi < g.words; wi += n_waves) {
-        uint32_t wx, y, z;
-        cc_word_at(g, wi, wx, y, z);
+    for (const uint64_t wi : bits_words(g)) {
+        const BitWord at = bits_word_at(g, wi);
         if ((bits[wi] >> lane) & 1ull) {
-            const uint32_t i = cc_index(g, wx * 64u + lane, y, z);
+            const uint32_t i = cc_index(g, at.wx * 64u + lane, at.y, at.z);
             P[i] = i;
         }
     }
@@ -322,13 +303,11 @@ template <bool All, bool Count>
 __global__ __launch_bounds__(kBlock) void k_cc_seams(CcGrid g, const unsigned long long *bits, uint32_t *P, unsigned long long *ctr)
 {
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t wave = (uint64_t) blockIdx.x * (kBlock / 64u) + (threadIdx.x >> 6), n_waves = (uint64_t) gridDim.x * (kBlock / 64u);
     uint32_t unions = 0, retries = 0;
-    for (uint64_t wi = wave; wi < g.words; wi += n_waves) {
+    for (const uint64_t wi : bits_words(g)) {
         if (bits[wi] == 0ull) continue;
-        uint32_t wx, y, z;
-        cc_word_at(g, wi, wx, y, z);
-        const CcCount n = cc_seam<All>(g, reinterpret_cast<const uint64_t *>(bits), P, wx, y, z, lane);
+        const BitWord at = bits_word_at(g, wi);
+        const CcCount n = cc_seam<All>(g, reinterpret_cast<const uint64_t *>(bits), P, at.wx, at.y, at.z, lane);
         unions += n.unions, retries += n.retries;
     }
     if (Count) {
@@ -342,14 +321,12 @@ __global__ __launch_bounds__(kBlock) void k_cc_seams(CcGrid g, const unsigned lo
 __global__ __launch_bounds__(kBlock) void k_cc_flatten(CcGrid g, const unsigned long long *__restrict__ bits, uint32_t *P, unsigned long long *__restrict__ roots)
 {
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t wave = (uint64_t) blockIdx.x * (kBlock / 64u) + (threadIdx.x >> 6), n_waves = (uint64_t) gridDim.x * (kBlock / 64u);
-    for (uint64_t wi = wave; wi < g.words; wi += n_waves) {
+    for (const uint64_t wi : bits_words(g)) {
         const unsigned long long w = bits[wi];
         bool is_root = false;
         if ((w >> lane) & 1ull) {
-            uint32_t wx, y, z;
-            cc_word_at(g, wi, wx, y, z);
-            const uint32_t i = cc_index(g, wx * 64u + lane, y, z), r = cc_root(P, i);
+            const BitWord at = bits_word_at(g, wi);
+            const uint32_t i = cc_index(g, at.wx * 64u + lane, at.y, at.z), r = cc_root(P, i);
             if (r != i) cc_store(P + i, r);
             is_root = r == i;
         }
@@ -379,11 +356,9 @@ __global__ __launch_bounds__(kBlock) void k_cc_labels(CcGrid g, const unsigned l
                                                       uint64_t s2)
 {
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t wave = (uint64_t) blockIdx.x * (kBlock / 64u) + (threadIdx.x >> 6), n_waves = (uint64_t) gridDim.x * (kBlock / 64u);
-    for (uint64_t wi = wave; wi < g.words; wi += n_waves) {
-        uint32_t wx, y, z;
-        cc_word_at(g, wi, wx, y, z);
-        const uint32_t x = wx * 64u + lane;
+    for (const uint64_t wi : bits_words(g)) {
+        const BitWord at = bits_word_at(g, wi);
+        const uint32_t x = at.wx * 64u + lane, y = at.y, z = at.z;
         if (x >= g.nx) continue;
         int32_t label = 0;
         if ((bits[wi] >> lane) & 1ull) {
@@ -409,7 +384,7 @@ __global__ __launch_bounds__(kBlock) void k_cc_seed_list(CcGrid g, const unsigne
     for (uint64_t s = (uint64_t) blockIdx.x * kBlock + threadIdx.x; s < n; s += (uint64_t) gridDim.x * kBlock) {
         const int32_t x = seeds[s * 3u], y = seeds[s * 3u + 1u], z = seeds[s * 3u + 2u];
         if ((uint32_t) x >= g.nx || (uint32_t) y >= g.ny || (uint32_t) z >= g.nz) continue;
-        if (!((bits[((uint64_t) z * g.ny + (uint32_t) y) * g.W + ((uint32_t) x >> 6)] >> (x & 63)) & 1ull)) continue;
+        if (!bits_has(g, bits, (uint32_t) x, (uint32_t) y, (uint32_t) z)) continue;
         cc_flag_root(g, P[cc_index(g, (uint32_t) x, (uint32_t) y, (uint32_t) z)], flags);
     }
 }
@@ -419,13 +394,10 @@ __global__ __launch_bounds__(kBlock) void k_cc_seed_border(CcGrid g, const unsig
                                                            unsigned long long *flags)
 {
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t wave = (uint64_t) blockIdx.x * (kBlock / 64u) + (threadIdx.x >> 6), n_waves = (uint64_t) gridDim.x * (kBlock / 64u);
-    for (uint64_t wi = wave; wi < g.words; wi += n_waves) {
-        uint32_t wx, y, z;
-        cc_word_at(g, wi, wx, y, z);
-        const uint32_t x = wx * 64u + lane;
-        const bool face = y == 0u || y == g.ny - 1u || z == 0u || z == g.nz - 1u || x == 0u || x == g.nx - 1u;
-        if (face && x < g.nx && ((bits[wi] >> lane) & 1ull)) cc_flag_root(g, P[cc_index(g, x, y, z)], flags);
+    for (const uint64_t wi : bits_words(g)) {
+        const BitWord at = bits_word_at(g, wi);
+        const uint32_t x = at.wx * 64u + lane, y = at.y, z = at.z;
+        if (bits_on_face(g, x, y, z) && x < g.nx && ((bits[wi] >> lane) & 1ull)) cc_flag_root(g, P[cc_index(g, x, y, z)], flags);
     }
 }
 
@@ -434,14 +406,11 @@ __global__ __launch_bounds__(kBlock) void k_cc_flood_out(CcGrid g, const unsigne
                                                          const unsigned long long *__restrict__ flags, uint32_t v0, uint32_t v1, uint32_t v2,
                                                          uint8_t *__restrict__ out, uint64_t s0, uint64_t s1, uint64_t s2, unsigned long long *reached)
 {
-    __shared__ unsigned long long s_sum[kBlock / 64];
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t wave = (uint64_t) blockIdx.x * (kBlock / 64u) + (threadIdx.x >> 6), n_waves = (uint64_t) gridDim.x * (kBlock / 64u);
     unsigned long long mine = 0;   // (the same in every lane of the wavefront)
-    for (uint64_t wi = wave; wi < g.words; wi += n_waves) {
-        uint32_t wx, y, z;
-        cc_word_at(g, wi, wx, y, z);
-        const uint32_t x = wx * 64u + lane;
+    for (const uint64_t wi : bits_words(g)) {
+        const BitWord at = bits_word_at(g, wi);
+        const uint32_t x = at.wx * 64u + lane, y = at.y, z = at.z;
         bool hit = false;
         uint32_t v = v2;
         if (x < g.nx && ((bits[wi] >> lane) & 1ull)) {
@@ -453,13 +422,7 @@ __global__ __launch_bounds__(kBlock) void k_cc_flood_out(CcGrid g, const unsigne
         if (x < g.nx) out[(uint64_t) x * s0 + (uint64_t) y * s1 + (uint64_t) z * s2] = (uint8_t) v;
         mine += (unsigned long long) __popcll(__ballot(hit));
     }
-    if (lane == 0u) s_sum[threadIdx.x >> 6] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long sum = 0;
-        for (uint32_t w = 0; w < kBlock / 64u; ++w) sum += s_sum[w];
-        if (sum) atomicAdd(reached, sum);
-    }
+    bits_add_wave_sums(mine, reached);
 }
 
 #endif   // O2V_CC_HOST

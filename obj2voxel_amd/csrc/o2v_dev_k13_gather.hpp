@@ -1,8 +1,9 @@
 // o2v_dev_k13_gather.hpp -- K13: the solid voxels of a dense grid as (x, y, z, argb) records (o2v_hip_gather_count / _write /
-// _save).  Included from o2v_device.hip inside its anonymous namespace, after K12 (whose classify kernel and word layout it uses).
+// _save).  Included from o2v_device.hip inside its anonymous namespace, after K12 (whose classify kernel it uses) and
+// o2v_dev_bits.hpp (the bit grid and its words).
 //
-// The set (include/o2v_hip.h) is classified once into one bit per voxel by K12's k_cc_classify (invert = 0): 64-bit words along
-// x, [z][y][W = ceil(nx / 64)], padding bits 0.  Word wi holds the voxels of linear indices (wi / W) * nx + (wi % W) * 64 + bit,
+// The set (include/o2v_hip.h) is classified once into the bit grid of o2v_dev_bits.hpp by K12's k_cc_classify (invert = 0).  Word
+// wi holds the voxels of linear indices (wi / W) * nx + (wi % W) * 64 + bit,
 // so the set bits in ascending (word, bit) order are the solid voxels in ascending linear index: record i is the i-th set bit.
 //
 //   k_cc_classify (K12)                    the only pass over the grid.
@@ -78,10 +79,8 @@ O2V_GA_FN uint32_t ga_select(uint64_t m, uint32_t r)
 // ---- kernels -----------------------------------------------------------------------------------------------------------------
 #ifndef O2V_GA_HOST
 
-struct GaGrid {
-    uint32_t nx, ny, nz, W;   // W = ceil(nx / 64) words per row
-    uint64_t words;           // W * ny * nz, at most 2^31 - 1
-    uint64_t n_blocks;        // of kBlock words
+struct GaGrid : BitGrid {   // (words: at most 2^31 - 1)
+    uint64_t n_blocks;      // of kBlock words
 };
 
 struct GaColor {
@@ -92,6 +91,15 @@ struct GaColor {
     uint64_t s0, s1, s2;
     const uint32_t *palette;
 };
+
+// the colour of voxel (x, y, z); s_pal: the palette in LDS (PALETTE)
+template <uint32_t Mode>
+__device__ __forceinline__ uint32_t ga_color_at(const GaColor &col, const uint32_t *s_pal, uint32_t x, uint32_t y, uint32_t z)
+{
+    if (Mode == kGaColorGrid) return col.colors[(uint64_t) x * col.c0 + (uint64_t) y * col.c1 + (uint64_t) z * col.c2];
+    if (Mode == kGaColorPalette) return s_pal[col.grid[(uint64_t) x * col.s0 + (uint64_t) y * col.s1 + (uint64_t) z * col.s2]];
+    return col.argb;
+}
 
 // local[wi] = the records of the words of wi's block before wi; block_sums[block] = the block's records
 __global__ __launch_bounds__(kBlock) void k_gather_count(const unsigned long long *__restrict__ bits, GaGrid g, uint32_t *__restrict__ local,
@@ -139,8 +147,8 @@ __global__ __launch_bounds__(kBlock) void k_gather_write(GaGrid g, const unsigne
     __shared__ uint64_t s_word[kBlock];
     __shared__ uint32_t s_x0[kBlock], s_yz[kBlock];   // the word's first x; y | z << 16 (both below 2^16)
     __shared__ uint32_t s_pal[Mode == kGaColorPalette ? 256 : 1];
-    static_assert(kBlock == 256u, "a thread per palette entry, a lane per word of a block");
-    if (Mode == kGaColorPalette) s_pal[threadIdx.x] = col.palette[threadIdx.x];   // (kBlock == 256; the first barrier below publishes it)
+    static_assert(kBlock == 256u, "a lane per word of a block");
+    bits_palette_to_lds<Mode == kGaColorPalette>(col.palette, s_pal, false);   // (the first barrier below publishes it)
     const uint64_t end = first + n;
     for (uint64_t b = *b_first + blockIdx.x; b < g.n_blocks; b += gridDim.x) {
         const uint64_t base = boff[b];
@@ -156,19 +164,16 @@ __global__ __launch_bounds__(kBlock) void k_gather_write(GaGrid g, const unsigne
             const bool in = wi < g.words;
             s_pref[threadIdx.x] = in ? local[wi] : cnt;   // (past the grid: no slot is below cnt)
             s_word[threadIdx.x] = in ? bits[wi] : 0ull;
-            const uint32_t w32 = (uint32_t) wi, row = w32 / g.W, z = row / g.ny;
-            s_x0[threadIdx.x] = (w32 - row * g.W) * 64u;
-            s_yz[threadIdx.x] = (row - z * g.ny) | z << 16;
+            const BitWord at = bits_word_at(g, wi);   // (past the grid: coordinates that no slot reads)
+            s_x0[threadIdx.x] = at.wx * 64u;
+            s_yz[threadIdx.x] = at.y | at.z << 16;
         }
         __syncthreads();
         for (uint32_t slot = slot_lo + threadIdx.x; slot < slot_hi; slot += kBlock) {
             const uint32_t l = ga_find_word(s_pref, slot);
             const uint32_t x = s_x0[l] + ga_select(s_word[l], slot - s_pref[l]);
             const uint32_t yz = s_yz[l], y = yz & 0xffffu, z = yz >> 16;
-            uint32_t argb = col.argb;
-            if (Mode == kGaColorGrid) argb = col.colors[(uint64_t) x * col.c0 + (uint64_t) y * col.c1 + (uint64_t) z * col.c2];
-            if (Mode == kGaColorPalette) argb = s_pal[col.grid[(uint64_t) x * col.s0 + (uint64_t) y * col.s1 + (uint64_t) z * col.s2]];
-            records[base + slot - first] = make_uint4(ox + x, oy + y, oz + z, argb);
+            records[base + slot - first] = make_uint4(ox + x, oy + y, oz + z, ga_color_at<Mode>(col, s_pal, x, y, z));
         }
     }
 }

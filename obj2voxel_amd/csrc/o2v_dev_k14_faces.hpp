@@ -1,9 +1,9 @@
 // o2v_dev_k14_faces.hpp -- K14: the exposed voxel faces of a dense grid as coloured quads (o2v_hip_faces_count / _write).
 // Included from o2v_device.hip inside its anonymous namespace, after K13 (whose slot -> word -> bit mapping and colour modes it
-// uses; the classify kernel and the word layout are K12's, the scans K6's).
+// uses; the classify kernel is K12's, the bit grid, its words and walk o2v_dev_bits.hpp's, the scans K6's).
 //
-// The set is classified once into one bit per voxel: 64-bit words along x, [z][y][W = ceil(nx / 64)], padding bits 0, so that
-// "outside the box is empty" needs no mask.  With a colour grid or a palette and MERGE_RUNS two more words per solid word say
+// The set is classified once into the bit grid of o2v_dev_bits.hpp; its padding bits are 0, so that "outside the box is empty"
+// needs no mask.  With a colour grid or a palette and MERGE_RUNS two more words per solid word say
 // where a voxel has the colour of the voxel at x - 1 and at y - 1.  Everything after that works on those words alone.
 //
 // An item is (row, direction, word): item = ((z * ny + y) * 6 + d) * W + wx.  The start mask of an item - the exposed faces of
@@ -30,16 +30,14 @@ O2V_FA_FN uint32_t fa_ctz64(uint64_t v) { return (uint32_t) __builtin_ctzll(v); 
 #endif
 
 // ---- words -> exposed faces -> starts of quads -> run lengths -> corners --------------------------------------------------------
-// (Plain C++ from here to the kernels: tests/test_host_faces.py compiles this part for the host, with O2V_FA_FN and fa_ctz64 of
-// its own, and runs it against the reference.)
+// (Plain C++ from here to the kernels: tests/test_host_faces.py compiles this part for the host behind the plain part of
+// o2v_dev_bits.hpp, with O2V_FA_FN and fa_ctz64 of its own, and runs it against the reference.)
 
-struct FaGrid {
-    uint32_t nx, ny, nz, W;   // W = ceil(nx / 64) words per row
-    uint32_t merge;           // kFaMergeNone / kFaMergeRuns
-    uint32_t colored;         // same_x / same_y exist (GRID or PALETTE with MERGE_RUNS); else all voxels are of one colour
-    uint64_t words;           // W * ny * nz, at most 2^31 - 1
-    uint64_t items;           // 6 * words
-    uint64_t n_blocks;        // of kBlock items
+struct FaGrid : BitGrid {   // (words: at most 2^31 - 1)
+    uint32_t merge;         // kFaMergeNone / kFaMergeRuns
+    uint32_t colored;       // same_x / same_y exist (GRID or PALETTE with MERGE_RUNS); else all voxels are of one colour
+    uint64_t items;         // 6 * words
+    uint64_t n_blocks;      // of kBlock items
 };
 
 struct FaBits {
@@ -137,12 +135,12 @@ O2V_FA_FN void fa_item_at(const FaGrid &g, uint64_t item, uint32_t &d, uint32_t 
 O2V_FA_FN uint32_t fa_pick(uint32_t axis, uint32_t vx, uint32_t vy, uint32_t vz) { return axis == 0u ? vx : axis == 1u ? vy : vz; }
 
 // The four corners (x, y, z each) of the quad of direction d over the `len` faces from lattice voxel (x, y, z) (the origin
-// included) along its run axis: in the plane a = voxel[a] + s, spanning [u0, u1] x [v0, v1] with (u, v) the axes after a in
+// included) along its run axis and `height` rows along its stack axis (K16: y for d = 4, 5, else z; 1 for a run): in the plane a = voxel[a] + s, spanning [u0, u1] x [v0, v1] with (u, v) the axes after a in
 // cyclic order, as (u0, v0), (u1, v0), (u1, v1), (u0, v1) for s = 1 and (u0, v0), (u0, v1), (u1, v1), (u1, v0) for s = 0.
-O2V_FA_FN void fa_quad(uint32_t d, uint32_t x, uint32_t y, uint32_t z, uint32_t len, float out[12])
+O2V_FA_FN void fa_quad(uint32_t d, uint32_t x, uint32_t y, uint32_t z, uint32_t len, uint32_t height, float out[12])
 {
     const uint32_t a = d >> 1, s = d & 1u, u = a == 2u ? 0u : a + 1u, v = u == 2u ? 0u : u + 1u;
-    const uint32_t hx = x + (d >= 2u ? len : 1u), hy = y + (d < 2u ? len : 1u), hz = z + 1u;
+    const uint32_t hx = x + (d >= 2u ? len : 1u), hy = y + (d < 2u ? len : d >= 4u ? height : 1u), hz = z + (d < 4u ? height : 1u);
     const uint32_t plane = fa_pick(a, x, y, z) + s;
     const uint32_t u0 = fa_pick(u, x, y, z), u1 = fa_pick(u, hx, hy, hz), v0 = fa_pick(v, x, y, z), v1 = fa_pick(v, hx, hy, hz);
 #pragma unroll
@@ -158,14 +156,6 @@ O2V_FA_FN void fa_quad(uint32_t d, uint32_t x, uint32_t y, uint32_t z, uint32_t 
 // ---- kernels -----------------------------------------------------------------------------------------------------------------
 #ifndef O2V_FA_HOST
 
-template <uint32_t Mode>
-__device__ __forceinline__ uint32_t fa_color(const GaColor &col, const uint32_t *s_pal, uint32_t x, uint32_t y, uint32_t z)
-{
-    if (Mode == kGaColorGrid) return col.colors[(uint64_t) x * col.c0 + (uint64_t) y * col.c1 + (uint64_t) z * col.c2];
-    if (Mode == kGaColorPalette) return s_pal[col.grid[(uint64_t) x * col.s0 + (uint64_t) y * col.s1 + (uint64_t) z * col.s2]];
-    return col.argb;
-}
-
 // same_x[wi] bit x: voxels x and x - 1 of the row are solid and of one colour; same_y[wi]: the same with the voxel at y - 1.
 // (Only solid voxels are read: the bits are looked at only where both faces are exposed.)
 template <uint32_t Mode>
@@ -173,27 +163,22 @@ __global__ __launch_bounds__(kBlock) void k_faces_same(FaGrid g, const unsigned 
                                                        unsigned long long *__restrict__ same_x, unsigned long long *__restrict__ same_y)
 {
     __shared__ uint32_t s_pal[Mode == kGaColorPalette ? 256 : 1];
-    static_assert(kBlock == 256u, "a thread per palette entry");
-    if (Mode == kGaColorPalette) {
-        s_pal[threadIdx.x] = col.palette[threadIdx.x];
-        __syncthreads();
-    }
+    bits_palette_to_lds<Mode == kGaColorPalette>(col.palette, s_pal, true);
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t wave = (uint64_t) blockIdx.x * (kBlock / 64u) + (threadIdx.x >> 6), n_waves = (uint64_t) gridDim.x * (kBlock / 64u);
-    for (uint64_t wi = wave; wi < g.words; wi += n_waves) {   // (uniform over the wavefront)
+    for (const uint64_t wi : bits_words(g)) {
         const uint64_t s = solid[wi];
         unsigned long long mx = 0, my = 0;
         if (s) {
-            const uint32_t w32 = (uint32_t) wi, row = w32 / g.W, wx = w32 - row * g.W, z = row / g.ny, y = row - z * g.ny;
-            const uint32_t x = wx * 64u + lane;   // (a solid bit is inside the box: the padding bits are 0)
+            const BitWord at = bits_word_at(g, wi);
+            const uint32_t wx = at.wx, x = wx * 64u + lane, y = at.y, z = at.z;   // (a solid bit is inside the box: the padding bits are 0)
             const uint64_t below = y ? solid[wi - g.W] : 0ull;
             const uint64_t left = s << 1 | (wx ? solid[wi - 1u] >> 63 : 0ull);
             const bool me = s >> lane & 1u;
-            const uint32_t c = me ? fa_color<Mode>(col, s_pal, x, y, z) : 0u;
+            const uint32_t c = me ? ga_color_at<Mode>(col, s_pal, x, y, z) : 0u;
             uint32_t cl = __shfl_up(c, 1);
-            if (lane == 0u && (s & left & 1u)) cl = fa_color<Mode>(col, s_pal, x - 1u, y, z);
+            if (lane == 0u && (s & left & 1u)) cl = ga_color_at<Mode>(col, s_pal, x - 1u, y, z);
             const bool both_y = (s & below) >> lane & 1u;
-            const uint32_t cb = both_y ? fa_color<Mode>(col, s_pal, x, y - 1u, z) : 0u;
+            const uint32_t cb = both_y ? ga_color_at<Mode>(col, s_pal, x, y - 1u, z) : 0u;
             mx = __ballot(((s & left) >> lane & 1u) && c == cl);
             my = __ballot(both_y && c == cb);
         }
@@ -201,8 +186,10 @@ __global__ __launch_bounds__(kBlock) void k_faces_same(FaGrid g, const unsigned 
     }
 }
 
-// block_sums[block] = the quads that begin in the block's items
-__global__ __launch_bounds__(kBlock) void k_faces_count(FaGrid g, FaBits b, unsigned long long *__restrict__ block_sums)
+// The count of K14 and K16, a lane per item: block_sums[block] = the set bits of the start masks of the block's items.
+// starts(item, d, wx, y, z): the start mask of an item below g.items.
+template <class Starts>
+__device__ __forceinline__ void fa_count_blocks(const FaGrid &g, unsigned long long *__restrict__ block_sums, Starts starts)
 {
     __shared__ uint64_t s_wave[kBlock / 64];
     for (uint64_t blk = blockIdx.x; blk < g.n_blocks; blk += gridDim.x) {
@@ -211,7 +198,7 @@ __global__ __launch_bounds__(kBlock) void k_faces_count(FaGrid g, FaBits b, unsi
         if (item < g.items) {
             uint32_t d, wx, y, z;
             fa_item_at(g, item, d, wx, y, z);
-            n = (uint64_t) __popcll(fa_starts(b, g, d, wx, y, z));
+            n = (uint64_t) __popcll(starts(item, d, wx, y, z));
         }
         uint64_t total;
         (void) fill_block_exscan64(n, s_wave, total);
@@ -219,18 +206,44 @@ __global__ __launch_bounds__(kBlock) void k_faces_count(FaGrid g, FaBits b, unsi
     }
 }
 
-// quad q of the numbering -> positions[12 q ..], faces[6 q ..] (if not null), quad_argb[q] (if not null)
-template <uint32_t Mode>
-__global__ __launch_bounds__(kBlock) void k_faces_write(FaGrid g, FaBits b, const unsigned long long *__restrict__ boff, uint32_t ox, uint32_t oy,
-                                                        uint32_t oz, GaColor col, float4 *__restrict__ positions, int2 *__restrict__ faces,
-                                                        uint32_t *__restrict__ quad_argb)
+// block_sums[block] = the quads that begin in the block's items
+__global__ __launch_bounds__(kBlock) void k_faces_count(FaGrid g, FaBits b, unsigned long long *__restrict__ block_sums)
+{
+    fa_count_blocks(g, block_sums, [&](uint64_t, uint32_t d, uint32_t wx, uint32_t y, uint32_t z) { return fa_starts(b, g, d, wx, y, z); });
+}
+
+// quad q: its corners p, its two triangles over the vertices 4 q .. 4 q + 3 (if faces is not null; 4 q + 3 is below 2^31: the
+// host refuses more), its colour (if quad_argb is not null)
+__device__ __forceinline__ void fa_store_quad(uint64_t q, const float p[12], uint32_t argb, float4 *__restrict__ positions, int2 *__restrict__ faces,
+                                              uint32_t *__restrict__ quad_argb)
+{
+    positions[3u * q] = make_float4(p[0], p[1], p[2], p[3]);
+    positions[3u * q + 1u] = make_float4(p[4], p[5], p[6], p[7]);
+    positions[3u * q + 2u] = make_float4(p[8], p[9], p[10], p[11]);
+    if (faces) {
+        const int32_t v = (int32_t) (4u * q);
+        faces[3u * q] = make_int2(v, v + 1);
+        faces[3u * q + 1u] = make_int2(v + 2, v);
+        faces[3u * q + 2u] = make_int2(v + 2, v + 3);
+    }
+    if (quad_argb) quad_argb[q] = argb;
+}
+
+// The write of K14 and K16, a workgroup per block of items in turns: the start masks again and their exclusive scan into LDS,
+// then a lane per quad: slot -> item (ga_find_word) -> bit (ga_select) -> extents -> fa_store_quad.  starts: as the count took
+// it; extents(d, wx, y, z, bit, len, height): the faces along the run axis and the rows along the stack axis of the quad that
+// begins at `bit` of item (d, wx, y, z).
+template <uint32_t Mode, class Starts, class Extents>
+__device__ __forceinline__ void fa_write_blocks(const FaGrid &g, const unsigned long long *__restrict__ boff, uint32_t ox, uint32_t oy, uint32_t oz,
+                                                const GaColor &col, float4 *__restrict__ positions, int2 *__restrict__ faces,
+                                                uint32_t *__restrict__ quad_argb, Starts starts, Extents extents)
 {
     __shared__ uint32_t s_pref[kBlock];
     __shared__ uint64_t s_start[kBlock];
     __shared__ uint64_t s_wave[kBlock / 64];
     __shared__ uint32_t s_pal[Mode == kGaColorPalette ? 256 : 1];
-    static_assert(kBlock == 256u, "a thread per palette entry, a lane per item of a block, ga_find_word over 256 prefixes");
-    if (Mode == kGaColorPalette) s_pal[threadIdx.x] = col.palette[threadIdx.x];   // (the first barrier below publishes it)
+    static_assert(kBlock == 256u, "a lane per item of a block, ga_find_word over 256 prefixes");
+    bits_palette_to_lds<Mode == kGaColorPalette>(col.palette, s_pal, false);   // (the first barrier below publishes it)
     for (uint64_t blk = blockIdx.x; blk < g.n_blocks; blk += gridDim.x) {
         const uint64_t base = boff[blk];
         const uint32_t cnt = (uint32_t) (boff[blk + 1] - base);   // at most 2^14
@@ -242,7 +255,7 @@ __global__ __launch_bounds__(kBlock) void k_faces_write(FaGrid g, FaBits b, cons
             if (item < g.items) {
                 uint32_t d, wx, y, z;
                 fa_item_at(g, item, d, wx, y, z);
-                start = fa_starts(b, g, d, wx, y, z);
+                start = starts(item, d, wx, y, z);
             }
             uint64_t total;
             s_pref[threadIdx.x] = (uint32_t) fill_block_exscan64((uint64_t) __popcll(start), s_wave, total);   // (past the items: the block's count)
@@ -252,25 +265,30 @@ __global__ __launch_bounds__(kBlock) void k_faces_write(FaGrid g, FaBits b, cons
         for (uint32_t slot = threadIdx.x; slot < cnt; slot += kBlock) {
             const uint32_t l = ga_find_word(s_pref, slot);
             const uint32_t bit = ga_select(s_start[l], slot - s_pref[l]);
-            uint32_t d, wx, y, z;
+            uint32_t d, wx, y, z, len, height;
             fa_item_at(g, blk * kBlock + l, d, wx, y, z);
+            extents(d, wx, y, z, bit, len, height);
             const uint32_t x = wx * 64u + bit;
-            const uint32_t len = fa_run_length(b, g, d, wx, y, z, bit);
-            const uint64_t q = base + slot;   // (4 q + 3 is below 2^31: the host refuses more)
             float p[12];
-            fa_quad(d, ox + x, oy + y, oz + z, len, p);
-            positions[3u * q] = make_float4(p[0], p[1], p[2], p[3]);
-            positions[3u * q + 1u] = make_float4(p[4], p[5], p[6], p[7]);
-            positions[3u * q + 2u] = make_float4(p[8], p[9], p[10], p[11]);
-            if (faces) {
-                const int32_t v = (int32_t) (4u * q);
-                faces[3u * q] = make_int2(v, v + 1);
-                faces[3u * q + 1u] = make_int2(v + 2, v);
-                faces[3u * q + 2u] = make_int2(v + 2, v + 3);
-            }
-            if (quad_argb) quad_argb[q] = fa_color<Mode>(col, s_pal, x, y, z);
+            fa_quad(d, ox + x, oy + y, oz + z, len, height, p);
+            fa_store_quad(base + slot, p, quad_argb ? ga_color_at<Mode>(col, s_pal, x, y, z) : 0u, positions, faces, quad_argb);
         }
     }
+}
+
+// quad q of the numbering -> positions[12 q ..], faces[6 q ..] (if not null), quad_argb[q] (if not null): the start masks
+// computed again (words from L2), a run's length by walking the continuation bits
+template <uint32_t Mode>
+__global__ __launch_bounds__(kBlock) void k_faces_write(FaGrid g, FaBits b, const unsigned long long *__restrict__ boff, uint32_t ox, uint32_t oy,
+                                                        uint32_t oz, GaColor col, float4 *__restrict__ positions, int2 *__restrict__ faces,
+                                                        uint32_t *__restrict__ quad_argb)
+{
+    fa_write_blocks<Mode>(
+        g, boff, ox, oy, oz, col, positions, faces, quad_argb,
+        [&](uint64_t, uint32_t d, uint32_t wx, uint32_t y, uint32_t z) { return fa_starts(b, g, d, wx, y, z); },
+        [&](uint32_t d, uint32_t wx, uint32_t y, uint32_t z, uint32_t bit, uint32_t &len, uint32_t &height) {
+            len = fa_run_length(b, g, d, wx, y, z, bit), height = 1u;
+        });
 }
 
 #endif   // O2V_FA_HOST

@@ -13,11 +13,11 @@
 //                         rectangle-start mask kept in rstarts[item], its popcount summed over the block -> boff[block].
 //   k_rects_write         K14's write over the kept masks: slot -> item -> bit -> run length (fa_run_length) and height: rows
 //                         along the stack axis while the bit is a run start (fa_starts) and no rectangle start (the kept mask)
-//                         -> corners over both extents.  The stores are K14's.
+//                         -> corners over both extents (fa_quad).  The body and the stores are K14's (fa_write_blocks).
 // The equality of a run with the one before it is tested once, in the count, by the lane of the run's item; the write of a
 // rectangle of L x H faces costs L / 64 + H steps (L + H for d < 2).  No atomics, no private segment.
 
-// ---- stacked runs -> rectangle starts -> heights -> corners ---------------------------------------------------------------------
+// ---- stacked runs -> rectangle starts -> heights --------------------------------------------------------------------------------
 // (Plain C++ from here to the kernels: tests/test_host_rects.py compiles this part for the host behind K14's.)
 
 // the row before (y, z) along the stack axis of direction d; false if there is none
@@ -121,22 +121,6 @@ O2V_FA_FN uint32_t rc_height(const FaBits &b, const FaGrid &g, const unsigned lo
     return h;
 }
 
-// fa_quad over two extents: `len` faces along the run axis and `height` rows along the stack axis from lattice voxel (x, y, z)
-O2V_FA_FN void rc_quad(uint32_t d, uint32_t x, uint32_t y, uint32_t z, uint32_t len, uint32_t height, float out[12])
-{
-    const uint32_t a = d >> 1, s = d & 1u, u = a == 2u ? 0u : a + 1u, v = u == 2u ? 0u : u + 1u;
-    const uint32_t hx = x + (d >= 2u ? len : 1u), hy = y + (d < 2u ? len : d >= 4u ? height : 1u), hz = z + (d < 4u ? height : 1u);
-    const uint32_t plane = fa_pick(a, x, y, z) + s;
-    const uint32_t u0 = fa_pick(u, x, y, z), u1 = fa_pick(u, hx, hy, hz), v0 = fa_pick(v, x, y, z), v1 = fa_pick(v, hx, hy, hz);
-#pragma unroll
-    for (uint32_t k = 0; k < 4u; ++k) {
-        const bool mid = k == 1u || k == 2u, late = k >= 2u;   // (the corner order of fa_quad)
-        const uint32_t cu = (s ? mid : late) ? u1 : u0, cv = (s ? late : mid) ? v1 : v0;
-#pragma unroll
-        for (uint32_t c = 0; c < 3u; ++c) out[3u * k + c] = (float) (c == a ? plane : c == u ? cu : cv);
-    }
-}
-
 // ---- kernels -----------------------------------------------------------------------------------------------------------------
 #ifndef O2V_FA_HOST
 
@@ -146,23 +130,18 @@ __global__ __launch_bounds__(kBlock) void k_rects_same_z(FaGrid g, const unsigne
                                                          unsigned long long *__restrict__ same_z)
 {
     __shared__ uint32_t s_pal[Mode == kGaColorPalette ? 256 : 1];
-    static_assert(kBlock == 256u, "a thread per palette entry");
-    if (Mode == kGaColorPalette) {
-        s_pal[threadIdx.x] = col.palette[threadIdx.x];
-        __syncthreads();
-    }
+    bits_palette_to_lds<Mode == kGaColorPalette>(col.palette, s_pal, true);
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t wave = (uint64_t) blockIdx.x * (kBlock / 64u) + (threadIdx.x >> 6), n_waves = (uint64_t) gridDim.x * (kBlock / 64u);
     const uint64_t layer = (uint64_t) g.W * g.ny;
-    for (uint64_t wi = wave; wi < g.words; wi += n_waves) {   // (uniform over the wavefront)
+    for (const uint64_t wi : bits_words(g)) {
         const uint64_t both = wi >= layer ? solid[wi] & solid[wi - layer] : 0ull;
         unsigned long long mz = 0;
         if (both) {
-            const uint32_t w32 = (uint32_t) wi, row = w32 / g.W, wx = w32 - row * g.W, z = row / g.ny, y = row - z * g.ny;
-            const uint32_t x = wx * 64u + lane;   // (a solid bit is inside the box)
+            const BitWord at = bits_word_at(g, wi);
+            const uint32_t x = at.wx * 64u + lane, y = at.y, z = at.z;   // (a solid bit is inside the box)
             const bool me = both >> lane & 1u;
-            const uint32_t c = me ? fa_color<Mode>(col, s_pal, x, y, z) : 0u;
-            const uint32_t cb = me ? fa_color<Mode>(col, s_pal, x, y, z - 1u) : 0u;
+            const uint32_t c = me ? ga_color_at<Mode>(col, s_pal, x, y, z) : 0u;
+            const uint32_t cb = me ? ga_color_at<Mode>(col, s_pal, x, y, z - 1u) : 0u;
             mz = __ballot(me && c == cb);
         }
         if (lane == 0u) same_z[wi] = mz;
@@ -173,71 +152,23 @@ __global__ __launch_bounds__(kBlock) void k_rects_same_z(FaGrid g, const unsigne
 __global__ __launch_bounds__(kBlock) void k_rects_count(FaGrid g, FaBits b, const unsigned long long *__restrict__ same_z,
                                                         unsigned long long *__restrict__ rstarts, unsigned long long *__restrict__ block_sums)
 {
-    __shared__ uint64_t s_wave[kBlock / 64];
-    for (uint64_t blk = blockIdx.x; blk < g.n_blocks; blk += gridDim.x) {
-        const uint64_t item = blk * kBlock + threadIdx.x;
-        uint64_t n = 0;
-        if (item < g.items) {
-            uint32_t d, wx, y, z;
-            fa_item_at(g, item, d, wx, y, z);
-            const uint64_t r = rc_rect_starts(b, same_z, g, d, wx, y, z);
-            rstarts[item] = r;
-            n = (uint64_t) __popcll(r);
-        }
-        uint64_t total;
-        (void) fill_block_exscan64(n, s_wave, total);
-        if (threadIdx.x == 0) block_sums[blk] = total;
-    }
+    fa_count_blocks(g, block_sums, [&](uint64_t item, uint32_t d, uint32_t wx, uint32_t y, uint32_t z) {
+        return rstarts[item] = rc_rect_starts(b, same_z, g, d, wx, y, z);
+    });
 }
 
-// rectangle q of the numbering -> positions[12 q ..], faces[6 q ..] (if not null), quad_argb[q] (if not null)
+// rectangle q of the numbering -> positions[12 q ..], faces[6 q ..] (if not null), quad_argb[q] (if not null): the kept masks,
+// a run's length as K14 finds it and the height by rc_height
 template <uint32_t Mode>
 __global__ __launch_bounds__(kBlock) void k_rects_write(FaGrid g, FaBits b, const unsigned long long *__restrict__ rstarts,
                                                         const unsigned long long *__restrict__ boff, uint32_t ox, uint32_t oy, uint32_t oz, GaColor col,
                                                         float4 *__restrict__ positions, int2 *__restrict__ faces, uint32_t *__restrict__ quad_argb)
 {
-    __shared__ uint32_t s_pref[kBlock];
-    __shared__ uint64_t s_start[kBlock];
-    __shared__ uint64_t s_wave[kBlock / 64];
-    __shared__ uint32_t s_pal[Mode == kGaColorPalette ? 256 : 1];
-    static_assert(kBlock == 256u, "a thread per palette entry, a lane per item of a block, ga_find_word over 256 prefixes");
-    if (Mode == kGaColorPalette) s_pal[threadIdx.x] = col.palette[threadIdx.x];   // (the first barrier below publishes it)
-    for (uint64_t blk = blockIdx.x; blk < g.n_blocks; blk += gridDim.x) {
-        const uint64_t base = boff[blk];
-        const uint32_t cnt = (uint32_t) (boff[blk + 1] - base);   // at most 2^14
-        if (!cnt) continue;                                       // (uniform over the workgroup)
-        __syncthreads();                                          // (the arrays of the block before have been read)
-        {
-            const uint64_t item = blk * kBlock + threadIdx.x;
-            const uint64_t start = item < g.items ? rstarts[item] : 0ull;
-            uint64_t total;
-            s_pref[threadIdx.x] = (uint32_t) fill_block_exscan64((uint64_t) __popcll(start), s_wave, total);
-            s_start[threadIdx.x] = start;
-        }
-        __syncthreads();
-        for (uint32_t slot = threadIdx.x; slot < cnt; slot += kBlock) {
-            const uint32_t l = ga_find_word(s_pref, slot);
-            const uint32_t bit = ga_select(s_start[l], slot - s_pref[l]);
-            uint32_t d, wx, y, z;
-            fa_item_at(g, blk * kBlock + l, d, wx, y, z);
-            const uint32_t x = wx * 64u + bit;
-            const uint32_t len = fa_run_length(b, g, d, wx, y, z, bit);
-            const uint32_t height = rc_height(b, g, rstarts, d, wx, y, z, bit);
-            const uint64_t q = base + slot;   // (4 q + 3 is below 2^31: the host refuses more)
-            float p[12];
-            rc_quad(d, ox + x, oy + y, oz + z, len, height, p);
-            positions[3u * q] = make_float4(p[0], p[1], p[2], p[3]);
-            positions[3u * q + 1u] = make_float4(p[4], p[5], p[6], p[7]);
-            positions[3u * q + 2u] = make_float4(p[8], p[9], p[10], p[11]);
-            if (faces) {
-                const int32_t v = (int32_t) (4u * q);
-                faces[3u * q] = make_int2(v, v + 1);
-                faces[3u * q + 1u] = make_int2(v + 2, v);
-                faces[3u * q + 2u] = make_int2(v + 2, v + 3);
-            }
-            if (quad_argb) quad_argb[q] = fa_color<Mode>(col, s_pal, x, y, z);
-        }
-    }
+    fa_write_blocks<Mode>(
+        g, boff, ox, oy, oz, col, positions, faces, quad_argb, [&](uint64_t item, uint32_t, uint32_t, uint32_t, uint32_t) { return (uint64_t) rstarts[item]; },
+        [&](uint32_t d, uint32_t wx, uint32_t y, uint32_t z, uint32_t bit, uint32_t &len, uint32_t &height) {
+            len = fa_run_length(b, g, d, wx, y, z, bit), height = rc_height(b, g, rstarts, d, wx, y, z, bit);
+        });
 }
 
 #endif   // O2V_FA_HOST

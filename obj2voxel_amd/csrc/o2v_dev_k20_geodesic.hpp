@@ -1,8 +1,8 @@
 // o2v_dev_k20_geodesic.hpp -- K20: geodesic distances and shortest paths through a dense grid (o2v_hip_geodesic_dense /
-// o2v_hip_geodesic_paths).  Included from o2v_device.hip inside its anonymous namespace, after K12 (whose classification, bits and
-// word walk it uses).
+// o2v_hip_geodesic_paths).  Included from o2v_device.hip inside its anonymous namespace, after K12 (whose classification it uses)
+// and o2v_dev_bits.hpp (the bit grid, its words, tiles and walk).
 //
-// The set S is K12's: one bit per voxel, 64-bit words along x, [z][y][ceil(nx / 64)], padding bits 0 (k_cc_classify).  D[i] is the
+// The set S is the bit grid of o2v_dev_bits.hpp, classified by K12's k_cc_classify.  D[i] is the
 // distance of voxel i = (z * ny + y) * nx + x so far, a uint32: kGeoInf (0x7fffffff) where nothing has reached it - so for every
 // voxel outside S, for good: a neighbour's D says by itself whether that neighbour is in S, and no pass but the owner's reads
 // the bits.  d(v) is the least fixed point of D[v] = min(D[v], D[u] + w(u, v)) over the neighbours u of v, with the seeds at 0:
@@ -45,12 +45,10 @@ static_assert((uint64_t) kGeoInf + kGeoMaxWeight <= 0xffffffffull && kGeoMaxDist
 // (Plain C++ from here to the kernels: tests/test_host_geodesic.py compiles this part for the host, with an O2V_GEO_FN of its
 // own, runs it tile by tile in a shuffled order and as whole-grid sweeps against the reference, and checks that one change is caught.)
 
-struct GeoGrid {
-    uint32_t nx, ny, nz, W;      // W = ceil(nx / 64) words per row = tiles along x
-    uint32_t tiles_y, tiles_z;   // ceil(ny / 8), ceil(nz / 8)
+struct GeoGrid : BitGrid {
+    uint32_t tiles_y, tiles_z;   // ceil(ny / 8), ceil(nz / 8); tiles along x: W
     uint32_t w[3];               // the cost of a step that differs on 1, 2, 3 axes; 0: no such step
     uint32_t max_distance;
-    uint64_t words;              // W * ny * nz
 };
 
 // The 26 offsets in ascending (dz, dy, dx) order: k = 0 .. 26 without 13.
@@ -163,14 +161,6 @@ O2V_GEO_FN int32_t geo_trace(const int32_t *dist, uint64_t s0, uint64_t s1, uint
 // ---- kernels -----------------------------------------------------------------------------------------------------------------
 #ifndef O2V_GEO_HOST
 
-__device__ __forceinline__ void geo_word_at(const GeoGrid &g, uint64_t wi, uint32_t &wx, uint32_t &y, uint32_t &z)
-{
-    const uint64_t row = wi / g.W;
-    wx = (uint32_t) (wi - row * g.W);
-    z = (uint32_t) (row / g.ny);
-    y = (uint32_t) (row - (uint64_t) z * g.ny);
-}
-
 // the tile's word of round 0; a tile flagged for the first time goes to the list
 __device__ __forceinline__ void geo_flag_tile(uint32_t tile, uint32_t *flags, uint32_t *list, uint32_t *count)
 {
@@ -197,7 +187,7 @@ __global__ __launch_bounds__(kBlock) void k_geo_seed_list(GeoGrid g, const unsig
     for (uint64_t s = (uint64_t) blockIdx.x * kBlock + threadIdx.x; s < n; s += (uint64_t) gridDim.x * kBlock) {
         const uint32_t x = (uint32_t) seeds[s * 3u], y = (uint32_t) seeds[s * 3u + 1u], z = (uint32_t) seeds[s * 3u + 2u];
         if (x >= g.nx || y >= g.ny || z >= g.nz) continue;   // (a negative coordinate is above any dim)
-        if (!((bits[((uint64_t) z * g.ny + y) * g.W + (x >> 6)] >> (x & 63u)) & 1ull)) continue;
+        if (!bits_has(g, bits, x, y, z)) continue;
         D[(z * g.ny + y) * g.nx + x] = 0u;
         if (flags) geo_flag_seed(g, x >> 6, y >> 3, z >> 3, geo_see_mask(x & 63u, y & 7u, z & 7u, g.w), flags, list, count);
     }
@@ -208,13 +198,10 @@ __global__ __launch_bounds__(kBlock) void k_geo_seed_border(GeoGrid g, const uns
                                                             uint32_t *list, uint32_t *count)
 {
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t wave = (uint64_t) blockIdx.x * (kBlock / 64u) + (threadIdx.x >> 6), n_waves = (uint64_t) gridDim.x * (kBlock / 64u);
-    for (uint64_t wi = wave; wi < g.words; wi += n_waves) {
-        uint32_t wx, y, z;
-        geo_word_at(g, wi, wx, y, z);
-        const uint32_t x = wx * 64u + lane;
-        const bool face = y == 0u || y == g.ny - 1u || z == 0u || z == g.nz - 1u || x == 0u || x == g.nx - 1u;
-        const bool seed = face && x < g.nx && ((bits[wi] >> lane) & 1ull);
+    for (const uint64_t wi : bits_words(g)) {
+        const BitWord at = bits_word_at(g, wi);
+        const uint32_t wx = at.wx, x = wx * 64u + lane, y = at.y, z = at.z;
+        const bool seed = bits_on_face(g, x, y, z) && x < g.nx && ((bits[wi] >> lane) & 1ull);
         if (seed) D[(z * g.ny + y) * g.nx + x] = 0u;
         if (__ballot(seed) == 0ull || !flags) continue;
         uint32_t see = seed ? geo_see_mask(lane, y & 7u, z & 7u, g.w) : 0u;   // (the word is one row of one tile)
@@ -235,15 +222,13 @@ __global__ __launch_bounds__(kBlock) void k_geo_tiles(GeoGrid g, const unsigned 
     __shared__ uint32_t s_see;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     for (uint32_t li = blockIdx.x; li < n_list; li += gridDim.x) {
-        const uint32_t tile = list[li], trow = tile / g.W;
-        const uint32_t tx = tile - trow * g.W, tz = trow / g.tiles_y, ty = trow - tz * g.tiles_y;
+        const uint32_t tile = list[li];
+        uint32_t tx, ty, tz;
+        bits_tile_at(g, g.tiles_y, tile, tx, ty, tz);
         const uint32_t x0 = tx * 64u, y0 = ty * 8u, z0 = tz * 8u;
         __syncthreads();   // (the last tile's words and distances are no longer read)
         if (threadIdx.x == 0) flags_cur[tile] = 0u, s_see = 0u;   // (nothing else touches this round's word in this launch)
-        if (threadIdx.x < kCcTileRows) {
-            const uint32_t y = y0 + (threadIdx.x & 7u), z = z0 + (threadIdx.x >> 3);
-            s_w[threadIdx.x] = y < g.ny && z < g.nz ? bits[((uint64_t) z * g.ny + y) * g.W + tx] : 0ull;
-        }
+        if (threadIdx.x < kCcTileRows) s_w[threadIdx.x] = bits_tile_word(g, bits, tx, ty, tz, threadIdx.x);
         // the tile and its halo: 100 rows of 66, kGeoInf outside the box (D holds it outside S)
         for (uint32_t row = wave; row < 100u; row += kBlock / 64u) {
             const uint32_t Y = y0 + row % 10u - 1u, Z = z0 + row / 10u - 1u;   // (-1 wraps to above any dim)
@@ -299,14 +284,12 @@ __global__ __launch_bounds__(kBlock) void k_geo_tiles(GeoGrid g, const unsigned 
 __global__ __launch_bounds__(kBlock) void k_geo_sweep(GeoGrid g, const unsigned long long *__restrict__ bits, uint32_t *D, uint32_t *changed)
 {
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t wave = (uint64_t) blockIdx.x * (kBlock / 64u) + (threadIdx.x >> 6), n_waves = (uint64_t) gridDim.x * (kBlock / 64u);
     bool any = false;
-    for (uint64_t wi = wave; wi < g.words; wi += n_waves) {
+    for (const uint64_t wi : bits_words(g)) {
         const unsigned long long w = bits[wi];
         if (!((w >> lane) & 1ull)) continue;
-        uint32_t wx, y, z;
-        geo_word_at(g, wi, wx, y, z);
-        const uint32_t x = wx * 64u + lane, i = (z * g.ny + y) * g.nx + x;
+        const BitWord at = bits_word_at(g, wi);
+        const uint32_t x = at.wx * 64u + lane, y = at.y, z = at.z, i = (z * g.ny + y) * g.nx + x;
         const uint32_t d = geo_relax_grid(g, D, x, y, z);
         if (d < D[i]) atomicMin(D + i, d), any = true;
     }
@@ -317,14 +300,11 @@ __global__ __launch_bounds__(kBlock) void k_geo_sweep(GeoGrid g, const unsigned 
 __global__ __launch_bounds__(kBlock) void k_geo_write(GeoGrid g, const uint32_t *D, int32_t *dist, uint64_t s0, uint64_t s1, uint64_t s2,
                                                       unsigned long long *reached)
 {
-    __shared__ unsigned long long s_sum[kBlock / 64];
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t wave = (uint64_t) blockIdx.x * (kBlock / 64u) + (threadIdx.x >> 6), n_waves = (uint64_t) gridDim.x * (kBlock / 64u);
     unsigned long long mine = 0;   // (the same in every lane of the wavefront)
-    for (uint64_t wi = wave; wi < g.words; wi += n_waves) {
-        uint32_t wx, y, z;
-        geo_word_at(g, wi, wx, y, z);
-        const uint32_t x = wx * 64u + lane;
+    for (const uint64_t wi : bits_words(g)) {
+        const BitWord at = bits_word_at(g, wi);
+        const uint32_t x = at.wx * 64u + lane, y = at.y, z = at.z;
         bool hit = false;
         if (x < g.nx) {
             const uint32_t d = D[(z * g.ny + y) * g.nx + x];   // (D may be dist itself: a lane reads its own element, then writes it)
@@ -333,13 +313,7 @@ __global__ __launch_bounds__(kBlock) void k_geo_write(GeoGrid g, const uint32_t 
         }
         mine += (unsigned long long) __popcll(__ballot(hit));
     }
-    if (lane == 0u) s_sum[threadIdx.x >> 6] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long sum = 0;
-        for (uint32_t w = 0; w < kBlock / 64u; ++w) sum += s_sum[w];
-        if (sum) atomicAdd(reached, sum);
-    }
+    bits_add_wave_sums(mine, reached);
 }
 
 struct GeoTrace {

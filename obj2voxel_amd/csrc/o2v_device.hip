@@ -101,6 +101,7 @@ namespace {
 #include "o2v_dev_k10_surface.hpp"
 #include "o2v_dev_k11_raycast.hpp"
 #include "o2v_dev_k8_distance.hpp"   // (behind K11: its seed test reads a set grid, K11's RaySource and kRay* formats)
+#include "o2v_dev_bits.hpp"           // (the bit grid of K12, K13, K14, K16 and K20)
 #include "o2v_dev_k12_components.hpp"
 #include "o2v_dev_k13_gather.hpp"
 #include "o2v_dev_k14_faces.hpp"

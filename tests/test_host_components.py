@@ -14,6 +14,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import bits_host
 from tests import components_ref as CR
 
 torch = pytest.importorskip("torch")
@@ -260,7 +261,8 @@ def words64(S):
 @pytest.fixture(scope="module")
 def host_cc(tmp_path_factory):
     """build(defines) -> label(S, connectivity, no_tiles) -> (labels, n, roots, (unions, retries)): the part of
-    o2v_dev_k12_components.hpp between "the union-find and the adjacency" and "kernels", compiled for the host."""
+    o2v_dev_k12_components.hpp between "the union-find and the adjacency" and "kernels", compiled for the host behind the plain part
+    of o2v_dev_bits.hpp."""
     cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++") or HIPCC
     if not shutil.which(cxx) and not os.path.exists(cxx):
         pytest.skip("no C++ compiler")
@@ -270,7 +272,7 @@ def host_cc(tmp_path_factory):
 
     def build(defines=()):
         name = "cc_%d" % len(list(tmp.iterdir()))
-        (tmp / (name + ".cpp")).write_text(HOST_CC % part)
+        (tmp / (name + ".cpp")).write_text(HOST_CC % (bits_host.plain_part() + part))
         subprocess.run([cxx, "-x", "c++", "-O2", "-std=c++17", "-shared", "-fPIC"] + ["-D" + d for d in defines] +
                        [str(tmp / (name + ".cpp")), "-o", str(tmp / (name + ".so"))], check=True, capture_output=True)
         L = hip.C.CDLL(str(tmp / (name + ".so")))

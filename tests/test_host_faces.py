@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import bits_host
 from tests import faces_ref as FR
 from tests import fill_ref
 from tests import gather_ref as GR
@@ -155,7 +156,7 @@ extern "C" uint64_t fa_host(const unsigned long long *solid, const unsigned long
         const uint64_t s = starts[item] = fa_starts(b, g, d, wx, y, z);
         for (uint32_t bit = 0; bit < 64u; ++bit) {
             if (!(s >> bit & 1u)) continue;
-            if (q < capacity) fa_quad(d, ox + wx * 64u + bit, oy + y, oz + z, fa_run_length(b, g, d, wx, y, z, bit), pos + 12u * q);
+            if (q < capacity) fa_quad(d, ox + wx * 64u + bit, oy + y, oz + z, fa_run_length(b, g, d, wx, y, z, bit), 1u, pos + 12u * q);
             ++q;
         }
     }
@@ -167,7 +168,7 @@ extern "C" uint64_t fa_host(const unsigned long long *solid, const unsigned long
 @pytest.fixture(scope="module")
 def host_fa(tmp_path_factory):
     """build(defines) -> run(S, Cv, merge, origin) -> (starts uint64 [6 * words], positions float32 [4Q, 3]): the plain C++ part of
-    o2v_dev_k14_faces.hpp, compiled for the host."""
+    o2v_dev_k14_faces.hpp, compiled for the host behind the plain part of o2v_dev_bits.hpp."""
     cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++") or HIPCC
     if not shutil.which(cxx) and not os.path.exists(cxx):
         pytest.skip("no C++ compiler")
@@ -178,7 +179,7 @@ def host_fa(tmp_path_factory):
 
     def build(defines=()):
         name = "fa_%d" % len(list(tmp.iterdir()))
-        (tmp / (name + ".cpp")).write_text(HOST_FA % (head + part))
+        (tmp / (name + ".cpp")).write_text(HOST_FA % (bits_host.plain_part() + head + part))
         subprocess.run([cxx, "-x", "c++", "-O2", "-std=c++17", "-shared", "-fPIC"] + ["-D" + d for d in defines] +
                        [str(tmp / (name + ".cpp")), "-o", str(tmp / (name + ".so"))], check=True, capture_output=True)
         L = C.CDLL(str(tmp / (name + ".so")))

@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import bits_host
 from tests import components_ref as CR
 from tests import geodesic_ref as GR
 
@@ -258,7 +259,7 @@ extern "C" void geo_host_trace(const int32_t *dist, const uint64_t *strides, con
 @pytest.fixture(scope="module")
 def host_geo(tmp_path_factory):
     """build(defines) -> a library with geo_host and geo_host_trace: the part of o2v_dev_k20_geodesic.hpp between "the relaxation"
-    and "kernels", compiled for the host."""
+    and "kernels", compiled for the host behind the plain part of o2v_dev_bits.hpp."""
     cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++") or HIPCC
     if not shutil.which(cxx) and not os.path.exists(cxx):
         pytest.skip("no C++ compiler")
@@ -270,7 +271,7 @@ def host_geo(tmp_path_factory):
     def build(defines=()):
         if defines not in built:
             name = "geo_%d" % len(built)
-            (tmp / (name + ".cpp")).write_text(HOST_GEO % part)
+            (tmp / (name + ".cpp")).write_text(HOST_GEO % (bits_host.plain_part() + part))
             subprocess.run([cxx, "-x", "c++", "-O2", "-std=c++17", "-shared", "-fPIC"] + ["-D" + d for d in defines] +
                            [str(tmp / (name + ".cpp")), "-o", str(tmp / (name + ".so"))], check=True, capture_output=True)
             built[defines] = hip.C.CDLL(str(tmp / (name + ".so")))

@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import bits_host
 from tests import faces_ref as FR
 from tests import fill_ref
 from tests import gather_ref as GR
@@ -209,7 +210,7 @@ extern "C" uint64_t rc_host(const unsigned long long *solid, const unsigned long
             if (q < capacity) {
                 const uint32_t len = fa_run_length(b, g, d, wx, y, z, bit), height = rc_height(b, g, rstarts, d, wx, y, z, bit);
                 extents[2u * q] = len, extents[2u * q + 1u] = height;
-                rc_quad(d, ox + wx * 64u + bit, oy + y, oz + z, len, height, pos + 12u * q);
+                fa_quad(d, ox + wx * 64u + bit, oy + y, oz + z, len, height, pos + 12u * q);
             }
             ++q;
         }
@@ -222,12 +223,12 @@ extern "C" uint64_t rc_host(const unsigned long long *solid, const unsigned long
 @pytest.fixture(scope="module")
 def host_rc(tmp_path_factory):
     """build(defines) -> run(S, Cv, origin) -> (rstarts uint64 [6 * words], positions float32 [4Q, 3], (length, height) [Q, 2]):
-    the plain C++ parts of o2v_dev_k14_faces.hpp and o2v_dev_k16_rects.hpp, compiled for the host."""
+    the plain C++ parts of o2v_dev_bits.hpp, o2v_dev_k14_faces.hpp and o2v_dev_k16_rects.hpp, compiled for the host."""
     cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++") or HIPCC
     if not shutil.which(cxx) and not os.path.exists(cxx):
         pytest.skip("no C++ compiler")
     k14, k16 = open(K14).read(), open(K16).read()
-    text = (k14[k14.index("constexpr uint32_t kFaMergeNone"):k14.index("#ifndef O2V_FA_HOST")] +
+    text = (bits_host.plain_part() + k14[k14.index("constexpr uint32_t kFaMergeNone"):k14.index("#ifndef O2V_FA_HOST")] +
             k14[k14.index("// ---- words -> exposed faces"):k14.index("// ---- kernels")] +
             k16[k16.index("// ---- stacked runs"):k16.index("// ---- kernels")])
     tmp = tmp_path_factory.mktemp("host_rc")

@@ -997,6 +997,68 @@ int o2v_hip_thickness_counters(const o2v_hip_ctx *ctx, uint64_t out3[3]);
  * L_k[R] > R.  O2V_HIP_ERR_BAD_ARGUMENT for a null out or a max_radius2 out of range. */
 int o2v_hip_thickness_cover_table(uint32_t max_radius2, uint32_t *out /* [3][max_radius2 + 1] */);
 
+/* ---- skeletons of a dense grid: topological thinning -------------------------------------------------------
+ *
+ * Reduces a set to its skeleton - the one-voxel-wide centrelines of a solid, or of its pore and channel space - by removing
+ * simple voxels from its border until none is left.  The numbers of object components, of cavities and of tunnels never change.
+ *
+ * The definition.  S is the set of a set grid, as in o2v_hip_components_dense: U8 non-zero, BITS, or F32_BELOW with a level.
+ * O2V_HIP_CC_INVERT takes the complement inside the box.  Voxels outside the box are background.  Objects are 26-connected.  The
+ * background is 6-connected.
+ *   Neighbourhood mask of a voxel: bit k = 9 (dz + 1) + 3 (dy + 1) + (dx + 1) is set where the neighbour is in S.  k runs 0 ... 26
+ *   without 13.  This is o2v_hip_geodesic_dense's offset order.
+ *   C26(m) is the number of 26-connected components of the set bits of m.
+ *   C6(m): take the clear bits of m among the 18 positions that differ from the centre on at most two axes.  Connect them by
+ *   6-adjacency within these 18.  Count the components that hold a face neighbour.
+ *   Simple: a voxel is simple iff C26 == 1 && C6 == 1.  Of the 2^26 masks, 25 985 144 are simple.
+ *   Border: a voxel of S is a border voxel if one of its six face neighbours is background.
+ *   Subfield: the subfield of a voxel is s = (x & 1) | (y & 1) << 1 | (z & 1) << 2, in box coordinates.  Two voxels of one subfield
+ *   are never 26-neighbours.
+ *   One iteration:
+ *     1. B := the border voxels of S as it is now.
+ *     2. For s = 0 ... 7 in turn, remove from S at once every voxel v that meets all of these in the current S: v is in subfield s;
+ *        v is in B; v is not in `keep`; v is simple; in mode CURVE, v has other than exactly one 26-neighbour in S.
+ *     3. Iterations repeat until one removes nothing.  That iteration counts.
+ *     4. If max_iterations != 0, they also stop once max_iterations have run.
+ * Because of the subfields, every sub-step equals some sequential removal of simple voxels.  Every sub-step is also a pure function
+ * of the grid, so the result is the same bits on every run and under every schedule.
+ *
+ * Modes.  O2V_HIP_THIN_ULTIMATE (no end points): a ball becomes one voxel, a torus a closed loop, a hollow shell a closed
+ * one-voxel surface.  O2V_HIP_THIN_CURVE: end points stay, so arms stay.
+ * Documented limits of the method: the result depends on the parity of the box's origin; the end-point rule keeps spurs at corners
+ * (a 9^3 box gives 25 voxels with 8 end points).
+ * keep: an optional U8 grid with strides of its own (may be NULL); non-zero means never removed.
+ *
+ * dst is uint8 with any strides that map no two voxels to one element.  O2V_HIP_THIN_DST_MASK: 1 in the skeleton, 0 elsewhere.
+ * O2V_HIP_THIN_DST_DEGREE: 0 outside the skeleton; inside it, 1 + the number of 26-neighbours in the skeleton - so 1 is isolated, 2 an
+ * end, 3 a plain curve voxel and 4 or more a junction.  Every voxel of the box is written.  grid may equal dst exactly (same pointer
+ * and strides, U8), to thin in place.  Any other overlap of dst with grid or keep is refused (grid and keep are only read).
+ * flags: O2V_HIP_CC_INVERT, O2V_HIP_FLAG_STAGE_TIMES (o2v_hip_thin_counters counts).
+ *
+ * Refused before any launch, the outputs untouched.  O2V_HIP_ERR_BAD_ARGUMENT: null arguments, zero dims, an unknown format, mode,
+ * dst_format or flag bit, a level that is not finite (F32_BELOW), BITS with strides[0] != 1, pointers that are not device memory of
+ * the context's device or reach outside their allocation, dst strides that map two voxels to one element.  O2V_HIP_ERR_LIMIT: a dim
+ * above 65 536, or nx * ny * nz above 2^31 - 1 (o2v_hip_components_dense's limits, whose classification is reused).  A failed
+ * scratch allocation returns O2V_HIP_ERR_OUT_OF_MEMORY and the context stays usable.  The call runs on the context's stream and
+ * returns when the writes are done (the caller must have finished writing grid and keep).  Nine launches per iteration - the
+ * border, then the eight subfields, tile by tile (64 x 8 x 8 voxels; a tile runs only while a voxel in its view was removed during
+ * this iteration or the last) - and one 8-byte read by the host.
+ *
+ * Scratch of the context, grown on demand: o2v_hip_thin_scratch_bytes(dims, have_keep) = (16, with keep 24) * ceil(nx / 64) * ny * nz
+ * (the bits of the set, of its border and of keep)  +  8 * the tiles (two stamps each)  +  64.  (0 for zero dims.) */
+enum { O2V_HIP_THIN_ULTIMATE = 0, O2V_HIP_THIN_CURVE = 1 };
+enum { O2V_HIP_THIN_DST_MASK = 0, O2V_HIP_THIN_DST_DEGREE = 1 };
+int o2v_hip_thin_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+                       uint32_t flags, uint32_t mode, uint32_t max_iterations, const uint8_t *keep /* may be NULL */, const uint64_t keep_strides[3],
+                       uint8_t *dst, const uint64_t dst_strides[3], uint32_t dst_format);
+uint64_t o2v_hip_thin_scratch_bytes(const uint32_t dims[3], int have_keep);
+/* The device times (ms) of the last o2v_hip_thin_dense call: classify, iterate (the host's reads included), write. */
+int o2v_hip_thin_times(const o2v_hip_ctx *ctx, float out_ms[3]);
+/* Of the last o2v_hip_thin_dense call made with O2V_HIP_FLAG_STAGE_TIMES (else zeros): the iterations, the launches of the
+ * iterations (nine each: the border and the eight sub-steps), the tile turns (the tiles that ran a sub-step with a candidate in
+ * them - a tile stamped by a neighbour while a launch runs may or may not count in that launch) and the voxels removed. */
+int o2v_hip_thin_counters(const o2v_hip_ctx *ctx, uint64_t out4[4]);
+
 int o2v_hip_get_timings(const o2v_hip_ctx *ctx, o2v_hip_timings *out);
 /* Per-kernel device times of the last o2v_hip_voxelize call made with O2V_HIP_FLAG_KERNEL_TIMES (else none): up to
  * max_entries entries are written, *out_count receives how many there are. */

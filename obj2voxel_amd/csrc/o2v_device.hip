@@ -53,6 +53,8 @@
 //                              grid, a relaxation tile by tile in LDS, round by round; the walk back; outside the pipeline
 //   K21 k_thick_*              o2v_hip_thickness_dense: local thickness, opening and erosion by a ball - two of K8's distance
 //                              transforms, a pruned list of ball centres, an atomicMax per ball voxel; outside the pipeline
+//   K22 k_thin_*               o2v_hip_thin_dense: skeletons by topological thinning - eight subfields per iteration, a 26-voxel
+//                              bit test per border voxel, tile by tile in LDS, in place on the bit grid; outside the pipeline
 //   plan k_zhist               o2v_hip_plan_slabs: predicted hits per z layer -> work-balanced slabs for N GPUs
 // With the direct MAX path K1's counters reach the host while K2 runs, and only the stages that have work are enqueued
 // behind it.  N > 1 GPUs: o2v_hip_voxelize_sharded (bounds / work-histogram passes sharded over the ranks, RCCL).
@@ -112,6 +114,7 @@ namespace {
 #include "o2v_dev_k19_label_stats.hpp"
 #include "o2v_dev_k20_geodesic.hpp"
 #include "o2v_dev_k21_thickness.hpp"
+#include "o2v_dev_k22_thinning.hpp"
 
 }  // namespace
 
@@ -246,6 +249,7 @@ struct Switches {
     bool cross_no_tile = env_on("O2V_CROSS_NO_TILE");          // A/B: no k_cross_prefix_tile, a lane per line stores along the ray
     bool ls_no_table = env_on("O2V_LS_NO_TABLE");              // A/B: k_label_stats without its table in LDS, every run to global memory
     bool geo_no_tiles = env_on("O2V_GEO_NO_TILES");            // A/B: no k_geo_tiles, whole-grid sweeps with atomic mins in global memory
+    bool thin_no_tiles = env_on("O2V_THIN_NO_TILES");          // A/B: no k_thin_substep, every sub-step a whole-grid sweep with the masks from global memory
     bool tiny_buffers = env_on("O2V_TEST_TINY_BUFFERS");       // test hook: minimal first capacities (every grow -> re-run path)
     bool block_list = env_on("O2V_TEST_BLOCK_LIST");           // test hook: the slab's block list for a mesh of any size
     int resolve_wgs_per_cu = env_int("O2V_RESOLVE_WGS_PER_CU", 0);  // A/B: workgroups per CU of resolve tier 1 (if > 0; else 2)
@@ -487,6 +491,14 @@ struct o2v_hip_ctx {
     uint32_t thick_table_cap = 0;
     StageTimes<5> thick_times;
     uint64_t thick_counters[3] = {};
+    // K22 (o2v_hip_thin_dense): the bits of the set, of its border voxels and of `keep` ([2 or 3][words]); per tile its stamps of
+    // the last odd and the last even iteration with a removal in view ([2][tiles]); [0] voxels removed, [1] tile turns; grown on
+    // demand; the times of the three stages and the four counters of the last call
+    DevArray<unsigned long long> d_thin_bits, d_thin_ctr;
+    DevArray<uint32_t> d_thin_stamps;
+    PinnedArray<unsigned long long> h_thin_ctr;
+    StageTimes<3> thin_times;
+    uint64_t thin_counters[4] = {};
 
     // results of the last run
     uint64_t n_vox = 0;
@@ -2466,6 +2478,7 @@ int o2v_hip_voxels_device_ptr(o2v_hip_ctx *ctx, const uint32_t **out_ptr, uint64
 #include "o2v_dev_host_k17_downsample.hpp"
 #include "o2v_dev_host_k19_label_stats.hpp"
 #include "o2v_dev_host_k21_thickness.hpp"
+#include "o2v_dev_host_k22_thinning.hpp"
 
 extern "C" {
 

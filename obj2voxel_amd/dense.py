@@ -31,7 +31,9 @@ without leaving the set - hop counts, the chamfer metric or any integer step cos
 shortest_paths walks back along those distances (o2v_hip_geodesic_dense / o2v_hip_geodesic_paths, DESIGN.md section 23);
 local_thickness says how thick a solid is at every voxel - the largest inscribed ball that holds it -, thin_regions where it is
 thinner than t, and inner_distance, erode, dilate, opening and closing are the ball morphology that falls out of the same passes
-(o2v_hip_thickness_dense).
+(o2v_hip_thickness_dense); skeletonize reduces a set to its skeleton - the one-voxel-wide centrelines of a
+solid or of its pore space - by topological thinning, and skeleton_nodes lists the end points and junctions (o2v_hip_thin_dense,
+DESIGN.md section 25).
 
 torch is imported first on purpose: the library must bind to the HIP runtime torch loaded (a process that loaded the library
 before torch holds two separate runtime copies, and this module refuses to work there).
@@ -1012,6 +1014,11 @@ def thin_regions(dv, grid, min_thickness, *, level=None, background=False, borde
     cap = _radius_cap((float(min_thickness) - 1.0) / 2.0, "(min_thickness - 1) / 2")
     dst, _ = _thickness(dv, grid, cap, level, background, border, hip.THICK_OPEN_ONLY, torch.int32, None, None)
     return (dst > 0) & (dst < cap)
+
+
+# ---- skeletons: topological thinning ---------------------------------------------------------------------
+
+from .skeleton import skeleton_nodes, skeletonize  # noqa: E402,F401  (the torch layer of o2v_hip_thin_dense, a module of its own)
 
 
 # ---- dense grids as voxel lists and voxel files --------------------------------------------------------

@@ -41,6 +41,8 @@ GEO_MAX_WEIGHT, GEO_MAX_DISTANCE = 65535, 2 ** 31 - 2  # o2v_hip_geodesic_dense:
 GEO_SCRATCH_CONTIGUOUS, GEO_SCRATCH_STRIDED = 0, 1  # o2v_hip_geodesic_scratch_bytes
 THICK_BACKGROUND, THICK_BORDER, THICK_F32, THICK_OPEN_ONLY = 16, 32, 64, 128  # o2v_hip_thickness_dense flags (with FLAG_STAGE_TIMES: the ball voxels counted)
 THICK_MAX_RADIUS2 = 1 << 14  # ... its largest max_radius2
+THIN_ULTIMATE, THIN_CURVE = 0, 1  # o2v_hip_thin_dense modes: no end points; end points stay
+THIN_DST_MASK, THIN_DST_DEGREE = 0, 1  # ... its dst formats: 1 / 0; 1 + the 26-neighbours in the skeleton
 STATS_BOX, STATS_SUMS, STATS_MOMENTS, STATS_FACES = 1, 2, 4, 8  # ... the bits of `which`
 STATS_COLUMNS = 17  # ... the int64 columns of a row of its table
 ERR_BAD_ARGUMENT = 3
@@ -205,6 +207,12 @@ def _bind():
     L.o2v_hip_thickness_times.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_thickness_counters.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_thickness_cover_table.argtypes = [C.c_uint32, C.c_void_p]
+    # ..., flags, mode, max_iterations, keep, keep_strides, dst, dst_strides, dst_format
+    L.o2v_hip_thin_dense.argtypes = _gather + [C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4 + [C.c_uint32]
+    L.o2v_hip_thin_scratch_bytes.argtypes = [C.c_void_p, C.c_int]
+    L.o2v_hip_thin_scratch_bytes.restype = C.c_uint64
+    L.o2v_hip_thin_times.argtypes = [C.c_void_p, C.c_void_p]
+    L.o2v_hip_thin_counters.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_max_slab_layers.argtypes = [C.c_void_p, C.POINTER(_Params), C.POINTER(C.c_uint32)]
     return L
 
@@ -275,6 +283,11 @@ def thickness_scratch_bytes(dims, max_radius2, have_depth2=False):
     """o2v_hip_thickness_scratch_bytes: the context scratch a thickness_dense call over dims (x, y, z) with that cap takes, with
     (have_depth2) or without a depth2 grid of the caller's; on top of it 4 bytes per kept ball centre."""
     return int(_bind().o2v_hip_thickness_scratch_bytes(_u32x3(dims), int(max_radius2), 1 if have_depth2 else 0))
+
+
+def thin_scratch_bytes(dims, have_keep=False):
+    """o2v_hip_thin_scratch_bytes: the context scratch a thin_dense call over dims (x, y, z) takes, with or without a keep grid."""
+    return int(_bind().o2v_hip_thin_scratch_bytes(_u32x3(dims), 1 if have_keep else 0))
 
 
 def thickness_cover_table(max_radius2):
@@ -715,6 +728,31 @@ class DeviceVoxelizer:
         the last only with FLAG_STAGE_TIMES (else 0)."""
         out = (C.c_uint64 * 3)()
         self._check(self._L.o2v_hip_thickness_counters(self._ctx, out), "o2v_hip_thickness_counters")
+        return tuple(int(v) for v in out)
+
+    def thin_dense(self, grid_ptr, fmt, strides, dims, level, flags, mode, max_iterations, keep_ptr, keep_strides, dst_ptr, dst_strides, dst_format):
+        """o2v_hip_thin_dense: the skeleton of the set of the grid at device pointer grid_ptr (dims, strides, fmt and level as
+        components_dense takes them; CC_INVERT: its complement) by topological thinning - simple border voxels removed subfield by
+        subfield until an iteration removes nothing, or max_iterations (if not 0) have run; THIN_CURVE keeps end points,
+        THIN_ULTIMATE does not; a voxel where the uint8 grid at keep_ptr (None: no such grid) is non-zero is never removed.  Into
+        the uint8 grid at dst_ptr: THIN_DST_MASK 1 / 0, THIN_DST_DEGREE 1 + the 26-neighbours in the skeleton.  dst may be the
+        grid itself (uint8, the same strides).  Strides in elements per axis x, y, z."""
+        self._check(self._L.o2v_hip_thin_dense(self._ctx, grid_ptr, fmt, _u64x3(strides), _u32x3(dims), float(level), flags, mode, max_iterations, keep_ptr,
+                                               _u64x3(keep_strides), dst_ptr, _u64x3(dst_strides), dst_format), "o2v_hip_thin_dense")
+
+    def thin_scratch_bytes(self, dims, have_keep=False):
+        """o2v_hip_thin_scratch_bytes: the context scratch a thin_dense call over dims (x, y, z) takes."""
+        return thin_scratch_bytes(dims, have_keep)
+
+    def thin_times(self):
+        """o2v_hip_thin_times: the device times (ms) of the last thin_dense call's classify, iterate and write stages."""
+        return self._stage_times("o2v_hip_thin_times", 3)
+
+    def thin_counters(self):
+        """o2v_hip_thin_counters: (iterations, launches, tile turns, voxels removed) of the last thin_dense call made with
+        FLAG_STAGE_TIMES (else zeros)."""
+        out = (C.c_uint64 * 4)()
+        self._check(self._L.o2v_hip_thin_counters(self._ctx, out), "o2v_hip_thin_counters")
         return tuple(int(v) for v in out)
 
     def nearest_scratch_bytes(self, dims):

@@ -14,6 +14,7 @@ import pytest
 
 from tests import bits_host
 from tests import thinning_ref as TR
+from tests import thinning_sets as TS
 
 torch = pytest.importorskip("torch")
 
@@ -368,6 +369,158 @@ def test_the_see_mask_and_the_spread(host_thin):
     for mode in (TR.ULTIMATE, TR.CURVE):
         for shuffle in (1, 2, 3):
             assert np.array_equal(host_thin_run(L, S, mode, shuffle=shuffle)[0], TR.thin(S, mode)[0])
+
+
+# ---- sets of isolated objects: the lemma, the shapes and the sets of the large device cases ----------------------------------------
+
+def lemma_objects():
+    """Four random objects of 13 x 11 x 9 at density 0.7 (one at an odd offset on every axis, two with keep), and a pair of
+    small ones with exactly two empty voxels between them, in a box of 70 x 64 x 40."""
+    rng = np.random.default_rng(2200)
+    objects = []
+    for i, origin in enumerate([(2, 4, 2), (41, 3, 5), (20, 30, 20), (48, 40, 24)]):
+        A = rng.random((9, 11, 13)) < 0.7
+        objects.append((origin, A, (rng.random(A.shape) < 0.05) if i in (1, 2) else None))
+    left, right = np.ones((5, 4, 6), bool), rng.random((5, 4, 6)) < 0.8
+    right[:, :, 0] = True                                      # (the facing sides are full: the gap is two voxels, no more)
+    objects += [((4, 52, 30), left, None), ((4 + 6 + 2, 52, 30), right, None)]
+    return (70, 64, 40), objects
+
+
+@pytest.mark.parametrize("mode", [TR.ULTIMATE, TR.CURVE])
+def test_the_locality_lemma(mode):
+    """tests/thinning_sets.py: objects two empty voxels apart thin as they do alone, in crops that keep the parities."""
+    dims, objects = lemma_objects()
+    assert TS.separation_holds(dims, objects) and all(o & 1 for o in objects[1][0])
+    assert not TS.separation_holds(dims, objects[:5] + [((11, 52, 30), objects[5][1], None)])          # (one empty voxel is too few)
+    S, keep = TS.grid_of(dims, TS.set_of(objects)), TS.grid_of(dims, TS.keep_of(objects))
+    assert keep.any() and (keep & S).any()
+    want, iterations, removed = TR.thin(S, mode, keep)
+    placements, skeleton, it, n = TS.isolated_objects(objects, mode)
+    assert np.array_equal(TS.grid_of(dims, skeleton), want)
+    alone = [TS.thin_alone(o, A, k, mode) for o, A, k in objects]
+    assert (it, n) == (iterations, removed) == (max(a[1] for a in alone), sum(a[2] for a in alone))
+    assert len({a[1] for a in alone}) > 1                                                               # (the maximum is of unequal counts)
+    assert all(K[k & A].all() for (_, A, k, K) in placements if k is not None)
+    print(f"mode {mode}: {int(S.sum())} -> {int(want.sum())} voxels in {iterations} = max{tuple(a[1] for a in alone)} iterations, {removed} removed")
+
+
+def test_a_crop_must_keep_the_parities():
+    """The object at the odd offset, thinned in a crop whose origin is odd (the object two voxels in, as if its own origin were
+    even): other bits than it has in the box."""
+    dims, objects = lemma_objects()
+    origin, A, keep = objects[1]
+    differs = 0
+    for mode in (TR.ULTIMATE, TR.CURVE):
+        right = TS.thin_alone(origin, A, keep, mode)[0]
+        wrong = TR.thin(np.pad(A, 2), mode, np.pad(keep, 2))[0][2:-2, 2:-2, 2:-2]
+        whole = TR.thin(TS.grid_of(dims, [(origin, A)]), mode, TS.grid_of(dims, [(origin, keep)]))[0]
+        assert np.array_equal(TS.grid_of(dims, [(origin, right)]), whole)
+        differs += not np.array_equal(wrong, right)
+    assert differs == 2
+
+
+CUS = (256, 304, 64)
+CHUNK_GRIDS = {"a": (3, 3), "b": (3, 70), "c": (32, 3)}        # tile_chunks' grids: (the chunk value wanted, nx)
+
+
+@pytest.mark.parametrize("cus", CUS)
+def test_the_shapes_hit_what_they_claim(cus):
+    """The host's choice restated (o2v_hip_thin_dense: chunk = clamp(tiles / (16 CUs), 1, 32), chunks = ceil(tiles / chunk), grid
+    = min(chunks, 2^20)): the boxes of tile_chunks and grid_turns get the chunk values they are built for, with ragged lists, and
+    the kernel's tile = thread * chunks + chunk over the grid's turns takes every tile once."""
+    text = open(os.path.join(SRC, "o2v_dev_host_k22_thinning.hpp")).read()
+    assert "tiles / ((uint64_t) ctx->num_cus * 16u), 1u), kThinChunk)" in text and "(tiles + chunk - 1u) / chunk, kCcMaxGrid)" in text
+    assert "constexpr uint32_t kThinChunk = 32u;" in open(K22).read() and "threadIdx.x * chunks + chunk" in open(K22).read()
+    assert "kCcMaxGrid = 1ull << 20;" in open(os.path.join(SRC, "o2v_dev_host_k12_components.hpp")).read()
+    for name, (want, nx) in CHUNK_GRIDS.items():
+        dims = TS.dims_for_chunk(cus, want, nx)
+        tiles = TS.tile_count(dims)
+        chunk, chunks, grid = TS.plan(tiles, cus)
+        assert chunk == want and tiles % chunk and grid == chunks <= TS.MAX_GRID and dims[0] == nx and dims[1] % 8 and dims[2] % 8, (name, dims)
+        seen, later = TS.visits(tiles, cus)
+        assert (seen == 1).all() and not len(later), name
+        assert max(dims) <= 65536 and dims[0] * dims[1] * dims[2] < 2 ** 31
+    assert TS.dims_for_chunk(256, 3, 3) == (3, 893, 895) and TS.dims_for_chunk(256, 32, 3) == (3, 2893, 2903)
+    # grid_turns: the same box on every device with 32 tiles per workgroup; a side less, and the chunks fit one turn
+    dims = TS.GRID_TURNS_DIMS
+    tiles = TS.tile_count(dims)
+    assert dims[1] * dims[2] == 2147395600 < 2 ** 31 <= 46341 ** 2 and tiles == 5793 ** 2 == 33558849
+    assert TS.plan(tiles, cus) == (32, 1048715, 1 << 20)
+    assert TS.plan(TS.tile_count((1, 46340, 46332)), cus)[1] <= 1 << 20 and TS.plan(5792 * 5793, cus)[1] <= 1 << 20
+    seen, later = TS.visits(tiles, cus)
+    assert (seen == 1).all() and len(later) == 139 and later[0] == 1 << 20 and later[-1] == 1048714
+    assert tiles % 32 == 1                                                                              # (the last chunk's list: one tile)
+
+
+@pytest.mark.parametrize("name, cus", [("a", 256), ("a", 64), ("b", 64), ("c", 64)])
+def test_the_sets_of_tile_chunks(name, cus):
+    """Objects separated as the lemma needs, inside the box; a candidate in every tile; every lattice object loses a voxel in
+    ULTIMATE; the palette's ten shapes all occur; the tiles of three workgroups' lists hold random objects."""
+    want, nx = CHUNK_GRIDS[name]
+    dims = TS.dims_for_chunk(cus, want, nx)
+    objects, what = TS.tile_chunks_objects(dims, cus, 7, with_keep=name == "a")
+    for origin, A, _ in objects:
+        b = TS.box_of(origin, A)
+        assert min(b[:3]) >= 0 and b[3] <= dims[0] and b[4] <= dims[1] and b[5] <= dims[2]
+    assert TS.separation_holds(dims, objects)
+    S = TS.grid_of(dims, TS.set_of(objects))
+    assert int(S.sum()) == sum(int(A.sum()) for _, A, _ in objects)
+    assert TS.tiles_with_candidates(dims, S).all()
+    lattice = objects[what["random"]:]
+    assert what["random"] >= 200 and what["lattice"] == len(lattice) > what["tiles"] // 2 and what["list_tiles"] == what["list_tiles_hit"] >= 2 * what["chunk"]
+    assert len({id(A) for _, A, _ in lattice}) == len(TS.PALETTE) >= 8
+    for origin, A, keep in lattice:
+        assert 2 <= origin[1] % 8 and origin[1] % 8 + 3 <= 6 and 2 <= origin[2] % 8 and origin[2] % 8 + 3 <= 6
+        assert dims[0] == 3 or (2 <= origin[0] % 64 and (origin[0] % 64 + 3 <= 62 or origin[0] + 3 > dims[0] - 3))
+        assert TS.thin_alone(origin, A, None, TR.ULTIMATE)[2] >= 1
+    assert (name == "a") == any(k is not None for _, _, k in lattice)
+    # consecutive entries of a workgroup's list differ in content: no two tiles t * chunks + c, (t + 1) * chunks + c of the first
+    # lists share a palette entry more often than chance (a tenth)
+    same = sum(TS._hash(t * what["chunks"] + c) % 10 == TS._hash((t + 1) * what["chunks"] + c) % 10 for c in range(200) for t in range(what["chunk"] - 1))
+    assert same < 0.2 * 200 * (what["chunk"] - 1)
+
+
+def test_the_set_of_grid_turns():
+    dims = TS.GRID_TURNS_DIMS
+    objects, required, what = TS.grid_turns_objects()
+    assert what["second_turn"] == 139 and what["required"] == 2 + 139 * 32 - 31 and what["random"] >= 200   # (chunk 1 048 714 has one tile)
+    placed = TS.set_of(objects)
+    hit = TS.tiles_hit(dims, placed)
+    assert set(required) <= hit and {0, what["tiles"] - 1} <= hit
+    z, y, x = TS.coords(placed)
+    assert x.max() == 0 and y.min() >= 0 and z.min() >= 0 and y.max() == dims[1] - 1 and z.max() == dims[2] - 1
+    assert bool(((y == dims[1] - 1) & (z == dims[2] - 1)).any())                                         # the last row and column
+    # separation, on the voxels: sorted keys, and no voxel of another object within two steps
+    owner = np.concatenate([np.full(int(A.sum()), i) for i, (_, A) in enumerate(placed)])
+    zz, yy, _ = (np.concatenate(v) for v in zip(*[TS.coords([p]) for p in placed]))
+    key = zz * dims[1] + yy
+    order = np.argsort(key)
+    key, owner, zz, yy = key[order], owner[order], zz[order], yy[order]
+    assert len(np.unique(key)) == len(key)
+    for dz in range(-2, 3):
+        for dy in range(-2, 3):
+            ok = (yy + dy >= 0) & (yy + dy < dims[1])
+            at = np.searchsorted(key, key + dz * dims[1] + dy)
+            found = ok & (at < len(key)) & (key[np.minimum(at, len(key) - 1)] == key + dz * dims[1] + dy)
+            assert (owner[np.minimum(at, len(key) - 1)][found] == owner[found]).all()
+    # objects cross tile borders: all but those pulled in at the box's end lie across a tile's corner, in four tiles
+    assert sum(o[1] % 8 == 5 and o[2] % 8 == 5 for o, _, _ in objects) >= 0.95 * len(objects)
+    for mode in (TR.ULTIMATE, TR.CURVE):
+        _, skeleton, iterations, removed = TS.isolated_objects(objects, mode)
+        assert iterations >= 3 and removed > 10 * len(objects)
+
+
+@pytest.mark.parametrize("axis", ["x", "y", "z"])
+def test_the_longest_axis_on_the_host_build(host_thin, axis):
+    """65 536 voxels along an axis, segments at both of its ends: thin_word's "-1 wraps to above any dim" and "one past the last"
+    with the largest dim there is, tile by tile and as whole-grid sweeps."""
+    S = TS.long_axis_set(axis)
+    K, iterations, removed = TR.thin(S, TR.ULTIMATE)
+    assert (np.argwhere(K)[:, {"x": 2, "y": 1, "z": 0}[axis]].tolist(), iterations, removed) == ([20, 32767, 65472, 65516], 11, 134)
+    for no_tiles in (False, True):
+        got, counts = host_thin_run(host_thin(), S, TR.ULTIMATE, no_tiles=no_tiles, shuffle=1)
+        assert np.array_equal(got, K) and (counts[0], counts[3]) == (iterations, removed), (axis, no_tiles)
 
 
 # ---- the torch layer against a stub ----------------------------------------------------------------------------------------------

@@ -16,6 +16,7 @@ import numpy as np
 
 from obj2voxel_amd import dense, hip, meshes
 from tests import thinning_ref as TR
+from tests import thinning_sets as TS
 from tests.components_cases import indexed, set_of
 from tests.dense_cases import expect_code3
 from tests.raycast_cases import dev, expect_code, formats, layouts
@@ -260,6 +261,212 @@ def case_pipeline():
               f"{want[1]} iterations, {after26} components, {ms:.1f} ms")
 
 
+# ---- sets of isolated objects (tests/thinning_sets.py: the lemma is tests/test_host_thinning.py's) ----------------------------------------
+
+def cus():
+    """The CU count the library reads for its choice of tiles per workgroup."""
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+class Isolated(Ref):
+    """The reference of a set of isolated objects, object by object: the Ref that check() takes, key "k" for the objects' keep."""
+
+    def __init__(self, dims, objects):
+        super().__init__(TS.grid_of(dims, TS.set_of(objects)))
+        self.dims, self.objects = dims, objects
+        self.bare = [(o, A, None) for o, A, _ in objects]
+        self.keep = TS.grid_of(dims, TS.keep_of(objects))
+
+    def get(self, mode, keep=None, cap=0, key=None):
+        assert cap == 0
+        k = (mode, key if keep is not None else None, 0)
+        if k not in self.memo:
+            _, skeleton, iterations, removed = TS.isolated_objects(self.objects if keep is not None else self.bare, mode)
+            self.memo[k] = (TS.grid_of(self.dims, skeleton), iterations, removed)
+        return self.memo[k]
+
+
+class FixedRef(Ref):
+    """A Ref with one result that needs no computing."""
+
+    def __init__(self, S, mode, K, iterations, removed):
+        super().__init__(S)
+        self.memo[mode, None, 0] = (np.asarray(K, bool), iterations, removed)
+
+
+def chunk_grid(name, with_keep=False):
+    """Grid (a), (b) or (c) of tile_chunks for this device: (dims, what, its Isolated reference)."""
+    want, nx = {"a": (3, 3), "b": (3, 70), "c": (32, 3)}[name]
+    dims = TS.dims_for_chunk(cus(), want, nx)
+    objects, what = TS.tile_chunks_objects(dims, cus(), 7, with_keep=with_keep)
+    assert what["chunk"] == want and what["tiles"] % want and what["list_tiles"] == what["list_tiles_hit"]
+    return dims, what, Isolated(dims, objects)
+
+
+def turns_within(counters, what, tiled=True):
+    """The tile-turn counter: every tile has a candidate in iteration 1, and none runs more than 8 sub-steps an iteration."""
+    assert what["tiles"] <= counters[2] <= 8 * counters[0] * what["tiles"] and (tiled or counters[2] == 8 * counters[0] * what["tiles"]), (counters, what)
+
+
+# ---- tile_chunks -----------------------------------------------------------------------------------------------------------------------
+
+def case_tile_chunks():
+    """Several tiles per workgroup (the host's own choice for boxes of this many tiles), ragged lists, LDS rows reused from tile
+    to tile: a lattice object in every tile and random objects across the tiles, against the objects' references."""
+    dv = hip.DeviceVoxelizer(0)
+    for name in ("a", "b", "c"):
+        dims, what, ref = chunk_grid(name, with_keep=name == "a")
+        t = dev(ref.S.astype(np.uint8))
+        for mode in MODES:
+            for off in ((False, True) if name != "c" else (False,)):
+                no_tiles(off)
+                _, counters = check(dv, t, ref, mode, what=(name, off))
+                turns_within(counters, what, not off)
+                print(f"tile_chunks ({name}) {dims[0]} x {dims[1]} x {dims[2]}, {cus()} CUs: {what['tiles']} tiles, chunk {what['chunk']}, {what['chunks']} chunks, "
+                      f"{what['lattice']} + {what['random']} objects, {what['list_tiles']} tiles of whole lists under random objects; {MODES[mode]}"
+                      f"{', no tiles' if off else ''}: {counters[0]} iterations, {counters[3]} removed, {counters[2]} tile turns")
+            no_tiles(False)
+        if name == "a":
+            keep = dev(ref.keep.astype(np.uint8))
+            out, counters = check(dv, t, ref, TR.ULTIMATE, keep=keep, keep_np=ref.keep, keep_key="k", what="(a) with keep")
+            turns_within(counters, what)
+            assert bool(out[keep != 0].all()) and not np.array_equal(ref.get(TR.ULTIMATE, ref.keep, 0, "k")[0], ref.get(TR.ULTIMATE)[0])
+            print(f"tile_chunks (a) with keep on {int(ref.keep.sum())} lattice voxels: {counters[0]} iterations, {counters[3]} removed")
+        del t
+    print("tile_chunks: chunk 3 and 32, ragged, both modes")
+
+
+# ---- grid_turns ------------------------------------------------------------------------------------------------------------------------
+
+def case_grid_turns():
+    """More than 2^20 chunks: the chunk loop's second turn, words and voxels near 2^31, in place on a uint8 grid."""
+    dims = TS.GRID_TURNS_DIMS
+    objects, required, what = TS.grid_turns_objects(dims, cus())
+    assert (what["tiles"], what["chunk"], what["chunks"], what["grid"], what["second_turn"]) == (33558849, 32, 1048715, 1 << 20, 139)
+    words = dims[1] * dims[2]
+    assert hip.thin_scratch_bytes(dims) == 16 * words + 8 * what["tiles"] + 64
+    dv = hip.DeviceVoxelizer(0)
+
+    def paint(t, placed):
+        z, y, x = TS.coords(placed)
+        t.view(-1)[torch.from_numpy((z * dims[1] + y) * dims[0] + x).to(DEV)] = 1
+
+    grid = torch.zeros((dims[2], dims[1], dims[0]), dtype=torch.uint8, device=DEV)
+    want = torch.zeros_like(grid)
+    for mode in MODES:
+        _, skeleton, iterations, removed = TS.isolated_objects(objects, mode)
+        grid.zero_(), want.zero_()
+        paint(grid, TS.set_of(objects)), paint(want, skeleton)
+        t0 = time.time()
+        counters = raw(dv, grid, None, mode, 0, 0, None, grid, hip.THIN_DST_MASK)
+        seconds = time.time() - t0
+        assert torch.equal(grid, want), (MODES[mode], int((grid != want).sum()), "voxels differ")
+        assert (counters[0], counters[3]) == (iterations, removed) and counters[1] == 9 * iterations, (MODES[mode], counters, iterations, removed)
+        assert counters[2] <= 8 * iterations * what["tiles"]
+        print(f"grid_turns 1 x {dims[1]} x {dims[2]} ({words} words, scratch {hip.thin_scratch_bytes(dims)} B): {what['tiles']} tiles, chunk {what['chunk']}, "
+              f"{what['chunks']} chunks on {what['grid']} workgroups, {what['second_turn']} second-turn chunks with {what['required'] - 2} tiles under objects, "
+              f"{len(objects)} objects; {MODES[mode]}: {counters[0]} iterations, {counters[3]} removed, {counters[2]} tile turns, call {seconds:.2f} s "
+              f"(classify, iterate, write: {', '.join('%.1f' % ms for ms in dv.thin_times())} ms)")
+
+
+# ---- long_runs -------------------------------------------------------------------------------------------------------------------------
+
+def case_long_runs():
+    """Hundreds of iterations: the stamps' two slots by the parity of the iteration, tiles that sleep until the front arrives."""
+    dv = hip.DeviceVoxelizer(0)
+    diagonal = np.zeros((74, 74, 74), bool)
+    diagonal[np.arange(1, 73), np.arange(1, 73), np.arange(1, 73)] = True
+    sets = [(f"line {axis}", TR.line(axis, 2051, 1)) for axis in "xyz"] + [("diagonal", diagonal)]
+    for name, S in sets:
+        if "line" in name:
+            S = np.pad(S, [(0, n == 2051) for n in S.shape])                                         # voxels 1 ... 2050 of 2052
+            assert int(S.sum()) == 2050 and sorted(S.shape) == [3, 3, 2052]
+        ref, t = Ref(S), dev(S.astype(np.uint8))
+        turns = {}
+        for off in (False, True):
+            no_tiles(off)
+            a, counters = check(dv, t, ref, TR.ULTIMATE, what=(name, off))
+            b, again = check(dv, t, ref, TR.ULTIMATE, what=(name, off, "again"))
+            assert torch.equal(a, b) and counters[:2] == again[:2] and counters[3] == again[3]
+            turns[off] = counters[2]
+        no_tiles(False)
+        K, it, removed = ref.get(TR.ULTIMATE)
+        at = np.argwhere(K)[:, ::-1].tolist()
+        print(f"long_runs {name} (ultimate): {int(S.sum())} -> {at} (x, y, z) in {it} iterations, {removed} removed; tile turns {turns[False]}, without the tile rule {turns[True]}")
+        assert len(at) == 1 and removed == int(S.sum()) - 1
+        if name == "line x":
+            assert (at, it, removed) == ([[1025, 1, 1]], 514, 2049)
+        if name == "diagonal":
+            assert (at, it, removed) == ([[36, 36, 36]], 19, 71) and turns[False] * 4 < turns[True]
+        else:
+            assert it > 500 and turns[False] * 20 < turns[True]
+            for off in (False, True):
+                no_tiles(off)
+                _, counters = check(dv, t, FixedRef(S, TR.CURVE, S, 1, 0), TR.CURVE, what=(name, "curve", off))
+                assert counters[0] == 1
+            no_tiles(False)
+    print("long_runs: lines of 2050 voxels along x, y and z and the diagonal of 72")
+
+
+# ---- long_axes -------------------------------------------------------------------------------------------------------------------------
+
+def case_long_axes():
+    """65 536 voxels along an axis - the documented limit -, segments at both ends of it and across its middle."""
+    dv = hip.DeviceVoxelizer(0)
+    n = TS.LONG_AXIS
+    for axis in "xyz":
+        S = TS.long_axis_set(axis)
+        ref, t = Ref(S), dev(S.astype(np.uint8))
+        K, it, removed = ref.get(TR.ULTIMATE)
+        survivors = np.argwhere(K)[:, {"x": 2, "y": 1, "z": 0}[axis]].tolist()
+        assert (survivors, it, removed) == ([20, 32767, 65472, 65516], 11, 134), (axis, survivors, it, removed)
+        for off in (False, True):
+            no_tiles(off)
+            for mode in MODES:
+                for degree in (False, True):
+                    check(dv, t, ref, mode, degree=degree, what=(axis, off))
+        no_tiles(False)
+        print(f"long_axes {axis}: {int(S.sum())} voxels in four segments of a box of {n} along {axis}; ultimate leaves {survivors} in {it} iterations, {removed} removed; "
+              f"curve {ref.get(TR.CURVE)[1:]}")
+    one = torch.zeros((1,), dtype=torch.uint8, device=DEV)
+    expect_code(5, lambda: dv.thin_dense(one.data_ptr(), hip.GRID_U8, (0, 0, 0), (n + 1, 1, 1), 0.0, 0, hip.THIN_CURVE, 0, None, None, one.data_ptr(), (0, 0, 0), hip.THIN_DST_MASK), "65 537")
+    print("long_axes: 65 536 along x, y and z, both modes, both tile modes, mask and degree")
+
+
+# ---- call_sequence ---------------------------------------------------------------------------------------------------------------------
+
+def case_call_sequence():
+    """One context through calls of different sizes, with and without keep and tiles: the scratch (set, border and keep bits, the
+    stamps) is grown on demand and reused, and every call gives what a fresh context gives."""
+    rng = np.random.default_rng(61)
+    dims, what, big = chunk_grid("a", with_keep=True)
+    small, mid, flat = TR.random_grid(rng, (70, 19, 21), 0.6), TR.random_grid(rng, (130, 19, 17), 0.6), np.ones((9, 9, 70), bool)
+    small_keep = rng.random(small.shape) < 0.03
+    refs = {"big": big, "small": Ref(small), "mid": Ref(mid), "flat": Ref(flat)}
+    tensors = {k: dev(r.S.astype(np.uint8)) for k, r in refs.items()}
+    keeps = {"big": (dev(big.keep.astype(np.uint8)), big.keep), "small": (dev(small_keep.astype(np.uint8)), small_keep)}
+    # (set, mode, keep, no tiles, cap, degree)
+    calls = [("big", TR.ULTIMATE, False, False, 0, False), ("small", TR.CURVE, True, False, 0, False), ("mid", TR.ULTIMATE, False, False, 0, False),
+             ("mid", TR.ULTIMATE, False, True, 0, False), ("big", TR.ULTIMATE, True, False, 0, False), ("flat", TR.CURVE, False, False, 1, True)]
+
+    def call(dv, name, mode, keep, off, cap, degree):
+        no_tiles(off)
+        kt, kn = keeps[name] if keep else (None, None)
+        out, counters = check(dv, tensors[name], refs[name], mode, keep=kt, keep_np=kn, keep_key="k", cap=cap, degree=degree, what=("call_sequence", name, keep, off))
+        no_tiles(False)
+        return out, counters
+    one = hip.DeviceVoxelizer(0)
+    for i, c in enumerate(calls):
+        a, ca = call(one, *c)
+        fresh = hip.DeviceVoxelizer(0)
+        b, cb = call(fresh, *c)
+        fresh.close()
+        assert torch.equal(a, b) and ca[:2] == cb[:2] and ca[3] == cb[3], (i, c, ca, cb)
+        print(f"call_sequence {i + 1}: {c[0]} {tuple(refs[c[0]].S.shape[::-1])}, {MODES[c[1]]}{', keep' if c[2] else ''}{', no tiles' if c[3] else ''}"
+              f"{', 1 iteration, degree' if c[4] else ''}: counters {ca}")
+    print(f"call_sequence: six calls on one context, each equal to the reference and to a fresh context ({what['tiles']} tiles, chunk {what['chunk']} in 1 and 5)")
+
+
 # ---- refusals --------------------------------------------------------------------------------------------------------------------------
 
 def case_refusals():
@@ -340,7 +547,8 @@ def case_refusals():
 
 
 CASES = {"formats_and_layouts": case_formats_and_layouts, "known_shapes": case_known_shapes, "tile_borders": case_tile_borders,
-         "keep_and_caps": case_keep_and_caps, "degree": case_degree, "pipeline": case_pipeline, "refusals": case_refusals}
+         "keep_and_caps": case_keep_and_caps, "degree": case_degree, "pipeline": case_pipeline, "refusals": case_refusals, "tile_chunks": case_tile_chunks,
+         "grid_turns": case_grid_turns, "long_runs": case_long_runs, "long_axes": case_long_axes, "call_sequence": case_call_sequence}
 
 if __name__ == "__main__":
     t0 = time.time()

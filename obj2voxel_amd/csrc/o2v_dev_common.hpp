@@ -170,6 +170,11 @@ struct Params {
     uint32_t cap_dirty;    // entries of each dirty-brick list
     uint32_t bounds_known;
     float bounds[6];
+    // Occupancy-only mode with the bounds in effect on the host (the caller's, or the upload's): the mesh transform of the call,
+    // computed on the host (compute_mesh_transform gives the same floats there), and k_setup is not launched.  The kernels of
+    // a pass take the transform through pass_xform() / pass_transform(), never from Counters::xform directly.
+    uint32_t xform_known;
+    float xform[12];
     int32_t unit[9];
     uint32_t has_uv;
     // Occupancy-only mode: every triangle is MATERIALLESS, so every voxel's colour is white whatever the weights are (MAX
@@ -230,6 +235,24 @@ __device__ __forceinline__ bool pools_no_hits(const Counters *c, const Params &p
 __device__ __forceinline__ bool pass_overflowed(const Counters *c, const Params &p)
 {
     return c->n_hits_reserved > p.cap_hits || c->n_sorted > p.cap_hits || c->n_vox > p.cap_vox;
+}
+
+// The mesh transform of the pass: the call's own (Params::xform, a kernel argument) where the host computed it, else what
+// k_setup left in the counters.  i: 0 .. 8 the matrix by rows, 9 .. 11 the translation.
+__device__ __forceinline__ float pass_xform(const Counters *c, const Params &p, int i) { return p.xform_known ? p.xform[i] : c->xform[i]; }
+__device__ __forceinline__ Affine pass_transform(const Counters *c, const Params &p)
+{
+    // (one uniform branch: the kernel arguments are read as scalars, and only the other side loads from global memory)
+    Affine a;
+    if (p.xform_known) {
+        for (int i = 0; i < 3; ++i) a.m[i] = {p.xform[i * 3], p.xform[i * 3 + 1], p.xform[i * 3 + 2]};
+        a.t = {p.xform[9], p.xform[10], p.xform[11]};
+    }
+    else {
+        for (int i = 0; i < 3; ++i) a.m[i] = {c->xform[i * 3], c->xform[i * 3 + 1], c->xform[i * 3 + 2]};
+        a.t = {c->xform[9], c->xform[10], c->xform[11]};
+    }
+    return a;
 }
 
 __device__ __forceinline__ uint32_t f2ord(float f)

@@ -160,6 +160,8 @@ __global__ __launch_bounds__(kBlock) void k_tri_extent(const float *__restrict__
     }
 }
 
+// The mesh transform of a pass, by one lane, into Counters::xform.  Not launched where the host computed the transform
+// (Params::xform_known, the occupancy-only route: o2v_hip_voxelize) - the kernels read it through pass_transform().
 __global__ void k_setup(Counters *c, Params p)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;

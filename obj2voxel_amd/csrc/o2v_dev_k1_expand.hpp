@@ -175,7 +175,7 @@ __global__ __launch_bounds__(kBlock) void k_list_blocks(const float2 *__restrict
                                                         const Counters *c, uint32_t *list, uint32_t *count, Params p)
 {
     bool valid = true;
-    for (int i = 0; i < 12; ++i) valid &= __float_as_uint(zrange_xform[i]) == __float_as_uint(c->xform[i]);
+    for (int i = 0; i < 12; ++i) valid &= __float_as_uint(zrange_xform[i]) == __float_as_uint(pass_xform(c, p, i));
     if (!valid) {
         if (blockIdx.x == 0 && threadIdx.x == 0) *count = 0xffffffffu;
         return;
@@ -218,16 +218,12 @@ __global__ __launch_bounds__(kBlock) void k_expand_roots(const float *__restrict
     unsigned long long my_bypass = 0, my_bypass_cand = 0, my_bypass_sq = 0;
     if (threadIdx.x < 3) s_bypass[threadIdx.x] = 0;
 
-    Affine xf;
-    xf.m[0] = {c->xform[0], c->xform[1], c->xform[2]};
-    xf.m[1] = {c->xform[3], c->xform[4], c->xform[5]};
-    xf.m[2] = {c->xform[6], c->xform[7], c->xform[8]};
-    xf.t = {c->xform[9], c->xform[10], c->xform[11]};
+    const Affine xf = pass_transform(c, p);
 
     // z extents per block of 256 triangles from the slab plan (k_zhist), valid if they were made with this transform
     bool use_zrange = zrange != nullptr;
     if (use_zrange)
-        for (int i = 0; i < 12; ++i) use_zrange &= __float_as_uint(zrange_xform[i]) == __float_as_uint(c->xform[i]);
+        for (int i = 0; i < 12; ++i) use_zrange &= __float_as_uint(zrange_xform[i]) == __float_as_uint(pass_xform(c, p, i));
 
     // One reservation (a handful of global atomics on the same few addresses, which serialise at ~88 per us) per
     // kRootBatch sub-batches of 256 triangles: the sub-batches are classified twice - first only to count what they
@@ -450,11 +446,7 @@ __global__ __launch_bounds__(kBlock) void k_count_roots(const float *__restrict_
     __shared__ unsigned long long s_sum[3];
     if (threadIdx.x < 3) s_sum[threadIdx.x] = 0;
     __syncthreads();
-    Affine xf;
-    xf.m[0] = {c->xform[0], c->xform[1], c->xform[2]};
-    xf.m[1] = {c->xform[3], c->xform[4], c->xform[5]};
-    xf.m[2] = {c->xform[6], c->xform[7], c->xform[8]};
-    xf.t = {c->xform[9], c->xform[10], c->xform[11]};
+    const Affine xf = pass_transform(c, p);
     const bool listed = seq_list != nullptr && *seq_count != 0xffffffffu;
     const uint64_t n_seq = listed ? (uint64_t) *seq_count : (p.n_tris + kBlock - 1) / kBlock;
     const uint32_t lane = threadIdx.x & 63u;

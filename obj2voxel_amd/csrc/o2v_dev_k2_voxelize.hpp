@@ -710,11 +710,7 @@ __device__ __forceinline__ void voxelize_body(const Leaf *__restrict__ leaves, c
             bool solo_leaf = false, solo_other = false;
             uint32_t solo_cnt = 0;
             if (threadIdx.x < nt) {
-                Affine xf;
-                xf.m[0] = {c->xform[0], c->xform[1], c->xform[2]};
-                xf.m[1] = {c->xform[3], c->xform[4], c->xform[5]};
-                xf.m[2] = {c->xform[6], c->xform[7], c->xform[8]};
-                xf.t = {c->xform[9], c->xform[10], c->xform[11]};
+                const Affine xf = pass_transform(c, p);
                 Sub sb{};
                 sb.v0 = affine_apply(xf, V3{q[0], q[1], q[2]});
                 sb.v1 = affine_apply(xf, V3{q[3], q[4], q[5]});

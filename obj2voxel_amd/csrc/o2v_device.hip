@@ -333,8 +333,14 @@ struct o2v_hip_ctx {
     bool lean_roots = false;          // this call: k_count_roots ahead of k_expand_roots (choose_routes)
     bool solo_roots = false;          // this call: no k_expand_roots at all, k_voxelize_occ counts the root leaves itself (plan_rounds)
     uint64_t solo_refused_key = 0;    // the mesh and settings for which a solo pass found a triangle that needs k_expand_roots
-    float mesh_bounds_hint[6] = {0, 0, 0, 0, 0, 0};  // bounds and largest triangle extent of the uploaded mesh: only used to
-    float max_tri_extent = -1.f;                     // bound the number of subdivision rounds (-1: unknown)
+    float mesh_bounds_hint[6] = {0, 0, 0, 0, 0, 0};  // bounds of the uploaded mesh, k_bounds' own result at the upload (or another rank's,
+                                                     // TriHints): they place the dense grids (grid_box), scale the estimates from the
+                                                     // hints (mesh_scale) and, on the occupancy-only route, are the bounds of the pass
+                                                     // itself (host_transform, o2v_hip_voxelize: no k_bounds, no k_setup)
+    uint64_t bounds_generation = ~0ull;              // ... valid while this equals tri_generation (ctx_finish_triangles sets it, whatever
+                                                     // replaces or appends triangles clears it)
+    float max_tri_extent = -1.f;                     // largest triangle extent of the uploaded mesh: bounds the number of subdivision
+                                                     // rounds (-1: unknown)
     uint32_t ext_hist[256] = {};                     // k_tri_extent: the uploaded mesh's triangles by the binary exponent of their extent
                                                      // (grid_modes: is the 64-bit max grid worth its memory?)
     uint64_t tri_generation = 0, zrange_generation = ~0ull;  // the extents belong to the triangles of that upload
@@ -719,7 +725,34 @@ struct GridBox {
     uint32_t lo[3], hi[3];  // output space, [lo, hi); lo[0], lo[1] multiples of the brick edge
     bool empty;             // the slab does not meet the mesh's box: nothing to voxelize
 };
-GridBox grid_box(const o2v_hip_ctx *ctx, const o2v_hip_params *params, const Switches &sw, uint32_t ss, uint32_t z0, uint32_t z1)
+
+// The bounds in effect of a call where the host knows them - the caller's, else the upload's while they belong to the uploaded
+// triangles (ctx->bounds_generation) - and the mesh transform from them: compute_mesh_transform gives the same floats on the host
+// as in k_setup (-ffp-contract=off; o2v_math.h).  Computed once per call: grid_box places the grids with it, and on the
+// occupancy-only route the kernels get it as an argument (Params::xform; o2v_hip_voxelize).
+struct HostTransform {
+    bool have = false;    // bounds[] and a are set
+    bool finite = false;  // ... and all six bounds are finite
+    float bounds[6] = {};
+    Affine a{};
+};
+bool upload_bounds_valid(const o2v_hip_ctx *ctx) { return ctx->bounds_generation == ctx->tri_generation; }
+HostTransform host_transform(const o2v_hip_ctx *ctx, const o2v_hip_params *params, uint32_t S)
+{
+    HostTransform t;
+    const float *e = params->bounds_known ? params->bounds : upload_bounds_valid(ctx) ? ctx->mesh_bounds_hint : nullptr;
+    if (!e || ctx->n_tris == 0) return t;
+    t.have = t.finite = true;
+    for (int i = 0; i < 6; ++i) {
+        t.bounds[i] = e[i];
+        t.finite &= std::isfinite(e[i]);
+    }
+    t.a = compute_mesh_transform(V3{e[0], e[1], e[2]}, V3{e[3], e[4], e[5]}, S, params->unit_transform);
+    return t;
+}
+
+GridBox grid_box(const o2v_hip_ctx *ctx, const o2v_hip_params *params, const Switches &sw, const HostTransform &xf, uint32_t ss, uint32_t z0,
+                 uint32_t z1)
 {
     const uint32_t G = params->resolution, S = G * ss;
     GridBox b{{0u, 0u, z0}, {G, G, z1}, false};
@@ -733,12 +766,11 @@ GridBox grid_box(const o2v_hip_ctx *ctx, const o2v_hip_params *params, const Swi
         b.hi[1] = std::min(params->y_end, G);
     }
     if (b.lo[0] >= b.hi[0] || b.lo[1] >= b.hi[1]) b.empty = true;
-    if (sw.no_crop || ctx->max_tri_extent < 0.f || ctx->n_tris == 0) return b;
+    if (sw.no_crop || !upload_bounds_valid(ctx) || !xf.have) return b;
     const float *h = ctx->mesh_bounds_hint;
     for (int i = 0; i < 6; ++i)
         if (!std::isfinite(h[i])) return b;
-    const float *e = params->bounds_known ? params->bounds : h;
-    const Affine a = compute_mesh_transform(V3{e[0], e[1], e[2]}, V3{e[3], e[4], e[5]}, S, params->unit_transform);
+    const Affine &a = xf.a;  // (of the bounds in effect: the caller's, or the mesh's own)
     double mn[3] = {1e300, 1e300, 1e300}, mx[3] = {-1e300, -1e300, -1e300};
     for (int corner = 0; corner < 8; ++corner) {
         const V3 t = affine_apply(a, V3{h[(corner & 1) ? 3 : 0], h[(corner & 2) ? 4 : 1], h[(corner & 4) ? 5 : 2]});
@@ -781,7 +813,8 @@ int launch_expand(o2v_hip_ctx *ctx, const Params &p, const Switches &sw, uint32_
                            dim3(kBoundsBlock), 0, s, ctx->d_verts.ptr, p.n_tris * 9, ctr);
     }
     // (letting the last workgroup of k_bounds compute the transform - one launch less - was measured: the stage 0.021 -> 0.027 ms)
-    O2V_LAUNCH("k_setup", s, k_setup, dim3(1), dim3(64), 0, s, ctr, p);
+    // (occupancy only with the bounds in effect on the host: the transform is in p already, o2v_hip_voxelize - neither launch)
+    if (!p.xform_known) O2V_LAUNCH("k_setup", s, k_setup, dim3(1), dim3(64), 0, s, ctr, p);
     if (ctx->stage_events) O2V_CHECK(ctx->pass_times.mark(1, s));
 
     // After a slab plan the z extent of every block of 256 triangles is known: a slab that is not the whole grid visits only
@@ -1069,13 +1102,18 @@ int run_pass(o2v_hip_ctx *ctx, const Params &p, const Switches &sw, bool use_uv,
                            ctx->d_out.ptr, p);
     }
     if (ctx->stage_events) O2V_CHECK(ctx->pass_times.mark(5, s));
-    return finish_pass(ctx);
+    if ((rc = finish_pass(ctx))) return rc;
+    // (a pass that got its transform as an argument: the counters' copy has arrived, the host puts the transform where k_setup's
+    // would be - publish and the fill stage read it there)
+    if (p.xform_known) std::memcpy(ctx->h_ctr.ptr->xform, p.xform, sizeof(p.xform));
+    return O2V_HIP_OK;
 }
 
 // One o2v_hip_voxelize call: its pass geometry and routes (Params), and what its passes ask of the buffers.
 struct Run {
     Params p{};
     GridBox box{};             // the pass box (output space)
+    HostTransform xf{};        // the bounds in effect and the transform from them, where the host knows them
     bool use_uv = false;
     uint64_t n_bricks = 0;
     uint32_t n_rounds = 0;     // subdivision rounds launched
@@ -1123,7 +1161,8 @@ int pass_geometry(o2v_hip_ctx *ctx, const o2v_hip_params *params, const Switches
     p.S = (uint32_t) S64;
     p.G = params->resolution;
     // the dense grids cover the mesh's voxel bounding box within the slab (grid_box)
-    const GridBox box = grid_box(ctx, params, sw, ss, z0, z1);   // (within the x / y tile, if the call names one)
+    r.xf = host_transform(ctx, params, p.S);  // (once per call: for the grids' box here, for the kernels in host_k0)
+    const GridBox box = grid_box(ctx, params, sw, r.xf, ss, z0, z1);   // (within the x / y tile, if the call names one)
     r.box = box;
     empty = box.empty;
     if (empty) return O2V_HIP_OK;
@@ -1282,6 +1321,28 @@ int ensure_grids(o2v_hip_ctx *ctx, Run &r)
         if ((rc = ensure_count_grid(ctx, r.n_bricks))) return rc;
     }
     return O2V_HIP_OK;
+}
+
+// K0 on the host, decided once per call (every pass of the call launches the same kernels): on the occupancy-only route, with
+// the bounds in effect on the host and finite - the caller's, the sharded step's reduced ones (they arrive as the caller's), or
+// the upload's, which k_bounds itself made from these triangles (min and max are exact and order-free: the same six floats) -
+// the pass gets the bounds and the transform as arguments and launches neither k_bounds nor k_setup.  Bounds that are unknown or
+// not finite, an empty mesh and the weighted routes keep both launches; so does O2V_ALL_LAUNCHES=1 (A/B).
+void host_k0(const Switches &sw, Run &r)
+{
+    Params &p = r.p;
+    if (!p.occupancy_only || !r.xf.have || !r.xf.finite || sw.all_launches) return;
+    p.bounds_known = 1;
+    for (int i = 0; i < 6; ++i) p.bounds[i] = r.xf.bounds[i];
+    p.xform_known = 1;
+    for (int i = 0; i < 3; ++i) {
+        p.xform[i * 3 + 0] = r.xf.a.m[i].x;
+        p.xform[i * 3 + 1] = r.xf.a.m[i].y;
+        p.xform[i * 3 + 2] = r.xf.a.m[i].z;
+    }
+    p.xform[9] = r.xf.a.t.x;
+    p.xform[10] = r.xf.a.t.y;
+    p.xform[11] = r.xf.a.t.z;
 }
 
 // The capacities the first pass asks for.
@@ -1668,6 +1729,7 @@ int voxelize(o2v_hip_ctx *ctx, const o2v_hip_params *params, const Switches &sw,
     choose_routes(ctx, params, sw, r);
     if ((rc = ensure_grids(ctx, r))) return rc;
     if (ctx->n_tris == 0) return O2V_HIP_OK;  // empty mesh: empty model (obj2voxel.cpp:590-594)
+    host_k0(sw, r);  // (behind ensure_grids: the route is final)
     // (= workgroups x VoxShape::queue for every shape; twice that for k_voxelize_occ)
     const uint64_t jobq = (uint64_t) ctx->num_cus * (O2V_K2_WAVES > O2V_K2_WAVES_UV ? O2V_K2_WAVES : O2V_K2_WAVES_UV) * (kBlock / 64u) * (64u * 64u) * 2u;
     if ((rc = grow(ctx, ctx->d_jobq, jobq))) return rc;
@@ -1725,6 +1787,7 @@ int ctx_alloc_triangles(o2v_hip_ctx *ctx, uint64_t count, bool uvs, bool types, 
         return rc;
     ctx->n_tris = count;
     ctx->tri_generation += 1;
+    ctx->bounds_generation = ~0ull;  // (the arrays are about to be replaced: ctx_finish_triangles brings the new bounds)
     ctx->max_tri_extent = -1.f;
     ctx->any_textured = false;
     return O2V_HIP_OK;
@@ -1756,6 +1819,7 @@ int ctx_finish_triangles(o2v_hip_ctx *ctx, bool any_textured, const TriHints *hi
     ctx->any_textured = any_textured;
     if (hints) {
         for (int i = 0; i < 6; ++i) ctx->mesh_bounds_hint[i] = hints->bounds[i];
+        ctx->bounds_generation = ctx->tri_generation;
         ctx->max_tri_extent = hints->max_tri_extent;
         std::memcpy(ctx->ext_hist, hints->ext_hist, sizeof(ctx->ext_hist));
         ctx->any_textured = hints->any_textured;
@@ -1771,6 +1835,7 @@ int ctx_finish_triangles(o2v_hip_ctx *ctx, bool any_textured, const TriHints *hi
         O2V_CHECK(hipMemcpyAsync(ctx->h_ctr.ptr, ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
         O2V_CHECK(hipStreamSynchronize(s));
         for (int i = 0; i < 6; ++i) ctx->mesh_bounds_hint[i] = ord2f_host(ctx->h_ctr.ptr->bounds_enc[i]);
+        ctx->bounds_generation = ctx->tri_generation;
         ctx->max_tri_extent = ord2f_host(ctx->h_ctr.ptr->pad2);
         std::memcpy(ctx->ext_hist, ctx->h_ctr.ptr->ext_hist, sizeof(ctx->ext_hist));
         return O2V_HIP_OK;
@@ -1896,6 +1961,7 @@ int o2v_hip_begin_triangles(o2v_hip_ctx *ctx, o2v_hip_staging *out_block)
     ctx->stream_count = 0;
     ctx->stream_arrays = 0;
     ctx->n_tris = 0;
+    ctx->bounds_generation = ~0ull;  // (the commits write over the arrays: the upload's bounds are nobody's until o2v_hip_end_triangles)
     *out_block = ctx->stage[0].view();
     return O2V_HIP_OK;
 }
@@ -1950,6 +2016,7 @@ int o2v_hip_commit_triangles(o2v_hip_ctx *ctx, uint64_t count, uint32_t arrays, 
         return rc;
     O2V_CHECK(hipEventRecord(ctx->ev_stage[ctx->stage_cur], s));
     ctx->stream_count = need;
+    ctx->bounds_generation = ~0ull;  // (triangles appended)
     ctx->stage_cur ^= 1;
     O2V_CHECK(hipEventSynchronize(ctx->ev_stage[ctx->stage_cur]));  // the other block's copy (two commits ago) has landed
     *out_next_block = ctx->stage[ctx->stage_cur].view();
@@ -1967,6 +2034,7 @@ int o2v_hip_end_triangles(o2v_hip_ctx *ctx, uint32_t any_textured)
     if (!(ctx->stream_arrays & O2V_HIP_ARRAY_TEXIDS)) retire(ctx, ctx->d_texids);
     ctx->n_tris = ctx->stream_count;
     ctx->tri_generation += 1;
+    ctx->bounds_generation = ~0ull;
     ctx->max_tri_extent = -1.f;
     const int rc = o2v::ctx_finish_triangles(ctx, any_textured != 0, nullptr);  // waits for the stream
     ctx->retired.clear();
@@ -2370,7 +2438,7 @@ int o2v_hip_max_slab_layers(o2v_hip_ctx *ctx, const o2v_hip_params *params, uint
     // (a layer of the grids is as wide as the mesh's voxel bounding box, grid_box)
     const uint32_t ss_l = params->supersampling ? params->supersampling : 1u;
     const Switches sw = read_switches();
-    const GridBox box = grid_box(ctx, params, sw, ss_l, 0u, params->resolution);
+    const GridBox box = grid_box(ctx, params, sw, host_transform(ctx, params, params->resolution * ss_l), ss_l, 0u, params->resolution);
     const uint64_t per_layer_bricks = box.empty ? 1ull
                                                 : (uint64_t) ((box.hi[0] - box.lo[0] + kBrickX - 1) / kBrickX) * ((box.hi[1] - box.lo[1] + kBrickY - 1) / kBrickY);
     // per brick: occupancy only (no triangle of the uploaded mesh has a material) one byte per cell; else the 32-bit counter

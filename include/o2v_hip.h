@@ -1059,6 +1059,65 @@ int o2v_hip_thin_times(const o2v_hip_ctx *ctx, float out_ms[3]);
  * them - a tile stamped by a neighbour while a launch runs may or may not count in that launch) and the voxels removed. */
 int o2v_hip_thin_counters(const o2v_hip_ctx *ctx, uint64_t out4[4]);
 
+/* ---- parts of a dense grid: watershed basins of a relief, merged by persistence ---------------------------
+ *
+ * Where one part ends and the next begins: two rooms joined by a corridor, two grains sintered at a neck.  The relief is usually a
+ * depth map (o2v_hip_thickness_dense's depth2, or a scaled square root of it); every top of the relief gets a part, and spurious
+ * tops are merged into their neighbours by how deep the pass between them is.
+ *
+ * The definition.
+ *   Relief.  H is an int32 grid, indexed [z, y, x], with any element strides.
+ *   The set.  S = { v : H[v] > 0 }.  Voxels outside the box are not in S.
+ *   Index.  i(v) = (z * ny + y) * nx + x.  It stays below 2^31 by o2v_hip_components_dense's limits: a dim of at most 65 536 and at
+ *   most 2^31 - 1 voxels.
+ *   Key.  K(v) = (H[v], i(v)), compared lexicographically.  It is a strict total order, so there are no plateaus left to argue about.
+ *   Ascent.  For v in S, take the neighbour u of v in S with the greatest key.  Connectivity is 6, 18 or 26.  If K(u) > K(v) then
+ *   parent(v) = u.  Otherwise v is a peak.  Keys rise strictly along parents, so the parents form a forest.  basin(v) is the peak
+ *   that v reaches.  This is ascent by value, not by slope: a diagonal neighbour counts like a face neighbour.
+ *   Saddle.  Two basins A != B are adjacent if some u in A and v in B are neighbours.  saddle(A, B) is the maximum over such pairs
+ *   of min(H[u], H[v]).
+ *   Persistence (elder rule).  Sort the adjacent pairs by (saddle descending, smaller peak index ascending, larger peak index
+ *   ascending).  Walk them with a union-find over the peaks.  Each class is represented by its peak of greatest key.  A pair that
+ *   joins two classes kills the class whose representative p has the smaller key.  Then pers(p) = H[p] - saddle and partner(p) is
+ *   the other class's representative at that moment.  A class that is never killed has infinite persistence.
+ *   Result for min_depth = h >= 0.  final(p) = p if pers(p) >= h, else final(partner(p)).  The chain ends because keys rise.  The
+ *   label of v in S is 1 + rank(final(basin(v))), where rank is among the surviving peaks in ascending linear index.  The label is
+ *   0 outside S.  *count is the number of survivors.  With h = 0 the labels are the ascent basins and no pair is looked at.
+ * What follows: the partitions for rising h nest; the surviving peak of a part is its voxel of greatest key; pers(p) = H[p] - t*,
+ * where t* is the highest level t at which the component of {H >= t} that holds p also holds a voxel of greater key.
+ * Documented limits of the method.  On a plateau the flow runs to the voxel of greatest index: a flat convex region is one basin
+ * with its peak at its last voxel.  Part borders are where ascent paths diverge; they are not smoothed.  A relief of squared depths
+ * measures min_depth in squared units.
+ *
+ * labels is int32 with any strides that map no two voxels to one element; every voxel of the box is written.  relief is only
+ * read.  flags: O2V_HIP_FLAG_STAGE_TIMES (o2v_hip_watershed_counters counts).  The result is integers, the same bits on every run,
+ * schedule and table size.
+ *
+ * Refused before any launch, the outputs untouched.  O2V_HIP_ERR_BAD_ARGUMENT: null arguments, zero dims, a connectivity other
+ * than 6, 18 or 26, unknown flag bits, pointers that are not 4-byte aligned, that are not device memory of the context's device or
+ * that reach outside their allocation, labels strides that map two voxels to one element, any overlap of labels with relief.
+ * O2V_HIP_ERR_LIMIT: a dim above 65 536, or nx * ny * nz above 2^31 - 1.  A failed allocation, the pair table's included, returns
+ * O2V_HIP_ERR_OUT_OF_MEMORY and the context stays usable.  The call runs on the context's stream and returns when the writes are
+ * done (the caller must have finished writing relief).  The host reads the number of peaks; with min_depth > 0 and two peaks or
+ * more it also reads the peaks and the distinct adjacent pairs, merges them (plain C++) and sends a label per peak back.
+ * O2V_WS_NO_TILES=1 in the environment (A/B): the ascent without its tile pass in LDS; same results.
+ *
+ * Scratch of the context, grown on demand.  o2v_hip_watershed_scratch_bytes(dims) = 4 * nx * ny * nz (a parent per voxel)  +  12 *
+ * words (the peak bits and their prefixes; words = ceil(nx / 64) * ny * nz)  +  8 * (ceil(words / 256) + 1)  +  64 is the part fixed
+ * by the box (0 for zero dims).  With a merge come 12 bytes per peak on the device and page-locked, the pair table - 12 bytes a
+ * slot, 2^k slots, at first 16 per peak and 2^10 at least, doubled while a probe run finds no place - and 12 bytes per distinct
+ * pair on the device and page-locked: the counters report them. */
+int o2v_hip_watershed_dense(o2v_hip_ctx *ctx, const int32_t *relief, const uint64_t strides[3], const uint32_t dims[3], uint32_t connectivity,
+                            uint32_t min_depth, uint32_t flags, int32_t *labels, const uint64_t labels_strides[3], uint32_t *count);
+uint64_t o2v_hip_watershed_scratch_bytes(const uint32_t dims[3]);
+/* The times (ms) of the last o2v_hip_watershed_dense call: ascent, flatten (with the peaks' ranks and list), pairs (every turn of
+ * the table and the list's way to the host), merge (on the host), labels. */
+int o2v_hip_watershed_times(const o2v_hip_ctx *ctx, float out_ms[5]);
+/* Of the last o2v_hip_watershed_dense call made with O2V_HIP_FLAG_STAGE_TIMES (else zeros): the peaks, the boundary pairs seen
+ * (neighbour pairs whose basins differ, in the table's last turn), the distinct adjacent basin pairs, the table's growths, the
+ * table's bytes at the end, the survivors. */
+int o2v_hip_watershed_counters(const o2v_hip_ctx *ctx, uint64_t out6[6]);
+
 int o2v_hip_get_timings(const o2v_hip_ctx *ctx, o2v_hip_timings *out);
 /* Per-kernel device times of the last o2v_hip_voxelize call made with O2V_HIP_FLAG_KERNEL_TIMES (else none): up to
  * max_entries entries are written, *out_count receives how many there are. */

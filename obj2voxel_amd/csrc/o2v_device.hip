@@ -55,6 +55,8 @@
 //                              transforms, a pruned list of ball centres, an atomicMax per ball voxel; outside the pipeline
 //   K22 k_thin_*               o2v_hip_thin_dense: skeletons by topological thinning - eight subfields per iteration, a 26-voxel
 //                              bit test per border voxel, tile by tile in LDS, in place on the bit grid; outside the pipeline
+//   K23 k_ws_*                 o2v_hip_watershed_dense: watershed basins of an int32 relief by steepest ascent of a packed key, the
+//                              basins merged by persistence on the host; outside the pipeline
 //   plan k_zhist               o2v_hip_plan_slabs: predicted hits per z layer -> work-balanced slabs for N GPUs
 // With the direct MAX path K1's counters reach the host while K2 runs, and only the stages that have work are enqueued
 // behind it.  N > 1 GPUs: o2v_hip_voxelize_sharded (bounds / work-histogram passes sharded over the ranks, RCCL).
@@ -115,6 +117,7 @@ namespace {
 #include "o2v_dev_k20_geodesic.hpp"
 #include "o2v_dev_k21_thickness.hpp"
 #include "o2v_dev_k22_thinning.hpp"
+#include "o2v_dev_k23_watershed.hpp"   // (behind K12: its grid, index and prefix count)
 
 }  // namespace
 
@@ -250,6 +253,8 @@ struct Switches {
     bool ls_no_table = env_on("O2V_LS_NO_TABLE");              // A/B: k_label_stats without its table in LDS, every run to global memory
     bool geo_no_tiles = env_on("O2V_GEO_NO_TILES");            // A/B: no k_geo_tiles, whole-grid sweeps with atomic mins in global memory
     bool thin_no_tiles = env_on("O2V_THIN_NO_TILES");          // A/B: no k_thin_substep, every sub-step a whole-grid sweep with the masks from global memory
+    bool ws_no_tiles = env_on("O2V_WS_NO_TILES");              // A/B: no k_ws_ascent_tiles, every voxel's neighbours from global memory and P[i] = the parent
+    int ws_table_log2 = env_int("O2V_WS_TABLE_LOG2", 0);       // test hook: the pair table of K23 starts with 2^k slots (if > 0; else sized from the peaks)
     bool tiny_buffers = env_on("O2V_TEST_TINY_BUFFERS");       // test hook: minimal first capacities (every grow -> re-run path)
     bool block_list = env_on("O2V_TEST_BLOCK_LIST");           // test hook: the slab's block list for a mesh of any size
     int resolve_wgs_per_cu = env_int("O2V_RESOLVE_WGS_PER_CU", 0);  // A/B: workgroups per CU of resolve tier 1 (if > 0; else 2)
@@ -505,6 +510,18 @@ struct o2v_hip_ctx {
     PinnedArray<unsigned long long> h_thin_ctr;
     StageTimes<3> thin_times;
     uint64_t thin_counters[4] = {};
+    // K23 (o2v_hip_watershed_dense): a parent per voxel, the peak bits with their prefixes and block offsets (+ the count), [0]
+    // overflow, [1] distinct pairs, [2] boundary pairs seen, [3] listed pairs - fixed by the box; the peaks' indices and heights
+    // ([2][peaks]), label_of_rank, the pair table's keys and values and its entries as a list (keys, then values), on the device
+    // and page-locked - grown with the data; the times of the five stages and the six counters of the last call
+    DevArray<uint32_t> d_ws_parent, d_ws_local, d_ws_peaks, d_ws_vals;
+    DevArray<unsigned long long> d_ws_flags, d_ws_boff, d_ws_ctr, d_ws_keys, d_ws_list;
+    DevArray<int32_t> d_ws_lab;
+    PinnedArray<unsigned long long> h_ws_ctr, h_ws_list;
+    PinnedArray<uint32_t> h_ws_peaks;
+    PinnedArray<int32_t> h_ws_lab;
+    StageTimes<5> ws_times;
+    uint64_t ws_counters[6] = {};
 
     // results of the last run
     uint64_t n_vox = 0;
@@ -2547,6 +2564,7 @@ int o2v_hip_voxels_device_ptr(o2v_hip_ctx *ctx, const uint32_t **out_ptr, uint64
 #include "o2v_dev_host_k19_label_stats.hpp"
 #include "o2v_dev_host_k21_thickness.hpp"
 #include "o2v_dev_host_k22_thinning.hpp"
+#include "o2v_dev_host_k23_watershed.hpp"
 
 extern "C" {
 

@@ -33,7 +33,9 @@ local_thickness says how thick a solid is at every voxel - the largest inscribed
 thinner than t, and inner_distance, erode, dilate, opening and closing are the ball morphology that falls out of the same passes
 (o2v_hip_thickness_dense); skeletonize reduces a set to its skeleton - the one-voxel-wide centrelines of a
 solid or of its pore space - by topological thinning, and skeleton_nodes lists the end points and junctions (o2v_hip_thin_dense,
-DESIGN.md section 25).
+DESIGN.md section 25); watershed splits a relief - usually the depth map - into the basins of its tops, merged by how deep the pass
+between them is, split_parts does so for a solid and watershed_peaks lists the parts' tops (o2v_hip_watershed_dense, DESIGN.md
+section 26).
 
 torch is imported first on purpose: the library must bind to the HIP runtime torch loaded (a process that loaded the library
 before torch holds two separate runtime copies, and this module refuses to work there).
@@ -1019,6 +1021,10 @@ def thin_regions(dv, grid, min_thickness, *, level=None, background=False, borde
 # ---- skeletons: topological thinning ---------------------------------------------------------------------
 
 from .skeleton import skeleton_nodes, skeletonize  # noqa: E402,F401  (the torch layer of o2v_hip_thin_dense, a module of its own)
+
+# ---- parts: watershed basins of a relief, merged by persistence ---------------------------------------------
+
+from .watershed import split_parts, watershed, watershed_peaks  # noqa: E402,F401  (the torch layer of o2v_hip_watershed_dense)
 
 
 # ---- dense grids as voxel lists and voxel files --------------------------------------------------------

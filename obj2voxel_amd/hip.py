@@ -213,6 +213,12 @@ def _bind():
     L.o2v_hip_thin_scratch_bytes.restype = C.c_uint64
     L.o2v_hip_thin_times.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_thin_counters.argtypes = [C.c_void_p, C.c_void_p]
+    # ctx, relief, strides, dims, connectivity, min_depth, flags, labels, labels_strides, count
+    L.o2v_hip_watershed_dense.argtypes = [C.c_void_p] * 4 + [C.c_uint32] * 3 + [C.c_void_p] * 3
+    L.o2v_hip_watershed_scratch_bytes.argtypes = [C.c_void_p]
+    L.o2v_hip_watershed_scratch_bytes.restype = C.c_uint64
+    L.o2v_hip_watershed_times.argtypes = [C.c_void_p, C.c_void_p]
+    L.o2v_hip_watershed_counters.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_max_slab_layers.argtypes = [C.c_void_p, C.POINTER(_Params), C.POINTER(C.c_uint32)]
     return L
 
@@ -283,6 +289,12 @@ def thickness_scratch_bytes(dims, max_radius2, have_depth2=False):
     """o2v_hip_thickness_scratch_bytes: the context scratch a thickness_dense call over dims (x, y, z) with that cap takes, with
     (have_depth2) or without a depth2 grid of the caller's; on top of it 4 bytes per kept ball centre."""
     return int(_bind().o2v_hip_thickness_scratch_bytes(_u32x3(dims), int(max_radius2), 1 if have_depth2 else 0))
+
+
+def watershed_scratch_bytes(dims):
+    """o2v_hip_watershed_scratch_bytes: the context scratch of a watershed_dense call over dims (x, y, z) that the box fixes (the
+    peaks, the pair table and the pair list grow with the data: watershed_counters)."""
+    return int(_bind().o2v_hip_watershed_scratch_bytes(_u32x3(dims)))
 
 
 def thin_scratch_bytes(dims, have_keep=False):
@@ -753,6 +765,33 @@ class DeviceVoxelizer:
         FLAG_STAGE_TIMES (else zeros)."""
         out = (C.c_uint64 * 4)()
         self._check(self._L.o2v_hip_thin_counters(self._ctx, out), "o2v_hip_thin_counters")
+        return tuple(int(v) for v in out)
+
+    def watershed_dense(self, relief_ptr, strides, dims, connectivity, min_depth, flags, labels_ptr, labels_strides):
+        """o2v_hip_watershed_dense: the parts of the int32 relief at device pointer relief_ptr - the set is where it is positive;
+        every voxel climbs to its neighbour (connectivity 6, 18 or 26) of greatest key (height, linear index) until a peak, and
+        peaks whose pass to a higher one is less than min_depth below them are merged into it (elder rule).  Into the int32 grid
+        at labels_ptr: 0 outside the set, else 1 + the rank of the part's surviving peak in ascending index.  Strides in elements
+        and dims per axis x, y, z.  Returns the number of parts."""
+        n = C.c_uint32(0)
+        self._check(self._L.o2v_hip_watershed_dense(self._ctx, relief_ptr, _u64x3(strides), _u32x3(dims), connectivity, min_depth, flags, labels_ptr,
+                                                    _u64x3(labels_strides), C.byref(n)), "o2v_hip_watershed_dense")
+        return int(n.value)
+
+    def watershed_scratch_bytes(self, dims):
+        """o2v_hip_watershed_scratch_bytes: the context scratch of a watershed_dense call over dims (x, y, z) that the box fixes."""
+        return watershed_scratch_bytes(dims)
+
+    def watershed_times(self):
+        """o2v_hip_watershed_times: the times (ms) of the last watershed_dense call's ascent, flatten, pairs, merge (on the host)
+        and labels stages."""
+        return self._stage_times("o2v_hip_watershed_times", 5)
+
+    def watershed_counters(self):
+        """o2v_hip_watershed_counters: (peaks, boundary pairs seen, distinct adjacent basin pairs, table growths, table bytes,
+        survivors) of the last watershed_dense call made with FLAG_STAGE_TIMES (else zeros)."""
+        out = (C.c_uint64 * 6)()
+        self._check(self._L.o2v_hip_watershed_counters(self._ctx, out), "o2v_hip_watershed_counters")
         return tuple(int(v) for v in out)
 
     def nearest_scratch_bytes(self, dims):

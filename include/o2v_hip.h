@@ -1118,6 +1118,65 @@ int o2v_hip_watershed_times(const o2v_hip_ctx *ctx, float out_ms[5]);
  * table's bytes at the end, the survivors. */
 int o2v_hip_watershed_counters(const o2v_hip_ctx *ctx, uint64_t out6[6]);
 
+/* ---- which labels touch: the region adjacency of a label grid ---------------------------------------------
+ *
+ * The grid.  labels, format (O2V_HIP_LABELS_I32 / O2V_HIP_LABELS_U8), strides (elements per axis x, y, z; any order, a stride may
+ * be 0) and dims are what o2v_hip_label_stats takes; the grid is only read.
+ *
+ * Contacts.  A contact is an unordered pair of voxels {u, v} of the box, u != v, whose coordinates differ by at most 1 on every
+ * axis.  Its class is the number of axes on which they differ: 1 a shared face, 2 a shared edge only, 3 a shared corner only.
+ * connectivity 6 counts class 1, 18 classes 1 and 2, 26 all three.  A voxel outside the box makes no contact.
+ *
+ * Which labels take part: lo ... n_labels, lo = 1 - the value 0 is background and touches nothing - or, with O2V_HIP_ADJ_ZERO, lo =
+ * 0: the background is a label like any other.  A voxel whose value is below lo, negative or above n_labels makes no contact;
+ * *out_outside receives the number of voxels that are negative or above n_labels, as o2v_hip_label_stats counts them.
+ *
+ * What is listed.  For every pair of labels a < b with at least one counted contact between a voxel of a and a voxel of b, one
+ * row of O2V_HIP_ADJ_COLUMNS int64:
+ *   0  face contacts: the contact area in voxel faces
+ *   1  edge-only contacts (0 where the connectivity does not count them)
+ *   2  corner-only contacts (0 where the connectivity does not count them)
+ *   3  with values: the maximum over the counted contacts of min(V[u], V[v]); else 0
+ *   4  with values: the minimum over the counted contacts of max(V[u], V[v]); else 0
+ * values is an int32 grid of the same dims with strides of its own (value_strides), or null.  Column 3 is the pass of an
+ * ascending relief - with the depth map of a solid the depth of the neck between two parts, o2v_hip_watershed_dense's saddle -,
+ * column 4 the pass of a descending one.  The pairs come sorted ascending by (a, b), as int32 [m][2].  Every column is a sum, a
+ * maximum or a minimum and the list is sorted: one run equals another bit for bit.  There are at most 13 (2^31 - 1) contacts in
+ * all, far below 2^63.
+ *
+ * o2v_hip_adjacency_count runs the pass and keeps the sorted list in the context: *out_pairs = m.  o2v_hip_adjacency_write copies
+ * it into the caller's device arrays pairs [m][2] and table [m][5]; it is refused (O2V_HIP_ERR_BAD_ARGUMENT) when no count precedes
+ * it on this context - a count that was refused is none -, when capacity < m, for null, misaligned or overlapping arrays or arrays
+ * that are not device memory of the context's device with m rows inside their allocation; with m = 0 both may be null.
+ *
+ * count is refused before anything is launched, the outputs untouched.  O2V_HIP_ERR_BAD_ARGUMENT: a null argument (values may be
+ * null; value_strides only without values), zero dims, an unknown format, a connectivity other than 6, 18 or 26, unknown flag bits
+ * (known: O2V_HIP_ADJ_ZERO, O2V_HIP_FLAG_STAGE_TIMES), n_labels above 255 with U8, an I32 grid or values not 4-byte aligned, a
+ * grid that is not device memory of the context's device or reaches outside its allocation.  O2V_HIP_ERR_LIMIT (before the
+ * pointers are looked at): a dim above 65 536, more than 2^31 - 1 voxels, n_labels above 2^31 - 2.  Both calls run on the
+ * context's stream and return when their writes have landed (the caller must have finished writing the grids).
+ *
+ * Scratch of the context, grown on demand: the pair table - 48 bytes a slot, 2^k slots, at first 16 per label that can occur
+ * (min(n_labels + 1, voxels)), 2^10 at least and 2^24 at most, doubled and the pass run again while a probe run finds no place
+ * (O2V_ADJ_TABLE_LOG2=k in the environment, a test hook, forces the first size) - and o2v_hip_adjacency_scratch_bytes(m) = 48 m +
+ * 64 for the list (as much again page-locked, twice: the host sorts it).  A table or list that cannot be allocated returns
+ * O2V_HIP_ERR_OUT_OF_MEMORY and leaves the context usable.  O2V_ADJ_NO_TABLE=1 in the environment (A/B): the pass without its
+ * table in LDS, every pending pair straight to global memory; same results. */
+enum { O2V_HIP_ADJ_ZERO = 16u };
+enum { O2V_HIP_ADJ_COLUMNS = 5 };
+int o2v_hip_adjacency_count(o2v_hip_ctx *ctx, const void *labels, uint32_t format, const uint64_t strides[3], const uint32_t dims[3],
+                            uint32_t n_labels, uint32_t connectivity, uint32_t flags, const int32_t *values, const uint64_t value_strides[3],
+                            uint64_t *out_pairs, uint64_t *out_outside);
+int o2v_hip_adjacency_write(o2v_hip_ctx *ctx, int32_t *pairs /* [m][2] */, int64_t *table /* [m][5] */, uint64_t capacity);
+/* The times (ms) of the last o2v_hip_adjacency_count call: the table's initialisation and the pass (of the table's last turn), the
+ * list and its way to the host, the sort (on the host) and its way back. */
+int o2v_hip_adjacency_times(const o2v_hip_ctx *ctx, float out_ms[4]);
+/* Of the last o2v_hip_adjacency_count call made with O2V_HIP_FLAG_STAGE_TIMES (else zeros): the pending pairs flushed into a
+ * workgroup's table in LDS and those flushed to global memory (in the table's last turn), the table's growths, the table's bytes
+ * at the end. */
+int o2v_hip_adjacency_counters(const o2v_hip_ctx *ctx, uint64_t out4[4]);
+uint64_t o2v_hip_adjacency_scratch_bytes(uint64_t pairs);
+
 int o2v_hip_get_timings(const o2v_hip_ctx *ctx, o2v_hip_timings *out);
 /* Per-kernel device times of the last o2v_hip_voxelize call made with O2V_HIP_FLAG_KERNEL_TIMES (else none): up to
  * max_entries entries are written, *out_count receives how many there are. */

@@ -57,6 +57,9 @@
 //                              bit test per border voxel, tile by tile in LDS, in place on the bit grid; outside the pipeline
 //   K23 k_ws_*                 o2v_hip_watershed_dense: watershed basins of an int32 relief by steepest ascent of a packed key, the
 //                              basins merged by persistence on the host; outside the pipeline
+//   K24 k_adj_*                o2v_hip_adjacency_count / _write: which labels of a label grid touch - per pair the face, edge and
+//                              corner contacts and the two passes of a values grid, one pass of K19's chunks into a pair table in
+//                              LDS and one in global memory, sorted on the host; outside the pipeline
 //   plan k_zhist               o2v_hip_plan_slabs: predicted hits per z layer -> work-balanced slabs for N GPUs
 // With the direct MAX path K1's counters reach the host while K2 runs, and only the stages that have work are enqueued
 // behind it.  N > 1 GPUs: o2v_hip_voxelize_sharded (bounds / work-histogram passes sharded over the ranks, RCCL).
@@ -118,6 +121,7 @@ namespace {
 #include "o2v_dev_k21_thickness.hpp"
 #include "o2v_dev_k22_thinning.hpp"
 #include "o2v_dev_k23_watershed.hpp"   // (behind K12: its grid, index and prefix count)
+#include "o2v_dev_k24_adjacency.hpp"   // (behind K19: its chunk and its reads)
 
 }  // namespace
 
@@ -255,6 +259,8 @@ struct Switches {
     bool thin_no_tiles = env_on("O2V_THIN_NO_TILES");          // A/B: no k_thin_substep, every sub-step a whole-grid sweep with the masks from global memory
     bool ws_no_tiles = env_on("O2V_WS_NO_TILES");              // A/B: no k_ws_ascent_tiles, every voxel's neighbours from global memory and P[i] = the parent
     int ws_table_log2 = env_int("O2V_WS_TABLE_LOG2", 0);       // test hook: the pair table of K23 starts with 2^k slots (if > 0; else sized from the peaks)
+    bool adj_no_table = env_on("O2V_ADJ_NO_TABLE");            // A/B: k_adj_pairs without its table in LDS, every flush to global memory
+    int adj_table_log2 = env_int("O2V_ADJ_TABLE_LOG2", 0);     // test hook: the pair table of K24 starts with 2^k slots (if > 0; else sized from the labels)
     bool tiny_buffers = env_on("O2V_TEST_TINY_BUFFERS");       // test hook: minimal first capacities (every grow -> re-run path)
     bool block_list = env_on("O2V_TEST_BLOCK_LIST");           // test hook: the slab's block list for a mesh of any size
     int resolve_wgs_per_cu = env_int("O2V_RESOLVE_WGS_PER_CU", 0);  // A/B: workgroups per CU of resolve tier 1 (if > 0; else 2)
@@ -522,6 +528,17 @@ struct o2v_hip_ctx {
     PinnedArray<int32_t> h_ws_lab;
     StageTimes<5> ws_times;
     uint64_t ws_counters[6] = {};
+    // K24 (o2v_hip_adjacency_count / _write): the pair table's keys and rows ([slots], [slots][5]); [0] overflow, [1] voxels outside,
+    // [2] flushes into LDS, [3] flushes to global memory, [4] listed pairs, [5] slots taken; the list - keys [m] and rows [m][5] as
+    // the table gives them, then pairs [m][2] and rows sorted by key - on the device and page-locked (both orders); grown with the
+    // data; the times of the four stages and the four counters of the last count, whether one stands, and its pairs
+    DevArray<unsigned long long> d_adj_keys, d_adj_ctr, d_adj_list;
+    DevArray<long long> d_adj_rows;
+    PinnedArray<unsigned long long> h_adj_ctr, h_adj_list;
+    StageTimes<4> adj_times;
+    uint64_t adj_counters[4] = {};
+    uint64_t adj_pairs = 0;
+    bool adj_counted = false;
 
     // results of the last run
     uint64_t n_vox = 0;
@@ -2565,6 +2582,7 @@ int o2v_hip_voxels_device_ptr(o2v_hip_ctx *ctx, const uint32_t **out_ptr, uint64
 #include "o2v_dev_host_k21_thickness.hpp"
 #include "o2v_dev_host_k22_thinning.hpp"
 #include "o2v_dev_host_k23_watershed.hpp"
+#include "o2v_dev_host_k24_adjacency.hpp"
 
 extern "C" {
 

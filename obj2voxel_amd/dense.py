@@ -35,7 +35,10 @@ thinner than t, and inner_distance, erode, dilate, opening and closing are the b
 solid or of its pore space - by topological thinning, and skeleton_nodes lists the end points and junctions (o2v_hip_thin_dense,
 DESIGN.md section 25); watershed splits a relief - usually the depth map - into the basins of its tops, merged by how deep the pass
 between them is, split_parts does so for a solid and watershed_peaks lists the parts' tops (o2v_hip_watershed_dense, DESIGN.md
-section 26).
+section 26); label_adjacency says which labels of a label grid touch - per pair the face, edge and corner contacts and the passes of
+a relief between them -, adjacency_neighbours and coordination turn that list into neighbour lists and counts, and skeleton_graph
+makes the nodes, branches and incidences of a skeleton with it (o2v_hip_adjacency_count / o2v_hip_adjacency_write, DESIGN.md
+section 27).
 
 torch is imported first on purpose: the library must bind to the HIP runtime torch loaded (a process that loaded the library
 before torch holds two separate runtime copies, and this module refuses to work there).
@@ -1025,6 +1028,11 @@ from .skeleton import skeleton_nodes, skeletonize  # noqa: E402,F401  (the torch
 # ---- parts: watershed basins of a relief, merged by persistence ---------------------------------------------
 
 from .watershed import split_parts, watershed, watershed_peaks  # noqa: E402,F401  (the torch layer of o2v_hip_watershed_dense)
+
+# ---- which labels touch: the region adjacency of a label grid ------------------------------------------------
+
+from .adjacency import (LabelAdjacency, SkeletonGraph, adjacency_neighbours, coordination, label_adjacency,  # noqa: E402,F401
+                        skeleton_graph)   # (the torch layer of o2v_hip_adjacency_count / _write)
 
 
 # ---- dense grids as voxel lists and voxel files --------------------------------------------------------

@@ -45,6 +45,8 @@ THIN_ULTIMATE, THIN_CURVE = 0, 1  # o2v_hip_thin_dense modes: no end points; end
 THIN_DST_MASK, THIN_DST_DEGREE = 0, 1  # ... its dst formats: 1 / 0; 1 + the 26-neighbours in the skeleton
 STATS_BOX, STATS_SUMS, STATS_MOMENTS, STATS_FACES = 1, 2, 4, 8  # ... the bits of `which`
 STATS_COLUMNS = 17  # ... the int64 columns of a row of its table
+ADJ_ZERO = 16  # o2v_hip_adjacency_count flag: the value 0 is a label like any other (with FLAG_STAGE_TIMES: the counters)
+ADJ_COLUMNS = 5  # ... the int64 columns of a row of its table: faces, edges, corners, pass_high, pass_low
 ERR_BAD_ARGUMENT = 3
 ERR_LIMIT = 5
 ERR_IO = 6  # o2v_hip_gather_save: the file cannot be opened, is of no output type, or stopped taking voxels
@@ -219,6 +221,14 @@ def _bind():
     L.o2v_hip_watershed_scratch_bytes.restype = C.c_uint64
     L.o2v_hip_watershed_times.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_watershed_counters.argtypes = [C.c_void_p, C.c_void_p]
+    # ctx, labels, format, strides, dims, n_labels, connectivity, flags, values, value_strides, out_pairs, out_outside
+    L.o2v_hip_adjacency_count.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                          C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.o2v_hip_adjacency_write.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+    L.o2v_hip_adjacency_times.argtypes = [C.c_void_p, C.c_void_p]
+    L.o2v_hip_adjacency_counters.argtypes = [C.c_void_p, C.c_void_p]
+    L.o2v_hip_adjacency_scratch_bytes.argtypes = [C.c_uint64]
+    L.o2v_hip_adjacency_scratch_bytes.restype = C.c_uint64
     L.o2v_hip_max_slab_layers.argtypes = [C.c_void_p, C.POINTER(_Params), C.POINTER(C.c_uint32)]
     return L
 
@@ -289,6 +299,12 @@ def thickness_scratch_bytes(dims, max_radius2, have_depth2=False):
     """o2v_hip_thickness_scratch_bytes: the context scratch a thickness_dense call over dims (x, y, z) with that cap takes, with
     (have_depth2) or without a depth2 grid of the caller's; on top of it 4 bytes per kept ball centre."""
     return int(_bind().o2v_hip_thickness_scratch_bytes(_u32x3(dims), int(max_radius2), 1 if have_depth2 else 0))
+
+
+def adjacency_scratch_bytes(pairs):
+    """o2v_hip_adjacency_scratch_bytes: the context scratch that the sorted list of `pairs` pairs of an adjacency_count takes (the
+    pair table grows with the data: adjacency_counters)."""
+    return int(_bind().o2v_hip_adjacency_scratch_bytes(int(pairs)))
 
 
 def watershed_scratch_bytes(dims):
@@ -793,6 +809,39 @@ class DeviceVoxelizer:
         out = (C.c_uint64 * 6)()
         self._check(self._L.o2v_hip_watershed_counters(self._ctx, out), "o2v_hip_watershed_counters")
         return tuple(int(v) for v in out)
+
+    def adjacency_count(self, labels_ptr, fmt, strides, dims, n_labels, connectivity, flags, values_ptr=None, value_strides=None):
+        """o2v_hip_adjacency_count: which of the labels 1 ... n_labels (0 ... n_labels with ADJ_ZERO in flags) of the label grid at
+        device address labels_ptr (LABELS_I32 / LABELS_U8; strides in elements, strides and dims per axis x, y, z) touch, at
+        connectivity 6, 18 or 26; values_ptr: None or an int32 grid of the same dims at value_strides.  The sorted list stays in
+        the context for adjacency_write.  Returns (pairs, outside): the number of pairs, and of voxels that are negative or above
+        n_labels."""
+        pairs, outside = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.o2v_hip_adjacency_count(self._ctx, labels_ptr, fmt, _u64x3(strides), _u32x3(dims), n_labels, connectivity, flags, values_ptr,
+                                                    None if value_strides is None else _u64x3(value_strides), C.byref(pairs), C.byref(outside)),
+                    "o2v_hip_adjacency_count")
+        return int(pairs.value), int(outside.value)
+
+    def adjacency_write(self, pairs_ptr, table_ptr, capacity):
+        """o2v_hip_adjacency_write: the list of the last adjacency_count into the device arrays pairs_ptr (int32 [m, 2], sorted by
+        (a, b)) and table_ptr (int64 [m, ADJ_COLUMNS]) of room for `capacity` pairs."""
+        self._check(self._L.o2v_hip_adjacency_write(self._ctx, pairs_ptr, table_ptr, capacity), "o2v_hip_adjacency_write")
+
+    def adjacency_times(self):
+        """o2v_hip_adjacency_times: the times (ms) of the last adjacency_count call's table initialisation, pass, list and sort
+        (on the host)."""
+        return self._stage_times("o2v_hip_adjacency_times", 4)
+
+    def adjacency_counters(self):
+        """o2v_hip_adjacency_counters: (flushes into LDS, flushes to global memory, table growths, table bytes) of the last
+        adjacency_count call made with FLAG_STAGE_TIMES (else zeros)."""
+        out = (C.c_uint64 * 4)()
+        self._check(self._L.o2v_hip_adjacency_counters(self._ctx, out), "o2v_hip_adjacency_counters")
+        return tuple(int(v) for v in out)
+
+    def adjacency_scratch_bytes(self, pairs):
+        """o2v_hip_adjacency_scratch_bytes: the context scratch of the sorted list of `pairs` pairs."""
+        return adjacency_scratch_bytes(pairs)
 
     def nearest_scratch_bytes(self, dims):
         """o2v_hip_nearest_scratch_bytes: the context scratch a nearest_dense call over dims (x, y, z) needs."""

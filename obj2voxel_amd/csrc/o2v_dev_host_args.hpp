@@ -1,5 +1,5 @@
-// Host side of the dense-grid entry points (K7 - K21): what they share.  Refusals, the checks of the caller's memory, scratch,
-// the set grid, the limits, run-time values as template arguments.  Included by o2v_device.hip only, once, like the kernels'
+// Host side of the dense-grid entry points (K7 - K24): what they share.  Refusals, the checks of the caller's memory, scratch,
+// the set grid, the limits, run-time values as template arguments, the pair table's grow loop.  Included by o2v_device.hip only, once, like the kernels'
 // headers: it needs the context and the launch macros defined there.
 
 namespace {
@@ -121,6 +121,13 @@ int grid_given(o2v_hip_ctx *ctx, const char *fn, const void *grid, const uint64_
     if (!grid || !strides || !dims) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
     if (!dims[0] || !dims[1] || !dims[2]) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "zero dims");
     return O2V_HIP_OK;
+}
+
+// The neighbourhoods of K12, K23 and K24.
+int connectivity_known(o2v_hip_ctx *ctx, const char *fn, uint32_t connectivity)
+{
+    if (connectivity == 6u || connectivity == 18u || connectivity == 26u) return O2V_HIP_OK;
+    return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "connectivity must be 6, 18 or 26, not " + std::to_string(connectivity));
 }
 
 // 16-byte loads from a grid of elem-byte elements: unit x stride and every row 16-byte aligned
@@ -282,6 +289,20 @@ int finish_stages(o2v_hip_ctx *ctx, StageTimes<N> &times)
     O2V_CHECK(hipStreamSynchronize(s));
     O2V_CHECK(times.finish());
     return O2V_HIP_OK;
+}
+
+// The pair table of K23 and K24 (o2v_dev_pair_table.hpp), doubled while a probe run overflows.  pass(log2, overflow) gives the
+// table 2^log2 slots, clears it, runs the family's pass and reads its counters back: a code that is not 0 ends the call, `overflow`
+// asks for the next size.  *log2: the first size, then the one that held every pair; *growths: the doublings.  Above 2^max_log2: refused.
+template <typename Pass>
+int pt_grow(o2v_hip_ctx *ctx, const char *fn, uint32_t max_log2, uint32_t *log2, uint64_t *growths, Pass &&pass)
+{
+    for (*growths = 0;; ++*log2, ++*growths) {
+        if (*log2 > max_log2) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "the pair table would pass 2^" + std::to_string(max_log2) + " slots");
+        bool overflow = false;
+        if (int rc = pass(*log2, overflow)) return rc;
+        if (!overflow) return O2V_HIP_OK;
+    }
 }
 
 // The tail of a count of K13 and K14, whose stage marks 0 and 1 the caller has set: the block sums boff[0, n_blocks) scanned in

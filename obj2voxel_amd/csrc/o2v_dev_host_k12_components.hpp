@@ -46,8 +46,7 @@ int cc_run(o2v_hip_ctx *ctx, const char *fn, const void *grid, uint32_t format, 
     SetGrid sg;
     int rc;
     if ((rc = set_grid(ctx, fn, grid, format, strides, dims, level, &sg))) return rc;
-    if (connectivity != 6u && connectivity != 18u && connectivity != 26u)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "connectivity must be 6, 18 or 26, not " + std::to_string(connectivity));
+    if ((rc = connectivity_known(ctx, fn, connectivity))) return rc;
     if ((flags & ~kCcFlagsKnown) || (labels && (flags & O2V_HIP_CC_SEED_BORDER)))
         return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown flag bits in " + std::to_string(flags));
     if ((rc = index_limits(ctx, fn, dims, n_seeds, "seeds"))) return rc;

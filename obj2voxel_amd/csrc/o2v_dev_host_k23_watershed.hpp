@@ -5,15 +5,6 @@ namespace {
 
 constexpr uint32_t kWsFlagsKnown = O2V_HIP_FLAG_STAGE_TIMES;
 
-// the table's first size for n peaks: 16 slots a peak (a basin in three dimensions touches a handful of others), 2^10 at least
-uint32_t ws_table_log2(uint64_t n_peaks, int forced)
-{
-    if (forced > 0) return (uint32_t) std::min<int>(forced, (int) kWsTableMaxLog2);
-    uint32_t log2 = kWsTableMinLog2;
-    while (log2 < kWsTableMaxLog2 && (1ull << log2) < 16u * n_peaks) ++log2;
-    return log2;
-}
-
 }  // namespace
 
 extern "C" {
@@ -34,8 +25,7 @@ int o2v_hip_watershed_dense(o2v_hip_ctx *ctx, const int32_t *relief, const uint6
     if (!labels || !labels_strides || !count) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "null argument");
     int rc;
     if ((rc = grid_given(ctx, fn, relief, strides, dims))) return rc;
-    if (connectivity != 6u && connectivity != 18u && connectivity != 26u)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "connectivity must be 6, 18 or 26, not " + std::to_string(connectivity));
+    if ((rc = connectivity_known(ctx, fn, connectivity))) return rc;
     if (flags & ~kWsFlagsKnown) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown flag bits in " + std::to_string(flags));
     if ((uintptr_t) relief % sizeof(int32_t) || (uintptr_t) labels % sizeof(int32_t))
         return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "relief and labels must be 4-byte aligned");
@@ -49,7 +39,7 @@ int o2v_hip_watershed_dense(o2v_hip_ctx *ctx, const int32_t *relief, const uint6
 
     const BitGrid bg = bit_grid(dims);
     const CcGrid g{bg, bit_tiles_y(bg), bit_tiles_z(bg), connectivity};
-    const WsRelief H{relief, strides[0], strides[1], strides[2]};
+    const I32View H{relief, strides[0], strides[1], strides[2]};
     const uint64_t voxels = (uint64_t) dims[0] * dims[1] * dims[2], n_blocks = (g.words + kBlock - 1) / kBlock;
     if ((rc = grow_scratch(ctx, ctx->d_ws_parent, voxels, fn, "parents")) || (rc = grow_scratch(ctx, ctx->d_ws_flags, g.words, fn, "peak bits")) ||
         (rc = grow_scratch(ctx, ctx->d_ws_local, g.words, fn, "prefixes")) || (rc = grow_scratch(ctx, ctx->d_ws_boff, n_blocks + 1u, fn, "block offsets")) ||
@@ -92,10 +82,11 @@ int o2v_hip_watershed_dense(o2v_hip_ctx *ctx, const int32_t *relief, const uint6
     // pairs: the table, doubled while a probe run overflows; then its entries as a list on the host
     O2V_CHECK(ctx->ws_times.mark(2, s));
     if (merge) {
-        for (uint32_t log2 = ws_table_log2(n_peaks, sw.ws_table_log2);; ++log2, ++growths) {
-            if (log2 > kWsTableMaxLog2) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "the pair table would pass 2^40 slots");
+        uint32_t held = pt_first_log2(n_peaks, sw.ws_table_log2, kWsTableMaxLog2, kWsTableMaxLog2);
+        rc = pt_grow(ctx, fn, kWsTableMaxLog2, &held, &growths, [&](uint32_t log2, bool &overflow) -> int {
             const uint64_t slots = 1ull << log2;
-            if ((rc = grow_scratch(ctx, ctx->d_ws_keys, slots, fn, "pair table")) || (rc = grow_scratch(ctx, ctx->d_ws_vals, slots, fn, "pair table"))) return rc;
+            if (int rc = grow_scratch(ctx, ctx->d_ws_keys, slots, fn, "pair table")) return rc;
+            if (int rc = grow_scratch(ctx, ctx->d_ws_vals, slots, fn, "pair table")) return rc;
             O2V_CHECK(hipMemsetAsync(ctx->d_ws_keys.ptr, 0xff, slots * sizeof(unsigned long long), s));
             O2V_CHECK(hipMemsetAsync(ctx->d_ws_vals.ptr, 0, slots * sizeof(uint32_t), s));
             O2V_CHECK(hipMemsetAsync(ctr, 0, 8u * sizeof(unsigned long long), s));
@@ -105,19 +96,21 @@ int o2v_hip_watershed_dense(o2v_hip_ctx *ctx, const int32_t *relief, const uint6
             O2V_CHECK(hipGetLastError());
             O2V_CHECK(hipMemcpyAsync(ctx->h_ws_ctr.ptr, ctr, 3u * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
             O2V_CHECK(hipStreamSynchronize(s));
-            if (h_ctr[0]) continue;
-            n_pairs = h_ctr[1], seen = h_ctr[2], table_bytes = slots * 12u;
-            // (the list: keys, then values, one array each on the device and page-locked)
-            if ((rc = grow_scratch(ctx, ctx->d_ws_list, n_pairs + (n_pairs + 1u) / 2u, fn, "pair list")) ||
-                (rc = grow_scratch(ctx, ctx->h_ws_list, n_pairs + (n_pairs + 1u) / 2u, fn, "pair list")))
-                return rc;
-            O2V_LAUNCH("k_ws_pairs_list", s, k_ws_pairs_list, dim3(stream_grid(ctx, slots, 16u)), dim3(kBlock), 0, s, ctx->d_ws_keys.ptr, ctx->d_ws_vals.ptr, slots,
-                       ctx->d_ws_list.ptr, reinterpret_cast<uint32_t *>(ctx->d_ws_list.ptr + n_pairs), ctr + 3);
-            O2V_CHECK(hipGetLastError());
-            if (n_pairs) O2V_CHECK(hipMemcpyAsync(ctx->h_ws_list.ptr, ctx->d_ws_list.ptr, n_pairs * 12u, hipMemcpyDeviceToHost, s));
-            O2V_CHECK(hipStreamSynchronize(s));
-            break;
-        }
+            overflow = h_ctr[0] != 0u;
+            return O2V_HIP_OK;
+        });
+        if (rc) return rc;
+        const uint64_t slots = 1ull << held;
+        n_pairs = h_ctr[1], seen = h_ctr[2], table_bytes = slots * 12u;
+        // (the list: keys, then values, one array each on the device and page-locked)
+        if ((rc = grow_scratch(ctx, ctx->d_ws_list, n_pairs + (n_pairs + 1u) / 2u, fn, "pair list")) ||
+            (rc = grow_scratch(ctx, ctx->h_ws_list, n_pairs + (n_pairs + 1u) / 2u, fn, "pair list")))
+            return rc;
+        O2V_LAUNCH("k_pt_list", s, (k_pt_list<uint32_t, 1u>), dim3(stream_grid(ctx, slots, 16u)), dim3(kBlock), 0, s, ctx->d_ws_keys.ptr, ctx->d_ws_vals.ptr, slots, 1u,
+                   ctx->d_ws_list.ptr, reinterpret_cast<uint32_t *>(ctx->d_ws_list.ptr + n_pairs), ctr + 3);
+        O2V_CHECK(hipGetLastError());
+        if (n_pairs) O2V_CHECK(hipMemcpyAsync(ctx->h_ws_list.ptr, ctx->d_ws_list.ptr, n_pairs * 12u, hipMemcpyDeviceToHost, s));
+        O2V_CHECK(hipStreamSynchronize(s));
     }
     // merge, on the host
     O2V_CHECK(ctx->ws_times.mark(3, s));

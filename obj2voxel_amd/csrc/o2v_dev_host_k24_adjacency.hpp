@@ -8,15 +8,6 @@ constexpr uint32_t kAdjFirstMaxLog2 = 24u;   // the table's first size is 2^24 s
 
 static_assert(kAdjCols == O2V_HIP_ADJ_COLUMNS, "one set of columns for the callers and the kernel");
 
-// the table's first size: 16 slots a label that can occur (K23's rule), 2^10 at least
-uint32_t adj_table_log2(uint64_t labels, int forced)
-{
-    if (forced > 0) return (uint32_t) std::min<int>(forced, (int) kAdjTableMaxLog2);
-    uint32_t log2 = kAdjTableMinLog2;
-    while (log2 < kAdjFirstMaxLog2 && (1ull << log2) < 16u * labels) ++log2;
-    return log2;
-}
-
 // The order that sorts m distinct keys ascending: a radix sort of (key, index) by 16-bit digits from the lowest, the digits that
 // all keys share left out (labels are small numbers: most of a key's 64 bits are zero).
 std::vector<uint64_t> adj_sorted_order(const unsigned long long *keys, uint64_t m)
@@ -59,8 +50,7 @@ int o2v_hip_adjacency_count(o2v_hip_ctx *ctx, const void *labels, uint32_t forma
     if ((rc = grid_given(ctx, fn, labels, strides, dims))) return rc;
     if (format != O2V_HIP_LABELS_I32 && format != O2V_HIP_LABELS_U8)
         return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown format " + std::to_string(format));
-    if (connectivity != 6u && connectivity != 18u && connectivity != 26u)
-        return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "connectivity must be 6, 18 or 26, not " + std::to_string(connectivity));
+    if ((rc = connectivity_known(ctx, fn, connectivity))) return rc;
     if (flags & ~kAdjFlagsKnown) return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "unknown flag bits in " + std::to_string(flags));
     if (format == O2V_HIP_LABELS_U8 && n_labels > 255u)
         return refuse(ctx, O2V_HIP_ERR_BAD_ARGUMENT, fn, "n_labels " + std::to_string(n_labels) + " is above 255, the highest value of a U8 grid");
@@ -92,16 +82,17 @@ int o2v_hip_adjacency_count(o2v_hip_ctx *ctx, const void *labels, uint32_t forma
     g.count = count_on ? 1u : 0u;
     const bool vec = rows_aligned16(labels, strides, elem);
     const RaySource src = ray_source(labels, strides, 0.f);
-    const AdjValues V{values, values ? value_strides[0] : 0u, values ? value_strides[1] : 0u, values ? value_strides[2] : 0u};
+    const I32View V{values, values ? value_strides[0] : 0u, values ? value_strides[1] : 0u, values ? value_strides[2] : 0u};
     unsigned long long *const ctr = ctx->d_adj_ctr.ptr;
     volatile unsigned long long *const h_ctr = ctx->h_adj_ctr.ptr;
     hipStream_t s = ctx->stream;
-    uint64_t growths = 0, slots = 0;
-    // the table, doubled while a probe run overflows
-    for (uint32_t log2 = adj_table_log2(std::min<uint64_t>((uint64_t) n_labels + 1u, voxels), sw.adj_table_log2);; ++log2, ++growths) {
-        if (log2 > kAdjTableMaxLog2) return refuse(ctx, O2V_HIP_ERR_LIMIT, fn, "the pair table would pass 2^36 slots");
-        slots = 1ull << log2;
-        if ((rc = grow_scratch(ctx, ctx->d_adj_keys, slots, fn, "pair table")) || (rc = grow_scratch(ctx, ctx->d_adj_rows, slots * kAdjCols, fn, "pair table"))) return rc;
+    uint64_t growths = 0;
+    // the table, doubled while a probe run overflows: 16 slots a label that can occur at first, 2^kAdjFirstMaxLog2 at most
+    uint32_t held = pt_first_log2(std::min<uint64_t>((uint64_t) n_labels + 1u, voxels), sw.adj_table_log2, kAdjFirstMaxLog2, kAdjTableMaxLog2);
+    rc = pt_grow(ctx, fn, kAdjTableMaxLog2, &held, &growths, [&](uint32_t log2, bool &overflow) -> int {
+        const uint64_t slots = 1ull << log2;
+        if (int rc = grow_scratch(ctx, ctx->d_adj_keys, slots, fn, "pair table")) return rc;
+        if (int rc = grow_scratch(ctx, ctx->d_adj_rows, slots * kAdjCols, fn, "pair table")) return rc;
         g.log2 = log2;
         O2V_CHECK(ctx->adj_times.mark(0, s));
         O2V_CHECK(hipMemsetAsync(ctr, 0, kAdjCtrs * sizeof(unsigned long long), s));
@@ -125,12 +116,15 @@ int o2v_hip_adjacency_count(o2v_hip_ctx *ctx, const void *labels, uint32_t forma
         O2V_CHECK(ctx->adj_times.mark(2, s));
         O2V_CHECK(hipMemcpyAsync(ctx->h_adj_ctr.ptr, ctr, kAdjCtrs * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
         O2V_CHECK(hipStreamSynchronize(s));
-        if (!h_ctr[0]) break;
-    }
+        overflow = h_ctr[0] != 0u;
+        return O2V_HIP_OK;
+    });
+    if (rc) return rc;
+    const uint64_t slots = 1ull << held;
     const uint64_t outside = h_ctr[1], to_lds = h_ctr[2], to_global = h_ctr[3], m = h_ctr[5];
     // the list: keys [m], then rows [m][5] - first as the table gives them, then sorted by key, as pairs [m][2] and rows
     if ((rc = grow_scratch(ctx, ctx->d_adj_list, 6u * m, fn, "pair list")) || (rc = grow_scratch(ctx, ctx->h_adj_list, 12u * m, fn, "pair list"))) return rc;
-    O2V_LAUNCH("k_adj_list", s, k_adj_list, dim3(stream_grid(ctx, slots, 16u)), dim3(kBlock), 0, s, ctx->d_adj_keys.ptr, ctx->d_adj_rows.ptr, slots, values ? 1u : 0u,
+    O2V_LAUNCH("k_pt_list", s, (k_pt_list<long long, kAdjCols>), dim3(stream_grid(ctx, slots, 16u)), dim3(kBlock), 0, s, ctx->d_adj_keys.ptr, ctx->d_adj_rows.ptr, slots, values ? kAdjCols : 3u,
                ctx->d_adj_list.ptr, reinterpret_cast<long long *>(ctx->d_adj_list.ptr + m), ctr + 4);
     O2V_CHECK(hipGetLastError());
     if (m) O2V_CHECK(hipMemcpyAsync(ctx->h_adj_list.ptr, ctx->d_adj_list.ptr, 48u * m, hipMemcpyDeviceToHost, s));

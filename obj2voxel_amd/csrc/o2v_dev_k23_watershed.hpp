@@ -1,5 +1,5 @@
 // o2v_dev_k23_watershed.hpp -- K23: the watershed basins of a relief, merged by persistence (o2v_hip_watershed_dense).  Included
-// from o2v_device.hip inside its anonymous namespace, after K12 (CcGrid, cc_index, cc_root_word, k_cc_count) and K22.
+// from o2v_device.hip inside its anonymous namespace, after K12 (CcGrid, cc_index, cc_root_word, k_cc_count), K22 and the pair table.
 //
 // The definition (include/o2v_hip.h, tests/watershed_ref.py).  H is an int32 relief, S = { v : H[v] > 0 }, i(v) = (z * ny + y) * nx
 // + x the linear index (below 2^31), K(v) = (H[v], i(v)) the key, compared lexicographically: a strict total order.  For v in S
@@ -25,11 +25,10 @@
 //   k_ws_peaks         the peaks' indices and heights, by rank, for the host.
 //   k_ws_pairs         (min_depth > 0, two peaks or more) a voxel looks back at its 3, 9 or 13 earlier neighbours, so every
 //                      unordered pair is seen once; where the peaks differ, key (smaller peak) << 32 | larger peak and value
-//                      min(H[u], H[v]) go into an open-addressing table in global memory: a plain read, else a 64-bit atomicCAS
-//                      on the key, linear probing, atomicMax on the 32-bit value where it is below.  A probe run of
-//                      kWsProbeLimit slots (or the whole table) without a place sets the overflow word: the host doubles the
-//                      table, clears it and runs this stage again.
-//   k_ws_pairs_list    the table's entries as a list (any order: the host sorts).  Only the set of distinct pairs and their
+//                      min(H[u], H[v]) go into the pair table (pt_slot) and its 32-bit values: atomicMax where a plain read finds
+//                      the value below.  A probe run without a place sets the overflow word: the host doubles the table, clears
+//                      it and runs this stage again.
+//   k_pt_list<uint32_t, 1>   the table's entries as a list (any order: the host sorts).  Only the set of distinct pairs and their
 //                      maxima leaves the stage, whatever the table's size and the order of insertion.
 //   ws_merge           on the host (plain C++): the sort, the elder-rule union-find, the final chains, label_of_rank.
 //   k_ws_labels        labels = label_of_rank[rank(P[v])] (rank + 1 without a merge), 0 outside S, through the strides.
@@ -38,22 +37,18 @@
 constexpr uint32_t kWsOutside = 0xffffffffu;                 // P of a voxel outside S
 constexpr uint32_t kWsHaloX = 66u, kWsHaloY = 10u, kWsHaloZ = 10u, kWsHalo = kWsHaloX * kWsHaloY * kWsHaloZ;
 constexpr uint32_t kWsExit = 0x80000000u;                    // an LDS word that holds a global index: a peak, or the parent outside the tile
-constexpr uint64_t kWsEmpty = ~0ull;                         // a free slot of the pair table (no pair: peaks are below 2^31)
-constexpr uint32_t kWsProbeLimit = 128u;                     // slots a probe run looks at before it reports overflow
-constexpr uint32_t kWsTableMinLog2 = 10u, kWsTableMaxLog2 = 40u;
+constexpr uint32_t kWsTableMaxLog2 = 40u;
 
 #ifndef O2V_WS_HOST
 #define O2V_WS_FN __device__ __forceinline__
 O2V_WS_FN uint32_t ws_load(const uint32_t *p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
 O2V_WS_FN void ws_store(uint32_t *p, uint32_t v) { __atomic_store_n(p, v, __ATOMIC_RELAXED); }
-O2V_WS_FN uint64_t ws_load64(const unsigned long long *p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
-O2V_WS_FN uint64_t ws_cas64(unsigned long long *p, uint64_t expect, uint64_t v) { return atomicCAS(p, (unsigned long long) expect, (unsigned long long) v); }
 O2V_WS_FN void ws_max32(uint32_t *p, uint32_t v) { (void) atomicMax(p, v); }
 #endif
 
 // ---- the key, the offsets, the ascent, the follow, the table, the merge ----------------------------------------------------------
-// (Plain C++ from here to the kernels: tests/test_host_watershed.py compiles this part for the host, with O2V_WS_FN, ws_load,
-// ws_store, ws_load64, ws_cas64 and ws_max32 of its own, runs it tile by tile in a shuffled order against the reference and checks
+// (Plain C++ from here to the kernels: tests/test_host_watershed.py compiles this part for the host behind the pair table's, with
+// O2V_WS_FN, ws_load, ws_store and ws_max32 of its own, runs it tile by tile in a shuffled order against the reference and checks
 // that a change is caught.)
 
 // The 26 offsets in ascending (dz, dy, dx) order, k = 0 .. 26 without 13: K20's order.  k < 13: the neighbour's index is smaller.
@@ -65,8 +60,8 @@ O2V_WS_FN bool ws_offset_on(uint32_t conn, int k)
 #ifdef O2V_WS_MUTATE_DROP_DIAGONAL
     if (k == 8) return false;   // (test only: the offset (+1, +1, -1) left out)
 #endif
-    const int axes = (ws_dx(k) != 0) + (ws_dy(k) != 0) + (ws_dz(k) != 0);
-    return k != 13 && axes <= (conn == 6u ? 1 : conn == 18u ? 2 : 3);
+    const uint32_t axes = (uint32_t) (ws_dx(k) != 0) + (uint32_t) (ws_dy(k) != 0) + (uint32_t) (ws_dz(k) != 0);
+    return k != 13 && axes <= pt_max_axes(conn);
 }
 
 // K(v) packed: H in 1 .. 2^31 - 1, i below 2^31
@@ -126,27 +121,16 @@ O2V_WS_FN uint32_t ws_root(const uint32_t *P, uint32_t i)
     }
 }
 
-O2V_WS_FN uint64_t ws_pair_key(uint32_t a, uint32_t b) { return a < b ? (uint64_t) a << 32 | b : (uint64_t) b << 32 | a; }
-O2V_WS_FN uint64_t ws_hash(uint64_t key, uint32_t log2) { return (key * 0x9e3779b97f4a7c15ull) >> (64u - log2); }
-
-// (key, value) into the table of 2^log2 slots: the value of a key becomes the maximum of what was inserted for it.  Returns 1
-// if the key took a free slot, 0 if it was there, -1 if the probe run found neither (overflow: the table has to grow).
-O2V_WS_FN int ws_table_insert(unsigned long long *keys, uint32_t *vals, uint32_t log2, uint64_t key, uint32_t val)
+// (key, value) into the pair table of 2^log2 slots (pt_slot): the value of a key becomes the maximum of what was inserted for
+// it.  Returns 1 if the key took a free slot, 0 if it was there, -1 if the probe run found neither (the table has to grow).
+template <typename Cas>
+O2V_WS_FN int ws_table_insert(unsigned long long *keys, uint32_t *vals, uint32_t log2, uint64_t key, uint32_t val, Cas &&cas)
 {
-    const uint64_t mask = (1ull << log2) - 1ull, run = mask + 1ull < kWsProbeLimit ? mask + 1ull : kWsProbeLimit;
-    uint64_t slot = ws_hash(key, log2);
-    for (uint64_t n = 0; n < run; ++n, slot = (slot + 1ull) & mask) {
-        uint64_t cur = ws_load64(keys + slot);
-        int fresh = 0;
-        if (cur == kWsEmpty) {
-            cur = ws_cas64(keys + slot, kWsEmpty, key);
-            if (cur == kWsEmpty) cur = key, fresh = 1;
-        }
-        if (cur != key) continue;
-        if (ws_load(vals + slot) < val) ws_max32(vals + slot, val);   // (a plain read first: a pair's voxels mostly repeat its maximum)
-        return fresh;
-    }
-    return -1;
+    bool fresh;
+    const uint64_t slot = pt_slot(keys, log2, key, cas, fresh);
+    if (slot == kPtNoPlace) return -1;
+    if (ws_load(vals + slot) < val) ws_max32(vals + slot, val);   // (a plain read first: a pair's voxels mostly repeat its maximum)
+    return fresh ? 1 : 0;
 }
 
 // The merge, on the host.  The n peaks by rank (ascending index) with their heights, the m distinct adjacent pairs in any order
@@ -199,15 +183,7 @@ inline uint32_t ws_merge(uint32_t n, const uint32_t *peak_index, const int32_t *
 // ---- kernels ---------------------------------------------------------------------------------------------------------------------
 #ifndef O2V_WS_HOST
 
-// the relief as the kernels read it: the caller's pointer and element strides
-struct WsRelief {
-    const int32_t *p;
-    uint64_t s0, s1, s2;
-};
-
-__device__ __forceinline__ int32_t ws_relief_at(const WsRelief &H, uint32_t x, uint32_t y, uint32_t z) { return H.p[(uint64_t) x * H.s0 + (uint64_t) y * H.s1 + (uint64_t) z * H.s2]; }
-
-__global__ __launch_bounds__(kBlock) void k_ws_ascent_tiles(CcGrid g, WsRelief H, uint32_t *__restrict__ P)
+__global__ __launch_bounds__(kBlock) void k_ws_ascent_tiles(CcGrid g, I32View H, uint32_t *__restrict__ P)
 {
     __shared__ int32_t s_h[kWsHalo];            // 26 400 bytes: [10 z][10 y][66 x], max(H, 0)
     __shared__ uint32_t s_q[kCcTileVoxels];     // 16 384 bytes: ws_tile_word
@@ -221,7 +197,7 @@ __global__ __launch_bounds__(kBlock) void k_ws_ascent_tiles(CcGrid g, WsRelief H
         for (uint32_t e = threadIdx.x; e < kWsHalo; e += kBlock) {
             const uint32_t r = e / kWsHaloX, hx = e - r * kWsHaloX, hz = r / kWsHaloY, hy = r - hz * kWsHaloY;
             const uint32_t x = x0 + hx - 1u, y = y0 + hy - 1u, z = z0 + hz - 1u;   // (-1 wraps above any dim)
-            const int32_t v = x < g.nx && y < g.ny && z < g.nz ? ws_relief_at(H, x, y, z) : 0;
+            const int32_t v = x < g.nx && y < g.ny && z < g.nz ? H.at(x, y, z) : 0;
             s_h[e] = v > 0 ? v : 0;
         }
         __syncthreads();
@@ -245,7 +221,7 @@ __global__ __launch_bounds__(kBlock) void k_ws_ascent_tiles(CcGrid g, WsRelief H
 }
 
 // O2V_WS_NO_TILES: the neighbours from global memory, P[i] = the parent
-__global__ __launch_bounds__(kBlock) void k_ws_ascent(CcGrid g, WsRelief H, uint32_t *__restrict__ P)
+__global__ __launch_bounds__(kBlock) void k_ws_ascent(CcGrid g, I32View H, uint32_t *__restrict__ P)
 {
     const uint32_t lane = threadIdx.x & 63u, sy = g.nx, sz = g.nx * g.ny;
     for (const uint64_t wi : bits_words(g)) {
@@ -253,14 +229,14 @@ __global__ __launch_bounds__(kBlock) void k_ws_ascent(CcGrid g, WsRelief H, uint
         const uint32_t x = at.wx * 64u + lane, y = at.y, z = at.z;
         if (x >= g.nx) continue;
         const uint32_t i = cc_index(g, x, y, z);
-        const int32_t h = ws_relief_at(H, x, y, z);
+        const int32_t h = H.at(x, y, z);
         if (h <= 0) {
             P[i] = kWsOutside;
             continue;
         }
         const int k = ws_ascent_step(g.conn, h, i, sy, sz, [&](int n) {
             const uint32_t X = x + (uint32_t) ws_dx(n), Y = y + (uint32_t) ws_dy(n), Z = z + (uint32_t) ws_dz(n);
-            return X < g.nx && Y < g.ny && Z < g.nz ? ws_relief_at(H, X, Y, Z) : 0;
+            return X < g.nx && Y < g.ny && Z < g.nz ? H.at(X, Y, Z) : 0;
         });
         P[i] = k < 0 ? i : ws_neighbour(i, k, sy, sz);
     }
@@ -297,7 +273,7 @@ __device__ __forceinline__ uint32_t ws_rank(const CcGrid &g, uint32_t r, const u
 }
 
 // index[rank] and height[rank] of every peak
-__global__ __launch_bounds__(kBlock) void k_ws_peaks(CcGrid g, WsRelief H, const unsigned long long *__restrict__ peaks, const uint32_t *__restrict__ local,
+__global__ __launch_bounds__(kBlock) void k_ws_peaks(CcGrid g, I32View H, const unsigned long long *__restrict__ peaks, const uint32_t *__restrict__ local,
                                                      const unsigned long long *__restrict__ block_offsets, uint32_t *__restrict__ index,
                                                      int32_t *__restrict__ height)
 {
@@ -308,13 +284,13 @@ __global__ __launch_bounds__(kBlock) void k_ws_peaks(CcGrid g, WsRelief H, const
         const BitWord at = bits_word_at(g, wi);
         const uint32_t x = at.wx * 64u + lane, rank = (uint32_t) block_offsets[wi / kBlock] + local[wi] + (uint32_t) __popcll(w & ((1ull << lane) - 1ull));
         index[rank] = cc_index(g, x, at.y, at.z);
-        height[rank] = ws_relief_at(H, x, at.y, at.z);
+        height[rank] = H.at(x, at.y, at.z);
     }
 }
 
 // ctr[0]: overflow, ctr[1] += the distinct pairs (the slots taken), ctr[2] += the boundary pairs seen (Count: O2V_HIP_FLAG_STAGE_TIMES)
 template <bool Count>
-__global__ __launch_bounds__(kBlock) void k_ws_pairs(CcGrid g, WsRelief H, const uint32_t *__restrict__ P, unsigned long long *keys, uint32_t *vals,
+__global__ __launch_bounds__(kBlock) void k_ws_pairs(CcGrid g, I32View H, const uint32_t *__restrict__ P, unsigned long long *keys, uint32_t *vals,
                                                      uint32_t log2, unsigned long long *ctr)
 {
     const uint32_t lane = threadIdx.x & 63u, sy = g.nx, sz = g.nx * g.ny;
@@ -334,9 +310,9 @@ __global__ __launch_bounds__(kBlock) void k_ws_pairs(CcGrid g, WsRelief H, const
             if (X >= g.nx || Y >= g.ny || Z >= g.nz) continue;
             const uint32_t other = P[ws_neighbour(i, k, sy, sz)];
             if (other == kWsOutside || other == mine) continue;
-            if (!h) h = ws_relief_at(H, x, y, z);
-            const int32_t hn = ws_relief_at(H, X, Y, Z);
-            const int got = ws_table_insert(keys, vals, log2, ws_pair_key(mine, other), (uint32_t) (h < hn ? h : hn));
+            if (!h) h = H.at(x, y, z);
+            const int32_t hn = H.at(X, Y, Z);
+            const int got = ws_table_insert(keys, vals, log2, pt_key(mine, other), (uint32_t) (h < hn ? h : hn), PtCas{});
             ++seen, fresh += got > 0 ? 1u : 0u, overflow |= got < 0;
         }
     }
@@ -346,27 +322,6 @@ __global__ __launch_bounds__(kBlock) void k_ws_pairs(CcGrid g, WsRelief H, const
     if (Count) {
         for (int d = 32; d >= 1; d >>= 1) seen += __shfl_xor(seen, d);
         if (lane == 0u && seen) atomicAdd(ctr + 2, (unsigned long long) seen);
-    }
-}
-
-// the taken slots of the table as a list, in any order; *n counts them
-__global__ __launch_bounds__(kBlock) void k_ws_pairs_list(const unsigned long long *__restrict__ keys, const uint32_t *__restrict__ vals, uint64_t slots,
-                                                          unsigned long long *__restrict__ list_keys, uint32_t *__restrict__ list_vals, unsigned long long *n)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-    for (uint64_t base = ((uint64_t) blockIdx.x * kBlock + (threadIdx.x & ~63u)); base < slots; base += (uint64_t) gridDim.x * kBlock) {
-        const uint64_t s = base + lane;
-        const unsigned long long key = s < slots ? keys[s] : kWsEmpty;
-        const unsigned long long taken = __ballot(key != kWsEmpty);
-        if (!taken) continue;
-        unsigned long long first = 0;
-        if (lane == 0u) first = atomicAdd(n, (unsigned long long) __popcll(taken));
-        first = __shfl(first, 0);
-        if (key != kWsEmpty) {
-            const uint64_t at = first + (uint64_t) __popcll(taken & ((1ull << lane) - 1ull));
-            list_keys[at] = key;
-            list_vals[at] = vals[s];
-        }
     }
 }
 

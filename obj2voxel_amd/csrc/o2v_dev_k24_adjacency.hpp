@@ -1,7 +1,8 @@
 // o2v_dev_k24_adjacency.hpp -- K24: the region adjacency of a label grid (o2v_hip_adjacency_count / _write): per pair of labels
 // a < b that touch a row of 5 int64 - the face, edge-only and corner-only contacts, and with a values grid V the maximum over the
 // contacts of min(V[u], V[v]) and the minimum of max(V[u], V[v]).  Included from o2v_device.hip inside its anonymous namespace,
-// after K23; it takes the chunk (LsVec, ls_value, ls_shift_up, ls_diff, ls_lane) and the read (ls_read, ls_load1) of K19.
+// after K23; it takes the chunk (LsVec, ls_value, ls_shift_up, ls_diff, ls_lane) and the read (ls_read, ls_load1) of K19 and the
+// table in global memory of o2v_dev_pair_table.hpp (pt_key, pt_hash, pt_slot, k_pt_list, I32View).
 //
 //   k_adj_init             the keys of the table in global memory: ~0 (free); its rows: 0, 0, 0, kAdjNoMax, kAdjNoMin.
 //   k_adj_pairs<Format, Connectivity, Values, Vec>   the one pass.  K19's cut of the rows: chunks of 16 bytes along x (4 int32 or
@@ -15,16 +16,15 @@
 //                          for the wavefront if all its pending pairs are one pair.  A flush goes into a table per workgroup in
 //                          LDS, open-addressed by the key a << 32 | b (adj_find_slot: kAdjSlots slots, kAdjProbes probes, a slot
 //                          is claimed by a 64-bit compare-and-swap), with 64-bit LDS add / max / min; a flush that finds no slot goes
-//                          to the table in global memory (adj_table_slot: K23's hash and probe run, five accumulators a slot), and so
-//                          does every flush with table = 0 (O2V_ADJ_NO_TABLE=1).  At its end the workgroup adds its occupied
-//                          slots to the global table.  A probe run there that finds no slot sets the overflow word: the host
-//                          doubles the table and runs the pass again.
-//   k_adj_list             the occupied slots of the global table as a list (keys, rows), in any order - the host sorts -, counted.
+//                          to the table in global memory (adj_to_global: pt_slot, five accumulators a slot), and so does every
+//                          flush with table = 0 (O2V_ADJ_NO_TABLE=1).  At its end the workgroup adds its occupied slots to the
+//                          global table.  A probe run there that finds no slot sets the overflow word: the host doubles the
+//                          table and runs the pass again.
+//   k_pt_list<long long, 5>   the global table's occupied slots as a list, any order, counted; without values columns 3 and 4 are 0.
 // Every column is an integer sum, maximum or minimum, so the table does not depend on any order.  No private segment.
 
 constexpr uint32_t kAdjCols = 5;                                      // O2V_HIP_ADJ_COLUMNS
 constexpr uint32_t kAdjFace = 0, kAdjEdge = 1, kAdjCorner = 2, kAdjHigh = 3, kAdjLow = 4;
-constexpr uint64_t kAdjEmpty = ~0ull;                                 // a free slot (no pair: labels are below 2^31)
 constexpr long long kAdjNoMax = -(1ll << 40), kAdjNoMin = 1ll << 40;  // columns 3 and 4 before any contact (a value is an int32)
 #ifndef O2V_ADJ_SLOT_BITS
 #define O2V_ADJ_SLOT_BITS 9
@@ -32,18 +32,16 @@ constexpr long long kAdjNoMax = -(1ll << 40), kAdjNoMin = 1ll << 40;  // columns
 constexpr uint32_t kAdjSlotBits = O2V_ADJ_SLOT_BITS, kAdjSlots = 1u << kAdjSlotBits;   // slots of a workgroup's table: 24 KiB of LDS
 constexpr uint32_t kAdjProbes = 16;                                   // slots a flush looks at before it goes to global memory
 constexpr uint32_t kAdjNoSlot = ~0u;
-constexpr uint32_t kAdjProbeLimit = 128;                              // slots a probe run of the global table looks at (K23's)
-constexpr uint64_t kAdjNoPlace = ~0ull;
-constexpr uint32_t kAdjTableMinLog2 = 10u, kAdjTableMaxLog2 = 36u;
+constexpr uint32_t kAdjTableMaxLog2 = 36u;
 constexpr uint32_t kAdjRows = 5;                                      // own, (y-1, z), (y-1, z-1), (y, z-1), (y+1, z-1)
 
 #ifndef O2V_ADJ_HOST
 #define O2V_ADJ_FN __host__ __device__ __forceinline__
 #endif
 
-// ---- contacts: the chunk's rows, the class, the key, the pending pair, the slot probes ------------------------------------------
-// (Plain C++ from here to the kernels: tests/test_host_adjacency.py compiles this part for the host behind K19's, with O2V_ADJ_FN
-// of its own, and runs it chunk by chunk against the reference.)
+// ---- contacts: the chunk's rows, the class, the pending pair, the probes of the table in LDS ------------------------------------
+// (Plain C++ from here to the kernels: tests/test_host_adjacency.py compiles this part for the host behind K19's and the pair
+// table's, with O2V_ADJ_FN of its own, and runs it chunk by chunk against the reference.)
 
 // The rows a chunk of n elements at x0 looks at.  row[r]: 0 its own, 1 (y-1, z), 2 (y-1, z-1), 3 (y, z-1), 4 (y+1, z-1); have: bit r,
 // the row lies in the box; before[r] / behind[r]: the element at x0 - 1 / x0 + n of row r, read where has_before / has_behind.
@@ -70,10 +68,9 @@ O2V_ADJ_FN int adj_row_dy(uint32_t r) { return r == 0u || r == 3u ? 0 : r == 4u 
 O2V_ADJ_FN int adj_row_dz(uint32_t r) { return r >= 2u ? -1 : 0; }
 // The class of a contact: the axes on which the two voxels differ - 1 a face, 2 an edge only, 3 a corner only.
 O2V_ADJ_FN uint32_t adj_class(int dx, int dy, int dz) { return (uint32_t) (dx != 0) + (uint32_t) (dy != 0) + (uint32_t) (dz != 0); }
-O2V_ADJ_FN uint32_t adj_max_class(uint32_t conn) { return conn == 6u ? 1u : conn == 18u ? 2u : 3u; }
 // Row r is read at connectivity conn; its elements before and behind the chunk are.
-O2V_ADJ_FN bool adj_row_on(uint32_t conn, uint32_t r) { return adj_class(0, adj_row_dy(r), adj_row_dz(r)) <= adj_max_class(conn); }
-O2V_ADJ_FN bool adj_ends_on(uint32_t conn, uint32_t r) { return adj_class(1, adj_row_dy(r), adj_row_dz(r)) <= adj_max_class(conn); }
+O2V_ADJ_FN bool adj_row_on(uint32_t conn, uint32_t r) { return adj_class(0, adj_row_dy(r), adj_row_dz(r)) <= pt_max_axes(conn); }
+O2V_ADJ_FN bool adj_ends_on(uint32_t conn, uint32_t r) { return adj_class(1, adj_row_dy(r), adj_row_dz(r)) <= pt_max_axes(conn); }
 
 // The chunk moved down by one element: element j is element j + 1 of v, the last element of a full chunk is `behind`.  (A chunk
 // that is not full ends its row: nothing is behind it.)
@@ -105,7 +102,7 @@ O2V_ADJ_FN uint32_t adj_chunk_masks(const AdjChunk &c, uint32_t masks[3u * kAdjR
         for (int dx = -1; dx <= 1; ++dx) {
             uint32_t m = 0;
             const bool earlier = r > 0u || dx < 0;
-            if (earlier && adj_class(dx, adj_row_dy(r), adj_row_dz(r)) <= adj_max_class(Conn) && ((c.have >> r) & 1u)) {
+            if (earlier && adj_class(dx, adj_row_dy(r), adj_row_dz(r)) <= pt_max_axes(Conn) && ((c.have >> r) & 1u)) {
                 const uint32_t valid = dx < 0 ? (c.has_before ? all : all & ~1u) : dx > 0 ? (c.has_behind ? all : all >> 1) : all;
                 const LsVec other = dx < 0 ? ls_shift_up<Format>(c.row[r], c.before[r]) : dx > 0 ? adj_shift_down<Format>(c.row[r], c.behind[r]) : c.row[r];
                 m = adj_diff<Format>(c.row[0], other) & valid;
@@ -139,7 +136,6 @@ O2V_ADJ_FN int32_t adj_neighbour_value(const AdjChunk &c, uint32_t r, int dx, ui
 // A value takes part: lo <= v <= n_labels (lo: 0 or 1, n_labels below 2^31 - 1).
 O2V_ADJ_FN bool adj_counted(int32_t v, uint32_t lo, uint32_t n_labels) { return v >= (int32_t) lo && (uint32_t) v <= n_labels; }
 O2V_ADJ_FN bool adj_outside(int32_t v, uint32_t n_labels) { return v < 0 || (uint32_t) v > n_labels; }
-O2V_ADJ_FN uint64_t adj_key(int32_t a, int32_t b) { return a < b ? (uint64_t) (uint32_t) a << 32 | (uint32_t) b : (uint64_t) (uint32_t) b << 32 | (uint32_t) a; }
 
 // The contacts of a chunk (masks: adj_chunk_masks' with a union that is not 0): emit(j, r, dx, a, b, cls) per contact between
 // element j, of value a, and its neighbour in row r at x offset dx, of value b != a.
@@ -168,7 +164,7 @@ struct AdjPending {
     long long hi, lo;
 };
 
-O2V_ADJ_FN void adj_pending_clear(AdjPending &p) { p.key = kAdjEmpty, p.cnt[0] = p.cnt[1] = p.cnt[2] = 0u, p.hi = kAdjNoMax, p.lo = kAdjNoMin; }
+O2V_ADJ_FN void adj_pending_clear(AdjPending &p) { p.key = kPtEmpty, p.cnt[0] = p.cnt[1] = p.cnt[2] = 0u, p.hi = kAdjNoMax, p.lo = kAdjNoMin; }
 
 // One contact of class cls of the pair `key` (values va, vb of the two voxels where with_values) into the pending pair;
 // flush(pending) first where the pair changes.
@@ -176,7 +172,7 @@ template <typename Flush>
 O2V_ADJ_FN void adj_merge(AdjPending &p, uint64_t key, uint32_t cls, bool with_values, int32_t va, int32_t vb, Flush &&flush)
 {
     if (p.key != key) {
-        if (p.key != kAdjEmpty) flush(p);
+        if (p.key != kPtEmpty) flush(p);
         adj_pending_clear(p);
         p.key = key;
     }
@@ -201,46 +197,22 @@ O2V_ADJ_FN void adj_apply(const AdjPending &p, bool with_values, Add &&add, Rais
 
 O2V_ADJ_FN long long adj_init_value(uint32_t column) { return column == kAdjHigh ? kAdjNoMax : column == kAdjLow ? kAdjNoMin : 0; }
 
-O2V_ADJ_FN uint64_t adj_hash(uint64_t key, uint32_t log2) { return (key * 0x9e3779b97f4a7c15ull) >> (64u - log2); }   // (K23's ws_hash)
-
-// The slot of `key` in a workgroup's table of kAdjSlots keys (kAdjEmpty: free), claimed if it has none yet: linear probing from
+// The slot of `key` in a workgroup's table of kAdjSlots keys (kPtEmpty: free), claimed if it has none yet: linear probing from
 // the key's hash, kAdjNoSlot if none of kAdjProbes slots is the key's or free.  cas(p, expected, desired) returns what *p held.
 template <typename Cas>
 O2V_ADJ_FN uint32_t adj_find_slot(unsigned long long *keys, uint64_t key, Cas &&cas)
 {
-    uint32_t h = (uint32_t) adj_hash(key, kAdjSlotBits);
+    uint32_t h = (uint32_t) pt_hash(key, kAdjSlotBits);
     for (uint32_t i = 0; i < kAdjProbes && i < kAdjSlots; ++i, h = (h + 1u) & (kAdjSlots - 1u)) {
         uint64_t seen = *(volatile unsigned long long *) (keys + h);
-        if (seen == kAdjEmpty) seen = cas(keys + h, kAdjEmpty, key);
-        if (seen == kAdjEmpty || seen == key) return h;
+        if (seen == kPtEmpty) seen = cas(keys + h, kPtEmpty, key);
+        if (seen == kPtEmpty || seen == key) return h;
     }
     return kAdjNoSlot;
 }
 
-// The slot of `key` in the global table of 2^log2 keys, claimed if it has none yet (K23's ws_table_insert without the value):
-// kAdjNoPlace if a probe run of kAdjProbeLimit slots (or the whole table) found neither - the table has to grow.  fresh: this call
-// took a free slot for the key.
-template <typename Cas>
-O2V_ADJ_FN uint64_t adj_table_slot(unsigned long long *keys, uint32_t log2, uint64_t key, Cas &&cas, bool &fresh)
-{
-    fresh = false;
-    const uint64_t mask = (1ull << log2) - 1ull, run = mask + 1ull < kAdjProbeLimit ? mask + 1ull : kAdjProbeLimit;
-    uint64_t slot = adj_hash(key, log2);
-    for (uint64_t n = 0; n < run; ++n, slot = (slot + 1ull) & mask) {
-        uint64_t cur = *(volatile unsigned long long *) (keys + slot);
-        if (cur == kAdjEmpty) {
-            cur = cas(keys + slot, kAdjEmpty, key);
-            if (cur == kAdjEmpty) cur = key, fresh = true;
-        }
-        if (cur == key) return slot;
-    }
-    return kAdjNoPlace;
-}
-
 // ---- kernels -----------------------------------------------------------------------------------------------------------------
 #ifndef O2V_ADJ_HOST
-
-#define O2V_ADJ_CAS [](unsigned long long *p, uint64_t expected, uint64_t desired) { return (uint64_t) atomicCAS(p, (unsigned long long) expected, (unsigned long long) desired); }
 
 struct AdjGrid {
     uint32_t n[3];
@@ -253,12 +225,6 @@ struct AdjGrid {
     uint32_t count;            // 1: the flushes are counted (O2V_HIP_FLAG_STAGE_TIMES)
 };
 
-// the values as the kernel reads them: the caller's pointer and element strides
-struct AdjValues {
-    const int32_t *p;
-    uint64_t s0, s1, s2;
-};
-
 // ctr: [0] overflow, [1] voxels outside [0, n_labels], [2] flushes into LDS, [3] flushes to global memory, [4] listed pairs, [5] slots taken
 constexpr uint32_t kAdjCtrs = 8;
 
@@ -267,32 +233,38 @@ __global__ __launch_bounds__(kBlock) void k_adj_init(unsigned long long *__restr
     const uint64_t n = slots * kAdjCols, step = (uint64_t) gridDim.x * kBlock;
     for (uint64_t i = (uint64_t) blockIdx.x * kBlock + threadIdx.x; i < n; i += step) {
         rows[i] = adj_init_value((uint32_t) (i % kAdjCols));
-        if (i < slots) keys[i] = kAdjEmpty;
+        if (i < slots) keys[i] = kPtEmpty;
     }
 }
 
-// a pending pair, or a slot of a workgroup's table, into the global table; false: no slot (overflow)
-__device__ __forceinline__ bool adj_to_global(const AdjPending &p, bool with_values, unsigned long long *keys, long long *rows, uint32_t log2, uint32_t &n_fresh)
+// What a pending pair, or a slot of a workgroup's table, holds of the pair `key` - its contacts by class (a workgroup's sums pass
+// 2^32) and its two passes - into the global table; false: no slot (overflow).
+__device__ __forceinline__ bool adj_to_global(uint64_t key, uint64_t faces, uint64_t edges, uint64_t corners, bool with_values, long long hi, long long lo,
+                                              unsigned long long *keys, long long *rows, uint32_t log2, uint32_t &n_fresh)
 {
     bool fresh;
-    const uint64_t slot = adj_table_slot(keys, log2, p.key, O2V_ADJ_CAS, fresh);
+    const uint64_t slot = pt_slot(keys, log2, key, PtCas{}, fresh);
     n_fresh += fresh ? 1u : 0u;
-    if (slot == kAdjNoPlace) return false;
+    if (slot == kPtNoPlace) return false;
     long long *const row = rows + slot * kAdjCols;
-    adj_apply(p, with_values, [&](uint32_t c, uint64_t v) { atomicAdd(reinterpret_cast<unsigned long long *>(row + c), (unsigned long long) v); },
-              [&](uint32_t c, long long v) { if (*(volatile long long *) (row + c) < v) atomicMax(row + c, v); },    // (a plain read first: a pair's
-              [&](uint32_t c, long long v) { if (*(volatile long long *) (row + c) > v) atomicMin(row + c, v); });   //  contacts mostly repeat its passes)
+    if (faces) atomicAdd(reinterpret_cast<unsigned long long *>(row + kAdjFace), (unsigned long long) faces);
+    if (edges) atomicAdd(reinterpret_cast<unsigned long long *>(row + kAdjEdge), (unsigned long long) edges);
+    if (corners) atomicAdd(reinterpret_cast<unsigned long long *>(row + kAdjCorner), (unsigned long long) corners);
+    if (with_values) {   // (a plain read first: a pair's contacts mostly repeat its passes)
+        if (*(volatile long long *) (row + kAdjHigh) < hi) atomicMax(row + kAdjHigh, hi);
+        if (*(volatile long long *) (row + kAdjLow) > lo) atomicMin(row + kAdjLow, lo);
+    }
     return true;
 }
 
 template <uint32_t Format, uint32_t Conn, bool Values, bool Vec>
-__global__ __launch_bounds__(kBlock) void k_adj_pairs(RaySource src, AdjValues V, AdjGrid g, unsigned long long *keys, long long *rows, unsigned long long *ctr)
+__global__ __launch_bounds__(kBlock) void k_adj_pairs(RaySource src, I32View V, AdjGrid g, unsigned long long *keys, long long *rows, unsigned long long *ctr)
 {
     constexpr uint32_t K = ls_lane<Format>();
     __shared__ unsigned long long s_key[kAdjSlots];
     __shared__ long long s_tab[kAdjSlots * kAdjCols];
     if (g.table) {
-        for (uint32_t i = threadIdx.x; i < kAdjSlots; i += kBlock) s_key[i] = kAdjEmpty;
+        for (uint32_t i = threadIdx.x; i < kAdjSlots; i += kBlock) s_key[i] = kPtEmpty;
         for (uint32_t i = threadIdx.x; i < kAdjSlots * kAdjCols; i += kBlock) s_tab[i] = adj_init_value(i % kAdjCols);
         __syncthreads();
     }
@@ -302,7 +274,7 @@ __global__ __launch_bounds__(kBlock) void k_adj_pairs(RaySource src, AdjValues V
     uint32_t to_lds = 0, to_global = 0, n_fresh = 0;
     bool overflow = false;
     const auto flush = [&](const AdjPending &p) {
-        const uint32_t slot = g.table ? adj_find_slot(s_key, p.key, O2V_ADJ_CAS) : kAdjNoSlot;
+        const uint32_t slot = g.table ? adj_find_slot(s_key, p.key, PtCas{}) : kAdjNoSlot;
         const bool in_lds = slot != kAdjNoSlot;
         to_lds += in_lds ? 1u : 0u, to_global += in_lds ? 0u : 1u;   // (both sums in both branches: the counters stay in registers)
         if (in_lds) {
@@ -310,7 +282,7 @@ __global__ __launch_bounds__(kBlock) void k_adj_pairs(RaySource src, AdjValues V
             adj_apply(p, Values, [&](uint32_t c, uint64_t v) { atomicAdd(reinterpret_cast<unsigned long long *>(row + c), (unsigned long long) v); },
                       [&](uint32_t c, long long v) { atomicMax(row + c, v); }, [&](uint32_t c, long long v) { atomicMin(row + c, v); });
         } else {
-            overflow |= !adj_to_global(p, Values, keys, rows, g.log2, n_fresh);
+            overflow |= !adj_to_global(p.key, p.cnt[0], p.cnt[1], p.cnt[2], Values, p.hi, p.lo, keys, rows, g.log2, n_fresh);
         }
     };
     for (uint32_t gi = g0; gi < g1; ++gi) {
@@ -346,16 +318,15 @@ __global__ __launch_bounds__(kBlock) void k_adj_pairs(RaySource src, AdjValues V
                     int32_t va = 0, vb = 0;
                     if (Values) {
                         const uint32_t x = x0 + j;
-                        va = V.p[(uint64_t) x * V.s0 + (uint64_t) y * V.s1 + (uint64_t) z * V.s2];
-                        vb = V.p[(uint64_t) (uint32_t) ((int) x + dx) * V.s0 + (uint64_t) (uint32_t) ((int) y + adj_row_dy(r)) * V.s1 +
-                                 (uint64_t) (uint32_t) ((int) z + adj_row_dz(r)) * V.s2];
+                        va = V.at(x, y, z);
+                        vb = V.at((uint32_t) ((int) x + dx), (uint32_t) ((int) y + adj_row_dy(r)), (uint32_t) ((int) z + adj_row_dz(r)));
                     }
-                    adj_merge(pend, adj_key(a, b), cls, Values, va, vb, flush);
+                    adj_merge(pend, pt_key((uint32_t) a, (uint32_t) b), cls, Values, va, vb, flush);
                 });
             }
         }
         // the chunk's end: if every pending pair of the wavefront is one pair, one lane flushes their sum
-        const bool has = pend.key != kAdjEmpty;
+        const bool has = pend.key != kPtEmpty;
         const unsigned long long with = __ballot(has);
         if (!with) continue;
         const uint32_t first = (uint32_t) __builtin_ctzll(with);
@@ -381,23 +352,11 @@ __global__ __launch_bounds__(kBlock) void k_adj_pairs(RaySource src, AdjValues V
     if (g.table) {
         __syncthreads();
         for (uint32_t slot = threadIdx.x; slot < kAdjSlots; slot += kBlock) {
-            AdjPending p;
-            p.key = s_key[slot];
-            if (p.key == kAdjEmpty) continue;
+            const uint64_t key = s_key[slot];
+            if (key == kPtEmpty) continue;
             const long long *const row = s_tab + slot * kAdjCols;
-            p.cnt[0] = p.cnt[1] = p.cnt[2] = 0u, p.hi = row[kAdjHigh], p.lo = row[kAdjLow];
-            bool fresh;
-            const uint64_t at = adj_table_slot(keys, g.log2, p.key, O2V_ADJ_CAS, fresh);
-            n_fresh += fresh ? 1u : 0u;
-            if (at == kAdjNoPlace) {
-                overflow = true;
-                continue;
-            }
-            long long *const dst = rows + at * kAdjCols;
-#pragma unroll
-            for (uint32_t c = 0; c < 3u; ++c)
-                if (row[c]) atomicAdd(reinterpret_cast<unsigned long long *>(dst + c), (unsigned long long) row[c]);   // (a workgroup's sums pass 2^32)
-            if (Values) atomicMax(dst + kAdjHigh, p.hi), atomicMin(dst + kAdjLow, p.lo);
+            overflow |= !adj_to_global(key, (uint64_t) row[kAdjFace], (uint64_t) row[kAdjEdge], (uint64_t) row[kAdjCorner], Values, row[kAdjHigh], row[kAdjLow], keys, rows,
+                                       g.log2, n_fresh);
         }
     }
     if (overflow) ctr[0] = 1ull;   // (every writer stores the same word)
@@ -412,27 +371,4 @@ __global__ __launch_bounds__(kBlock) void k_adj_pairs(RaySource src, AdjValues V
     }
 }
 
-// the occupied slots of the table as a list, in any order; *n counts them.  Without values columns 3 and 4 are 0.
-__global__ __launch_bounds__(kBlock) void k_adj_list(const unsigned long long *__restrict__ keys, const long long *__restrict__ rows, uint64_t slots, uint32_t with_values,
-                                                     unsigned long long *__restrict__ list_keys, long long *__restrict__ list_rows, unsigned long long *n)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-    for (uint64_t base = ((uint64_t) blockIdx.x * kBlock + (threadIdx.x & ~63u)); base < slots; base += (uint64_t) gridDim.x * kBlock) {
-        const uint64_t s = base + lane;
-        const unsigned long long key = s < slots ? keys[s] : kAdjEmpty;
-        const unsigned long long taken = __ballot(key != kAdjEmpty);
-        if (!taken) continue;
-        unsigned long long first = 0;
-        if (lane == 0u) first = atomicAdd(n, (unsigned long long) __popcll(taken));
-        first = __shfl(first, 0);
-        if (key != kAdjEmpty) {
-            const uint64_t at = first + (uint64_t) __popcll(taken & ((1ull << lane) - 1ull));
-            list_keys[at] = key;
-#pragma unroll
-            for (uint32_t c = 0; c < kAdjCols; ++c) list_rows[at * kAdjCols + c] = c < 3u || with_values ? rows[s * kAdjCols + c] : 0;
-        }
-    }
-}
-
-#undef O2V_ADJ_CAS
 #endif   // O2V_ADJ_HOST

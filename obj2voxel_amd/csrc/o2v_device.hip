@@ -56,10 +56,11 @@
 //   K22 k_thin_*               o2v_hip_thin_dense: skeletons by topological thinning - eight subfields per iteration, a 26-voxel
 //                              bit test per border voxel, tile by tile in LDS, in place on the bit grid; outside the pipeline
 //   K23 k_ws_*                 o2v_hip_watershed_dense: watershed basins of an int32 relief by steepest ascent of a packed key, the
-//                              basins merged by persistence on the host; outside the pipeline
+//                              adjacent basins through the pair table, merged by persistence on the host; outside the pipeline
 //   K24 k_adj_*                o2v_hip_adjacency_count / _write: which labels of a label grid touch - per pair the face, edge and
-//                              corner contacts and the two passes of a values grid, one pass of K19's chunks into a pair table in
-//                              LDS and one in global memory, sorted on the host; outside the pipeline
+//                              corner contacts and the two passes of a values grid, one pass of K19's chunks into a table in LDS
+//                              and the pair table, sorted on the host; outside the pipeline
+//       k_pt_list              o2v_dev_pair_table.hpp: the table of id pairs in global memory of K23 and K24, its occupied slots as a list
 //   plan k_zhist               o2v_hip_plan_slabs: predicted hits per z layer -> work-balanced slabs for N GPUs
 // With the direct MAX path K1's counters reach the host while K2 runs, and only the stages that have work are enqueued
 // behind it.  N > 1 GPUs: o2v_hip_voxelize_sharded (bounds / work-histogram passes sharded over the ranks, RCCL).
@@ -120,6 +121,7 @@ namespace {
 #include "o2v_dev_k20_geodesic.hpp"
 #include "o2v_dev_k21_thickness.hpp"
 #include "o2v_dev_k22_thinning.hpp"
+#include "o2v_dev_pair_table.hpp"      // (the table of id pairs in global memory of K23 and K24)
 #include "o2v_dev_k23_watershed.hpp"   // (behind K12: its grid, index and prefix count)
 #include "o2v_dev_k24_adjacency.hpp"   // (behind K19: its chunk and its reads)
 

@@ -1,10 +1,12 @@
 """Region adjacency without a GPU: the numpy reference (tests/adjacency_ref.py) against the definition as a
-scalar loop, known answers, the plain C++ of o2v_dev_k24_adjacency.hpp compiled for the host behind K19's and run chunk by chunk
+scalar loop, known answers, the plain C++ of o2v_dev_k24_adjacency.hpp compiled for the host behind K19's and the pair table's
+(o2v_dev_pair_table.hpp, through tests/pair_table_host.py) and run chunk by chunk
 and wavefront by wavefront against the reference (with a tiny slot count, so that the probe limit is met, and one mutation seen to
 fail), and obj2voxel_amd.dense's label_adjacency, adjacency_neighbours, coordination and skeleton_graph against a stub of the device
-calls that computes with the references."""
+calls that computes with the references; the K24 kernels' metadata in the gfx950 code object."""
 import ctypes as C
 import os
+import re
 import shutil
 import subprocess
 
@@ -13,11 +15,12 @@ import pytest
 
 from tests import adjacency_ref as R
 from tests import label_stats_ref as LR
+from tests import pair_table_host
 
 torch = pytest.importorskip("torch")
 
 from obj2voxel_amd import dense, hip  # noqa: E402
-from tests.test_host_dense import HIPCC, SRC, on_cpu  # noqa: E402,F401
+from tests.test_host_dense import HIPCC, SRC, device_asm, on_cpu  # noqa: E402,F401
 from tests.test_host_label_stats import LsStub, _strided  # noqa: E402
 
 K19 = os.path.join(SRC, "o2v_dev_k19_label_stats.hpp")
@@ -139,10 +142,10 @@ static int adj_host_t(const T *grid, const int32_t *values, const uint32_t *dims
     const uint32_t nx = dims[0], ny = dims[1], nz = dims[2], cpr = (nx + K - 1u) / K;
     const uint64_t chunks = (uint64_t) cpr * ny * nz, slots = 1ull << log2;
     const bool with_values = values != nullptr;
-    std::vector<unsigned long long> s_key(kAdjSlots, kAdjEmpty);
+    std::vector<unsigned long long> s_key(kAdjSlots, kPtEmpty);
     std::vector<long long> s_tab(kAdjSlots * kAdjCols);
     for (uint32_t i = 0; i < kAdjSlots * kAdjCols; ++i) s_tab[i] = adj_init_value(i %% kAdjCols);
-    for (uint64_t i = 0; i < slots; ++i) keys[i] = kAdjEmpty;
+    for (uint64_t i = 0; i < slots; ++i) keys[i] = kPtEmpty;
     for (uint64_t i = 0; i < slots * kAdjCols; ++i) rows[i] = adj_init_value((uint32_t) (i %% kAdjCols));
     for (int i = 0; i < 6; ++i) ctr[i] = 0;
     auto at = [&](uint32_t x, uint32_t y, uint32_t z) { return ((size_t) z * ny + y) * nx + x; };
@@ -152,9 +155,9 @@ static int adj_host_t(const T *grid, const int32_t *values, const uint32_t *dims
     };
     auto to_global = [&](const AdjPending &p) {
         bool fresh;
-        const uint64_t slot = adj_table_slot(keys, log2, p.key, cas64, fresh);
+        const uint64_t slot = pt_slot(keys, log2, p.key, cas64, fresh);
         ctr[5] += fresh;
-        if (slot == kAdjNoPlace) ctr[0] = 1;
+        if (slot == kPtNoPlace) ctr[0] = 1;
         else into(rows + slot * kAdjCols, p);
     };
     auto flush = [&](const AdjPending &p) {
@@ -197,14 +200,14 @@ static int adj_host_t(const T *grid, const int32_t *values, const uint32_t *dims
                     va = values[at(x0 + j, y, z)];
                     vb = X >= 0 ? values[at((uint32_t) X, (uint32_t) ((int) y + adj_row_dy(r)), (uint32_t) ((int) z + adj_row_dz(r)))] : 0;
                 }
-                adj_merge(pend[l], adj_key(a, b), cls, with_values, va, vb, flush);
+                adj_merge(pend[l], pt_key((uint32_t) a, (uint32_t) b), cls, with_values, va, vb, flush);
             });
         }
         // the chunk's end: one flush for the wavefront if all its pending pairs are one pair
         uint32_t with = 0, first = 64u;
         bool one = true;
         for (uint32_t l = 0; l < 64u; ++l)
-            if (pend[l].key != kAdjEmpty) {
+            if (pend[l].key != kPtEmpty) {
                 if (first == 64u) first = l;
                 one = one && pend[l].key == pend[first].key;
                 ++with;
@@ -212,22 +215,22 @@ static int adj_host_t(const T *grid, const int32_t *values, const uint32_t *dims
         if (with > 1u && one) {
             AdjPending sum = pend[first];
             for (uint32_t l = first + 1u; l < 64u; ++l) {
-                if (pend[l].key == kAdjEmpty) continue;
+                if (pend[l].key == kPtEmpty) continue;
                 for (int c = 0; c < 3; ++c) sum.cnt[c] += pend[l].cnt[c];
                 sum.hi = pend[l].hi > sum.hi ? pend[l].hi : sum.hi, sum.lo = pend[l].lo < sum.lo ? pend[l].lo : sum.lo;
             }
             flush(sum);
         } else {
             for (uint32_t l = 0; l < 64u; ++l)
-                if (pend[l].key != kAdjEmpty) flush(pend[l]);
+                if (pend[l].key != kPtEmpty) flush(pend[l]);
         }
     }
     for (uint32_t slot = 0; slot < kAdjSlots; ++slot) {
-        if (s_key[slot] == kAdjEmpty) continue;
+        if (s_key[slot] == kPtEmpty) continue;
         bool fresh;
-        const uint64_t place = adj_table_slot(keys, log2, s_key[slot], cas64, fresh);
+        const uint64_t place = pt_slot(keys, log2, s_key[slot], cas64, fresh);
         ctr[5] += fresh;
-        if (place == kAdjNoPlace) {
+        if (place == kPtNoPlace) {
             ctr[0] = 1;
             continue;
         }
@@ -253,12 +256,13 @@ extern "C" uint32_t adj_class_of(int dx, int dy, int dz) { return adj_class(dx, 
 @pytest.fixture(scope="module")
 def host_adj(tmp_path_factory):
     """build(defines) -> run(grid, n, conn, zero, values, use_table, log2) -> (pairs, table, outside, counters): the plain C++
-    part of o2v_dev_k24_adjacency.hpp (behind K19's), compiled for the host; the table's list is sorted here as the host side does."""
+    part of o2v_dev_k24_adjacency.hpp (behind K19's and the pair table's), compiled for the host; the table's list is sorted here as the host side does."""
     cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++") or HIPCC
     if not shutil.which(cxx) and not os.path.exists(cxx):
         pytest.skip("no C++ compiler")
     k19, k24 = open(K19).read(), open(K24).read()
     text = (k19[k19.index("constexpr uint32_t kLsI32"):k19.index("#ifndef O2V_LS_HOST")] + k19[k19.index("// ---- runs:"):k19.index("// ---- kernels")] +
+            pair_table_host.plain_part() +
             k24[k24.index("constexpr uint32_t kAdjCols"):k24.index("#ifndef O2V_ADJ_HOST")] + k24[k24.index("// ---- contacts:"):k24.index("// ---- kernels")])
     tmp = tmp_path_factory.mktemp("host_adj")
 
@@ -565,3 +569,22 @@ def test_the_docstrings_and_constants():
     assert "O2V_HIP_ADJ_ZERO = %du" % hip.ADJ_ZERO in header and "O2V_HIP_ADJ_COLUMNS = %d" % hip.ADJ_COLUMNS in header
     for name in ("adjacency_count", "adjacency_write", "adjacency_times", "adjacency_counters", "adjacency_scratch_bytes"):
         assert callable(getattr(hip.DeviceVoxelizer, name))
+
+
+# ---- the code object ---------------------------------------------------------------------------------------------------------------
+
+K24_KERNELS = (["k_adj_pairsILj%dELj%dELb%dELb%dEE" % (f, c, v, vec) for f in (0, 1) for c in (6, 18, 26) for v in (0, 1) for vec in (0, 1)] +
+               ["k_pt_listIxLj5EE", "k_adj_initE"])
+PAIRS_LDS = 512 * 8 + 512 * 5 * 8   # a workgroup's table: 512 keys and their rows of five int64 (the kernel's comment)
+
+
+@pytest.mark.parametrize("kernel", K24_KERNELS)
+def test_k24_kernels_in_the_code_object(device_asm, kernel):  # noqa: F811
+    """From the code object's metadata only: no private segment, and the 24 KiB of LDS of the pass alone."""
+    meta = device_asm[device_asm.index("amdhsa.kernels:"):]
+    entry = [e for e in meta.split("\n  - ") if re.search(r"\.name: +_ZN\S*" + kernel + r"\S*\n", e)]
+    assert len(entry) == 1, kernel + " is not in the gfx950 code object"
+    assert re.search(r"\.private_segment_fixed_size: +0\n", entry[0])
+    assert int(re.search(r"\.wavefront_size: +(\d+)", entry[0]).group(1)) == 64 and int(re.search(r"\.max_flat_workgroup_size: +(\d+)", entry[0]).group(1)) == 256
+    lds = int(re.search(r"\.group_segment_fixed_size: +(\d+)", entry[0]).group(1))
+    assert lds == (PAIRS_LDS if "pairs" in kernel else 0) and PAIRS_LDS == 24576

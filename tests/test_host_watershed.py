@@ -1,7 +1,7 @@
 """Watershed parts without a GPU: the numpy reference (tests/watershed_ref.py) against what follows from the
 definition - persistences against threshold floods with scipy.ndimage.label, nesting, the surviving peak - and against the pinned
-results; the kernel header's plain part - the key, the offsets, the ascent step, the tile-local follow, the pair table and the merge
-- compiled for the host and run tile by tile in a shuffled order against the reference, with the change that must be caught; the
+results; the kernel header's plain part - the key, the offsets, the ascent step, the tile-local follow, the insert into the pair
+table (o2v_dev_pair_table.hpp, through tests/pair_table_host.py) and the merge - compiled for the host and run tile by tile in a shuffled order against the reference, with the change that must be caught; the
 torch layer against a stand-in that computes with the reference; the scratch formula; the K23 kernels' metadata in the gfx950 code
 object."""
 import math
@@ -13,7 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests import bits_host
+from tests import bits_host, pair_table_host
 from tests import watershed_ref as WR
 
 torch = pytest.importorskip("torch")
@@ -125,8 +125,7 @@ HOST_WS = r"""
 #define O2V_WS_FN static inline
 static inline uint32_t ws_load(const uint32_t *p) { return *p; }
 static inline void ws_store(uint32_t *p, uint32_t v) { *p = v; }
-static inline uint64_t ws_load64(const unsigned long long *p) { return *p; }
-static inline uint64_t ws_cas64(unsigned long long *p, uint64_t expect, uint64_t v) { const uint64_t old = *p; if (old == expect) *p = v; return old; }
+static inline uint64_t cas64(unsigned long long *p, uint64_t expect, uint64_t v) { const uint64_t old = *p; if (old == expect) *p = v; return old; }
 static inline void ws_max32(uint32_t *p, uint32_t v) { if (*p < v) *p = v; }
 constexpr uint32_t kCcTileRows = 64u, kCcTileVoxels = 4096u;
 %s
@@ -139,8 +138,8 @@ extern "C" void ws_host_offsets(uint32_t conn, int32_t *out /* [27][4]: on, dx, 
 // keys / values into a table of 2^log2 slots in the given order; out: per insert ws_table_insert's result.  Then the table's content.
 extern "C" void ws_host_table(uint32_t log2, const unsigned long long *k, const uint32_t *v, uint64_t n, int32_t *out, unsigned long long *keys, uint32_t *vals)
 {
-    for (uint64_t s = 0; s < (1ull << log2); ++s) keys[s] = kWsEmpty, vals[s] = 0u;
-    for (uint64_t e = 0; e < n; ++e) out[e] = ws_table_insert(keys, vals, log2, k[e], v[e]);
+    for (uint64_t s = 0; s < (1ull << log2); ++s) keys[s] = kPtEmpty, vals[s] = 0u;
+    for (uint64_t e = 0; e < n; ++e) out[e] = ws_table_insert(keys, vals, log2, k[e], v[e], cas64);
 }
 
 extern "C" uint32_t ws_host_merge(uint32_t n, const uint32_t *index, const int32_t *h, uint64_t m, const unsigned long long *keys, const uint32_t *vals,
@@ -212,9 +211,9 @@ extern "C" int ws_host(const int32_t *H, uint32_t nx, uint32_t ny, uint32_t nz, 
         std::vector<unsigned long long> keys, list_k;
         std::vector<uint32_t> vals, list_v;
         uint32_t log2 = table_log2;
-        if (!log2) for (log2 = kWsTableMinLog2; (1ull << log2) < 16ull * n; ++log2) {}
+        if (!log2) for (log2 = kPtMinLog2; (1ull << log2) < 16ull * n; ++log2) {}
         for (;; ++log2, ++growths) {
-            keys.assign(1ull << log2, kWsEmpty), vals.assign(1ull << log2, 0u);
+            keys.assign(1ull << log2, kPtEmpty), vals.assign(1ull << log2, 0u);
             bool overflow = false;
             seen = distinct = 0;
             for (const uint32_t i : walk) {
@@ -226,7 +225,7 @@ extern "C" int ws_host(const int32_t *H, uint32_t nx, uint32_t ny, uint32_t nz, 
                     if (X >= nx || Y >= ny || Z >= nz) continue;
                     const uint32_t j = ws_neighbour(i, k, sy, sz);
                     if (P[j] == kWsOutside || P[j] == P[i]) continue;
-                    const int got = ws_table_insert(keys.data(), vals.data(), log2, ws_pair_key(P[i], P[j]), (uint32_t) std::min(H[i], H[j]));
+                    const int got = ws_table_insert(keys.data(), vals.data(), log2, pt_key(P[i], P[j]), (uint32_t) std::min(H[i], H[j]), cas64);
                     ++seen, distinct += got > 0, overflow |= got < 0;
                 }
             }
@@ -234,7 +233,7 @@ extern "C" int ws_host(const int32_t *H, uint32_t nx, uint32_t ny, uint32_t nz, 
         }
         bytes = 12ull << log2;
         for (uint64_t s = 0; s < keys.size(); ++s)
-            if (keys[s] != kWsEmpty) list_k.push_back(keys[s]), list_v.push_back(vals[s]);
+            if (keys[s] != kPtEmpty) list_k.push_back(keys[s]), list_v.push_back(vals[s]);
         if (list_k.size() != distinct) return 1;
         survivors = ws_merge(n, index.data(), height.data(), distinct, list_k.data(), list_v.data(), min_depth, lab.data());
     }
@@ -248,7 +247,7 @@ extern "C" int ws_host(const int32_t *H, uint32_t nx, uint32_t ny, uint32_t nz, 
 @pytest.fixture(scope="module")
 def host_ws(tmp_path_factory):
     """build(defines) -> a library with the part of o2v_dev_k23_watershed.hpp between its constants and "kernels", compiled for the
-    host behind the plain part of o2v_dev_bits.hpp."""
+    host behind the plain parts of o2v_dev_bits.hpp and o2v_dev_pair_table.hpp."""
     cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++") or HIPCC
     if not shutil.which(cxx) and not os.path.exists(cxx):
         pytest.skip("no C++ compiler")
@@ -261,7 +260,7 @@ def host_ws(tmp_path_factory):
     def build(defines=()):
         if defines not in built:
             name = "ws_%d" % len(built)
-            (tmp / (name + ".cpp")).write_text(HOST_WS % (bits_host.plain_part() + consts + part))
+            (tmp / (name + ".cpp")).write_text(HOST_WS % (bits_host.plain_part() + pair_table_host.plain_part() + consts + part))
             subprocess.run([cxx, "-x", "c++", "-O2", "-std=c++17", "-shared", "-fPIC"] + ["-D" + d for d in defines] +
                            [str(tmp / (name + ".cpp")), "-o", str(tmp / (name + ".so"))], check=True, capture_output=True)
             L = hip.C.CDLL(str(tmp / (name + ".so")))
@@ -545,7 +544,7 @@ def test_scratch_bytes_formula(dims):
     assert hip.watershed_scratch_bytes((4, 0, 4)) == 0
 
 
-K23_KERNELS = ["k_ws_ascent_tilesE", "k_ws_ascentE", "k_ws_flattenE", "k_ws_peaksE", "k_ws_pairsILb0EE", "k_ws_pairsILb1EE", "k_ws_pairs_listE", "k_ws_labelsE"]
+K23_KERNELS = ["k_ws_ascent_tilesE", "k_ws_ascentE", "k_ws_flattenE", "k_ws_peaksE", "k_ws_pairsILb0EE", "k_ws_pairsILb1EE", "k_pt_listIjLj1EE", "k_ws_labelsE"]
 ASCENT_LDS = 66 * 10 * 10 * 4 + 4096 * 4   # the relief with its halo and a word per voxel of the tile: the kernel's comment, DESIGN.md section 26
 
 

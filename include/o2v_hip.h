@@ -1177,6 +1177,47 @@ int o2v_hip_adjacency_times(const o2v_hip_ctx *ctx, float out_ms[4]);
 int o2v_hip_adjacency_counters(const o2v_hip_ctx *ctx, uint64_t out4[4]);
 uint64_t o2v_hip_adjacency_scratch_bytes(uint64_t pairs);
 
+/* ---- Euler numbers: the cell counts of a label grid -----------------------------------------------------
+ *
+ * What shape class a piece has - handles, through-holes, closed shells, loops - is read off its Euler characteristic, an exact
+ * integer sum over the 2x2x2 neighbourhoods of the grid.  This call counts, per value of a label grid, the cells that the sums
+ * are made of; defined so that a numpy restatement (tests/topology_ref.py) reproduces every bit.
+ *
+ * Input.  A label grid exactly as o2v_hip_label_stats takes it: O2V_HIP_LABELS_I32 or O2V_HIP_LABELS_U8, element strides per
+ * axis in any order (a stride may be 0), dims (nx, ny, nz); the grid is only read.  Rows 0 ... n_labels take part, row 0 like
+ * every other row.  A voxel whose value is negative or above n_labels belongs to no row and is counted in *out_outside.
+ * Everything outside the box belongs to no row.
+ *
+ * Cells.  Take the unit lattice of the box: (nx + 1)(ny + 1)(nz + 1) vertices, with the edges, faces and cubes between them.  A
+ * lattice cell is incident to 8 (vertex), 4 (edge), 2 (face) or 1 (cube) voxel positions; positions outside the box hold no
+ * label.  For label L a cell is closed-in if at least one incident voxel has value L, and inner if every incident position lies
+ * in the box and has value L.
+ *
+ * The table: int64 [n_labels + 1][O2V_HIP_EULER_COLUMNS], contiguous, every element written:
+ *   [0] voxels (n3)                [1] closed-in faces (n2)     [2] closed-in edges (n1)     [3] closed-in vertices (n0)
+ *   [4] inner faces: face-adjacent pairs both L   [5] inner edges: 2x2x1 blocks all L   [6] inner vertices: 2x2x2 blocks all L
+ *
+ * The same as 2x2x2 windows.  The window at lattice vertex v holds the voxels at v + {-1, 0}^3 and owns v, the three edges from v
+ * towards +x, +y and +z, the three faces spanned by two of these directions and the cube at v.  All incident positions of these
+ * eight cells lie inside the window, so a label's 8-bit configuration in the window gives its increment to all seven columns; a
+ * window of one label adds (1, 3, 3, 1, 3, 3, 1).
+ *
+ * What follows from a row: chi_26 = n0 - n1 + n2 - n3 (the set as a union of closed cubes: 26-connectivity), chi_6 = n3 - [4] +
+ * [5] - [6] (the dual complex: 6-connectivity), the intrinsic volumes of the closed model V0 = chi_26, V1 = n1 - 2 n2 + 3 n3,
+ * V2 = n2 - 3 n3 (half the surface area), V3 = n3, and the exposed faces 6 n3 - 2 [4], o2v_hip_label_stats' faces column.
+ *
+ * Limits: dims at most 65 536 per axis and at most 2^31 - 1 voxels (every column then stays below 2^36), n_labels at most
+ * 2^31 - 2 (O2V_HIP_ERR_LIMIT).  O2V_HIP_ERR_BAD_ARGUMENT: a null argument, zero dims, an unknown format, n_labels above 255 with
+ * U8, a table that is not 8-byte aligned or an I32 grid that is not 4-byte aligned, a table that overlaps the grid, a pointer
+ * outside its allocation.  A refusal comes before any launch and leaves the outputs untouched.  The scratch is one counter
+ * (O2V_HIP_ERR_OUT_OF_MEMORY).  Every result is an integer sum: one run equals another bit for bit. */
+enum { O2V_HIP_EULER_COLUMNS = 7 };
+int o2v_hip_euler_stats(o2v_hip_ctx *ctx, const void *labels, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], uint32_t n_labels,
+                        int64_t *table, uint64_t *out_outside);
+/* The device times (ms) of the last o2v_hip_euler_stats call, from events around them: [0] the table's initialisation, [1] the
+ * pass over the grid. */
+int o2v_hip_euler_stats_times(const o2v_hip_ctx *ctx, float out_ms[2]);
+
 int o2v_hip_get_timings(const o2v_hip_ctx *ctx, o2v_hip_timings *out);
 /* Per-kernel device times of the last o2v_hip_voxelize call made with O2V_HIP_FLAG_KERNEL_TIMES (else none): up to
  * max_entries entries are written, *out_count receives how many there are. */

@@ -124,6 +124,7 @@ namespace {
 #include "o2v_dev_pair_table.hpp"      // (the table of id pairs in global memory of K23 and K24)
 #include "o2v_dev_k23_watershed.hpp"   // (behind K12: its grid, index and prefix count)
 #include "o2v_dev_k24_adjacency.hpp"   // (behind K19: its chunk and its reads)
+#include "o2v_dev_k25_euler.hpp"       // (behind K19: its chunk and its reads)
 
 }  // namespace
 
@@ -262,6 +263,7 @@ struct Switches {
     bool ws_no_tiles = env_on("O2V_WS_NO_TILES");              // A/B: no k_ws_ascent_tiles, every voxel's neighbours from global memory and P[i] = the parent
     int ws_table_log2 = env_int("O2V_WS_TABLE_LOG2", 0);       // test hook: the pair table of K23 starts with 2^k slots (if > 0; else sized from the peaks)
     bool adj_no_table = env_on("O2V_ADJ_NO_TABLE");            // A/B: k_adj_pairs without its table in LDS, every flush to global memory
+    bool eu_no_table = env_on("O2V_EU_NO_TABLE");              // A/B: k_euler without its table in LDS, every row to global memory
     int adj_table_log2 = env_int("O2V_ADJ_TABLE_LOG2", 0);     // test hook: the pair table of K24 starts with 2^k slots (if > 0; else sized from the labels)
     bool tiny_buffers = env_on("O2V_TEST_TINY_BUFFERS");       // test hook: minimal first capacities (every grow -> re-run path)
     bool block_list = env_on("O2V_TEST_BLOCK_LIST");           // test hook: the slab's block list for a mesh of any size
@@ -541,6 +543,10 @@ struct o2v_hip_ctx {
     uint64_t adj_counters[4] = {};
     uint64_t adj_pairs = 0;
     bool adj_counted = false;
+    // K25 (o2v_hip_euler_stats): the number of voxels outside [0, n_labels]; the times of the initialisation and of the pass
+    DevArray<unsigned long long> d_eu_ctr;
+    PinnedArray<unsigned long long> h_eu_ctr;
+    StageTimes<2> eu_times;
 
     // results of the last run
     uint64_t n_vox = 0;
@@ -2585,6 +2591,7 @@ int o2v_hip_voxels_device_ptr(o2v_hip_ctx *ctx, const uint32_t **out_ptr, uint64
 #include "o2v_dev_host_k22_thinning.hpp"
 #include "o2v_dev_host_k23_watershed.hpp"
 #include "o2v_dev_host_k24_adjacency.hpp"
+#include "o2v_dev_host_k25_euler.hpp"
 
 extern "C" {
 

@@ -38,7 +38,9 @@ between them is, split_parts does so for a solid and watershed_peaks lists the p
 section 26); label_adjacency says which labels of a label grid touch - per pair the face, edge and corner contacts and the passes of
 a relief between them -, adjacency_neighbours and coordination turn that list into neighbour lists and counts, and skeleton_graph
 makes the nodes, branches and incidences of a skeleton with it (o2v_hip_adjacency_count / o2v_hip_adjacency_write, DESIGN.md
-section 27).
+section 27); euler_stats counts per label the cells of the unit lattice that its voxels close in and hold, euler_numbers and
+intrinsic_volumes make the Euler characteristic and the Minkowski functionals of them, and betti_numbers the components, tunnels
+and cavities of a set (o2v_hip_euler_stats).
 
 torch is imported first on purpose: the library must bind to the HIP runtime torch loaded (a process that loaded the library
 before torch holds two separate runtime copies, and this module refuses to work there).
@@ -1033,6 +1035,10 @@ from .watershed import split_parts, watershed, watershed_peaks  # noqa: E402,F40
 
 from .adjacency import (LabelAdjacency, SkeletonGraph, adjacency_neighbours, coordination, label_adjacency,  # noqa: E402,F401
                         skeleton_graph)   # (the torch layer of o2v_hip_adjacency_count / _write)
+
+# ---- Euler numbers, tunnels and cavities: the cell counts of a label grid ------------------------------------
+
+from .topology import EulerStats, betti_numbers, euler_numbers, euler_stats, intrinsic_volumes  # noqa: E402,F401  (the torch layer of o2v_hip_euler_stats)
 
 
 # ---- dense grids as voxel lists and voxel files --------------------------------------------------------

@@ -47,6 +47,7 @@ STATS_BOX, STATS_SUMS, STATS_MOMENTS, STATS_FACES = 1, 2, 4, 8  # ... the bits o
 STATS_COLUMNS = 17  # ... the int64 columns of a row of its table
 ADJ_ZERO = 16  # o2v_hip_adjacency_count flag: the value 0 is a label like any other (with FLAG_STAGE_TIMES: the counters)
 ADJ_COLUMNS = 5  # ... the int64 columns of a row of its table: faces, edges, corners, pass_high, pass_low
+EULER_COLUMNS = 7  # o2v_hip_euler_stats: the int64 columns of a row of its table: voxels, closed-in faces, edges, vertices, inner faces, edges, vertices
 ERR_BAD_ARGUMENT = 3
 ERR_LIMIT = 5
 ERR_IO = 6  # o2v_hip_gather_save: the file cannot be opened, is of no output type, or stopped taking voxels
@@ -229,6 +230,9 @@ def _bind():
     L.o2v_hip_adjacency_counters.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_adjacency_scratch_bytes.argtypes = [C.c_uint64]
     L.o2v_hip_adjacency_scratch_bytes.restype = C.c_uint64
+    # ctx, labels, format, strides, dims, n_labels, table, out_outside
+    L.o2v_hip_euler_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]
+    L.o2v_hip_euler_stats_times.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_max_slab_layers.argtypes = [C.c_void_p, C.POINTER(_Params), C.POINTER(C.c_uint32)]
     return L
 
@@ -842,6 +846,20 @@ class DeviceVoxelizer:
     def adjacency_scratch_bytes(self, pairs):
         """o2v_hip_adjacency_scratch_bytes: the context scratch of the sorted list of `pairs` pairs."""
         return adjacency_scratch_bytes(pairs)
+
+    def euler_stats(self, labels_ptr, fmt, strides, dims, n_labels, table_ptr):
+        """o2v_hip_euler_stats: per value 0 ... n_labels of the label grid at device address labels_ptr (LABELS_I32 / LABELS_U8;
+        strides in elements, strides and dims per axis x, y, z) a row of EULER_COLUMNS int64 at device address table_ptr
+        ([n_labels + 1, 7], contiguous): its voxels, the closed-in faces, edges and vertices of the unit lattice and the inner
+        ones.  Returns the number of voxels whose value is negative or above n_labels: they are in no row."""
+        outside = C.c_uint64(0)
+        self._check(self._L.o2v_hip_euler_stats(self._ctx, labels_ptr, fmt, _u64x3(strides), _u32x3(dims), n_labels, table_ptr, C.byref(outside)),
+                    "o2v_hip_euler_stats")
+        return int(outside.value)
+
+    def euler_stats_times(self):
+        """o2v_hip_euler_stats_times: the device times (ms) of the last euler_stats call's table initialisation and pass."""
+        return self._stage_times("o2v_hip_euler_stats_times", 2)
 
     def nearest_scratch_bytes(self, dims):
         """o2v_hip_nearest_scratch_bytes: the context scratch a nearest_dense call over dims (x, y, z) needs."""

@@ -1218,6 +1218,69 @@ int o2v_hip_euler_stats(o2v_hip_ctx *ctx, const void *labels, uint32_t format, c
  * pass over the grid. */
 int o2v_hip_euler_stats_times(const o2v_hip_ctx *ctx, float out_ms[2]);
 
+/* ---- Sparse voxel octrees of dense grids ------------------------------------------------------------------
+ *
+ * The set of a dense grid as a tree that can be stored, shipped and queried by coordinate: the format renderers and collision
+ * queries consume, the LOD chain of the grid (level l is its occupancy at 1 / 2^(D - l)), and for solids far smaller than the grid.
+ * Defined so that a numpy restatement (tests/octree_ref.py) reproduces every bit.
+ *
+ * The set and the cube.  The set grid, its three formats (O2V_HIP_GRID_U8, _BITS, _F32_BELOW), strides and `level` are those of
+ * o2v_hip_gather_count; the grid is only read.  origin[3] (global voxel coordinates of the box's low corner) and dims[3] give the
+ * box; every voxel outside it is empty.  The root cube is [0, 2^D)^3 in global coordinates - low corner 0, the global lattice, as
+ * o2v_hip_downsample has it -, so trees of different boxes of one model line up with each other and with the levels of
+ * o2v_hip_downsample.  depth = D, 1 <= D <= 16, origin[a] + dims[a] <= 2^D on every axis; depth = 0 on entry asks for the
+ * smallest such D.  A cell of level l (0 <= l <= D) is an aligned cube of side 2^(D - l); level D is the voxels.  A cell is
+ * non-empty if it holds a solid voxel and full if all 8^(D - l) of its voxels are solid (it then lies wholly in the box).
+ *
+ * Nodes.  A node is a stored cell of level l < D; the root (level 0) is always stored.  Per node, bit o of `valid` (uint8) is set
+ * iff child octant o = dx + 2 dy + 4 dz is non-empty, bit o of `full` (uint8) iff it is full; at level D - 1 the children are
+ * voxels and full == valid.  The stored children of a node of level l < D - 1 are stored = valid, and stored = valid & ~full with
+ * O2V_HIP_OCT_COLLAPSE: a full cell is then a leaf and nothing below it is stored.  Nodes of level D - 1 have no stored children.
+ *
+ * Order.  Nodes are stored level by level, within level l + 1 by (index of the parent, octant): the children of a node are
+ * contiguous, and every level is in Morton order (z the high bit).  first_child[i] (int32): for a node of level < D - 1 the index
+ * of its first stored child, -1 if stored == 0; for a node of level D - 1 the number of solid voxels under all earlier nodes of
+ * level D - 1 - the index of its first voxel in a per-voxel attribute array in Morton order, a voxel's slot being first_child[i] +
+ * popcount(valid & ((1 << o) - 1)).  voxels_listed is the total of these popcounts (voxels inside collapsed cells are not
+ * listed).  coords[i] (int32 [3], optional) is the low corner (x, y, z) of the node's cell.  level_counts[l] is the number of nodes
+ * of level l, 0 from l = D on.
+ *
+ * Descent.  For an int32 point (x, y, z) in global coordinates the result is int32 [4] = (solid, level, node, voxel_index).
+ * Outside the root cube: (0, -1, -1, -1).  Start at node 0, level 0; at node i of level l take o, the octant of the point:
+ * `valid` bit clear: (0, l, i, -1); l = D - 1: (1, l, i, first_child[i] + rank of o in valid); `full` bit set and the tree
+ * collapsed: (1, l, i, -1); otherwise go to child first_child[i] + rank of o in stored.  At most D steps; a child index outside
+ * [0, n_nodes), or a -1 where a child is needed, ends it with (0, -2, -1, -1): no array is read outside its n_nodes entries.
+ *
+ * o2v_hip_octree_build builds the tree into scratch of the context (flags: O2V_HIP_OCT_COLLAPSE, O2V_HIP_FLAG_STAGE_TIMES) and
+ * returns its depth, level counts, node count and listed voxels; o2v_hip_octree_write copies it into the caller's contiguous device
+ * arrays of *out_nodes entries (coords may be null).  o2v_hip_octree_lookup runs the descent per point on the caller's arrays (a
+ * tree from anywhere works; flags say whether it is collapsed); o2v_hip_octree_to_dense writes out(x, y, z) = 1 where the descent
+ * is solid and 0 elsewhere for every voxel of any box, also one that sticks out of the root cube.
+ *
+ * Limits (O2V_HIP_ERR_LIMIT): dims above 65 536 per axis or 2^31 - 1 voxels in all, origin + dims above 65 536 (build) or 2^32
+ * (to_dense), n_nodes or n above 2^31 - 1.  O2V_HIP_ERR_BAD_ARGUMENT: what o2v_hip_gather_count refuses of a grid, depth above
+ * 16 or origin + dims above 2^depth, unknown flag bits, a null argument, n_nodes = 0, arrays that are not 4-byte aligned where they
+ * hold int32, output arrays that overlap each other or the inputs, out strides that map two voxels to one element, a pointer that is
+ * not device memory of the context's device with its whole extent inside its allocation, o2v_hip_octree_write without a build
+ * ("no o2v_hip_octree_build").  A refusal comes before any launch.  A failed scratch allocation is O2V_HIP_ERR_OUT_OF_MEMORY and
+ * leaves the context usable.  Scratch: o2v_hip_octree_scratch_bytes is the most a build of the box takes - 1/8 byte per voxel of
+ * bits, 2 bytes per touched cell of the pyramid (2/7 byte per voxel) and 18 bytes per node with a node per cell; a build sizes its
+ * nodes by the cells that are nodes.  Integers throughout: one run equals another bit for bit. */
+enum { O2V_HIP_OCT_COLLAPSE = 64u, O2V_HIP_OCT_MAX_DEPTH = 16 };
+int o2v_hip_octree_build(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+                         const uint32_t origin[3], uint32_t depth, uint32_t flags, uint32_t *out_depth, uint64_t level_counts[16], uint64_t *out_nodes,
+                         uint64_t *out_voxels_listed);
+int o2v_hip_octree_write(o2v_hip_ctx *ctx, uint8_t *valid, uint8_t *full, int32_t *first_child, int32_t *coords);
+int o2v_hip_octree_lookup(o2v_hip_ctx *ctx, const uint8_t *valid, const uint8_t *full, const int32_t *first_child, uint64_t n_nodes, uint32_t depth,
+                          uint32_t flags, const int32_t *points, uint64_t n, int32_t *out);
+int o2v_hip_octree_to_dense(o2v_hip_ctx *ctx, const uint8_t *valid, const uint8_t *full, const int32_t *first_child, uint64_t n_nodes, uint32_t depth,
+                            uint32_t flags, const uint32_t origin[3], const uint32_t dims[3], uint8_t *out, const uint64_t out_strides[3]);
+/* The device times (ms) of the last build's classify, pyramid and order stages and of the last write, from events around them. */
+int o2v_hip_octree_times(const o2v_hip_ctx *ctx, float out_ms[4]);
+uint64_t o2v_hip_octree_scratch_bytes(const uint32_t dims[3], const uint32_t origin[3], uint32_t depth);
+/* The smallest depth whose root cube holds origin + [0, dims); 0 if a dim is 0 or origin + dims is above 65 536.  Needs no device. */
+uint32_t o2v_hip_octree_depth(const uint32_t origin[3], const uint32_t dims[3]);
+
 int o2v_hip_get_timings(const o2v_hip_ctx *ctx, o2v_hip_timings *out);
 /* Per-kernel device times of the last o2v_hip_voxelize call made with O2V_HIP_FLAG_KERNEL_TIMES (else none): up to
  * max_entries entries are written, *out_count receives how many there are. */

@@ -60,6 +60,9 @@
 //   K24 k_adj_*                o2v_hip_adjacency_count / _write: which labels of a label grid touch - per pair the face, edge and
 //                              corner contacts and the two passes of a values grid, one pass of K19's chunks into a table in LDS
 //                              and the pair table, sorted on the host; outside the pipeline
+//   K26 k_oct_*                o2v_hip_octree_build / _write / _lookup / _to_dense: the sparse voxel octree of a dense grid - a
+//                              pyramid of (valid, full) masks bottom-up, the nodes level by level top-down by scans, the descent
+//                              per point and per 2^3 block; outside the pipeline
 //       k_pt_list              o2v_dev_pair_table.hpp: the table of id pairs in global memory of K23 and K24, its occupied slots as a list
 //   plan k_zhist               o2v_hip_plan_slabs: predicted hits per z layer -> work-balanced slabs for N GPUs
 // With the direct MAX path K1's counters reach the host while K2 runs, and only the stages that have work are enqueued
@@ -116,6 +119,7 @@ namespace {
 #include "o2v_dev_k16_rects.hpp"
 #include "o2v_dev_k15_nearest.hpp"
 #include "o2v_dev_k17_downsample.hpp"
+#include "o2v_dev_k26_octree.hpp"      // (behind K12 and K6: the bit grid, the classify kernel, the block scan)
 #include "o2v_dev_k18_crossings.hpp"
 #include "o2v_dev_k19_label_stats.hpp"
 #include "o2v_dev_k20_geodesic.hpp"
@@ -547,6 +551,23 @@ struct o2v_hip_ctx {
     DevArray<unsigned long long> d_eu_ctr;
     PinnedArray<unsigned long long> h_eu_ctr;
     StageTimes<2> eu_times;
+    // K26 (o2v_hip_octree_build / _write): the bits of the set, the pyramid (an entry valid | full << 8 per touched cell, level by
+    // level), the counters (kOctMeta words) and the block offsets of a level's scan - fixed by the box; the node arrays - grown with
+    // the data; what the last build was made of; the times of classify, pyramid and order (events 0 - 2 and 3 - 4 of oct_times:
+    // the host waits between them) and of the last write
+    DevArray<unsigned long long> d_oct_bits, d_oct_meta, d_oct_boff;
+    DevArray<uint16_t> d_oct_pyr;
+    DevArray<uint8_t> d_oct_valid, d_oct_full;
+    DevArray<int32_t> d_oct_first, d_oct_coords;
+    PinnedArray<unsigned long long> h_oct_meta;
+    StageTimes<4> oct_times;
+    StageTimes<1> oct_write_times;
+    struct OctreeBuild {
+        bool valid = false;
+        GridKey key;
+        uint32_t origin[3] = {}, depth = 0, flags = 0;
+        uint64_t nodes = 0, voxels = 0;
+    } oct;
 
     // results of the last run
     uint64_t n_vox = 0;
@@ -2586,6 +2607,7 @@ int o2v_hip_voxels_device_ptr(o2v_hip_ctx *ctx, const uint32_t **out_ptr, uint64
 #include "o2v_dev_host_k12_components.hpp"
 #include "o2v_dev_host_k13_gather.hpp"
 #include "o2v_dev_host_k17_downsample.hpp"
+#include "o2v_dev_host_k26_octree.hpp"
 #include "o2v_dev_host_k19_label_stats.hpp"
 #include "o2v_dev_host_k21_thickness.hpp"
 #include "o2v_dev_host_k22_thinning.hpp"

@@ -40,7 +40,10 @@ a relief between them -, adjacency_neighbours and coordination turn that list in
 makes the nodes, branches and incidences of a skeleton with it (o2v_hip_adjacency_count / o2v_hip_adjacency_write, DESIGN.md
 section 27); euler_stats counts per label the cells of the unit lattice that its voxels close in and hold, euler_numbers and
 intrinsic_volumes make the Euler characteristic and the Minkowski functionals of them, and betti_numbers the components, tunnels
-and cavities of a set (o2v_hip_euler_stats).
+and cavities of a set (o2v_hip_euler_stats); build_octree turns any of these grids into a sparse voxel octree -
+valid and full masks per node, level by level in Morton order, full cells collapsed -, octree_lookup descends it per point,
+octree_to_dense expands it into any box and octree_level gives one level of it (o2v_hip_octree_build / _write / _lookup /
+_to_dense).
 
 torch is imported first on purpose: the library must bind to the HIP runtime torch loaded (a process that loaded the library
 before torch holds two separate runtime copies, and this module refuses to work there).
@@ -1039,6 +1042,11 @@ from .adjacency import (LabelAdjacency, SkeletonGraph, adjacency_neighbours, coo
 # ---- Euler numbers, tunnels and cavities: the cell counts of a label grid ------------------------------------
 
 from .topology import EulerStats, betti_numbers, euler_numbers, euler_stats, intrinsic_volumes  # noqa: E402,F401  (the torch layer of o2v_hip_euler_stats)
+
+# ---- sparse voxel octrees: build, look up, expand --------------------------------------------------------------
+
+from .octree import (Octree, build_octree, octree_depth, octree_level, octree_lookup,  # noqa: E402,F401
+                     octree_to_dense)   # (the torch layer of o2v_hip_octree_build / _write / _lookup / _to_dense)
 
 
 # ---- dense grids as voxel lists and voxel files --------------------------------------------------------

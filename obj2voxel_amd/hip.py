@@ -47,6 +47,8 @@ STATS_BOX, STATS_SUMS, STATS_MOMENTS, STATS_FACES = 1, 2, 4, 8  # ... the bits o
 STATS_COLUMNS = 17  # ... the int64 columns of a row of its table
 ADJ_ZERO = 16  # o2v_hip_adjacency_count flag: the value 0 is a label like any other (with FLAG_STAGE_TIMES: the counters)
 ADJ_COLUMNS = 5  # ... the int64 columns of a row of its table: faces, edges, corners, pass_high, pass_low
+OCT_COLLAPSE = 64  # o2v_hip_octree_build / _lookup / _to_dense: full cells are leaves
+OCT_MAX_DEPTH = 16  # ... the deepest tree: a root cube of 65 536 voxels along an axis
 EULER_COLUMNS = 7  # o2v_hip_euler_stats: the int64 columns of a row of its table: voxels, closed-in faces, edges, vertices, inner faces, edges, vertices
 ERR_BAD_ARGUMENT = 3
 ERR_LIMIT = 5
@@ -233,6 +235,18 @@ def _bind():
     # ctx, labels, format, strides, dims, n_labels, table, out_outside
     L.o2v_hip_euler_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]
     L.o2v_hip_euler_stats_times.argtypes = [C.c_void_p, C.c_void_p]
+    # ctx, grid, format, strides, dims, level, origin, depth, flags, out_depth, level_counts, out_nodes, out_voxels_listed
+    L.o2v_hip_octree_build.argtypes = _gather + [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.POINTER(C.c_uint64),
+                                                 C.POINTER(C.c_uint64)]
+    L.o2v_hip_octree_write.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    _tree = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32]   # ctx, valid, full, first_child, n_nodes, depth, flags
+    L.o2v_hip_octree_lookup.argtypes = _tree + [C.c_void_p, C.c_uint64, C.c_void_p]
+    L.o2v_hip_octree_to_dense.argtypes = _tree + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.o2v_hip_octree_times.argtypes = [C.c_void_p, C.c_void_p]
+    L.o2v_hip_octree_scratch_bytes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    L.o2v_hip_octree_scratch_bytes.restype = C.c_uint64
+    L.o2v_hip_octree_depth.argtypes = [C.c_void_p, C.c_void_p]
+    L.o2v_hip_octree_depth.restype = C.c_uint32
     L.o2v_hip_max_slab_layers.argtypes = [C.c_void_p, C.POINTER(_Params), C.POINTER(C.c_uint32)]
     return L
 
@@ -346,6 +360,19 @@ def faces_scratch_bytes(dims, color_mode=GATHER_COLOR_CONSTANT, merge=None):
     if merge is None:
         return int(_bind().o2v_hip_faces_scratch_bytes(_u32x3(dims), color_mode))
     return int(_bind().o2v_hip_faces_scratch_bytes_merge(_u32x3(dims), color_mode, merge))
+
+
+def octree_scratch_bytes(dims, origin=(0, 0, 0), depth=0):
+    """o2v_hip_octree_scratch_bytes: the most context scratch an octree_build of the box origin + [0, dims) (x, y, z) takes."""
+    return int(_bind().o2v_hip_octree_scratch_bytes(_u32x3(dims), _u32x3(origin), int(depth)))
+
+
+def octree_depth(origin, dims):
+    """o2v_hip_octree_depth: the smallest depth whose root cube [0, 2^depth)^3 holds origin + [0, dims) (x, y, z); 0 if a dim is 0 or
+    origin + dims is above 65 536.  Needs no device."""
+    if any(not 0 <= int(v) < 2 ** 32 for v in tuple(origin) + tuple(dims)):
+        return 0
+    return int(_bind().o2v_hip_octree_depth(_u32x3(origin), _u32x3(dims)))
 
 
 def device_count():
@@ -860,6 +887,38 @@ class DeviceVoxelizer:
     def euler_stats_times(self):
         """o2v_hip_euler_stats_times: the device times (ms) of the last euler_stats call's table initialisation and pass."""
         return self._stage_times("o2v_hip_euler_stats_times", 2)
+
+    def octree_build(self, grid_ptr, fmt, strides, dims, level, origin, depth=0, flags=OCT_COLLAPSE):
+        """o2v_hip_octree_build: the sparse voxel octree of the set grid at device address grid_ptr (grid arguments as gather_count
+        takes them) whose voxel (0, 0, 0) is `origin` of the global lattice, into the context's scratch.  depth 0: the smallest
+        depth whose root cube [0, 2^depth)^3 holds the box; OCT_COLLAPSE in flags: full cells are leaves.  Returns (depth, level
+        counts [depth], nodes, voxels listed); octree_write copies the arrays out."""
+        d, counts, n, v = C.c_uint32(0), (C.c_uint64 * 16)(), C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.o2v_hip_octree_build(self._ctx, grid_ptr, fmt, _u64x3(strides), _u32x3(dims), float(level), _u32x3(origin), depth, flags,
+                                                 C.byref(d), counts, C.byref(n), C.byref(v)), "o2v_hip_octree_build")
+        return d.value, tuple(int(c) for c in counts[:d.value]), n.value, v.value
+
+    def octree_write(self, valid_ptr, full_ptr, first_child_ptr, coords_ptr=None):
+        """o2v_hip_octree_write: the last octree_build's nodes into the contiguous device arrays valid, full (uint8 [nodes]),
+        first_child (int32 [nodes]) and, unless None, coords (int32 [nodes, 3])."""
+        self._check(self._L.o2v_hip_octree_write(self._ctx, valid_ptr, full_ptr, first_child_ptr, coords_ptr), "o2v_hip_octree_write")
+
+    def octree_lookup(self, valid_ptr, full_ptr, first_child_ptr, n_nodes, depth, flags, points_ptr, n, out_ptr):
+        """o2v_hip_octree_lookup: the descent through the tree in the caller's device arrays for n int32 points (x, y, z) in global
+        coordinates; out int32 [n, 4] = (solid, level, node, voxel_index)."""
+        self._check(self._L.o2v_hip_octree_lookup(self._ctx, valid_ptr, full_ptr, first_child_ptr, n_nodes, depth, flags, points_ptr, n, out_ptr),
+                    "o2v_hip_octree_lookup")
+
+    def octree_to_dense(self, valid_ptr, full_ptr, first_child_ptr, n_nodes, depth, flags, origin, dims, out_ptr, out_strides):
+        """o2v_hip_octree_to_dense: 1 where the tree is solid and 0 elsewhere into the uint8 grid at out_ptr, the box origin + [0,
+        dims) of the global lattice, which may stick out of the root cube."""
+        self._check(self._L.o2v_hip_octree_to_dense(self._ctx, valid_ptr, full_ptr, first_child_ptr, n_nodes, depth, flags, _u32x3(origin), _u32x3(dims),
+                                                    out_ptr, _u64x3(out_strides)), "o2v_hip_octree_to_dense")
+
+    def octree_times(self):
+        """o2v_hip_octree_times: the device times (ms) of the last octree_build's classify, pyramid and order stages and of the last
+        octree_write."""
+        return self._stage_times("o2v_hip_octree_times", 4)
 
     def nearest_scratch_bytes(self, dims):
         """o2v_hip_nearest_scratch_bytes: the context scratch a nearest_dense call over dims (x, y, z) needs."""

@@ -1281,6 +1281,62 @@ uint64_t o2v_hip_octree_scratch_bytes(const uint32_t dims[3], const uint32_t ori
 /* The smallest depth whose root cube holds origin + [0, dims); 0 if a dim is 0 or origin + dims is above 65 536.  Needs no device. */
 uint32_t o2v_hip_octree_depth(const uint32_t origin[3], const uint32_t dims[3]);
 
+/* ---- Sky visibility and ambient occlusion of dense grids --------------------------------------------------
+ *
+ * Per target voxel, in how many of D integer directions a ray from its centre gets out: the quantity ambient occlusion is baked
+ * from, and which tells what a spray, a tool or a sun direction reaches.  Defined so that a numpy restatement
+ * (tests/openness_ref.py) reproduces every bit; integers only, one run equals another bit for bit.
+ *
+ * The set grid, its three formats (O2V_HIP_RAY_GRID_U8, _BITS, _F32_BELOW), strides and `level` are those of
+ * o2v_hip_raycast_build; the grid is only read, the box is [0, dims).  directions: D rows of int32 (dx, dy, dz) in host memory,
+ * none all zero, |d_a| <= 127, 1 <= D <= 254.  max_distance2: uint32, 0 means unlimited.
+ *
+ * The walk.  For the target voxel c0 and the direction d let s_a = sgn d_a, m_a = |d_a| and k_a the crossings made so far on axis
+ * a (0 at the start).  The next event of an axis with m_a != 0 is T_a = (2 k_a + 1) / (2 m_a): the ray c0 + 1/2 + t d meets the
+ * next lattice plane of axis a there.  Events are compared by cross-multiplication in integers.  A step takes the least event and
+ * crosses EVERY axis whose event equals it, together (k_a += 1 for each): a ray through a lattice edge or corner does not enter
+ * the cells beside it, a voxel blocks a ray only if the ray passes through its open interior.  After a step the cell is
+ * c0 + s * k, and the ray is, in this order,
+ *   open     if the cell is outside the box (the box is convex: the ray never returns),
+ *   open     if max_distance2 != 0 and k_x^2 + k_y^2 + k_z^2 > max_distance2 (the sum grows with every step),
+ *   blocked  if the cell is solid;
+ * otherwise the next step follows.  The start cell is never tested.  With dims <= 65 536 and m <= 127 every product
+ * (2 k + 1) * m is below 2^25: int32 is enough everywhere.  The rule for ties makes the result commute with the 48 symmetries of
+ * the lattice applied to the grid and the direction set together (the lowest-axis-first rule of o2v_hip_raycast does not: with it
+ * the centre of a flat roof sees 1 of the 26 neighbour directions, not 9).
+ *
+ * Targets (target_mode): O2V_HIP_OPEN_SURFACE - solid voxels with at least one of the six neighbours empty, outside the box
+ * counting as empty; _SOLID - all solid voxels; _EMPTY - all empty voxels; _GRID - the voxels where target_grid, a uint8 grid of
+ * the same dims at target_strides (any strides), is nonzero.  target_grid and target_strides are read with _GRID only.
+ *
+ * Results.  dst (uint8, any strides that keep the voxels apart): the number of open directions of every target, 255 for every
+ * voxel that is no target.  mask (int64, optional, D <= 64): bit i set iff direction i is open, 0 for voxels that are no targets.
+ * *out_targets: the number of targets.  A sun shadow is one direction and dst == 0.
+ *
+ * The call builds the three mask levels of o2v_hip_raycast_build into scratch of its own: a snapshot of o2v_hip_raycast_build
+ * and o2v_hip_raycast_generation are untouched by it.  flags: O2V_HIP_FLAG_STAGE_TIMES or 0.  O2V_OPEN_NO_SKIP=1 in the
+ * environment makes the kernel walk every fine cell (an A/B switch: the results are the same).
+ *
+ * O2V_HIP_ERR_BAD_ARGUMENT: what o2v_hip_raycast_build refuses of a grid, a null argument (mask may be null; target_grid and
+ * target_strides with _GRID only), an unknown target mode or flag bit, D = 0, a zero direction, a component above 127 in
+ * magnitude, a mask with D > 64 or not 8-byte aligned, dst or mask strides that map two voxels to one element, dst or mask
+ * overlapping each other, the grid or the target grid, a pointer that is not device memory of the context's device with its whole
+ * extent inside its allocation.  O2V_HIP_ERR_LIMIT: D above 254, a dim above 65 536, more than 2^31 - 1 voxels.  A refusal comes
+ * before any launch and leaves the outputs untouched.  A failed scratch allocation is O2V_HIP_ERR_OUT_OF_MEMORY and leaves the
+ * context usable and the outputs untouched.  Scratch: o2v_hip_openness_scratch_bytes is the most a call over dims takes - the
+ * masks of o2v_hip_raycast_scratch_bytes and 4 bytes per voxel for the list of targets if every voxel is one; a call sizes its
+ * list by the targets it counted. */
+enum { O2V_HIP_OPEN_SURFACE = 0, O2V_HIP_OPEN_SOLID = 1, O2V_HIP_OPEN_EMPTY = 2, O2V_HIP_OPEN_GRID = 3 };
+enum { O2V_HIP_OPEN_MAX_DIRECTIONS = 254, O2V_HIP_OPEN_MAX_COMPONENT = 127 };
+int o2v_hip_openness(o2v_hip_ctx *ctx, const void *grid, uint32_t format, const uint64_t strides[3], const uint32_t dims[3], float level,
+                     const int32_t *directions, uint32_t n_directions, uint32_t target_mode, const uint8_t *target_grid,
+                     const uint64_t target_strides[3], uint32_t max_distance2, uint32_t flags, uint8_t *dst, const uint64_t dst_strides[3],
+                     int64_t *mask, const uint64_t mask_strides[3], uint64_t *out_targets);
+/* The device times (ms) of the last call's stages: build (the masks), targets (counted, the host's wait for their number, listed)
+ * and walk, from events around them. */
+int o2v_hip_openness_times(const o2v_hip_ctx *ctx, float out_ms[3]);
+uint64_t o2v_hip_openness_scratch_bytes(const uint32_t dims[3]);
+
 int o2v_hip_get_timings(const o2v_hip_ctx *ctx, o2v_hip_timings *out);
 /* Per-kernel device times of the last o2v_hip_voxelize call made with O2V_HIP_FLAG_KERNEL_TIMES (else none): up to
  * max_entries entries are written, *out_count receives how many there are. */

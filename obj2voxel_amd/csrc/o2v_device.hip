@@ -63,6 +63,9 @@
 //   K26 k_oct_*                o2v_hip_octree_build / _write / _lookup / _to_dense: the sparse voxel octree of a dense grid - a
 //                              pyramid of (valid, full) masks bottom-up, the nodes level by level top-down by scans, the descent
 //                              per point and per 2^3 block; outside the pipeline
+//   K27 k_open_*               o2v_hip_openness: in how many of D integer directions a voxel sees out of the grid - K11's masks built
+//                              into scratch of its own, the targets compacted into a list, a lane per target walking one direction
+//                              at a time in 32-bit integers, empty 4^3 / 16^3 / 64^3 blocks left in one exact skip; outside the pipeline
 //       k_pt_list              o2v_dev_pair_table.hpp: the table of id pairs in global memory of K23 and K24, its occupied slots as a list
 //   plan k_zhist               o2v_hip_plan_slabs: predicted hits per z layer -> work-balanced slabs for N GPUs
 // With the direct MAX path K1's counters reach the host while K2 runs, and only the stages that have work are enqueued
@@ -120,6 +123,7 @@ namespace {
 #include "o2v_dev_k15_nearest.hpp"
 #include "o2v_dev_k17_downsample.hpp"
 #include "o2v_dev_k26_octree.hpp"      // (behind K12 and K6: the bit grid, the classify kernel, the block scan)
+#include "o2v_dev_k27_openness.hpp"    // (behind K11: it walks the masks that k_ray_build makes)
 #include "o2v_dev_k18_crossings.hpp"
 #include "o2v_dev_k19_label_stats.hpp"
 #include "o2v_dev_k20_geodesic.hpp"
@@ -259,6 +263,7 @@ struct Switches {
     bool all_launches = env_on("O2V_ALL_LAUNCHES");            // A/B: no launch left out on the strength of the upload's hints
     bool no_slabs = env_on("O2V_NO_SLABS");                    // A/B: no new hit slabs, every hit pooled
     bool ray_no_skip = env_on("O2V_RAY_NO_SKIP");              // A/B: k_ray_cast walks every fine cell, no empty block is skipped
+    bool open_no_skip = env_on("O2V_OPEN_NO_SKIP");            // A/B: k_open_walk walks every fine cell, no empty block is skipped
     bool cc_no_tiles = env_on("O2V_CC_NO_TILES");              // A/B: no k_cc_tiles, every adjacent pair is united in global memory
     bool cross_no_tile = env_on("O2V_CROSS_NO_TILE");          // A/B: no k_cross_prefix_tile, a lane per line stores along the ray
     bool ls_no_table = env_on("O2V_LS_NO_TABLE");              // A/B: k_label_stats without its table in LDS, every run to global memory
@@ -568,6 +573,14 @@ struct o2v_hip_ctx {
         uint32_t origin[3] = {}, depth = 0, flags = 0;
         uint64_t nodes = 0, voxels = 0;
     } oct;
+    // K27 (o2v_hip_openness): the three levels of masks of its own (a RayCaster's snapshot is not touched), the counters (targets
+    // counted, targets listed), the direction table (nine words per direction) on both sides, the list of the targets' linear
+    // indices - grown with the data; the times of build, targets and walk
+    DevArray<unsigned long long> d_open_masks, d_open_ctr;
+    PinnedArray<unsigned long long> h_open_ctr;
+    DevArray<uint32_t> d_open_dirs, d_open_list;
+    PinnedArray<uint32_t> h_open_dirs;
+    StageTimes<3> open_times;
 
     // results of the last run
     uint64_t n_vox = 0;
@@ -2608,6 +2621,7 @@ int o2v_hip_voxels_device_ptr(o2v_hip_ctx *ctx, const uint32_t **out_ptr, uint64
 #include "o2v_dev_host_k13_gather.hpp"
 #include "o2v_dev_host_k17_downsample.hpp"
 #include "o2v_dev_host_k26_octree.hpp"
+#include "o2v_dev_host_k27_openness.hpp"
 #include "o2v_dev_host_k19_label_stats.hpp"
 #include "o2v_dev_host_k21_thickness.hpp"
 #include "o2v_dev_host_k22_thinning.hpp"

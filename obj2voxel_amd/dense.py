@@ -43,7 +43,8 @@ intrinsic_volumes make the Euler characteristic and the Minkowski functionals of
 and cavities of a set (o2v_hip_euler_stats); build_octree turns any of these grids into a sparse voxel octree -
 valid and full masks per node, level by level in Morton order, full cells collapsed -, octree_lookup descends it per point,
 octree_to_dense expands it into any box and octree_level gives one level of it (o2v_hip_octree_build / _write / _lookup /
-_to_dense).
+_to_dense); openness counts per voxel the directions of a direction_set in which one sees out of the grid -
+sky visibility, sun shadows -, and shade_colors bakes it into colours as ambient occlusion (o2v_hip_openness).
 
 torch is imported first on purpose: the library must bind to the HIP runtime torch loaded (a process that loaded the library
 before torch holds two separate runtime copies, and this module refuses to work there).
@@ -1047,6 +1048,10 @@ from .topology import EulerStats, betti_numbers, euler_numbers, euler_stats, int
 
 from .octree import (Octree, build_octree, octree_depth, octree_level, octree_lookup,  # noqa: E402,F401
                      octree_to_dense)   # (the torch layer of o2v_hip_octree_build / _write / _lookup / _to_dense)
+
+# ---- sky visibility and ambient occlusion -------------------------------------------------------------------
+
+from .visibility import direction_set, openness, shade_colors  # noqa: E402,F401  (the torch layer of o2v_hip_openness)
 
 
 # ---- dense grids as voxel lists and voxel files --------------------------------------------------------

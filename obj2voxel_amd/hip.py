@@ -49,6 +49,9 @@ ADJ_ZERO = 16  # o2v_hip_adjacency_count flag: the value 0 is a label like any o
 ADJ_COLUMNS = 5  # ... the int64 columns of a row of its table: faces, edges, corners, pass_high, pass_low
 OCT_COLLAPSE = 64  # o2v_hip_octree_build / _lookup / _to_dense: full cells are leaves
 OCT_MAX_DEPTH = 16  # ... the deepest tree: a root cube of 65 536 voxels along an axis
+OPEN_SURFACE, OPEN_SOLID, OPEN_EMPTY, OPEN_GRID = 0, 1, 2, 3  # o2v_hip_openness: the target modes
+OPEN_MAX_DIRECTIONS = 254  # ... the most directions of a call (a count is one byte, 255 marks the voxels that are no targets)
+OPEN_MAX_COMPONENT = 127  # ... the largest magnitude of a direction's component
 EULER_COLUMNS = 7  # o2v_hip_euler_stats: the int64 columns of a row of its table: voxels, closed-in faces, edges, vertices, inner faces, edges, vertices
 ERR_BAD_ARGUMENT = 3
 ERR_LIMIT = 5
@@ -247,6 +250,13 @@ def _bind():
     L.o2v_hip_octree_scratch_bytes.restype = C.c_uint64
     L.o2v_hip_octree_depth.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_octree_depth.restype = C.c_uint32
+    # ctx, grid, format, strides, dims, level, directions, n_directions, target_mode, target_grid, target_strides, max_distance2, flags,
+    # dst, dst_strides, mask, mask_strides, out_targets
+    L.o2v_hip_openness.argtypes = _gather + [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    L.o2v_hip_openness_times.argtypes = [C.c_void_p, C.c_void_p]
+    L.o2v_hip_openness_scratch_bytes.argtypes = [C.c_void_p]
+    L.o2v_hip_openness_scratch_bytes.restype = C.c_uint64
     L.o2v_hip_max_slab_layers.argtypes = [C.c_void_p, C.POINTER(_Params), C.POINTER(C.c_uint32)]
     return L
 
@@ -365,6 +375,11 @@ def faces_scratch_bytes(dims, color_mode=GATHER_COLOR_CONSTANT, merge=None):
 def octree_scratch_bytes(dims, origin=(0, 0, 0), depth=0):
     """o2v_hip_octree_scratch_bytes: the most context scratch an octree_build of the box origin + [0, dims) (x, y, z) takes."""
     return int(_bind().o2v_hip_octree_scratch_bytes(_u32x3(dims), _u32x3(origin), int(depth)))
+
+
+def openness_scratch_bytes(dims):
+    """o2v_hip_openness_scratch_bytes: the most context scratch an openness call over dims (x, y, z) takes."""
+    return int(_bind().o2v_hip_openness_scratch_bytes(_u32x3(dims)))
 
 
 def octree_depth(origin, dims):
@@ -919,6 +934,25 @@ class DeviceVoxelizer:
         """o2v_hip_octree_times: the device times (ms) of the last octree_build's classify, pyramid and order stages and of the last
         octree_write."""
         return self._stage_times("o2v_hip_octree_times", 4)
+
+    def openness(self, grid_ptr, fmt, strides, dims, level, directions, target_mode, target_ptr, target_strides, max_distance2, dst_ptr, dst_strides,
+                 mask_ptr=None, mask_strides=None, flags=0):
+        """o2v_hip_openness: per target voxel of the set grid at device address grid_ptr (grid arguments as gather_count takes them)
+        the number of the directions - rows (dx, dy, dz) of ints - along which a ray from its centre leaves the box or passes
+        max_distance2 (0: unlimited) before it enters a solid voxel, into the uint8 grid at dst_ptr (255: no target), and the
+        directions as bits into the int64 grid at mask_ptr unless None.  target_mode: OPEN_SURFACE, OPEN_SOLID, OPEN_EMPTY, or
+        OPEN_GRID with the uint8 grid at target_ptr.  Returns the number of targets."""
+        rows = [tuple(int(v) for v in d) for d in directions]
+        flat = (C.c_int32 * (3 * len(rows)))(*[v for d in rows for v in d])
+        n = C.c_uint64(0)
+        self._check(self._L.o2v_hip_openness(self._ctx, grid_ptr, fmt, _u64x3(strides), _u32x3(dims), float(level), flat, len(rows), target_mode, target_ptr,
+                                             None if target_strides is None else _u64x3(target_strides), max_distance2, flags, dst_ptr, _u64x3(dst_strides),
+                                             mask_ptr, None if mask_strides is None else _u64x3(mask_strides), C.byref(n)), "o2v_hip_openness")
+        return n.value
+
+    def openness_times(self):
+        """o2v_hip_openness_times: the device times (ms) of the last openness call's build, targets and walk stages."""
+        return self._stage_times("o2v_hip_openness_times", 3)
 
     def nearest_scratch_bytes(self, dims):
         """o2v_hip_nearest_scratch_bytes: the context scratch a nearest_dense call over dims (x, y, z) needs."""

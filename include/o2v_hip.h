@@ -1118,6 +1118,74 @@ int o2v_hip_watershed_times(const o2v_hip_ctx *ctx, float out_ms[5]);
  * table's bytes at the end, the survivors. */
 int o2v_hip_watershed_counters(const o2v_hip_ctx *ctx, uint64_t out6[6]);
 
+/* ---- seeded watershed: markers grown through a relief ------------------------------------------------------
+ *
+ * o2v_hip_watershed_dense finds its own peaks; here the caller says where the parts are.  The hierarchical-queue flood of Meyer,
+ * with its accidental FIFO order replaced by a distance and a smallest-label rule, so that the result is a unique fixed point.
+ *
+ * The definition.
+ *   Relief.  H is an int32 grid indexed [z, y, x] with any strides.  The set is S = { v : H[v] > 0 }.  Voxels outside the box are
+ *   not in S.  This is o2v_hip_watershed_dense's contract and orientation: high is the middle of a part, and the flood runs
+ *   downhill from the markers.
+ *   Markers.  M is an int32 grid of the same dims with any strides.  A voxel v in S with M[v] > 0 is a seed of label M[v], which
+ *   may be 1 .. 2^31 - 1.  Markers outside S and values <= 0 are ignored.
+ *   Steps.  weights[3] are o2v_hip_geodesic_dense's.  Each is 0 .. 65 535, not all are 0, and 0 means "no such step".  A diagonal
+ *   step needs only its two end voxels in S.
+ *   Key.  Every v in S gets a key K(v) = (Q, T).  Q is the level and T the ticks.  (Q, T) is better than (Q', T') if Q > Q', or if
+ *   Q == Q' and T < T'.
+ *     A seed has K(s) = (H[s], 0).
+ *     A step from u to v with weight w turns (Q, T) into (H[v], 0) if H[v] < Q.  The flood descends onto v and the clock restarts.
+ *     Otherwise it turns it into (Q, min(T + w, 2^31 - 2)).  The flood spreads on a plateau, or spills uphill at the level of the
+ *     pass it came over, and the clock runs and saturates.
+ *   This step is monotone in the key, so K is the best fixed point of "seed key, or the best step from a neighbour", and it is
+ *   unique.  Label comparison must not be part of this relaxation.  With the label in the key the step is no longer monotone and
+ *   the result depends on the schedule.
+ *   The three phases.  K decomposes into three 32-bit fixed points, each final before the next is computed.
+ *   1. Level.  Q(v) = max(seed ? H[v] : 0, max_u min(Q(u), H[v])), starting from 0 and only rising.  This is the max-min
+ *      (bottleneck) height over all paths from a seed.  Q(v) >= t exactly if the component of {H >= t} that holds v (connectivity
+ *      by the weights) holds a seed s with H[s] >= t.  Q = 0 means not reached.
+ *   2. Ticks.  T(v) = 0 if v is a seed or has a neighbour u with Q(u) > H[v].  Otherwise T(v) = min over neighbours u with Q(u) ==
+ *      Q(v) of min(T(u) + w, 2^31 - 2), only falling.
+ *   3. Label.  A seed keeps M[v].  Every other reached v takes the smallest L(u) over its tight neighbours u, those whose step
+ *      gives exactly K(v).  A neighbour is tight if Q(u) > H[v], which implies T(v) == 0.  It is also tight if Q(u) == Q(v) and
+ *      min(T(u) + w, cap) == T(v).  Labels only fall, and every reached voxel has a tight path to a seed.
+ *   Outputs.  labels is int32: L, or 0 outside S and where not reached.  level (optional) is int32: Q, or 0.  ticks (optional) is
+ *   int32: T, or -1 outside S and where not reached.  *reached is the number of voxels with Q > 0.
+ * On a constant relief ticks is o2v_hip_geodesic_dense's distance to the nearest seed, and labels is the geodesic Voronoi diagram,
+ * with the smallest label on a tie.
+ *
+ * level and ticks may be null; their strides are then not read.  The outputs take any strides that map no two voxels to one
+ * element; every voxel of the box is written.  relief and markers are only read.  flags: O2V_HIP_FLAG_STAGE_TIMES
+ * (o2v_hip_grow_counters counts).  The result is integers, the same bits on every run and schedule.
+ *
+ * Refused before any launch, the outputs untouched.  O2V_HIP_ERR_BAD_ARGUMENT: a null relief, markers, labels, reached, weights
+ * or strides of a grid that is given, zero dims, a weight above 65 535 or all weights 0, unknown flag bits, pointers that are not
+ * 4-byte aligned, that are not device memory of the context's device or that reach outside their allocation, output strides that
+ * map two voxels to one element, any overlap between an output and an input or between two outputs.  O2V_HIP_ERR_LIMIT: a dim
+ * above 65 536, or nx * ny * nz above 2^31 - 1.  A failed allocation returns O2V_HIP_ERR_OUT_OF_MEMORY and the context stays usable.
+ * The call runs on the context's stream and returns when the writes are done (the caller must have finished writing relief and
+ * markers).  The host reads 4 bytes between the rounds of a phase.  O2V_GROW_NO_TILES=1 in the environment (A/B): every phase by
+ * whole-grid sweeps instead of tiles in LDS; same results.
+ *
+ * Scratch of the context, grown on demand.  Q, T and L live in level, ticks and labels themselves where those are given and
+ * contiguous (linear index (z * ny + y) * nx + x is the element).  o2v_hip_grow_scratch_bytes(dims, which), `which` the OR of
+ * O2V_HIP_GROW_SCRATCH_LABELS / _LEVEL / _TICKS for those of the three that are not: 4 * nx * ny * nz (the neighbour masks)  +  4 *
+ * nx * ny * nz for each bit of `which`  +  16 * tiles (per tile two flag words and two list places; tiles of 64 x 8 x 8 voxels)  +
+ * 128.  (0 for zero dims or unknown bits.) */
+enum { O2V_HIP_GROW_MAX_TICKS = 0x7ffffffeu };
+enum { O2V_HIP_GROW_SCRATCH_LABELS = 1u, O2V_HIP_GROW_SCRATCH_LEVEL = 2u, O2V_HIP_GROW_SCRATCH_TICKS = 4u };
+int o2v_hip_grow_dense(o2v_hip_ctx *ctx, const int32_t *relief, const uint64_t relief_strides[3], const int32_t *markers,
+                       const uint64_t marker_strides[3], const uint32_t dims[3], const uint32_t weights[3], uint32_t flags,
+                       int32_t *labels, const uint64_t labels_strides[3], int32_t *level, const uint64_t level_strides[3],
+                       int32_t *ticks, const uint64_t ticks_strides[3], uint64_t *reached);
+uint64_t o2v_hip_grow_scratch_bytes(const uint32_t dims[3], uint32_t which);
+/* The device times (ms) of the last o2v_hip_grow_dense call: init, level rounds, sources, tick rounds, tight, label rounds (the
+ * host's reads between the rounds included), write. */
+int o2v_hip_grow_times(const o2v_hip_ctx *ctx, float out_ms[7]);
+/* Of the last o2v_hip_grow_dense call made with O2V_HIP_FLAG_STAGE_TIMES (else zeros), for the level, the ticks and the labels
+ * in turn: the rounds (launches of the tile kernel, or whole-grid sweeps), the tile visits, the in-tile sweeps. */
+int o2v_hip_grow_counters(const o2v_hip_ctx *ctx, uint64_t out9[9]);
+
 /* ---- which labels touch: the region adjacency of a label grid ---------------------------------------------
  *
  * The grid.  labels, format (O2V_HIP_LABELS_I32 / O2V_HIP_LABELS_U8), strides (elements per axis x, y, z; any order, a stride may

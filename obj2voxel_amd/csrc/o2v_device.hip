@@ -66,6 +66,9 @@
 //   K27 k_open_*               o2v_hip_openness: in how many of D integer directions a voxel sees out of the grid - K11's masks built
 //                              into scratch of its own, the targets compacted into a list, a lane per target walking one direction
 //                              at a time in 32-bit integers, empty 4^3 / 16^3 / 64^3 blocks left in one exact skip; outside the pipeline
+//   K28 k_grow_*               o2v_hip_grow_dense: seeded watershed - markers grown through an int32 relief by three fixed points (level,
+//                              ticks, label), each K20's relaxation tile by tile in LDS, round by round, with a streaming pass that
+//                              writes the next one's neighbour masks in between; outside the pipeline
 //       k_pt_list              o2v_dev_pair_table.hpp: the table of id pairs in global memory of K23 and K24, its occupied slots as a list
 //   plan k_zhist               o2v_hip_plan_slabs: predicted hits per z layer -> work-balanced slabs for N GPUs
 // With the direct MAX path K1's counters reach the host while K2 runs, and only the stages that have work are enqueued
@@ -133,6 +136,7 @@ namespace {
 #include "o2v_dev_k23_watershed.hpp"   // (behind K12: its grid, index and prefix count)
 #include "o2v_dev_k24_adjacency.hpp"   // (behind K19: its chunk and its reads)
 #include "o2v_dev_k25_euler.hpp"       // (behind K19: its chunk and its reads)
+#include "o2v_dev_k28_grow.hpp"        // (behind K20 and the pair table: the offsets, see masks and tile flags; I32View)
 
 }  // namespace
 
@@ -268,6 +272,7 @@ struct Switches {
     bool cross_no_tile = env_on("O2V_CROSS_NO_TILE");          // A/B: no k_cross_prefix_tile, a lane per line stores along the ray
     bool ls_no_table = env_on("O2V_LS_NO_TABLE");              // A/B: k_label_stats without its table in LDS, every run to global memory
     bool geo_no_tiles = env_on("O2V_GEO_NO_TILES");            // A/B: no k_geo_tiles, whole-grid sweeps with atomic mins in global memory
+    bool grow_no_tiles = env_on("O2V_GROW_NO_TILES");          // A/B: no k_grow_tiles, every phase by whole-grid sweeps with the neighbours from global memory
     bool thin_no_tiles = env_on("O2V_THIN_NO_TILES");          // A/B: no k_thin_substep, every sub-step a whole-grid sweep with the masks from global memory
     bool ws_no_tiles = env_on("O2V_WS_NO_TILES");              // A/B: no k_ws_ascent_tiles, every voxel's neighbours from global memory and P[i] = the parent
     int ws_table_log2 = env_int("O2V_WS_TABLE_LOG2", 0);       // test hook: the pair table of K23 starts with 2^k slots (if > 0; else sized from the peaks)
@@ -541,6 +546,15 @@ struct o2v_hip_ctx {
     PinnedArray<int32_t> h_ws_lab;
     StageTimes<5> ws_times;
     uint64_t ws_counters[6] = {};
+    // K28 (o2v_hip_grow_dense): the neighbour masks (4 bytes a voxel); Q, T and L where they cannot live in the caller's level,
+    // ticks and labels; per tile its flag words of two rounds and its places in the two rounds' lists ([4][tiles]); [0 .. 2] the
+    // in-tile sweeps per phase, [3] reached, then as uint32 the two lists' lengths and the changed word; grown on demand; the
+    // times of the seven stages and the nine counters of the last call
+    DevArray<uint32_t> d_grow_mask, d_grow_q, d_grow_t, d_grow_l, d_grow_tiles;
+    DevArray<unsigned long long> d_grow_ctr;
+    PinnedArray<unsigned long long> h_grow_ctr;
+    StageTimes<7> grow_times;
+    uint64_t grow_counters[9] = {};
     // K24 (o2v_hip_adjacency_count / _write): the pair table's keys and rows ([slots], [slots][5]); [0] overflow, [1] voxels outside,
     // [2] flushes into LDS, [3] flushes to global memory, [4] listed pairs, [5] slots taken; the list - keys [m] and rows [m][5] as
     // the table gives them, then pairs [m][2] and rows sorted by key - on the device and page-locked (both orders); grown with the
@@ -2628,6 +2642,7 @@ int o2v_hip_voxels_device_ptr(o2v_hip_ctx *ctx, const uint32_t **out_ptr, uint64
 #include "o2v_dev_host_k23_watershed.hpp"
 #include "o2v_dev_host_k24_adjacency.hpp"
 #include "o2v_dev_host_k25_euler.hpp"
+#include "o2v_dev_host_k28_grow.hpp"
 
 extern "C" {
 

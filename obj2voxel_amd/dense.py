@@ -1034,6 +1034,7 @@ from .skeleton import skeleton_nodes, skeletonize  # noqa: E402,F401  (the torch
 # ---- parts: watershed basins of a relief, merged by persistence ---------------------------------------------
 
 from .watershed import split_parts, watershed, watershed_peaks  # noqa: E402,F401  (the torch layer of o2v_hip_watershed_dense)
+from .grow import grow_labels, markers_from_seeds, seeded_watershed  # noqa: E402,F401  (the torch layer of o2v_hip_grow_dense)
 
 # ---- which labels touch: the region adjacency of a label grid ------------------------------------------------
 

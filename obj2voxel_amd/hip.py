@@ -39,6 +39,8 @@ AXIS_X, AXIS_Y, AXIS_Z = 1, 2, 4  # o2v_hip_crossings_dense: the bits of `axes`
 LABELS_I32, LABELS_U8 = 0, 1  # o2v_hip_label_stats formats
 GEO_MAX_WEIGHT, GEO_MAX_DISTANCE = 65535, 2 ** 31 - 2  # o2v_hip_geodesic_dense: the largest weight, the largest (and default) max_distance
 GEO_SCRATCH_CONTIGUOUS, GEO_SCRATCH_STRIDED = 0, 1  # o2v_hip_geodesic_scratch_bytes
+GROW_MAX_TICKS = 2 ** 31 - 2  # o2v_hip_grow_dense: where the ticks saturate
+GROW_SCRATCH_LABELS, GROW_SCRATCH_LEVEL, GROW_SCRATCH_TICKS = 1, 2, 4  # o2v_hip_grow_scratch_bytes: which of the three live in scratch
 THICK_BACKGROUND, THICK_BORDER, THICK_F32, THICK_OPEN_ONLY = 16, 32, 64, 128  # o2v_hip_thickness_dense flags (with FLAG_STAGE_TIMES: the ball voxels counted)
 THICK_MAX_RADIUS2 = 1 << 14  # ... its largest max_radius2
 THIN_ULTIMATE, THIN_CURVE = 0, 1  # o2v_hip_thin_dense modes: no end points; end points stay
@@ -227,6 +229,12 @@ def _bind():
     L.o2v_hip_watershed_scratch_bytes.restype = C.c_uint64
     L.o2v_hip_watershed_times.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_watershed_counters.argtypes = [C.c_void_p, C.c_void_p]
+    # ctx, relief, relief_strides, markers, marker_strides, dims, weights, flags, labels, strides, level, strides, ticks, strides, reached
+    L.o2v_hip_grow_dense.argtypes = [C.c_void_p] * 7 + [C.c_uint32] + [C.c_void_p] * 7
+    L.o2v_hip_grow_scratch_bytes.argtypes = [C.c_void_p, C.c_uint32]
+    L.o2v_hip_grow_scratch_bytes.restype = C.c_uint64
+    L.o2v_hip_grow_times.argtypes = [C.c_void_p, C.c_void_p]
+    L.o2v_hip_grow_counters.argtypes = [C.c_void_p, C.c_void_p]
     # ctx, labels, format, strides, dims, n_labels, connectivity, flags, values, value_strides, out_pairs, out_outside
     L.o2v_hip_adjacency_count.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                           C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -333,6 +341,12 @@ def adjacency_scratch_bytes(pairs):
     """o2v_hip_adjacency_scratch_bytes: the context scratch that the sorted list of `pairs` pairs of an adjacency_count takes (the
     pair table grows with the data: adjacency_counters)."""
     return int(_bind().o2v_hip_adjacency_scratch_bytes(int(pairs)))
+
+
+def grow_scratch_bytes(dims, which=0):
+    """o2v_hip_grow_scratch_bytes: the context scratch a grow_dense call over dims (x, y, z) takes; `which`: the OR of
+    GROW_SCRATCH_LABELS / _LEVEL / _TICKS for those of the three that are absent or not contiguous."""
+    return int(_bind().o2v_hip_grow_scratch_bytes(_u32x3(dims), which))
 
 
 def watershed_scratch_bytes(dims):
@@ -854,6 +868,36 @@ class DeviceVoxelizer:
         survivors) of the last watershed_dense call made with FLAG_STAGE_TIMES (else zeros)."""
         out = (C.c_uint64 * 6)()
         self._check(self._L.o2v_hip_watershed_counters(self._ctx, out), "o2v_hip_watershed_counters")
+        return tuple(int(v) for v in out)
+
+    def grow_dense(self, relief_ptr, relief_strides, markers_ptr, marker_strides, dims, weights, flags, labels_ptr, labels_strides, level_ptr=None,
+                   level_strides=None, ticks_ptr=None, ticks_strides=None):
+        """o2v_hip_grow_dense: the seeded watershed of the int32 relief at device pointer relief_ptr - the set is where it is
+        positive - from the int32 markers at markers_ptr (a seed where both are positive), with the step weights (face, edge,
+        corner; 0: no such step).  Into the int32 grids at labels_ptr, level_ptr and ticks_ptr (the last two may be None): the
+        label, the level and the ticks of every voxel, 0 / 0 / -1 outside the set and where no marker reaches.  Strides in
+        elements and dims per axis x, y, z.  Returns the number of voxels reached."""
+        w = (C.c_uint32 * 3)(*[int(v) for v in weights])
+        n = C.c_uint64(0)
+        self._check(self._L.o2v_hip_grow_dense(self._ctx, relief_ptr, _u64x3(relief_strides), markers_ptr, _u64x3(marker_strides), _u32x3(dims), w, flags,
+                                               labels_ptr, _u64x3(labels_strides), level_ptr, None if level_ptr is None else _u64x3(level_strides), ticks_ptr,
+                                               None if ticks_ptr is None else _u64x3(ticks_strides), C.byref(n)), "o2v_hip_grow_dense")
+        return int(n.value)
+
+    def grow_scratch_bytes(self, dims, which=0):
+        """o2v_hip_grow_scratch_bytes: the context scratch a grow_dense call over dims (x, y, z) takes."""
+        return grow_scratch_bytes(dims, which)
+
+    def grow_times(self):
+        """o2v_hip_grow_times: the device times (ms) of the last grow_dense call's init, level rounds, sources, tick rounds,
+        tight, label rounds and write stages."""
+        return self._stage_times("o2v_hip_grow_times", 7)
+
+    def grow_counters(self):
+        """o2v_hip_grow_counters: (rounds, tile visits, in-tile sweeps) of the level, the ticks and the labels - nine numbers - of
+        the last grow_dense call made with FLAG_STAGE_TIMES (else zeros)."""
+        out = (C.c_uint64 * 9)()
+        self._check(self._L.o2v_hip_grow_counters(self._ctx, out), "o2v_hip_grow_counters")
         return tuple(int(v) for v in out)
 
     def adjacency_count(self, labels_ptr, fmt, strides, dims, n_labels, connectivity, flags, values_ptr=None, value_strides=None):

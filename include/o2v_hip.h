@@ -1435,6 +1435,80 @@ int o2v_hip_debug_hits(o2v_hip_ctx *ctx, uint32_t *out8, uint64_t max_hits, uint
 /* Debugging aid: log2 histogram of hits per occupied cell of the last run (32 buckets; bucket b: 2^(b-1) < hits <= 2^b). */
 int o2v_hip_debug_hits_histogram(o2v_hip_ctx *ctx, uint64_t *out32);
 
+/* ---- smooth meshes of label grids: shared-interface surface nets ------------------------------------------
+ *
+ * The interfaces between the parts of a label grid as ONE indexed mesh, by surface nets in Gibson's form on labels: one vertex per
+ * cell of 2 x 2 x 2 samples that are not all equal, one quad per pair of face-adjacent samples with different labels - so the wall
+ * between two parts is meshed once, and the meshes of two parts share its vertices - and a relaxation that moves every vertex
+ * towards its neighbours in the net without leaving its cell.
+ *
+ * Grid.  labels is device memory of the context's device, only read: O2V_HIP_LABELS_I32 or O2V_HIP_LABELS_U8 exactly as
+ * o2v_hip_label_stats takes them (a bool tensor is U8), sample (x, y, z) at labels[x * strides[0] + y * strides[1] + z * strides[2]]
+ * (elements, any order, a stride may be 0), dims = (nx, ny, nz).  Labels are compared as signed int32; any value is allowed and no
+ * n_labels is needed.  E = 1 if flags has O2V_HIP_LABEL_SURFACE_CLOSED, else 0.  The extended lattice has the samples (x, y, z) with
+ * -E <= x < nx + E, -E <= y < ny + E, -E <= z < nz + E; a sample outside the box has label 0, L(c) is the label of sample c.  CLOSED
+ * therefore caps every part at the sides of the box; without it a surface that leaves the box is open there, as
+ * o2v_hip_surface_write's.
+ *   Cells: (i, j, k) with -E <= i < nx - 1 + E, -E <= j < ny - 1 + E, -E <= k < nz - 1 + E, named by its lowest sample; it holds
+ *   the samples (i + a, j + b, k + c), each of a, b, c 0 or 1.  A cell is active if its eight labels are not all equal.
+ *   Vertices: one per active cell, numbered in ascending (k, j, i).  cells[v] = (i, j, k), int32 (a component is -1 at the lower
+ *   sides of a CLOSED box).  Its centre is (float) (o + i + 1) per axis for an origin o: exact, and >= 0.  (Sample (x, y, z) stands
+ *   for the voxel centre o + (x, y, z) + 0.5, so the cell's centre is the lattice point between its eight voxels.)
+ *   Quads: for every extended sample c and axis ax in 0, 1, 2, with q = c + e_ax, u = (ax + 1) % 3, v = (ax + 2) % 3, one quad if q
+ *   is in the extended lattice, L(c) != L(q), and the edge is interior across: -E + 1 <= c[u] <= n_u + E - 2 and the same for v.  Its
+ *   cells are c0 = c - e_u - e_v, c1 = c - e_v, c2 = c, c3 = c - e_u, exactly o2v_hip_surface_write's (all four are active: they
+ *   contain the edge).  If L(c) > L(q) the quad is (c0, c1, c2, c3), else (c0, c3, c2, c1): the normal points from the larger label
+ *   to the smaller, against the background 0 outward for positive labels.  pairs[quad] = (hi, lo), the larger label first.  The quad
+ *   is written as the two triangles (q0, q1, q2), (q0, q2, q3): faces [2 Q][3] int32, triangles 2 n and 2 n + 1 are quad n.  Quads
+ *   come in ascending ((z * NY + y) * NX + x) * 3 + ax over the extended lattice (NX = nx + 2 E, x counted from -E).
+ *   Links: links[v][d] for d = -x, +x, -y, +y, -z, +z is the vertex of the neighbouring cell in that direction if that cell exists
+ *   and the four samples of the face the two cells share are not all equal (both cells are then active), else -1.  "The neighbour
+ *   is active" is NOT the rule: two active cells may share a uniform face, and they are not linked.  The links are the edges of the
+ *   quads.
+ *
+ * Relaxation (o2v_hip_label_surface_relax): a pure function of cells, links, origin and iterations, relaxation, reach; float32, op
+ * by op, no FMA, the division correctly rounded.
+ *   p_0[v] = centre(v).  For t < iterations every vertex is computed from p_t (Jacobi, two buffers, never in place):
+ *     s = (0, 0, 0); for d = 0 .. 5 in turn, if links[v][d] is valid, s = s + p_t[links[v][d]] component by component; m = the
+ *     number of valid links.  m == 0: p_{t+1}[v] = p_t[v].  Else avg = s / (float) m, r = p_t[v] + relaxation * (avg - p_t[v]),
+ *     p_{t+1}[v] = fminf(fmaxf(r, centre - reach), centre + reach) per component.
+ *   A link < 0 or >= n_vertices is no link and is never followed: arrays from anywhere cannot make the call read outside them.
+ *   0 < relaxation <= 1, 0 <= reach <= 0.5, 0 <= iterations <= 1024.  With iterations 0, positions are the centres; with them the
+ *   signed volume of the quads of a label is its number of voxels.
+ *   With reach 0.5 a feature one voxel wide collapses as the iterations go on (a single voxel's eight vertices meet in its centre):
+ *   Gibson's behaviour; reach 0.25 keeps such a feature at half its size.  The relaxation is Laplacian smoothing and shrinks noisy
+ *   labels; neither is corrected.
+ *
+ * Two calls, as for o2v_hip_surface_*.  o2v_hip_label_surface_count classifies the grid (its only pass over the labels) and keeps in
+ * scratch of the context, per 64 extended samples along x, three difference words (the label differs from the one at x + 1, y + 1,
+ * z + 1), the word of active cells and two 16-bit prefixes - 36 bytes per 64 samples - and per 256 such words two offsets; it
+ * returns the vertices V and the quads Q.  o2v_hip_label_surface_write must follow a count with the same labels, format, strides,
+ * dims and flags (else O2V_HIP_ERR_BAD_ARGUMENT, "no matching o2v_hip_label_surface_count"; another count, refused or not, replaces
+ * the last one) and fills cells [V][3], links [V][6], faces [2 Q][3], pairs [Q][2], all int32 and contiguous; it may be repeated.
+ * Only the pairs and the winding are read from the labels again: if the grid changed between the calls they may be meaningless,
+ * but every index written is below V and nothing is written outside the arrays.  o2v_hip_label_surface_relax needs no count: it
+ * takes cells and links from anywhere and writes positions [n_vertices][3] float32; its second buffer is scratch of the context.
+ * No atomics anywhere: one run equals another bit for bit.
+ * Refused before any launch (O2V_HIP_ERR_BAD_ARGUMENT): null arguments (an output may be null only where its count is 0), zero
+ * dims, an unknown format or flag bit, an I32 grid that is not 4-byte aligned, outputs that are not 4-byte aligned, capacities
+ * below the counted totals, outputs overlapping each other or the grid (relax: positions overlapping cells or links), a pointer
+ * that is not device memory of the context's device with its whole extent inside its allocation, a relaxation or reach outside
+ * its range (a NaN included).  O2V_HIP_ERR_LIMIT: a dim above 65 536 - 2 E, more than 2^31 - 1 vertices or triangles (2 Q), more
+ * than 1024 iterations, an origin component above 65 536 (the caller keeps origin[a] + dims[a] + E at or below 65 536: centres are
+ * then exact and positions exact to 2^-7 voxel).  A failed scratch allocation returns O2V_HIP_ERR_OUT_OF_MEMORY and the context
+ * stays usable.  The calls run on the context's stream and return when their results have landed. */
+enum { O2V_HIP_LABEL_SURFACE_CLOSED = 1 };
+int o2v_hip_label_surface_count(o2v_hip_ctx *ctx, const void *labels, uint32_t format, const uint64_t strides[3], const uint32_t dims[3],
+                                uint32_t flags, uint64_t *out_vertices, uint64_t *out_quads);
+int o2v_hip_label_surface_write(o2v_hip_ctx *ctx, const void *labels, uint32_t format, const uint64_t strides[3], const uint32_t dims[3],
+                                uint32_t flags, int32_t *cells, int32_t *links, uint64_t vertex_capacity, int32_t *faces, int32_t *pairs,
+                                uint64_t quad_capacity);
+int o2v_hip_label_surface_relax(o2v_hip_ctx *ctx, const int32_t *cells, const int32_t *links, uint64_t n_vertices, const uint32_t origin[3],
+                                uint32_t iterations, float relaxation, float reach, float *positions);
+/* The device times (ms) of the stages: classify, count + scan (the last count), vertices (cells + links), faces (+ pairs) (the last
+ * write; 0 after a count), relax (the last relax, all its iterations). */
+int o2v_hip_label_surface_times(const o2v_hip_ctx *ctx, float out_ms[5]);
+
 /* ---- multi-GPU: the grid sharded by z-slab over the GPUs of one node --------------------------
  *
  * Every rank (one per GPU) holds the whole triangle list, like every 64^3 chunk of the reference sees every triangle

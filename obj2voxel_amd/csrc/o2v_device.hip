@@ -137,6 +137,7 @@ namespace {
 #include "o2v_dev_k24_adjacency.hpp"   // (behind K19: its chunk and its reads)
 #include "o2v_dev_k25_euler.hpp"       // (behind K19: its chunk and its reads)
 #include "o2v_dev_k28_grow.hpp"        // (behind K20 and the pair table: the offsets, see masks and tile flags; I32View)
+#include "o2v_dev_k29_label_surface.hpp"   // (behind K10 and K6: its words, prefixes, search and select; the block scan)
 
 }  // namespace
 
@@ -278,6 +279,7 @@ struct Switches {
     int ws_table_log2 = env_int("O2V_WS_TABLE_LOG2", 0);       // test hook: the pair table of K23 starts with 2^k slots (if > 0; else sized from the peaks)
     bool adj_no_table = env_on("O2V_ADJ_NO_TABLE");            // A/B: k_adj_pairs without its table in LDS, every flush to global memory
     bool eu_no_table = env_on("O2V_EU_NO_TABLE");              // A/B: k_euler without its table in LDS, every row to global memory
+    bool lsf_no_tile = env_on("O2V_LSF_NO_TILE");              // A/B: k_lsf_classify, every label's neighbours at y + 1 and z + 1 re-read through L2, no tile in LDS
     int adj_table_log2 = env_int("O2V_ADJ_TABLE_LOG2", 0);     // test hook: the pair table of K24 starts with 2^k slots (if > 0; else sized from the labels)
     bool tiny_buffers = env_on("O2V_TEST_TINY_BUFFERS");       // test hook: minimal first capacities (every grow -> re-run path)
     bool block_list = env_on("O2V_TEST_BLOCK_LIST");           // test hook: the slab's block list for a mesh of any size
@@ -595,6 +597,15 @@ struct o2v_hip_ctx {
     DevArray<uint32_t> d_open_dirs, d_open_list;
     PinnedArray<uint32_t> h_open_dirs;
     StageTimes<3> open_times;
+    // K29 (o2v_hip_label_surface_count / _write / _relax): per word of 64 extended samples its three difference words (x, y, z: one
+    // array, three parts), active cells and block-local prefixes, per block of words the vertex and quad offsets; the second
+    // position buffer of the relaxation - all grown on demand; the grid they were counted for; the times of the five stages
+    DevArray<unsigned long long> d_lsf_diff, d_lsf_active, d_lsf_voff, d_lsf_qoff;
+    DevArray<uint32_t> d_lsf_local;
+    DevArray<float> d_lsf_pos;
+    PinnedArray<unsigned long long> h_lsf_ctr;
+    StageTimes<5> lsf_times;
+    SurfaceCount lsf;   // (the labels; format | flags << 8)
 
     // results of the last run
     uint64_t n_vox = 0;
@@ -2643,6 +2654,7 @@ int o2v_hip_voxels_device_ptr(o2v_hip_ctx *ctx, const uint32_t **out_ptr, uint64
 #include "o2v_dev_host_k24_adjacency.hpp"
 #include "o2v_dev_host_k25_euler.hpp"
 #include "o2v_dev_host_k28_grow.hpp"
+#include "o2v_dev_host_k29_label_surface.hpp"
 
 extern "C" {
 

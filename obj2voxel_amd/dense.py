@@ -44,7 +44,10 @@ and cavities of a set (o2v_hip_euler_stats); build_octree 
 valid and full masks per node, level by level in Morton order, full cells collapsed -, octree_lookup descends it per point,
 octree_to_dense expands it into any box and octree_level gives one level of it (o2v_hip_octree_build / _write / _lookup /
 _to_dense); openness counts per voxel the directions of a direction_set in which one sees out of the grid -
-sky visibility, sun shadows -, and shade_colors bakes it into colours as ambient occlusion (o2v_hip_openness).
+sky visibility, sun shadows -, and shade_colors bakes it into colours as ambient occlusion (o2v_hip_openness); label_surfaces turns a label
+grid into one smooth mesh of all its interfaces - the wall between two parts meshed once -, relax_surface smooths a kept net anew,
+part_mesh cuts one part's closed mesh out of it and interface_areas measures the walls (o2v_hip_label_surface_count / _write /
+_relax).
 
 torch is imported first on purpose: the library must bind to the HIP runtime torch loaded (a process that loaded the library
 before torch holds two separate runtime copies, and this module refuses to work there).
@@ -502,10 +505,7 @@ def extract_surface(dv, field, level=0.0, *, origin=(0, 0, 0), transform=None, s
     origin = _origin(origin)
     if any(o + n > MAX_SURFACE_EXTENT for o, n in zip(origin, field.shape[::-1])):
         raise ValueError(f"origin {origin} + field's extent {tuple(field.shape[::-1])} [x, y, z] is above {MAX_SURFACE_EXTENT}")
-    if transform is not None:
-        transform = torch.as_tensor(transform, dtype=torch.float64).reshape(-1)
-        if transform.numel() != 12:
-            raise ValueError("transform must hold 12 numbers: a row-major 3 x 3 matrix, then the translation")
+    transform = _mesh_transform(transform)
     nz, ny, nx = field.shape
     args = (field.data_ptr(), _strides(field), (nx, ny, nz), level)
     _sync(device)   # (the caller's writes to field have landed)
@@ -514,11 +514,28 @@ def extract_surface(dv, field, level=0.0, *, origin=(0, 0, 0), transform=None, s
     faces = torch.empty((n_triangles, 3), dtype=torch.int32, device=device)
     if n_vertices:
         dv.surface_write(*args, origin, positions.data_ptr(), n_vertices, _ptr(faces) if n_triangles else None, n_triangles)
-    if transform is not None and n_vertices:
-        inverse = torch.linalg.inv(transform[:9].reshape(3, 3)).to(device)   # (3 x 3, on the host)
-        p = positions.to(torch.float64) * supersampling - transform[9:].to(device)
-        positions = (p[:, None, :] * inverse[None, :, :]).sum(dim=2).to(torch.float32).contiguous()
-    return positions, faces
+    return _to_model_space(positions, transform, supersampling), faces
+
+
+def _mesh_transform(transform):
+    """The transform argument of extract_surface and label_surfaces: None, or its 12 numbers as a float64 tensor on the host."""
+    if transform is None:
+        return None
+    transform = torch.as_tensor(transform, dtype=torch.float64).reshape(-1)
+    if transform.numel() != 12:
+        raise ValueError("transform must hold 12 numbers: a row-major 3 x 3 matrix, then the translation")
+    return transform
+
+
+def _to_model_space(positions, transform, supersampling):
+    """Voxel-space positions float32 [V, 3] in model space: A^-1 (supersampling * p - t) for transform = (A, t) as _mesh_transform
+    returns it, computed in float64 and rounded once; the positions themselves if transform is None or there are none."""
+    if transform is None or not positions.shape[0]:
+        return positions
+    device = positions.device
+    inverse = torch.linalg.inv(transform[:9].reshape(3, 3)).to(device)   # (3 x 3, on the host)
+    p = positions.to(torch.float64) * supersampling - transform[9:].to(device)
+    return (p[:, None, :] * inverse[None, :, :]).sum(dim=2).to(torch.float32).contiguous()
 
 
 def _origin(origin):
@@ -1035,6 +1052,7 @@ from .skeleton import skeleton_nodes, skeletonize  # noqa: E402,F401  (the torch
 
 from .watershed import split_parts, watershed, watershed_peaks  # noqa: E402,F401  (the torch layer of o2v_hip_watershed_dense)
 from .grow import grow_labels, markers_from_seeds, seeded_watershed  # noqa: E402,F401  (the torch layer of o2v_hip_grow_dense)
+from .labelmesh import LabelMesh, interface_areas, label_surfaces, part_mesh, relax_surface  # noqa: E402,F401  (the torch layer of o2v_hip_label_surface_*)
 
 # ---- which labels touch: the region adjacency of a label grid ------------------------------------------------
 

@@ -54,6 +54,7 @@ OCT_MAX_DEPTH = 16  # ... the deepest tree: a root cube of 65 536 voxels along a
 OPEN_SURFACE, OPEN_SOLID, OPEN_EMPTY, OPEN_GRID = 0, 1, 2, 3  # o2v_hip_openness: the target modes
 OPEN_MAX_DIRECTIONS = 254  # ... the most directions of a call (a count is one byte, 255 marks the voxels that are no targets)
 OPEN_MAX_COMPONENT = 127  # ... the largest magnitude of a direction's component
+LABEL_SURFACE_CLOSED = 1  # o2v_hip_label_surface_count / _write: the box is surrounded by label 0, every part is capped at its sides
 EULER_COLUMNS = 7  # o2v_hip_euler_stats: the int64 columns of a row of its table: voxels, closed-in faces, edges, vertices, inner faces, edges, vertices
 ERR_BAD_ARGUMENT = 3
 ERR_LIMIT = 5
@@ -265,6 +266,15 @@ def _bind():
     L.o2v_hip_openness_times.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_openness_scratch_bytes.argtypes = [C.c_void_p]
     L.o2v_hip_openness_scratch_bytes.restype = C.c_uint64
+    # ctx, labels, format, strides, dims, flags, out_vertices, out_quads
+    L.o2v_hip_label_surface_count.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64),
+                                              C.POINTER(C.c_uint64)]
+    # ctx, labels, format, strides, dims, flags, cells, links, vertex_capacity, faces, pairs, quad_capacity
+    L.o2v_hip_label_surface_write.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
+                                              C.c_void_p, C.c_void_p, C.c_uint64]
+    # ctx, cells, links, n_vertices, origin, iterations, relaxation, reach, positions
+    L.o2v_hip_label_surface_relax.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_void_p]
+    L.o2v_hip_label_surface_times.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_max_slab_layers.argtypes = [C.c_void_p, C.POINTER(_Params), C.POINTER(C.c_uint32)]
     return L
 
@@ -946,6 +956,32 @@ class DeviceVoxelizer:
     def euler_stats_times(self):
         """o2v_hip_euler_stats_times: the device times (ms) of the last euler_stats call's table initialisation and pass."""
         return self._stage_times("o2v_hip_euler_stats_times", 2)
+
+    def label_surface_count(self, labels_ptr, fmt, strides, dims, flags=LABEL_SURFACE_CLOSED):
+        """o2v_hip_label_surface_count: (vertices, quads) of the surface nets of the label grid at device address labels_ptr
+        (LABELS_I32 / LABELS_U8; strides in elements, strides and dims per axis x, y, z); LABEL_SURFACE_CLOSED in flags: the box
+        is surrounded by label 0.  What label_surface_write needs stays in the context."""
+        v, q = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.o2v_hip_label_surface_count(self._ctx, labels_ptr, fmt, _u64x3(strides), _u32x3(dims), flags, C.byref(v), C.byref(q)),
+                    "o2v_hip_label_surface_count")
+        return v.value, q.value
+
+    def label_surface_write(self, labels_ptr, fmt, strides, dims, flags, cells_ptr, links_ptr, vertex_capacity, faces_ptr, pairs_ptr, quad_capacity):
+        """o2v_hip_label_surface_write: the net label_surface_count counted for the same grid and flags, into int32 cells
+        [vertices, 3], links [vertices, 6], faces [2 quads, 3] and pairs [quads, 2] at device addresses, contiguous."""
+        self._check(self._L.o2v_hip_label_surface_write(self._ctx, labels_ptr, fmt, _u64x3(strides), _u32x3(dims), flags, cells_ptr, links_ptr,
+                                                        vertex_capacity, faces_ptr, pairs_ptr, quad_capacity), "o2v_hip_label_surface_write")
+
+    def label_surface_relax(self, cells_ptr, links_ptr, n_vertices, origin, iterations, relaxation, reach, positions_ptr):
+        """o2v_hip_label_surface_relax: `iterations` Jacobi steps of the net's relaxation from the cells' centres, into float32
+        positions [n_vertices, 3] at a device address (voxel space; iterations 0: the centres)."""
+        self._check(self._L.o2v_hip_label_surface_relax(self._ctx, cells_ptr, links_ptr, n_vertices, _u32x3(origin), iterations, float(relaxation),
+                                                        float(reach), positions_ptr), "o2v_hip_label_surface_relax")
+
+    def label_surface_times(self):
+        """o2v_hip_label_surface_times: the device times (ms) of the last label_surface_count call's classify and count + scan
+        stages, of the last label_surface_write call's vertex and face stages and of the last label_surface_relax call."""
+        return self._stage_times("o2v_hip_label_surface_times", 5)
 
     def octree_build(self, grid_ptr, fmt, strides, dims, level, origin, depth=0, flags=OCT_COLLAPSE):
         """o2v_hip_octree_build: the sparse voxel octree of the set grid at device address grid_ptr (grid arguments as gather_count

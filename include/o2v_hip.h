@@ -1349,6 +1349,75 @@ uint64_t o2v_hip_octree_scratch_bytes(const uint32_t dims[3], const uint32_t ori
 /* The smallest depth whose root cube holds origin + [0, dims); 0 if a dim is 0 or origin + dims is above 65 536.  Needs no device. */
 uint32_t o2v_hip_octree_depth(const uint32_t origin[3], const uint32_t dims[3]);
 
+/* ---- Sparse voxel DAGs: equal subtrees of an octree merged -------------------------------------------------
+ *
+ * An octree of a voxelized model repeats itself: at level D - 1 there are at most 255 different nodes, and flat walls, the inside
+ * of shells and periodic structures repeat one level up and further.  Merging equal subtrees gives the sparse voxel DAG (Kaempe,
+ * Sintorn, Assarsson 2013), which is what makes trees of fine grids cheap to keep and to ship.  Per child pointer it keeps the
+ * number of listed voxels under the earlier siblings, so a descent through the DAG finds the same voxel slot as one through the
+ * tree, and an attribute array made for the tree works unchanged with the DAG.  Integers only; defined so that a numpy restatement
+ * (tests/dag_ref.py) reproduces every bit.
+ *
+ * Input.  A tree as o2v_hip_octree_build defines it, in the caller's device arrays valid, full, first_child of n_nodes entries,
+ * its depth D, O2V_HIP_OCT_COLLAPSE in flags or not, and level_counts[16], the nodes per level (0 from level D on, 1 at level 0;
+ * their sum is n_nodes): the merge works level by level.  stored(i) is `valid` at level D - 1 and, above it, `valid` for a plain
+ * tree and valid & ~full for a collapsed one.  listed(i) is popcount(valid) at level D - 1 and the sum of `listed` over the stored
+ * children above it, in uint32 arithmetic.
+ *
+ * Equality.  Two nodes of one level are equal if their `valid` masks are equal, their `full` masks are equal, and their stored
+ * children are equal one by one, recursively; at level D - 1: equal `valid`.  Nodes of different levels are never merged.
+ *
+ * Numbering.  The classes of level l are numbered by the smallest tree index among their members, ascending: the first occurrence
+ * in Morton order decides.  DAG node dag_offset[l] + rank is that class, dag_offset the exclusive scan of out_level_counts, the
+ * classes per level; the root is DAG node 0; M is their sum.
+ *
+ * Arrays.  valid, full (uint8 [M]) are those of the class.  first_child (int32 [M]) is the node's first entry in the pointer
+ * arrays, -1 at level D - 1 and where stored == 0.  child (int32 [P]) is the DAG node of each stored child, the entries in node
+ * order and within a node in octant order, so first_child is the exclusive scan of popcount(stored) over the nodes above level
+ * D - 1.  skip (int32 [P], uint32 bits) is the sum of `listed` over the node's stored children before this one - the same for every
+ * member of a class, which is why it can live in the DAG.
+ *
+ * Descent.  For an int32 point (x, y, z) the result is int32 [4] = (solid, level, node, voxel_index); outside the root cube
+ * (0, -1, -1, -1).  Start at node 0 with acc = 0 (uint32); at node i of level l take o, the octant of the point: `valid` bit
+ * clear: (0, l, i, -1); l = D - 1: (1, l, i, acc + rank of o in valid), or (1, l, i, -1) without skip; `full` bit set and the DAG
+ * collapsed: (1, l, i, -1); otherwise e = first_child[i] + rank of o in stored: first_child[i] < 0 or e outside [0, P) ends it
+ * with (0, -2, -1, -1); else acc += skip[e], i = child[e], and an i outside [0, M) ends it with (0, -2, -1, -1).  At most D steps,
+ * and nothing is read outside the arrays, whatever they hold.  On the DAG of a tree, columns 0, 1 and 3 equal
+ * o2v_hip_octree_lookup's on that tree for every point, and column 2 is the class of the tree node it reports.
+ *
+ * o2v_hip_octree_dag_build merges into scratch of the context (flags: O2V_HIP_OCT_COLLAPSE, O2V_HIP_FLAG_STAGE_TIMES) and returns
+ * the classes per level, M and P; o2v_hip_octree_dag_write copies the DAG into the caller's contiguous device arrays (skip may be
+ * null; child too where P is 0).  o2v_hip_octree_dag_lookup runs the descent per point on the caller's arrays (skip may be null:
+ * voxel_index is then -1, except where P is 0 - a root alone has nothing to skip), o2v_hip_octree_dag_to_dense writes out(x, y, z) = 1 where the descent is solid and 0 elsewhere for
+ * every voxel of any box, as o2v_hip_octree_to_dense does.
+ *
+ * A tree that is not one.  A stored child index outside the next level, [offset[l + 1], offset[l + 2]), makes the build fail with
+ * O2V_HIP_ERR_BAD_ARGUMENT ("... are not a tree of these level counts").  The index is checked before it is used; the failure is
+ * found through a flag on the device that the host reads at the wait the build has anyway; nothing is written to caller memory.
+ *
+ * O2V_HIP_ERR_BAD_ARGUMENT, in this order: a null argument, unknown flag bits, depth outside 1 ... 16, level counts that do not
+ * add up to n_nodes (n_nodes = 0 for the queries); O2V_HIP_ERR_LIMIT: n_nodes, P or n above 2^31 - 1, and what
+ * o2v_hip_octree_to_dense limits of a box; then O2V_HIP_ERR_BAD_ARGUMENT again: int32 arrays that are not 4-byte aligned, output
+ * arrays that overlap each other or the inputs, a pointer that is not device memory of the context's device with its whole extent
+ * inside its allocation, o2v_hip_octree_dag_write without a build ("no o2v_hip_octree_dag_build").  All of these come before any
+ * launch.  A failed scratch allocation is O2V_HIP_ERR_OUT_OF_MEMORY and leaves the context usable.  Scratch:
+ * o2v_hip_octree_dag_scratch_bytes is the most a build takes (0 for level counts a build refuses) - 8 bytes per tree node, 4 per
+ * node of the widest level, 4 per table entry (a power of two, at least twice the widest level above D - 1) and a DAG that merges
+ * nothing, 6 bytes per node and 8 per pointer; a build sizes the DAG by what it merged. */
+int o2v_hip_octree_dag_build(o2v_hip_ctx *ctx, const uint8_t *valid, const uint8_t *full, const int32_t *first_child, uint64_t n_nodes, uint32_t depth,
+                             uint32_t flags, const uint64_t level_counts[16], uint64_t out_level_counts[16], uint64_t *out_nodes, uint64_t *out_pointers);
+int o2v_hip_octree_dag_write(o2v_hip_ctx *ctx, uint8_t *valid, uint8_t *full, int32_t *first_child, int32_t *child, int32_t *skip);
+int o2v_hip_octree_dag_lookup(o2v_hip_ctx *ctx, const uint8_t *valid, const uint8_t *full, const int32_t *first_child, const int32_t *child,
+                              const int32_t *skip, uint64_t n_nodes, uint64_t n_pointers, uint32_t depth, uint32_t flags, const int32_t *points, uint64_t n,
+                              int32_t *out);
+int o2v_hip_octree_dag_to_dense(o2v_hip_ctx *ctx, const uint8_t *valid, const uint8_t *full, const int32_t *first_child, const int32_t *child, uint64_t n_nodes,
+                                uint64_t n_pointers, uint32_t depth, uint32_t flags, const uint32_t origin[3], const uint32_t dims[3], uint8_t *out,
+                                const uint64_t out_strides[3]);
+/* The device times (ms) of the last build's merge of level D - 1, merge of the levels above and output (the pointers scanned, the
+ * DAG filled) and of the last write, from events around them. */
+int o2v_hip_octree_dag_times(const o2v_hip_ctx *ctx, float out_ms[4]);
+uint64_t o2v_hip_octree_dag_scratch_bytes(const uint64_t level_counts[16], uint32_t depth);
+
 /* ---- Sky visibility and ambient occlusion of dense grids --------------------------------------------------
  *
  * Per target voxel, in how many of D integer directions a ray from its centre gets out: the quantity ambient occlusion is baked

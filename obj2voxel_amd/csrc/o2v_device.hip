@@ -60,7 +60,7 @@
 //   K24 k_adj_*                o2v_hip_adjacency_count / _write: which labels of a label grid touch - per pair the face, edge and
 //                              corner contacts and the two passes of a values grid, one pass of K19's chunks into a table in LDS
 //                              and the pair table, sorted on the host; outside the pipeline
-//   K26 k_oct_*                o2v_hip_octree_build / _write / _lookup / _to_dense: the sparse voxel octree of a dense grid - a
+//   K26 k_oct_*              o2v_hip_octree_build / _write / _lookup / _to_dense: the sparse voxel octree of a dense grid - a
 //                              pyramid of (valid, full) masks bottom-up, the nodes level by level top-down by scans, the descent
 //                              per point and per 2^3 block; outside the pipeline
 //   K27 k_open_*               o2v_hip_openness: in how many of D integer directions a voxel sees out of the grid - K11's masks built
@@ -69,6 +69,9 @@
 //   K28 k_grow_*               o2v_hip_grow_dense: seeded watershed - markers grown through an int32 relief by three fixed points (level,
 //                              ticks, label), each K20's relaxation tile by tile in LDS, round by round, with a streaming pass that
 //                              writes the next one's neighbour masks in between; outside the pipeline
+//   K30 k_dag_*                o2v_hip_octree_dag_build / _write / _lookup / _to_dense: equal subtrees of an octree merged level by
+//                              level, bottom up - a table of 256 smallest indices at level D - 1, an open-addressing table of node
+//                              indices above, the classes ranked by scans -, the descent with per-pointer skips; outside the pipeline
 //       k_pt_list              o2v_dev_pair_table.hpp: the table of id pairs in global memory of K23 and K24, its occupied slots as a list
 //   plan k_zhist               o2v_hip_plan_slabs: predicted hits per z layer -> work-balanced slabs for N GPUs
 // With the direct MAX path K1's counters reach the host while K2 runs, and only the stages that have work are enqueued
@@ -126,6 +129,7 @@ namespace {
 #include "o2v_dev_k15_nearest.hpp"
 #include "o2v_dev_k17_downsample.hpp"
 #include "o2v_dev_k26_octree.hpp"      // (behind K12 and K6: the bit grid, the classify kernel, the block scan)
+#include "o2v_dev_k30_dag.hpp"         // (behind K26: its octants, ranks and stored masks, its box of 2^3 blocks)
 #include "o2v_dev_k27_openness.hpp"    // (behind K11: it walks the masks that k_ray_build makes)
 #include "o2v_dev_k18_crossings.hpp"
 #include "o2v_dev_k19_label_stats.hpp"
@@ -589,6 +593,22 @@ struct o2v_hip_ctx {
         uint32_t origin[3] = {}, depth = 0, flags = 0;
         uint64_t nodes = 0, voxels = 0;
     } oct;
+    // K30 (o2v_hip_octree_dag_build / _write): per tree node its class and its listed voxels, per node of the widest level the
+    // block-local scans, the table of node indices (at least the 256 entries of level D - 1), the block offsets of a level's scan
+    // and the counters (kDagMeta words) - fixed by the level counts; the DAG's arrays - grown with the data; what the last build
+    // made; the times of level D - 1, the levels above and the output (events 0 - 2 and 3 - 4 of dag_times: the host waits between
+    // them) and of the last write
+    DevArray<uint32_t> d_dag_cls, d_dag_listed, d_dag_num, d_dag_tab;
+    DevArray<unsigned long long> d_dag_boff, d_dag_meta;
+    DevArray<uint8_t> d_dag_valid, d_dag_full;
+    DevArray<int32_t> d_dag_first, d_dag_child, d_dag_skip;
+    PinnedArray<unsigned long long> h_dag_meta;
+    StageTimes<4> dag_times;
+    StageTimes<1> dag_write_times;
+    struct DagBuild {
+        bool valid = false;
+        uint64_t nodes = 0, pointers = 0;
+    } dag;
     // K27 (o2v_hip_openness): the three levels of masks of its own (a RayCaster's snapshot is not touched), the counters (targets
     // counted, targets listed), the direction table (nine words per direction) on both sides, the list of the targets' linear
     // indices - grown with the data; the times of build, targets and walk
@@ -2646,6 +2666,7 @@ int o2v_hip_voxels_device_ptr(o2v_hip_ctx *ctx, const uint32_t **out_ptr, uint64
 #include "o2v_dev_host_k13_gather.hpp"
 #include "o2v_dev_host_k17_downsample.hpp"
 #include "o2v_dev_host_k26_octree.hpp"
+#include "o2v_dev_host_k30_dag.hpp"
 #include "o2v_dev_host_k27_openness.hpp"
 #include "o2v_dev_host_k19_label_stats.hpp"
 #include "o2v_dev_host_k21_thickness.hpp"

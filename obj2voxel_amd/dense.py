@@ -47,7 +47,9 @@ _to_dense); openness counts per voxel the directions of a 
 sky visibility, sun shadows -, and shade_colors bakes it into colours as ambient occlusion (o2v_hip_openness); label_surfaces turns a label
 grid into one smooth mesh of all its interfaces - the wall between two parts meshed once -, relax_surface smooths a kept net anew,
 part_mesh cuts one part's closed mesh out of it and interface_areas measures the walls (o2v_hip_label_surface_count / _write /
-_relax).
+_relax); octree_dag merges the equal subtrees of an Octree into a sparse voxel DAG that keeps every voxel's
+slot, dag_lookup descends it per point and dag_to_dense expands it (o2v_hip_octree_dag_build / _write / _lookup / _to_dense,
+DESIGN.md section 34).
 
 torch is imported first on purpose: the library must bind to the HIP runtime torch loaded (a process that loaded the library
 before torch holds two separate runtime copies, and this module refuses to work there).
@@ -1067,6 +1069,8 @@ from .topology import EulerStats, betti_numbers, euler_numbers, euler_stats, int
 
 from .octree import (Octree, build_octree, octree_depth, octree_level, octree_lookup,  # noqa: E402,F401
                      octree_to_dense)   # (the torch layer of o2v_hip_octree_build / _write / _lookup / _to_dense)
+# ---- sparse voxel DAGs: equal subtrees of an octree merged ----------------------------------------------------
+from .octree import OctreeDag, dag_lookup, dag_to_dense, octree_dag  # noqa: E402,F401   (o2v_hip_octree_dag_build / _write / _lookup / _to_dense)
 
 # ---- sky visibility and ambient occlusion -------------------------------------------------------------------
 

@@ -259,6 +259,15 @@ def _bind():
     L.o2v_hip_octree_scratch_bytes.restype = C.c_uint64
     L.o2v_hip_octree_depth.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_octree_depth.restype = C.c_uint32
+    # ctx, valid, full, first_child, n_nodes, depth, flags, level_counts, out_level_counts, out_nodes, out_pointers
+    L.o2v_hip_octree_dag_build.argtypes = _tree + [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.o2v_hip_octree_dag_write.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    # ctx, valid, full, first_child, child, (skip,) n_nodes, n_pointers, depth, flags
+    L.o2v_hip_octree_dag_lookup.argtypes = [C.c_void_p] * 6 + [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.o2v_hip_octree_dag_to_dense.argtypes = [C.c_void_p] * 5 + [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.o2v_hip_octree_dag_times.argtypes = [C.c_void_p, C.c_void_p]
+    L.o2v_hip_octree_dag_scratch_bytes.argtypes = [C.c_void_p, C.c_uint32]
+    L.o2v_hip_octree_dag_scratch_bytes.restype = C.c_uint64
     # ctx, grid, format, strides, dims, level, directions, n_directions, target_mode, target_grid, target_strides, max_distance2, flags,
     # dst, dst_strides, mask, mask_strides, out_targets
     L.o2v_hip_openness.argtypes = _gather + [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
@@ -399,6 +408,19 @@ def faces_scratch_bytes(dims, color_mode=GATHER_COLOR_CONSTANT, merge=None):
 def octree_scratch_bytes(dims, origin=(0, 0, 0), depth=0):
     """o2v_hip_octree_scratch_bytes: the most context scratch an octree_build of the box origin + [0, dims) (x, y, z) takes."""
     return int(_bind().o2v_hip_octree_scratch_bytes(_u32x3(dims), _u32x3(origin), int(depth)))
+
+
+def _level_counts(level_counts):
+    counts = [int(c) for c in level_counts]
+    if len(counts) > OCT_MAX_DEPTH or any(not 0 <= c < 2 ** 64 for c in counts):
+        raise ValueError(f"level_counts must be at most {OCT_MAX_DEPTH} counts, not {level_counts!r}")
+    return (C.c_uint64 * OCT_MAX_DEPTH)(*(counts + [0] * (OCT_MAX_DEPTH - len(counts))))
+
+
+def octree_dag_scratch_bytes(level_counts, depth):
+    """o2v_hip_octree_dag_scratch_bytes: the most context scratch an octree_dag_build of a tree of these nodes per level takes; 0
+    for level counts a build refuses."""
+    return int(_bind().o2v_hip_octree_dag_scratch_bytes(_level_counts(level_counts), int(depth)))
 
 
 def openness_scratch_bytes(dims):
@@ -1014,6 +1036,37 @@ class DeviceVoxelizer:
         """o2v_hip_octree_times: the device times (ms) of the last octree_build's classify, pyramid and order stages and of the last
         octree_write."""
         return self._stage_times("o2v_hip_octree_times", 4)
+
+    def octree_dag_build(self, valid_ptr, full_ptr, first_child_ptr, n_nodes, depth, flags, level_counts):
+        """o2v_hip_octree_dag_build: the equal subtrees of the tree in the caller's device arrays merged, level by level, into the
+        context's scratch.  level_counts: the tree's nodes per level.  Returns (classes per level [depth], nodes, pointers);
+        octree_dag_write copies the arrays out."""
+        counts, n, p = (C.c_uint64 * OCT_MAX_DEPTH)(), C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.o2v_hip_octree_dag_build(self._ctx, valid_ptr, full_ptr, first_child_ptr, n_nodes, depth, flags, _level_counts(level_counts), counts,
+                                                     C.byref(n), C.byref(p)), "o2v_hip_octree_dag_build")
+        return tuple(int(c) for c in counts[:depth]), n.value, p.value
+
+    def octree_dag_write(self, valid_ptr, full_ptr, first_child_ptr, child_ptr, skip_ptr=None):
+        """o2v_hip_octree_dag_write: the last octree_dag_build's DAG into the contiguous device arrays valid, full (uint8 [nodes]),
+        first_child (int32 [nodes]), child and, unless None, skip (int32 [pointers])."""
+        self._check(self._L.o2v_hip_octree_dag_write(self._ctx, valid_ptr, full_ptr, first_child_ptr, child_ptr, skip_ptr), "o2v_hip_octree_dag_write")
+
+    def octree_dag_lookup(self, valid_ptr, full_ptr, first_child_ptr, child_ptr, skip_ptr, n_nodes, n_pointers, depth, flags, points_ptr, n, out_ptr):
+        """o2v_hip_octree_dag_lookup: the descent through the DAG in the caller's device arrays for n int32 points (x, y, z); out int32
+        [n, 4] = (solid, level, node, voxel_index), voxel_index -1 where skip_ptr is None."""
+        self._check(self._L.o2v_hip_octree_dag_lookup(self._ctx, valid_ptr, full_ptr, first_child_ptr, child_ptr, skip_ptr, n_nodes, n_pointers, depth, flags,
+                                                      points_ptr, n, out_ptr), "o2v_hip_octree_dag_lookup")
+
+    def octree_dag_to_dense(self, valid_ptr, full_ptr, first_child_ptr, child_ptr, n_nodes, n_pointers, depth, flags, origin, dims, out_ptr, out_strides):
+        """o2v_hip_octree_dag_to_dense: 1 where the DAG is solid and 0 elsewhere into the uint8 grid at out_ptr, the box origin + [0,
+        dims) of the global lattice, which may stick out of the root cube."""
+        self._check(self._L.o2v_hip_octree_dag_to_dense(self._ctx, valid_ptr, full_ptr, first_child_ptr, child_ptr, n_nodes, n_pointers, depth, flags,
+                                                        _u32x3(origin), _u32x3(dims), out_ptr, _u64x3(out_strides)), "o2v_hip_octree_dag_to_dense")
+
+    def octree_dag_times(self):
+        """o2v_hip_octree_dag_times: the device times (ms) of the last octree_dag_build's merge of the last level, merge of the levels
+        above and output, and of the last octree_dag_write."""
+        return self._stage_times("o2v_hip_octree_dag_times", 4)
 
     def openness(self, grid_ptr, fmt, strides, dims, level, directions, target_mode, target_ptr, target_strides, max_distance2, dst_ptr, dst_strides,
                  mask_ptr=None, mask_strides=None, flags=0):

@@ -174,6 +174,145 @@ def octree_to_dense(dv, tree, shape, *, origin=(0, 0, 0), out=None):
     return out
 
 
+@dataclasses.dataclass(frozen=True)
+class OctreeDag:
+    """What octree_dag returns (the definition: include/o2v_hip.h): an Octree whose equal subtrees are stored once.  DAG node i is a
+    class of tree nodes of the level l with level_offsets[l] <= i < level_offsets[l + 1], the classes of a level in the order of
+    their first member; the root is node 0."""
+    valid: torch.Tensor            # uint8 [M]
+    full: torch.Tensor             # uint8 [M]
+    first_child: torch.Tensor      # int32 [M]: the node's first entry in child and skip; -1 at level depth - 1 and without stored children
+    child: torch.Tensor            # int32 [P]: the DAG node of each stored child, node by node, within a node in octant order
+    skip: object                   # int32 [P]: the listed voxels under the node's stored children before this one, or None
+    level_offsets: tuple           # depth + 1 Python ints
+    depth: int
+    collapsed: bool
+    voxels_listed: int             # the tree's: the length of a per-voxel attribute array, which the DAG's voxel_index addresses
+    tree_nodes: int                # the nodes of the tree it was made of
+
+    @property
+    def nbytes(self):
+        """the bytes of its arrays: 6 per node, 4 or 8 per pointer"""
+        return sum(t.numel() * t.element_size() for t in (self.valid, self.full, self.first_child, self.child, self.skip) if t is not None)
+
+
+def octree_dag(dv, tree, skips=True):
+    """The sparse voxel DAG of an Octree: its equal subtrees merged on the voxelizer's device, level by level from the bottom
+    (DESIGN.md section 34): an OctreeDag.  Two nodes of a level are equal if their valid masks, their full masks and their stored
+    children are; a class is numbered by its first member.  Integers only; one run equals another bit for bit.
+
+        tree = dense.build_octree(dv, labels, collapse=False)
+        dag = dense.octree_dag(dv, tree)                              # dag.nbytes against 6 * len(tree.valid)
+        hit = dense.dag_lookup(dv, dag, points)                       # columns 0, 1, 3 == dense.octree_lookup(dv, tree, points)
+        argb[hit[:, 3].long()]                                        # an attribute array made for the tree works unchanged
+
+    skips:  keep per child pointer the listed voxels under the earlier siblings, which is what dag_lookup makes voxel_index of;
+            False: 4 bytes per pointer less, and voxel_index is -1."""
+    from . import dense
+    device, tree_args = _tree_args(dv, tree)
+    _flag(skips, "skips")
+    offs = tree.level_offsets
+    if (not isinstance(offs, tuple) or len(offs) != tree.depth + 1 or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in offs)
+            or offs[0] != 0 or any(b < a for a, b in zip(offs, offs[1:])) or offs[1] != 1 or offs[-1] != tree_args[3]):
+        raise ValueError(f"tree.level_offsets must be {tree.depth + 1} rising integers from 0 through 1 to the tree's {tree_args[3]} nodes, not {offs!r}")
+    dense._sync(device)   # (the caller's writes to the tree have landed)
+    counts, nodes, pointers = dv.octree_dag_build(*tree_args, [b - a for a, b in zip(offs, offs[1:])])
+    valid = torch.empty(nodes, dtype=torch.uint8, device=device)
+    full = torch.empty(nodes, dtype=torch.uint8, device=device)
+    first_child = torch.empty(nodes, dtype=torch.int32, device=device)
+    child = torch.empty(pointers, dtype=torch.int32, device=device)
+    skip = torch.empty(pointers, dtype=torch.int32, device=device) if skips else None
+    dv.octree_dag_write(valid.data_ptr(), full.data_ptr(), first_child.data_ptr(), child.data_ptr() if pointers else None,
+                        skip.data_ptr() if skips and pointers else None)
+    offsets = [0]
+    for c in counts:
+        offsets.append(offsets[-1] + int(c))
+    return OctreeDag(valid=valid, full=full, first_child=first_child, child=child, skip=skip, level_offsets=tuple(offsets), depth=int(tree.depth),
+                     collapsed=bool(tree.collapsed), voxels_listed=int(tree.voxels_listed), tree_nodes=int(tree_args[3]))
+
+
+def _dag_args(dv, dag):
+    """(device, (valid_ptr, full_ptr, first_child_ptr, child_ptr), skip_ptr, (n_nodes, n_pointers, depth, flags)) of an OctreeDag, checked."""
+    from . import dense
+    dense._require_shared_runtime()
+    device = dense._device(dv)
+    if not isinstance(dag, OctreeDag):
+        raise TypeError("dag must be an OctreeDag, what octree_dag returns")
+    if isinstance(dag.depth, bool) or not isinstance(dag.depth, numbers.Integral) or not 1 <= dag.depth <= MAX_OCTREE_DEPTH:
+        raise ValueError(f"dag.depth must be 1 ... {MAX_OCTREE_DEPTH}, not {dag.depth!r}")
+    lengths = {}
+    for name, dtype, group in (("valid", torch.uint8, "n"), ("full", torch.uint8, "n"), ("first_child", torch.int32, "n"), ("child", torch.int32, "p"),
+                               ("skip", torch.int32, "p")):
+        t = getattr(dag, name)
+        if name == "skip" and t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != dtype or not t.is_contiguous():
+            raise TypeError(f"dag.{name} must be a contiguous 1-D {dtype} tensor" + (" or None" if name == "skip" else ""))
+        if t.device != device:
+            raise ValueError(f"dag.{name} is on {t.device}, the voxelizer on {device}")
+        if lengths.setdefault(group, t.shape[0]) != t.shape[0]:
+            raise ValueError("dag.valid, dag.full and dag.first_child must have one length, dag.child and dag.skip another")
+    if lengths["n"] == 0:
+        raise ValueError("the DAG has no nodes: a DAG has its root")
+    p = lengths["p"]
+    return (device, (dag.valid.data_ptr(), dag.full.data_ptr(), dag.first_child.data_ptr(), dag.child.data_ptr() if p else None),
+            dag.skip.data_ptr() if dag.skip is not None and p else None,
+            (lengths["n"], p, int(dag.depth), hip.OCT_COLLAPSE if _flag(dag.collapsed, "dag.collapsed") else 0))
+
+
+def dag_lookup(dv, dag, points):
+    """The descent through an OctreeDag for every point, on the voxelizer's device: int32 [..., 4] = (solid,
+    level, node, voxel_index) for int32 points [..., 3] = (x, y, z) in global coordinates, negative ones allowed.
+
+    solid, level and voxel_index are those of octree_lookup on the tree the DAG was made of; node is the DAG node, the class of the
+    tree node.  voxel_index is -1 throughout for a DAG without skips (but a DAG of a root alone has nothing to skip).  Arrays that point outside themselves give (0, -2, -1, -1)
+    there and nothing is read outside them."""
+    from . import dense
+    device, arrays, skip, rest = _dag_args(dv, dag)
+    if not isinstance(points, torch.Tensor) or points.dim() < 1 or points.shape[-1] != 3:
+        raise ValueError("points must be a tensor [..., 3] of (x, y, z)")
+    if points.dtype != torch.int32:
+        raise TypeError(f"points must be int32, not {points.dtype}")
+    if points.device != device:
+        raise ValueError(f"points is on {points.device}, the voxelizer on {device}")
+    n = points.numel() // 3
+    if n > MAX_OCTREE_POINTS:
+        raise ValueError(f"{n} points are more than {MAX_OCTREE_POINTS} in one call")
+    flat = points.reshape(-1, 3).contiguous()
+    out = torch.empty((n, 4), dtype=torch.int32, device=device)
+    dense._sync(device)   # (the caller's writes to the DAG and the points have landed)
+    if n:
+        dv.octree_dag_lookup(*arrays, skip, *rest, flat.data_ptr(), n, out.data_ptr())
+    return out.reshape(points.shape[:-1] + (4,))
+
+
+def dag_to_dense(dv, dag, shape, *, origin=(0, 0, 0), out=None):
+    """An OctreeDag back as a dense grid on the voxelizer's device: a bool tensor of `shape` (nz, ny, nx),
+    True where the DAG is solid, for the box whose voxel (0, 0, 0) is `origin` (x, y, z) of the global lattice - any box: the part
+    outside the root cube is False.  It equals octree_to_dense of the tree the DAG was made of.
+
+    out:  a bool or uint8 tensor of that shape (any strides that keep the voxels apart) to write 1 / 0 into; it is returned."""
+    from . import dense
+    device, arrays, _, rest = _dag_args(dv, dag)
+    origin = dense._origin(origin)
+    shape = tuple(int(n) for n in shape)
+    if len(shape) != 3 or any(n < 1 for n in shape):
+        raise ValueError(f"shape {shape} must be three positive extents (nz, ny, nx)")
+    dims = shape[::-1]
+    dense._limit_voxels(dims)
+    if any(o + n > 2 ** 32 for o, n in zip(origin, dims)):
+        raise ValueError(f"origin {origin} + the extent {dims} [x, y, z] is above 2^32")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.bool, device=device)
+    else:
+        if isinstance(out, torch.Tensor) and out.dtype not in (torch.bool, torch.uint8):
+            raise TypeError(f"out must be bool or uint8, not {out.dtype}")
+        dense._check_grid(out, "out", out.dtype if isinstance(out, torch.Tensor) else torch.bool, device, shape)
+    dense._sync(device)   # (the caller's writes to the DAG have landed, its reads of out are done)
+    dv.octree_dag_to_dense(*arrays, *rest, origin, dims, out.data_ptr(), dense._strides(out))
+    return out
+
+
 def octree_level(tree, l):   # noqa: E741
     """(valid, full, first_child, coords or None) of the nodes of level l of an Octree, 0 <= l < depth: views, in Morton order.
     (valid != 0) scattered to coords >> (depth - l - 1) is the occupancy at 1 / 2^(depth - l - 1).  Plain torch."""

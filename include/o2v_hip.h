@@ -1418,6 +1418,48 @@ int o2v_hip_octree_dag_to_dense(o2v_hip_ctx *ctx, const uint8_t *valid, const ui
 int o2v_hip_octree_dag_times(const o2v_hip_ctx *ctx, float out_ms[4]);
 uint64_t o2v_hip_octree_dag_scratch_bytes(const uint64_t level_counts[16], uint32_t depth);
 
+/* ---- Rays through sparse voxel octrees and DAGs ------------------------------------------------------------
+ *
+ * The first solid voxel along each ray, found in the tree or the DAG itself: nothing is expanded, nothing is kept in the context.
+ * Defined so that a numpy restatement (tests/treeray_ref.py) reproduces every bit, and so that for any arrays at all
+ *   o2v_hip_octree_raycast(arrays) == o2v_hip_raycast_build(o2v_hip_octree_to_dense(arrays)) + o2v_hip_raycast.
+ *
+ * Space.  Voxel space and rays are those of o2v_hip_raycast: a ray is six float32 widened to double; the plane i of axis a is
+ * crossed at T_a(i) = ((double) i - o_a) * (1.0 / d_a), computed per plane, without FMA; the walk starts in floor(o) with t = 0 and
+ * face -1; of planes with equal T the lowest axis is crossed first; a ray misses when the next T > t_max.  An invalid ray (a
+ * component that is not finite, |o_a| above 2^22) gives (-1, -1, -1, -2) and NaN, a miss (-1, -1, -1, -1) and +inf; d = 0 tests the
+ * start cell only.
+ *
+ * Solid set.  The voxels for which the descent of o2v_hip_octree_lookup (tree) or o2v_hip_octree_dag_lookup (DAG) says solid.  The
+ * root cube [0, 2^D)^3 sits on the global lattice and everything outside it is empty; there is no origin argument.
+ *
+ * Corrupt arrays.  A step that the descent calls corrupt - a child or pointer index outside the arrays, a -1 where a child is
+ * needed - makes that octant empty, which is what o2v_hip_octree_to_dense and o2v_hip_octree_dag_to_dense do.  Nothing is read
+ * outside the n_nodes / n_pointers entries; a descent takes at most D steps, cyclic pointers included; every event moves the ray
+ * strictly forward in (T, axis), so the walk ends.
+ *
+ * Outputs.  hit int32 [n][4] = (x, y, z, face), t float32 [n] as o2v_hip_raycast writes them; voxel_index int32 [n] (may be null):
+ * column 3 of o2v_hip_octree_lookup / o2v_hip_octree_dag_lookup at the hit cell, so -1 for a miss, an invalid ray, a hit inside a
+ * full cell of a collapsed tree, or a DAG passed without skip.
+ *
+ * flags: O2V_HIP_OCT_COLLAPSE or 0.  No scratch and no snapshot: the caller's arrays are walked in place.  O2V_TREERAY_NO_STACK=1 in
+ * the environment makes every event descend again from the root instead of from the deepest common ancestor of the old and the new
+ * cell (an A/B switch: the results are the same).
+ *
+ * O2V_HIP_ERR_BAD_ARGUMENT: a null argument (voxel_index and skip may be null, child too where n_pointers is 0), unknown flag
+ * bits, depth outside 1 ... 16, n_nodes = 0, t_max NaN or negative, int32 / float arrays that are not 4-byte aligned, outputs that
+ * overlap each other, the rays or the tree, a pointer that is not device memory of the context's device with its whole extent
+ * inside its allocation.  O2V_HIP_ERR_LIMIT: n_nodes, n_pointers or n above 2^31 - 1.  All of these come before any launch and
+ * leave the outputs untouched.  n = 0 succeeds and writes nothing. */
+int o2v_hip_octree_raycast(o2v_hip_ctx *ctx, const uint8_t *valid, const uint8_t *full, const int32_t *first_child, uint64_t n_nodes, uint32_t depth,
+                           uint32_t flags, const float *origins, const float *directions, uint64_t n, float t_max, int32_t *hit, float *t,
+                           int32_t *voxel_index);
+int o2v_hip_octree_dag_raycast(o2v_hip_ctx *ctx, const uint8_t *valid, const uint8_t *full, const int32_t *first_child, const int32_t *child,
+                               const int32_t *skip, uint64_t n_nodes, uint64_t n_pointers, uint32_t depth, uint32_t flags, const float *origins,
+                               const float *directions, uint64_t n, float t_max, int32_t *hit, float *t, int32_t *voxel_index);
+/* The device time (ms) of the last cast of either kind, from events around it. */
+int o2v_hip_octree_raycast_times(const o2v_hip_ctx *ctx, float out_ms[1]);
+
 /* ---- Sky visibility and ambient occlusion of dense grids --------------------------------------------------
  *
  * Per target voxel, in how many of D integer directions a ray from its centre gets out: the quantity ambient occlusion is baked

@@ -130,6 +130,7 @@ namespace {
 #include "o2v_dev_k17_downsample.hpp"
 #include "o2v_dev_k26_octree.hpp"      // (behind K12 and K6: the bit grid, the classify kernel, the block scan)
 #include "o2v_dev_k30_dag.hpp"         // (behind K26: its octants, ranks and stored masks, its box of 2^3 blocks)
+#include "o2v_dev_k31_treeray.hpp"     // (behind K11, K26 and K30: K11's ray and its advance, the steps of the two descents)
 #include "o2v_dev_k27_openness.hpp"    // (behind K11: it walks the masks that k_ray_build makes)
 #include "o2v_dev_k18_crossings.hpp"
 #include "o2v_dev_k19_label_stats.hpp"
@@ -273,6 +274,7 @@ struct Switches {
     bool no_slabs = env_on("O2V_NO_SLABS");                    // A/B: no new hit slabs, every hit pooled
     bool ray_no_skip = env_on("O2V_RAY_NO_SKIP");              // A/B: k_ray_cast walks every fine cell, no empty block is skipped
     bool open_no_skip = env_on("O2V_OPEN_NO_SKIP");            // A/B: k_open_walk walks every fine cell, no empty block is skipped
+    bool treeray_no_stack = env_on("O2V_TREERAY_NO_STACK");    // A/B: k_tree_cast keeps no ancestors in LDS, every event descends again from the root
     bool cc_no_tiles = env_on("O2V_CC_NO_TILES");              // A/B: no k_cc_tiles, every adjacent pair is united in global memory
     bool cross_no_tile = env_on("O2V_CROSS_NO_TILE");          // A/B: no k_cross_prefix_tile, a lane per line stores along the ray
     bool ls_no_table = env_on("O2V_LS_NO_TABLE");              // A/B: k_label_stats without its table in LDS, every run to global memory
@@ -609,6 +611,8 @@ struct o2v_hip_ctx {
         bool valid = false;
         uint64_t nodes = 0, pointers = 0;
     } dag;
+    // K31 (o2v_hip_octree_raycast / o2v_hip_octree_dag_raycast): no scratch - the caller's arrays are walked in place; the time of the last cast
+    StageTimes<1> treeray_times;
     // K27 (o2v_hip_openness): the three levels of masks of its own (a RayCaster's snapshot is not touched), the counters (targets
     // counted, targets listed), the direction table (nine words per direction) on both sides, the list of the targets' linear
     // indices - grown with the data; the times of build, targets and walk
@@ -2667,6 +2671,7 @@ int o2v_hip_voxels_device_ptr(o2v_hip_ctx *ctx, const uint32_t **out_ptr, uint64
 #include "o2v_dev_host_k17_downsample.hpp"
 #include "o2v_dev_host_k26_octree.hpp"
 #include "o2v_dev_host_k30_dag.hpp"
+#include "o2v_dev_host_k31_treeray.hpp"
 #include "o2v_dev_host_k27_openness.hpp"
 #include "o2v_dev_host_k19_label_stats.hpp"
 #include "o2v_dev_host_k21_thickness.hpp"

@@ -49,7 +49,8 @@ grid into one smooth mesh of all its interfaces - the wall between two parts mes
 part_mesh cuts one part's closed mesh out of it and interface_areas measures the walls (o2v_hip_label_surface_count / _write /
 _relax); octree_dag merges the equal subtrees of an Octree into a sparse voxel DAG that keeps every voxel's
 slot, dag_lookup descends it per point and dag_to_dense expands it (o2v_hip_octree_dag_build / _write / _lookup / _to_dense,
-DESIGN.md section 34).
+DESIGN.md section 34); octree_raycast and dag_raycast find the first solid voxel along rays in the tree or the DAG itself, and its
+slot, without expanding either (o2v_hip_octree_raycast / o2v_hip_octree_dag_raycast).
 
 torch is imported first on purpose: the library must bind to the HIP runtime torch loaded (a process that loaded the library
 before torch holds two separate runtime copies, and this module refuses to work there).
@@ -1071,6 +1072,8 @@ from .octree import (Octree, build_octree, octree_depth, octree_level, octree_lo
                      octree_to_dense)   # (the torch layer of o2v_hip_octree_build / _write / _lookup / _to_dense)
 # ---- sparse voxel DAGs: equal subtrees of an octree merged ----------------------------------------------------
 from .octree import OctreeDag, dag_lookup, dag_to_dense, octree_dag  # noqa: E402,F401   (o2v_hip_octree_dag_build / _write / _lookup / _to_dense)
+# ---- rays through octrees and DAGs ---------------------------------------------------------------------------
+from .octree import dag_raycast, octree_raycast  # noqa: E402,F401   (o2v_hip_octree_raycast / o2v_hip_octree_dag_raycast)
 
 # ---- sky visibility and ambient occlusion -------------------------------------------------------------------
 

@@ -268,6 +268,11 @@ def _bind():
     L.o2v_hip_octree_dag_times.argtypes = [C.c_void_p, C.c_void_p]
     L.o2v_hip_octree_dag_scratch_bytes.argtypes = [C.c_void_p, C.c_uint32]
     L.o2v_hip_octree_dag_scratch_bytes.restype = C.c_uint64
+    # ... origins, directions, n, t_max, hit, t, voxel_index
+    _rays = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.o2v_hip_octree_raycast.argtypes = _tree + _rays
+    L.o2v_hip_octree_dag_raycast.argtypes = [C.c_void_p] * 6 + [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32] + _rays
+    L.o2v_hip_octree_raycast_times.argtypes = [C.c_void_p, C.c_void_p]
     # ctx, grid, format, strides, dims, level, directions, n_directions, target_mode, target_grid, target_strides, max_distance2, flags,
     # dst, dst_strides, mask, mask_strides, out_targets
     L.o2v_hip_openness.argtypes = _gather + [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
@@ -1067,6 +1072,26 @@ class DeviceVoxelizer:
         """o2v_hip_octree_dag_times: the device times (ms) of the last octree_dag_build's merge of the last level, merge of the levels
         above and output, and of the last octree_dag_write."""
         return self._stage_times("o2v_hip_octree_dag_times", 4)
+
+    def octree_raycast(self, valid_ptr, full_ptr, first_child_ptr, n_nodes, depth, flags, origins_ptr, directions_ptr, n, t_max, hit_ptr, t_ptr,
+                       voxel_index_ptr=None):
+        """o2v_hip_octree_raycast: n rays (float32 [n, 3] origins and directions at device addresses) through the tree in the
+        caller's device arrays, into int32 hit [n, 4] = (x, y, z, face), float32 t [n] and, unless None, int32 voxel_index [n]; a
+        miss is (-1, -1, -1, -1), +inf, -1."""
+        self._check(self._L.o2v_hip_octree_raycast(self._ctx, valid_ptr, full_ptr, first_child_ptr, n_nodes, depth, flags, origins_ptr, directions_ptr, n,
+                                                   float(t_max), hit_ptr, t_ptr, voxel_index_ptr), "o2v_hip_octree_raycast")
+
+    def octree_dag_raycast(self, valid_ptr, full_ptr, first_child_ptr, child_ptr, skip_ptr, n_nodes, n_pointers, depth, flags, origins_ptr, directions_ptr, n,
+                           t_max, hit_ptr, t_ptr, voxel_index_ptr=None):
+        """o2v_hip_octree_dag_raycast: the same through the DAG in the caller's device arrays; voxel_index is -1 where skip_ptr is
+        None."""
+        self._check(self._L.o2v_hip_octree_dag_raycast(self._ctx, valid_ptr, full_ptr, first_child_ptr, child_ptr, skip_ptr, n_nodes, n_pointers, depth, flags,
+                                                       origins_ptr, directions_ptr, n, float(t_max), hit_ptr, t_ptr, voxel_index_ptr),
+                    "o2v_hip_octree_dag_raycast")
+
+    def octree_raycast_times(self):
+        """o2v_hip_octree_raycast_times: the device time (ms) of the last octree_raycast or octree_dag_raycast."""
+        return self._stage_times("o2v_hip_octree_raycast_times", 1)
 
     def openness(self, grid_ptr, fmt, strides, dims, level, directions, target_mode, target_ptr, target_strides, max_distance2, dst_ptr, dst_strides,
                  mask_ptr=None, mask_strides=None, flags=0):

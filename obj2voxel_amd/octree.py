@@ -1,6 +1,7 @@
 """Sparse voxel octrees of dense grids on the voxelizer's device (o2v_hip_octree_build / _write / _lookup / _to_dense, DESIGN.md
 section 30): the torch layer, which obj2voxel_amd.dense re-exports as dense.Octree, dense.build_octree, dense.octree_lookup,
-dense.octree_to_dense, dense.octree_level and dense.octree_depth.  It waits on the voxelizer's device (dense._sync) before every
+dense.octree_to_dense, dense.octree_level and dense.octree_depth; the DAG of section 34 (OctreeDag, octree_dag, dag_lookup,
+dag_to_dense) and the rays of section 35 (octree_raycast, dag_raycast) are here too.  It waits on the voxelizer's device (dense._sync) before every
 library call, as every function of dense.py does; tests/test_host_octree.py holds that wait.
 
 torch is imported first on purpose (see obj2voxel_amd/dense.py)."""
@@ -311,6 +312,70 @@ def dag_to_dense(dv, dag, shape, *, origin=(0, 0, 0), out=None):
     dense._sync(device)   # (the caller's writes to the DAG have landed, its reads of out are done)
     dv.octree_dag_to_dense(*arrays, *rest, origin, dims, out.data_ptr(), dense._strides(out))
     return out
+
+
+def _ray_args(device, origins, directions, t_max, voxel_index):
+    """(shape, origins [n, 3], directions [n, 3], n, t_max) of the rays of a cast, checked as RayCaster.cast checks them."""
+    if isinstance(t_max, bool) or not isinstance(t_max, numbers.Real) or not float(t_max) >= 0.0:
+        raise ValueError(f"t_max must be a number >= 0 or inf, not {t_max!r}")
+    _flag(voxel_index, "voxel_index")
+    for name, r in (("origins", origins), ("directions", directions)):
+        if not isinstance(r, torch.Tensor):
+            raise TypeError(f"{name} must be a torch tensor")
+        if r.dtype != torch.float32:
+            raise TypeError(f"{name} must be torch.float32, not {r.dtype}")
+        if r.dim() < 1 or r.shape[-1] != 3:
+            raise ValueError(f"{name} must have shape [..., 3], not {tuple(r.shape)}")
+        if r.device != device:
+            raise ValueError(f"{name} is on {r.device}, the voxelizer on {device}")
+    if origins.shape != directions.shape:
+        raise ValueError(f"origins {tuple(origins.shape)} and directions {tuple(directions.shape)} must have one shape")
+    n = origins.numel() // 3
+    if n > MAX_OCTREE_POINTS:
+        raise ValueError(f"{n} rays are more than {MAX_OCTREE_POINTS} in one call")
+    return tuple(origins.shape[:-1]), origins.reshape(-1, 3).contiguous(), directions.reshape(-1, 3).contiguous(), n, float(t_max)
+
+
+def _cast(device, call, origins, directions, t_max, voxel_index):
+    """The outputs of a cast around call(origins_ptr, directions_ptr, n, t_max, hit_ptr, t_ptr, voxel_index_ptr)."""
+    from . import dense
+    shape, o, d, n, t_max = _ray_args(device, origins, directions, t_max, voxel_index)
+    hit = torch.empty((n, 4), dtype=torch.int32, device=device)
+    t = torch.empty((n,), dtype=torch.float32, device=device)
+    slot = torch.empty((n,), dtype=torch.int32, device=device) if voxel_index else None
+    dense._sync(device)   # (the caller's writes to the arrays and the rays have landed)
+    if n:
+        call(o.data_ptr(), d.data_ptr(), n, t_max, hit.data_ptr(), t.data_ptr(), None if slot is None else slot.data_ptr())
+    out = (hit.reshape(shape + (4,)), t.reshape(shape))
+    return out + (slot.reshape(shape),) if voxel_index else out
+
+
+def octree_raycast(dv, tree, origins, directions, *, t_max=float("inf"), voxel_index=False):
+    """The first solid voxel along rays through an Octree, found in the tree itself on the voxelizer's device (DESIGN.md
+    section 35): (hit, t), bit for bit what RayCaster(dv, octree_to_dense(dv, tree, ...)).cast(origins, directions, t_max) gives -
+    nothing is expanded and nothing is kept.
+
+        hit, depth = dense.octree_raycast(dv, tree, *dense.camera_rays(640, 480, eye, target, up, 40.0, device))
+
+    origins, directions, t_max, hit, t:  as RayCaster.cast takes and gives them; voxel space is the tree's global lattice, the
+                  root cube [0, 2^depth)^3, and everything outside it is empty.
+    voxel_index:  True: (hit, t, slot) with slot int32 [...], column 3 of octree_lookup at the hit voxel - its place in a per-voxel
+                  attribute array - and -1 for a miss, an invalid ray and a hit inside a full cell of a collapsed tree.
+    A tree whose first_child points outside its arrays is empty there, as in octree_to_dense; nothing is read outside them."""
+    device, tree_args = _tree_args(dv, tree)
+    return _cast(device, lambda *rays: dv.octree_raycast(*tree_args, *rays), origins, directions, t_max, voxel_index)
+
+
+def dag_raycast(dv, dag, origins, directions, *, t_max=float("inf"), voxel_index=False):
+    """octree_raycast through an OctreeDag: the same (hit, t) as through the tree it was made of.  The
+    skips are added on the way down, so the slot of the hit voxel comes with the hit:
+
+        hit, depth, slot = dense.dag_raycast(dv, dag, origins, directions, voxel_index=True)
+        image = argb[slot.clamp(min=0).long()].where(slot >= 0, background)     # argb: made for the tree (build_octree's example)
+
+    slot is -1 throughout for a DAG without skips (but a DAG of a root alone has nothing to skip)."""
+    device, arrays, skip, rest = _dag_args(dv, dag)
+    return _cast(device, lambda *rays: dv.octree_dag_raycast(*arrays, skip, *rest, *rays), origins, directions, t_max, voxel_index)
 
 
 def octree_level(tree, l):   # noqa: E741

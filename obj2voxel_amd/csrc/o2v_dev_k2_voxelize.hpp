@@ -235,17 +235,52 @@ __device__ __forceinline__ Piece<UV> stack_load(const PieceStack<UV> &st, uint32
 // never separates), and all comparisons are written so that a NaN rejects nothing.  Not reference arithmetic.
 // For leaves far from the origin the clip's own rounding grows with the coordinates - a vertex of a sub-piece drifts by up to
 // 1.2e-6 x the largest |coordinate| m over the five generations (see piece_masks) - so the inflation does too:
-// sat_margin(m) = max(0.02, 2.5e-6 m), twice that drift (0.02 up to m = 8000, 0.16 at m = 65536).
-constexpr float kSatMargin = 0.02f;
+// sat_margin(m) = max(kSatMargin, 2.5e-6 m), twice that drift (0.16 at m = 65536).
+//
+// The error budget of the floor kSatMargin = F.  It is the margin of every leaf with m <= F / 2.5e-6 (the proportional term
+// takes over there, so the floor never protects a larger m).  Every pair inside the inflated voxel but outside the voxel
+// itself becomes a voxel job that the clip then rejects, so the floor is work, not only safety.  It has to cover, in voxels:
+//   drift of the clip's vertices      1.2e-6 m <= 0.48 F at the largest m it applies to (the proportional rule's factor 2)
+//   the 2^-16 planarity band          1.53e-5
+//   the projections' rounding         each projection is a difference of two products of an edge component and an offset in
+//                                     the leaf's frame: <= 3 roundings of 2^-24 on terms of |E| x (the leaf's extent along one
+//                                     axis), i.e. 1.8e-7 x extent in units of the radius' |E|.  Coordinates lie in [-m, m], so
+//                                     an axis extent is <= 2 m, for the largest axis-aligned leaf too: 3.6e-7 m <= 0.15 F
+//   v_rcp's ulp and the division      relative 1.2e-7 of the bound: covered by row_span's `slack`, not by F
+// together <= 0.63 F + 1.53e-5.  The floors compared (profiles/r09/NOTES.md):
+//   F = 0.02    m <= 8000: 1.26e-2 + 1.5e-5      covered 1.6 times at m = 8000, 15 times at m = 1024
+//   F = 0.01    m <= 4000: 6.3e-3 + 1.5e-5       covered 1.6 times at m = 4000, 7 times at m = 1024
+//   F = 0.005   m <= 2000: 3.2e-3 + 1.5e-5       covered 1.6 times at m = 2000, 3.7 times at m = 1024
+// The factor at the hand-over is that of the proportional term, which is all that protects m > F / 2.5e-6 at any floor
+// (tests/test_gpu_fuzz.py::test_far_corner_case); no shape needs a floor of its own, since the extent of a leaf is bounded by
+// 2 m whatever its shape.  Below 0.005 (330 planarity bands) the floor is not to be set.
+// Kept: 0.01 with D = 0.0075 - on the bench mesh within noise of the fastest pair measured (0.005, 0.0075), and the larger
+// floor stays where the budget's factor is the smaller one (1.6 here against 3.1 for D).
+#ifndef O2V_SAT_FLOOR
+#define O2V_SAT_FLOOR 0.01f
+#endif
+constexpr float kSatMargin = O2V_SAT_FLOOR;
+static_assert(kSatMargin >= 0.005f, "the row test's inflation floor is below its error budget");
 __device__ __forceinline__ float sat_margin(float m) { return fmaxf(kSatMargin, 2.5e-6f * m); }
 
 // The test is solved for x: for one row of candidate voxels (fixed y and z of the leaf's clamped AABB) every axis is a
 // linear function of the voxel centre's x, so it bounds x to an interval; the row's candidates are the voxels whose centre
 // lies in the intersection of the intervals.  Evaluated in the leaf's own frame (origin = the AABB's first voxel, so all
 // magnitudes are extents, not positions).  The box is inflated by kSatMargin in projection space, which covers the
-// rounding of the projections (a few 1e-7 of extent x edge length against 0.02 x edge length); the division by the axis'
-// x component adds a relative 1e-7, covered by `slack` voxels on either side.  An axis whose x component (nearly)
-// vanishes is not used (the x x edge axes, which do not depend on x at all, reject whole rows).
+// rounding of the projections (a few 1e-7 of extent x edge length against kSatMargin x edge length: the budget above);
+// the division by the axis' x component adds a relative 1e-7, covered by `slack` voxels on either side.  An axis whose
+// x component (nearly) vanishes is not used (the x x edge axes, which do not depend on x at all, reject whole rows).
+//
+// slack = kRowSlack + 4e-6 x extent voxels.  A bound x0 = b / a is a voxel centre in the leaf's frame, |x0| <= extent where it
+// matters (the row is clamped to the AABB), and carries the rcp's ulp, the product's rounding and those of the +- slack
+// and - 0.5 that follow: < 4 x 2^-23 relative, 4.8e-7 x extent - an eighth of the proportional part.  The constant part has
+// only the absolute remainder to cover (the rounding of an |x0| below one voxel, < 1e-7) and otherwise widens the inflation
+// along x, where every voxel it admits is a rejected job; 0.002 is its lower limit, 2e4 times that remainder.
+#ifndef O2V_ROW_SLACK
+#define O2V_ROW_SLACK 0.005f
+#endif
+constexpr float kRowSlack = O2V_ROW_SLACK;
+static_assert(kRowSlack >= 0.002f, "the constant part of row_span's x slack is below its lower limit");
 struct RowClip {
     float lo, hi;  // interval of admissible voxel centres (x, leaf frame)
     bool any;
@@ -287,7 +322,7 @@ __device__ __forceinline__ uint32_t row_span(V3 p0, V3 p1, V3 p2, float cy, floa
                                              float margin, uint32_t &first)
 {
     const float h = 0.5f + margin;  // margin = sat_margin(the leaf's largest |coordinate|)
-    const float slack = 0.01f + 4e-6f * extent;
+    const float slack = kRowSlack + 4e-6f * extent;
     RowClip rc{(float) xlo + 0.5f, (float) xhi + 0.5f, true};
     const V3 e0 = p1 - p0, e1 = p2 - p1, e2 = p0 - p2;
     {
@@ -409,28 +444,49 @@ __device__ __forceinline__ uint32_t single_plane_kept(const Piece<UV> &q, uint32
 // the exact intersection of leaf and voxel except for a band along its boundary no wider than the drift of their vertices
 // (< 1.2e-6 x the largest |coordinate| m over the five generations, see piece_masks) plus the 2^-16 planarity band (a vertex
 // that close to a plane counts as on it; a piece with two such vertices goes to the third one's side: both move the boundary
-// by < 2^-16).  With D = rho = certain_margin(m) = 1.5 sat_margin(m) >= 0.03 that band is thirty times narrower than the
-// margins.  The point tried is the one the voxel centre's column along the normal's dominant axis d meets the leaf's plane
-// in: q = centre - t e_d, t = n . (centre - v0) / n_d.  It lies in the voxel by 0.5 in the two other axes and by 0.5 - |t| in
-// d; its barycentric coordinates - computed in the projection along d, which preserves them - say how far inside the leaf it
-// is: lambda_i x (altitude on vertex i) is its distance from the edge opposite i.  So the test is
+// by < 2^-16).  D = rho = certain_margin(m) = max(kCertainMargin, 3.75e-6 m): three times the drift, with a floor of its
+// own (budget below).  The point tried is the one the voxel centre's column along the normal's dominant axis d meets the
+// leaf's plane in: q = centre - t e_d, t = n . (centre - v0) / n_d.  It lies in the voxel by 0.5 in the two other axes and by
+// 0.5 - |t| in d; its barycentric coordinates - computed in the projection along d, which preserves them - say how far inside
+// the leaf it is: lambda_i x (altitude on vertex i) is its distance from the edge opposite i.  So the test is
 //     |t| <= 0.5 - D   and   lambda_0, lambda_1, lambda_2 >= tau = rho / (smallest altitude) + 1e-4
-// and it is tried not only for the centre's column but for every column through five lines across the voxel (spaced 0.22
-// or less in one of the two other axes, any offset within 0.5 - D along the other: along a line all conditions are linear
-// inequalities in the offset, which leave an interval), so that q stays inside the voxel by >= D in those axes too.  Some 150
-// instructions per candidate, all lanes busy, against a voxel job's ~4000 on partly idle lanes.  A sliver has tau > 1/3 and is never certain; a
-// degenerate or non-finite leaf is excluded outright, as is a leaf of a triangle of zero area (its weight would be zero:
-// no hit, voxelization.cpp:466).  Not reference arithmetic: like the separating-axis test it only removes work, and the
-// fast-vs-exact comparison (tests/test_gpu_exact_ab.py) runs with it switched off on the exact side.
+// and it is tried not only for the centre's column but for every column through O2V_CERTAIN_N lines across the voxel
+// (O2V_CERTAIN_STEP apart in one of the two other axes and never farther than 0.5 - D from the centre, any offset within 0.5
+// - D along the other: along a line all conditions are linear inequalities in the offset, which leave an interval), so that q
+// stays inside the voxel by >= D in those axes too.  Three lines since the floors of the margins came down
+// (profiles/r09/NOTES.md: five lines find 3 % more certain hits and cost more than the jobs they save; at D = 0.03 the two
+// took the same time, profiles/r05/NOTES.md).  Some 100 instructions per candidate (an estimate: the five-line form was
+// counted at some 150 and a line is about 25 of them), all lanes busy, against a voxel job's ~4000 on partly idle lanes.  A
+// sliver has tau > 1/3 and is never certain; a degenerate or non-finite leaf is excluded outright, as is a leaf of a triangle
+// of zero area (its weight would be zero: no hit, voxelization.cpp:466).  Not reference arithmetic: like the separating-axis
+// test it only removes work, and the fast-vs-exact comparison (tests/test_gpu_exact_ab.py) runs with it switched off on the
+// exact side.
 #ifndef O2V_CERTAIN_N
-#define O2V_CERTAIN_N 5
-#define O2V_CERTAIN_STEP 0.22f
+#define O2V_CERTAIN_N 3
+#define O2V_CERTAIN_STEP 0.44f
 #endif
 struct CertainPrep {
     float m00, m01, m10, m11, tau;
     uint32_t axis;  // dominant axis of the normal; tau = +inf: the leaf has no certain hits
 };
-__device__ __forceinline__ float certain_margin(float m) { return 1.5f * sat_margin(m); }
+// The error budget of the floor kCertainMargin = D (for both D and rho; the margin of every leaf with m <= D / 3.75e-6).  A hit
+// that enters its voxel by less than D, or lies closer than rho to the leaf's edges, goes to the clip loop as a voxel job, so
+// this floor is work too.  What it has to cover is the band along the boundary of (leaf and voxel) that the float clip may lose:
+//   drift of the clip's vertices      1.2e-6 m <= 0.32 D at the largest m it applies to (the proportional rule's factor 3.1)
+//   the 2^-16 planarity band          1.53e-5
+// The test's own rounding is not in D: t, the lambdas and the interval ends are sums of a few products of O(1) quantities in the
+// leaf's frame times coordinates relative to v0 (a few 1e-7 of the leaf's extent in voxels), plus an ulp of v_rcp on each bound;
+// the 1e-3 in `lim`, the 1e-4 in tau and the 2e-3 the interval must be long absorb them and stay as they were.
+//   D = 0.03     m <= 8000: 9.6e-3 + 1.5e-5      covered 3.1 times at m = 8000, 24 times at m = 1024
+//   D = 0.015    m <= 4000: 4.8e-3 + 1.5e-5      covered 3.1 times at m = 4000, 12 times at m = 1024
+//   D = 0.0075   m <= 2000: 2.4e-3 + 1.5e-5      covered 3.1 times at m = 2000, 6 times at m = 1024
+// Below 0.0075 the floor is not to be set.  tests/test_gpu_margin_band.py places geometry on both sides of D and of kSatMargin.
+#ifndef O2V_CERTAIN_FLOOR
+#define O2V_CERTAIN_FLOOR 0.0075f
+#endif
+constexpr float kCertainMargin = O2V_CERTAIN_FLOOR;
+static_assert(kCertainMargin >= 0.0075f, "the certain-hit margin's floor is below its error budget");
+__device__ __forceinline__ float certain_margin(float m) { return fmaxf(kCertainMargin, 3.75e-6f * m); }
 __device__ __forceinline__ CertainPrep certain_prepare(V3 v0, V3 v1, V3 v2, V3 nrm, float m, bool small, float parent_area)
 {
     CertainPrep c{0.f, 0.f, 0.f, 0.f, __builtin_inff(), 0u};
@@ -885,13 +941,13 @@ __device__ __forceinline__ void voxelize_body(const Leaf *__restrict__ leaves, c
                     keep = !(abs_f(sd) > kPlaneDistanceLimit);
                     if (OCC && keep) {
                         // certain hit (see certain_prepare): no voxel job, the voxel is marked here.  Tried are the columns
-                        // through a 5 x 5 lattice of points around the voxel centre (every quantity of the test is linear in
+                        // through kN lines of points around the voxel centre (every quantity of the test is linear in
                         // the offset); the lattice stays inside the voxel by the margin D.
                         const uint32_t axis = lf[17];
                         const uint32_t iu = axis == 0u ? 1u : 0u, iw = axis == 2u ? 1u : 2u;
                         const float tau = __uint_as_float(lf[16]);
                         if (tau < 0.34f) {  // (else no point of the leaf is far enough from its edges)
-                            const float lim = 0.5f - (1.5f * sat_margin(s_mcoord[kk]) + 1e-3f);  // 0.5 - D, D = certain_margin(m)
+                            const float lim = 0.5f - (certain_margin(s_mcoord[kk]) + 1e-3f);  // 0.5 - D, D = certain_margin(m)
                             // kN lines across the voxel (constant offset in the second lattice axis); along a line every
                             // condition is a linear inequality in the offset o: they leave an interval, the point exists if it is
                             // not empty (by a slack that absorbs this code's own rounding)

@@ -174,6 +174,58 @@ static_assert(kGeoMaxDistance == O2V_HIP_GEO_MAX_DISTANCE && kGeoMaxWeight == O2
 
 uint64_t geo_tiles(const uint32_t dims[3]) { return bit_tiles(bit_grid(dims)); }
 
+// The worklist of a relaxation over tiles (k_geo_tiles, k_grow_tiles): of an array of [4][tiles] words the two alternating flag
+// words of every tile and the two lists; of the family's counter block three uint32 on the device and their page-locked copies:
+// the lengths of the two lists and the changed word of the whole-grid sweeps.
+struct TileRounds {
+    uint32_t *tile_flags[2], *tile_list[2];
+    uint32_t *cnt;
+    volatile uint32_t *h_cnt;
+};
+
+TileRounds tile_rounds(uint32_t *words, uint64_t tiles, unsigned long long *cnt, unsigned long long *h_cnt)
+{
+    return TileRounds{{words, words + tiles}, {words + 2u * tiles, words + 3u * tiles}, reinterpret_cast<uint32_t *>(cnt), reinterpret_cast<volatile uint32_t *>(h_cnt)};
+}
+
+struct RoundCounts {
+    uint64_t rounds, visits, reads;   // launches, listed tiles over all of them, 4-byte reads by the host
+};
+
+// The rounds of one relaxation, from round 0's list (or from nothing: the whole-grid sweeps) to its fixed point.  launch_tiles(cur,
+// nxt, n, blocks) enqueues the tile kernel over list cur of n tiles; launch_sweep(changed) one sweep over the whole grid
+// (O2V_*_NO_TILES).  No cap: a round is launched only if the last one moved a value on a tile's rim (tiles) or anywhere (sweeps),
+// and the values are whole numbers that move one way between fixed bounds.
+template <typename Tiles, typename Sweep>
+int run_tile_rounds(o2v_hip_ctx *ctx, const TileRounds &tr, bool use_tiles, Tiles &&launch_tiles, Sweep &&launch_sweep, RoundCounts *out)
+{
+    hipStream_t s = ctx->stream;
+    uint32_t *const h_cnt = const_cast<uint32_t *>(tr.h_cnt);
+    *out = RoundCounts{};
+    if (use_tiles) {
+        O2V_CHECK(hipMemcpyAsync(h_cnt, tr.cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        O2V_CHECK(hipStreamSynchronize(s));
+        ++out->reads;
+        for (uint32_t cur = 0, n = tr.h_cnt[0]; n; cur ^= 1u, n = tr.h_cnt[cur]) {
+            const uint32_t nxt = cur ^ 1u;
+            O2V_CHECK(hipMemsetAsync(tr.cnt + nxt, 0, sizeof(uint32_t), s));
+            launch_tiles(cur, nxt, n, dim3((uint32_t) std::min<uint64_t>(n, kCcMaxGrid)));
+            O2V_CHECK(hipMemcpyAsync(h_cnt + nxt, tr.cnt + nxt, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            O2V_CHECK(hipStreamSynchronize(s));
+            ++out->rounds, ++out->reads, out->visits += n;
+        }
+    } else {
+        do {
+            O2V_CHECK(hipMemsetAsync(tr.cnt + 2, 0, sizeof(uint32_t), s));
+            launch_sweep(tr.cnt + 2);
+            O2V_CHECK(hipMemcpyAsync(h_cnt + 2, tr.cnt + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            O2V_CHECK(hipStreamSynchronize(s));
+            ++out->rounds, ++out->reads;
+        } while (tr.h_cnt[2]);
+    }
+    return O2V_HIP_OK;
+}
+
 // weights: each 0 ... 65 535, not all 0
 int geo_weights(o2v_hip_ctx *ctx, const char *fn, const uint32_t weights[3])
 {
@@ -225,10 +277,7 @@ int o2v_hip_geodesic_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format, 
         return rc;
     uint32_t *const D = in_place ? reinterpret_cast<uint32_t *>(dist) : ctx->d_geo_dist.ptr;
     unsigned long long *const bits = ctx->d_geo_bits.ptr, *const ctr = ctx->d_geo_ctr.ptr;
-    uint32_t *const tile_flags[2] = {ctx->d_geo_tiles.ptr, ctx->d_geo_tiles.ptr + tiles};
-    uint32_t *const tile_list[2] = {ctx->d_geo_tiles.ptr + 2u * tiles, ctx->d_geo_tiles.ptr + 3u * tiles};
-    uint32_t *const cnt = reinterpret_cast<uint32_t *>(ctr + 2);                                   // the lists' lengths, the changed word
-    volatile uint32_t *const h_cnt = reinterpret_cast<volatile uint32_t *>(ctx->h_geo_ctr.ptr + 2);
+    const TileRounds tr = tile_rounds(ctx->d_geo_tiles.ptr, tiles, ctr + 2, ctx->h_geo_ctr.ptr + 2);
     const bool count = (flags & O2V_HIP_FLAG_STAGE_TIMES) != 0, use_tiles = !sw.geo_no_tiles;
     const dim3 per_word(stream_grid(ctx, g.words * 64u, 16u));
     hipStream_t s = ctx->stream;
@@ -237,40 +286,23 @@ int o2v_hip_geodesic_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format, 
     launch_classify(ctx, sg, (flags & O2V_HIP_CC_INVERT) ? 1u : 0u, bits);
     O2V_CHECK(ctx->geo_times.mark(1, s));
     O2V_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(D), (int) kGeoInf, voxels, s));
-    if (use_tiles) O2V_CHECK(hipMemsetAsync(tile_flags[0], 0, 2u * tiles * sizeof(uint32_t), s));
-    uint32_t *const fl0 = use_tiles ? tile_flags[0] : nullptr;
+    if (use_tiles) O2V_CHECK(hipMemsetAsync(tr.tile_flags[0], 0, 2u * tiles * sizeof(uint32_t), s));
+    uint32_t *const fl0 = use_tiles ? tr.tile_flags[0] : nullptr;
     if (n_seeds)
-        O2V_LAUNCH("k_geo_seed_list", s, k_geo_seed_list, dim3(stream_grid(ctx, n_seeds, 8u)), dim3(kBlock), 0, s, g, bits, seeds, n_seeds, D, fl0, tile_list[0], cnt);
-    if (flags & O2V_HIP_CC_SEED_BORDER) O2V_LAUNCH("k_geo_seed_border", s, k_geo_seed_border, per_word, dim3(kBlock), 0, s, g, bits, D, fl0, tile_list[0], cnt);
+        O2V_LAUNCH("k_geo_seed_list", s, k_geo_seed_list, dim3(stream_grid(ctx, n_seeds, 8u)), dim3(kBlock), 0, s, g, bits, seeds, n_seeds, D, fl0, tr.tile_list[0], tr.cnt);
+    if (flags & O2V_HIP_CC_SEED_BORDER) O2V_LAUNCH("k_geo_seed_border", s, k_geo_seed_border, per_word, dim3(kBlock), 0, s, g, bits, D, fl0, tr.tile_list[0], tr.cnt);
     O2V_CHECK(ctx->geo_times.mark(2, s));
-    // The rounds.  No cap: a round is launched only if the last one decreased a distance on a tile's rim (tiles) or anywhere
-    // (sweeps), and distances are whole numbers that only decrease.
-    uint64_t rounds = 0, visits = 0, reads = 0;
-    if (use_tiles) {
-        O2V_CHECK(hipMemcpyAsync(const_cast<uint32_t *>(h_cnt), cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        O2V_CHECK(hipStreamSynchronize(s));
-        ++reads;
-        for (uint32_t cur = 0, n = h_cnt[0]; n; cur ^= 1u, n = h_cnt[cur]) {
-            const uint32_t nxt = cur ^ 1u;
-            const dim3 blocks((uint32_t) std::min<uint64_t>(n, kCcMaxGrid));
-            O2V_CHECK(hipMemsetAsync(cnt + nxt, 0, sizeof(uint32_t), s));
+    RoundCounts done;
+    rc = run_tile_rounds(
+        ctx, tr, use_tiles,
+        [&](uint32_t cur, uint32_t nxt, uint32_t n, dim3 blocks) {
             with_flag(count, [&](auto counts) {
-                O2V_LAUNCH("k_geo_tiles", s, k_geo_tiles<decltype(counts)::value>, blocks, dim3(kBlock), 0, s, g, bits, D, tile_list[cur], n, tile_flags[cur],
-                           tile_flags[nxt], tile_list[nxt], cnt + nxt, ctr);
+                O2V_LAUNCH("k_geo_tiles", s, k_geo_tiles<decltype(counts)::value>, blocks, dim3(kBlock), 0, s, g, bits, D, tr.tile_list[cur], n, tr.tile_flags[cur],
+                           tr.tile_flags[nxt], tr.tile_list[nxt], tr.cnt + nxt, ctr);
             });
-            O2V_CHECK(hipMemcpyAsync(const_cast<uint32_t *>(h_cnt) + nxt, cnt + nxt, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            O2V_CHECK(hipStreamSynchronize(s));
-            ++rounds, ++reads, visits += n;
-        }
-    } else {
-        do {
-            O2V_CHECK(hipMemsetAsync(cnt + 2, 0, sizeof(uint32_t), s));
-            O2V_LAUNCH("k_geo_sweep", s, k_geo_sweep, per_word, dim3(kBlock), 0, s, g, bits, D, cnt + 2);
-            O2V_CHECK(hipMemcpyAsync(const_cast<uint32_t *>(h_cnt) + 2, cnt + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            O2V_CHECK(hipStreamSynchronize(s));
-            ++rounds, ++reads;
-        } while (h_cnt[2]);
-    }
+        },
+        [&](uint32_t *changed) { O2V_LAUNCH("k_geo_sweep", s, k_geo_sweep, per_word, dim3(kBlock), 0, s, g, bits, D, changed); }, &done);
+    if (rc) return rc;
     O2V_CHECK(ctx->geo_times.mark(3, s));
     O2V_LAUNCH("k_geo_write", s, k_geo_write, per_word, dim3(kBlock), 0, s, g, D, dist, dist_strides[0], dist_strides[1], dist_strides[2], ctr + 1);
     O2V_CHECK(hipGetLastError());
@@ -278,7 +310,7 @@ int o2v_hip_geodesic_dense(o2v_hip_ctx *ctx, const void *grid, uint32_t format, 
     O2V_CHECK(hipMemcpyAsync(ctx->h_geo_ctr.ptr, ctr, 2u * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     O2V_CHECK(hipStreamSynchronize(s));
     O2V_CHECK(ctx->geo_times.finish());
-    const uint64_t counters[4] = {rounds, visits, ctx->h_geo_ctr.ptr[0], reads};
+    const uint64_t counters[4] = {done.rounds, done.visits, ctx->h_geo_ctr.ptr[0], done.reads};
     for (int i = 0; i < 4; ++i) ctx->geo_counters[i] = count ? counters[i] : 0u;
     *out_reached = ctx->h_geo_ctr.ptr[1];
     return O2V_HIP_OK;

@@ -60,10 +60,7 @@ int o2v_hip_grow_dense(o2v_hip_ctx *ctx, const int32_t *relief, const uint64_t r
     uint32_t *const L = l_in_place ? reinterpret_cast<uint32_t *>(labels) : ctx->d_grow_l.ptr;
     uint32_t *const mask = ctx->d_grow_mask.ptr;
     unsigned long long *const ctr = ctx->d_grow_ctr.ptr;
-    uint32_t *const tile_flags[2] = {ctx->d_grow_tiles.ptr, ctx->d_grow_tiles.ptr + tiles};
-    uint32_t *const tile_list[2] = {ctx->d_grow_tiles.ptr + 2u * tiles, ctx->d_grow_tiles.ptr + 3u * tiles};
-    uint32_t *const cnt = reinterpret_cast<uint32_t *>(ctr + 4);
-    volatile uint32_t *const h_cnt = reinterpret_cast<volatile uint32_t *>(ctx->h_grow_ctr.ptr + 4);
+    const TileRounds tr = tile_rounds(ctx->d_grow_tiles.ptr, tiles, ctr + 4, ctx->h_grow_ctr.ptr + 4);
     const bool count = (flags & O2V_HIP_FLAG_STAGE_TIMES) != 0, use_tiles = !sw.grow_no_tiles;
     const dim3 per_word(stream_grid(ctx, g.words * 64u, 16u));
     hipStream_t s = ctx->stream;
@@ -71,58 +68,42 @@ int o2v_hip_grow_dense(o2v_hip_ctx *ctx, const int32_t *relief, const uint64_t r
 
     // What a phase's round 0 needs: both flag words clear, list 0 empty.  (A phase that has ended leaves them so; the first has not.)
     auto clear_lists = [&]() -> int {
-        O2V_CHECK(hipMemsetAsync(cnt, 0, 4u * sizeof(uint32_t), s));
-        if (use_tiles) O2V_CHECK(hipMemsetAsync(tile_flags[0], 0, 2u * tiles * sizeof(uint32_t), s));
+        O2V_CHECK(hipMemsetAsync(tr.cnt, 0, 4u * sizeof(uint32_t), s));
+        if (use_tiles) O2V_CHECK(hipMemsetAsync(tr.tile_flags[0], 0, 2u * tiles * sizeof(uint32_t), s));
         return O2V_HIP_OK;
     };
-    // The rounds of phase P on V.  No cap: a round is launched only if the last one moved a value on a tile's rim (tiles) or anywhere
-    // (sweeps), and the values of a phase are whole numbers that move one way between fixed bounds.
+    // the rounds of phase P on V
     auto run_rounds = [&](auto phase, uint32_t *V) -> int {
         constexpr int P = decltype(phase)::value;
-        uint64_t rounds = 0, visits = 0;
-        if (use_tiles) {
-            O2V_CHECK(hipMemcpyAsync(const_cast<uint32_t *>(h_cnt), cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            O2V_CHECK(hipStreamSynchronize(s));
-            for (uint32_t cur = 0, n = h_cnt[0]; n; cur ^= 1u, n = h_cnt[cur]) {
-                const uint32_t nxt = cur ^ 1u;
-                const dim3 blocks((uint32_t) std::min<uint64_t>(n, kCcMaxGrid));
-                O2V_CHECK(hipMemsetAsync(cnt + nxt, 0, sizeof(uint32_t), s));
+        RoundCounts done;
+        const int r = run_tile_rounds(
+            ctx, tr, use_tiles,
+            [&](uint32_t cur, uint32_t nxt, uint32_t n, dim3 blocks) {
                 with_flag(count, [&](auto counts) {
-                    O2V_LAUNCH("k_grow_tiles", s, (k_grow_tiles<P, decltype(counts)::value>), blocks, dim3(kBlock), 0, s, g, H, mask, V, tile_list[cur], n, tile_flags[cur],
-                               tile_flags[nxt], tile_list[nxt], cnt + nxt, ctr + P);
+                    O2V_LAUNCH("k_grow_tiles", s, (k_grow_tiles<P, decltype(counts)::value>), blocks, dim3(kBlock), 0, s, g, H, mask, V, tr.tile_list[cur], n,
+                               tr.tile_flags[cur], tr.tile_flags[nxt], tr.tile_list[nxt], tr.cnt + nxt, ctr + P);
                 });
-                O2V_CHECK(hipMemcpyAsync(const_cast<uint32_t *>(h_cnt) + nxt, cnt + nxt, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                O2V_CHECK(hipStreamSynchronize(s));
-                ++rounds, visits += n;
-            }
-        } else {
-            do {
-                O2V_CHECK(hipMemsetAsync(cnt + 2, 0, sizeof(uint32_t), s));
-                O2V_LAUNCH("k_grow_sweep", s, k_grow_sweep<P>, per_word, dim3(kBlock), 0, s, g, H, mask, V, cnt + 2);
-                O2V_CHECK(hipMemcpyAsync(const_cast<uint32_t *>(h_cnt) + 2, cnt + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                O2V_CHECK(hipStreamSynchronize(s));
-                ++rounds;
-            } while (h_cnt[2]);
-        }
-        counters[3 * P] = rounds, counters[3 * P + 1] = visits;
-        return O2V_HIP_OK;
+            },
+            [&](uint32_t *changed) { O2V_LAUNCH("k_grow_sweep", s, k_grow_sweep<P>, per_word, dim3(kBlock), 0, s, g, H, mask, V, changed); }, &done);
+        counters[3 * P] = done.rounds, counters[3 * P + 1] = done.visits;
+        return r;
     };
-    uint32_t *const fl0 = use_tiles ? tile_flags[0] : nullptr;
+    uint32_t *const fl0 = use_tiles ? tr.tile_flags[0] : nullptr;
 
     O2V_CHECK(ctx->grow_times.mark(0, s));   // init
     O2V_CHECK(hipMemsetAsync(ctr, 0, kGrowCtrWords * sizeof(unsigned long long), s));
     if ((rc = clear_lists())) return rc;
-    O2V_LAUNCH("k_grow_init", s, k_grow_init, per_word, dim3(kBlock), 0, s, g, H, M, Q, fl0, tile_list[0], cnt);
+    O2V_LAUNCH("k_grow_init", s, k_grow_init, per_word, dim3(kBlock), 0, s, g, H, M, Q, fl0, tr.tile_list[0], tr.cnt);
     O2V_CHECK(ctx->grow_times.mark(1, s));   // level rounds
     if ((rc = run_rounds(std::integral_constant<int, 0>{}, Q))) return rc;
     O2V_CHECK(ctx->grow_times.mark(2, s));   // sources
     if ((rc = clear_lists())) return rc;
-    O2V_LAUNCH("k_grow_between", s, k_grow_between<false>, per_word, dim3(kBlock), 0, s, g, H, M, Q, T, L, mask, fl0, tile_list[0], cnt);
+    O2V_LAUNCH("k_grow_between", s, k_grow_between<false>, per_word, dim3(kBlock), 0, s, g, H, M, Q, T, L, mask, fl0, tr.tile_list[0], tr.cnt);
     O2V_CHECK(ctx->grow_times.mark(3, s));   // tick rounds
     if ((rc = run_rounds(std::integral_constant<int, 1>{}, T))) return rc;
     O2V_CHECK(ctx->grow_times.mark(4, s));   // tight
     if ((rc = clear_lists())) return rc;
-    O2V_LAUNCH("k_grow_between", s, k_grow_between<true>, per_word, dim3(kBlock), 0, s, g, H, M, Q, T, L, mask, fl0, tile_list[0], cnt);
+    O2V_LAUNCH("k_grow_between", s, k_grow_between<true>, per_word, dim3(kBlock), 0, s, g, H, M, Q, T, L, mask, fl0, tr.tile_list[0], tr.cnt);
     O2V_CHECK(ctx->grow_times.mark(5, s));   // label rounds
     if ((rc = run_rounds(std::integral_constant<int, 2>{}, L))) return rc;
     O2V_CHECK(ctx->grow_times.mark(6, s));   // write

@@ -193,6 +193,15 @@ __global__ __launch_bounds__(kBlock) void k_geo_seed_list(GeoGrid g, const unsig
     }
 }
 
+// The seeds of one word - a row of tile (tx, ty, tz) -, each lane with the see mask of its own (0: no seed): the masks or-ed over
+// the wavefront, lane 0 wakes the tiles.
+__device__ __forceinline__ void geo_wake_row(const GeoGrid &g, uint32_t tx, uint32_t ty, uint32_t tz, uint32_t see, uint32_t *flags, uint32_t *list,
+                                             uint32_t *count)
+{
+    for (int d = 32; d >= 1; d >>= 1) see |= __shfl_xor(see, d);
+    if ((threadIdx.x & 63u) == 0u) geo_flag_seed(g, tx, ty, tz, see, flags, list, count);
+}
+
 // O2V_HIP_CC_SEED_BORDER: D = 0 at the voxels of S on the six faces of the box
 __global__ __launch_bounds__(kBlock) void k_geo_seed_border(GeoGrid g, const unsigned long long *__restrict__ bits, uint32_t *D, uint32_t *flags,
                                                             uint32_t *list, uint32_t *count)
@@ -204,9 +213,7 @@ __global__ __launch_bounds__(kBlock) void k_geo_seed_border(GeoGrid g, const uns
         const bool seed = bits_on_face(g, x, y, z) && x < g.nx && ((bits[wi] >> lane) & 1ull);
         if (seed) D[(z * g.ny + y) * g.nx + x] = 0u;
         if (__ballot(seed) == 0ull || !flags) continue;
-        uint32_t see = seed ? geo_see_mask(lane, y & 7u, z & 7u, g.w) : 0u;   // (the word is one row of one tile)
-        for (int d = 32; d >= 1; d >>= 1) see |= __shfl_xor(see, d);
-        if (lane == 0u) geo_flag_seed(g, wx, y >> 3, z >> 3, see, flags, list, count);
+        geo_wake_row(g, wx, y >> 3, z >> 3, seed ? geo_see_mask(lane, y & 7u, z & 7u, g.w) : 0u, flags, list, count);   // (the word is one row of one tile)
     }
 }
 

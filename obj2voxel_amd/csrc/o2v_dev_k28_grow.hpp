@@ -232,9 +232,7 @@ __global__ __launch_bounds__(kBlock) void k_grow_init(GeoGrid g, I32View H, I32V
             Q[((uint64_t) z * g.ny + y) * g.nx + x] = seed ? (uint32_t) h : 0u;
         }
         if (__ballot(seed) == 0ull || !flags) continue;
-        uint32_t see = seed ? geo_see_mask(lane, y & 7u, z & 7u, g.w) : 0u;
-        for (int d = 32; d >= 1; d >>= 1) see |= __shfl_xor(see, d);
-        if (lane == 0u) geo_flag_seed(g, at.wx, y >> 3, z >> 3, see, flags, list, count);
+        geo_wake_row(g, at.wx, y >> 3, z >> 3, seed ? geo_see_mask(lane, y & 7u, z & 7u, g.w) : 0u, flags, list, count);
     }
 }
 

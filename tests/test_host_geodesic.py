@@ -654,6 +654,7 @@ def test_k20_kernels_in_the_code_object(device_asm, kernel):  # noqa: F811
     atomics = set(re.findall(r"^\s*(\S*atomic\S*)", body, re.M))
     if "k_geo_tiles" in kernel:
         assert lds == TILE_LDS and 6 * lds <= 160 * 1024 < 7 * lds        # six workgroups in a CU's LDS
+        assert int(re.search(r"\.vgpr_count: +(\d+)", entry[0]).group(1)) <= 80   # ... and six waves a SIMD: registers come in eights, 88 - 96 give five
         assert "ds_read" in body and "global_atomic_swap" in atomics       # the relaxation reads LDS; the flag is an exchange
         assert not any("min" in a for a in atomics), atomics               # no atomic min: a voxel has one writer
     elif kernel == "k_geo_sweepE":
